@@ -28,6 +28,7 @@ kernel on the launch stream (bfgx_plan_timing_*) for `kernel_ms` and `roofline` 
 `ms_per_step_with_kernel_events` shows what the events cost).  At N = 1 the line also carries `value_acc_f64` (the same
 step in fp64 throughout), `end_to_end` (the drop-in BaryonifyShell.process() from numpy arrays, PCIe-inclusive) and
 `cpu_baseline` (the CPU oracle -- oracle/, the checker, never the product -- on the box's host cores).
+--dump-outputs DIR writes what the last timed step computed (the map, the mass sums; grid modes: the map and P(k)) as DIR/*.npy.
 Diagnostics (stderr, never in `value`): BFGX_BENCH_STAGE_TIMES=1 adds one untimed, stage-by-stage synchronised step of the N > 1 path and
 prints its stage times; BFGX_BENCH_ENQUEUE_TIME=1 prints how much of a step is host-side enqueue time.
 """
@@ -49,6 +50,9 @@ DTYPES = {0: "f64 ring-row geometry + f64 LDS accumulation / map; f32 pair math,
           1: "f64 throughout (fp64 pair math, fp64 pix_offsets, fp64 regrid): the reference's own arithmetic",
           3: "f64 throughout in the parity-grade mode: f64 ring-row geometry, f64 pair math with 1e-11 elementary functions (fp32 seeds + one Newton step), "
              "f64 LDS accumulation, pix_offsets stored as two f32 arrays (hi + lo), f64 regrid geometry, f64 map"}
+# --dump-outputs: larger outputs are written as a sample of this many seeded flat indices (2 x 16 MB at most per output)
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 20250105
 
 
 def parse():
@@ -103,7 +107,33 @@ def parse():
     ap.add_argument('--no-kernel-events', action='store_true', help='do not bracket the kernels with HIP events in the timed region (no roofline object)')
     ap.add_argument('--cpu-sample', type=int, default=100_000, help='halos in the CPU-oracle sample (single-thread baseline)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='threads of the CPU baseline (0 = all available cores, at most 16)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, < 64 MB in all; a map "
+                         "larger than %d elements as a fixed, seeded sample: <name>_sample.npy + its flat indices <name>_index.npy); the inputs "
+                         "are seeded, so two builds run with the same arguments can be compared output for output" % DUMP_SAMPLE)
     return ap.parse_args()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write `arrays` (name -> torch tensor or numpy array) as path/<name>.npy in float64.  A tensor of more than
+    DUMP_SAMPLE elements is sampled on the device at DUMP_SAMPLE seeded flat indices (drawn with replacement, unique, sorted: the
+    same indices for the same size in every run), written as <name>_sample.npy with the indices as <name>_index.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        for stale in (name, name + '_sample', name + '_index'):         # (a run of another size may have written the other form)
+            if os.path.exists(os.path.join(path, stale + '.npy')):
+                os.remove(os.path.join(path, stale + '.npy'))
+        if torch.is_tensor(a):
+            flat = a.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+                picked = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+                np.save(os.path.join(path, name + '_sample.npy'), picked.cpu().numpy().astype(np.float64))
+                np.save(os.path.join(path, name + '_index.npy'), idx.astype(np.float64))
+                continue
+            a = flat.cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(args, cat, hmap, axes, table):
@@ -206,6 +236,10 @@ def main_grid_slabs(args):
         out = GS.slab_step(be, rows, cat_dev, N, L, Nk)
     fence()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:
+        # the last timed step (before the stage-timer pass below reuses the buffers): rank 0's slab of the new map, the binned P(k), the
+        # two sums over all ranks
+        dump_outputs(args.dump_outputs, dict(zip(('slab0', 'k', 'pk', 'counts', 'sums'), out)))
     stages = {}
     GS.slab_step(be, rows, cat_dev, N, L, Nk, timers=stages)     # one more pass with synchronising stage timers (not in `value`)
     el = torch.tensor([t1 - t0], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
@@ -368,6 +402,13 @@ def main_grid(args):
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     ev_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in lst])) for k, lst in ev.items() if lst}      # (the timed region's events)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's map (BaryonifyGrid's map_out; snapshot: the displaced particles deposited) and its binned P(k)
+        dump = {'map': d_out, 'k': d_ks / d_cnt, 'pk': d_pk / d_cnt, 'counts': d_cnt}
+        if not snapshot:
+            dump['sums'] = d_sums
+        dump_outputs(args.dump_outputs, dump)
+        del dump
     sorted_companion = None
     if snapshot and not args.sorted_particles and not args.no_extras:
         # the same flow on the same particles in the order snapshot files stored along a space-filling curve have (raster order of 64^3
@@ -965,6 +1006,17 @@ def shell_line(args, ctx, scaling, brief):
         step()
     # the timed region proper: EXACTLY --steps passes, no per-kernel events (they cost ~0.05 ms per step); `value` comes from it
     elapsed, _ = timed(step, args.steps, False)
+    if args.dump_outputs and not brief:
+        # what the last timed step left for the caller: the map assembled on rank 0 (and, displacing, the two mass sums over all ranks)
+        dump = {'map': (ov['fin'][ov['last']] if spatial else d_fin) if (slices or spatial) else d_out}
+        if not paint:
+            tot = d_sums.clone() if backend == 'nccl' or not dist.is_initialized() else d_sums.cpu()
+            if (slices or spatial) and dist.is_initialized():
+                dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+            dump['sums'] = tot
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dump)
+        del dump
     # the same K steps again with HIP events around every kernel on the launch stream (bfgx_plan_timing_*): kernel_ms, roofline
     elapsed_ev, kt = timed(step, args.steps, True) if not (args.no_kernel_events or brief) else (None, None)
     if spatial and os.environ.get('BFGX_BENCH_STAGE_TIMES') == '1':

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -125,3 +126,33 @@ def test_forced_single_rank_exchange_over_rccl_with_the_overlapped_gather(gpu):
     d = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith('{')][0])
     assert d['backend'] == 'nccl' and d['world_size_seen'] == 1 and d['gather_overlapped'] is True and d['mass_conserved'] is True
     assert d['check']['ok'] is True and 'asynchronous' in d['step_launches'][-1]
+
+
+def _dump(tmp, *args):
+    d = _run(*args, '--dump-outputs', str(tmp))
+    return d, {f[:-4]: np.load(os.path.join(tmp, f)) for f in sorted(os.listdir(tmp))}
+
+
+def test_dump_outputs_repeatable(gpu, tmp_path):
+    """--dump-outputs DIR: the last timed step's map and mass sums as float64 .npy files, the same from run to run with the same arguments
+    (seeded inputs); a map larger than bench.DUMP_SAMPLE pixels is written as a seeded sample with its flat indices, < 64 MB in all"""
+    import bench
+    small = ('--halos', '20000', '--nside', '128', '--steps', '3', '--warmup', '1', '--no-extras', '--no-cpu-baseline')
+    d1, a = _dump(tmp_path / 'a', *small)
+    d2, b = _dump(tmp_path / 'b', *small)
+    assert d1['steps'] == d2['steps'] == 3 and d1['ms_per_step'] > 0
+    assert set(a) == set(b) == {'map', 'sums'} and all(v.dtype == np.float64 for v in a.values())
+    assert a['map'].shape == (12 * 128 ** 2,) and a['sums'].shape == (2,)
+    assert np.isclose(a['map'].sum(), a['sums'][1]) and np.isclose(a['sums'][1], a['sums'][0])
+    scale = np.abs(a['map']).max()
+    assert np.abs(a['map'] - b['map']).max() <= 1e-12 * scale and np.allclose(a['sums'], b['sums'], rtol=1e-12, atol=0)
+    # a shell of 12 * 512^2 > DUMP_SAMPLE pixels: sampled
+    d3, c = _dump(tmp_path / 'c', '--halos', '20000', '--nside', '512', '--steps', '2', '--warmup', '1', '--no-extras', '--no-cpu-baseline')
+    assert set(c) == {'map_sample', 'map_index', 'sums'} and c['map_sample'].shape == c['map_index'].shape
+    idx = c['map_index'].astype(np.int64)
+    assert np.array_equal(idx, c['map_index']) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 12 * 512 ** 2
+    assert c['map_index'].size <= bench.DUMP_SAMPLE and np.all(np.isfinite(c['map_sample']))
+    assert sum(os.path.getsize(os.path.join(tmp_path / 'c', f)) for f in os.listdir(tmp_path / 'c')) < 64 << 20
+    # the grid path: BaryonifyGrid's map, P(k) and the sums
+    d4, g = _dump(tmp_path / 'g', '--mode', 'grid3d', '--ngrid', '64', '--grid-halos', '500', '--steps', '2', '--warmup', '1', '--no-cpu-baseline')
+    assert set(g) == {'map', 'k', 'pk', 'counts', 'sums'} and g['map'].shape == (64 ** 3,) and np.isclose(g['map'].sum(), g['sums'][1])
