@@ -6,6 +6,12 @@ exceptions.  `process()` does no per-halo work in Python except the 2x2 shear ma
 catalog, map and the model's raw table go through the C ABI (include/bfgx.h, "regular-grid path") to the HIP kernels
 in csrc/bfgx_grid.hpp.  There is no CPU fallback.
 
+A model that is a plain Python callable (displacement(r, M, a) / projected or real(cosmo, r, M, a), no table) is tabulated once
+(with a RuntimeWarning) unless it sets `bfgx_exact = True`: then it is called once per halo on r_grid.flatten() of the halo's whole
+cutout, with M = cat['M'][j] and a = 1/(1+z), as the reference's loop does (:534, :577, :801).  The device makes the cutouts' radii
+and applies the values (bfgx_grid_pairs_*, csrc/bfgx_grid_pairs.hpp); the host holds one batch of them at a time
+(_model.EXACT_BATCH_PAIRS).
+
 Not built: `PaintProfilesAnisGrid` (:820-942).
 """
 import ctypes as C
@@ -15,7 +21,7 @@ import numpy as np
 from .. import _lib
 from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
-from ._model import build_model
+from ._model import build_model, process_grid_exact, wants_exact
 
 __all__ = ['DefaultRunnerGrid', 'BaryonifyGrid', 'PaintProfilesGrid', 'regrid_pixels_2D', 'regrid_pixels_3D']
 
@@ -151,6 +157,8 @@ class BaryonifyGrid(DefaultRunnerGrid):
             if not self.GriddedMap.is2D:
                 raise NotImplementedError("Currently not able to ellipticities with 3D maps.")    # :559
             rmat = self._rmats("not positive")
+        if wants_exact(self, 'displacement'):            # a plain-Python model with bfgx_exact = True: called per halo, as the reference does
+            return process_grid_exact(self, 'displacement', rmat)
         model, p_keys, keep = build_model(self, 'displacement', self._runner_cosmo())
         cat, cols = self._catalog(p_keys, rmat)
         grid, gkeep = self._grid()
@@ -179,7 +187,10 @@ class PaintProfilesGrid(DefaultRunnerGrid):
             if not self.GriddedMap.is2D:
                 raise ValueError("use_ellipticity is not implemented for 3D maps")                # :784
             rmat = self._rmats("zero")
-        model, p_keys, keep = build_model(self, 'projected' if self.GriddedMap.is2D else 'real', self._runner_cosmo())
+        kind = 'projected' if self.GriddedMap.is2D else 'real'
+        if wants_exact(self, kind):
+            return process_grid_exact(self, kind, rmat)
+        model, p_keys, keep = build_model(self, kind, self._runner_cosmo())
         cat, cols = self._catalog(p_keys, rmat)
         grid, gkeep = self._grid()
         new_map = _lib.pinned_empty(int(np.prod(self.GriddedMap.map.shape))).reshape(self.GriddedMap.map.shape)

@@ -4,6 +4,11 @@ Particle-snapshot runner: drop-in for BaryonForge/Runners/SnapshotRunner.py (`De
 structured array with displaced, periodically re-wrapped x, y(, z).  No KD-tree is built: the HIP path bins the halos
 into a periodic cell grid and gathers per particle (csrc/bfgx_snapshot.hpp); `KDTree_kwargs` is accepted and ignored,
 `tree` is None.  There is no CPU fallback.
+
+A model that is a plain Python callable (displacement(r, M, a), no table) is tabulated once (with a RuntimeWarning) unless it sets
+`bfgx_exact = True`: then it is called once per halo, every halo, on the distances of the particles within R_q (ascending particle
+index within a halo), with M = cat['M'][j] and a = 1/(1+z), as the reference's loop does (:228, :245; bfgx_snapshot_pairs_*,
+csrc/bfgx_snapshot_pairs.hpp).
 """
 import ctypes as C
 
@@ -11,7 +16,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils.cosmology import MassDef
-from ._model import build_model
+from ._model import build_model, process_snapshot_exact, wants_exact
 
 __all__ = ['DefaultRunnerSnapshot', 'BaryonifySnapshot']
 
@@ -68,6 +73,8 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
         once, the displaced coordinates exist only as the deposit's sort keys, the map comes back.  Not in the reference's API; the result
         equals the two calls (cell for cell with unit masses, to the order of the sums inside a cell otherwise).  Snapshots whose `cat` is
         not one C-contiguous structured array of float64 fields take the two calls."""
+        if wants_exact(self, 'displacement'):            # a plain-Python model with bfgx_exact = True: the two calls
+            return self._map_of(self.process(), N_grid)
         snap, is2D, model, keep, cat, cols = self._setup()
         rec = snap.cat
         fields = rec.dtype.fields or {}
@@ -91,13 +98,19 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
                 self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
                 del keep, cols
                 return out
+        return self._map_of(self.process(), N_grid)
+
+    def _map_of(self, new_cat, N_grid):
+        """ParticleSnapshot(cat=new_cat, ...).make_map(N_grid) with the snapshot's other attributes"""
         from ..utils.io import ParticleSnapshot
         new = ParticleSnapshot.__new__(ParticleSnapshot)
-        new.__dict__.update(snap.__dict__)
-        new.cat = self.process()
+        new.__dict__.update(self.ParticleSnapshot.__dict__)
+        new.cat = new_cat
         return new.make_map(N_grid)
 
     def process(self):
+        if wants_exact(self, 'displacement'):            # a plain-Python model with bfgx_exact = True: called per halo (:228, :245)
+            return process_snapshot_exact(self)
         snap, is2D, model, keep, cat, cols = self._setup()
         opts = _lib.bfgx_opts(int(self.device), 1, 1, 0, 1, 0)
         stats = _lib.bfgx_stats()

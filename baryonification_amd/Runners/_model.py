@@ -160,12 +160,28 @@ def plain_callable(model, kind):
 
 
 def wants_exact(runner, kind):
-    """the per-halo route for a plain callable: model.bfgx_exact = True / False, default by the size of the catalog (the route makes one
-    Python call per halo, as the reference's loop does: HealpixRunner.py:321, :441)"""
+    """the per-halo route for a plain callable (one Python call per halo, as the reference's loop makes: HealpixRunner.py:321, :441;
+    Map2DRunner.py:534, :577, :801; SnapshotRunner.py:228, :245).  Shell runners: model.bfgx_exact = True / False, default by the size of
+    the catalog.  Grid and snapshot runners: only with model.bfgx_exact = True; they tabulate by default."""
     if not plain_callable(runner.model, kind):
         return False
     flag = getattr(runner.model, 'bfgx_exact', None)
-    return runner.HaloLightConeCatalog.cat.size <= EXACT_MAX_HALOS if flag is None else bool(flag)
+    if hasattr(runner, 'HaloLightConeCatalog'):
+        return runner.HaloLightConeCatalog.cat.size <= EXACT_MAX_HALOS if flag is None else bool(flag)
+    return flag is True
+
+
+def _placeholder_model(runner, cosmo_dict):
+    """the bfgx_model of the per-halo routes: the runner's side of the geometry only (cosmology, mass definition, epsilon_max); the table is
+    a placeholder nobody reads.  Returns (bfgx_model, keepalive)."""
+    table, keep = _lib.make_table([np.array([0.0, 1.0])] * 3, np.zeros((2, 2, 2)), False, False, 0.0)
+    m = _lib.bfgx_model()
+    m.table = table
+    m.cosmo_runner = m.cosmo_model = _lib.make_cosmo(cosmo_dict)
+    D, rho = massdef_to_tuple(runner.mass_def)
+    m.massdef_runner = m.massdef_model = _lib.make_massdef(D, rho)
+    m.eps_runner = float(runner.epsilon_max)
+    return m, keep
 
 
 def process_callable_exact(runner, kind, orig_map=None):
@@ -179,14 +195,7 @@ def process_callable_exact(runner, kind, orig_map=None):
     model = runner.model
     cat = runner.HaloLightConeCatalog.cat
     paint = kind != 'displacement'
-    # the runner's side of the geometry only (cosmology, mass definition, epsilon_max); the table is a placeholder nobody reads
-    table, keep = _lib.make_table([np.array([0.0, 1.0])] * 3, np.zeros((2, 2, 2)), False, False, 0.0)
-    m = _lib.bfgx_model()
-    m.table = table
-    m.cosmo_runner = m.cosmo_model = _lib.make_cosmo(cosmo_to_dict(runner.cosmo))
-    D, rho = massdef_to_tuple(runner.mass_def)
-    m.massdef_runner = m.massdef_model = _lib.make_massdef(D, rho)
-    m.eps_runner = float(runner.epsilon_max)
+    m, keep = _placeholder_model(runner, cosmo_to_dict(runner.cosmo))
     cols = [_lib.f8(cat[k]) for k in ('M', 'z', 'ra', 'dec')]
     c, ckeep = _lib.make_catalog_host(cols[0], cols[1], cols[2], cols[3], [])
     nside = int(runner.LightconeShell.NSIDE)
@@ -220,6 +229,130 @@ def process_callable_exact(runner, kind, orig_map=None):
     runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
     del keep, ckeep
     return new_map
+
+
+EXACT_BATCH_PAIRS = 1 << 25     # the grid route's host batch: radii and values of at most this many (halo, pixel) pairs (one halo above it: alone)
+
+
+def _halo_batches(off, budget):
+    """halo ranges [j0, j1) whose pairs (off = exclusive prefix sum of the counts) fit `budget`; a halo larger than that is a batch of its own"""
+    n, j0 = off.size - 1, 0
+    while j0 < n:
+        j1 = max(int(np.searchsorted(off, off[j0] + budget, side='right')) - 1, j0 + 1)
+        yield j0, min(j1, n)
+        j0 = min(j1, n)
+
+
+def process_grid_exact(runner, kind, rmat=None):
+    """BaryonifyGrid / PaintProfilesGrid .process() for a plain-callable model with model.bfgx_exact = True, evaluated as the reference does:
+    once per halo on r_grid.flatten() of the halo's whole cutout (Map2DRunner.py:476-607, :667-817).  The device finds the cutouts and their
+    radii (bfgx_grid_pairs_begin / _radii), this loop calls the model with the reference's arguments -- M_j = cat['M'][j] (a float32 scalar),
+    a_j = 1 / (1 + redshift), r a float64 array; PaintProfilesGrid also the package Cosmology of the runner's dict -- and the device turns
+    the values into pixel offsets and regrids, or paints (bfgx_grid_pairs_apply / _finish).  At most EXACT_BATCH_PAIRS pairs are on the host
+    at a time.  No table, hence no interpolation error."""
+    import ctypes as C
+    from ..utils.cosmology import Cosmology
+    model = runner.model
+    paint = kind != 'displacement'
+    cosmo_dict = runner._runner_cosmo()
+    m, keep = _placeholder_model(runner, cosmo_dict)
+    hcat = runner.HaloNDCatalog.cat
+    G = runner.GriddedMap
+    c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if G.is2D else hcat['z'], None, rmat)
+    grid, gkeep = runner._grid()
+    lib = _lib.load()
+    h = C.c_void_p()
+    n = hcat.size
+    counts = np.zeros(max(n, 1), dtype=np.int64)
+    _lib.check(lib.bfgx_grid_pairs_begin(C.byref(c), C.byref(m), C.byref(grid), int(paint), int(runner.device), C.byref(h), counts.ctypes.data))
+    try:
+        off = np.concatenate([[0], np.cumsum(counts[:n])]).astype(np.int64)
+        Mcol = hcat['M']
+        a_j = 1 / (1 + runner.HaloNDCatalog.redshift)                                   # :485, :717
+        if paint:
+            profile = model.projected if G.is2D else model.real                        # :752, :781
+            cosmo_obj = Cosmology.from_dict(cosmo_dict)
+        for j0, j1 in _halo_batches(off, int(EXACT_BATCH_PAIRS)):
+            base, npairs = int(off[j0]), int(off[j1] - off[j0])
+            r = np.empty(max(npairs, 1))
+            _lib.check(lib.bfgx_grid_pairs_radii(h, j0, j1, r.ctypes.data))
+            vals = np.empty_like(r)
+            for j in range(j0, j1):
+                lo, hi = int(off[j]) - base, int(off[j + 1]) - base
+                if hi == lo and not paint:                                              # Nsize < 2: skipped (:498)
+                    continue
+                rj = r[lo:hi]
+                v = profile(cosmo_obj, rj, Mcol[j], a_j) if paint else model.displacement(rj, Mcol[j], a_j)
+                if hi > lo:                         # (PaintProfilesGrid calls every halo; one with an invalid mass or position has no pixels)
+                    vals[lo:hi] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (hi - lo,))
+            _lib.check(lib.bfgx_grid_pairs_apply(h, j0, j1, vals.ctypes.data))
+            del r, vals
+        new_map = _lib.pinned_empty(int(np.prod(G.map.shape))).reshape(G.map.shape)
+        src = None if paint else _lib.f8(G.map)
+        stats = _lib.bfgx_stats()
+        _lib.check(lib.bfgx_grid_pairs_finish(h, None if paint else src.ctypes.data, new_map.ctypes.data, 1, C.byref(stats)))
+    finally:
+        lib.bfgx_grid_pairs_end(h)
+    runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
+    del keep, ckeep, gkeep
+    return new_map
+
+
+def process_snapshot_exact(runner):
+    """BaryonifySnapshot.process() for a plain-callable model with model.bfgx_exact = True, evaluated as the reference does: once per halo
+    (every halo, an empty array when no particle is inside) on the distances of the particles within R_q (SnapshotRunner.py:217-245), with
+    M_j = cat['M'][j] (a float32 scalar) and a_j = 1 / (1 + redshift).  Within a halo the particles come in ascending index (the reference's
+    KD-tree order is unspecified).  The device finds the pairs and their distances (bfgx_snapshot_pairs_begin / _radii), accumulates
+    value * a_j along the unit vectors and re-wraps the positions once (_apply / _finish).  Returns the new structured array."""
+    import ctypes as C
+    model = runner.model
+    if vars(model).get('p_keys', []):
+        raise NotImplementedError("BaryonifySnapshot passes no halo properties to the model (SnapshotRunner.py:240)")
+    snap = runner.ParticleSnapshot
+    is2D = snap.is2D
+    cosmo = dict(runner.cosmo)
+    cosmo['w0'] = -1.0                                                    # SnapshotRunner.py:204-207 does not pass w0
+    m, keep = _placeholder_model(runner, cosmo_to_dict(cosmo))
+    hcat = runner.HaloNDCatalog.cat
+    c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if is2D else hcat['z'])
+    x, y = _lib.f8(snap.cat['x']), _lib.f8(snap.cat['y'])
+    z = None if is2D else _lib.f8(snap.cat['z'])
+    s = _lib.bfgx_snapshot(2 if is2D else 3, 0, x.size, x.ctypes.data, y.ctypes.data, None if is2D else z.ctypes.data,
+                           float(snap.L), float(runner.HaloNDCatalog.redshift))
+    lib = _lib.load()
+    h = C.c_void_p()
+    n = hcat.size
+    counts = np.zeros(max(n, 1), dtype=np.int64)
+    _lib.check(lib.bfgx_snapshot_pairs_begin(C.byref(c), C.byref(m), C.byref(s), int(runner.device), C.byref(h), counts.ctypes.data))
+    try:
+        off = np.concatenate([[0], np.cumsum(counts[:n])]).astype(np.int64)
+        Mcol = hcat['M']
+        a_j = 1 / (1 + runner.HaloNDCatalog.redshift)                                   # :219
+        for j0, j1 in _halo_batches(off, int(EXACT_BATCH_PAIRS)):
+            base, npairs = int(off[j0]), int(off[j1] - off[j0])
+            d = np.empty(max(npairs, 1))
+            _lib.check(lib.bfgx_snapshot_pairs_radii(h, j0, j1, d.ctypes.data))
+            vals = np.empty_like(d)
+            for j in range(j0, j1):
+                lo, hi = int(off[j]) - base, int(off[j + 1]) - base
+                v = model.displacement(d[lo:hi], Mcol[j], a_j)                          # :228, :245 (every halo)
+                if hi > lo:
+                    vals[lo:hi] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (hi - lo,))
+            _lib.check(lib.bfgx_snapshot_pairs_apply(h, j0, j1, vals.ctypes.data))
+            del d, vals
+        ox, oy = np.empty_like(x), np.empty_like(y)
+        oz = None if is2D else np.empty_like(z)
+        stats = _lib.bfgx_stats()
+        _lib.check(lib.bfgx_snapshot_pairs_finish(h, ox.ctypes.data, oy.ctypes.data, None if is2D else oz.ctypes.data, C.byref(stats)))
+    finally:
+        lib.bfgx_snapshot_pairs_end(h)
+    runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
+    new_cat = snap.cat.copy()
+    new_cat['x'], new_cat['y'] = ox, oy
+    if not is2D:
+        new_cat['z'] = oz
+    del keep, ckeep
+    return new_cat
 
 
 def build_model(runner, kind, runner_cosmo=None):

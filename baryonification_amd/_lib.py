@@ -184,6 +184,16 @@ SYMBOLS = {
     'bfgx_shell_pairs_radii': (C.c_int, [C.c_void_p, C.c_void_p]),
     'bfgx_shell_pairs_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(bfgx_stats)]),
     'bfgx_shell_pairs_end': (None, [C.c_void_p]),
+    'bfgx_grid_pairs_begin': (C.c_int, [_P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_grid), C.c_int32, C.c_int32, _P(C.c_void_p), C.c_void_p]),
+    'bfgx_grid_pairs_radii': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'bfgx_grid_pairs_apply': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'bfgx_grid_pairs_finish': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(bfgx_stats)]),
+    'bfgx_grid_pairs_end': (None, [C.c_void_p]),
+    'bfgx_snapshot_pairs_begin': (C.c_int, [_P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_snapshot), C.c_int32, _P(C.c_void_p), C.c_void_p]),
+    'bfgx_snapshot_pairs_radii': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'bfgx_snapshot_pairs_apply': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'bfgx_snapshot_pairs_finish': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(bfgx_stats)]),
+    'bfgx_snapshot_pairs_end': (None, [C.c_void_p]),
     'bfgx_baryonify_snapshot_records_map': (C.c_int, [_P(bfgx_grid_catalog), _P(bfgx_model), C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_void_p,
                                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                       _P(bfgx_opts), _P(bfgx_stats)]),

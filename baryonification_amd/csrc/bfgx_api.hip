@@ -39,9 +39,11 @@ template <typename T> static inline hipError_t bfgx_counted_malloc(T **p, size_t
 #endif
 #include "bfgx_tables.hpp"
 #include "bfgx_grid.hpp"
+#include "bfgx_grid_pairs.hpp"
 #include "bfgx_fft.hpp"
 #include "bfgx_deposit.hpp"
 #include "bfgx_snapshot.hpp"
+#include "bfgx_snapshot_pairs.hpp"
 #include "bfgx_grid_gather.hpp"
 #include "bfgx_fftlog.hpp"
 
@@ -2409,3 +2411,5 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // ------------------------------------------------------------------------------ models that are Python callables
 #include "bfgx_callable_api.inc"
+#include "bfgx_grid_pairs_api.inc"
+#include "bfgx_snapshot_pairs_api.inc"

@@ -14,7 +14,21 @@ struct bfgx_pairs {
     int paint = 0;
     DevBuf off, vals, counts;
     PoolBuf acc, in, out, sums;
-    ~bfgx_pairs() { for (PoolBuf *b : {&acc, &in, &out, &sums}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } }
+    // the regular-grid runners' handle (bfgx_grid_pairs_*, bfgx_grid_pairs_api.inc): plan == nullptr, gplan != nullptr
+    bfgx_grid_plan *gplan = nullptr;
+    GridHostCatalog gcat;
+    DevBuf item0, item_halo;
+    PoolBuf batch;
+    std::vector<int64_t> off_h, item0_h;
+    // BaryonifySnapshot's handle (bfgx_snapshot_pairs_*, bfgx_snapshot_pairs_api.inc): sdev >= 0
+    int sdev = -1;
+    hipStream_t sstream = nullptr;
+    SnapGeom sg;
+    DevModel smodel;
+    std::vector<void *> sowned;
+    int64_t snp = 0;
+    DevBuf sxyz[3], srecs, skeys, sacc;
+    ~bfgx_pairs() { for (PoolBuf *b : {&acc, &in, &out, &sums, &batch}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } }
 };
 
 extern "C" {
@@ -23,9 +37,18 @@ void bfgx_shell_pairs_end(bfgx_pairs *h)
 {
     if (!h) return;
     if (h->plan) { (void)hipSetDevice(h->plan->device); (void)hipStreamSynchronize(h->plan->stream); }
+    if (h->gplan) { (void)hipSetDevice(h->gplan->device); (void)hipStreamSynchronize(h->gplan->stream); }
+    if (h->sdev >= 0) { (void)hipSetDevice(h->sdev); (void)hipStreamSynchronize(h->sstream); }
     bfgx_plan *p = h->plan;
+    bfgx_grid_plan *gp = h->gplan;
+    hipStream_t ss = h->sstream;
+    std::vector<void *> sowned;
+    sowned.swap(h->sowned);
     delete h;                       // (device buffers first: they were allocated on the plan's device)
     if (p) bfgx_plan_destroy(p);
+    if (gp) bfgx_grid_plan_destroy(gp);
+    for (void *d : sowned) (void)hipFree(d);
+    if (ss) (void)hipStreamDestroy(ss);
 }
 
 int bfgx_shell_pairs_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, int32_t paint, int32_t device, bfgx_pairs **out,

@@ -567,6 +567,45 @@ int  bfgx_shell_pairs_radii(bfgx_pairs *h, double *r_host);
 int  bfgx_shell_pairs_apply(bfgx_pairs *h, const double *vals_host, const double *map_in, double *map_out, int32_t check_mass, bfgx_stats *stats);
 void bfgx_shell_pairs_end(bfgx_pairs *h);
 
+/* The regular-grid runners serve such a model the same way, through a bfgx_pairs handle of their own: BaryonifyGrid calls
+ * model.displacement(r, M_j, a_j) and PaintProfilesGrid profile(cosmo, r, M_j, a_j) once per halo on r_grid.flatten() of the halo's WHOLE
+ * Nsize^d cutout (Map2DRunner.py:534, :577, :801; no cut: a callable declares none), in the reference's order (meshgrid indexing='xy', first
+ * axis around x_cen).  Halo ranges [j0, j1) let the caller hold one batch of radii / values at a time.
+ *   begin   paint = 0: BaryonifyGrid (R_q clipped to max(bins)/2, halos with Nsize < 2 skipped: count 0, :487-498); paint = 1: PaintProfilesGrid
+ *           (Nsize clipped to [2, npix/2], :726-728).  counts_host[n] = Nsize^ndim of every halo.  cat_host->rmat = use_ellipticity (2D only);
+ *           `model` as for the shell entries (grid runners: cosmo_runner with w0 = -1).  BFGX_ERR_ASSERT: the 2D offset assert (:516, :747)
+ *   radii   r_host[off[j1] - off[j0]] = the radii of halos [j0, j1) (sheared with use_ellipticity, :525-530), off = exclusive prefix sum of
+ *           the counts; bit for bit numpy's without ellipticity
+ *   apply   vals_host (same layout) = what the model returned for halos [j0, j1); accumulated on the device, once per range: paint = 0:
+ *           value / res along the unsheared unit vector (:534-536, :577-579); paint = 1: value where isfinite(value) & r < eps * R_j (:800-812)
+ *   finish  paint = 0: non-finite offsets -> 0, regrid of map_in into map_out (:577-599), mass check (:601-605: BFGX_ERR_MASS);
+ *           paint = 1: map_out = the painted map (map_in ignored)
+ *   end     bfgx_shell_pairs_end's twin: frees the handle (also after an error). */
+int  bfgx_grid_pairs_begin(const bfgx_grid_catalog *cat_host, const bfgx_model *model, const bfgx_grid *grid, int32_t paint, int32_t device,
+                           bfgx_pairs **out, int64_t *counts_host);
+int  bfgx_grid_pairs_radii(bfgx_pairs *h, int64_t j0, int64_t j1, double *r_host);
+int  bfgx_grid_pairs_apply(bfgx_pairs *h, int64_t j0, int64_t j1, const double *vals_host);
+int  bfgx_grid_pairs_finish(bfgx_pairs *h, const double *map_in, double *map_out, int32_t check_mass, bfgx_stats *stats);
+void bfgx_grid_pairs_end(bfgx_pairs *h);
+
+/* BaryonifySnapshot calls model.displacement(d, M_j, a_j) once per halo on the distances of the particles within R_q = clip(eps * R_j / a,
+ * 0, L/2) of it (SnapshotRunner.py:217-245), every halo, an empty array when none is inside.  Same five-call shape:
+ *   begin   halos_host as for bfgx_baryonify_snapshot (float32-valued columns; lnM / rmat / extra ignored), `model` as for the shell entries
+ *           (cosmo_runner with w0 = -1); counts_host[n] = particles of every halo: the containment test and the minimum-image separations are
+ *           those of bfgx_baryonify_snapshot (d^2 <= R_q^2); within a halo the particles come in ascending index.  Particles outside [0, L]:
+ *           BFGX_ERR_INVALID
+ *   radii   r_host[off[j1] - off[j0]] = d of the pairs of halos [j0, j1), off = exclusive prefix sum of the counts
+ *   apply   vals_host (same layout) = what the model returned; offset = value * a, non-finite -> 0, along the min-image unit vector, accumulated
+ *           per particle on the device (once per range)
+ *   finish  x / y (/ z) _out[n_particles] = position + offset, re-wrapped into [0, L] once (:254-262)
+ *   end     frees the handle (also after an error). */
+int  bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_model *model, const bfgx_snapshot *snap_host, int32_t device,
+                               bfgx_pairs **out, int64_t *counts_host);
+int  bfgx_snapshot_pairs_radii(bfgx_pairs *h, int64_t j0, int64_t j1, double *r_host);
+int  bfgx_snapshot_pairs_apply(bfgx_pairs *h, int64_t j0, int64_t j1, const double *vals_host);
+int  bfgx_snapshot_pairs_finish(bfgx_pairs *h, double *x_out, double *y_out, double *z_out, bfgx_stats *stats);
+void bfgx_snapshot_pairs_end(bfgx_pairs *h);
+
 #ifdef __cplusplus
 }
 #endif
