@@ -3,12 +3,14 @@
 Generates tests/golden/grid_*.npz by running the UNMODIFIED reference (imported from /root/reference through the
 oracle/refshim stand-ins for pyccl / healpy / numba) on small synthetic inputs.  Build container only:
 
-    python tests/golden/make_golden_grid.py
+    python tests/golden/make_golden_grid.py              # grid2d_* / grid3d_* runner, regrid and make_map fixtures
+    python tests/golden/make_golden_grid.py params       # grid*_param*_paint: PaintProfilesGrid with a ParamTabulatedProfile
+    python tests/golden/make_golden_grid.py snapshot     # snap*: BaryonifySnapshot
 
 Reference code exercised as shipped:
 
     BaryonForge.Runners.BaryonifyGrid.process        (Map2DRunner.py:431-607), 2D, 2D + ellipticity, 3D
-    BaryonForge.Runners.PaintProfilesGrid.process    (Map2DRunner.py:676-817), 2D and 3D
+    BaryonForge.Runners.PaintProfilesGrid.process    (Map2DRunner.py:676-817), 2D and 3D, with per-halo properties o_j (:707-801)
     BaryonForge.Runners.regrid_pixels_2D / _3D       (Map2DRunner.py:14-163; numba.njit -> plain Python here)
     BaryonForge.utils.HaloNDCatalog / GriddedMap / ParticleSnapshot.make_map   (io.py)
 
@@ -194,6 +196,98 @@ def main():
 
 
 
+def run_param_paint(name, shape, L, cat, extra, redshift, eps_runner, table_axes, p_axes, P_table):
+    """PaintProfilesGrid with a ParamTabulatedProfile: per-halo property columns o_j (Map2DRunner.py:707-801)"""
+    ndim = len(shape)
+    N = shape[0]
+    bins = (np.arange(N) + 0.5) * (L / N)
+    z, M, r_axis = table_axes
+    cols = dict(extra, **{k: cat[k] for k in p_axes})
+    HCat = bfg.utils.HaloNDCatalog(x=cat['x'], y=cat['y'], M=cat['M'], redshift=redshift, cosmo=COSMO, z=cat['z'], **cols)
+    used = {k: np.array(HCat.cat[k], dtype=np.float64) for k in ('M', 'x', 'y', 'z') + tuple(p_axes)}   # float32 columns
+    rmat = None
+    if 'q_ell' in extra:
+        runner0 = bfg.Runners.DefaultRunnerGrid.__new__(bfg.Runners.DefaultRunnerGrid)
+        rmat = np.zeros((used['M'].size, 2, 2))
+        for j in range(used['M'].size):
+            A_j = HCat.cat['A_ell'][j]
+            rmat[j] = runner0.build_Rmat(A_j / np.sqrt(np.sum(A_j ** 2)), HCat.cat['q_ell'][j])
+    t0 = time.time()
+    GMap = bfg.utils.GriddedMap(map=np.zeros(shape), redshift=redshift, bins=bins, cosmo=COSMO)
+    model = MG.ref_param_profile(z, M, r_axis, P_table, p_axes, COSMO)
+    out = bfg.Runners.PaintProfilesGrid(HCat, GMap, eps_runner, model, use_ellipticity=rmat is not None, verbose=False).process()
+    otab = O.Table([np.log(1 + z), np.log(M), np.log(r_axis)] + [p_axes[k] for k in p_axes], np.log(P_table), p_keys=list(p_axes))
+    oout = G.paint_grid(shape, bins, used, redshift, otab, eps_runner, G.grid_background(COSMO), rmat)
+    print(f"{name:24s} paint     shape={shape} N={used['M'].size:4d} p_keys={list(p_axes)} ref+oracle {time.time() - t0:6.1f}s  "
+          f"max|oracle-ref|/max|ref| = {np.abs(oout - out).max() / np.abs(out).max():.3e}   nonzero px = {int((out != 0).sum())}")
+    np.savez_compressed(
+        os.path.join(HERE, name + '.npz'), kind='paint', ndim=ndim, npix=N, L=L, bins=bins, redshift=redshift,
+        eps_runner=eps_runner, eps_model=0.0, rdelta=False,
+        cat_M=used['M'], cat_x=used['x'], cat_y=used['y'], cat_z=used['z'],
+        rmat=rmat if rmat is not None else np.zeros(0),
+        tab_z=z, tab_M=M, tab_r=r_axis, tab_values=P_table, map_in=np.zeros(0, dtype=np.uint8),
+        cosmo_runner=np.array([COSMO[k] for k in ('Omega_m', 'Omega_b', 'h', 'sigma8', 'n_s', 'w0')]),
+        cosmo_model=np.array([COSMO[k] for k in ('Omega_m', 'Omega_b', 'h', 'sigma8', 'n_s', 'w0')]),
+        p_keys=np.array(list(p_axes)), **{'p_axis_' + k: v for k, v in p_axes.items()},
+        **{'cat_' + k: used[k] for k in p_axes}, expected=out)
+
+
+# property axes of the grid fixtures: a non-uniform one and a uniform one
+C_AX = np.array([3.0, 5.0, 9.0])
+F_AX = np.linspace(0.05, 0.15, 4)
+# halos (by catalog index) whose property sits on a node or outside its axis; the others draw theirs inside.  The catalog
+# stores float32 columns (HaloNDCatalog, '>f4'): fgas = 0.15 reads 0.15000000596 > F_AX[-1], outside -> NaN -> the reference
+# paints nothing for that halo (checked: the whole ball of halo 10 stays empty); fgas = 0.05 reads 0.05000000075, inside.
+C_SPECIAL = {4: 3.0, 5: 9.0, 6: 5.0, 7: 2.5, 8: 9.5}
+F_SPECIAL = {9: 0.05, 10: 0.15, 11: 0.04, 12: 0.16, 13: F_AX[1]}
+OUT_OF_AXIS = {'cdelta': [7, 8], 'fgas': [10, 11, 12]}
+
+
+def param_columns(cat, seed, logM_hi):
+    """cdelta / fgas columns with the special values above; the special halos get large masses, so that a halo that
+    should paint nothing would paint a visible ball"""
+    rng = np.random.default_rng(seed)
+    n = cat['M'].size
+    cat['cdelta'] = rng.uniform(C_AX[0], C_AX[-1], n)
+    cat['fgas'] = rng.uniform(F_AX[0], F_AX[-1] - 0.01, n)
+    for i, v in C_SPECIAL.items():
+        cat['cdelta'][i] = v
+    for i, v in F_SPECIAL.items():
+        cat['fgas'][i] = v
+    idx = sorted(set(C_SPECIAL) | set(F_SPECIAL))
+    cat['M'][idx] = 10 ** np.linspace(logM_hi - 0.15, logM_hi - 0.6, len(idx))
+    return cat
+
+
+def param_tables(z, M, r):
+    base = syn.paint_table(z, M, r)
+    P1 = base[..., None] * (1 + 0.1 * (C_AX - 5.0))[None, None, None, :]
+    P2 = P1[..., None] * (F_AX / 0.1)[None, None, None, None, :] ** 1.5
+    return P1, P2
+
+
+def main_params():
+    # 2D: 96^2 pixels of 1.5 Mpc
+    L, N, zr = 144.0, 96, 0.25
+    ax = table_for(zr, 12.6, 15.2, NR=120)
+    P1, P2 = param_tables(*ax)
+    cat, extra = grid_catalog(300, L, 51, 12.6, 15.2, 2)
+    cat = param_columns(cat, 52, 15.2)
+    run_param_paint('grid2d_param1_paint', (N, N), L, cat, {}, zr, 4.0, ax, {'cdelta': C_AX}, P1)
+    run_param_paint('grid2d_param2_paint', (N, N), L, cat, {}, zr, 4.0, ax, {'cdelta': C_AX, 'fgas': F_AX}, P2)
+    cat, extra = grid_catalog(200, L, 53, 12.6, 15.2, 2, ell=True)
+    cat = param_columns(cat, 54, 15.2)
+    run_param_paint('grid2d_param1_paint_ell', (N, N), L, cat, extra, zr, 4.0, ax, {'cdelta': C_AX}, P1)
+    # 3D: 40^3 pixels of 2 Mpc
+    L, N, zr = 80.0, 40, 0.0
+    ax = table_for(zr, 12.5, 15.3, NR=120)
+    P1, P2 = param_tables(*ax)
+    cat, extra = grid_catalog(200, L, 55, 12.5, 15.3, 3)
+    cat = param_columns(cat, 56, 15.3)
+    run_param_paint('grid3d_param1_paint', (N, N, N), L, cat, {}, zr, 3.0, ax, {'cdelta': C_AX}, P1)
+    run_param_paint('grid3d_param2_paint', (N, N, N), L, cat, {}, zr, 3.0, ax, {'cdelta': C_AX, 'fgas': F_AX}, P2)
+
+
 def run_snapshot(name, ndim, L, npart, nh, seed, redshift, eps_runner, eps_model, rdelta=False, cosmo_model=None):
     """BaryonifySnapshot.process (SnapshotRunner.py:199-262) with scipy's own periodic KDTree"""
     rng = np.random.default_rng(seed)
@@ -244,5 +338,7 @@ def main_snapshot():
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'snapshot':
         main_snapshot()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'params':
+        main_params()
     else:
         main()

@@ -71,6 +71,9 @@ def product_runner(g, acc_f64=None):
 # ------------------------------------------------------------------------------------------ regular-grid path
 GRID_RUNNER_CASES = ['grid2d_baryonify', 'grid2d_baryonify_ell', 'grid2d_paint', 'grid2d_paint_ell', 'grid3d_baryonify',
                      'grid3d_paint']
+# PaintProfilesGrid with a ParamTabulatedProfile (model.p_keys: one or two property axes)
+GRID_PARAM_CASES = ['grid2d_param1_paint', 'grid2d_param2_paint', 'grid2d_param1_paint_ell', 'grid3d_param1_paint',
+                    'grid3d_param2_paint']
 
 
 def load_grid_golden(name):
@@ -90,20 +93,25 @@ def load_grid_golden(name):
         g['rmat'] = g['rmat'] if g['rmat'].size else None
         g['shape'] = (g['npix'],) * g['ndim']
         g['map_in'] = g['map_in'].astype(np.float64)
+        g['p_keys'] = [str(k) for k in g['p_keys']] if 'p_keys' in g else []
+        g['p_axes'] = {k: g['p_axis_' + k] for k in g['p_keys']}
+        for k in g['p_keys']:                  # the float32-rounded property columns, as the catalog holds them
+            g['cat'][k] = g['cat_' + k]
     return g
 
 
 def grid_oracle_run(g):
     from oracle import grid as G
     from oracle import oracle as O
-    axes = [np.log(1 + g['tab_z']), np.log(g['tab_M']), np.log(g['tab_r'])]
+    p_keys = g.get('p_keys', [])               # (callers also pass hand-built dicts without property axes)
+    axes = [np.log(1 + g['tab_z']), np.log(g['tab_M']), np.log(g['tab_r'])] + [g['p_axes'][k] for k in p_keys]
     bg = G.grid_background(g['cosmo_runner'])
     if g['kind'] == 'baryonify':
-        tab = O.Table(axes, g['tab_values'], g['rdelta'], g['eps_model'])
+        tab = O.Table(axes, g['tab_values'], g['rdelta'], g['eps_model'], p_keys=p_keys)
         return G.baryonify_grid(g['map_in'], g['bins'], g['cat'], g['redshift'], tab, g['eps_runner'], bg,
                                 O.Background.from_dict(g['cosmo_model']), g['rmat'])
     with np.errstate(divide='ignore'):
-        tab = O.Table(axes, np.log(g['tab_values']))
+        tab = O.Table(axes, np.log(g['tab_values']), p_keys=p_keys)
     return G.paint_grid(g['shape'], g['bins'], g['cat'], g['redshift'], tab, g['eps_runner'], bg, g['rmat'])
 
 
@@ -124,6 +132,8 @@ def grid_product_runner(g):
     extra = {}
     if ell:         # placeholders: the constructor asserts the columns exist; the matrices come from the fixture
         extra = {'q_ell': np.ones(cat['M'].size), 'A_ell': np.ones((cat['M'].size, 2))}
+    p_keys = g.get('p_keys', [])
+    extra.update({k: cat[k] for k in p_keys})
     HCat = bfg.utils.HaloNDCatalog(x=cat['x'], y=cat['y'], M=cat['M'], redshift=g['redshift'], cosmo=g['cosmo_runner'],
                                    z=cat['z'] if g['ndim'] == 3 else None, **extra)
     cosmo_model = bfg.utils.Cosmology.from_dict(g['cosmo_model'])
@@ -134,8 +144,12 @@ def grid_product_runner(g):
         base = bfg.Runners.BaryonifyGrid
     else:
         GMap = bfg.utils.GriddedMap(map=np.zeros(g['shape']), redshift=g['redshift'], bins=g['bins'], cosmo=g['cosmo_runner'])
-        model = bfg.utils.TabulatedProfile(None, cosmo_model)
-        model.set_table(g['tab_z'], g['tab_M'], g['tab_r'], g['tab_values'])
+        if p_keys:
+            model = bfg.utils.ParamTabulatedProfile(None, cosmo_model)
+            model.set_table(g['tab_z'], g['tab_M'], g['tab_r'], g['tab_values'], other_params=g['p_axes'])
+        else:
+            model = bfg.utils.TabulatedProfile(None, cosmo_model)
+            model.set_table(g['tab_z'], g['tab_M'], g['tab_r'], g['tab_values'])
         base = bfg.Runners.PaintProfilesGrid
     cls = type(base.__name__, (_FixedRmat, base), {}) if ell else base
     runner = cls(HCat, GMap, g['eps_runner'], model, use_ellipticity=ell, verbose=False)

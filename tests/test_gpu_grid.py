@@ -845,3 +845,168 @@ def test_make_map_refuses_nan_masses_as_the_reference(gpu):
         Snap.make_map(16)
     Snap.cat['M'][4321] = 1.0
     assert Snap.make_map(16).sum() == 5000
+
+
+# ------------------------------------------------------------------------------------------ property axes (model.p_keys)
+@pytest.mark.parametrize('name', H.GRID_PARAM_CASES)
+def test_grid_param_paint_vs_reference_golden_and_oracle(gpu, name):
+    """PaintProfilesGrid with a ParamTabulatedProfile (one / two property axes: the NC = 8 / 16 corner-row kernels) against the
+    reference's output and the oracle; halos with a property on an axis node, on both axis ends and outside an axis (NaN: they paint
+    nothing), incl. fgas = 0.15 that is outside the axis only as the catalog's float32"""
+    g = H.load_grid_golden(name)
+    out = H.grid_product_runner(g).process()
+    exp = g['expected']
+    assert out.dtype == np.float64 and out.shape == exp.shape
+    ora = H.grid_oracle_run(g)
+    print('%s: max|hip-reference|/max = %.2e  max|hip-oracle|/max = %.2e' % (name, np.abs(out - exp).max() / np.abs(exp).max(),
+                                                                          np.abs(out - ora).max() / np.abs(ora).max()))
+    assert np.abs(out - exp).max() <= 1e-10 * np.abs(exp).max()
+    assert np.array_equal(out != 0, exp != 0)
+    assert np.abs(out - ora).max() <= 1e-10 * np.abs(ora).max()
+
+
+@pytest.mark.parametrize('name', H.GRID_PARAM_CASES)
+def test_grid_param_paint_out_of_axis_halos_paint_nothing(gpu, name):
+    """a catalog of only the halos whose property lies outside its axis paints an all-zero map; the same halos with the property
+    moved onto an interior node do paint (the check is not empty)"""
+    g = H.load_grid_golden(name)
+    cat = g['cat']
+    out_of_axis = np.zeros(cat['M'].size, dtype=bool)
+    for k in g['p_keys']:
+        out_of_axis |= (cat[k] < g['p_axes'][k][0]) | (cat[k] > g['p_axes'][k][-1])
+    idx = np.nonzero(out_of_axis)[0]
+    assert idx.size == (2 if len(g['p_keys']) == 1 else 5)
+    if 'fgas' in g['p_keys']:
+        assert np.float32(0.15) in cat['fgas'][idx]                   # the float32-rounded axis end
+    for k in cat:
+        if cat[k] is not None and np.ndim(cat[k]):
+            cat[k] = cat[k][idx]
+    if g['rmat'] is not None:
+        g['rmat'] = g['rmat'][idx]
+    assert np.all(H.grid_product_runner(g).process() == 0)
+    for k in g['p_keys']:
+        cat[k] = np.full(idx.size, g['p_axes'][k][1])
+    assert np.count_nonzero(H.grid_product_runner(g).process()) > 20 * idx.size
+
+
+def test_grid_paint_three_property_axes_refused(gpu):
+    """the regular-grid runners read out at most two property axes: a third is refused with NotImplementedError
+    (BFGX_ERR_UNSUPPORTED from bfgx_grid_plan_create), and no map comes back"""
+    import baryonification_amd as bfg
+    g = H.load_grid_golden('grid2d_param2_paint')
+    t_ax = np.array([2.0, 3.5, 6.0])
+    g['p_keys'] = g['p_keys'] + ['theta']
+    g['p_axes']['theta'] = t_ax
+    g['cat']['theta'] = np.full(g['cat']['M'].size, 3.0)
+    g['tab_values'] = g['tab_values'][..., None] * (1 + 0.05 * (t_ax - 4.0))
+    runner = H.grid_product_runner(g)
+    assert isinstance(runner.model, bfg.utils.ParamTabulatedProfile) and len(runner.model.p_keys) == 3
+    with pytest.raises(NotImplementedError, match='at most 2 property axes'):
+        runner.process()
+    assert np.all(runner.GriddedMap.map == 0)
+
+
+C_AX = np.array([3.0, 5.0, 9.0])              # non-uniform property axis
+F_AX = np.linspace(0.05, 0.15, 4)
+
+
+def _param_grid_case(ndim, N, nh, nprop, seed, ell=False):
+    """_big_case with one / two property columns (float32-rounded as a catalog holds them) and a displacement table that depends
+    on them.  Halos 0-2 sit on both ends and an interior node of the first axis, 3-4 outside it; with two axes 5-6 on the ends of the
+    second, 7-8 outside it (halo 6: fgas = 0.15 is outside only after float32 rounding).  Halos 0-8 are massive."""
+    from oracle import grid as G
+    c = _big_case(ndim, N, nh, seed)
+    rng = np.random.default_rng(seed + 1)
+    cols = [rng.uniform(C_AX[0], C_AX[-1], nh), rng.uniform(F_AX[0], F_AX[-1] - 0.01, nh)][:nprop]
+    cols[0][:5] = [3.0, 9.0, 5.0, 2.5, 9.5]
+    out_idx = [3, 4]
+    if nprop == 2:
+        cols[1][5:9] = [0.05, 0.15, 0.04, 0.16]
+        out_idx += [6, 7, 8]
+    c['cols'] = [v.astype(np.float32).astype(np.float64) for v in cols]
+    c['cat']['M'][:9] = (10 ** np.linspace(14.9, 14.4, 9)).astype(np.float32)
+    c['out_idx'] = out_idx
+    c['p_axes'] = [C_AX, F_AX][:nprop]
+    d = c['d'][..., None] * (1 + 0.1 * (C_AX - 5.0))
+    if nprop == 2:
+        d = d[..., None] * (F_AX / 0.1) ** 1.5
+    c['d'] = 40.0 * d                                 # moves of up to about a cell: the regrid sees the property dependence
+    c['rmat'] = G.build_Rmat(rng.normal(size=(nh, 2)), rng.uniform(0.4, 1.0, nh)) if ell else None
+    return c
+
+
+@pytest.mark.parametrize('ndim,N,nh,nprop,ell', [(2, 128, 300, 1, False), (2, 128, 300, 2, False), (3, 48, 200, 1, False),
+                                                 (3, 48, 200, 2, False), (2, 96, 200, 2, True)])
+def test_grid_param_displacement_every_route_vs_oracle(gpu, monkeypatch, ndim, N, nh, nprop, ell):
+    """a displacement table with property axes (NC = 8 / 16) through every regular-grid route -- the one-shot bfgx_baryonify_grid
+    (streamed cell-owned gather), the same call on the halo-owned scatter kernels, GridPlan.baryonify, GridPlan.offsets + regrid --
+    against the oracle (BaryonifyGrid's loop with o_j): maps at 1e-10 max, mass conserved, and the pix_offsets themselves (cells
+    poisoned by an out-of-axis halo are NaN in both)"""
+    import ctypes as C
+    import torch
+    from baryonification_amd import _lib, engine
+    from oracle import grid as G
+    from oracle import oracle as O
+    c = _param_grid_case(ndim, N, nh, nprop, 31 + 2 * ndim + nprop, ell)
+    keys = ['p%d' % k for k in range(nprop)]
+    cat = dict(c['cat'], **dict(zip(keys, c['cols'])))
+    hmap, rmat = c['map'], c['rmat']
+    axes = [np.log(1 + c['z']), np.log(c['Mt']), np.log(c['r'])] + c['p_axes']
+    cos = dict(c['cosmo'], w0=-1.0)
+    m, keep = engine.model_from_tables(axes, c['d'], cos, 6.0, 8.0)
+    tab = O.Table(axes, c['d'], False, 8.0, p_keys=keys)
+    ora_off = G.baryonify_grid_offsets(hmap.shape, c['bins'], cat, c['redshift'], tab, 6.0, G.grid_background(cos), rmat=rmat)
+    ora = G.regrid_offsets(hmap, ora_off)
+    fin = np.isfinite(ora_off)
+    assert not fin.all() and np.isclose(ora.sum(), hmap.sum())      # the out-of-axis halos poison their balls
+    scale = np.abs(ora).max()
+
+    lnM = np.log(cat['M'].astype(np.float32)).astype(np.float64)
+    hcat, hkeep = _lib.make_grid_catalog_host(cat['M'], cat['x'], cat['y'], cat['z'] if ndim == 3 else None, lnM, rmat, c['cols'])
+    grid, gkeep = _lib.make_grid(c['bins'], ndim, c['redshift'])
+
+    def one_shot():
+        out = np.full_like(hmap, np.nan)
+        opts, stats = _lib.bfgx_opts(0, 1, 1, 1, 1, 0), _lib.bfgx_stats()
+        _lib.check(_lib.load().bfgx_baryonify_grid(C.byref(hcat), C.byref(m), C.byref(grid), hmap.ctypes.data, out.ctypes.data,
+                                                   C.byref(opts), C.byref(stats)))
+        assert stats.n_pairs > 0 and np.isclose(stats.sum_out, stats.sum_in, rtol=1e-12)
+        return out
+
+    res = {'one_shot': one_shot()}
+    monkeypatch.setenv('BFGX_GRID_PATH', 'scatter')
+    res['one_shot_scatter'] = one_shot()
+    monkeypatch.delenv('BFGX_GRID_PATH')
+
+    dev = torch.device('cuda:0')
+    t = {k: torch.tensor(cat[k], dtype=torch.float64, device=dev) for k in ['M', 'x', 'y', 'z'] + keys}
+    t['lnM'] = torch.tensor(lnM, device=dev)
+    t['rmat'] = torch.tensor(rmat.reshape(-1, 4), device=dev) if ell else None
+    stream = torch.cuda.current_stream().cuda_stream
+    plan = engine.GridPlan(m, keep, c['bins'], ndim, c['redshift'], nh, 0, stream)
+    dcat = _lib.make_grid_catalog_dev(nh, t['M'].data_ptr(), t['x'].data_ptr(), t['y'].data_ptr(), t['z'].data_ptr() if ndim == 3 else 0,
+                                      t['lnM'].data_ptr(), t['rmat'].data_ptr() if ell else 0, [t[k].data_ptr() for k in keys])
+    m_in = torch.tensor(hmap, device=dev)
+    off = torch.full((N ** ndim, ndim), float('nan'), dtype=torch.float64, device=dev)
+    o_cell, o_scat = torch.full_like(m_in, float('nan')), torch.full_like(m_in, float('nan'))
+    s_cell, s_scat = (torch.zeros(2, dtype=torch.float64, device=dev) for _ in range(2))
+    n_cell = plan.baryonify(dcat, m_in.data_ptr(), o_cell.data_ptr(), s_cell.data_ptr())
+    n_scat = plan.offsets(dcat, off.data_ptr())
+    plan.regrid(m_in.data_ptr(), off.data_ptr(), o_scat.data_ptr(), s_scat.data_ptr())
+    torch.cuda.synchronize()
+    plan.close()
+    assert n_cell == n_scat > 0
+    res['plan_baryonify'], res['plan_offsets_regrid'] = o_cell.cpu().numpy(), o_scat.cpu().numpy()
+    for s in (s_cell, s_scat):
+        s = s.cpu().numpy()
+        assert np.isclose(s[0], hmap.sum(), rtol=1e-12) and np.isclose(s[1], s[0], rtol=1e-12)
+
+    d_off = off.cpu().numpy()
+    print('ndim %d nprop %d ell %d: offsets %.2e, maps %s' % (ndim, nprop, ell, np.abs(d_off[fin] - ora_off[fin]).max() / np.abs(ora_off[fin]).max(),
+                                                           {k: '%.2e' % (np.abs(v - ora).max() / scale) for k, v in res.items()}))
+    assert np.array_equal(np.isfinite(d_off), fin)
+    assert np.abs(d_off[fin] - ora_off[fin]).max() <= 1e-10 * np.abs(ora_off[fin]).max()
+    for route, out in res.items():
+        assert out.shape == hmap.shape and np.isfinite(out).all(), route
+        assert np.abs(out - ora).max() <= 1e-10 * scale, (route, np.abs(out - ora).max() / scale)
+        assert np.isclose(out.sum(), hmap.sum(), rtol=1e-12), route

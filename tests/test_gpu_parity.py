@@ -449,3 +449,115 @@ def test_callable_models_per_halo_and_tabulated(gpu):
         bfg.Runners.BaryonifyShell(Catalog, Shell, eps, object(), verbose=False).process()
     with pytest.raises(NameError):                                              # a table class that was never set up: as the reference
         bfg.Runners.BaryonifyShell(Catalog, Shell, eps, bfg.Profiles.Baryonification2D(None, None, cosmo), verbose=False).process()
+
+
+# ------------------------------------------------------------------------------------------ displacement tables with property axes
+SHELL_P_AXES = [np.array([3.0, 5.0, 9.0]), np.linspace(0.05, 0.15, 4), np.array([2.0, 3.5, 6.0]), np.array([-0.2, 0.1, 0.4])]
+
+
+def _param_shell_case(nprop, nh, seed):
+    """low-z catalog with halos on (the catalog's clipped) poles, near them and across ra = 0 / 360, and `nprop` property columns:
+    every axis gets halos on both of its ends, on an interior node, and below and above it (NaN read-out: on the shell such a halo
+    moves nothing, HealpixRunner.py:323).  The displacement table depends on every property axis (non-uniform ones included)."""
+    from baryonification_amd import synthetic as syn
+    cat = syn.make_catalog(nh, seed=seed, z_lo=0.01, z_hi=0.06, logM_lo=13.0, logM_hi=15.3)
+    cat['dec'][:6] = [90.0 - 1e-8, -90.0 + 1e-8, 89.7, -89.6, 0.0, 35.0]
+    cat['ra'][:6] = [10.0, 200.0, 123.0, 300.0, 0.0, 359.999]
+    cat['M'][:6] = 10.0 ** np.array([14.9, 14.7, 15.0, 14.5, 14.8, 14.6])
+    rng = np.random.default_rng(seed + 1)
+    keys = ['p%d' % k for k in range(nprop)]
+    for i, (k, ax) in enumerate(zip(keys, SHELL_P_AXES)):
+        cat[k] = rng.uniform(ax[0], ax[-1], nh)
+        j = 6 + 5 * i
+        cat[k][j:j + 5] = [ax[0], ax[-1], ax[1], ax[0] - 0.5 * (ax[1] - ax[0]), ax[-1] + 0.5 * (ax[-1] - ax[-2])]
+        cat['M'][j:j + 5] = 10.0 ** np.array([14.6, 14.5, 14.4, 14.7, 14.6])
+    z, M, r = syn.table_grid(cat, Nz=4, NM=5, NR=90, pad=1e-9)
+    d = syn.displacement_table(z, M, r)
+    factors = [lambda a: 1 + 0.1 * (a - 5.0), lambda a: (a / 0.1) ** 1.5, lambda a: 1 + 0.05 * (a - 4.0), lambda a: np.exp(0.3 * a)]
+    for ax, f in zip(SHELL_P_AXES[:nprop], factors):
+        d = d[..., None] * f(ax)
+    axes = [np.log(1 + z), np.log(M), np.log(r)] + SHELL_P_AXES[:nprop]
+    return cat, keys, axes, d
+
+
+@pytest.mark.parametrize('nprop,nside', [(1, 128), (2, 128), (3, 64), (4, 64)])
+def test_param_displacement_shell_every_precision_vs_oracle(gpu, nprop, nside):
+    """BaryonifyShell's loop with a displacement table of 1-4 property axes (NC = 8 ... 64: the generic tile kernel and its corner
+    rows), through engine.ShellPlan and the one-shot bfgx_baryonify_shell (algo 1), against the oracle in every precision mode:
+    ACC_F64 and ACC_PARITY (resolves to fp64 on these tables) at 1e-10 max on a table that moves pixels by about one pixel side,
+    ACC_F32 at SURVEY 8(d)'s 1e-6 mean(map) on the same table scaled to move them by 0.05, ACC_AUTO on both scalings (asserting what
+    it resolves to), mass conserved everywhere; algo 0 refuses these tables"""
+    import ctypes as C
+    import torch
+    from baryonification_amd import _lib, engine, synthetic as syn
+    from oracle import oracle as O
+    nh = 300
+    cat, keys, axes, d = _param_shell_case(nprop, nh, 60 + nprop)
+    eps = 12.0
+    hmap = syn.make_map(nside, seed=5 + nprop)
+    npix = hmap.size
+    dev = torch.device('cuda:0')
+    st = torch.cuda.current_stream().cuda_stream
+    hcat, hkeep = _lib.make_catalog_host(cat['M'], cat['z'], cat['ra'], cat['dec'], [cat[k] for k in keys])
+    t = {k: torch.tensor(v, dtype=torch.float64, device=dev) for k, v in cat.items()}
+    lnz, lnM = _lib.table_coords(cat['M'], cat['z'])
+    t['lnz'], t['lnM'] = torch.tensor(lnz, device=dev), torch.tensor(lnM, device=dev)
+    dcat = _lib.make_catalog_dev(nh, t['M'].data_ptr(), t['z'].data_ptr(), t['ra'].data_ptr(), t['dec'].data_ptr(),
+                                 [t[k].data_ptr() for k in keys], t['lnz'].data_ptr(), t['lnM'].data_ptr())
+    d_map = torch.tensor(hmap, device=dev)
+
+    def plan_for(scale):
+        model, keep = engine.model_from_tables(axes, scale * d, syn.COSMO, eps, eps)
+        return model, keep, engine.ShellPlan(model, keep, nside, nh, 0, st)
+
+    model, keep, plan = plan_for(1.0)
+    disp1 = plan.precision(_lib.ACC_AUTO)[1]                            # pixel sides the unscaled table moves a pixel by
+    plan.close()
+    assert disp1 > 0
+    errs = {}
+    for scale_px in (1.0, 0.05):
+        scale = scale_px / disp1
+        model, keep, plan = plan_for(scale)
+        assert np.isclose(plan.precision(_lib.ACC_AUTO)[1], scale_px, rtol=1e-9)
+        ora = O.baryonify_shell(nside, hmap, cat, O.Table(axes, scale * d, False, eps, p_keys=keys), eps, O.Background.from_dict(syn.COSMO))
+        moved = np.abs(ora - hmap).max()
+        assert moved > 1e-3 * hmap.mean()
+        auto = plan.precision(_lib.ACC_AUTO)[0]
+        assert auto == (_lib.ACC_F64 if scale_px == 1.0 else _lib.ACC_F32), auto
+        assert plan.precision(_lib.ACC_PARITY)[0] == _lib.ACC_F64
+        modes = (_lib.ACC_F64, _lib.ACC_PARITY, _lib.ACC_AUTO) if scale_px == 1.0 else (_lib.ACC_F32, _lib.ACC_AUTO)
+        for acc in modes:
+            resolved = plan.precision(acc)[0]
+            tol = 1e-10 * np.abs(ora).max() if resolved == _lib.ACC_F64 else 1e-6 * hmap.mean()
+            off = torch.full((npix * 3,), float('nan'), dtype=torch.float32 if resolved == _lib.ACC_F32 else torch.float64, device=dev)
+            out = torch.full((npix,), float('nan'), dtype=torch.float64, device=dev)
+            sums = torch.zeros(2, dtype=torch.float64, device=dev)
+            plan.baryonify(dcat, d_map.data_ptr(), off.data_ptr(), out.data_ptr(), sums.data_ptr(), acc_f64=acc)
+            torch.cuda.synchronize()
+            got, sm = out.cpu().numpy(), sums.cpu().numpy()
+            # mass: 1e-12 in fp64; fp32 pix_offsets move mass by up to the per-pixel bound summed, 1e-6 of the map's sum (measured 3e-10)
+            rtol = 1e-12 if resolved == _lib.ACC_F64 else 1e-6
+            assert np.isclose(sm[1], sm[0], rtol=rtol) and np.isclose(got.sum(), hmap.sum(), rtol=rtol), acc
+            one = np.full(npix, np.nan)
+            opts, stats = _lib.bfgx_opts(0, acc, 1, 1, 1, 0), _lib.bfgx_stats()
+            _lib.check(_lib.load().bfgx_baryonify_shell(C.byref(hcat), C.byref(model), nside, hmap.ctypes.data, one.ctypes.data,
+                                                        C.byref(opts), C.byref(stats)))
+            assert np.isclose(one.sum(), hmap.sum(), rtol=rtol) and np.isclose(stats.sum_out, stats.sum_in, rtol=rtol), acc
+            for route, res in (('plan', got), ('one_shot', one)):
+                err = np.abs(res - ora).max()
+                errs[(scale_px, acc, route)] = err / (np.abs(ora).max() if resolved == _lib.ACC_F64 else hmap.mean())
+                assert np.isfinite(res).all() and err <= tol, (route, acc, scale_px, errs[(scale_px, acc, route)])
+        plan.close()
+    print('nprop %d: %s' % (nprop, {k: '%.2e' % v for k, v in errs.items()}))
+    # algo 0 (per-halo global atomics) has no property-axis read-out: refused, no map
+    model, keep, plan = plan_for(1.0 / disp1)
+    plan.set_algo(0)
+    off = torch.zeros(npix * 3, dtype=torch.float64, device=dev)
+    out = torch.zeros(npix, dtype=torch.float64, device=dev)
+    with pytest.raises(NotImplementedError, match='algo 1'):
+        plan.baryonify(dcat, d_map.data_ptr(), off.data_ptr(), out.data_ptr(), 0, acc_f64=_lib.ACC_F64)
+    plan.close()
+    one = np.zeros(npix)
+    with pytest.raises(NotImplementedError, match='algo 1'):
+        _lib.check(_lib.load().bfgx_baryonify_shell(C.byref(hcat), C.byref(model), nside, hmap.ctypes.data, one.ctypes.data,
+                                                    C.byref(_lib.bfgx_opts(0, _lib.ACC_F64, 1, 1, 0, 0)), C.byref(_lib.bfgx_stats())))

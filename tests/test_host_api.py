@@ -79,6 +79,20 @@ def test_model_protocol_errors():
         r.process()
 
 
+def test_grid_property_keys_need_a_param_tabulated_profile():
+    """BaryonifyGrid / PaintProfilesGrid with model.p_keys but a model that is not a ParamTabulatedProfile: the reference's assert and
+    text (Map2DRunner.py:471-474, :703-706), raised before any device work"""
+    import re
+    from helpers import load_grid_golden, grid_product_runner
+    for name in ('grid2d_baryonify', 'grid3d_paint'):
+        r = grid_product_runner(load_grid_golden(name))
+        r.model.p_keys = ['cdelta']
+        txt = ("You asked to use ['cdelta'] properties in Baryonification. You must pass a ParamTabulatedProfile"
+               "as the model. You have passed %s instead" % type(r.model))
+        with pytest.raises(AssertionError, match=re.escape(txt)):
+            r.process()
+
+
 def test_build_model_struct_contents():
     g = load_golden('rdelta_baryonify')
     r = product_runner(g)
