@@ -34,9 +34,6 @@ template <typename T> static inline hipError_t bfgx_counted_malloc(T **p, size_t
 #include "bfgx_kernels.hpp"
 #include "bfgx_scatter2.hpp"
 #include "bfgx_regrid2.hpp"
-#ifndef BFGX_NP
-#define BFGX_NP 1          // pairs per lane per trip of the fast kernel's pair loop
-#endif
 #include "bfgx_tables.hpp"
 #include "bfgx_grid.hpp"
 #include "bfgx_grid_pairs.hpp"
@@ -424,8 +421,9 @@ template <int MODE, typename ACC, typename real, int PM = 0>
 static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
 {
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
+    constexpr int kNP = 1;          // pairs per lane per trip of the fast kernel's pair loop
     const size_t lds = tile2_lds_bytes<real>(p->tiling.BR, p->tiling.W, NCOMP);
-    auto kern = tile_scatter2_kernel<MODE, ACC, real, BFGX_NP, PM>;
+    auto kern = tile_scatter2_kernel<MODE, ACC, real, kNP, PM>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Tab8T<real> tb;
     tb.v = (sizeof(real) == 4) ? (const real *)p->tab8f : (const real *)p->tab8d;
@@ -616,7 +614,6 @@ static void plan_pick_precision(bfgx_plan *p, const bfgx_model *model)
     }
     p->table_disp_pixels = worst;
     if (worst > kAutoDispPixels) p->auto_acc = BFGX_ACC_PARITY;
-    if (const char *e = std::getenv("BFGX_AUTO_ACC")) { const int v = std::atoi(e); if (v == 0 || v == 1 || v == 3) p->auto_acc = v; }      // tests / A-B runs
 }
 
 }  // namespace
@@ -624,18 +621,6 @@ static void plan_pick_precision(bfgx_plan *p, const bfgx_model *model)
 extern "C" {
 
 int bfgx_abi_version(void) { return BFGX_ABI_VERSION; }
-
-#if BFGX_K1F_PROF
-// variant builds only (scripts/k1f_prof.py): the fluid kernel's shader-clock accounting, summed over waves and launches since the last reset
-int bfgx_debug_k1f_prof(unsigned long long *out8, int reset)
-{
-    HIP_TRY(hipDeviceSynchronize());
-    if (out8) HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(bfgx::g_k1f_prof), 8 * sizeof(unsigned long long)));
-    if (reset) { unsigned long long z[8] = {0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(bfgx::g_k1f_prof), z, sizeof(z))); }
-    return BFGX_OK;
-}
-#endif
-
 
 const char *bfgx_last_error(void) { return g_err.c_str(); }
 
@@ -742,7 +727,7 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
     }
     {   // fast tiled scatter: possible for a 3-axis table with a uniform ln r axis whose interleaved copy stays small
         const size_t n8 = (size_t)(t.n[0] - 1) * (size_t)(t.n[1] - 1) * (size_t)(t.n[2] - 1) * 8;
-        p->fast_ok = (t.ndim == 3) && p->model.tab.r_uniform && n8 * sizeof(double) <= ((size_t)256 << 20) && !std::getenv("BFGX_NO_FAST");
+        p->fast_ok = (t.ndim == 3) && p->model.tab.r_uniform && n8 * sizeof(double) <= ((size_t)256 << 20);
         if (p->fast_ok) {
             std::vector<float> v32;
             std::vector<double> v64;

@@ -26,10 +26,7 @@ constexpr int kDepChunk = 4096;                   // keys per workgroup in the s
 constexpr int kDepPer = kDepChunk / 256;
 constexpr int kDepTileThreads = 1024;             // 64 KB of LDS per tile: two workgroups per CU, so make them large
 constexpr int kDepEdgesLds = 2049;                // edges staged in LDS up to 2048 cells per axis
-#ifndef BFGX_DEP_PAD
-#define BFGX_DEP_PAD 16
-#endif
-constexpr int kDepPad = BFGX_DEP_PAD;             // words between two tiles' level-2 cursors (a workgroup adds to the ~128 cursors of its bucket, the ~128 workgroups of
+constexpr int kDepPad = 16;                       // words between two tiles' level-2 cursors (a workgroup adds to the ~128 cursors of its bucket, the ~128 workgroups of
                                                   // that bucket run together: atomics to one cache line serialise)
 constexpr int kDepHist = 2048;                    // LDS histogram entries of a sort pass (buckets a workgroup ranks locally)
 
@@ -288,10 +285,8 @@ deposit_split_kernel(DepGeom g, int64_t n_host, const int32_t *__restrict__ n_de
 // workgroup per tile: accumulate the tile's particles in LDS, store every cell of the tile once.  Unit masses (MASS = false) are COUNTED:
 // 32-bit integer cells (ds_add_u32: 32 KB per tile instead of 64 KB of fp64 -- four workgroups of NT = 512 threads per CU instead of two of
 // 1024, half the zeroing and read-out), converted on the way out -- exact, like the fp64 sum of ones it replaces.
-#ifndef BFGX_DEP_TILE_NT
-#define BFGX_DEP_TILE_NT 512
-#endif
-template <bool MASS> struct DepTileThreads { static constexpr int n = MASS ? kDepTileThreads : BFGX_DEP_TILE_NT; };
+constexpr int kDepCountThreads = 512;
+template <bool MASS> struct DepTileThreads { static constexpr int n = MASS ? kDepTileThreads : kDepCountThreads; };
 template <bool MASS>
 __global__ void __launch_bounds__(DepTileThreads<MASS>::n)
 deposit_tiles_kernel(DepGeom g, const int32_t *__restrict__ start2, const uint32_t *__restrict__ keys, const double *__restrict__ mass,

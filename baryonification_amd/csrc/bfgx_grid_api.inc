@@ -1169,13 +1169,11 @@ struct FftSetup {
         dk = kb1 - k_lo;
         if (dtw.up(tw.data(), sizeof(double) * N) || dkl.up(klin.data(), sizeof(double) * N)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
         lt = kFftTileLog2;
-        if (const char *e = std::getenv("BFGX_FFT_TILE")) lt = (std::atoi(e) >= 8) ? 3 : 2;          // tuning knob
         while (((size_t)N << lt) > 4096 && lt > 2) --lt;                                              // at most 64 KB of tile per workgroup
         tile = 1 << lt;
         // two radix-4 quads per thread and pass where the tile has that many (N = 512, 8 lines)
         const int nq = (N >> 2) << lt;
         threads = nq >= 512 ? 512 : 256;       // (1024 threads: one workgroup per CU, measured 15 % slower at N = 512)
-        if (const char *e = std::getenv("BFGX_FFT_THREADS")) threads = std::atoi(e) >= 1024 ? 1024 : (std::atoi(e) >= 512 ? 512 : 256);   // tuning knob
         ztiles = (unsigned)((nz + tile - 1) / tile);
         lds = fft_c2c_lds_bytes(N, lt, 0, 0);
         lds_bin1 = fft_c2c_lds_bytes(N, lt, nk, 1);
@@ -1258,7 +1256,7 @@ int fft_axis0_pk(FftSetup &f, hipStream_t s, int N, int nb, int b0, double2 *F, 
     const unsigned wgs = (unsigned)std::min<int64_t>(ntiles, (int64_t)f.n_cu * std::max<size_t>(1, (size_t)(160 * 1024) / f.lds_bin2));
     PkBins pb{f.dkl.as<double>(), f.k_lo, f.dk, 1.0 / f.dk, nk, b0, pk_sum_dev, k_sum_dev, counts_dev, nullptr, pitch};
     // bins, counts and |k| sums are functions of (N, L, nk) alone: tabulated by the first call (one byte per mode), looked up afterwards
-    const bool use_tab = nk <= 254 && !std::getenv("BFGX_PK_NO_TABLE");
+    const bool use_tab = nk <= 254;
     if (use_tab && !f.tab_ready) {
         if (f.dtab.up(nullptr, ((size_t)N * f.ztiles * N) << f.lt) || f.dksb.up(nullptr, sizeof(double) * (size_t)N * nk) ||
             f.dcnb.up(nullptr, sizeof(unsigned long long) * (size_t)N * nk))

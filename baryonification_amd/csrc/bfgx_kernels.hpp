@@ -17,15 +17,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#ifndef BFGX_PAIR32
-#define BFGX_PAIR32 1      // 1: fp32 pair tail when pix_offsets are stored as fp32 (pair_value_fast32)
-#endif
-#ifndef BFGX_ABLATE
-#define BFGX_ABLATE 0      // >0: timing-only ablation builds (scripts/ablate.sh); never shipped
-#endif
-#ifndef BFGX_ABL0
-#define BFGX_ABL0 0        // K0 ablations (timing only): 1 no record stores, 2 no tile binning, 3 neither, 16 no list stores, 32 no census of small discs
-#endif
 #include "bfgx_cosmo.hpp"
 #include "bfgx_math.hpp"
 
@@ -612,11 +603,9 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
 // workgroups of 256 per CU the kernel is compiled for (register budget 512 / this per lane).  Measured, config 2 on the S19 table (K0 in ms):
 // 3: 0.133, 4: 0.136, 5: 0.164, 6: 0.219, 8: 0.269 -- more waves only buy spills: the kernel is bound by the instructions it issues (2560 per
 // wave), not by the latency of its atomics
-#ifndef BFGX_K0_OCC
-#define BFGX_K0_OCC 4
-#endif
+constexpr int kK0Occ = 4;
 template <int NC, typename real>
-__global__ void __launch_bounds__(256, BFGX_K0_OCC)
+__global__ void __launch_bounds__(256, kK0Occ)
 halo_prep_kernel(DevModel m, Hpx h, int64_t nhalo,
                  const double *__restrict__ M, const double *__restrict__ z,
                  const double *__restrict__ ra, const double *__restrict__ dec,
@@ -744,7 +733,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     // <4-pixel fallback (HealpixRunner.py:309-310): only discs of a few pixels can qualify -> exact census
     r.fb = 0; r._pad = 0;
     for (int q = 0; q < 4; ++q) { r.fb_ring[q] = 0; r.fb_k[q] = 0; }
-    if (fallback4 && !bad && (r.rlast - r.rfirst) < 8 && !(BFGX_ABL0 & 32)) {
+    if (fallback4 && !bad && (r.rlast - r.rfirst) < 8) {
         // (from the middle ring outwards -- mid, mid + 1, mid - 1, ... --: the longest rows come first, and a disc of 4 or more pixels is
         // recognised after two rows instead of three or four from the edge; the slowest lane of a wave sets the trip count)
         int total = 0;
@@ -786,7 +775,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     for (int i = 0; i < kRefMax; ++i) { run[i].base = 0; run[i].hr = 0; }
     ref.n = 0; ref.cls = cls; ref._pad[0] = ref._pad[1] = 0;
     for (int i = 0; i < kRefMax; ++i) { ref.few.tile[i] = 0; ref.few.slot[i] = 0; }
-    if (o.tref && !(BFGX_ABL0 & 2)) {
+    if (o.tref) {
         DiscSpan ds;
         ds.fb = r.fb; ds.rfirst = r.rfirst; ds.rlast = r.rlast; ds.allphi = r.allphi; ds.flo = r.flo; ds.fhi = r.fhi;
         for (int q = 0; q < 4; ++q) { ds.fb_ring[q] = r.fb_ring[q]; ds.fb_k[q] = r.fb_k[q]; }
@@ -835,7 +824,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     }
 
     if (live && o.rec && (o.rec_all || cls == kClsWide)) o.rec[j] = r;
-    if (cls == kClsNarrow && !(BFGX_ABL0 & 1)) {
+    if (cls == kClsNarrow) {
         RowRec rr;
         rr.z0 = r.z0; rr.s0 = r.s0; rr.xa = r.xa; rr.cosr = r.cosr; rr.phi0 = r.phi0;
         rr.rfirst = r.rfirst; rr.rlast = r.rlast; rr.fb = (r.fb ? 1 : 0) | (geo_wide ? 2 : 0); rr._pad = 0;
@@ -874,8 +863,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
             o.fbrec[j] = f;
         }
     }
-    if (BFGX_ABL0 & 1) { if (r.cosr == 1.2345 && wv[0] == 0.5) o.rowrec[j].z0 = r.lnoff + r.rcut; }      // keep the values alive
-    if (o.tref && !(BFGX_ABL0 & 2)) {                          // (the slots were reserved above, see there)
+    if (o.tref) {                          // (the slots were reserved above, see there)
 #pragma unroll
         for (int i = 0; i < kRefMax; ++i) {
             const int sl = wave_run_resolve(run[i]);
@@ -885,7 +873,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
         if (ref.cls == kClsNarrow && ref.n <= kRefMax) {
             for (int i = 0; i < kRefMax; ++i) if (i < ref.n) {
                 const int sl = ref.few.slot[i];
-                if (o.entries_a && sl < o.cap_a) { if (!(BFGX_ABL0 & 16)) o.entries_a[(int64_t)ref.few.tile[i] * o.cap_a + sl] = (int32_t)j; }
+                if (o.entries_a && sl < o.cap_a) o.entries_a[(int64_t)ref.few.tile[i] * o.cap_a + sl] = (int32_t)j;
                 else if (o.entries_a) { ref.few.slot[i] = -1; atomicAdd(o.cnt_b + ref.few.tile[i], 1); slow = true; }      // the tile's fixed list is full: region B
                 else slow = true;                                                                                         // (no direct placement: every halo is listed)
             }
@@ -1386,16 +1374,12 @@ __device__ inline bool pair_value_fast(const PairTable &tab, const PairHaloT<NC>
     const int i = max(0, min((int)u, tab.nr - 2));
     const double tr = u - (double)i, t0 = 1.0 - tr;
     double d = 0.0;
-#if BFGX_ABLATE == 1      // timing-only build: no table loads
-    d = tr * r.w[0] + t0 * r.w[1] + 1e-3;
-#else
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const double *row = tab.values + r.rowoff[c] + i;
         d = d + row[0] * (r.w[c] * t0);
         d = d + row[1] * (r.w[c] * tr);
     }
-#endif
     if (MODE == MODE_PAINT) {
         const double paint = fast_exp(d);                                                // Tabulate.py:286
         v[0] = paint;
@@ -1768,7 +1752,7 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
         if (lane < kChunk) L.ring[lane].prefix = incl_e - nrows;
         __builtin_amdgcn_wave_barrier();
 
-        for (int rb = 0; rb < (BFGX_ABLATE == 8 ? 0 : total_rows); rb += kWave) {
+        for (int rb = 0; rb < total_rows; rb += kWave) {
             // ---- lanes = ring rows (clipped to this tile)
             const int R = rb + lane;
             int firstA = 0, cntA = 0, firstB = 0, cntB = 0, nr = 1, ldsbase = 0, es = 0;
@@ -1833,7 +1817,7 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
                 const unsigned long long le = lt | (1ull << lane);
                 const bool fastok = pt.r_uniform != 0;
                 int base = 0;                                      // rows started before the current 64 pairs
-                for (int T0 = 0; T0 < (BFGX_ABLATE == 4 ? 0 : total); T0 += 2 * kWave) {
+                for (int T0 = 0; T0 < total; T0 += 2 * kWave) {
                     const unsigned long long mA = L.mask[T0 >> 6], mB = L.mask[(T0 >> 6) + 1];
                     const int tA = T0 + lane, tB = T0 + kWave + lane;
                     const bool actA = tA < total, actB = tB < total;
@@ -1856,11 +1840,8 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
                     double vA[3], vB[3];
                     bool okA, okB;
                     const bool small = (!actA || fabs(xA) <= 0.5) && (!actB || fabs(xB) <= 0.5);
-#if BFGX_ABLATE == 3 || BFGX_ABLATE == 6 || BFGX_ABLATE == 7     // timing-only build: no per-pair math at all
-                    if (true) { okA = okB = true; vA[0] = vA[1] = vA[2] = xA; vB[0] = vB[1] = vB[2] = xB; } else
-#endif
                     if (fastok && __all(small)) {
-                        if (MODE == MODE_OFFSETS && sizeof(ACC) == 4 && BFGX_PAIR32) {
+                        if (MODE == MODE_OFFSETS && sizeof(ACC) == 4) {
                             okA = pair_value_fast32<NC>(pt, hA, L.z[rowA], L.sth[rowA], xA, vA);
                             okB = pair_value_fast32<NC>(pt, hB, L.z[rowB], L.sth[rowB], xB, vB);
                         } else {
@@ -1881,13 +1862,6 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
                             else { okA = ok; vA[0] = vv[0]; vA[1] = vv[1]; vA[2] = vv[2]; }
                         }
                     }
-#if BFGX_ABLATE == 7      // timing-only: plain LDS stores instead of atomics
-                    if (actA && okA) { double *o = acc + NCOMP * (L.ldsbase[rowA] + kA); for (int cc = 0; cc < NCOMP; ++cc) o[cc] = vA[cc]; }
-                    if (actB && okB) { double *o = acc + NCOMP * (L.ldsbase[rowB] + kB); for (int cc = 0; cc < NCOMP; ++cc) o[cc] = vB[cc]; }
-#elif BFGX_ABLATE == 2 || BFGX_ABLATE == 6     // timing-only build: no LDS accumulation (keep the values alive)
-                    if (actA && okA && vA[0] == 1.2345e300) acc[0] = vA[1] + vA[2];
-                    if (actB && okB && vB[0] == 1.2345e300) acc[1] = vB[1] + vB[2];
-#else
                     if (actA && okA) {
                         double *o = acc + NCOMP * (L.ldsbase[rowA] + kA);
                         for (int cc = 0; cc < NCOMP; ++cc) atomicAdd(o + cc, vA[cc]);           // ds_add_f64
@@ -1896,7 +1870,6 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
                         double *o = acc + NCOMP * (L.ldsbase[rowB] + kB);
                         for (int cc = 0; cc < NCOMP; ++cc) atomicAdd(o + cc, vB[cc]);
                     }
-#endif
                 }
             }
             __builtin_amdgcn_wave_barrier();

@@ -186,15 +186,6 @@ struct RMathE {
 // The apron of a tile follows the data: tile_reach_kernel leaves the largest |o| of every tile, a tile takes the maximum m
 // over the tiles around it and evaluates R = regrid_reach_rings(m) rings and K columns beyond its own pixels -- 1 ring and
 // 4 columns (1.2x the evaluations) for sub-pixel displacements, more only where the map really moves that far.
-#ifndef BFGX_ABLK2
-#define BFGX_ABLK2 0                // timing-only ablation builds of the walking kernel (scripts/k2_variants.sh)
-#endif
-#ifndef BFGX_K2U
-#define BFGX_K2U 2
-#endif
-#ifndef BFGX_K2LEAN_U
-#define BFGX_K2LEAN_U 2          // window pixels per lane and trip of the lean / repair kernels
-#endif
 constexpr int kReachMax = 16;       // most rings a gathered deposit travels; the ring tables hold BR + 2 kReachMax + 2 rings
 constexpr int kReachColsMax = 256;  // most apron columns per side
 
@@ -496,15 +487,8 @@ __device__ inline bool regrid_gather_targets(const RegRow *rows, const RegRowC<r
 }
 
 // one source pixel by the generic route, its four deposits appended to the far list; returns the sum of the deposits.  (Out of line it costs
-// the walking kernel 23 spilled registers around the call and 3 % of its time, the lean kernel 20 %: inlined by default.)
-#ifndef BFGX_FAR_INLINE
-#define BFGX_FAR_INLINE 1
-#endif
-#if BFGX_FAR_INLINE
+// the walking kernel 23 spilled registers around the call and 3 % of its time, the lean kernel 20 %: inlined.)
 __device__ inline double regrid_far_pixel(
-#else
-__device__ __noinline__ double regrid_far_pixel(
-#endif
     const Hpx &h, const RegRow *rows, int LR, int rth0, int ti, int x, double o0, double o1, double o2,
                                                 double val, FarList far)
 {
@@ -537,11 +521,9 @@ __device__ __noinline__ double regrid_far_pixel(
 // global atomics; runs after the map has been stored, does nothing unless the list overflowed).
 // SPLIT (the parity-grade mode): pix_offsets are two fp32 arrays, offsets = hi and offsets_lo = (float)(o - hi), indexed alike; the scan decides on
 // hi alone (its thresholds are fp32 comparisons anyway), a survivor's low halves are fetched when it is evaluated -- in fp64 (real = double)
+constexpr int kK2Occ = 4;         // waves per SIMD the regrid kernels are compiled for.  Measured, config 2 / S19 table (K2 in ms): 3: 0.240 / 0.514, 4: 0.201 / 0.354, 5: 0.228 / 0.412, 6: 0.261
 template <typename ACC, typename real, int PASS, bool SPLIT = false>
-#ifndef BFGX_K2_OCC
-#define BFGX_K2_OCC 4             // waves per SIMD the regrid kernels are compiled for.  Measured, config 2 / S19 table (K2 in ms): 3: 0.240 / 0.514, 4: 0.201 / 0.354, 5: 0.228 / 0.412, 6: 0.261
-#endif
-__global__ void __launch_bounds__(256, BFGX_K2_OCC)
+__global__ void __launch_bounds__(256, kK2Occ)
 tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const ACC *__restrict__ offsets, const ACC *__restrict__ offsets_lo,
                     double *__restrict__ map_out, FarList far, ReachArgs reach, double *__restrict__ tile_sums, int tile_off, int ntiles,
                     int *__restrict__ todo, double *__restrict__ sums_out, int *__restrict__ lean_reset = nullptr)
@@ -642,13 +624,12 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             int64_t st, nr64; bool shf_;
             ring_info_small(h, ring, st, nr64, shf_);
             ring_z_sth(h, ring, rw.z, rw.sth);
-            rw.theta = (BFGX_ABLK2 == 5) ? kHalfPi - rw.z : atan2_generic(rw.sth, rw.z);        // (5: timing only -- what the tables' trigonometry costs)
+            rw.theta = atan2_generic(rw.sth, rw.z);
             rw.start = st; rw.nr = (int)nr64; rw.shf = shf_ ? 1 : 0;
             rw.dphi = kTwoPi / (double)rw.nr;
             rw.inv_dphi = (double)rw.nr * kInvTwoPi;
             rw.ks = tile_ks(tj, rw.nr, nphi);
             rw.ke = tile_ks(tj + 1, rw.nr, nphi);
-            if (BFGX_ABLK2 == 5) { rw.s0 = 0.0; rw.c0 = 1.0; } else
             sincos_bounded(((double)rw.ks + (shf_ ? 0.5 : 0.0)) * rw.dphi, rw.s0, rw.c0);
             // gathered <=> |o|^2 < lim2
             const double lim = fmin(fmin(reach.cap, 0.09 * rw.sth), 0.999 * fmin(rw.theta - reach.theta_first, reach.theta_last - rw.theta));
@@ -728,7 +709,7 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
                 int k = rw.ks + x;
                 if (k < 0) k += rw.nr;
                 if (k >= rw.nr) k -= rw.nr;
-                const int64_t p = (BFGX_ABLK2 == 4) ? (int64_t)((rw.start + k) & 4095) : rw.start + k;      // (4: every tile reads the same 4096 pixels -- what the loads' latency costs)
+                const int64_t p = rw.start + k;
                 sx.own = (r >= R) && (r < R + (i1 - i0)) && (x >= 0) && (x < span);
                 if (PASS != 1 || sx.own) {
                     sx.ok = true; sx.ti = r + 1; sx.x = x;
@@ -765,7 +746,6 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
         auto deposit = [&](int ti, int x, QT q0, QT q1, QT q2, double val) {
             int tt[4], tk[4];
             real w[4];
-            if (BFGX_ABLK2 == 1) return;
             real o0 = (real)q0, o1 = (real)q1, o2 = (real)q2;
             if (SPLIT) {                                                       // the low halves of this survivor (its pixel from the ring table)
                 const RegRow &rs_ = rows[ti];
@@ -803,9 +783,9 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
         int32_t *fq = farq + wid * kWalkQ;
         int fn = 0;                                                            // entries in this wave's queue of generic-route pixels
         int qn = 0;                                                            // entries in this wave's queue (wave-uniform)
-        constexpr int U = BFGX_K2U;                                                   // window pixels per lane and trip: 2 U loads in flight
+        constexpr int U = 2;                                                          // window pixels per lane and trip: 2 U loads in flight
         const int64_t pdummy = rows[R + 1].start + rows[R + 1].ks;             // (a pixel this tile may read, for the lanes without one)
-        for (int base = wid * kWave; base < (BFGX_ABLK2 == 2 ? 0 : total); base += 256 * U) {
+        for (int base = wid * kWave; base < total; base += 256 * U) {
             int cpos[U], cx[U], cspan[U];
             bool cin[U], cown[U];
             float cneed2[U], ccf2[U], clim2[U];
@@ -914,15 +894,12 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             }
         }
     };
-    if (BFGX_K2LEAN_U == 2) {
-        // two window pixels per lane and trip: the four loads are in flight before either pixel is evaluated
-        for (int idx = tid; idx < (BFGX_ABLK2 == 3 ? 0 : NR * LWs); idx += 512) {
-            const Src a = fetch(idx), b = fetch(idx + 256);
-            handle(a);
-            handle(b);
-        }
-    } else
-        for (int idx = tid; idx < NR * LWs; idx += 256) handle(fetch(idx));
+    // two window pixels per lane and trip: the four loads are in flight before either pixel is evaluated
+    for (int idx = tid; idx < NR * LWs; idx += 512) {
+        const Src a = fetch(idx), b = fetch(idx + 256);
+        handle(a);
+        handle(b);
+    }
     }
     if (PASS == 1) continue;
     __syncthreads();

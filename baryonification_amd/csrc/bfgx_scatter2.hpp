@@ -26,14 +26,8 @@
 
 namespace bfgx {
 
-#ifndef BFGX_ABL2
-#define BFGX_ABL2 0               // >0: timing-only ablation builds (scripts/ablate2.sh); never shipped
-#endif
 constexpr int kW2 = 8;            // waves per workgroup
-#ifndef BFGX_CHUNK2
-#define BFGX_CHUNK2 16
-#endif
-constexpr int kChunk2 = BFGX_CHUNK2;   // entries a wave takes at a time (8 / 12 / 20 measured: 0.486 / 0.466 / see DESIGN section 4)
+constexpr int kChunk2 = 16;       // entries a wave takes at a time (8 / 12 / 20 measured: 0.486 / 0.466 / see DESIGN section 4)
 constexpr int kPlanePad = 11;     // doubles between accumulator planes: plane stride = 22 banks mod 64 (conflict-free flush)
 
 // ---------------------------------------------------------------------------------- pair-phase math per precision
@@ -148,10 +142,6 @@ template <typename real>
 struct alignas(16) RingC2 { real sth, zf, dphi, _pad; };      // sin / cos of the colatitude, 2 pi / nr
 
 struct EntC2 { int32_t hidx, prefix, ring_lo, fb; };      // one non-empty entry of the chunk (compacted)
-struct RowGeo { double z0, s0, xa, cosr, phi0; };          // what the ring-row phase needs of a halo's RowRec, staged per entry (BFGX_K1_GEO)
-#ifndef BFGX_K1_GEO
-#define BFGX_K1_GEO 0
-#endif
 
 // entries per chunk and row slots per pass, by the precision of the pair phase (LDS per wave: 2.9 KB fp32, 4.5 KB fp64 at 16 / 64)
 // (measured, fp64 pair math: sixteen waves per workgroup with chunks of 8 entries and 32 row slots -- what LDS then holds -- 0.739 ms against
@@ -164,9 +154,6 @@ struct Wave2Lds {
     unsigned long long mask[K1Cfg<real>::rowl + 4];      // bit t set <=> pair t is the first pair of a row (<= 64 rows x 64 pixels)
     EntC2 ent[K1Cfg<real>::chunk];
     unsigned long long emask[K1Cfg<real>::chunk];       // bit R set <=> row R of the chunk is the first row of an entry (<= 16 x 64 rows)
-#if BFGX_K1_GEO
-    RowGeo geo[K1Cfg<real>::chunk];
-#endif
 };
 
 template <typename real>
@@ -303,8 +290,7 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
     const real tr_ = uu - (real)i;
     const real *tp = tb.v + (unsigned)(ph.cell + i * 8);           // (cell >= 0: 32-bit offset from the uniform table base)
     real q[8];
-    if (BFGX_ABL2 == 6) { for (int k = 0; k < 8; ++k) q[k] = tr_ * (real)(k + 1); }
-    else if (sizeof(real) == 4) {
+    if (sizeof(real) == 4) {
         const float4 a0 = reinterpret_cast<const float4 *>(tp)[0], a1 = reinterpret_cast<const float4 *>(tp)[1];
         q[0] = a0.x; q[1] = a0.y; q[2] = a0.z; q[3] = a0.w; q[4] = a1.x; q[5] = a1.y; q[6] = a1.z; q[7] = a1.w;
     } else {
@@ -364,13 +350,10 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
     int nrows = 0;
     EntC2 en;
     en.hidx = 0; en.prefix = 0; en.ring_lo = 0; en.fb = 0;
-    RowGeo gg;
-    gg.z0 = gg.s0 = gg.xa = gg.cosr = gg.phi0 = 0.0;
     if (lane < ecnt) {
         const int ei = ebeg + lane * estride;            // (estride > 1: the chunk takes every estride-th entry of region A, see the fluid kernel)
         en.hidx = ei < na ? ea[ei] : eb[ei - na];
         const RowRec &rr = rowrecs[en.hidx];
-        if (BFGX_K1_GEO) { gg.z0 = rr.z0; gg.s0 = rr.s0; gg.xa = rr.xa; gg.cosr = rr.cosr; gg.phi0 = rr.phi0; }
         en.fb = rr.fb;
         if (en.fb & 1) nrows = 4;
         else {
@@ -389,9 +372,6 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
         if (nrows > 0) {
             const int slot = __popcll(nzE & lt);
             L.ent[slot] = en;
-#if BFGX_K1_GEO
-            L.geo[slot] = gg;
-#endif
             if (MODE != MODE_COUNT) L.pair[slot] = pairrecs[en.hidx];
             atomicOr(&L.emask[en.prefix >> 6], 1ull << (en.prefix & 63));
         }
@@ -404,7 +384,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
     auto rows_and_pairs = [&](auto wide_tag) __attribute__((always_inline)) {
     constexpr bool WIDE = decltype(wide_tag)::value;
     const int rowlanes = (nphi == 1 || WIDE) ? K1Cfg<real>::rowl / 2 : K1Cfg<real>::rowl;
-    for (int rb = 0; rb < (BFGX_ABL2 == 2 ? 0 : total_rows); rb += rowlanes) {
+    for (int rb = 0; rb < total_rows; rb += rowlanes) {
         // ---- lanes = ring rows (clipped to this tile)
         const int R = rb + lane;
         const bool rvalid = lane < rowlanes && R < total_rows;
@@ -420,11 +400,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
         double x0A = 0.0, x0B = 0.0, dzv = 0.0, dsv = 0.0;
         if (rvalid) {
             const int q = R - ep;
-#if BFGX_K1_GEO
-            const RowGeo rr = L.geo[es];                       // (staged by the entry phase: one global read per halo instead of one per ring row)
-#else
             const RowRec &rr = rowrecs[eh];
-#endif
             if (efb & 1) {
                 const int ring = fbrecs[eh].ring[q], fk = fbrecs[eh].k[q];
                 if (ring >= i0 && ring < i1) {
@@ -462,7 +438,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
         const int tot2 = __builtin_amdgcn_readlane(incl, kWave - 1);
         const int total = tot2 & 0xFFFF;
         npairs += (unsigned long long)total;
-        if (MODE == MODE_COUNT || total == 0 || BFGX_ABL2 == 3) continue;
+        if (MODE == MODE_COUNT || total == 0) continue;
         {
             // compact the runs into row slots and mark each run's first pair in a bit mask
             const int excl = incl - ((cA + cB) | (nrun << 16));
@@ -502,7 +478,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
                 base += __popcll(m);
                 rc_nx[u] = L.rows[(u * kWave + lane < total) ? row : 0];
             }
-            for (int T0 = 0; T0 < (BFGX_ABL2 == 4 ? 0 : total); T0 += NP * kWave) {
+            for (int T0 = 0; T0 < total; T0 += NP * kWave) {
                 PairEval<real> pv[NP];
                 RowC2<real> rc_cur[NP];
 #pragma unroll
@@ -540,8 +516,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
                 }
 #pragma unroll
                 for (int u = 0; u < NP; ++u) {
-                    if (BFGX_ABL2 == 5) { if (pv[u].ok && pv[u].v0 == (real)1.2345e30) acc[pv[u].la] = (double)(pv[u].v1 + pv[u].v2); }
-                    else if (pv[u].ok) {
+                    if (pv[u].ok) {
                         atomicAdd(acc + pv[u].la, (double)pv[u].v0);                         // ds_add_f64
                         if (MODE == MODE_OFFSETS) {
                             atomicAdd(acc + PL + pv[u].la, (double)pv[u].v1);
@@ -645,7 +620,7 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
     // large-NSIDE tile lists ~20 halos with hundreds of pixels each: in chunks of 16 entries two of the eight waves did all the
     // work).  One chunk per wave measured best (NSIDE 2048: K1 1.91 -> 1.56 ms, 8192: 56.8 -> 24.0 ms; 16 or 32 chunks per tile pack worse)
     const int csz = max(1, min(K1Cfg<real>::chunk, (ne + kW2 - 1) / kW2));
-    const int nchunks = (BFGX_ABL2 == 1) ? 0 : (ne + csz - 1) / csz;
+    const int nchunks = (ne + csz - 1) / csz;
     WaveLds &L = wl[wid];
     unsigned long long npairs = 0;
 
@@ -722,29 +697,13 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
 // ~155 VGPRs and 4.5 KB of LDS each: three per SIMD, against two for the barrier form (one 8-wave workgroup per CU: its LDS does not fit twice)
 // (measured, config 2: 16 waves x 1 pair per lane 0.387 ms; 16 x 2: 0.410; 12 x 2 -- 132 VGPRs --: 0.431; 12 x 1: 0.444.  More than 16 waves would be
 // a second workgroup per CU, which LDS does not hold.)
-#ifndef BFGX_K1F_WAVES32
-#define BFGX_K1F_WAVES32 16
-#endif
-#ifndef BFGX_K1F_CSZ
-#define BFGX_K1F_CSZ kChunk2      // entries per chunk of a long list (<= kChunk2).  Measured, config 2: 10 / 12 / 14 / 16 entries 0.421 / 0.406 / 0.393 / 0.387 ms;
-#endif                            // BFGX_CHUNK2 = 18 / 20 (5 KB more LDS: the last that fits): 0.387 / 0.387 (config 3: 1.002 -> 0.987)
-#ifndef BFGX_K1F_NP
-#define BFGX_K1F_NP 1
-#endif
-template <typename real> struct FluidWaves { static constexpr int n = sizeof(real) == 4 ? BFGX_K1F_WAVES32 : 12; };
-#ifndef BFGX_CHUNKB
-#define BFGX_CHUNKB 2
-#endif
-constexpr int kChunkB = BFGX_CHUNKB;  // entries per chunk of region B
-#ifndef BFGX_K1F_SLEEP
-#define BFGX_K1F_SLEEP 2              // s_sleep argument (x 64 clocks) of a wave that polls for its next tile slot
-#endif
-#ifndef BFGX_K1F_PROF
-#define BFGX_K1F_PROF 0              // 1: shader-clock accounting of the fluid kernel's waves (variant builds only: scripts/k1f_prof.py)
-#endif
-#if BFGX_K1F_PROF
-__device__ unsigned long long g_k1f_prof[8];       // wait for a slot, chunks, flush + refill, whole wave, flushes
-#endif
+constexpr int kK1fWaves32 = 16;
+constexpr int kK1fCsz = kChunk2;      // entries per chunk of a long list (<= kChunk2).  Measured, config 2: 10 / 12 / 14 / 16 entries 0.421 / 0.406 / 0.393 / 0.387 ms;
+                                      // kChunk2 = 18 / 20 (5 KB more LDS: the last that fits): 0.387 / 0.387 (config 3: 1.002 -> 0.987)
+constexpr int kK1fNP = 1;             // pairs per lane and trip of the fp32 pair phase
+template <typename real> struct FluidWaves { static constexpr int n = sizeof(real) == 4 ? kK1fWaves32 : 12; };
+constexpr int kChunkB = 2;            // entries per chunk of region B
+constexpr int kK1fSleep = 2;          // s_sleep argument (x 64 clocks) of a wave that polls for its next tile slot
 struct alignas(16) FluidSlot {
     int32_t seq;                      // sequence number (per workgroup) of the tile this slot holds; -1: none yet
     int32_t tile;                     // < 0: no tile left
@@ -760,9 +719,6 @@ struct alignas(16) FluidSlot {
     int32_t nx_tile, nx_i0, nx_i1;
     int32_t nx_nphi, nx_na, nx_ne, nx_pad;
     const int32_t *nx_ea, *nx_eb;
-#if BFGX_K1F_PROF
-    uint32_t pf_maxchunk, pf_pad[3];
-#endif
 };
 
 template <typename real>
@@ -888,7 +844,7 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             // Region B of the list (discs over more than kRefMax tiles: the large ones) goes out FIRST and in chunks of kChunkB entries, so that
             // the long items are not what the tile's waves finish on; then region A in chunks of csz.
             constexpr int kCh = K1Cfg<real>::chunk;
-            S.ne = S.nx_ne; S.csz = S.nx_na >= kCh * kWF / 2 ? min(BFGX_K1F_CSZ, kCh) : max(1, min(kCh, (S.nx_na + kWF - 1) / kWF));
+            S.ne = S.nx_ne; S.csz = S.nx_na >= kCh * kWF / 2 ? min(kK1fCsz, kCh) : max(1, min(kCh, (S.nx_na + kWF - 1) / kWF));
             // (painting: pairs are cheap, so a list of 128 - 384 entries is better cut into ~24 chunks than into 8 - 24 of sixteen entries --
             // config 3 lists 210 per tile: K3 1.058 -> 1.01 ms; the displacement kernel loses 2 % with the same rule)
             if (MODE == MODE_PAINT && S.nx_na >= kCh * kWF / 2 && S.nx_na < 24 * kCh) S.csz = max(1, min(kCh, (S.nx_na + 23) / 24));
@@ -905,9 +861,6 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
         const int nz = (int)(2 * plane_bytes / sizeof(double));
         for (int i = tid; i < nz; i += kWave * kWF) accz[i] = 0.0;
         if (tid < 2) { slots[tid].seq = -1; slots[tid].staged = -1; slots[tid].flushing = 0; slots[tid].fl_next = 1 << 30; slots[tid].fl_done = 0; slots[tid].om2 = 0u;
-#if BFGX_K1F_PROF
-            slots[tid].pf_maxchunk = 0u;
-#endif
         }
     }
     __syncthreads();
@@ -916,13 +869,6 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
     WaveLds &L = wl[wid];
     unsigned long long npairs = 0;
     bool ended = false;
-#if BFGX_K1F_PROF
-    unsigned long long pf_wait = 0, pf_chunk = 0, pf_flush = 0, pf_nfl = 0, pf_nchunk = 0, pf_maxsum = 0;
-    const unsigned long long pf_t0 = __builtin_readcyclecounter();
-#define PF_NOW() __builtin_readcyclecounter()
-#else
-#define PF_NOW() 0ull
-#endif
     // The flush of a slot, in groups of four rows handed out by an LDS counter: to the last wave out of the tile, and to every wave that
     // reaches the slot's NEXT tile while the flush is still going on (instead of sleeping).  A group: twelve LDS reads in flight (one pixel per
     // lane and row; W <= 64), the planes zeroed as they are read, four stores; the group's largest |offset|^2 goes to the slot.
@@ -989,8 +935,6 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
 
     for (int k = 0;; ++k) {
         const int s = k & 1;
-        const unsigned long long pf_a = PF_NOW();
-        (void)pf_a;
         FluidSlot &S = slots[s];
         // wait for the slot to hold tile k of this workgroup (it held tile k - 2 until the last wave out of that one had flushed it), and
         // help with that flush meanwhile
@@ -998,7 +942,7 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             int spins = 0;
             while (__hip_atomic_load(&S.seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != k) {
                 if (__hip_atomic_load(&S.flushing, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 1) flush_groups(s, ((k >> 1) & 1) ^ 1);
-                __builtin_amdgcn_s_sleep(BFGX_K1F_SLEEP);
+                __builtin_amdgcn_s_sleep(kK1fSleep);
                 if (++spins > (1 << 22)) {
                     if (lane == 0) atomicOr(err, 4);
                     return;
@@ -1008,18 +952,13 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
         // The workgroup's two slots are refilled by different waves, so the draws of tiles k and k + 1 may come in either order: a slot
         // without a tile is passed through like an empty tile (its successor may still hold one); two of them in a row end the
         // sequence, because the tile counter only grows and every later draw follows one of those two.
-        const unsigned long long pf_b = PF_NOW();
-        (void)pf_b;
-#if BFGX_K1F_PROF
-        pf_wait += pf_b - pf_a;
-#endif
         const int tile = __builtin_amdgcn_readfirstlane(S.tile);
         if (tile < 0 && ended) break;
         ended = tile < 0;
         const int i0 = __builtin_amdgcn_readfirstlane(S.i0), i1 = __builtin_amdgcn_readfirstlane(S.i1);
         const int nphi = __builtin_amdgcn_readfirstlane(S.nphi), na = __builtin_amdgcn_readfirstlane(S.na);
         const int ne = __builtin_amdgcn_readfirstlane(S.ne), nchb = __builtin_amdgcn_readfirstlane(S._pad);
-        const int nchunks = (BFGX_ABL2 == 1 || tile < 0) ? 0 : __builtin_amdgcn_readfirstlane(S.nchunks);
+        const int nchunks = (tile < 0) ? 0 : __builtin_amdgcn_readfirstlane(S.nchunks);
         const int32_t *ea = reinterpret_cast<const int32_t *>(wave_uniform64((unsigned long long)S.ea));
         const int32_t *eb = reinterpret_cast<const int32_t *>(wave_uniform64((unsigned long long)S.eb));
         double *acc = reinterpret_cast<double *>(smem + (size_t)s * plane_bytes);
@@ -1031,9 +970,6 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             if (lane == 0) c = atomicAdd(&S.next_chunk, 1);
             c = __builtin_amdgcn_readfirstlane(c);
             if (c >= nchunks) break;
-#if BFGX_K1F_PROF
-            const unsigned long long pf_c0 = PF_NOW();
-#endif
             // region A is dealt out INTERLEAVED: chunk j takes the entries j, j + n, j + 2 n, ... (n = the number of chunks), so that whatever
             // order the catalog came in -- heaviest halos first (a chunk of sixteen heavy ones: K1 + 7 %), patch by patch (sixteen
             // neighbours adding to the same pixels: + 2 %) -- every chunk is a sample of the whole list
@@ -1041,16 +977,9 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             const int ebeg = c < nchb ? na + c * kChunkB : c - nchb;
             const int ecnt = c < nchb ? min(kChunkB, ne - ebeg) : (na - ebeg + ncha - 1) / ncha;
             const int estride = c < nchb ? 1 : ncha;
-            k1_chunk<MODE, real, (sizeof(real) == 4 ? BFGX_K1F_NP : 1), PM>(tb, rowrecs, pairrecs, fbrecs, ea, eb, na, ebeg, ecnt, estride, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
+            k1_chunk<MODE, real, (sizeof(real) == 4 ? kK1fNP : 1), PM>(tb, rowrecs, pairrecs, fbrecs, ea, eb, na, ebeg, ecnt, estride, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
                                     lane, npairs);
-#if BFGX_K1F_PROF
-            if (lane == 0) { const unsigned d = (unsigned)(PF_NOW() - pf_c0); atomicMax(&S.pf_maxchunk, d); pf_nchunk += 1; }
-#endif
         }
-#if BFGX_K1F_PROF
-        const unsigned long long pf_c = PF_NOW();
-        pf_chunk += pf_c - pf_b;
-#endif
         // leave tile k; the last wave out starts the flush, takes part in it, and refills the slot when the last row group is done
         int prev = 0;
         if (lane == 0) prev = __hip_atomic_fetch_add(&S.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1068,9 +997,6 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             __hip_atomic_store(&S.om2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_store(&S.flushing, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-#if BFGX_K1F_PROF
-        if (lane == 0) { pf_maxsum += S.pf_maxchunk; S.pf_maxchunk = 0u; }
-#endif
         flush_groups(s, (k >> 1) & 1);
         {
             const int ngroups = (i1 - i0 + 3) >> 2;
@@ -1091,17 +1017,7 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
         }
         if (!promote(s, k + 2)) { if (lane == 0) atomicOr(err, 4); return; }
         stage_next(s, k + 4);
-#if BFGX_K1F_PROF
-        pf_flush += PF_NOW() - pf_c; pf_nfl += 1;
-#endif
     }
-#if BFGX_K1F_PROF
-    if (lane == 0) {
-        atomicAdd(&g_k1f_prof[0], pf_wait); atomicAdd(&g_k1f_prof[1], pf_chunk); atomicAdd(&g_k1f_prof[2], pf_flush);
-        atomicAdd(&g_k1f_prof[3], PF_NOW() - pf_t0); atomicAdd(&g_k1f_prof[4], pf_nfl); atomicAdd(&g_k1f_prof[5], 1ull);
-        atomicAdd(&g_k1f_prof[6], pf_nchunk); atomicAdd(&g_k1f_prof[7], pf_maxsum);
-    }
-#endif
 }
 
 }  // namespace bfgx

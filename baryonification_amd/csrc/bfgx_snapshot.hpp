@@ -281,19 +281,15 @@ __device__ inline double min_image(double dx, double L)
 // LDS accumulator -- with one thread per particle doing this inline a wave ran the read-out whenever ANY of its 64 unrelated
 // particles had a hit (~15 % lane utilisation, 0.9 of the kernel's 2.9 ms).  Phase 3 (lane = particle): displaced, re-wrapped
 // position, written once.
-#ifndef BFGX_SNAP_PPT
-#define BFGX_SNAP_PPT 1             // particles per thread and round.  2 / 4 keep that many look-up chains (occupancy bit -> cell start -> list
-#endif                              // entries) of a thread in flight together; measured (round 4): 2.15 / 2.99 / 2.34 ms for 1 / 2 / 4 -- the entry
+constexpr int kSnapPPT = 1;         // particles per thread and round.  2 / 4 keep that many look-up chains (occupancy bit -> cell start -> list
+                                    // entries) of a thread in flight together; measured (round 4): 2.15 / 2.99 / 2.34 ms for 1 / 2 / 4 -- the entry
                                     // records of the extra chains cost registers (126 -> 239 VGPRs at 4: two waves per SIMD), and waves hide this
                                     // kernel's latency better than chains do.  Capping the registers instead (launch bounds for 6 / 8 waves per
                                     // SIMD: 92 / 160 bytes of scratch per lane in the fp64 read-out) gave 3.1 / 3.7 ms.
-constexpr int kSnapPPT = BFGX_SNAP_PPT;
 constexpr int kSnapBlock = 256 * kSnapPPT;           // particles per workgroup and round
 constexpr int kSnapQueue = 768 * kSnapPPT;           // queued hits per round (3 per particle; more are done inline)
 
-#ifndef BFGX_SNAP_OCC
-#define BFGX_SNAP_OCC 4             // workgroups of 256 threads per SIMD group the kernel is compiled for (register budget 512 / (4 x this))
-#endif
+constexpr int kSnapOcc = 4;         // workgroups of 256 threads per SIMD group the kernel is compiled for (register budget 512 / (4 x this))
 // KEYS: where the deposit keys of the displaced particles go.  The workgroup then owns CHUNKS of kDepChunk consecutive particles -- the unit
 // deposit_split_kernel<1> works on -- and leaves each chunk's histogram of level-1 buckets in wg_hist[bucket][chunk], as deposit_keys_kernel does.
 struct SnapDepArgs {
@@ -305,7 +301,7 @@ struct SnapDepArgs {
 };
 
 template <int DIM, bool KEYS>
-__global__ void __launch_bounds__(256, BFGX_SNAP_OCC)
+__global__ void __launch_bounds__(256, kSnapOcc)
 snap_displace_kernel(PairTable pt, SnapGeom g, int64_t np, const double *px, const double *py,
                      const double *pz, const SnapHaloRec *__restrict__ recs, const uint32_t *__restrict__ bitmap,
                      const int32_t *__restrict__ cell_start, const SnapEntry *__restrict__ entries, double *ox, double *oy, double *oz,
