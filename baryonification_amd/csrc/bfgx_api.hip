@@ -43,6 +43,7 @@ template <typename T> static inline hipError_t bfgx_counted_malloc(T **p, size_t
 #include "bfgx_snapshot_pairs.hpp"
 #include "bfgx_grid_gather.hpp"
 #include "bfgx_fftlog.hpp"
+#include "bfgx_sht.hpp"
 
 using namespace bfgx;
 
@@ -2398,3 +2399,6 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 #include "bfgx_callable_api.inc"
 #include "bfgx_grid_pairs_api.inc"
 #include "bfgx_snapshot_pairs_api.inc"
+
+// spherical-harmonic transforms of HEALPix shells (map2alm / alm2map / alm2cl / anafast)
+#include "bfgx_sht_api.inc"

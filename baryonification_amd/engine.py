@@ -446,3 +446,120 @@ class SnapshotPlan(object):
                                                                     C.c_void_p(int(part_ptrs[1])), z_in, C.c_void_p(int(mass_ptr) or None),
                                                                     int(n_grid), C.c_void_p(int(edges_ptr)), C.c_void_p(int(map_out_ptr)), C.byref(n)))
         return int(n.value)
+
+
+# ---------------------------------------------------------------------------------------------- spherical-harmonic transforms
+def sht_alm_size(lmax, mmax):
+    """complex coefficients of healpy's alm layout: index m (2 lmax + 1 - m) / 2 + l, 0 <= m <= mmax, m <= l <= lmax"""
+    return (mmax + 1) * (2 * lmax + 2 - mmax) // 2
+
+
+def sht_work_doubles(nside, lmax, mmax):
+    """doubles of the transform workspace (ring geometry, Bluestein kernels, lambda_mm prefactors, F_m per ring, one scratch map)"""
+    n = int(_lib.load().bfgx_sht_work_doubles(int(nside), int(lmax), int(mmax)))
+    if n < 0:
+        raise ValueError(_lib.load().bfgx_last_error().decode('utf-8', 'replace'))
+    return n
+
+
+class ShtPlan(object):
+    """Resident spherical-harmonic transforms of one shape (nside, lmax, mmax) on one device: the workspace (ring geometry,
+    Bluestein kernels of the ring FFTs, recurrence prefactors, per-ring F_m and a scratch map) is allocated and filled once;
+    the transforms below then allocate only their outputs (or nothing, with out=)."""
+
+    def __init__(self, nside, lmax, mmax, device=0):
+        import torch
+        self.nside, self.lmax, self.mmax, self.device = int(nside), int(lmax), int(mmax), int(device)
+        self.npix = 12 * self.nside * self.nside
+        self.nalm = sht_alm_size(self.lmax, self.mmax)
+        nw = sht_work_doubles(self.nside, self.lmax, self.mmax)
+        L = _lib.load()
+        if L.bfgx_device_count() <= 0:
+            raise _lib.BfgxError("bfgx: no HIP device visible: libbfgx has no CPU fallback")
+        self.dev = torch.device('cuda', self.device)
+        self.work = torch.empty(nw, dtype=torch.float64, device=self.dev)
+        _lib.check(L.bfgx_sht_prepare_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, C.c_void_p(self.work.data_ptr())))
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream or None)
+
+    def map2alm_device(self, map_dev, iter=3, out=None):
+        """complex128 alm [nalm] of a float64 RING map [npix] on the device"""
+        import torch
+        alm = out if out is not None else torch.empty(self.nalm, dtype=torch.complex128, device=self.dev)
+        _lib.check(_lib.load().bfgx_sht_map2alm_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, int(iter),
+                                                      C.c_void_p(map_dev.data_ptr()), C.c_void_p(alm.data_ptr()),
+                                                      C.c_void_p(self.work.data_ptr())))
+        return alm
+
+    def alm2map_device(self, alm_dev, out=None):
+        """float64 RING map [npix] of complex128 alm [nalm] on the device"""
+        import torch
+        m = out if out is not None else torch.empty(self.npix, dtype=torch.float64, device=self.dev)
+        _lib.check(_lib.load().bfgx_sht_alm2map_device(self.device, self._stream(), self.nside, self.lmax, self.mmax,
+                                                      C.c_void_p(alm_dev.data_ptr()), C.c_void_p(m.data_ptr()),
+                                                      C.c_void_p(self.work.data_ptr())))
+        return m
+
+    def alm2cl_device(self, alm1_dev, alm2_dev=None, lmax_out=None, out=None):
+        """cl [lmax_out + 1] (auto- or cross-spectrum) of device alm"""
+        return alm2cl_device(alm1_dev, alm2_dev, self.lmax, self.mmax, lmax_out, out=out, device=self.device)
+
+
+def alm2cl_device(alm1_dev, alm2_dev, lmax, mmax, lmax_out=None, out=None, device=0):
+    import torch
+    lmax_out = int(lmax) if lmax_out is None else int(lmax_out)
+    cl = out if out is not None else torch.empty(lmax_out + 1, dtype=torch.float64, device=alm1_dev.device)
+    stream = torch.cuda.current_stream(alm1_dev.device).cuda_stream
+    _lib.check(_lib.load().bfgx_sht_alm2cl_device(int(device), C.c_void_p(stream or None), int(lmax), int(mmax), lmax_out,
+                                                 C.c_void_p(alm1_dev.data_ptr()),
+                                                 C.c_void_p(alm2_dev.data_ptr()) if alm2_dev is not None else None,
+                                                 C.c_void_p(cl.data_ptr())))
+    return cl
+
+
+_SHT_PLANS = {}
+
+
+def sht_plan(nside, lmax, mmax, device=0):
+    """the cached ShtPlan of a shape: a repeated call of the same shape allocates no new workspace"""
+    key = (int(nside), int(lmax), int(mmax), int(device))
+    p = _SHT_PLANS.get(key)
+    if p is None:
+        p = _SHT_PLANS[key] = ShtPlan(*key)
+    return p
+
+
+def sht_map2alm_host(map_, nside, lmax, mmax, iter, device=0):
+    """one-shot host entry (map and alm cross PCIe)"""
+    alm = np.empty(sht_alm_size(lmax, mmax), dtype=np.complex128)
+    _lib.check(_lib.load().bfgx_sht_map2alm(int(device), int(nside), int(lmax), int(mmax), int(iter), map_.ctypes.data, alm.ctypes.data))
+    return alm
+
+
+def sht_alm2map_host(alm, nside, lmax, mmax, device=0):
+    m = np.empty(12 * int(nside) ** 2)
+    a = np.ascontiguousarray(alm, dtype=np.complex128)
+    _lib.check(_lib.load().bfgx_sht_alm2map(int(device), int(nside), int(lmax), int(mmax), a.ctypes.data, m.ctypes.data))
+    return m
+
+
+def sht_alm2cl_host(alm1, alm2, lmax, mmax, lmax_out, device=0):
+    a = np.ascontiguousarray(alm1, dtype=np.complex128)
+    b = None if alm2 is None else np.ascontiguousarray(alm2, dtype=np.complex128)
+    cl = np.empty(int(lmax_out) + 1)
+    _lib.check(_lib.load().bfgx_sht_alm2cl(int(device), int(lmax), int(mmax), int(lmax_out), a.ctypes.data,
+                                          None if b is None else b.ctypes.data, cl.ctypes.data))
+    return cl
+
+
+def sht_anafast_host(map1, map2, nside, lmax, mmax, iter, want_alm=False, device=0):
+    cl = np.empty(int(lmax) + 1)
+    n = sht_alm_size(lmax, mmax)
+    a1 = np.empty(n, dtype=np.complex128) if want_alm else None
+    a2 = np.empty(n, dtype=np.complex128) if (want_alm and map2 is not None) else None
+    _lib.check(_lib.load().bfgx_sht_anafast(int(device), int(nside), int(lmax), int(mmax), int(iter), map1.ctypes.data,
+                                           None if map2 is None else map2.ctypes.data, cl.ctypes.data,
+                                           None if a1 is None else a1.ctypes.data, None if a2 is None else a2.ctypes.data))
+    return cl, a1, a2

@@ -606,6 +606,31 @@ int  bfgx_snapshot_pairs_apply(bfgx_pairs *h, int64_t j0, int64_t j1, const doub
 int  bfgx_snapshot_pairs_finish(bfgx_pairs *h, double *x_out, double *y_out, double *z_out, bfgx_stats *stats);
 void bfgx_snapshot_pairs_end(bfgx_pairs *h);
 
+/* ---- spherical-harmonic transforms of RING-ordered HEALPix maps (healpy.sphtfunc, spin 0, fp64) -------------------------
+ * alm are complex128 in healpy order, index m (2 lmax + 1 - m) / 2 + l for 0 <= m <= mmax, m <= l <= lmax, stored as
+ * interleaved (re, im) doubles.  1 <= nside <= 2048, 0 <= mmax <= lmax.  map2alm: alm = A(map), then `iter` times
+ * alm += A(map - S(alm)), A(m) = 4 pi / Npix sum_p m_p Y*_lm(p); pixels within healpy's mask_bad tolerance of UNSEEN count as 0.
+ * alm2map: map = sum_l a_l0 lambda_l0 + 2 Re sum_{m>0} a_lm lambda_lm e^{i m phi} (Im a_l0 ignored).
+ * alm2cl: cl[l] = (Re a_l0 b*_l0 + 2 sum_{m=1}^{min(l, mmax)} Re a_lm b*_lm) / (2l + 1) for l <= min(lmax, lmax_out), 0 beyond
+ * (alm2 NULL: auto-spectrum).
+ * Device entries: work_dev holds bfgx_sht_work_doubles(nside, lmax, mmax) doubles (16-byte aligned; -1 = invalid shape), filled once
+ * by bfgx_sht_prepare_device and reused by every transform of the same (nside, lmax, mmax); enqueue-only on hip_stream. */
+int64_t bfgx_sht_work_doubles(int32_t nside, int32_t lmax, int32_t mmax);
+int  bfgx_sht_prepare_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, double *work_dev);
+int  bfgx_sht_map2alm_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map_dev,
+                             double *alm_dev, double *work_dev);
+int  bfgx_sht_alm2map_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, const double *alm_dev,
+                             double *map_dev, double *work_dev);
+int  bfgx_sht_alm2cl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int32_t lmax_out, const double *alm1_dev,
+                            const double *alm2_dev, double *cl_dev);
+/* one-shot host entries (host arrays, PCIe included).  anafast: cl[lmax + 1]; alm1_out / alm2_out (optional) receive the alm */
+int  bfgx_sht_map2alm(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map_host, double *alm_host);
+int  bfgx_sht_alm2map(int device, int32_t nside, int32_t lmax, int32_t mmax, const double *alm_host, double *map_host);
+int  bfgx_sht_alm2cl(int device, int32_t lmax, int32_t mmax, int32_t lmax_out, const double *alm1_host, const double *alm2_host,
+                     double *cl_host);
+int  bfgx_sht_anafast(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map1_host,
+                      const double *map2_host, double *cl_host, double *alm1_out, double *alm2_out);
+
 #ifdef __cplusplus
 }
 #endif
