@@ -128,17 +128,11 @@ struct bfgx_plan {
     int32_t *regrid_todo = nullptr;  // [0] = count, then the tiles the lean gather kernel leaves to the one with the ring walk
     int32_t *regrid_lean = nullptr;  // [0] = count (zeroed by the regrid's last launch), then the tiles of the lean kernel (reach <= 1 ring)
     float *tile_omax = nullptr;      // largest |offset|^2 of every tile (K1's flush or tile_reach_kernel): the reach of the gathering regrid
-    bool omax_from_k1 = false;       // set while a fused offsets + regrid call is in flight
-    bool paint_pair_f32 = false;     // set while a paint call with acc_f64 = 2 is in flight: f32 pair math into the f64 map
     // precision of the displacement path when the caller leaves it to the plan (BFGX_ACC_AUTO): chosen at plan creation from how far the
     // TABLE can move a pixel (plan_pick_precision): fp32 pair math holds SURVEY 8(d)'s 1e-6 mean(map) while one halo moves a pixel by less
     // than kAutoDispPixels; beyond that the parity-grade mode (BFGX_ACC_PARITY), or fp64 throughout where the fast kernel cannot take the table
     int auto_acc = 0;
     double table_disp_pixels = 0.0;  // largest |d| a / D_A of the table within its model-side cut, in pixel sides of this plan's NSIDE
-    float *offsets_lo = nullptr;     // set while a BFGX_ACC_PARITY call is in flight: the low halves of the split pix_offsets
-    int k1_tile_lo = 0, k1_tile_n = -1;   // tiles K1 / K3 process (-1: the whole sphere); set by the *_bands_device entries
-    int k1_spread_tiles = -1;             // tiles the binned catalog is spread over when that is NOT the tile range of the launch (the one-shot paint entry bins
-                                          // the whole catalog once and launches K3 range by range: the density that picks the kernel's form is per sphere); -1: the launch's tiles
     int32_t *tile_apron = nullptr;   // [ntiles][2] rings / columns of apron (tile_apron_kernel)
     int band_reach = 1;              // banded regrid: rings of apron every rank uses (bfgx_plan_set_band_reach)
     int route_margin = 0;            // rings by which bfgx_disc_rings_device widens every halo's range (bfgx_plan_set_route_margin)
@@ -297,15 +291,58 @@ static int check_catalog(const bfgx_plan *p, const bfgx_catalog *c)
 
 static bool use_fast(const bfgx_plan *p) { return p->fast_ok && p->algo == 1; }
 
-// the precision a displacement call runs in: BFGX_ACC_AUTO -> what the plan chose from its table; BFGX_ACC_PARITY needs the fast tile kernel
-// (3-axis table, uniform ln r) with the wide discs in it and falls back to fp64 throughout (a superset of its accuracy) elsewhere
-static int resolve_acc(const bfgx_plan *p, int acc)
+// The precision and pix_offsets layout of one displacement call, settled once per entry by disp_mode, and the K1 / K2 instantiations it selects:
+//   F32    fp32 pair math, float [n][3]:   launch_tile_scatter<OFFSETS, float>,  tile_regrid3_kernel<float, float>
+//   F64    fp64 throughout, double [n][3]: launch_tile_scatter<OFFSETS, double>, tile_regrid3_kernel<double, double>
+//   SPLIT  parity-grade: fp64 pair records, float hi [n][3] then lo [n][3]: <OFFSETS, float> + TileLaunch::offsets_lo, <float, double, SPLIT>
+struct DispMode {
+    enum Kind { F32, F64, SPLIT } kind = F32;
+    bool fp64() const { return kind != F32; }                 // fp64 pair records from K0, fp64 geometry in the regrid
+    bool split() const { return kind == SPLIT; }
+    size_t pixel_bytes() const { return fp64() ? 24 : 12; }
+    float *lo(const void *offsets, int64_t n) const { return split() ? (float *)offsets + 3 * (size_t)n : nullptr; }   // of n pixels at `offsets`
+    int acc() const { return kind == F32 ? BFGX_ACC_F32 : kind == F64 ? BFGX_ACC_F64 : BFGX_ACC_PARITY; }
+};
+
+// BFGX_ACC_AUTO -> what the plan chose from its table; BFGX_ACC_PARITY needs the fast tile kernel (3-axis table, uniform ln r) with the wide
+// discs in it and falls back to fp64 throughout (a superset of its accuracy) elsewhere.  one_array: the caller's pix_offsets are ONE array
+// (the band entries, whose slices travel between ranks): the parity-grade mode is served by fp64 throughout there
+static int disp_mode(const bfgx_plan *p, int acc, bool one_array, DispMode &m)
 {
+    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
+    if (acc != BFGX_ACC_AUTO && acc != BFGX_ACC_F32 && acc != BFGX_ACC_F64 && acc != BFGX_ACC_PARITY)
+        return fail(BFGX_ERR_INVALID, "acc_f64 = %d: must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)", acc);
     if (acc == BFGX_ACC_AUTO) acc = p->auto_acc;
-    if (acc == BFGX_ACC_PARITY && !(use_fast(p) && p->k1_wide)) acc = BFGX_ACC_F64;
-    return acc;
+    const bool parity = acc == BFGX_ACC_PARITY && use_fast(p) && p->k1_wide;
+    m.kind = acc == BFGX_ACC_F32 ? DispMode::F32 : (parity && !one_array) ? DispMode::SPLIT : DispMode::F64;
+    return BFGX_OK;
 }
-static bool acc_valid(int acc) { return acc == BFGX_ACC_AUTO || acc == BFGX_ACC_F32 || acc == BFGX_ACC_F64 || acc == BFGX_ACC_PARITY; }
+
+// The precision of one painting call (acc_f64 0 / 1 / 2), settled once per entry by paint_mode: F32 float map, fp32 pair math; F64 double map,
+// fp64 throughout; MIXED fp32 pair math (K0 writes fp32 pair records), fp64 LDS accumulation and map -- F64 where the fast kernel cannot take the table
+struct PaintMode {
+    enum Kind { F32, F64, MIXED } kind = F64;
+    bool map_f64() const { return kind != F32; }              // K3 launch_tile_scatter<PAINT, double>, else <PAINT, float>
+    bool k0_f64() const { return kind == F64; }
+    bool pair_f32() const { return kind == MIXED; }
+};
+
+static int paint_mode(const bfgx_plan *p, int acc, PaintMode &m)
+{
+    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
+    if (acc < 0 || acc > 2) return fail(BFGX_ERR_INVALID, "acc_f64 must be 0, 1 or 2");
+    m.kind = acc == 0 ? PaintMode::F32 : (acc == 2 && use_fast(p)) ? PaintMode::MIXED : PaintMode::F64;
+    return BFGX_OK;
+}
+
+// what one K1 / K3 launch does beyond the plan's configuration; the defaults: the whole sphere, one output array
+struct TileLaunch {
+    float *offsets_lo = nullptr;     // SPLIT pix_offsets: the low halves, indexed like the high ones
+    bool paint_pair_f32 = false;     // PaintMode::MIXED
+    float *omax = nullptr;           // K1's flush stores the largest |offset|^2 of every tile here (p->tile_omax: the reach of the regrid)
+    int tile_lo = 0, tile_n = -1;    // tiles to process (-1: the whole sphere)
+    int spread_tiles = -1;           // tiles the binned catalog covers when not the launch's (the density that picks the fast kernel's form)
+};
 
 // K0.  bin: also reserve the halo's slots in the tile entry lists; f64: precision of the fast kernel's pair records;
 // rec_all: write the full HaloRec of every halo (halo-centric kernels), otherwise only of the wide ones
@@ -396,7 +433,7 @@ static int launch_scatter(bfgx_plan *p, int64_t n, ACC *out, int64_t *counts)
 }
 
 template <int MODE, typename ACC, int NC>
-static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, bool wide_only)
+static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, const TileLaunch &k, bool wide_only)
 {
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     const size_t lds = tile_lds_bytes<NC>(p->tiling.BR, p->tiling.W, NCOMP);
@@ -404,22 +441,20 @@ static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, bool wide_only)
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     KernelTimer kt(p, wide_only ? BFGX_K_WIDE : (MODE == MODE_OFFSETS ? BFGX_K_OFFSETS : (MODE == MODE_PAINT ? BFGX_K_PAINT : BFGX_K_COUNT)));
     // wide pass: a small fixed grid walks the list of tiles that have wide entries (usually empty or a few polar tiles)
-    const int grid = wide_only ? std::min(p->tiling.ntiles, 512) : (p->k1_tile_n < 0 ? p->tiling.ntiles : std::max(p->k1_tile_n, 1));
+    const int grid = wide_only ? std::min(p->tiling.ntiles, 512) : (k.tile_n < 0 ? p->tiling.ntiles : std::max(k.tile_n, 1));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * kWavesPerBlock), lds, p->stream,
                        make_pair_table(p->model.tab), p->hpx, p->tiling, (const HaloRec *)p->recs, (const RowSetX *)p->rowsx,
                        (const int32_t *)p->tile_start, (const int32_t *)p->entries, p->capacity, out, p->pair_total,
                        wide_only ? (const int32_t *)p->tile_zeros : (const int32_t *)nullptr,
                        wide_only ? (const int32_t *)p->tile_count_b : (const int32_t *)nullptr, wide_only ? 1 : 0,
-                       wide_only ? (const int32_t *)p->wide_tiles : (const int32_t *)nullptr,
-                       (MODE == MODE_OFFSETS && p->omax_from_k1) ? (unsigned int *)p->tile_omax : (unsigned int *)nullptr,
-                       p->k1_tile_lo, p->k1_tile_n);
+                       wide_only ? (const int32_t *)p->wide_tiles : (const int32_t *)nullptr, (unsigned int *)k.omax, k.tile_lo, k.tile_n);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
 
 // fast kernel over the narrow-halo region of every tile (stores the tile)
 template <int MODE, typename ACC, typename real, int PM = 0>
-static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
+static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC *out_lo = nullptr)
 {
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     constexpr int kNP = 1;          // pairs per lane per trip of the fast kernel's pair loop
@@ -433,7 +468,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
     // persistent grid: two 512-thread workgroups per CU (LDS and registers allow exactly that) draw tiles from a counter that the
     // binning step has reset (the sixth block of the counter array)
     unsigned int *tile_counter = (unsigned int *)(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1));
-    const int ntodo = p->k1_tile_n < 0 ? p->tiling.ntiles : std::max(p->k1_tile_n, 1);
+    const int ntodo = k.tile_n < 0 ? p->tiling.ntiles : std::max(k.tile_n, 1);
     KernelTimer kt(p, MODE == MODE_OFFSETS ? BFGX_K_OFFSETS : (MODE == MODE_PAINT ? BFGX_K_PAINT : BFGX_K_COUNT));
     int32_t *form = nullptr;               // non-NULL: both forms are launched and this device word says which one works
     if constexpr (MODE != MODE_COUNT) {
@@ -449,7 +484,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
         // per sphere the fluid form is taken outright; below, K0's per-workgroup sums of the halos' estimated pixels decide ON THE DEVICE
         // (k1_form_kernel) and both forms are launched -- the one not chosen returns at once (~5 us).
         const bool eligible = p->k1_fluid && ldsf <= (size_t)160 * 1024 && p->tiling.BR <= kWave && ntodo >= 2 * p->num_cus;
-        const int nspread = p->k1_spread_tiles > 0 ? p->k1_spread_tiles : ntodo;      // (the tiles the binned halos cover)
+        const int nspread = k.spread_tiles > 0 ? k.spread_tiles : ntodo;      // (the tiles the binned halos cover)
         const bool dense = (double)p->k1_nhalos * (double)p->tiling.ntiles >= 6.0e5 * (double)nspread;
         const bool forced = p->k1_fluid == 2 && ldsf <= (size_t)160 * 1024 && p->tiling.BR <= kWave;
         if (eligible && !dense && !forced && p->k0_work_est && p->k1_nhalos > 0) {
@@ -465,8 +500,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
                                (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
                                (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->tile_count_pad : p->tile_count), (const int32_t *)p->tile_count_b,
                                (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, tile_counter,
-                               (MODE == MODE_OFFSETS && p->omax_from_k1) ? (unsigned int *)p->tile_omax : (unsigned int *)nullptr,
-                               p->k1_tile_lo, p->k1_tile_n, p->overflow, (const int32_t *)form, 1);
+                               (unsigned int *)k.omax, k.tile_lo, k.tile_n, p->overflow, (const int32_t *)form, 1);
             HIP_TRY(hipGetLastError());
             if (!form) return BFGX_OK;
         }
@@ -476,38 +510,37 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, ACC *out_lo = nullptr)
                        (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
                        (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->tile_count_pad : p->tile_count), (const int32_t *)p->tile_count_b,
                        (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, p->pair_total, tile_counter,
-                       (MODE == MODE_OFFSETS && p->omax_from_k1) ? (unsigned int *)p->tile_omax : (unsigned int *)nullptr,
-                       p->k1_tile_lo, p->k1_tile_n, (const int32_t *)form, 0);
+                       (unsigned int *)k.omax, k.tile_lo, k.tile_n, (const int32_t *)form, 0);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
 
 // the tiled scatter: fast kernel for the narrow halos (if the table allows) + generic kernel for the rest
 template <int MODE, typename ACC>
-static int launch_tile_scatter(bfgx_plan *p, ACC *out)
+static int launch_tile_scatter(bfgx_plan *p, ACC *out, const TileLaunch &k)
 {
     if (use_fast(p)) {
         using real = typename std::conditional<sizeof(ACC) == 8, double, float>::type;
         if constexpr (MODE == MODE_OFFSETS && sizeof(ACC) == 4) {
             // BFGX_ACC_PARITY: fp64 pair math (K0 wrote fp64 pair records) with the parity-grade functions, pix_offsets as two fp32 arrays
-            if (p->offsets_lo) return launch_tile_scatter2<MODE, ACC, double, 1>(p, out, (ACC *)p->offsets_lo);
+            if (k.offsets_lo) return launch_tile_scatter2<MODE, ACC, double, 1>(p, out, k, (ACC *)k.offsets_lo);
         }
         if constexpr (MODE == MODE_PAINT && sizeof(ACC) == 8) {
             // acc_f64 = 2: the pair phase in fp32 (K0 wrote fp32 pair records), LDS accumulation and the stored map in fp64
-            if (p->paint_pair_f32) {
-                if (int rc = launch_tile_scatter2<MODE, ACC, float>(p, out)) return rc;
-                return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, true);
+            if (k.paint_pair_f32) {
+                if (int rc = launch_tile_scatter2<MODE, ACC, float>(p, out, k)) return rc;
+                return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, true);
             }
         }
-        if (int rc = launch_tile_scatter2<MODE, ACC, real>(p, out)) return rc;
-        return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, true);      // (k1_wide: K0 classed no halo as wide)
+        if (int rc = launch_tile_scatter2<MODE, ACC, real>(p, out, k)) return rc;
+        return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, true);      // (k1_wide: K0 classed no halo as wide)
     }
-    if (p->NC == 4) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, false);
-    if (MODE == MODE_COUNT) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, false);      // census never reads the rows
-    if (p->NC == 8) return launch_tile_scatter_nc<MODE, ACC, 8>(p, out, false);
-    if (p->NC == 16) return launch_tile_scatter_nc<MODE, ACC, 16>(p, out, false);
-    if (p->NC == 32) return launch_tile_scatter_nc<MODE, ACC, 32>(p, out, false);       // three / four property axes (Tabulate.py:524-561)
-    return launch_tile_scatter_nc<MODE, ACC, 64>(p, out, false);
+    if (p->NC == 4) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, false);
+    if (MODE == MODE_COUNT) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, false);      // census never reads the rows
+    if (p->NC == 8) return launch_tile_scatter_nc<MODE, ACC, 8>(p, out, k, false);
+    if (p->NC == 16) return launch_tile_scatter_nc<MODE, ACC, 16>(p, out, k, false);
+    if (p->NC == 32) return launch_tile_scatter_nc<MODE, ACC, 32>(p, out, k, false);       // three / four property axes (Tabulate.py:524-561)
+    return launch_tile_scatter_nc<MODE, ACC, 64>(p, out, k, false);
 }
 
 // blocking: if the entry list overflowed, grow it to the exact size and redo the fill pass
@@ -950,9 +983,9 @@ int bfgx_plan_status(bfgx_plan *p)
 
 int bfgx_plan_precision(bfgx_plan *p, int acc_requested, int32_t *acc_resolved, double *table_disp_pixels)
 {
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    if (!acc_valid(acc_requested)) return fail(BFGX_ERR_INVALID, "acc must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)");
-    if (acc_resolved) *acc_resolved = resolve_acc(p, acc_requested);
+    DispMode m;
+    if (int rc = disp_mode(p, acc_requested, false, m)) return rc;
+    if (acc_resolved) *acc_resolved = m.acc();
     if (table_disp_pixels) *table_disp_pixels = p->table_disp_pixels;
     return BFGX_OK;
 }
@@ -1021,15 +1054,11 @@ int bfgx_plan_set_band_reach(bfgx_plan *p, int32_t rings)
 
 // reset_far = false: the far-deposit list keeps what earlier calls have listed (the one-shot host entry regrids the sphere in several
 // band ranges while the map is still arriving, and applies one list at the end)
-// offsets_lo_dev != NULL: split pix_offsets (the parity-grade mode; the one-shot host entry), the low halves of the same pixels [olo, ohi);
-// otherwise acc_f64 says whether the one array is fp32 or fp64 (BFGX_ACC_PARITY / AUTO: as bfgx_offsets_bands_device resolves them)
+// m SPLIT (the fused band entry, the one-shot host entry): the low halves of the pixels [olo, ohi) follow their high halves
 static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const double *map_in_dev, const void *offsets_dev,
-                             int64_t olo, int64_t ohi, int acc_f64, double *out_slice_dev, double *sums_dev, bool reset_far,
-                             const float *offsets_lo_dev = nullptr, bool sums_later = false)
+                             int64_t olo, int64_t ohi, const DispMode &m, double *out_slice_dev, double *sums_dev, bool reset_far,
+                             bool sums_later = false)
 {
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (!acc_valid(acc_f64)) return fail(BFGX_ERR_INVALID, "acc_f64 out of range");
-    acc_f64 = offsets_lo_dev ? 0 : (resolve_acc(p, acc_f64) != BFGX_ACC_F32 ? 1 : 0);
     if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "banded regrid needs the tiled algorithm (algo 1)");
     int64_t need_lo = 0, need_hi = 0;
     if (int rc = bfgx_plan_band_apron(p, band0, band1, &need_lo, &need_hi)) return rc;
@@ -1050,8 +1079,8 @@ static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const d
     const int t0 = p->band_tile0_host[band0], t1 = p->band_tile0_host[band1];
     {
         KernelTimer kt(p, BFGX_K_REGRID);
-        const size_t lds = regrid3_lds_bytes(p->tiling.BR, p->tiling.W, (acc_f64 || offsets_lo_dev) ? sizeof(double) : sizeof(float), p->band_reach > 1,
-                                             offsets_lo_dev ? sizeof(float) : 0);
+        const size_t lds = regrid3_lds_bytes(p->tiling.BR, p->tiling.W, m.fp64() ? sizeof(double) : sizeof(float), p->band_reach > 1,
+                                             m.split() ? sizeof(float) : 0);
         // virtual bases: the kernel indexes every array by global pixel number
         double *out_base = out_slice_dev - p0;
         // every rank gathers with the same fixed reach (so that all of them classify a source pixel the same way)
@@ -1061,25 +1090,18 @@ static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const d
         double *ts = sums_dev ? p->tile_sums : nullptr;
         const dim3 grid(t1 - t0), blk(256);
         int *none = nullptr;
-        if (offsets_lo_dev) {
-            const float *o = (const float *)offsets_dev - 3 * olo, *ol = offsets_lo_dev - 3 * olo;
-            if (p->band_reach == 1)
-                hipLaunchKernelGGL((tile_regrid3_kernel<float, double, 0, true>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, ol, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-            else
-                hipLaunchKernelGGL((tile_regrid3_kernel<float, double, 2, true>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, ol, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-        } else if (acc_f64) {
-            const double *o = (const double *)offsets_dev - 3 * olo;
-            if (p->band_reach == 1)
-                hipLaunchKernelGGL((tile_regrid3_kernel<double, double, 0>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, (decltype(o))nullptr, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-            else
-                hipLaunchKernelGGL((tile_regrid3_kernel<double, double, 2>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, (decltype(o))nullptr, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-        } else {
-            const float *o = (const float *)offsets_dev - 3 * olo;
-            if (p->band_reach == 1)
-                hipLaunchKernelGGL((tile_regrid3_kernel<float, float, 0>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, (decltype(o))nullptr, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-            else
-                hipLaunchKernelGGL((tile_regrid3_kernel<float, float, 2>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, (decltype(o))nullptr, out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);
-        }
+#define BFGX_REGRID3(ACC, REAL, SPLIT, OL)                                                                                                     \
+        do {                                                                                                                                    \
+            const ACC *o = (const ACC *)offsets_dev - 3 * olo;                                                                                  \
+            if (p->band_reach == 1) hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 0, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
+                                                       out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);                      \
+            else hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 2, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
+                                    out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);                                         \
+        } while (0)
+        if (m.split()) BFGX_REGRID3(float, double, true, m.lo(offsets_dev, ohi - olo) - 3 * olo);
+        else if (m.fp64()) BFGX_REGRID3(double, double, false, (const double *)nullptr);
+        else BFGX_REGRID3(float, float, false, (const float *)nullptr);
+#undef BFGX_REGRID3
         HIP_TRY(hipGetLastError());
     }
     if (sums_dev && !sums_later) {             // (sums_later: the caller's next kernel adds the per-tile sums up)
@@ -1105,7 +1127,9 @@ int bfgx_plan_set_route_margin(bfgx_plan *p, int32_t rings)
 int bfgx_regrid_bands_device(bfgx_plan *p, int32_t band0, int32_t band1, const double *map_in_dev, const void *offsets_dev,
                              int64_t olo, int64_t ohi, int acc_f64, double *out_slice_dev, double *sums_dev)
 {
-    return regrid_bands_impl(p, band0, band1, map_in_dev, offsets_dev, olo, ohi, acc_f64, out_slice_dev, sums_dev, true);
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, true, m)) return rc;
+    return regrid_bands_impl(p, band0, band1, map_in_dev, offsets_dev, olo, ohi, m, out_slice_dev, sums_dev, true);
 }
 
 int bfgx_plan_far_apply_device(bfgx_plan *p, double *out_slice_dev, int64_t p0, int64_t p1, unsigned long long *foreign_dev)
@@ -1160,88 +1184,98 @@ int bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_overf
     return BFGX_OK;
 }
 
-int bfgx_offsets_device(bfgx_plan *p, const bfgx_catalog *cat, void *offsets_dev, int acc_f64)
+// the checks of a K0 + K1 / K3 entry: the catalog, the kind of table (paint: a profile table), the output pointer.  bands: a pass over the tiles
+// of bands [band0, band1) only; a rank that owns no band (more ranks than bands) passes the data pointer of an empty buffer, which is NULL
+static int check_scatter(const bfgx_plan *p, const bfgx_catalog *cat, const void *out, bool paint, bool bands = false, int32_t band0 = 0, int32_t band1 = 0)
 {
     if (int rc = check_catalog(p, cat)) return rc;
-    if (!offsets_dev) return fail(BFGX_ERR_INVALID, "offsets pointer is NULL");
-    if (p->model.tab.logv) return fail(BFGX_ERR_INVALID, "displacement read-out needs a table with log_values = 0");
-    if (!acc_valid(acc_f64)) return fail(BFGX_ERR_INVALID, "acc_f64 must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)");
-    acc_f64 = resolve_acc(p, acc_f64);
+    if (bands && p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "band-restricted passes need the tiled algorithm (algo 1)");
+    if (bands && (band0 < 0 || band1 > p->tiling.nbands || band0 > band1)) return fail(BFGX_ERR_INVALID, "band range out of bounds");
+    if ((p->model.tab.logv != 0) != paint) return fail(BFGX_ERR_INVALID, paint ? "profile painting needs a table with log_values = 1"
+                                                                               : "displacement read-out needs a table with log_values = 0");
+    if ((!bands || band0 < band1) && !out) return fail(BFGX_ERR_INVALID, paint ? "map pointer is NULL" : "offsets pointer is NULL");
+    return BFGX_OK;
+}
+
+// K0 ahead of K1 / K3: with the halo -> tile binning for the tiled algorithm (f64: fp64 pair records), the per-halo records otherwise
+static int launch_k0(bfgx_plan *p, const bfgx_catalog *cat, int fallback4, bool f64)
+{
     HIP_TRY(hipSetDevice(p->device));
-    if (p->algo == 1) {      // tile-owned: every element of offsets is overwritten, no zero-fill needed
-        if (int rc = launch_prep_and_bin(p, cat, 1, acc_f64 != 0)) return rc;
-        if (p->blocking_growth) if (int rc = ensure_entry_capacity(p, cat)) return rc;
-        if (acc_f64 == BFGX_ACC_PARITY) {      // (resolve_acc: the fast kernel takes this table) hi [npix][3], then lo [npix][3]
-            p->offsets_lo = (float *)offsets_dev + 3 * (size_t)p->hpx.npix;
-            const int rc = launch_tile_scatter<MODE_OFFSETS, float>(p, (float *)offsets_dev);
-            p->offsets_lo = nullptr;
-            return rc;
-        }
-        if (acc_f64) return launch_tile_scatter<MODE_OFFSETS, double>(p, (double *)offsets_dev);
-        return launch_tile_scatter<MODE_OFFSETS, float>(p, (float *)offsets_dev);
+    if (p->algo == 1) {
+        if (int rc = launch_prep_and_bin(p, cat, fallback4, f64)) return rc;
+        return p->blocking_growth ? ensure_entry_capacity(p, cat) : BFGX_OK;
     }
     if (p->NC != 4) return fail(BFGX_ERR_UNSUPPORTED, "tables with extra parameter axes need algo 1 (LDS tiles)");
-    if (int rc = launch_prep(p, cat, 1, false, false, true)) return rc;
-    if (acc_f64) return launch_scatter<MODE_OFFSETS, double>(p, cat->n, (double *)offsets_dev, nullptr);
+    return launch_prep(p, cat, fallback4, false, false, true);
+}
+
+// K1 into the pixels [p0, p1) of pix_offsets held at `slice` in m's layout (the kernels index pixels by global number: virtual bases)
+static int launch_offsets(bfgx_plan *p, const DispMode &m, void *slice, int64_t p0, int64_t p1, TileLaunch k1)
+{
+    if (m.split()) k1.offsets_lo = m.lo(slice, p1 - p0) - 3 * p0;
+    if (m.kind != DispMode::F64) return launch_tile_scatter<MODE_OFFSETS, float>(p, (float *)slice - 3 * p0, k1);
+    return launch_tile_scatter<MODE_OFFSETS, double>(p, (double *)slice - 3 * p0, k1);
+}
+
+// K0 + K1 into the whole sphere's pix_offsets
+static int offsets_impl(bfgx_plan *p, const bfgx_catalog *cat, void *offsets_dev, const DispMode &m, const TileLaunch &k1)
+{
+    if (int rc = check_scatter(p, cat, offsets_dev, false)) return rc;
+    if (int rc = launch_k0(p, cat, 1, m.fp64())) return rc;
+    if (p->algo == 1) return launch_offsets(p, m, offsets_dev, 0, p->hpx.npix, k1);      // (every element is stored: no zero-fill needed)
+    if (m.fp64()) return launch_scatter<MODE_OFFSETS, double>(p, cat->n, (double *)offsets_dev, nullptr);
     return launch_scatter<MODE_OFFSETS, float>(p, cat->n, (float *)offsets_dev, nullptr);
 }
 
-// K0 + K1 / K3 for the tiles of bands [band0, band1) only: out_slice_dev points at the first pixel of band0
-static int bands_scatter(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *out_slice_dev, int acc_f64, bool paint,
-                         float *lo_slice_dev = nullptr)
+int bfgx_offsets_device(bfgx_plan *p, const bfgx_catalog *cat, void *offsets_dev, int acc_f64)
 {
-    // lo_slice_dev (displacements only): the parity-grade mode -- out_slice_dev takes the fp32 high halves of pix_offsets, lo_slice_dev the low halves of the
-    // same pixels (a caller that keeps both on ONE device: nothing of them crosses a link)
-    if (int rc = check_catalog(p, cat)) return rc;
-    if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "band-restricted passes need the tiled algorithm (algo 1)");
-    if (band0 < 0 || band1 > p->tiling.nbands || band0 > band1) return fail(BFGX_ERR_INVALID, "band range out of bounds");
-    if ((p->model.tab.logv != 0) != paint) return fail(BFGX_ERR_INVALID, paint ? "profile painting needs a table with log_values = 1"
-                                                                               : "displacement read-out needs a table with log_values = 0");
-    // a rank that owns no band (more ranks than bands) passes the data pointer of an empty buffer, which is NULL: nothing to do
-    if (band0 == band1) return BFGX_OK;
-    if (!out_slice_dev) return fail(BFGX_ERR_INVALID, "output pointer is NULL");
-    HIP_TRY(hipSetDevice(p->device));
-    const int64_t p0 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0);
-    p->k1_tile_lo = p->band_tile0_host[band0];
-    p->k1_tile_n = p->band_tile0_host[band1] - p->k1_tile_lo;
-    struct Reset { bfgx_plan *p; ~Reset() { p->k1_tile_lo = 0; p->k1_tile_n = -1; } } reset{p};
-    const bool split = !paint && lo_slice_dev != nullptr && use_fast(p);
-    if (!paint) {        // ONE array of pix_offsets (what travels between ranks): the parity-grade mode is served by fp64 throughout there
-        if (!acc_valid(acc_f64)) return fail(BFGX_ERR_INVALID, "acc_f64 out of range");
-        acc_f64 = split ? 0 : (resolve_acc(p, acc_f64) != BFGX_ACC_F32 ? 1 : 0);
-    }
-    if (acc_f64 < 0 || acc_f64 > (paint ? 2 : 1)) return fail(BFGX_ERR_INVALID, "acc_f64 out of range");
-    const bool mixed = paint && acc_f64 == 2 && use_fast(p);
-    if (int rc = launch_prep_and_bin(p, cat, paint ? 0 : 1, (acc_f64 != 0 && !mixed) || split)) return rc;
-    if (p->blocking_growth) if (int rc = ensure_entry_capacity(p, cat)) return rc;
-    p->paint_pair_f32 = mixed;
-    struct ResetP { bfgx_plan *p; ~ResetP() { p->paint_pair_f32 = false; } } resetp{p};
-    // virtual base: the kernels index the output by global pixel number
-    if (paint) {
-        if (acc_f64) return launch_tile_scatter<MODE_PAINT, double>(p, (double *)out_slice_dev - p0);
-        return launch_tile_scatter<MODE_PAINT, float>(p, (float *)out_slice_dev - p0);
-    }
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
+    return offsets_impl(p, cat, offsets_dev, m, TileLaunch{});
+}
+
+// K0 + K1 for the bands [band0, band1) (band0 < band1) into pix_offsets from the first pixel of band0 (SPLIT: the low halves follow the high ones)
+static int offsets_bands(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *slice, const DispMode &m)
+{
+    TileLaunch k1;
+    k1.tile_lo = p->band_tile0_host[band0];
+    k1.tile_n = p->band_tile0_host[band1] - k1.tile_lo;
+    if (int rc = launch_k0(p, cat, 1, m.fp64())) return rc;
     // K1's flush leaves the largest |offset|^2 of every tile it stores (bfgx_bands_max_offset2_device reduces them: the reach of the
     // regrid then needs no second pass over the slice)
-    p->omax_from_k1 = true;
-    struct ResetO { bfgx_plan *p; ~ResetO() { p->omax_from_k1 = false; } } reseto{p};
-    if (split) {         // fp64 pair records + the parity-grade pair functions, high and low halves stored (launch_tile_scatter)
-        p->offsets_lo = lo_slice_dev - 3 * p0;
-        struct ResetL { bfgx_plan *p; ~ResetL() { p->offsets_lo = nullptr; } } resetl{p};
-        return launch_tile_scatter<MODE_OFFSETS, float>(p, (float *)out_slice_dev - 3 * p0);
-    }
-    if (acc_f64) return launch_tile_scatter<MODE_OFFSETS, double>(p, (double *)out_slice_dev - 3 * p0);
-    return launch_tile_scatter<MODE_OFFSETS, float>(p, (float *)out_slice_dev - 3 * p0);
+    k1.omax = p->tile_omax;
+    return launch_offsets(p, m, slice, ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0),
+                          ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band1), k1);
 }
 
 int bfgx_offsets_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *offsets_slice_dev, int acc_f64)
 {
-    return bands_scatter(p, cat, band0, band1, offsets_slice_dev, acc_f64, false);
+    if (int rc = check_scatter(p, cat, offsets_slice_dev, false, true, band0, band1)) return rc;
+    if (band0 == band1) return BFGX_OK;
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, true, m)) return rc;
+    return offsets_bands(p, cat, band0, band1, offsets_slice_dev, m);
+}
+
+// K3 into the map held at `slice` from pixel p0 on (virtual base: the kernels index the output by global pixel number)
+static int launch_paint(bfgx_plan *p, const PaintMode &m, void *slice, int64_t p0, TileLaunch k3)
+{
+    k3.paint_pair_f32 = m.pair_f32();
+    if (m.map_f64()) return launch_tile_scatter<MODE_PAINT, double>(p, (double *)slice - p0, k3);
+    return launch_tile_scatter<MODE_PAINT, float>(p, (float *)slice - p0, k3);
 }
 
 int bfgx_paint_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *map_slice_dev, int acc_f64)
 {
-    return bands_scatter(p, cat, band0, band1, map_slice_dev, acc_f64, true);
+    if (int rc = check_scatter(p, cat, map_slice_dev, true, true, band0, band1)) return rc;
+    if (band0 == band1) return BFGX_OK;
+    PaintMode m;
+    if (int rc = paint_mode(p, acc_f64, m)) return rc;
+    TileLaunch k3;
+    k3.tile_lo = p->band_tile0_host[band0];
+    k3.tile_n = p->band_tile0_host[band1] - k3.tile_lo;
+    if (int rc = launch_k0(p, cat, 0, m.k0_f64())) return rc;
+    return launch_paint(p, m, map_slice_dev, ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0), k3);
 }
 
 // One rank's share of a resident multi-GPU BaryonifyShell step after the routing, as ONE enqueue-only call (Parallelize.py:250-318 has one call
@@ -1255,17 +1289,17 @@ int bfgx_offsets_regrid_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int3
 {
     if (!p || !cat) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (B0 < 0 || B1 > p->tiling.nbands || B0 > b0 || b1 > B1 || b0 > b1) return fail(BFGX_ERR_INVALID, "band ranges must nest: [B0, B1) around [b0, b1)");
-    if (!acc_valid(acc_f64)) return fail(BFGX_ERR_INVALID, "acc_f64 out of range");
+    // the parity-grade mode: both halves of pix_offsets stay on this device (24 bytes per pixel, as fp64 would take)
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
     const int64_t wlo = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * B0), whi = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * B1);
-    // the parity-grade mode: both halves of pix_offsets stay on this device (24 bytes per pixel, as fp64 would take): high halves
-    // [whi - wlo][3] fp32, then the low halves
-    float *lo = (resolve_acc(p, acc_f64) == BFGX_ACC_PARITY && use_fast(p) && offsets_dev) ? (float *)offsets_dev + 3 * (size_t)(whi - wlo) : nullptr;
-    if (int rc = bands_scatter(p, cat, B0, B1, offsets_dev, acc_f64, false, lo)) return rc;       // (its memset also zeroes the far list's counter)
+    if (int rc = check_scatter(p, cat, offsets_dev, false, true, B0, B1)) return rc;
+    if (B0 < B1) if (int rc = offsets_bands(p, cat, B0, B1, offsets_dev, m)) return rc;      // (its memset also zeroes the far list's counter)
     if (b0 == b1) {
         if (sums_dev) HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
         return BFGX_OK;
     }
-    if (int rc = regrid_bands_impl(p, b0, b1, map_in_dev, offsets_dev, wlo, whi, acc_f64, out_slice_dev, sums_dev, false, lo, true)) return rc;
+    if (int rc = regrid_bands_impl(p, b0, b1, map_in_dev, offsets_dev, wlo, whi, m, out_slice_dev, sums_dev, false, true)) return rc;
     const int64_t p0 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * b0), p1 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * b1);
     const int t0 = p->band_tile0_host[b0], t1 = p->band_tile0_host[b1];
     hipLaunchKernelGGL(regrid_far_local_kernel, dim3(64), dim3(256), 0, p->stream, p->far, out_slice_dev, p0, p1, foreign_dev, t1 - t0,
@@ -1293,11 +1327,13 @@ int bfgx_max_offset2_device(bfgx_plan *p, const void *offsets_dev, int64_t npixe
 {
     if (!p || !out_dev || (npixels > 0 && !offsets_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (npixels < 0) return fail(BFGX_ERR_INVALID, "npixels < 0");
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, true, m)) return rc;       // (the band entries' one array: BFGX_ACC_PARITY is read as fp64)
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipMemsetAsync(out_dev, 0, sizeof(float), p->stream));
     if (npixels > 0) {
         const unsigned grid = (unsigned)std::min<int64_t>((npixels + 255) / 256, 1024);
-        if (acc_valid(acc_f64) && resolve_acc(p, acc_f64) != BFGX_ACC_F32) hipLaunchKernelGGL(max_offset_kernel<double>, dim3(grid), dim3(256), 0, p->stream, npixels, (const double *)offsets_dev, (unsigned *)out_dev);
+        if (m.fp64()) hipLaunchKernelGGL(max_offset_kernel<double>, dim3(grid), dim3(256), 0, p->stream, npixels, (const double *)offsets_dev, (unsigned *)out_dev);
         else hipLaunchKernelGGL(max_offset_kernel<float>, dim3(grid), dim3(256), 0, p->stream, npixels, (const float *)offsets_dev, (unsigned *)out_dev);
         HIP_TRY(hipGetLastError());
     }
@@ -1452,26 +1488,21 @@ int bfgx_disc_rings_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t *rings
     return BFGX_OK;
 }
 
+// K0 + K3 over the whole sphere
+static int paint_impl(bfgx_plan *p, const bfgx_catalog *cat, void *map_out_dev, const PaintMode &m)
+{
+    if (int rc = check_scatter(p, cat, map_out_dev, true)) return rc;
+    if (int rc = launch_k0(p, cat, 0, m.k0_f64())) return rc;
+    if (p->algo == 1) return launch_paint(p, m, map_out_dev, 0, TileLaunch{});
+    if (m.map_f64()) return launch_scatter<MODE_PAINT, double>(p, cat->n, (double *)map_out_dev, nullptr);
+    return launch_scatter<MODE_PAINT, float>(p, cat->n, (float *)map_out_dev, nullptr);
+}
+
 int bfgx_paint_device(bfgx_plan *p, const bfgx_catalog *cat, void *map_out_dev, int acc_f64)
 {
-    if (int rc = check_catalog(p, cat)) return rc;
-    if (!map_out_dev) return fail(BFGX_ERR_INVALID, "map pointer is NULL");
-    if (!p->model.tab.logv) return fail(BFGX_ERR_INVALID, "profile painting needs a table with log_values = 1");
-    HIP_TRY(hipSetDevice(p->device));
-    if (acc_f64 < 0 || acc_f64 > 2) return fail(BFGX_ERR_INVALID, "acc_f64 must be 0, 1 or 2");
-    if (p->algo == 1) {
-        const bool mixed = acc_f64 == 2 && use_fast(p);          // (tables the fast kernel cannot take: fp64 throughout)
-        if (int rc = launch_prep_and_bin(p, cat, 0, acc_f64 != 0 && !mixed)) return rc;
-        if (p->blocking_growth) if (int rc = ensure_entry_capacity(p, cat)) return rc;
-        p->paint_pair_f32 = mixed;
-        struct Reset { bfgx_plan *p; ~Reset() { p->paint_pair_f32 = false; } } reset{p};
-        if (acc_f64) return launch_tile_scatter<MODE_PAINT, double>(p, (double *)map_out_dev);
-        return launch_tile_scatter<MODE_PAINT, float>(p, (float *)map_out_dev);
-    }
-    if (p->NC != 4) return fail(BFGX_ERR_UNSUPPORTED, "tables with extra parameter axes need algo 1 (LDS tiles)");
-    if (int rc = launch_prep(p, cat, 0, false, false, true)) return rc;
-    if (acc_f64) return launch_scatter<MODE_PAINT, double>(p, cat->n, (double *)map_out_dev, nullptr);
-    return launch_scatter<MODE_PAINT, float>(p, cat->n, (float *)map_out_dev, nullptr);
+    PaintMode m;
+    if (int rc = paint_mode(p, acc_f64, m)) return rc;
+    return paint_impl(p, cat, map_out_dev, m);
 }
 
 }  // extern "C"
@@ -1511,12 +1542,9 @@ namespace { void dep_release_all(); void fft_release_all(); void gcache_release_
 
 extern "C" {
 
-static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offsets_dev, int acc_f64, double *map_out_dev, double *sums_dev,
+static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offsets_dev, const DispMode &m, double *map_out_dev, double *sums_dev,
                        bool from_k1)
 {
-    if (!p || !map_in_dev || !offsets_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (!acc_valid(acc_f64)) return fail(BFGX_ERR_INVALID, "acc_f64 must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)");
-    acc_f64 = resolve_acc(p, acc_f64);
     HIP_TRY(hipSetDevice(p->device));
     {
     KernelTimer kt(p, BFGX_K_REGRID);
@@ -1526,14 +1554,14 @@ static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offse
         // entries, overflow, tiles left to the walking kernel (the fused call's binning step has zeroed them with its counters)
         if (!from_k1) HIP_TRY(hipMemsetAsync(p->far.count, 0, 4 * sizeof(int32_t), p->stream));
         double *ts = sums_dev ? p->tile_sums : nullptr;
-        if (acc_f64 == BFGX_ACC_PARITY)      // pix_offsets as two fp32 arrays (hi, then lo behind the npix high triples), fp64 geometry
-            launch_regrid_gather<float, double, true>(p, map_in_dev, (const float *)offsets_dev, (const float *)offsets_dev + 3 * (size_t)p->hpx.npix,
+        if (m.split())      // pix_offsets as two fp32 arrays (hi, then lo behind the npix high triples), fp64 geometry
+            launch_regrid_gather<float, double, true>(p, map_in_dev, (const float *)offsets_dev, m.lo(offsets_dev, p->hpx.npix),
                                                       map_out_dev, ts, from_k1, sums_dev);
-        else if (acc_f64) launch_regrid_gather<double, double>(p, map_in_dev, (const double *)offsets_dev, (const double *)nullptr, map_out_dev, ts, from_k1, sums_dev);
+        else if (m.fp64()) launch_regrid_gather<double, double>(p, map_in_dev, (const double *)offsets_dev, (const double *)nullptr, map_out_dev, ts, from_k1, sums_dev);
         else launch_regrid_gather<float, float>(p, map_in_dev, (const float *)offsets_dev, (const float *)nullptr, map_out_dev, ts, from_k1, sums_dev);
     } else {
         const unsigned grid = (unsigned)((p->hpx.npix + 255) / 256);
-        if (acc_f64)
+        if (m.fp64())
             hipLaunchKernelGGL(regrid_kernel<double>, dim3(grid), dim3(256), 0, p->stream, p->hpx, map_in_dev,
                                (const double *)offsets_dev, map_out_dev);
         else
@@ -1558,19 +1586,23 @@ static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offse
 int bfgx_regrid_device(bfgx_plan *p, const double *map_in_dev, const void *offsets_dev, int acc_f64,
                        double *map_out_dev, double *sums_dev)
 {
-    return regrid_impl(p, map_in_dev, offsets_dev, acc_f64, map_out_dev, sums_dev, false);
+    if (!p || !map_in_dev || !offsets_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
+    return regrid_impl(p, map_in_dev, offsets_dev, m, map_out_dev, sums_dev, false);
 }
 
 int bfgx_baryonify_device(bfgx_plan *p, const bfgx_catalog *cat, const double *map_in_dev, void *offsets_work_dev, int acc_f64,
                           double *map_out_dev, double *sums_dev)
 {
     if (!p || !map_in_dev || !offsets_work_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    DispMode m;
+    if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
+    TileLaunch k1;
     const bool fused = p->algo == 1;         // K1's flush leaves the largest |offset|^2 of every tile for the regrid's aprons
-    p->omax_from_k1 = fused;
-    const int rc = bfgx_offsets_device(p, cat, offsets_work_dev, acc_f64);
-    p->omax_from_k1 = false;
-    if (rc) return rc;
-    return regrid_impl(p, map_in_dev, offsets_work_dev, acc_f64, map_out_dev, sums_dev, fused);
+    if (fused) k1.omax = p->tile_omax;
+    if (int rc = offsets_impl(p, cat, offsets_work_dev, m, k1)) return rc;
+    return regrid_impl(p, map_in_dev, offsets_work_dev, m, map_out_dev, sums_dev, fused);
 }
 
 int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4, int64_t *counts_dev, int64_t *total_host)
@@ -1580,7 +1612,7 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
     if (p->algo == 1 && !counts_dev) {       // census through the tile path (checks the binning is complete)
         HIP_TRY(hipMemsetAsync(p->pair_total, 0, sizeof(unsigned long long), p->stream));
         if (int rc = launch_prep_and_bin(p, cat, fallback4, false)) return rc;
-        if (int rc = launch_tile_scatter<MODE_COUNT, float>(p, (float *)nullptr)) return rc;
+        if (int rc = launch_tile_scatter<MODE_COUNT, float>(p, (float *)nullptr, TileLaunch{})) return rc;
         unsigned long long tot = 0;
         HIP_TRY(hipMemcpyAsync(&tot, p->pair_total, sizeof(tot), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1695,11 +1727,10 @@ struct Timer {
 
 constexpr int kCatCols = 4 + BFGX_MAX_EXTRA + 2;       // M, z, ra, dec, extra[2], ln1pz, lnM
 
-int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], bfgx_catalog *d, std::vector<double> &hostlog)
+// the host columns of a catalog in upload order (M, z, ra, dec, extra[], ln1pz, lnM).  The (z, M) table coordinates are the caller's numpy
+// values when given, else libm on the host here (never the device's log: README.md:78-80 puts table edges exactly on the catalog's min/max)
+int catalog_columns(const bfgx_catalog *h, int nex, std::vector<double> &hostlog, const double *src[kCatCols])
 {
-    const int nex = p->model.tab.ndim - 3;
-    // the (z, M) table coordinates travel as columns: the caller's numpy values when given, else libm on the host here
-    // (never the device's log: README.md:78-80 puts table edges exactly on the catalog's min/max)
     const double *lnz = h->ln1pz, *lnm = h->lnM;
     if (h->n > 0 && (!lnz || !lnm)) {
         if (!h->M || !h->z) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
@@ -1712,23 +1743,36 @@ int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], b
         if (!lnz) lnz = hostlog.data();
         if (!lnm) lnm = hostlog.data() + h->n;
     }
-    const double *src[kCatCols];
     src[0] = h->M; src[1] = h->z; src[2] = h->ra; src[3] = h->dec;
     for (int k = 0; k < BFGX_MAX_EXTRA; ++k) src[4 + k] = k < nex ? h->extra[k] : nullptr;
     src[4 + BFGX_MAX_EXTRA] = lnz; src[5 + BFGX_MAX_EXTRA] = lnm;
+    for (int i = 0; i < kCatCols; ++i)
+        if ((i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA) && h->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
+    return BFGX_OK;
+}
+
+// the device catalog of n halos whose columns (upload order) are at col[]
+void catalog_view(int64_t n, int nex, const double *const col[kCatCols], bfgx_catalog *d)
+{
+    std::memset(d, 0, sizeof(*d));
+    d->n = n;
+    d->M = col[0]; d->z = col[1]; d->ra = col[2]; d->dec = col[3];
+    for (int k = 0; k < nex; ++k) d->extra[k] = col[4 + k];
+    d->ln1pz = col[4 + BFGX_MAX_EXTRA]; d->lnM = col[5 + BFGX_MAX_EXTRA];
+}
+
+int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], bfgx_catalog *d, std::vector<double> &hostlog)
+{
+    const int nex = p->model.tab.ndim - 3;
+    const double *src[kCatCols], *dp[kCatCols] = {};
+    if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
     for (int i = 0; i < kCatCols; ++i) {
-        const bool wanted = i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA;
-        if (!wanted) continue;
-        if (h->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
+        if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
         if (cols[i].alloc(sizeof(double) * (size_t)h->n)) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
         if (h->n > 0) HIP_TRY(hipMemcpyAsync(cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
+        dp[i] = (const double *)cols[i].p;
     }
-    std::memset(d, 0, sizeof(*d));
-    d->n = h->n;
-    d->M = (const double *)cols[0].p; d->z = (const double *)cols[1].p;
-    d->ra = (const double *)cols[2].p; d->dec = (const double *)cols[3].p;
-    for (int k = 0; k < nex; ++k) d->extra[k] = (const double *)cols[4 + k].p;
-    d->ln1pz = (const double *)cols[4 + BFGX_MAX_EXTRA].p; d->lnM = (const double *)cols[5 + BFGX_MAX_EXTRA].p;
+    catalog_view(h->n, nex, dp, d);
     return BFGX_OK;
 }
 
@@ -1875,38 +1919,86 @@ int upload_catalog_pooled(CacheEntry *e, const bfgx_catalog *h, bfgx_catalog *d,
     e->cat_token = 0;
     g_catalog_uploads.fetch_add(1);
     const int nex = p->model.tab.ndim - 3;
-    const double *lnz = h->ln1pz, *lnm = h->lnM;
-    if (h->n > 0 && (!lnz || !lnm)) {                        // see upload_catalog
-        if (!h->M || !h->z) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-        hostlog.resize(2 * (size_t)h->n);
-        for (int64_t i = 0; i < h->n; ++i) {
-            const double a = 1.0 / (1.0 + h->z[i]);
-            hostlog[i] = std::log(1.0 / a);
-            hostlog[(size_t)h->n + i] = std::log(h->M[i]);
-        }
-        if (!lnz) lnz = hostlog.data();
-        if (!lnm) lnm = hostlog.data() + h->n;
-    }
-    const double *src[kCatCols];
-    src[0] = h->M; src[1] = h->z; src[2] = h->ra; src[3] = h->dec;
-    for (int k = 0; k < BFGX_MAX_EXTRA; ++k) src[4 + k] = k < nex ? h->extra[k] : nullptr;
-    src[4 + BFGX_MAX_EXTRA] = lnz; src[5 + BFGX_MAX_EXTRA] = lnm;
-    const double *dp[kCatCols] = {};
+    const double *src[kCatCols], *dp[kCatCols] = {};
+    if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
     for (int i = 0; i < kCatCols; ++i) {
-        const bool wanted = i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA;
-        if (!wanted) continue;
-        if (h->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
+        if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
         if (e->cols[i].need(sizeof(double) * (size_t)std::max<int64_t>(h->n, 1))) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
         if (h->n > 0) HIP_TRY(hipMemcpyAsync(e->cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
         dp[i] = (const double *)e->cols[i].p;
     }
-    std::memset(d, 0, sizeof(*d));
-    d->n = h->n;
-    d->M = dp[0]; d->z = dp[1]; d->ra = dp[2]; d->dec = dp[3];
-    for (int k = 0; k < nex; ++k) d->extra[k] = dp[4 + k];
-    d->ln1pz = dp[4 + BFGX_MAX_EXTRA]; d->lnM = dp[5 + BFGX_MAX_EXTRA];
+    catalog_view(h->n, nex, dp, d);
     // (the copies above are from pageable memory: they have left the host buffers when hipMemcpyAsync returns)
     e->cat_token = token; e->cat_n = h->n; e->cat_dev = *d;
+    return BFGX_OK;
+}
+
+// np.isclose(new_sum, old_sum): rtol 1e-5, atol 1e-8  (HealpixRunner.py:344-346)
+int check_mass(double sum_in, double sum_out)
+{
+    if (!(std::fabs(sum_out - sum_in) <= 1e-8 + 1e-5 * std::fabs(sum_in)))
+        return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sum_out, sum_in);
+    return BFGX_OK;
+}
+
+// the options of a one-shot entry; NULL: the defaults (each entry reads only its own fields)
+bfgx_opts shell_opts(const bfgx_opts *opts)
+{
+    bfgx_opts o{};
+    o.check_mass = 1; o.algo = 1; o.acc_offsets_f64 = BFGX_ACC_AUTO; o.acc_paint_f64 = 1;
+    if (opts) o = *opts;
+    return o;
+}
+
+// the start of a one-shot entry (g_cache_mu held): the cached plan for (device, nside, model) set to o.algo, its streams drained at exit
+int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const bfgx_opts &o, CacheEntry **e, DrainOnExit &drain)
+{
+    if (o.algo != 0 && o.algo != 1) return fail(BFGX_ERR_INVALID, "opts.algo must be 0 or 1");
+    if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
+    if (int rc = cache_acquire(o.device, nside, model, cat->n, e)) return rc;
+    bfgx_plan *p = (*e)->plan;
+    p->algo = o.algo;
+    HIP_TRY(hipSetDevice(p->device));
+    drain.s[0] = &p->stream; drain.s[1] = &(*e)->copy_stream; drain.s[2] = &(*e)->out_stream; drain.null_stream = (p->stream == nullptr);
+    return BFGX_OK;
+}
+
+// Large maps travel in band ranges (contiguous RING pixel ranges) of at least 16 MB (8 ranges of 12.6 MB: 4.0 ms per call, 6 of 16.8 MB: 3.3 ms),
+// at most kChunksMax.  BFGX_PIPE_CHUNKS sets the count (tests: small maps, staged: HostSpan), BFGX_NO_PIPELINE sends every call down one pass.
+constexpr int kChunksMax = 16;
+struct Chunks {
+    int n = 0;
+    bool piped = false, stage = false;
+    int cb[kChunksMax + 1] = {};     // first band of every range, then nbands
+    std::vector<int64_t> bfp;        // first pixel of every band, then npix
+};
+
+void chunk_plan(bfgx_plan *p, bool eligible, Chunks &c)
+{
+    const size_t npix = (size_t)p->hpx.npix;
+    c.n = (int)std::min<size_t>(kChunksMax, npix * sizeof(double) / ((size_t)16 << 20));
+    const char *ce = std::getenv("BFGX_PIPE_CHUNKS");
+    if (ce) c.n = std::max(2, std::min(kChunksMax, std::atoi(ce)));
+    c.stage = ce != nullptr;
+    c.piped = eligible && c.n >= 2 && p->tiling.nbands >= 2 * c.n && !std::getenv("BFGX_NO_PIPELINE");
+    if (!c.piped) return;
+    int nb = 0;
+    c.bfp.resize((size_t)p->tiling.nbands + 1);
+    (void)bfgx_plan_bands(p, &nb, c.bfp.data());
+    c.cb[0] = 0; c.cb[c.n] = nb;
+    for (int k = 1; k < c.n; ++k) {
+        const int64_t target = (int64_t)(npix * (size_t)k / c.n);
+        const int b = (int)(std::lower_bound(c.bfp.begin(), c.bfp.end(), target) - c.bfp.begin());
+        c.cb[k] = std::min(std::max(b, c.cb[k - 1] + 1), nb - (c.n - k));
+    }
+}
+
+// the second stream of a streamed call and at least n events in each per-range pool (kept with the cache entry)
+int pipe_setup(CacheEntry *e, int n)
+{
+    if (!e->out_stream) HIP_TRY(hipStreamCreateWithFlags(&e->out_stream, hipStreamNonBlocking));
+    for (auto *pool : {&e->ev_in, &e->ev_k2})
+        while ((int)pool->size() < n) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); pool->push_back(v); }
     return BFGX_OK;
 }
 
@@ -1952,28 +2044,17 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
                          const double *map_in, double *map_out, const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !map_in || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    bfgx_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.check_mass = 1;
-    o.algo = 1;
-    o.acc_offsets_f64 = BFGX_ACC_AUTO;
-    if (opts) o = *opts;
-    if (o.algo != 0 && o.algo != 1) return fail(BFGX_ERR_INVALID, "opts.algo must be 0 or 1");
-    if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
+    const bfgx_opts o = shell_opts(opts);
     std::lock_guard<std::mutex> lk(g_cache_mu);              // one one-shot call at a time (they share the cached plans)
-    CacheEntry *e = nullptr;
-    if (int rc = cache_acquire(o.device, nside, model, cat->n, &e)) return rc;
-    bfgx_plan *p = e->plan;
-    p->algo = o.algo;
-    HIP_TRY(hipSetDevice(p->device));
     DrainOnExit drain;
-    drain.s[0] = &p->stream; drain.s[1] = &e->copy_stream; drain.s[2] = &e->out_stream; drain.null_stream = (p->stream == nullptr);
+    CacheEntry *e = nullptr;
+    if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
+    bfgx_plan *p = e->plan;
 
     const size_t npix = (size_t)p->hpx.npix;
-    if (!acc_valid(o.acc_offsets_f64)) return fail(BFGX_ERR_INVALID, "opts.acc_offsets_f64 must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)");
-    const int acc = resolve_acc(p, o.acc_offsets_f64);       // (BFGX_ACC_AUTO: what the plan chose from the model's table)
-    const bool off_split = (acc == BFGX_ACC_PARITY);         // pix_offsets as two fp32 arrays: hi [npix][3], then lo [npix][3]
-    const size_t acc_bytes = npix * 3 * (acc != BFGX_ACC_F32 ? sizeof(double) : sizeof(float));
+    DispMode m;
+    if (int rc = disp_mode(p, o.acc_offsets_f64, false, m)) return rc;      // (BFGX_ACC_AUTO: what the plan chose from the model's table)
+    const size_t acc_bytes = npix * m.pixel_bytes();
     std::vector<double> hostlog;
     bfgx_catalog dcat;
     if (!e->copy_stream) {
@@ -1990,46 +2071,28 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         HIP_TRY(hipMemsetAsync(e->off.p, 0, acc_bytes, p->stream));
         HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
     }
-    p->omax_from_k1 = (o.algo == 1);                         // K1's flush leaves the largest |offset|^2 of every tile for K2's aprons
-    const int rc_off = bfgx_offsets_device(p, &dcat, e->off.p, acc);
-    p->omax_from_k1 = false;
-    if (rc_off) return rc_off;
+    TileLaunch k1;
+    if (o.algo == 1) k1.omax = p->tile_omax;                 // K1's flush leaves the largest |offset|^2 of every tile for K2's aprons
+    if (int rc = offsets_impl(p, &dcat, e->off.p, m, k1)) return rc;
     double sums[2] = {0, 0};
-    // Large maps travel in band ranges (contiguous RING pixel ranges): a range is regridded as soon as it and its apron have arrived
-    // and goes back to the host while the next ones are still coming in, so that the two directions of the link work at the same
-    // time.  The gathering regrid stores every pixel of a range exactly once; the few deposits it cannot gather (next to a pole) are
-    // listed and added on the host.
-    // Range size: copies below ~16 MB take a slower path here (8 ranges of 12.6 MB: 4.0 ms per call, 6 of 16.8 MB: 3.3 ms), so a map is cut
-    // into ranges of at least that, at most 16 of them; both host buffers are page-locked for the duration of the call (hipHostRegister:
-    // 2 us here) -- from pageable memory the copies in and out take turns on the host thread and the one-pass route below is faster
-    // (4.3 against 4.5 ms), which is also where a map goes that cannot be registered.
-    constexpr int kChunksMax = 16;
-    int kChunks = (int)std::min<size_t>(kChunksMax, npix * sizeof(double) / ((size_t)16 << 20));
-    if (const char *ce = std::getenv("BFGX_PIPE_CHUNKS")) kChunks = std::max(2, std::min(kChunksMax, std::atoi(ce)));       // (tests: small maps)
-    bool piped = o.algo == 1 && kChunks >= 2 && p->tiling.nbands >= 2 * kChunks && !std::getenv("BFGX_NO_PIPELINE");
+    // Large maps travel in band ranges (chunk_plan): a range is regridded as soon as it and its apron have arrived and goes back to the
+    // host while the next ones are still coming in, so that the two directions of the link work at the same time.  The gathering regrid
+    // stores every pixel of a range exactly once; the few deposits it cannot gather (next to a pole) are listed and added on the host.
+    // Both host buffers are page-locked for the duration of the call (hipHostRegister: 2 us here) -- from pageable memory the copies in
+    // and out take turns on the host thread and the one-pass route below is faster (4.3 against 4.5 ms), which is also where a map goes
+    // that cannot be registered.
+    Chunks ch;
+    chunk_plan(p, o.algo == 1, ch);
+    const int kChunks = ch.n, *cb = ch.cb;
+    const std::vector<int64_t> &bfp = ch.bfp;
+    bool piped = ch.piped;
     bool whole_map_sent = false;
     HostSpan hin, hout;
     hin.streams[0] = hout.streams[0] = &e->copy_stream; hin.streams[1] = hout.streams[1] = &p->stream; hin.streams[2] = hout.streams[2] = &e->out_stream;
-    const bool stage_small = std::getenv("BFGX_PIPE_CHUNKS") != nullptr;
-    if (piped) piped = hin.open(map_in, npix * sizeof(double), false, stage_small) && hout.open(map_out, npix * sizeof(double), true, stage_small);
-    const double *const user_map_in = map_in;
-    double *const user_map_out = map_out;
-    (void)user_map_in; (void)user_map_out;
+    if (piped) piped = hin.open(map_in, npix * sizeof(double), false, ch.stage) && hout.open(map_out, npix * sizeof(double), true, ch.stage);
     if (piped) { map_in = (const double *)hin.use; map_out = (double *)hout.use; }       // (from here on: the page-locked views)
     if (piped) {
-        int nb = 0;
-        std::vector<int64_t> bfp((size_t)p->tiling.nbands + 1);
-        if (int rc = bfgx_plan_bands(p, &nb, bfp.data())) return rc;
-        int cb[kChunksMax + 1];
-        cb[0] = 0; cb[kChunks] = nb;
-        for (int c = 1; c < kChunks; ++c) {
-            const int64_t target = (int64_t)(npix * (size_t)c / kChunks);
-            int b = (int)(std::lower_bound(bfp.begin(), bfp.end(), target) - bfp.begin());
-            cb[c] = std::min(std::max(b, cb[c - 1] + 1), nb - (kChunks - c));
-        }
-        if (!e->out_stream) HIP_TRY(hipStreamCreateWithFlags(&e->out_stream, hipStreamNonBlocking));
-        while ((int)e->ev_in.size() < kChunks) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_in.push_back(v); }
-        while ((int)e->ev_k2.size() < kChunks) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_k2.push_back(v); }
+        if (int rc = pipe_setup(e, kChunks)) return rc;
         if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(sums) failed");
         double *dsums = (double *)e->sums.p;
         float *domax = (float *)(dsums + 2 * kChunks);
@@ -2043,7 +2106,7 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         if (int rc = send(1)) return rc;
         // how many rings a deposit travels: from the largest displacement K1 has seen (by now K1 has finished underneath the two copies)
         float m2 = 0.0f;
-        if (int rc = bfgx_bands_max_offset2_device(p, 0, nb, domax)) return rc;
+        if (int rc = bfgx_bands_max_offset2_device(p, 0, p->tiling.nbands, domax)) return rc;
         HIP_TRY(hipMemcpyAsync(&m2, domax, sizeof(float), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
         int32_t rings = kReachMax;
@@ -2064,9 +2127,8 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
                     if (need >= sent) break;
                     HIP_TRY(hipStreamWaitEvent(p->stream, e->ev_in[need], 0));
                     const int64_t lo = bfp[cb[next]], n = bfp[cb[next + 1]] - lo;
-                    if (int rc = regrid_bands_impl(p, cb[next], cb[next + 1], (const double *)e->in.p, e->off.p, 0, (int64_t)npix, acc,
-                                                   (double *)e->out.p + lo, dsums + 2 * next, next == 0,
-                                                   off_split ? (const float *)e->off.p + 3 * npix : nullptr)) return rc;
+                    if (int rc = regrid_bands_impl(p, cb[next], cb[next + 1], (const double *)e->in.p, e->off.p, 0, (int64_t)npix, m,
+                                                   (double *)e->out.p + lo, dsums + 2 * next, next == 0)) return rc;
                     HIP_TRY(hipEventRecord(e->ev_k2[next], p->stream));
                     HIP_TRY(hipStreamWaitEvent(e->out_stream, e->ev_k2[next], 0));
                     HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->out_stream));
@@ -2113,7 +2175,7 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         if (!whole_map_sent) HIP_TRY(hipMemcpyAsync(e->in.p, map_in, npix * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
         HIP_TRY(hipEventRecord(e->ev[1], e->copy_stream));
         HIP_TRY(hipStreamWaitEvent(p->stream, e->ev[1], 0));
-        if (int rc = regrid_impl(p, (const double *)e->in.p, e->off.p, acc, (double *)e->out.p, (double *)e->sums.p, o.algo == 1)) return rc;
+        if (int rc = regrid_impl(p, (const double *)e->in.p, e->off.p, m, (double *)e->out.p, (double *)e->sums.p, o.algo == 1)) return rc;
         HIP_TRY(hipEventRecord(e->ev[2], p->stream));
         HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipMemcpyAsync(sums, e->sums.p, sizeof(sums), hipMemcpyDeviceToHost, p->stream));
@@ -2134,32 +2196,21 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
         stats->n_pairs = -1;
     }
-    if (o.check_mass) {      // np.isclose(new_sum, old_sum): rtol 1e-5, atol 1e-8  (HealpixRunner.py:344-346)
-        if (!(std::fabs(sums[1] - sums[0]) <= 1e-8 + 1e-5 * std::fabs(sums[0])))
-            return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sums[1], sums[0]);
-    }
-    return BFGX_OK;
+    return o.check_mass ? check_mass(sums[0], sums[1]) : BFGX_OK;
 }
 
 int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside,
                      double *map_out, const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    bfgx_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.acc_paint_f64 = 1;
-    o.algo = 1;
-    if (opts) o = *opts;
-    if (o.algo != 0 && o.algo != 1) return fail(BFGX_ERR_INVALID, "opts.algo must be 0 or 1");
-    if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
+    const bfgx_opts o = shell_opts(opts);
     std::lock_guard<std::mutex> lk(g_cache_mu);
-    CacheEntry *e = nullptr;
-    if (int rc = cache_acquire(o.device, nside, model, cat->n, &e)) return rc;
-    bfgx_plan *p = e->plan;
-    p->algo = o.algo;
-    HIP_TRY(hipSetDevice(p->device));
     DrainOnExit drain;
-    drain.s[0] = &p->stream; drain.s[1] = &e->copy_stream; drain.s[2] = &e->out_stream; drain.null_stream = (p->stream == nullptr);
+    CacheEntry *e = nullptr;
+    if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
+    bfgx_plan *p = e->plan;
+    PaintMode m;
+    if (int rc = paint_mode(p, o.acc_paint_f64, m)) return rc;
 
     const size_t npix = (size_t)p->hpx.npix;
     std::vector<double> hostlog;
@@ -2170,67 +2221,50 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     if (e->out.need(npix * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
     const double ms_h2d = t.stop(p->stream);
     t.start(p->stream);
-    // Large fp64 maps are painted in band ranges, each copied back while the next ones are painted (as in bfgx_baryonify_shell: ranges of
-    // at least 16 MB, at most 16, map_out page-locked for the call); K0 runs once, K3 on the tiles of each range
-    constexpr int kChunksMax = 16;
-    int kChunks = (int)std::min<size_t>(kChunksMax, npix * sizeof(double) / ((size_t)16 << 20));
-    if (const char *ce = std::getenv("BFGX_PIPE_CHUNKS")) kChunks = std::max(2, std::min(kChunksMax, std::atoi(ce)));       // (tests: small maps)
-    bool piped = o.algo == 1 && o.acc_paint_f64 != 0 && kChunks >= 2 && p->tiling.nbands >= 2 * kChunks && !std::getenv("BFGX_NO_PIPELINE");
+    // Large fp64 maps are painted in band ranges (chunk_plan), each copied back while the next ones are painted (map_out page-locked for
+    // the call); K0 runs once, K3 on the tiles of each range
+    Chunks ch;
+    chunk_plan(p, o.algo == 1 && m.map_f64(), ch);
     HostSpan hout;
     hout.streams[0] = &p->stream; hout.streams[1] = &e->out_stream;
-    if (piped) piped = hout.open(map_out, npix * sizeof(double), true, std::getenv("BFGX_PIPE_CHUNKS") != nullptr);
-    if (piped) map_out = (double *)hout.use;                 // (from here on: the page-locked view)
+    if (ch.piped) ch.piped = hout.open(map_out, npix * sizeof(double), true, ch.stage);
+    if (ch.piped) map_out = (double *)hout.use;              // (from here on: the page-locked view)
     double ms_k = 0.0;
-    if (piped) {
-        if (int rc = check_catalog(p, &dcat)) return rc;
-        if (!p->model.tab.logv) return fail(BFGX_ERR_INVALID, "profile painting needs a table with log_values = 1");
-        if (o.acc_paint_f64 < 0 || o.acc_paint_f64 > 2) return fail(BFGX_ERR_INVALID, "acc_f64 must be 0, 1 or 2");
-        int nb = 0;
-        std::vector<int64_t> bfp((size_t)p->tiling.nbands + 1);
-        if (int rc = bfgx_plan_bands(p, &nb, bfp.data())) return rc;
-        int cb[kChunksMax + 1];
-        cb[0] = 0; cb[kChunks] = nb;
-        for (int c = 1; c < kChunks; ++c) {
-            const int64_t target = (int64_t)(npix * (size_t)c / kChunks);
-            const int b = (int)(std::lower_bound(bfp.begin(), bfp.end(), target) - bfp.begin());
-            cb[c] = std::min(std::max(b, cb[c - 1] + 1), nb - (kChunks - c));
-        }
-        if (!e->out_stream) HIP_TRY(hipStreamCreateWithFlags(&e->out_stream, hipStreamNonBlocking));
-        while ((int)e->ev_k2.size() < kChunks) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_k2.push_back(v); }
-        const bool mixed = o.acc_paint_f64 == 2 && use_fast(p);      // (tables the fast kernel cannot take: fp64 throughout)
-        if (int rc = launch_prep_and_bin(p, &dcat, 0, !mixed)) return rc;
-        if (p->blocking_growth) if (int rc = ensure_entry_capacity(p, &dcat)) return rc;
-        p->paint_pair_f32 = mixed;
-        struct Reset { bfgx_plan *p; ~Reset() { p->paint_pair_f32 = false; p->k1_tile_lo = 0; p->k1_tile_n = -1; p->k1_spread_tiles = -1; } } reset{p};
-        p->k1_spread_tiles = p->tiling.ntiles;           // K0 has binned the WHOLE catalog; every range launch sees the same density (ADVICE, round 4)
-        for (int c = 0; c < kChunks; ++c) {
-            p->k1_tile_lo = p->band_tile0_host[cb[c]];
-            p->k1_tile_n = p->band_tile0_host[cb[c + 1]] - p->k1_tile_lo;
+    if (ch.piped) {
+        if (int rc = check_scatter(p, &dcat, e->out.p, true)) return rc;
+        if (int rc = pipe_setup(e, ch.n)) return rc;
+        if (int rc = launch_k0(p, &dcat, 0, m.k0_f64())) return rc;
+        TileLaunch k3;
+        k3.paint_pair_f32 = m.pair_f32();
+        k3.spread_tiles = p->tiling.ntiles;              // K0 has binned the WHOLE catalog; every range launch sees the same density (ADVICE, round 4)
+        for (int c = 0; c < ch.n; ++c) {
+            k3.tile_lo = p->band_tile0_host[ch.cb[c]];
+            k3.tile_n = p->band_tile0_host[ch.cb[c + 1]] - k3.tile_lo;
             // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
             if (c > 0) HIP_TRY(hipMemsetAsync(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1), 0, sizeof(unsigned int), p->stream));
-            if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p)) return rc;      // (indexed by global pixel number)
+            if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
             HIP_TRY(hipEventRecord(e->ev_k2[c], p->stream));
             HIP_TRY(hipStreamWaitEvent(e->out_stream, e->ev_k2[c], 0));
-            const int64_t lo = bfp[cb[c]], n = bfp[cb[c + 1]] - lo;
+            const int64_t lo = ch.bfp[ch.cb[c]], n = ch.bfp[ch.cb[c + 1]] - lo;
             HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->out_stream));
         }
         ms_k = t.stop(p->stream);
         t.start(p->stream);
         HIP_TRY(hipStreamSynchronize(e->out_stream));
     } else {
-    if (o.algo == 0) HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
-    if (int rc = bfgx_paint_device(p, &dcat, e->out.p, o.acc_paint_f64)) return rc;
-    ms_k = t.stop(p->stream);
-    t.start(p->stream);
-    if (o.acc_paint_f64) {
-        HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-    } else {
-        std::vector<float> tmp(npix);
-        HIP_TRY(hipMemcpyAsync(tmp.data(), e->out.p, npix * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        for (size_t i = 0; i < npix; ++i) map_out[i] = (double)tmp[i];
-    }
+        if (o.algo == 0) HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
+        if (int rc = paint_impl(p, &dcat, e->out.p, m)) return rc;
+        ms_k = t.stop(p->stream);
+        t.start(p->stream);
+        if (m.map_f64()) {
+            HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+        } else {
+            std::vector<float> tmp(npix);
+            HIP_TRY(hipMemcpyAsync(tmp.data(), e->out.p, npix * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            for (size_t i = 0; i < npix; ++i) map_out[i] = (double)tmp[i];
+        }
     }
     const double ms_d2h = t.stop(p->stream);
     if (int rc = bfgx_plan_status(p)) return rc;

@@ -129,7 +129,7 @@ int bfgx_shell_pairs_apply(bfgx_pairs *h, const double *vals_host, const double 
         HIP_TRY(hipMemcpyAsync(map_out, h->acc.p, npix * sizeof(double), hipMemcpyDeviceToHost, s));
     } else {
         HIP_TRY(hipMemcpyAsync(h->in.p, map_in, npix * sizeof(double), hipMemcpyHostToDevice, s));
-        if (int rc = regrid_impl(p, (const double *)h->in.p, h->acc.p, BFGX_ACC_F64, (double *)h->out.p, (double *)h->sums.p, false)) return rc;
+        if (int rc = regrid_impl(p, (const double *)h->in.p, h->acc.p, DispMode{DispMode::F64}, (double *)h->out.p, (double *)h->sums.p, false)) return rc;
         HIP_TRY(hipMemcpyAsync(map_out, h->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(sums, h->sums.p, sizeof(sums), hipMemcpyDeviceToHost, s));
     }

@@ -85,16 +85,8 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
     const int navail = bfgx_device_count();
     if (navail <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
     for (int d = 0; d < ndev; ++d) if (devices[d] < 0 || devices[d] >= navail) return fail(BFGX_ERR_INVALID, "device %d is not visible", devices[d]);
-    bfgx_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.check_mass = 1; o.algo = 1; o.acc_paint_f64 = 1; o.acc_offsets_f64 = BFGX_ACC_AUTO;
-    if (opts) o = *opts;
+    const bfgx_opts o = shell_opts(opts);
     if (o.algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "the multi-device calls use the tiled algorithm (algo 1)");
-    if (!paint && !acc_valid(o.acc_offsets_f64)) return fail(BFGX_ERR_INVALID, "opts.acc_offsets_f64 must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)");
-    // the slices that travel between the devices are ONE array of pix_offsets, so anything wider than fp32 pair math runs as fp64 throughout
-    // (as the band-restricted entries resolve it); BFGX_ACC_AUTO is settled below, once the probe plan has read the model's table
-    bool f64 = paint ? true : (o.acc_offsets_f64 != BFGX_ACC_F32);
-    size_t esz = f64 ? sizeof(double) : sizeof(float);
     const int width = paint ? 1 : 3;
     const int N = ndev;
     const auto t_start = std::chrono::steady_clock::now();
@@ -117,26 +109,8 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
     const int64_t per = cat->n > 0 ? (cat->n + N - 1) / N : 0;                        // Parallelize.py:250-253
     const int nex = model->table.ndim - 3;
     std::vector<double> hostlog;
-    const double *lnz = cat->ln1pz, *lnm = cat->lnM;
-    if (cat->n > 0 && (!lnz || !lnm)) {                                               // see upload_catalog
-        if (!cat->M || !cat->z) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-        hostlog.resize(2 * (size_t)cat->n);
-        for (int64_t i = 0; i < cat->n; ++i) {
-            const double a = 1.0 / (1.0 + cat->z[i]);
-            hostlog[i] = std::log(1.0 / a);
-            hostlog[(size_t)cat->n + i] = std::log(cat->M[i]);
-        }
-        if (!lnz) lnz = hostlog.data();
-        if (!lnm) lnm = hostlog.data() + cat->n;
-    }
     const double *src[kCatCols];
-    src[0] = cat->M; src[1] = cat->z; src[2] = cat->ra; src[3] = cat->dec;
-    for (int k = 0; k < BFGX_MAX_EXTRA; ++k) src[4 + k] = k < nex ? cat->extra[k] : nullptr;
-    src[4 + BFGX_MAX_EXTRA] = lnz; src[5 + BFGX_MAX_EXTRA] = lnm;
-    for (int i = 0; i < kCatCols; ++i) {
-        const bool wanted = i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA;
-        if (wanted && cat->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    }
+    if (int rc = catalog_columns(cat, nex, hostlog, src)) return rc;
     // the catalog columns that travel with a halo (M, z, ra, dec, property columns, the caller's table coordinates)
     int colidx[kCatCols], ncol = 0;
     for (int i = 0; i < kCatCols; ++i) if (i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA) colidx[ncol++] = i;
@@ -164,13 +138,12 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
             if (n > 0) HIP_TRY(hipMemcpyAsync(r.cols[i], src[i] + r.n0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, r.stream));
         }
     }
-    if (!paint) {
-        f64 = resolve_acc(R[0].plan, o.acc_offsets_f64) != BFGX_ACC_F32;
-        esz = f64 ? sizeof(double) : sizeof(float);
-    }
+    // the slices that travel between the devices are ONE array of pix_offsets, so anything wider than fp32 pair math runs as fp64 throughout
+    // (as the band-restricted entries resolve it); BFGX_ACC_AUTO is settled by the probe plan, which has read the model's table
+    DispMode dm;
+    if (!paint) if (int rc = disp_mode(R[0].plan, o.acc_offsets_f64, true, dm)) return rc;
+    const size_t esz = (paint || dm.fp64()) ? sizeof(double) : sizeof(float);
     // ---- pixel ownership: contiguous runs of ring bands
-    const size_t npix = (size_t)R[0].plan->hpx.npix;
-    (void)npix;
     std::vector<int64_t> first((size_t)R[0].plan->tiling.nbands + 1);
     int32_t nb = 0;
     if (int rc = bfgx_plan_bands(R[0].plan, &nb, first.data())) return rc;
@@ -182,9 +155,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         HIP_TRY(hipSetDevice(r.device));
         const int64_t n = r.n1 - r.n0;
         bfgx_catalog dc;
-        std::memset(&dc, 0, sizeof(dc));
-        dc.n = n;
-        dc.M = (const double *)r.cols[0]; dc.z = (const double *)r.cols[1]; dc.ra = (const double *)r.cols[2]; dc.dec = (const double *)r.cols[3];
+        catalog_view(n, nex, (const double *const *)r.cols, &dc);
         HIP_TRY(hipMalloc(&r.rings, sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(n, 1)));
         HIP_TRY(hipMalloc(&r.counts, sizeof(int32_t) * N));
         HIP_TRY(hipMalloc(&r.cursor, sizeof(int32_t) * N));
@@ -239,13 +210,9 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
             HIP_TRY(hipGetLastError());
         }
         bfgx_catalog dc;
-        std::memset(&dc, 0, sizeof(dc));
-        dc.n = r.nrecv;
         const double *colp[kCatCols] = {};
         for (int q = 0; q < ncol; ++q) colp[colidx[q]] = (const double *)r.rcols + (int64_t)q * r.nrecv;
-        dc.M = colp[0]; dc.z = colp[1]; dc.ra = colp[2]; dc.dec = colp[3];
-        for (int k = 0; k < nex; ++k) dc.extra[k] = colp[4 + k];
-        dc.ln1pz = colp[4 + BFGX_MAX_EXTRA]; dc.lnM = colp[5 + BFGX_MAX_EXTRA];
+        catalog_view(r.nrecv, nex, colp, &dc);
         // the slice is computed in place inside a buffer that also has room for the widest apron (16 rings either side)
         r.flo = r.p0; r.fhi = r.p1;
         if (!paint) {
@@ -260,7 +227,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         if (nown > 0) {
             if (paint) { if (int rc = bfgx_paint_bands_device(r.plan, &dc, r.b0, r.b1, slice, 1)) return rc; }
             else {
-                if (int rc = bfgx_offsets_bands_device(r.plan, &dc, r.b0, r.b1, slice, f64 ? 1 : 0)) return rc;
+                if (int rc = bfgx_offsets_bands_device(r.plan, &dc, r.b0, r.b1, slice, dm.acc())) return rc;
                 if (int rc = bfgx_bands_max_offset2_device(r.plan, r.b0, r.b1, (float *)r.omax)) return rc;
             }
         }
@@ -303,7 +270,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         HIP_TRY(hipMemcpyAsync(r.map, map_in + r.olo, sizeof(double) * (size_t)(r.ohi - r.olo), hipMemcpyHostToDevice, r.stream));
         // the kernel indexes the map by global pixel number: virtual base
         if (int rc = bfgx_regrid_bands_device(r.plan, r.b0, r.b1, (const double *)r.map - r.olo, (const char *)r.full + (size_t)(r.olo - r.flo) * width * esz,
-                                              r.olo, r.ohi, f64 ? 1 : 0, (double *)r.out, (double *)r.sums)) return rc;
+                                              r.olo, r.ohi, dm.acc(), (double *)r.out, (double *)r.sums)) return rc;
         HIP_TRY(hipMemcpyAsync(map_out + r.p0, r.out, sizeof(double) * (size_t)nown, hipMemcpyDeviceToHost, r.stream));
     }
     // ---- join: the slices are disjoint; far deposits (global pixel numbers, almost always none) are added on the host
@@ -336,11 +303,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         stats->sum_in = sum_in; stats->sum_out = sum_out; stats->n_pairs = -1;
         stats->ms_kernels = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();   // whole call
     }
-    if (!paint && o.check_mass) {      // np.isclose(new_sum, old_sum): rtol 1e-5, atol 1e-8  (HealpixRunner.py:344-346)
-        if (!(std::fabs(sum_out - sum_in) <= 1e-8 + 1e-5 * std::fabs(sum_in)))
-            return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sum_out, sum_in);
-    }
-    return BFGX_OK;
+    return (!paint && o.check_mass) ? check_mass(sum_in, sum_out) : BFGX_OK;
 }
 
 }  // namespace

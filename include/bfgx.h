@@ -42,7 +42,10 @@ extern "C" {
  *   BFGX_ACC_PARITY the parity-grade mode: fp64 pair math whose elementary functions carry 1e-11 (fp32 hardware seeds + one Newton step), pix_offsets
  *                   as TWO fp32 arrays -- hi [npix][3], then lo [npix][3] = (float)(o - hi) behind it (24 bytes per pixel, as fp64) --, the regrid scans
  *                   the high halves and evaluates survivors in fp64 on hi + lo.  Within 1e-9 mean(map) of BFGX_ACC_F64 at any displacement.  Needs the fast
- *                   tile kernel (3-axis table, uniform ln r axis); elsewhere, and in the band-restricted entries, it runs as BFGX_ACC_F64.
+ *                   tile kernel (3-axis table, uniform ln r axis); elsewhere it runs as BFGX_ACC_F64.  The split layout is what it means for the full-map
+ *                   entries (bfgx_offsets_device, bfgx_regrid_device, bfgx_baryonify_device) and the fused bfgx_offsets_regrid_bands_device;
+ *                   bfgx_offsets_bands_device, bfgx_regrid_bands_device and bfgx_max_offset2_device, whose slices travel between ranks as ONE
+ *                   array, serve it as BFGX_ACC_F64 (pix_offsets double [n][3]).
  *   BFGX_ACC_AUTO   the plan chooses from its table at creation: BFGX_ACC_F32 while the table cannot move a pixel by more than 0.1 pixel sides of the
  *                   plan's NSIDE (largest |d| a / D_A over the table's (z, M) nodes inside the model-side cut), BFGX_ACC_PARITY beyond.  The default of
  *                   the one-shot host entries and of the Python runners.  Scratch for pix_offsets must then hold 24 bytes per pixel.
@@ -245,7 +248,9 @@ int  bfgx_plan_bands(bfgx_plan *p, int32_t *nbands, int64_t *band_first_pixel);
  * maxima K1's flush leaves behind (a few thousand values) instead of a second pass over the slice.  Valid only while nothing
  * else has been added to that slice (spatial sharding: every rank computes its own pixels). */
 int  bfgx_bands_max_offset2_device(bfgx_plan *p, int32_t band0, int32_t band1, float *out_dev);
-/* *out_dev (float, device) = largest |offset|^2 of npixels pixels of pix_offsets (enqueue-only): what the ranks all-reduce (MAX) */
+/* *out_dev (float, device) = largest |offset|^2 of npixels pixels of pix_offsets (enqueue-only): what the ranks all-reduce (MAX).  acc_f64 reads
+ * the array as the band entries write it: BFGX_ACC_F32 fp32 [n][3], BFGX_ACC_F64 and BFGX_ACC_PARITY fp64 [n][3], BFGX_ACC_AUTO as the plan
+ * resolves it; any other value is refused with BFGX_ERR_INVALID before anything is enqueued. */
 int  bfgx_max_offset2_device(bfgx_plan *p, const void *offsets_dev, int64_t npixels, int acc_f64, float *out_dev);
 int  bfgx_plan_reach_rings(bfgx_plan *p, double max_offset, int32_t *rings);
 int  bfgx_plan_set_band_reach(bfgx_plan *p, int32_t rings);

@@ -556,6 +556,8 @@ def test_band_restricted_pass_with_selected_halos_equals_full_pass(gpu, paint):
                 torch.cuda.synchronize()
                 a, b = float(m_k1.item()), float(m_pass.item())
                 assert b > 0 and b <= a <= b * (1 + 3e-6), (a, b)
+                with pytest.raises(ValueError):                             # not a BFGX_ACC_* value: refused, not read as fp32
+                    plan.max_offset2(sl.data_ptr(), p1 - p0, m_pass.data_ptr(), acc_f64=2)
         assert N <= taken <= 1.5 * N                                        # boundary halos go to two ranks, nothing is lost
     plan.close()
 
