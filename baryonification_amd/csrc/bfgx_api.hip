@@ -1538,8 +1538,6 @@ static void launch_regrid_gather(bfgx_plan *p, const double *map_in_dev, const A
     }
 }
 
-namespace { void dep_release_all(); void fft_release_all(); void gcache_release_all(); void scache_release_all(); void deprec_release_all(); }
-
 extern "C" {
 
 static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offsets_dev, const DispMode &m, double *map_out_dev, double *sums_dev,
@@ -1643,6 +1641,8 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
     if (tmp) (void)hipFree(tmp);
     return rc;
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------ one-shot host API
 namespace {
@@ -1778,138 +1778,186 @@ int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], b
 
 }  // namespace
 
-// ---- plan cache of the one-shot API: a process() call re-uses the plan (model on the device, tiling, binning workspace) and
-// the device buffers of the previous call with the same model / nside / device, so that a warm call performs no hipMalloc
+// ---- plan caches of the one-shot API: a process() call re-uses the plan (model on the device, tiling, binning workspace) and the
+// device buffers of the previous call with the same model, geometry and device, so that a warm call performs no hipMalloc
 namespace {
 
+// A grow-only device buffer: a request beyond its capacity reallocates it with a slack of bytes / div + add, after the device has
+// drained (an earlier call may still use the old buffer on another stream).  Only growth waits; a warm call finds the buffer large enough.
 struct PoolBuf {
-    void *p = nullptr; size_t cap = 0;
-    int need(size_t bytes)
+    void *p = nullptr;
+    size_t cap = 0;
+    PoolBuf() = default;
+    PoolBuf(const PoolBuf &) = delete;
+    PoolBuf &operator=(const PoolBuf &) = delete;
+    ~PoolBuf() { if (p) (void)hipFree(p); }
+    int need(size_t bytes, size_t div = 4, size_t add = 256)
     {
         if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
+        if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); }
         p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
+        const size_t want = bytes + bytes / div + add;
         if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return 1; }
         cap = want;
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-struct CacheEntry {
-    uint64_t key = 0, key2 = 0, stamp = 0;     // two independent 64-bit hashes of (device, nside, model contents) + table size
-    int64_t table_values = 0;
-    bfgx_plan *plan = nullptr;
-    PoolBuf cols[kCatCols], in, out, off, sums;
-    hipStream_t copy_stream = nullptr;       // the map travels to the device while K0 / K1 run on the plan's stream
-    hipStream_t out_stream = nullptr;        // the regridded band ranges travel back while the rest of the map is still arriving
+// The key of a cached entry: two independent 64-bit hashes (an FNV-style basis and prime; another basis and odd multiplier) and the
+// model table's value count.  A hit needs all three to agree, so that one 64-bit collision cannot hand a model another model's table.
+struct CacheKey {
+    uint64_t h[2] = {0xcbf29ce484222325ull, 0x2545f4914f6cdd1dull};
+    int64_t values = 0;
+    void add(const void *data, size_t bytes)
+    {
+        constexpr uint64_t m0 = 0x100000001b3ull, m1 = 0x9e3779b97f4a7c15ull;
+        const unsigned char *c = (const unsigned char *)data;
+        uint64_t a = h[0], b = h[1];
+        size_t i = 0;
+        for (; i + 8 <= bytes; i += 8) {
+            uint64_t w;
+            std::memcpy(&w, c + i, 8);
+            a = (a ^ w) * m0; a ^= a >> 29;
+            b = (b ^ w) * m1; b ^= b >> 29;
+        }
+        for (; i < bytes; ++i) { a = (a ^ c[i]) * m0; b = (b ^ c[i]) * m1; }
+        h[0] = a; h[1] = b;
+    }
+    template <typename T> void add(const T &v) { add(&v, sizeof(v)); }
+    bool operator==(const CacheKey &o) const { return h[0] == o.h[0] && h[1] == o.h[1] && values == o.values; }
+};
+
+// (device, model contents); the model has been validated: its table pointers are readable.  Each cache adds its geometry.
+CacheKey model_key(int device, const bfgx_model *m)
+{
+    CacheKey k;
+    k.add(device);
+    const bfgx_table &t = m->table;
+    k.add(t.ndim);
+    k.add(t.n, sizeof(t.n));
+    size_t nv = 1;
+    for (int d = 0; d < t.ndim; ++d) { k.add(t.axis[d], sizeof(double) * (size_t)t.n[d]); nv *= (size_t)t.n[d]; }
+    k.add(t.values, sizeof(double) * nv);
+    k.add(&t.rdelta_sampling, sizeof(int32_t) * 2);
+    k.add(t.eps_model);
+    k.add(m->cosmo_runner); k.add(m->cosmo_model);
+    k.add(m->massdef_runner.Delta); k.add(m->massdef_runner.rho_type);
+    k.add(m->massdef_model.Delta); k.add(m->massdef_model.rho_type);
+    k.add(m->eps_runner);
+    k.values = (int64_t)nv;
+    return k;
+}
+
+// A cached entry: its key, its plan and its streams and events.  The data travels up and down on streams of its own while the plan's
+// stream computes; phase events (timed) for bfgx_stats; two pools of per-range events: a range has arrived (ev_up) / has been computed (ev_k).
+template <typename Plan> struct CacheEntry {
+    CacheKey key;
+    uint64_t stamp = 0;
+    int device = 0;
+    Plan *plan = nullptr;
+    hipStream_t up = nullptr, down = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> ev_in, ev_k2;    // per band range: its part of the map has arrived / has been regridded
+    std::vector<hipEvent_t> ev_up, ev_k;
+    int create()
+    {
+        HIP_TRY(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
+        for (auto &v : ev) HIP_TRY(hipEventCreate(&v));
+        return BFGX_OK;
+    }
+    // at least nup events in ev_up and nk in ev_k
+    int pools(int nup, int nk)
+    {
+        while ((int)ev_up.size() < nup || (int)ev_k.size() < nk) {
+            std::vector<hipEvent_t> &pool = (int)ev_up.size() < nup ? ev_up : ev_k;
+            hipEvent_t v;
+            HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming));
+            pool.push_back(v);
+        }
+        return BFGX_OK;
+    }
+    ~CacheEntry()            // (the plan is destroyed by PlanCache::drop, before the entry's own buffers are freed)
+    {
+        if (up) (void)hipStreamDestroy(up);
+        if (down) (void)hipStreamDestroy(down);
+        for (auto &v : ev) if (v) (void)hipEventDestroy(v);
+        for (auto &v : ev_up) (void)hipEventDestroy(v);
+        for (auto &v : ev_k) (void)hipEventDestroy(v);
+    }
+};
+
+void plan_destroy(bfgx_plan *p) { bfgx_plan_destroy(p); }
+void plan_destroy(bfgx_grid_plan *p) { bfgx_grid_plan_destroy(p); }
+void plan_destroy(bfgx_snapshot_plan *p) { bfgx_snapshot_plan_destroy(p); }
+
+// A least-recently-used cache of at most kMax entries E (a CacheEntry<Plan> with the entry's own device buffers).  One call at a time
+// holds mu; the shell, grid and snapshot entries each have a cache (and a mutex) of their own.
+template <typename E, size_t kMax> struct PlanCache {
+    std::mutex mu;
+    std::vector<E *> v;
+    uint64_t stamp = 0;
+
+    static void drop(E *e)
+    {
+        (void)hipSetDevice(e->device);
+        if (e->plan) plan_destroy(e->plan);
+        delete e;
+    }
+    // the entry for key, with a plan for at least n halos (make(capacity, &plan) builds it) and its streams; setup(e) then readies the
+    // entry's own buffers.  An entry whose set-up fails is removed.  mu is held by the caller.
+    template <typename Make, typename Setup> int acquire(const CacheKey &key, int device, int64_t n, Make make, Setup setup, E **out)
+    {
+        auto it = std::find_if(v.begin(), v.end(), [&](E *c) { return c->key == key; });
+        E *e = it != v.end() ? *it : nullptr;
+        if (e && e->plan->max_halos < n) {                   // grew: rebuild the plan (its workspace scales with max_halos)
+            (void)hipSetDevice(device);
+            plan_destroy(e->plan);
+            e->plan = nullptr;
+        }
+        if (!e) {
+            if (v.size() >= kMax) {
+                auto lru = std::min_element(v.begin(), v.end(), [](E *a, E *b) { return a->stamp < b->stamp; });
+                drop(*lru);
+                v.erase(lru);
+            }
+            e = new E();
+            e->key = key; e->device = device;
+            v.push_back(e);
+        }
+        int rc = BFGX_OK;
+        if (!e->plan && (rc = make(std::max<int64_t>(n + n / 4, 1024), &e->plan))) e->plan = nullptr;
+        if (!rc && hipSetDevice(device) != hipSuccess) rc = fail(BFGX_ERR_HIP, "hipSetDevice(%d) failed", device);
+        if (!rc && !e->up) rc = e->create();
+        if (!rc) rc = setup(e);
+        if (rc) {
+            v.erase(std::find(v.begin(), v.end(), e));
+            drop(e);
+            return rc;
+        }
+        e->stamp = ++stamp;
+        *out = e;
+        return BFGX_OK;
+    }
+    void clear()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (E *e : v) drop(e);
+        v.clear();
+    }
+};
+
+struct ShellEntry : CacheEntry<bfgx_plan> {
+    PoolBuf cols[kCatCols], in, out, off, sums;
     // the catalog columns of the last call stay on the device under the caller's token (bfgx_opts.catalog_token)
     uint64_t cat_token = 0;
     int64_t cat_n = -1;
     bfgx_catalog cat_dev;
 };
-
-std::mutex g_cache_mu;
-std::vector<CacheEntry *> g_cache;
-uint64_t g_cache_stamp = 0;
-constexpr size_t kCacheMax = 4;
-
-uint64_t g_hash_mul = 0x100000001b3ull;       // multiplier of hash_bytes (set by model_key: two passes with different constants)
-
-uint64_t hash_bytes(uint64_t h, const void *data, size_t bytes)
-{
-    const unsigned char *c = (const unsigned char *)data;
-    const uint64_t mul = g_hash_mul;
-    size_t i = 0;
-    for (; i + 8 <= bytes; i += 8) { uint64_t w; std::memcpy(&w, c + i, 8); h = (h ^ w) * mul; h ^= h >> 29; }
-    for (; i < bytes; ++i) h = (h ^ c[i]) * mul;
-    return h;
-}
-
-// which = 0: FNV-style offset basis and prime; which = 1: a second, independent pass (other basis, other odd multiplier) -- a cache hit
-// needs both to agree (and the table size), so that one 64-bit collision cannot hand a model another model's device table
-uint64_t model_key(int device, int64_t nside, const bfgx_model *m, int which = 0)
-{
-    g_hash_mul = which ? 0x9e3779b97f4a7c15ull : 0x100000001b3ull;
-    struct Restore { ~Restore() { g_hash_mul = 0x100000001b3ull; } } restore;
-    uint64_t h = which ? 0x2545f4914f6cdd1dull : 0xcbf29ce484222325ull;
-    h = hash_bytes(h, &device, sizeof(device));
-    h = hash_bytes(h, &nside, sizeof(nside));
-    const bfgx_table &t = m->table;
-    h = hash_bytes(h, &t.ndim, sizeof(t.ndim));
-    h = hash_bytes(h, t.n, sizeof(t.n));
-    size_t nv = 1;
-    for (int d = 0; d < t.ndim; ++d) { h = hash_bytes(h, t.axis[d], sizeof(double) * (size_t)t.n[d]); nv *= (size_t)t.n[d]; }
-    h = hash_bytes(h, t.values, sizeof(double) * nv);
-    h = hash_bytes(h, &t.rdelta_sampling, sizeof(int32_t) * 2);
-    h = hash_bytes(h, &t.eps_model, sizeof(double));
-    h = hash_bytes(h, &m->cosmo_runner, sizeof(bfgx_cosmo));
-    h = hash_bytes(h, &m->cosmo_model, sizeof(bfgx_cosmo));
-    h = hash_bytes(h, &m->massdef_runner.Delta, sizeof(double)); h = hash_bytes(h, &m->massdef_runner.rho_type, sizeof(int32_t));
-    h = hash_bytes(h, &m->massdef_model.Delta, sizeof(double)); h = hash_bytes(h, &m->massdef_model.rho_type, sizeof(int32_t));
-    h = hash_bytes(h, &m->eps_runner, sizeof(double));
-    return h;
-}
-
-void cache_drop(CacheEntry *e)
-{
-    if (e->plan) { (void)hipSetDevice(e->plan->device); bfgx_plan_destroy(e->plan); }
-    for (auto &c : e->cols) c.release();
-    e->in.release(); e->out.release(); e->off.release(); e->sums.release();
-    if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
-    if (e->out_stream) (void)hipStreamDestroy(e->out_stream);
-    for (auto &v : e->ev) if (v) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_in) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_k2) (void)hipEventDestroy(v);
-    delete e;
-}
-
-// the cached entry for (device, nside, model), its plan large enough for n halos; g_cache_mu is held by the caller
-int cache_acquire(int device, int64_t nside, const bfgx_model *model, int64_t n, CacheEntry **out)
-{
-    if (int rc = validate_model(model)) return rc;           // before hashing: the table pointers must be readable
-    const uint64_t key = model_key(device, nside, model), key2 = model_key(device, nside, model, 1);
-    int64_t nvals = 1;
-    for (int d = 0; d < model->table.ndim; ++d) nvals *= model->table.n[d];
-    CacheEntry *e = nullptr;
-    for (CacheEntry *c : g_cache) if (c->key == key && c->key2 == key2 && c->table_values == nvals) e = c;
-    if (e && e->plan->max_halos < n) {                       // grew: rebuild the plan (its workspace scales with max_halos)
-        (void)hipSetDevice(device);
-        bfgx_plan_destroy(e->plan);
-        e->plan = nullptr;
-    }
-    if (!e) {
-        if (g_cache.size() >= kCacheMax) {                   // evict the least recently used entry
-            size_t lru = 0;
-            for (size_t i = 1; i < g_cache.size(); ++i) if (g_cache[i]->stamp < g_cache[lru]->stamp) lru = i;
-            cache_drop(g_cache[lru]);
-            g_cache.erase(g_cache.begin() + (long)lru);
-        }
-        e = new CacheEntry();
-        e->key = key; e->key2 = key2; e->table_values = nvals;
-        g_cache.push_back(e);
-    }
-    if (!e->plan) {
-        const int64_t cap = std::max<int64_t>(n + n / 4, 1024);
-        if (int rc = bfgx_plan_create(device, nullptr, nside, cap, model, &e->plan)) {
-            e->plan = nullptr;
-            g_cache.erase(std::find(g_cache.begin(), g_cache.end(), e));
-            cache_drop(e);
-            return rc;
-        }
-        e->plan->blocking_growth = true;
-    }
-    e->stamp = ++g_cache_stamp;
-    *out = e;
-    return BFGX_OK;
-}
+PlanCache<ShellEntry, 4> g_shells;
 
 std::atomic<long long> g_catalog_uploads{0};
 
-int upload_catalog_pooled(CacheEntry *e, const bfgx_catalog *h, bfgx_catalog *d, std::vector<double> &hostlog, uint64_t token)
+int upload_catalog_pooled(ShellEntry *e, const bfgx_catalog *h, bfgx_catalog *d, std::vector<double> &hostlog, uint64_t token)
 {
     bfgx_plan *p = e->plan;
     if (token != 0 && token == e->cat_token && h->n == e->cat_n) {      // the same catalog as last time: its columns are still there
@@ -1942,7 +1990,7 @@ int check_mass(double sum_in, double sum_out)
 }
 
 // the options of a one-shot entry; NULL: the defaults (each entry reads only its own fields)
-bfgx_opts shell_opts(const bfgx_opts *opts)
+bfgx_opts entry_opts(const bfgx_opts *opts)
 {
     bfgx_opts o{};
     o.check_mass = 1; o.algo = 1; o.acc_offsets_f64 = BFGX_ACC_AUTO; o.acc_paint_f64 = 1;
@@ -1950,16 +1998,23 @@ bfgx_opts shell_opts(const bfgx_opts *opts)
     return o;
 }
 
-// the start of a one-shot entry (g_cache_mu held): the cached plan for (device, nside, model) set to o.algo, its streams drained at exit
-int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const bfgx_opts &o, CacheEntry **e, DrainOnExit &drain)
+// the start of a one-shot entry (g_shells.mu held): the cached plan for (device, nside, model) set to o.algo, its streams drained at exit
+int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const bfgx_opts &o, ShellEntry **e, DrainOnExit &drain)
 {
     if (o.algo != 0 && o.algo != 1) return fail(BFGX_ERR_INVALID, "opts.algo must be 0 or 1");
     if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
-    if (int rc = cache_acquire(o.device, nside, model, cat->n, e)) return rc;
+    if (int rc = validate_model(model)) return rc;           // before hashing: the table pointers must be readable
+    CacheKey key = model_key(o.device, model);
+    key.add(nside);
+    auto make = [&](int64_t cap, bfgx_plan **p) -> int {
+        if (int rc = bfgx_plan_create(o.device, nullptr, nside, cap, model, p)) return rc;
+        (*p)->blocking_growth = true;
+        return BFGX_OK;
+    };
+    if (int rc = g_shells.acquire(key, o.device, cat->n, make, [](ShellEntry *) -> int { return BFGX_OK; }, e)) return rc;
     bfgx_plan *p = (*e)->plan;
     p->algo = o.algo;
-    HIP_TRY(hipSetDevice(p->device));
-    drain.s[0] = &p->stream; drain.s[1] = &(*e)->copy_stream; drain.s[2] = &(*e)->out_stream; drain.null_stream = (p->stream == nullptr);
+    drain.s[0] = &p->stream; drain.s[1] = &(*e)->up; drain.s[2] = &(*e)->down; drain.null_stream = (p->stream == nullptr);
     return BFGX_OK;
 }
 
@@ -1993,16 +2048,9 @@ void chunk_plan(bfgx_plan *p, bool eligible, Chunks &c)
     }
 }
 
-// the second stream of a streamed call and at least n events in each per-range pool (kept with the cache entry)
-int pipe_setup(CacheEntry *e, int n)
-{
-    if (!e->out_stream) HIP_TRY(hipStreamCreateWithFlags(&e->out_stream, hipStreamNonBlocking));
-    for (auto *pool : {&e->ev_in, &e->ev_k2})
-        while ((int)pool->size() < n) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); pool->push_back(v); }
-    return BFGX_OK;
-}
-
 }  // namespace
+
+extern "C" {
 
 long long bfgx_debug_catalog_uploads(void) { return g_catalog_uploads.load(); }
 
@@ -2011,20 +2059,6 @@ void bfgx_debug_host_spans(long long *pinned_in_place, long long *staged, long l
     if (pinned_in_place) *pinned_in_place = g_host_pinned_in_place.load();
     if (staged) *staged = g_host_staged.load();
     if (smallest_pinned_bytes) *smallest_pinned_bytes = g_host_pin_min_bytes.load();
-}
-
-void bfgx_cache_clear(void)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        for (CacheEntry *e : g_cache) cache_drop(e);
-        g_cache.clear();
-    }
-    dep_release_all();           // workspace of the tiled particle deposit (bfgx_grid_api.inc)
-    fft_release_all();           // twiddle / wavenumber tables of the power spectrum
-    gcache_release_all();        // plans + device maps of the one-shot grid entries
-    scache_release_all();        // plan + device record buffer of the snapshot records entry
-    deprec_release_all();        // device buffers of the deposit's records entry
 }
 
 long long bfgx_debug_alloc_count(void) { return (long long)g_bfgx_allocs.load(); }
@@ -2044,10 +2078,10 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
                          const double *map_in, double *map_out, const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !map_in || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    const bfgx_opts o = shell_opts(opts);
-    std::lock_guard<std::mutex> lk(g_cache_mu);              // one one-shot call at a time (they share the cached plans)
+    const bfgx_opts o = entry_opts(opts);
+    std::lock_guard<std::mutex> lk(g_shells.mu);             // one shell call at a time (they share the cached plans)
     DrainOnExit drain;
-    CacheEntry *e = nullptr;
+    ShellEntry *e = nullptr;
     if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
     bfgx_plan *p = e->plan;
 
@@ -2057,10 +2091,6 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     const size_t acc_bytes = npix * m.pixel_bytes();
     std::vector<double> hostlog;
     bfgx_catalog dcat;
-    if (!e->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-        for (auto &v : e->ev) HIP_TRY(hipEventCreate(&v));
-    }
     // phases: catalog -> device, K0 + K1 launched (enqueue-only), THEN the map -> device on a second stream (a copy from
     // pageable memory occupies the host, the kernels run meanwhile), K2 after both, map -> host
     HIP_TRY(hipEventRecord(e->ev[0], p->stream));
@@ -2088,18 +2118,18 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     bool piped = ch.piped;
     bool whole_map_sent = false;
     HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &e->copy_stream; hin.streams[1] = hout.streams[1] = &p->stream; hin.streams[2] = hout.streams[2] = &e->out_stream;
+    hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &p->stream; hin.streams[2] = hout.streams[2] = &e->down;
     if (piped) piped = hin.open(map_in, npix * sizeof(double), false, ch.stage) && hout.open(map_out, npix * sizeof(double), true, ch.stage);
     if (piped) { map_in = (const double *)hin.use; map_out = (double *)hout.use; }       // (from here on: the page-locked views)
     if (piped) {
-        if (int rc = pipe_setup(e, kChunks)) return rc;
+        if (int rc = e->pools(kChunks, kChunks)) return rc;
         if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(sums) failed");
         double *dsums = (double *)e->sums.p;
         float *domax = (float *)(dsums + 2 * kChunks);
         auto send = [&](int c) -> int {
             const int64_t lo = bfp[cb[c]], n = bfp[cb[c + 1]] - lo;
-            HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
-            HIP_TRY(hipEventRecord(e->ev_in[c], e->copy_stream));
+            HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, e->up));
+            HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
             return BFGX_OK;
         };
         if (int rc = send(0)) return rc;
@@ -2125,13 +2155,13 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
                     int need = next;
                     while (need < kChunks - 1 && bfp[cb[need + 1]] < ohi) ++need;
                     if (need >= sent) break;
-                    HIP_TRY(hipStreamWaitEvent(p->stream, e->ev_in[need], 0));
+                    HIP_TRY(hipStreamWaitEvent(p->stream, e->ev_up[need], 0));
                     const int64_t lo = bfp[cb[next]], n = bfp[cb[next + 1]] - lo;
                     if (int rc = regrid_bands_impl(p, cb[next], cb[next + 1], (const double *)e->in.p, e->off.p, 0, (int64_t)npix, m,
                                                    (double *)e->out.p + lo, dsums + 2 * next, next == 0)) return rc;
-                    HIP_TRY(hipEventRecord(e->ev_k2[next], p->stream));
-                    HIP_TRY(hipStreamWaitEvent(e->out_stream, e->ev_k2[next], 0));
-                    HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->out_stream));
+                    HIP_TRY(hipEventRecord(e->ev_k[next], p->stream));
+                    HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[next], 0));
+                    HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
                     ++next;
                 }
                 return BFGX_OK;
@@ -2143,13 +2173,13 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
                 if (rc_run == BFGX_OK) rc_run = run_ready();
             }
             p->band_reach = reach_before;
-            if (rc_run) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamSynchronize(p->stream); (void)hipStreamSynchronize(e->out_stream); return rc_run; }
-            HIP_TRY(hipEventRecord(e->ev[1], e->copy_stream));
+            if (rc_run) { (void)hipStreamSynchronize(e->up); (void)hipStreamSynchronize(p->stream); (void)hipStreamSynchronize(e->down); return rc_run; }
+            HIP_TRY(hipEventRecord(e->ev[1], e->up));
             HIP_TRY(hipEventRecord(e->ev[2], p->stream));
             double hs[2 * kChunksMax];
             HIP_TRY(hipMemcpyAsync(hs, dsums, sizeof(double) * 2 * (size_t)kChunks, hipMemcpyDeviceToHost, p->stream));
             HIP_TRY(hipStreamSynchronize(p->stream));
-            HIP_TRY(hipStreamSynchronize(e->out_stream));
+            HIP_TRY(hipStreamSynchronize(e->down));
             HIP_TRY(hipEventRecord(e->ev[3], p->stream));
             for (int c = 0; c < kChunks; ++c) { sums[0] += hs[2 * c]; sums[1] += hs[2 * c + 1]; }
             // the listed deposits (pixels next to a pole): added on the host; an overflowing list sends the call down the one-pass route
@@ -2166,14 +2196,14 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         if (!piped) {                                        // the rest of the map in one piece, then the one-pass route below
             if (!whole_map_sent && sent < kChunks) {
                 const int64_t lo = bfp[cb[sent]];
-                HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (npix - (size_t)lo) * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
+                HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (npix - (size_t)lo) * sizeof(double), hipMemcpyHostToDevice, e->up));
             }
             whole_map_sent = true;
         }
     }
     if (!piped) {
-        if (!whole_map_sent) HIP_TRY(hipMemcpyAsync(e->in.p, map_in, npix * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
-        HIP_TRY(hipEventRecord(e->ev[1], e->copy_stream));
+        if (!whole_map_sent) HIP_TRY(hipMemcpyAsync(e->in.p, map_in, npix * sizeof(double), hipMemcpyHostToDevice, e->up));
+        HIP_TRY(hipEventRecord(e->ev[1], e->up));
         HIP_TRY(hipStreamWaitEvent(p->stream, e->ev[1], 0));
         if (int rc = regrid_impl(p, (const double *)e->in.p, e->off.p, m, (double *)e->out.p, (double *)e->sums.p, o.algo == 1)) return rc;
         HIP_TRY(hipEventRecord(e->ev[2], p->stream));
@@ -2203,10 +2233,10 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
                      double *map_out, const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    const bfgx_opts o = shell_opts(opts);
-    std::lock_guard<std::mutex> lk(g_cache_mu);
+    const bfgx_opts o = entry_opts(opts);
+    std::lock_guard<std::mutex> lk(g_shells.mu);
     DrainOnExit drain;
-    CacheEntry *e = nullptr;
+    ShellEntry *e = nullptr;
     if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
     bfgx_plan *p = e->plan;
     PaintMode m;
@@ -2226,13 +2256,13 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     Chunks ch;
     chunk_plan(p, o.algo == 1 && m.map_f64(), ch);
     HostSpan hout;
-    hout.streams[0] = &p->stream; hout.streams[1] = &e->out_stream;
+    hout.streams[0] = &p->stream; hout.streams[1] = &e->down;
     if (ch.piped) ch.piped = hout.open(map_out, npix * sizeof(double), true, ch.stage);
     if (ch.piped) map_out = (double *)hout.use;              // (from here on: the page-locked view)
     double ms_k = 0.0;
     if (ch.piped) {
         if (int rc = check_scatter(p, &dcat, e->out.p, true)) return rc;
-        if (int rc = pipe_setup(e, ch.n)) return rc;
+        if (int rc = e->pools(ch.n, ch.n)) return rc;
         if (int rc = launch_k0(p, &dcat, 0, m.k0_f64())) return rc;
         TileLaunch k3;
         k3.paint_pair_f32 = m.pair_f32();
@@ -2243,14 +2273,14 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
             // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
             if (c > 0) HIP_TRY(hipMemsetAsync(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1), 0, sizeof(unsigned int), p->stream));
             if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
-            HIP_TRY(hipEventRecord(e->ev_k2[c], p->stream));
-            HIP_TRY(hipStreamWaitEvent(e->out_stream, e->ev_k2[c], 0));
+            HIP_TRY(hipEventRecord(e->ev_k[c], p->stream));
+            HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
             const int64_t lo = ch.bfp[ch.cb[c]], n = ch.bfp[ch.cb[c + 1]] - lo;
-            HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->out_stream));
+            HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
         }
         ms_k = t.stop(p->stream);
         t.start(p->stream);
-        HIP_TRY(hipStreamSynchronize(e->out_stream));
+        HIP_TRY(hipStreamSynchronize(e->down));
     } else {
         if (o.algo == 0) HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
         if (int rc = paint_impl(p, &dcat, e->out.p, m)) return rc;
@@ -2436,3 +2466,13 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // spherical-harmonic transforms of HEALPix shells (map2alm / alm2map / alm2cl / anafast)
 #include "bfgx_sht_api.inc"
+
+extern "C" void bfgx_cache_clear(void)
+{
+    g_shells.clear();            // plans + device buffers of the one-shot shell entries
+    dep_release_all();           // workspace of the tiled particle deposit (bfgx_grid_api.inc)
+    fft_release_all();           // twiddle / wavenumber tables of the power spectrum
+    g_grids.clear();             // plans + device maps of the one-shot grid entries
+    g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
+    deprec_release_all();        // device buffers of the deposit's records entry
+}

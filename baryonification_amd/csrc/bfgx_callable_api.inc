@@ -28,7 +28,6 @@ struct bfgx_pairs {
     std::vector<void *> sowned;
     int64_t snp = 0;
     DevBuf sxyz[3], srecs, skeys, sacc;
-    ~bfgx_pairs() { for (PoolBuf *b : {&acc, &in, &out, &sums, &batch}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } }
 };
 
 extern "C" {

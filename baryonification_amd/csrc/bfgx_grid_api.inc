@@ -135,7 +135,7 @@ int grid_halo_loop(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode, doub
 }
 
 struct GridHostCatalog {
-    DevBuf cols[4 + 2 + BFGX_MAX_EXTRA];
+    PoolBuf cols[4 + 2 + BFGX_MAX_EXTRA];          // (kept by the cached one-shot entries: a warm call re-uses them)
     bfgx_grid_catalog d;
     int upload(const bfgx_grid_catalog *h, int ndim, int nex, hipStream_t s)
     {
@@ -148,7 +148,7 @@ struct GridHostCatalog {
         for (int i = 0; i < 6 + nex; ++i) {
             if (!src[i]) continue;
             const size_t bytes = sizeof(double) * (size_t)h->n * width[i];
-            if (cols[i].alloc(bytes)) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
+            if (cols[i].need(std::max<size_t>(bytes, 8))) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
             if (h->n > 0) HIP_TRY(hipMemcpyAsync(cols[i].p, src[i], bytes, hipMemcpyHostToDevice, s));
             *dst[i] = (const double *)cols[i].p;
         }
@@ -505,87 +505,28 @@ int bfgx_grid_plan_timing_read(bfgx_grid_plan *p, double *ms_sum, int64_t *launc
 namespace {
 
 // ---- cache of the one-shot grid entries: plan + device maps per (device, grid, model), as the shell entries keep theirs --------------
-struct GridCacheEntry {
-    uint64_t key = 0, key2 = 0, stamp = 0;
-    int64_t table_values = 0;
-    bfgx_grid_plan *plan = nullptr;
+struct GridEntry : CacheEntry<bfgx_grid_plan> {
     DevBuf in, out, sums;
-    hipStream_t up = nullptr, down = nullptr;      // the map arrives / leaves in ranges of planes while the plan's stream computes
-    std::vector<hipEvent_t> ev_up, ev_g;
-    hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
+    GridHostCatalog hc;
 };
-std::mutex g_gcache_mu;
-std::atomic<long long> g_grid_pipe_fallbacks{0};       // streamed bfgx_baryonify_grid calls that repeated the regrid in one pass (a cell moved too far along axis 0)
-std::vector<GridCacheEntry *> g_gcache;
-uint64_t g_gcache_stamp = 0;
-constexpr size_t kGridCacheMax = 2;                  // (an entry holds two maps: 2.1 GB at 512^3)
+PlanCache<GridEntry, 2> g_grids;                    // (an entry holds two maps: 2.1 GB at 512^3)
+std::atomic<long long> g_grid_pipe_fallbacks{0};     // streamed bfgx_baryonify_grid calls that repeated the regrid in one pass (a cell moved too far along axis 0)
 
-void gcache_drop(GridCacheEntry *e)
-{
-    if (e->plan) { (void)hipSetDevice(e->plan->device); bfgx_grid_plan_destroy(e->plan); }
-    if (e->up) (void)hipStreamDestroy(e->up);
-    if (e->down) (void)hipStreamDestroy(e->down);
-    for (auto &v : e->ev_up) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_g) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_t) if (v) (void)hipEventDestroy(v);
-    delete e;                                        // (DevBuf members free the maps)
-}
-
-uint64_t grid_key(int device, const bfgx_grid *g, const bfgx_model *m, int which)
-{
-    uint64_t h = model_key(device, g->npix, m, which);
-    g_hash_mul = which ? 0x9e3779b97f4a7c15ull : 0x100000001b3ull;
-    h = hash_bytes(h, &g->ndim, sizeof(g->ndim));
-    h = hash_bytes(h, &g->redshift, sizeof(g->redshift));
-    h = hash_bytes(h, g->bins, sizeof(double) * (size_t)g->npix);
-    g_hash_mul = 0x100000001b3ull;
-    return h;
-}
-
-// the cached entry for (device, grid, model) with a plan for at least n halos and the two device maps; g_gcache_mu is held by the caller
-int gcache_acquire(int device, const bfgx_grid *grid, const bfgx_model *model, int64_t n, GridCacheEntry **out)
+// the cached entry for (device, grid, model) with a plan for at least n halos and the two device maps; g_grids.mu is held by the caller
+int grid_acquire(int device, const bfgx_grid *grid, const bfgx_model *model, int64_t n, GridEntry **out)
 {
     if (int rc = validate_grid(grid)) return rc;
     if (int rc = validate_model(model)) return rc;
-    const uint64_t key = grid_key(device, grid, model, 0), key2 = grid_key(device, grid, model, 1);
-    int64_t nvals = 1;
-    for (int d = 0; d < model->table.ndim; ++d) nvals *= model->table.n[d];
-    GridCacheEntry *e = nullptr;
-    for (GridCacheEntry *c : g_gcache) if (c->key == key && c->key2 == key2 && c->table_values == nvals) e = c;
-    if (e && e->plan && e->plan->max_halos < n) { (void)hipSetDevice(device); bfgx_grid_plan_destroy(e->plan); e->plan = nullptr; }
-    if (!e) {
-        if (g_gcache.size() >= kGridCacheMax) {
-            size_t lru = 0;
-            for (size_t i = 1; i < g_gcache.size(); ++i) if (g_gcache[i]->stamp < g_gcache[lru]->stamp) lru = i;
-            gcache_drop(g_gcache[lru]);
-            g_gcache.erase(g_gcache.begin() + (long)lru);
-        }
-        e = new GridCacheEntry();
-        e->key = key; e->key2 = key2; e->table_values = nvals;
-        g_gcache.push_back(e);
-    }
-    auto bail = [&](int rc) { g_gcache.erase(std::find(g_gcache.begin(), g_gcache.end(), e)); gcache_drop(e); return rc; };
-    if (!e->plan) {
-        const int64_t cap = std::max<int64_t>(n + n / 4, 1024);
-        if (int rc = bfgx_grid_plan_create(device, nullptr, grid, cap, model, &e->plan)) { e->plan = nullptr; return bail(rc); }
-    }
-    const size_t bytes = (size_t)e->plan->geom.ntot * sizeof(double);
-    if (!e->in.p && (e->in.alloc(bytes) || e->out.alloc(bytes) || e->sums.alloc(2 * sizeof(double)))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed"));
-    if (!e->up) {
-        if (hipStreamCreateWithFlags(&e->up, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&e->down, hipStreamNonBlocking) != hipSuccess)
-            return bail(fail(BFGX_ERR_HIP, "hipStreamCreate failed"));
-        for (auto &v : e->ev_t) if (hipEventCreate(&v) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipEventCreate failed"));
-    }
-    e->stamp = ++g_gcache_stamp;
-    *out = e;
-    return BFGX_OK;
-}
-
-void gcache_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_gcache_mu);
-    for (GridCacheEntry *e : g_gcache) gcache_drop(e);
-    g_gcache.clear();
+    CacheKey key = model_key(device, model);
+    key.add(grid->npix); key.add(grid->ndim); key.add(grid->redshift);
+    key.add(grid->bins, sizeof(double) * (size_t)grid->npix);
+    auto make = [&](int64_t cap, bfgx_grid_plan **p) { return bfgx_grid_plan_create(device, nullptr, grid, cap, model, p); };
+    auto setup = [](GridEntry *e) -> int {
+        const size_t bytes = (size_t)e->plan->geom.ntot * sizeof(double);
+        if (!e->in.p && (e->in.alloc(bytes) || e->out.alloc(bytes) || e->sums.alloc(2 * sizeof(double)))) return fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed");
+        return BFGX_OK;
+    };
+    return g_grids.acquire(key, device, n, make, setup, out);
 }
 
 constexpr int kGridChunksMax = 32;
@@ -598,26 +539,22 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
                         double *map_out, const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !grid || !map_in || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    bfgx_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.check_mass = 1;
-    if (opts) o = *opts;
-    std::lock_guard<std::mutex> lk(g_gcache_mu);
-    GridCacheEntry *e = nullptr;
-    if (int rc = gcache_acquire(o.device, grid, model, cat->n, &e)) return rc;
+    const bfgx_opts o = entry_opts(opts);
+    std::lock_guard<std::mutex> lk(g_grids.mu);
+    GridEntry *e = nullptr;
+    if (int rc = grid_acquire(o.device, grid, model, cat->n, &e)) return rc;
     bfgx_grid_plan *p = e->plan;
-    HIP_TRY(hipSetDevice(p->device));
-    DrainOnExit drain;                                       // (first: destroyed after the catalog columns and the Pin objects)
+    DrainOnExit drain;                                       // (first: destroyed after the HostSpans)
     drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.s[2] = &e->down; drain.null_stream = (p->stream == nullptr);
     const size_t ntot = (size_t)p->geom.ntot;
     const int ndim = p->geom.ndim, N = p->geom.npix;
-    GridHostCatalog hc;
+    GridHostCatalog &hc = e->hc;
     // BFGX_GRID_PATH=scatter keeps the halo-owned kernels (what the multi-GPU entry points use) reachable from the one-shot API for tests
     const char *path = std::getenv("BFGX_GRID_PATH");
     const bool scatter = path && std::strcmp(path, "scatter") == 0;
     double *d_in = (double *)e->in.p, *d_out = (double *)e->out.p, *d_sums = (double *)e->sums.p;
     hipStream_t s = p->stream;
-    HIP_TRY(hipEventRecord(e->ev_t[0], s));
+    HIP_TRY(hipEventRecord(e->ev[0], s));
     if (int rc = hc.upload(cat, ndim, p->model.tab.ndim - 3, s)) return rc;
     HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(double), s));
     int64_t npairs = 0;
@@ -648,8 +585,7 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
     if (piped) {
         if (int rc = grid_check_catalog(p, &hc.d)) return rc;
         if (int rc = gather_workspace(p)) return rc;
-        while ((int)e->ev_up.size() < C) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_up.push_back(v); }
-        while ((int)e->ev_g.size() < C + 1) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_g.push_back(v); }
+        if (int rc = e->pools(C, C + 1)) return rc;
         // ranges: chunk c = block rows [c rows_per, (c + 1) rows_per); gather range 0 = block row 0 alone, 1 = the rest of chunk 0, c + 1 = chunk c
         const int64_t blocks_per_row = (ndim == 3) ? (int64_t)nbk * nbk : nbk;
         auto row0 = [&](int c) { return std::min(c * rows_per, nbk); };
@@ -665,7 +601,7 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
             HIP_TRY(hipMemcpyAsync(d_in + lo, map_in + lo, n * sizeof(double), hipMemcpyHostToDevice, e->up));
             HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
         }
-        HIP_TRY(hipEventRecord(e->ev_t[1], e->up));                          // the last byte of the map has arrived
+        HIP_TRY(hipEventRecord(e->ev[1], e->up));                          // the last byte of the map has arrived
         if (int rc = grid_lists_stage(p, &hc.d, gr)) return rc;
         // How far may a cell move along the first array axis in this route?  Range 1 (the rest of chunk 0) is gathered when only chunks 0 and 1
         // hold their start values: a deposit that travels back through block row 0 and across the periodic face lands in the LAST chunk before
@@ -688,18 +624,18 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
             if (c >= 1) {
                 // chunk c - 1 has its own cells and both neighbours' start values (chunk 0: all but its first block row, which needs the LAST chunk)
                 if (int rc = grid_gather_stage(p, d_in, d_out, gr, c - 1 == 0 ? 1 : c)) return rc;
-                HIP_TRY(hipEventRecord(e->ev_g[c - 1], s));
-                if (c - 2 >= 1) if (int rc = download(c - 2, e->ev_g[c - 1])) return rc;      // nothing deposits into chunk c - 2 any more
+                HIP_TRY(hipEventRecord(e->ev_k[c - 1], s));
+                if (c - 2 >= 1) if (int rc = download(c - 2, e->ev_k[c - 1])) return rc;      // nothing deposits into chunk c - 2 any more
             }
         }
         if (int rc = grid_gather_stage(p, d_in, d_out, gr, C)) return rc;                      // the last chunk (deposits into plane 0: chunk 0 is all there)
         if (int rc = grid_gather_stage(p, d_in, d_out, gr, 0)) return rc;                      // block row 0 (deposits into the last plane)
-        HIP_TRY(hipEventRecord(e->ev_g[C - 1], s));
+        HIP_TRY(hipEventRecord(e->ev_k[C - 1], s));
         if (int rc = grid_sums_stage(p, C * nwg, d_sums, &npairs)) return rc;                  // (synchronises the plan's stream)
-        HIP_TRY(hipEventRecord(e->ev_t[2], s));
-        if (C - 2 >= 1) if (int rc = download(C - 2, e->ev_g[C - 1])) return rc;
-        if (int rc = download(C - 1, e->ev_g[C - 1])) return rc;
-        if (int rc = download(0, e->ev_g[C - 1])) return rc;
+        HIP_TRY(hipEventRecord(e->ev[2], s));
+        if (C - 2 >= 1) if (int rc = download(C - 2, e->ev_k[C - 1])) return rc;
+        if (int rc = download(C - 1, e->ev_k[C - 1])) return rc;
+        if (int rc = download(0, e->ev_k[C - 1])) return rc;
         int32_t moved_too_far = 0;
         HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(&moved_too_far, p->axis0_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -712,22 +648,22 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
             ++g_grid_pipe_fallbacks;
             HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(double), s));
             if (int rc = bfgx_grid_baryonify_device(p, &hc.d, d_in, d_out, d_sums, &npairs)) return rc;
-            HIP_TRY(hipEventRecord(e->ev_t[2], s));
+            HIP_TRY(hipEventRecord(e->ev[2], s));
             HIP_TRY(hipMemcpyAsync(map_out, d_out, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
-        hipEvent_t endv = e->ev_t[0];                                          // reuse: phases are read before it is re-recorded
-        (void)hipEventElapsedTime(&ms_h2d, e->ev_t[0], e->ev_t[1]);
-        (void)hipEventElapsedTime(&ms_k, e->ev_t[1], e->ev_t[2]);
+        hipEvent_t endv = e->ev[0];                                          // reuse: phases are read before it is re-recorded
+        (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
+        (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
         if (ms_k < 0) ms_k = 0;
         HIP_TRY(hipEventRecord(endv, e->down));
         HIP_TRY(hipEventSynchronize(endv));
-        (void)hipEventElapsedTime(&ms_d2h, e->ev_t[2], endv);
+        (void)hipEventElapsedTime(&ms_d2h, e->ev[2], endv);
     } else {
         // one pass: the whole map up, the cell-owned pass (or the halo-owned kernels), the whole map down
         HIP_TRY(hipMemcpyAsync(d_in, map_in, ntot * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(e->ev_t[1], s));
+        HIP_TRY(hipEventRecord(e->ev[1], s));
         if (scatter) {
             DevBuf d_off;
             if (d_off.alloc(ntot * ndim * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(pix_offsets) failed");
@@ -735,15 +671,15 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
             if (int rc = bfgx_grid_regrid_device(p, d_in, (const double *)d_off.p, d_out, d_sums)) return rc;
             HIP_TRY(hipStreamSynchronize(s));
         } else if (int rc = bfgx_grid_baryonify_device(p, &hc.d, d_in, d_out, d_sums, &npairs)) return rc;
-        HIP_TRY(hipEventRecord(e->ev_t[2], s));
+        HIP_TRY(hipEventRecord(e->ev[2], s));
         HIP_TRY(hipMemcpyAsync(map_out, d_out, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        (void)hipEventElapsedTime(&ms_h2d, e->ev_t[0], e->ev_t[1]);
-        (void)hipEventElapsedTime(&ms_k, e->ev_t[1], e->ev_t[2]);
-        HIP_TRY(hipEventRecord(e->ev_t[0], s));
-        HIP_TRY(hipEventSynchronize(e->ev_t[0]));
-        (void)hipEventElapsedTime(&ms_d2h, e->ev_t[2], e->ev_t[0]);
+        (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
+        (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
+        HIP_TRY(hipEventRecord(e->ev[0], s));
+        HIP_TRY(hipEventSynchronize(e->ev[0]));
+        (void)hipEventElapsedTime(&ms_d2h, e->ev[2], e->ev[0]);
     }
     hout.commit();                                           // (a staged result reaches the caller's array)
     if (stats) {
@@ -752,11 +688,7 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
         stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
         stats->n_pairs = npairs;
     }
-    if (o.check_mass) {      // np.isclose(new_sum, old_sum)  (Map2DRunner.py:601-605)
-        if (!(std::fabs(sums[1] - sums[0]) <= 1e-8 + 1e-5 * std::fabs(sums[0])))
-            return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sums[1], sums[0]);
-    }
-    return BFGX_OK;
+    return o.check_mass ? check_mass(sums[0], sums[1]) : BFGX_OK;      // (Map2DRunner.py:601-605)
 }
 
 long long bfgx_debug_grid_pipe_fallbacks(void) { return g_grid_pipe_fallbacks.load(); }
@@ -765,9 +697,7 @@ int bfgx_paint_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, const
                     const bfgx_opts *opts, bfgx_stats *stats)
 {
     if (!cat || !model || !grid || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    bfgx_opts o;
-    std::memset(&o, 0, sizeof(o));
-    if (opts) o = *opts;
+    const bfgx_opts o = entry_opts(opts);
     bfgx_grid_plan *p = nullptr;
     if (int rc = bfgx_grid_plan_create(o.device, nullptr, grid, cat->n, model, &p)) return rc;
     struct Guard { bfgx_grid_plan *p; ~Guard() { bfgx_grid_plan_destroy(p); } } guard{p};       // (its destructor drains the plan's stream first)
@@ -1040,18 +970,20 @@ int bfgx_deposit_particles(int device, int32_t ndim, int64_t n, const double *x,
 
 namespace {
 // device buffers of the records entry below, kept between calls per device (bfgx_cache_clear frees them)
-struct DepRecBuf { void *rec = nullptr, *map = nullptr, *edges = nullptr; size_t rec_bytes = 0, map_bytes = 0, edge_bytes = 0; hipStream_t up = nullptr; };
+struct DepRecBuf {
+    PoolBuf rec, map, edges;                   // (slack: an eighth + 8 bytes)
+    hipStream_t up = nullptr;
+    ~DepRecBuf() { if (up) (void)hipStreamDestroy(up); }
+};
 std::mutex g_deprec_mu;
 std::map<int, DepRecBuf> g_deprec;
 void deprec_release_all()
 {
     std::lock_guard<std::mutex> lk(g_deprec_mu);
-    for (auto &kv : g_deprec) {
-        (void)hipSetDevice(kv.first);
-        for (void *q : {kv.second.rec, kv.second.map, kv.second.edges}) if (q) (void)hipFree(q);
-        if (kv.second.up) (void)hipStreamDestroy(kv.second.up);
+    while (!g_deprec.empty()) {
+        (void)hipSetDevice(g_deprec.begin()->first);
+        g_deprec.erase(g_deprec.begin());
     }
-    g_deprec.clear();
 }
 }  // namespace
 
@@ -1072,15 +1004,7 @@ int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const vo
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
-    auto grow = [&](void **q, size_t *have, size_t want) {
-        if (*have >= want && *q) return 0;
-        if (*q) { (void)hipDeviceSynchronize(); (void)hipFree(*q); *q = nullptr; *have = 0; }
-        const size_t cap = want + want / 8 + 8;
-        if (hipMalloc(q, cap) != hipSuccess) return 1;
-        *have = cap;
-        return 0;
-    };
-    if (grow(&b.rec, &b.rec_bytes, rbytes) || grow(&b.map, &b.map_bytes, mbytes) || grow(&b.edges, &b.edge_bytes, ebytes + 16)) return fail(BFGX_ERR_HIP, "hipMalloc(deposit records) failed");
+    if (b.rec.need(rbytes, 8, 8) || b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return fail(BFGX_ERR_HIP, "hipMalloc(deposit records) failed");
     if (!b.up) HIP_TRY(hipStreamCreateWithFlags(&b.up, hipStreamNonBlocking));
     DrainOnExit drain;
     drain.s[0] = &b.up;
@@ -1091,23 +1015,23 @@ int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const vo
     (void)hin.open(records, rbytes, false, false);           // (large arrays are page-locked for the call; small ones are copied from pageable memory)
     (void)hout.open(map_out, mbytes, true, false);
     hipStream_t s = b.up;
-    HIP_TRY(hipMemcpyAsync(b.edges, edges, ebytes, hipMemcpyHostToDevice, s));
-    if (rbytes) HIP_TRY(hipMemcpyAsync(b.rec, records, rbytes, hipMemcpyHostToDevice, s));
-    const double *base = (const double *)b.rec;
+    HIP_TRY(hipMemcpyAsync(b.edges.p, edges, ebytes, hipMemcpyHostToDevice, s));
+    if (rbytes) HIP_TRY(hipMemcpyAsync(b.rec.p, records, rbytes, hipMemcpyHostToDevice, s));
+    const double *base = (const double *)b.rec.p;
     const int64_t stride = itemsize / 8;
     int32_t nanflag = 0;
     if (off_mass >= 0 && n > 0) {
         // "If you want to make a map, provide a value for the particle mass" (io.py:636): the NaN test of the masses, on the device
-        int32_t *dflag = (int32_t *)((char *)b.edges + ebytes);
+        int32_t *dflag = (int32_t *)((char *)b.edges.p + ebytes);
         HIP_TRY(hipMemsetAsync(dflag, 0, sizeof(int32_t), s));
         hipLaunchKernelGGL(nan_scan_strided_kernel, dim3(2048), dim3(256), 0, s, n, base + off_mass / 8, stride, dflag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&nanflag, dflag, sizeof(nanflag), hipMemcpyDeviceToHost, s));
     }
     if (int rc = deposit_impl(device, (void *)s, ndim, n, base + off_x / 8, base + off_y / 8, ndim == 3 ? base + off_z / 8 : nullptr,
-                              off_mass >= 0 ? base + off_mass / 8 : nullptr, n_grid, (const double *)b.edges, 0, n_grid, (double *)b.map, nullptr, nullptr, nullptr,
+                              off_mass >= 0 ? base + off_mass / 8 : nullptr, n_grid, (const double *)b.edges.p, 0, n_grid, (double *)b.map.p, nullptr, nullptr, nullptr,
                               stride)) return rc;
-    HIP_TRY(hipMemcpyAsync(map_out, b.map, mbytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(map_out, b.map.p, mbytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (nanflag) return fail(BFGX_ERR_ASSERT, "If you want to make a map, provide a value for the particle mass");
     return BFGX_OK;

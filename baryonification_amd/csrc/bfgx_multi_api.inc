@@ -85,7 +85,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
     const int navail = bfgx_device_count();
     if (navail <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
     for (int d = 0; d < ndev; ++d) if (devices[d] < 0 || devices[d] >= navail) return fail(BFGX_ERR_INVALID, "device %d is not visible", devices[d]);
-    const bfgx_opts o = shell_opts(opts);
+    const bfgx_opts o = entry_opts(opts);
     if (o.algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "the multi-device calls use the tiled algorithm (algo 1)");
     const int width = paint ? 1 : 3;
     const int N = ndev;

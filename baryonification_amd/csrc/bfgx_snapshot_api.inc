@@ -276,84 +276,24 @@ int bfgx_baryonify_snapshot(const bfgx_grid_catalog *halos, const bfgx_model *mo
 
 namespace {
 
-// cache of the records entry: plan + one device buffer for the particle records per (device, box, model)
-struct SnapCacheEntry {
-    uint64_t key = 0, key2 = 0, stamp = 0;
-    int64_t table_values = 0;
-    bfgx_snapshot_plan *plan = nullptr;
-    DevBuf rec;
-    size_t rec_bytes = 0;
-    hipStream_t up = nullptr, down = nullptr;
-    std::vector<hipEvent_t> ev_up, ev_k;
-    hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
+// cache of the records entries: plan + one device buffer for the particle records per (device, box, model)
+struct RecordsEntry : CacheEntry<bfgx_snapshot_plan> {
+    PoolBuf rec;
+    GridHostCatalog hc;
 };
-std::mutex g_scache_mu;
-std::vector<SnapCacheEntry *> g_scache;
-uint64_t g_scache_stamp = 0;
-constexpr size_t kSnapCacheMax = 2;
+PlanCache<RecordsEntry, 2> g_snaps;
 constexpr int kSnapChunksMax = 64;
 
-void scache_drop(SnapCacheEntry *e)
+// the cached plan + device record buffer (of at least `bytes`) of the records entries for (device, box, redshift, model); the caller holds
+// g_snaps.mu and has validated the model
+int snap_acquire(int device, const bfgx_model *model, int32_t ndim, double L, double redshift, int64_t nhalo, size_t bytes, RecordsEntry **out)
 {
-    if (e->plan) { (void)hipSetDevice(e->plan->device); bfgx_snapshot_plan_destroy(e->plan); }
-    if (e->up) (void)hipStreamDestroy(e->up);
-    if (e->down) (void)hipStreamDestroy(e->down);
-    for (auto &v : e->ev_up) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_k) (void)hipEventDestroy(v);
-    for (auto &v : e->ev_t) if (v) (void)hipEventDestroy(v);
-    delete e;
-}
-
-// the cached plan + device record buffer of the records entries for (device, box, redshift, model); the caller holds g_scache_mu
-int scache_acquire(int device, const bfgx_model *model, int32_t ndim, double L, double redshift, int64_t nhalo, size_t bytes, SnapCacheEntry **out)
-{
-    uint64_t key = model_key(device, (int64_t)ndim, model, 0), key2 = model_key(device, (int64_t)ndim, model, 1);
+    CacheKey key = model_key(device, model);
     const int ncells = snapshot_cells(ndim);                 // (BFGX_SNAP_CELLS: a plan is built for one cell grid)
-    key = hash_bytes(key, &L, sizeof(L)); key = hash_bytes(key, &redshift, sizeof(redshift)); key = hash_bytes(key, &ncells, sizeof(ncells));
-    key2 = hash_bytes(key2, &L, sizeof(L)); key2 = hash_bytes(key2, &redshift, sizeof(redshift)); key2 = hash_bytes(key2, &ncells, sizeof(ncells));
-    int64_t nvals = 1;
-    for (int d = 0; d < model->table.ndim; ++d) nvals *= model->table.n[d];
-    SnapCacheEntry *e = nullptr;
-    for (SnapCacheEntry *c : g_scache) if (c->key == key && c->key2 == key2 && c->table_values == nvals) e = c;
-    if (e && e->plan && e->plan->max_halos < nhalo) { bfgx_snapshot_plan_destroy(e->plan); e->plan = nullptr; }
-    if (!e) {
-        if (g_scache.size() >= kSnapCacheMax) {
-            size_t lru = 0;
-            for (size_t i = 1; i < g_scache.size(); ++i) if (g_scache[i]->stamp < g_scache[lru]->stamp) lru = i;
-            scache_drop(g_scache[lru]);
-            g_scache.erase(g_scache.begin() + (long)lru);
-        }
-        e = new SnapCacheEntry();
-        e->key = key; e->key2 = key2; e->table_values = nvals;
-        g_scache.push_back(e);
-    }
-    auto bail = [&](int rc) { g_scache.erase(std::find(g_scache.begin(), g_scache.end(), e)); scache_drop(e); return rc; };
-    if (!e->plan) {
-        const int64_t cap = std::max<int64_t>(nhalo + nhalo / 4, 1024);
-        if (int rc = bfgx_snapshot_plan_create(device, nullptr, model, ndim, L, redshift, cap, &e->plan)) { e->plan = nullptr; return bail(rc); }
-    }
-    HIP_TRY(hipSetDevice(device));
-    if (bytes > e->rec_bytes) {
-        if (e->rec.p) { (void)hipDeviceSynchronize(); (void)hipFree(e->rec.p); e->rec.p = nullptr; e->rec_bytes = 0; }
-        const size_t want = bytes + bytes / 8;
-        if (e->rec.alloc(want)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(particle records) failed"));
-        e->rec_bytes = want;
-    }
-    if (!e->up) {
-        if (hipStreamCreateWithFlags(&e->up, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&e->down, hipStreamNonBlocking) != hipSuccess)
-            return bail(fail(BFGX_ERR_HIP, "hipStreamCreate failed"));
-        for (auto &v : e->ev_t) if (hipEventCreate(&v) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipEventCreate failed"));
-    }
-    e->stamp = ++g_scache_stamp;
-    *out = e;
-    return BFGX_OK;
-}
-
-void scache_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_scache_mu);
-    for (SnapCacheEntry *e : g_scache) scache_drop(e);
-    g_scache.clear();
+    key.add(ndim); key.add(L); key.add(redshift); key.add(ncells);
+    auto make = [&](int64_t cap, bfgx_snapshot_plan **p) { return bfgx_snapshot_plan_create(device, nullptr, model, ndim, L, redshift, cap, p); };
+    auto setup = [&](RecordsEntry *e) -> int { return e->rec.need(bytes, 8, 0) ? fail(BFGX_ERR_HIP, "hipMalloc(particle records) failed") : BFGX_OK; };
+    return g_snaps.acquire(key, device, nhalo, make, setup, out);
 }
 
 }  // namespace
@@ -371,17 +311,17 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
         (ndim == 3 && (off_z < 0 || off_z % 8 || off_z + 8 > itemsize)))
         return fail(BFGX_ERR_INVALID, "records must be a multiple of 8 bytes with 8-byte aligned float64 coordinate fields");
     if (int rc = validate_model(model)) return rc;
-    const int device = opts ? opts->device : 0;
-    std::lock_guard<std::mutex> lk(g_scache_mu);
-    SnapCacheEntry *e = nullptr;
-    if (int rc = scache_acquire(device, model, ndim, L, redshift, halos->n, (size_t)n * (size_t)itemsize, &e)) return rc;
+    const int device = entry_opts(opts).device;
+    std::lock_guard<std::mutex> lk(g_snaps.mu);
+    RecordsEntry *e = nullptr;
+    if (int rc = snap_acquire(device, model, ndim, L, redshift, halos->n, (size_t)n * (size_t)itemsize, &e)) return rc;
     bfgx_snapshot_plan *p = e->plan;
     const size_t bytes = (size_t)n * (size_t)itemsize;
     hipStream_t s = p->stream;
     DrainOnExit drain;
     drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.s[2] = &e->down; drain.null_stream = (p->stream == nullptr);
-    GridHostCatalog hc;
-    HIP_TRY(hipEventRecord(e->ev_t[0], s));
+    GridHostCatalog &hc = e->hc;
+    HIP_TRY(hipEventRecord(e->ev[0], s));
     if (int rc = hc.upload(halos, ndim, 0, s)) return rc;
     // ---- the records travel in chunks of at least 16 MB: a chunk is displaced IN PLACE on the device as soon as it has arrived (the halo
     // lists are built underneath the first uploads) and travels back while the next ones arrive.  Page-locked on both sides for the call.
@@ -394,8 +334,7 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
     if (C > 1 && !(hin.open(records_in, bytes, false, stage_small) && hout.open(records_out, bytes, true, stage_small))) C = 1;      // pageable memory: one piece
     const char *src = (C > 1) ? (const char *)hin.use : (const char *)records_in;
     char *dst = (C > 1) ? (char *)hout.use : (char *)records_out;
-    while ((int)e->ev_up.size() < C) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_up.push_back(v); }
-    while ((int)e->ev_k.size() < C) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_k.push_back(v); }
+    if (int rc = e->pools(C, C)) return rc;
     char *d_rec = (char *)e->rec.p;
     auto first = [&](int c) { return (int64_t)(((__int128)n * c) / C); };
     for (int c = 0; c < C; ++c) {
@@ -403,7 +342,7 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
         if (cnt > 0) HIP_TRY(hipMemcpyAsync(d_rec + (size_t)lo * itemsize, src + (size_t)lo * itemsize, (size_t)cnt * itemsize, hipMemcpyHostToDevice, e->up));
         HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
     }
-    HIP_TRY(hipEventRecord(e->ev_t[1], e->up));
+    HIP_TRY(hipEventRecord(e->ev[1], e->up));
     if (int rc = snap_lists_stage(p, &hc.d)) return rc;
     const int64_t stride = itemsize / 8;
     for (int c = 0; c < C; ++c) {
@@ -416,7 +355,7 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
         HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
         if (cnt > 0) HIP_TRY(hipMemcpyAsync(dst + (size_t)lo * itemsize, d_rec + (size_t)lo * itemsize, (size_t)cnt * itemsize, hipMemcpyDeviceToHost, e->down));
     }
-    HIP_TRY(hipEventRecord(e->ev_t[2], s));
+    HIP_TRY(hipEventRecord(e->ev[2], s));
     int64_t npairs = 0;
     const int rc_fin = snap_finish_stage(p, &npairs);
     HIP_TRY(hipStreamSynchronize(e->down));
@@ -424,11 +363,11 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
     if (rc_fin) return rc_fin;
     if (C > 1) hout.commit();
     float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
-    (void)hipEventElapsedTime(&ms_h2d, e->ev_t[0], e->ev_t[1]);
-    (void)hipEventElapsedTime(&ms_k, e->ev_t[1], e->ev_t[2]);
-    HIP_TRY(hipEventRecord(e->ev_t[0], e->down));
-    HIP_TRY(hipEventSynchronize(e->ev_t[0]));
-    (void)hipEventElapsedTime(&ms_d2h, e->ev_t[2], e->ev_t[0]);
+    (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
+    (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
+    HIP_TRY(hipEventRecord(e->ev[0], e->down));
+    HIP_TRY(hipEventSynchronize(e->ev[0]));
+    (void)hipEventElapsedTime(&ms_d2h, e->ev[2], e->ev[0]);
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->n_pairs = npairs; stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k < 0 ? 0 : ms_k; stats->ms_d2h = ms_d2h < 0 ? 0 : ms_d2h;
@@ -451,41 +390,33 @@ int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bf
         return fail(BFGX_ERR_INVALID, "records must be a multiple of 8 bytes with 8-byte aligned float64 fields");
     for (int i = 1; i <= n_grid; ++i) if (!(edges[i] > edges[i - 1])) return fail(BFGX_ERR_INVALID, "edges must be strictly ascending");
     if (int rc = validate_model(model)) return rc;
-    const int device = opts ? opts->device : 0;
-    std::lock_guard<std::mutex> lk(g_scache_mu);
-    SnapCacheEntry *e = nullptr;
-    if (int rc = scache_acquire(device, model, ndim, L, redshift, halos->n, (size_t)n * (size_t)itemsize, &e)) return rc;
+    const int device = entry_opts(opts).device;
+    std::lock_guard<std::mutex> lk(g_snaps.mu);
+    RecordsEntry *e = nullptr;
+    if (int rc = snap_acquire(device, model, ndim, L, redshift, halos->n, (size_t)n * (size_t)itemsize, &e)) return rc;
     bfgx_snapshot_plan *p = e->plan;
     std::lock_guard<std::mutex> lk2(g_deprec_mu);
     DepRecBuf &b = g_deprec[device];
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
-    auto grow = [&](void **q, size_t *have, size_t want) {
-        if (*have >= want && *q) return 0;
-        if (*q) { (void)hipDeviceSynchronize(); (void)hipFree(*q); *q = nullptr; *have = 0; }
-        const size_t cap = want + want / 8 + 8;
-        if (hipMalloc(q, cap) != hipSuccess) return 1;
-        *have = cap;
-        return 0;
-    };
-    if (grow(&b.map, &b.map_bytes, mbytes) || grow(&b.edges, &b.edge_bytes, ebytes + 16)) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
+    if (b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
     hipStream_t s = p->stream;
     DrainOnExit drain;
     drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.null_stream = (p->stream == nullptr);
-    GridHostCatalog hc;
-    HIP_TRY(hipEventRecord(e->ev_t[0], s));
+    GridHostCatalog &hc = e->hc;
+    HIP_TRY(hipEventRecord(e->ev[0], s));
     if (int rc = hc.upload(halos, ndim, 0, s)) return rc;
     HostSpan hin, hout;
     hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &p->stream;
     (void)hin.open(records_in, rbytes, false, false);        // (large arrays are page-locked for the call; small ones go up from pageable memory)
     (void)hout.open(map_out, mbytes, true, false);
     // the records go up on their own stream while the halo lists are built
-    HIP_TRY(hipMemcpyAsync(b.edges, edges, ebytes, hipMemcpyHostToDevice, e->up));
+    HIP_TRY(hipMemcpyAsync(b.edges.p, edges, ebytes, hipMemcpyHostToDevice, e->up));
     if (rbytes) HIP_TRY(hipMemcpyAsync(e->rec.p, records_in, rbytes, hipMemcpyHostToDevice, e->up));
-    while (e->ev_up.empty()) { hipEvent_t v; HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming)); e->ev_up.push_back(v); }
+    if (int rc = e->pools(1, 0)) return rc;
     HIP_TRY(hipEventRecord(e->ev_up[0], e->up));
-    HIP_TRY(hipEventRecord(e->ev_t[1], e->up));
+    HIP_TRY(hipEventRecord(e->ev[1], e->up));
     if (int rc = snap_lists_stage(p, &hc.d)) return rc;
     HIP_TRY(hipStreamWaitEvent(s, e->ev_up[0], 0));
     const double *base = (const double *)e->rec.p;
@@ -493,23 +424,23 @@ int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bf
     int32_t nanflag = 0;
     if (off_mass >= 0 && n > 0) {
         // "If you want to make a map, provide a value for the particle mass" (io.py:636): the NaN test of the masses, on the device
-        int32_t *dflag = (int32_t *)((char *)b.edges + ebytes);
+        int32_t *dflag = (int32_t *)((char *)b.edges.p + ebytes);
         HIP_TRY(hipMemsetAsync(dflag, 0, sizeof(int32_t), s));
         hipLaunchKernelGGL(nan_scan_strided_kernel, dim3(2048), dim3(256), 0, s, n, base + off_mass / 8, stride, dflag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&nanflag, dflag, sizeof(nanflag), hipMemcpyDeviceToHost, s));
     }
     if (int rc = snap_displace_deposit_stage(p, n, base + off_x / 8, base + off_y / 8, ndim == 3 ? base + off_z / 8 : nullptr,
-                                             off_mass >= 0 ? base + off_mass / 8 : nullptr, stride, n_grid, (const double *)b.edges, (double *)b.map)) return rc;
-    HIP_TRY(hipEventRecord(e->ev_t[2], s));
-    HIP_TRY(hipMemcpyAsync(map_out, b.map, mbytes, hipMemcpyDeviceToHost, s));
+                                             off_mass >= 0 ? base + off_mass / 8 : nullptr, stride, n_grid, (const double *)b.edges.p, (double *)b.map.p)) return rc;
+    HIP_TRY(hipEventRecord(e->ev[2], s));
+    HIP_TRY(hipMemcpyAsync(map_out, b.map.p, mbytes, hipMemcpyDeviceToHost, s));
     int64_t npairs = 0;
     if (int rc = snap_finish_stage(p, &npairs)) return rc;                      // (synchronises the stream: the map has arrived)
     HIP_TRY(hipStreamSynchronize(e->up));
     if (nanflag) return fail(BFGX_ERR_ASSERT, "If you want to make a map, provide a value for the particle mass");
     float ms_h2d = 0, ms_k = 0;
-    (void)hipEventElapsedTime(&ms_h2d, e->ev_t[0], e->ev_t[1]);
-    (void)hipEventElapsedTime(&ms_k, e->ev_t[1], e->ev_t[2]);
+    (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
+    (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->n_pairs = npairs; stats->ms_h2d = ms_h2d < 0 ? 0 : ms_h2d; stats->ms_kernels = ms_k < 0 ? 0 : ms_k;

@@ -182,9 +182,10 @@ int bfgx_baryonify_shell_multi(const bfgx_catalog *cat_host, const bfgx_model *m
 int bfgx_paint_shell_multi(const bfgx_catalog *cat_host, const bfgx_model *model, int64_t nside, double *map_out_host,
                            int32_t ndev, const int32_t *devices, const bfgx_opts *opts, bfgx_stats *stats);
 
-/* The one-shot calls keep the plan (model on the device, tiling, binning workspace) and their device buffers in a small
- * process-wide cache keyed by (device, nside, model contents): a repeated call with the same model performs no device
- * allocation.  bfgx_cache_clear frees the cache; bfgx_debug_alloc_count = device allocations made so far (tests).
+/* The one-shot calls keep the plan (model on the device, tiling, binning workspace) and their device buffers in small
+ * process-wide caches keyed by (device, model contents, nside / grid / box): a repeated call with the same model performs no
+ * device allocation.  The shell, grid and snapshot-records entries each have a cache and a lock of their own.
+ * bfgx_cache_clear frees the caches; bfgx_debug_alloc_count = device allocations made so far (tests).
  * bfgx_host_alloc / bfgx_host_free: page-locked host memory for map_out (D2H at full PCIe rate; plain memory works too). */
 void      bfgx_cache_clear(void);
 long long bfgx_debug_alloc_count(void);

@@ -778,6 +778,22 @@ def test_grid_host_entry_in_plane_ranges_equals_one_pass(gpu, monkeypatch, ndim,
     assert np.abs(piped - ora).max() <= 1e-10 * np.abs(ora).max()
 
 
+def test_grid_warm_process_call_allocates_nothing(gpu):
+    """BaryonifyGrid.process() re-uses the cached plan, device maps and catalog columns: warm calls make no device allocation"""
+    from baryonification_amd import _lib
+    L = _lib.load()
+    L.bfgx_cache_clear()
+    runner = H.grid_product_runner(H.load_grid_golden('grid3d_baryonify'))
+    out1 = runner.process().copy()
+    n = L.bfgx_debug_alloc_count()
+    out2 = runner.process().copy()
+    out3 = runner.process().copy()
+    assert L.bfgx_debug_alloc_count() == n
+    for o in (out2, out3):
+        assert np.array_equal(o, out1) or np.abs(o - out1).max() <= 1e-13 * np.abs(out1).max()
+    L.bfgx_cache_clear()
+
+
 @pytest.mark.parametrize('ndim,N,nh,chunks,scale', [(3, 96, 300, 6, 3000.0), (2, 512, 200, 8, 6000.0)])
 def test_grid_host_entry_in_plane_ranges_with_large_moves_along_the_first_axis(gpu, monkeypatch, ndim, N, nh, chunks, scale):
     """The streamed route gathers the map in ranges of planes of the first array axis, and a deposit may only travel 2^S - 1 cells (7 in 3-D, 15

@@ -177,6 +177,25 @@ def test_snapshot_records_entry_streamed_equals_columns(gpu, monkeypatch, ndim, 
     assert out.dtype == odd.dtype and same(out['x'], cols['x']) and np.array_equal(out['tag'], odd['tag'])
 
 
+def test_snapshot_records_warm_process_call_allocates_nothing(gpu):
+    """BaryonifySnapshot.process() through the records entry re-uses the cached plan, record buffer and catalog columns: warm calls
+    make no device allocation"""
+    from baryonification_amd import _lib
+    L = _lib.load()
+    L.bfgx_cache_clear()
+    g = H.load_snapshot_golden('snap3d_baryonify')
+    runner = H.snapshot_product_runner(g)
+    runner.use_records = True
+    out1 = _positions(runner.process(), g['ndim'])
+    n = L.bfgx_debug_alloc_count()
+    out2 = _positions(runner.process(), g['ndim'])
+    out3 = _positions(runner.process(), g['ndim'])
+    assert L.bfgx_debug_alloc_count() == n
+    for o in (out2, out3):             # (a particle inside several balls sums their offsets in the order the LDS adds arrive)
+        assert np.array_equal(np.isnan(o), np.isnan(out1)) and np.nanmax(np.abs(o - out1), initial=0.0) <= 1e-13 * g['L']
+    L.bfgx_cache_clear()
+
+
 @pytest.mark.parametrize('ndim,n_grid,masses', [(3, 64, False), (3, 50, True), (2, 256, False), (2, 333, True)])
 def test_snapshot_displace_deposit_fused_equals_process_then_make_map(gpu, ndim, n_grid, masses):
     """bfgx_snapshot_displace_deposit_device (the displacement kernel writes the deposit's sort keys; the displaced coordinates are never

@@ -217,6 +217,64 @@ def test_warm_process_call_allocates_nothing(gpu):
     _lib.pinned_pool_clear()
 
 
+def _agree(a, b):
+    """equal, or equal up to the order of the LDS adds (the last bits may differ from call to call)"""
+    return np.array_equal(a, b) or np.abs(a - b).max() <= 1e-13 * np.abs(a).max()
+
+
+@pytest.mark.gpu
+def test_shell_cache_evicts_the_least_recently_used_model(gpu):
+    """the shell entries keep the plans of four models: a fifth evicts the one used longest ago, which then allocates again"""
+    from baryonification_amd import _lib
+    L = _lib.load()
+    L.bfgx_cache_clear()
+    g = load_golden('lowz_baryonify')
+    runners = [product_runner(dict(g, tab_values=g['tab_values'] * f), acc_f64=True) for f in (1.0, 0.9, 0.8, 0.7, 0.6)]
+    for r in runners:
+        r.process()
+    n = L.bfgx_debug_alloc_count()
+    runners[4].process()                                             # model 5: still cached
+    assert L.bfgx_debug_alloc_count() == n
+    runners[0].process()                                             # model 1: evicted when model 5 came in
+    assert L.bfgx_debug_alloc_count() > n
+    L.bfgx_cache_clear()
+
+
+@pytest.mark.gpu
+def test_shell_and_grid_calls_run_concurrently(gpu):
+    """the shell and grid entries have a cache (and a lock) each: warm calls from two threads at once give the results of
+    sequential calls and allocate nothing"""
+    import threading
+    from baryonification_amd import _lib
+    from helpers import grid_product_runner, load_grid_golden
+    L = _lib.load()
+    L.bfgx_cache_clear()
+    shell = product_runner(load_golden('lowz_baryonify'), acc_f64=True)
+    grid = grid_product_runner(load_grid_golden('grid3d_baryonify'))
+    ref = {'shell': shell.process().copy(), 'grid': grid.process().copy()}
+    n = L.bfgx_debug_alloc_count()
+    out = {'shell': [], 'grid': []}
+    errors = []
+
+    def work(name, runner):
+        try:
+            for _ in range(4):
+                out[name].append(runner.process().copy())
+        except Exception as e:          # (re-raised in the main thread)
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=('shell', shell)), threading.Thread(target=work, args=('grid', grid))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert L.bfgx_debug_alloc_count() == n
+    for name in ('shell', 'grid'):
+        assert len(out[name]) == 4 and all(_agree(ref[name], o) for o in out[name]), name
+    L.bfgx_cache_clear()
+
+
 @pytest.mark.gpu
 def test_in_place_catalog_edit_between_calls_is_seen(gpu):
     """the contiguous catalog columns are cached on the catalog object between process() calls; an in-place edit of ONE halo that a
