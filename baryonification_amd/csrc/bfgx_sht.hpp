@@ -1,5 +1,6 @@
-// bfgx_sht.hpp -- scalar (spin-0) spherical-harmonic transforms of RING-ordered HEALPix maps in fp64 (healpy.map2alm /
-// alm2map / alm2cl / anafast, the last step of reference notebooks 04, 05 and 09) for gfx950.
+// bfgx_sht.hpp -- spherical-harmonic transforms of RING-ordered HEALPix maps in fp64 for gfx950: scalar (spin 0: healpy.map2alm /
+// alm2map / alm2cl / anafast, the last step of reference notebooks 04, 05 and 09) and spin-weighted (healpy.map2alm_spin /
+// alm2map_spin, weak lensing of shells; the spin Legendre stage is described above sht_spin_legendre_analysis_kernel).
 //
 // Two stages per transform:
 //  * ring stage, one workgroup per ring: a ring of n = 4k pixels (k = ring number in the caps, nside in the belt) is split into
@@ -390,6 +391,278 @@ sht_legendre_synthesis_kernel(const double2 *__restrict__ alm, const Ring *__res
                 const int rs = nrings - 1 - p;
                 G[(int64_t)m * nrings + p] = add2(ge[r], go[r]);
                 if (rs != p) G[(int64_t)m * nrings + rs] = sub2(ge[r], go[r]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- spin-weighted Legendre stage
+// Spin-s transforms (healpy map2alm_spin / alm2map_spin, HEALPix/libsharp convention) of a pair of real maps:
+//   map0 + i map1 = -sum_{l >= s} sum_{m = -l..l} (G_lm + i C_lm) sY_lm,   sY_lm(theta, phi) = slambda_lm(theta) e^{i m phi},
+// G and C the coefficients of real fields (only m >= 0 stored).  Per m >= 0 a lane runs two columns in l:
+//   lam+ = slambda_lm,  lam- = (-1)^m slambda_{l,-m},
+// both by the normalised Wigner-d recurrence lam_L = a_L (x +- b_L) lam_{L-1} - c_L lam_{L-2} (b_L = m s / (L (L - 1)); + for lam+,
+// - for lam-), from l0 = max(m, s) with
+//   lam+_{l0} = (-1)^m P cos^|m-s|(theta/2) sin^(m+s)(theta/2),  lam-_{l0} = (m >= s ? (-1)^(m+s) : 1) P cos^(m+s)(theta/2) sin^|m-s|(theta/2),
+//   P = sqrt((2 l0 + 1) / (4 pi) binom(2 l0, m + s)).
+// The south ring of a pair follows from lam+(pi - theta) = (-1)^(l+m+s) lam-(theta) and lam-(pi - theta) = (-1)^(l+m+s) lam+(theta).
+// With P = F0 + i F1 and M = F0 - i F1 (F0, F1: ring stage of map0, map1) the analysis is G + i C = -sum lam+ P, G - i C = -sum lam- M;
+// the synthesis is F0 + i F1 = -sum_l (G + i C) lam+, F0 - i F1 = -sum_l (G - i C) lam-.  Both columns keep their own
+// (value, scale index) as lambda_mm does: P and the powers of cos and sin(theta/2) are built with exact exponents.
+constexpr int kSpinRings = 2;             // ring pairs per lane (two columns, four inputs or outputs per ring)
+
+// mant 2^e *= x^n for x > 0, the exponent kept exactly (binary powering with frexp)
+__device__ inline void mul_pow(double &mant, int &e, double x, int n)
+{
+    int be, t;
+    double b = frexp(x, &be);
+    for (int nn = n; nn; nn >>= 1) {
+        if (nn & 1) { mant = frexp(mant * b, &t); e += t + be; }
+        b = frexp(b * b, &t);
+        be = 2 * be + t;
+    }
+}
+
+// mant 2^e as (value, scale index): true = value 2^(512 k), |value| in [2^-256, 2^256)
+__device__ inline void to_scaled(double mant, int e, double &v, int &k)
+{
+    k = (e + 256) >= 0 ? (e + 256) / 512 : -((-(e + 256) + 511) / 512);
+    v = ldexp(mant, e - 512 * k);
+}
+
+// P = sqrt((2 l0 + 1) / (4 pi) binom(2 l0, l0 + t)), l0 = max(m, s), t = min(m, s), as mant 2^e.  binom(2 l0, l0 + t) =
+// 4^l0 prod_{k <= l0} (2k - 1) / (2k) prod_{i <= t} (l0 - t + i) / (l0 + i); for m >= s the first two factors are the spin-0
+// prefactor pref[m]^2 (4 pi / (2m + 1)) of the plan
+__device__ inline void spin_pref(const double *__restrict__ pref, int m, int s, double &mant, int &e)
+{
+    const int l0 = max(m, s), t = min(m, s);
+    int tt;
+    mant = 1.0; e = 0;
+    for (int i = 1; i <= t; ++i) { mant = frexp(mant * ((double)(l0 - t + i) / (double)(l0 + i)), &tt); e += tt; }
+    double base;
+    if (m >= s) base = fabs(pref[m]);
+    else {
+        double q = (2.0 * s + 1.0) / (4.0 * M_PI);
+        for (int k = 1; k <= s; ++k) q *= (2.0 * k - 1.0) / (2.0 * k);
+        base = sqrt(q);
+    }
+    if (e & 1) { mant *= 2.0; --e; }
+    mant = frexp(base * sqrt(mant), &tt);
+    e = e / 2 + l0 + tt;
+}
+
+// start values of both columns at l0 on a north ring (z >= 0): cos(theta/2) from z, sin(theta/2) = sin(theta) / (2 cos(theta/2))
+__device__ inline void spin_start(double pmant, int pe, int m, int s, double z, double sn, double &vp, int &kp, double &vm, int &km)
+{
+    const double c = sqrt(0.5 * (1.0 + z)), h = sn / (2.0 * c);
+    const int d = abs(m - s);
+    double mp = pmant, mm = pmant;
+    int ep = pe, em = pe;
+    mul_pow(mp, ep, c, d);
+    mul_pow(mp, ep, h, m + s);
+    mul_pow(mm, em, c, m + s);
+    mul_pow(mm, em, h, d);
+    to_scaled((m & 1) ? -mp : mp, ep, vp, kp);
+    to_scaled((m >= s && ((m + s) & 1)) ? -mm : mm, em, vm, km);
+}
+
+// a_L, a_L b_L and c_L of the spin recurrence (0 beyond lmax and for L <= l0, so that a last block runs on harmlessly)
+__device__ inline void spin_rec_coef(int L, int m, int s, int lmax, double &a, double &ab, double &c)
+{
+    if (L > lmax || L <= max(m, s)) { a = 0.0; ab = 0.0; c = 0.0; return; }
+    const double dl = L, dm = m, ds = s, d1 = dl - 1.0;
+    const double den = (dl * dl - dm * dm) * (dl * dl - ds * ds);
+    a = dl * sqrt((2.0 * dl + 1.0) * (2.0 * dl - 1.0) / den);
+    ab = a * (dm * ds) / (dl * d1);
+    c = (dl / d1) * sqrt((2.0 * dl + 1.0) / (2.0 * dl - 3.0) * ((d1 * d1 - dm * dm) * (d1 * d1 - ds * ds)) / den);
+}
+
+__device__ inline double2 neg2(double2 a) { return make_double2(-a.x, -a.y); }
+
+// spin analysis Legendre stage: G, C [l, m] for l = max(m, s) .. lmax (0 for m <= l < s), one workgroup per m.  A lane accumulates
+// Ap = sum lam+ P and Am = sum lam- M for 16 l in registers; the reduce-scatter and the fixed-order row sum are those of
+// sht_legendre_analysis_kernel, once for Ap and once for Am; then G = -(Ap + Am) / 2, C = i (Ap - Am) / 2.
+__global__ void __launch_bounds__(kLegThreads)
+sht_spin_legendre_analysis_kernel(const double2 *__restrict__ F0, const double2 *__restrict__ F1, const Ring *__restrict__ rings, int nside,
+                                  int lmax, int spin, const double *__restrict__ pref, double2 *__restrict__ almG, double2 *__restrict__ almC)
+{
+    __shared__ double cA[2][kLB], cAB[2][kLB], cC[2][kLB];        // a, a b, c of l0 + 1 + j
+    __shared__ double2 red[2][2][kLegThreads / kLB][kLB];          // per-row partial sums of Ap, Am
+    const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int nrings = 4 * nside - 1, npairs = 2 * nside, ls = max(m, spin);
+    const int64_t a0 = alm_index(lmax, 0, m);
+    for (int l = m + tid; l < ls; l += kLegThreads) { almG[a0 + l] = make_double2(0.0, 0.0); almC[a0 + l] = make_double2(0.0, 0.0); }
+    double pmant;
+    int pe;
+    spin_pref(pref, m, spin, pmant, pe);
+    const int nchunks = (npairs + kLegThreads * kSpinRings - 1) / (kLegThreads * kSpinRings);
+    int cb = 0;
+    for (int ch = 0; ch < nchunks; ++ch) {
+        double x[kSpinRings], p0[kSpinRings], p1[kSpinRings], q0[kSpinRings], q1[kSpinRings];
+        int kp[kSpinRings], km[kSpinRings];
+        double2 PN[kSpinRings], MN[kSpinRings], PS[kSpinRings], MS[kSpinRings];
+#pragma unroll
+        for (int r = 0; r < kSpinRings; ++r) {
+            const int p = (ch * kSpinRings + r) * kLegThreads + tid;
+            double sn = 1.0;
+            x[r] = 0.0;
+            PN[r] = MN[r] = PS[r] = MS[r] = make_double2(0.0, 0.0);
+            if (p < npairs) {
+                const Ring R = rings[p];
+                const int rs = nrings - 1 - p;
+                x[r] = R.z; sn = R.s;
+                const double2 a = F0[(int64_t)m * nrings + p], b = F1[(int64_t)m * nrings + p];
+                PN[r] = make_double2(a.x - b.y, a.y + b.x); MN[r] = make_double2(a.x + b.y, a.y - b.x);
+                if (rs != p) {
+                    const double2 c = F0[(int64_t)m * nrings + rs], d = F1[(int64_t)m * nrings + rs];
+                    PS[r] = make_double2(c.x - d.y, c.y + d.x); MS[r] = make_double2(c.x + d.y, c.y - d.x);
+                }
+            }
+            spin_start(pmant, pe, m, spin, x[r], sn, p1[r], kp[r], q1[r], km[r]);
+            p0[r] = q0[r] = 0.0;
+        }
+        for (int l0 = ls; l0 <= lmax; l0 += kLB) {
+            if (tid < kLB) spin_rec_coef(l0 + 1 + tid, m, spin, lmax, cA[cb][tid], cAB[cb][tid], cC[cb][tid]);
+            __syncthreads();
+            double2 ap[kLB], am[kLB];
+#pragma unroll
+            for (int j = 0; j < kLB; ++j) ap[j] = am[j] = make_double2(0.0, 0.0);
+            const double sg0 = ((l0 + m + spin) & 1) ? -1.0 : 1.0;      // (-1)^(l+m+s) at l = l0
+#pragma unroll
+            for (int r = 0; r < kSpinRings; ++r) {
+                const double onp = kp[r] == 0 ? 1.0 : 0.0, onm = km[r] == 0 ? 1.0 : 0.0;
+                const double2 pn = scl2(PN[r], onp), ms = scl2(MS[r], onp * sg0), mn = scl2(MN[r], onm), ps = scl2(PS[r], onm * sg0);
+                double a = p0[r], b = p1[r], c = q0[r], d = q1[r];
+                const double xr = x[r];
+#pragma unroll
+                for (int j = 0; j < kLB; ++j) {
+                    const double2 psj = (j & 1) ? neg2(ps) : ps, msj = (j & 1) ? neg2(ms) : ms;
+                    ap[j].x = fma(b, pn.x, ap[j].x); ap[j].y = fma(b, pn.y, ap[j].y);
+                    ap[j].x = fma(d, psj.x, ap[j].x); ap[j].y = fma(d, psj.y, ap[j].y);
+                    am[j].x = fma(d, mn.x, am[j].x); am[j].y = fma(d, mn.y, am[j].y);
+                    am[j].x = fma(b, msj.x, am[j].x); am[j].y = fma(b, msj.y, am[j].y);
+                    const double A = cA[cb][j], AB = cAB[cb][j], C = cC[cb][j];
+                    const double nb = fma(fma(A, xr, AB), b, -C * a), nd = fma(fma(A, xr, -AB), d, -C * c);
+                    a = b; b = nb; c = d; d = nd;
+                }
+                p0[r] = a; p1[r] = b; q0[r] = c; q1[r] = d;
+                rescale(p0[r], p1[r], kp[r]);
+                rescale(q0[r], q1[r], km[r]);
+            }
+            rs_level<8, 0x140>(ap, lane & 8); rs_level<8, 0x140>(am, lane & 8);
+            rs_level<4, 0x141>(ap, lane & 4); rs_level<4, 0x141>(am, lane & 4);
+            rs_level<2, 0x1B>(ap, lane & 2);  rs_level<2, 0x1B>(am, lane & 2);
+            rs_level<1, 0xB1>(ap, lane & 1);  rs_level<1, 0xB1>(am, lane & 1);
+            red[cb][0][tid >> 4][tid & 15] = ap[0];
+            red[cb][1][tid >> 4][tid & 15] = am[0];
+            __syncthreads();
+            if (tid < 4 * kLB) {
+                // c = 0: Re G = -(Ap + Am).x / 2, 1: Im G = -(Ap + Am).y / 2, 2: Re C = -(Ap - Am).y / 2, 3: Im C = (Ap - Am).x / 2
+                const int j = tid >> 2, c = tid & 3;
+                const bool useY = c == 1 || c == 2;
+                double sp = 0.0, sm = 0.0;
+                for (int w = 0; w < kLegThreads / kLB; ++w) {
+                    sp += useY ? red[cb][0][w][j].y : red[cb][0][w][j].x;
+                    sm += useY ? red[cb][1][w][j].y : red[cb][1][w][j].x;
+                }
+                const double v = (c < 2) ? -0.5 * (sp + sm) : (c == 2 ? -0.5 * (sp - sm) : 0.5 * (sp - sm));
+                const int l = l0 + j;
+                if (l <= lmax) {
+                    double *dst = reinterpret_cast<double *>((c < 2 ? almG : almC) + a0 + l) + (c & 1);
+                    *dst = ch == 0 ? v : *dst + v;
+                }
+            }
+            cb ^= 1;
+        }
+    }
+}
+
+// spin synthesis Legendre stage: F0, F1 [m][ring] from G, C (l >= max(m, s); Im G_l0, Im C_l0 drop out in the ring stage), one
+// workgroup per m, no reduction
+__global__ void __launch_bounds__(kLegThreads)
+sht_spin_legendre_synthesis_kernel(const double2 *__restrict__ almG, const double2 *__restrict__ almC, const Ring *__restrict__ rings,
+                                   int nside, int lmax, int spin, const double *__restrict__ pref, double2 *__restrict__ F0,
+                                   double2 *__restrict__ F1)
+{
+    __shared__ double2 sP[kSynL], sM[kSynL];                       // G + i C and G - i C of l = L0 + j
+    __shared__ double sA[kSynL], sAB[kSynL], sC[kSynL];            // a, a b, c of L0 + 1 + j
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int nrings = 4 * nside - 1, npairs = 2 * nside, ls = max(m, spin);
+    const int64_t a0 = alm_index(lmax, 0, m);
+    double pmant;
+    int pe;
+    spin_pref(pref, m, spin, pmant, pe);
+    const int nchunks = (npairs + kLegThreads * kSpinRings - 1) / (kLegThreads * kSpinRings);
+    for (int ch = 0; ch < nchunks; ++ch) {
+        double x[kSpinRings], p0[kSpinRings], p1[kSpinRings], q0[kSpinRings], q1[kSpinRings];
+        int kp[kSpinRings], km[kSpinRings];
+        double2 QPN[kSpinRings], QMN[kSpinRings], QPS[kSpinRings], QMS[kSpinRings];
+#pragma unroll
+        for (int r = 0; r < kSpinRings; ++r) {
+            const int p = (ch * kSpinRings + r) * kLegThreads + tid;
+            double sn = 1.0;
+            x[r] = 0.0;
+            if (p < npairs) { x[r] = rings[p].z; sn = rings[p].s; }
+            spin_start(pmant, pe, m, spin, x[r], sn, p1[r], kp[r], q1[r], km[r]);
+            p0[r] = q0[r] = 0.0;
+            QPN[r] = QMN[r] = QPS[r] = QMS[r] = make_double2(0.0, 0.0);
+        }
+        for (int L0 = ls; L0 <= lmax; L0 += kSynL) {
+            __syncthreads();
+            for (int j = tid; j < kSynL; j += kLegThreads) {
+                const int l = L0 + j;
+                double2 g = make_double2(0.0, 0.0), c = g;
+                if (l <= lmax) { g = almG[a0 + l]; c = almC[a0 + l]; }
+                sP[j] = make_double2(g.x - c.y, g.y + c.x);
+                sM[j] = make_double2(g.x + c.y, g.y - c.x);
+                spin_rec_coef(l + 1, m, spin, lmax, sA[j], sAB[j], sC[j]);
+            }
+            __syncthreads();
+            const int nb = min(kSynL, lmax - L0 + 1);
+            for (int j0 = 0; j0 < nb; j0 += kLB) {
+                const double sg0 = ((L0 + j0 + m + spin) & 1) ? -1.0 : 1.0;
+#pragma unroll
+                for (int r = 0; r < kSpinRings; ++r) {
+                    const double onp = kp[r] == 0 ? 1.0 : 0.0, onm = km[r] == 0 ? 1.0 : 0.0;
+                    double a = p0[r], b = p1[r], c = q0[r], d = q1[r];
+                    const double xr = x[r];
+                    double2 pn = make_double2(0.0, 0.0), mn = pn, ps = pn, ms = pn;
+#pragma unroll
+                    for (int j = 0; j < kLB; ++j) {
+                        const double2 P = sP[j0 + j], M = sM[j0 + j];     // (zero beyond lmax)
+                        const double2 Pj = (j & 1) ? neg2(P) : P, Mj = (j & 1) ? neg2(M) : M;
+                        pn.x = fma(b, P.x, pn.x); pn.y = fma(b, P.y, pn.y);
+                        mn.x = fma(d, M.x, mn.x); mn.y = fma(d, M.y, mn.y);
+                        ps.x = fma(d, Pj.x, ps.x); ps.y = fma(d, Pj.y, ps.y);
+                        ms.x = fma(b, Mj.x, ms.x); ms.y = fma(b, Mj.y, ms.y);
+                        const double A = sA[j0 + j], AB = sAB[j0 + j], C = sC[j0 + j];
+                        const double nbv = fma(fma(A, xr, AB), b, -C * a), ndv = fma(fma(A, xr, -AB), d, -C * c);
+                        a = b; b = nbv; c = d; d = ndv;
+                    }
+                    p0[r] = a; p1[r] = b; q0[r] = c; q1[r] = d;
+                    const double fps = onm * sg0, fms = onp * sg0;
+                    QPN[r].x = fma(onp, pn.x, QPN[r].x); QPN[r].y = fma(onp, pn.y, QPN[r].y);
+                    QMN[r].x = fma(onm, mn.x, QMN[r].x); QMN[r].y = fma(onm, mn.y, QMN[r].y);
+                    QPS[r].x = fma(fps, ps.x, QPS[r].x); QPS[r].y = fma(fps, ps.y, QPS[r].y);
+                    QMS[r].x = fma(fms, ms.x, QMS[r].x); QMS[r].y = fma(fms, ms.y, QMS[r].y);
+                    rescale(p0[r], p1[r], kp[r]);
+                    rescale(q0[r], q1[r], km[r]);
+                }
+            }
+        }
+        // F0 = -(Qp + Qm) / 2, F1 = i (Qp - Qm) / 2
+#pragma unroll
+        for (int r = 0; r < kSpinRings; ++r) {
+            const int p = (ch * kSpinRings + r) * kLegThreads + tid;
+            if (p < npairs) {
+                const int rs = nrings - 1 - p;
+                const int64_t on = (int64_t)m * nrings + p, os = (int64_t)m * nrings + rs;
+                F0[on] = scl2(add2(QPN[r], QMN[r]), -0.5);
+                F1[on] = make_double2(-0.5 * (QPN[r].y - QMN[r].y), 0.5 * (QPN[r].x - QMN[r].x));
+                if (rs != p) {
+                    F0[os] = scl2(add2(QPS[r], QMS[r]), -0.5);
+                    F1[os] = make_double2(-0.5 * (QPS[r].y - QMS[r].y), 0.5 * (QPS[r].x - QMS[r].x));
+                }
             }
         }
     }

@@ -4,6 +4,7 @@
 // transform of that shape (all offsets in doubles, 16-byte aligned):
 //   twiddles of every power of two up to Mmax | Bluestein kernels B_k, k = 1..nside | their offsets (int64) | Ring[4 nside - 1] |
 //   lambda_mm prefactors [mmax + 1] | F / G [mmax + 1][4 nside - 1] complex | one map of scratch (iterations of map2alm)
+// The spin entries take a second array of bfgx_sht_spin_work_doubles(nside, lmax, mmax) doubles: the F / G of the second map.
 namespace {
 
 struct ShtLayout {
@@ -123,6 +124,53 @@ int sht_alm2cl(hipStream_t s, int lmax, int mmax, int lmax_out, const double2 *a
 }
 
 int64_t sht_alm_size(int lmax, int mmax) { return (int64_t)(mmax + 1) * (2 * (int64_t)lmax + 2 - mmax) / 2; }
+
+// spin transforms: a second F buffer (F of map1), [mmax + 1][4 nside - 1] complex, outside the spin-0 work array
+int64_t sht_spin_work(const ShtLayout &L) { return 2 * (int64_t)(L.mmax + 1) * L.nrings; }
+
+int sht_spin_check(int32_t lmax, int32_t spin)
+{
+    if (spin < 1) return fail(BFGX_ERR_INVALID, "spin must be >= 1 (got %d; spin 0 is bfgx_sht_map2alm / bfgx_sht_alm2map)", spin);
+    if (spin > lmax) return fail(BFGX_ERR_INVALID, "spin must be <= lmax (got spin %d, lmax %d)", spin, lmax);
+    return BFGX_OK;
+}
+
+int sht_spin_begin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const void *in, const void *out, const void *work,
+                   const void *spin_work)
+{
+    if (!in || !out || !spin_work) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(spin_work) & 15) return fail(BFGX_ERR_INVALID, "spin_work_dev must be 16-byte aligned (complex values)");
+    if (int rc = sht_check(nside, lmax, mmax)) return rc;
+    if (int rc = sht_spin_check(lmax, spin)) return rc;
+    return sht_begin(device, nside, lmax, mmax, work);
+}
+
+// [G | C] = A_s(map0, map1): maps = map0 | map1 (npix each), alms = G | C (alm size each)
+int sht_spin_analysis(const ShtLayout &L, const ShtPtrs &p, double2 *F1, hipStream_t s, int spin, const double *maps, double2 *alms)
+{
+    const double norm = 4.0 * M_PI / (double)L.npix;
+    hipLaunchKernelGGL(sht::sht_ring_analysis_kernel, dim3(L.nrings), dim3(sht::kRingThreads), sht_ring_lds(L), s,
+                       maps, p.rings, L.nrings, L.mmax, norm, p.tw, p.btab, p.F);
+    hipLaunchKernelGGL(sht::sht_ring_analysis_kernel, dim3(L.nrings), dim3(sht::kRingThreads), sht_ring_lds(L), s,
+                       maps + L.npix, p.rings, L.nrings, L.mmax, norm, p.tw, p.btab, F1);
+    hipLaunchKernelGGL(sht::sht_spin_legendre_analysis_kernel, dim3(L.mmax + 1), dim3(sht::kLegThreads), 0, s,
+                       (const double2 *)p.F, (const double2 *)F1, p.rings, L.nside, L.lmax, spin, p.pref, alms,
+                       alms + sht_alm_size(L.lmax, L.mmax));
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
+int sht_spin_synthesis(const ShtLayout &L, const ShtPtrs &p, double2 *F1, hipStream_t s, int spin, const double2 *alms, double *maps)
+{
+    hipLaunchKernelGGL(sht::sht_spin_legendre_synthesis_kernel, dim3(L.mmax + 1), dim3(sht::kLegThreads), 0, s,
+                       alms, alms + sht_alm_size(L.lmax, L.mmax), p.rings, L.nside, L.lmax, spin, p.pref, p.F, F1);
+    hipLaunchKernelGGL(sht::sht_ring_synthesis_kernel, dim3(L.nrings), dim3(sht::kRingThreads), sht_ring_lds(L), s,
+                       (const double2 *)p.F, p.rings, L.nrings, L.mmax, p.tw, p.btab, maps);
+    hipLaunchKernelGGL(sht::sht_ring_synthesis_kernel, dim3(L.nrings), dim3(sht::kRingThreads), sht_ring_lds(L), s,
+                       (const double2 *)F1, p.rings, L.nrings, L.mmax, p.tw, p.btab, maps + L.npix);
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
 
 }  // namespace
 
@@ -298,6 +346,74 @@ int bfgx_sht_anafast(int device, int32_t nside, int32_t lmax, int32_t mmax, int3
     HIP_TRY(hipMemcpy(cl, dc.p, sizeof(double) * (lmax + 1), hipMemcpyDeviceToHost));
     if (alm1_out) HIP_TRY(hipMemcpy(alm1_out, da1.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
     if (alm2_out && map2) HIP_TRY(hipMemcpy(alm2_out, da2.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
+    return BFGX_OK;
+}
+
+
+// spin-s transforms of a pair of maps (healpy map2alm_spin / alm2map_spin); maps = map0 | map1, alms = G | C
+int64_t bfgx_sht_spin_work_doubles(int32_t nside, int32_t lmax, int32_t mmax)
+{
+    if (sht_check(nside, lmax, mmax)) return -1;
+    return sht_spin_work(sht_layout(nside, lmax, mmax));
+}
+
+int bfgx_sht_map2alm_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps_dev,
+                                 double *alms_dev, double *work_dev, double *spin_work_dev)
+{
+    if (int rc = sht_spin_begin(device, nside, lmax, mmax, spin, maps_dev, alms_dev, work_dev, spin_work_dev)) return rc;
+    const ShtLayout L = sht_layout(nside, lmax, mmax);
+    if (int rc = sht_set_lds(L)) return rc;
+    return sht_spin_analysis(L, sht_ptrs(L, work_dev), reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin, maps_dev,
+                             reinterpret_cast<double2 *>(alms_dev));
+}
+
+int bfgx_sht_alm2map_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms_dev,
+                                 double *maps_dev, double *work_dev, double *spin_work_dev)
+{
+    if (int rc = sht_spin_begin(device, nside, lmax, mmax, spin, alms_dev, maps_dev, work_dev, spin_work_dev)) return rc;
+    const ShtLayout L = sht_layout(nside, lmax, mmax);
+    if (int rc = sht_set_lds(L)) return rc;
+    return sht_spin_synthesis(L, sht_ptrs(L, work_dev), reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin,
+                              reinterpret_cast<const double2 *>(alms_dev), maps_dev);
+}
+
+int bfgx_sht_map2alm_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps, double *alms)
+{
+    if (!maps || !alms) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = sht_check(nside, lmax, mmax)) return rc;
+    if (int rc = sht_spin_check(lmax, spin)) return rc;
+    if (int rc = tables_begin(device)) return rc;
+    const ShtLayout L = sht_layout(nside, lmax, mmax);
+    const int64_t na = sht_alm_size(lmax, mmax);
+    DevArr dw, ds, dm, da;
+    if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(maps, sizeof(double) * 2 * L.npix) ||
+        da.up(nullptr, sizeof(double2) * 2 * na))
+        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
+    if (int rc = bfgx_sht_map2alm_spin_device(device, nullptr, nside, lmax, mmax, spin, dm.as<double>(), da.as<double>(), dw.as<double>(),
+                                              ds.as<double>()))
+        return rc;
+    HIP_TRY(hipMemcpy(alms, da.p, sizeof(double2) * 2 * na, hipMemcpyDeviceToHost));
+    return BFGX_OK;
+}
+
+int bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms, double *maps)
+{
+    if (!maps || !alms) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = sht_check(nside, lmax, mmax)) return rc;
+    if (int rc = sht_spin_check(lmax, spin)) return rc;
+    if (int rc = tables_begin(device)) return rc;
+    const ShtLayout L = sht_layout(nside, lmax, mmax);
+    const int64_t na = sht_alm_size(lmax, mmax);
+    DevArr dw, ds, dm, da;
+    if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(nullptr, sizeof(double) * 2 * L.npix) ||
+        da.up(alms, sizeof(double2) * 2 * na))
+        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
+    if (int rc = bfgx_sht_alm2map_spin_device(device, nullptr, nside, lmax, mmax, spin, da.as<double>(), dm.as<double>(), dw.as<double>(),
+                                              ds.as<double>()))
+        return rc;
+    HIP_TRY(hipMemcpy(maps, dm.p, sizeof(double) * 2 * L.npix, hipMemcpyDeviceToHost));
     return BFGX_OK;
 }
 

@@ -462,6 +462,14 @@ def sht_work_doubles(nside, lmax, mmax):
     return n
 
 
+def sht_spin_work_doubles(nside, lmax, mmax):
+    """doubles of the extra workspace of the spin transforms (F_m per ring of the second map)"""
+    n = int(_lib.load().bfgx_sht_spin_work_doubles(int(nside), int(lmax), int(mmax)))
+    if n < 0:
+        raise ValueError(_lib.load().bfgx_last_error().decode('utf-8', 'replace'))
+    return n
+
+
 class ShtPlan(object):
     """Resident spherical-harmonic transforms of one shape (nside, lmax, mmax) on one device: the workspace (ring geometry,
     Bluestein kernels of the ring FFTs, recurrence prefactors, per-ring F_m and a scratch map) is allocated and filled once;
@@ -478,6 +486,7 @@ class ShtPlan(object):
             raise _lib.BfgxError("bfgx: no HIP device visible: libbfgx has no CPU fallback")
         self.dev = torch.device('cuda', self.device)
         self.work = torch.empty(nw, dtype=torch.float64, device=self.dev)
+        self.spin_work = None                                 # F of a spin transform's second map, on the first spin call
         _lib.check(L.bfgx_sht_prepare_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, C.c_void_p(self.work.data_ptr())))
 
     def _stream(self):
@@ -505,6 +514,30 @@ class ShtPlan(object):
     def alm2cl_device(self, alm1_dev, alm2_dev=None, lmax_out=None, out=None):
         """cl [lmax_out + 1] (auto- or cross-spectrum) of device alm"""
         return alm2cl_device(alm1_dev, alm2_dev, self.lmax, self.mmax, lmax_out, out=out, device=self.device)
+
+    def _spin_work(self):
+        if self.spin_work is None:
+            import torch
+            self.spin_work = torch.empty(sht_spin_work_doubles(self.nside, self.lmax, self.mmax), dtype=torch.float64, device=self.dev)
+        return self.spin_work
+
+    def map2alm_spin_device(self, maps_dev, spin, out=None):
+        """complex128 [G, C] [2, nalm] of a pair of float64 RING maps [2, npix] on the device (spin >= 1)"""
+        import torch
+        alms = out if out is not None else torch.empty((2, self.nalm), dtype=torch.complex128, device=self.dev)
+        _lib.check(_lib.load().bfgx_sht_map2alm_spin_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, int(spin),
+                                                           C.c_void_p(maps_dev.data_ptr()), C.c_void_p(alms.data_ptr()),
+                                                           C.c_void_p(self.work.data_ptr()), C.c_void_p(self._spin_work().data_ptr())))
+        return alms
+
+    def alm2map_spin_device(self, alms_dev, spin, out=None):
+        """float64 RING maps [2, npix] of complex128 [G, C] [2, nalm] on the device (spin >= 1)"""
+        import torch
+        maps = out if out is not None else torch.empty((2, self.npix), dtype=torch.float64, device=self.dev)
+        _lib.check(_lib.load().bfgx_sht_alm2map_spin_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, int(spin),
+                                                           C.c_void_p(alms_dev.data_ptr()), C.c_void_p(maps.data_ptr()),
+                                                           C.c_void_p(self.work.data_ptr()), C.c_void_p(self._spin_work().data_ptr())))
+        return maps
 
 
 def alm2cl_device(alm1_dev, alm2_dev, lmax, mmax, lmax_out=None, out=None, device=0):
@@ -542,6 +575,22 @@ def sht_alm2map_host(alm, nside, lmax, mmax, device=0):
     m = np.empty(12 * int(nside) ** 2)
     a = np.ascontiguousarray(alm, dtype=np.complex128)
     _lib.check(_lib.load().bfgx_sht_alm2map(int(device), int(nside), int(lmax), int(mmax), a.ctypes.data, m.ctypes.data))
+    return m
+
+
+def sht_map2alm_spin_host(maps, nside, lmax, mmax, spin, device=0):
+    """one-shot host entry of map2alm_spin: float64 [2, npix] in, complex128 [G, C] [2, nalm] out (PCIe included)"""
+    m = np.ascontiguousarray(maps, dtype=np.float64)
+    alms = np.empty((2, sht_alm_size(lmax, mmax)), dtype=np.complex128)
+    _lib.check(_lib.load().bfgx_sht_map2alm_spin(int(device), int(nside), int(lmax), int(mmax), int(spin), m.ctypes.data, alms.ctypes.data))
+    return alms
+
+
+def sht_alm2map_spin_host(alms, nside, lmax, mmax, spin, device=0):
+    """one-shot host entry of alm2map_spin: complex128 [G, C] [2, nalm] in, float64 [2, npix] out"""
+    a = np.ascontiguousarray(alms, dtype=np.complex128)
+    m = np.empty((2, 12 * int(nside) ** 2))
+    _lib.check(_lib.load().bfgx_sht_alm2map_spin(int(device), int(nside), int(lmax), int(mmax), int(spin), a.ctypes.data, m.ctypes.data))
     return m
 
 

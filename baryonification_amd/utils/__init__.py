@@ -3,4 +3,4 @@ from .cosmology import *
 from .Tabulate import *
 from .Parallelize import *
 from .Pixel import *
-from .sphtfunc import map2alm, alm2map, alm2cl, anafast
+from .sphtfunc import map2alm, alm2map, alm2cl, anafast, map2alm_spin, alm2map_spin

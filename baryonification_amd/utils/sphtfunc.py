@@ -1,16 +1,35 @@
 """Spherical-harmonic transforms of RING-ordered HEALPix maps, named and defaulted after healpy.sphtfunc (healpy >= 1.16),
-spin 0, fp64, on the GPU (libbfgx: bfgx_sht_*).  `bfg.utils.anafast(shell_map)` replaces `hp.anafast(shell_map)`.
+fp64, on the GPU (libbfgx: bfgx_sht_*).  `bfg.utils.anafast(shell_map)` replaces `hp.anafast(shell_map)`.
 
 Inputs are numpy arrays (or anything np.asarray takes); results come back as numpy arrays.  A CUDA torch tensor is analysed
 where it is, without crossing PCIe, and the results stay on the device as torch tensors.  Every call of one shape
 (nside, lmax, mmax) reuses one cached engine.ShtPlan, so repeated calls allocate no new device workspace.
+
+map2alm / alm2map / alm2cl / anafast are spin 0.  map2alm_spin / alm2map_spin transform a pair of real maps of spin s >= 1
+in the HEALPix/libsharp convention:
+
+    map0 + i map1 = -sum_{l >= s} sum_{m = -l..l} (G_lm + i C_lm) sY_lm(theta, phi),
+
+G and C being the coefficients of real fields (X_{l,-m} = (-1)^m conj(X_lm); only m >= 0 is stored, in healpy's alm layout).
+sY_lm = sqrt((l - s)! / (l + s)!) edth^s Y_lm, with edth eta = -(sin theta)^s (d_theta + (i / sin theta) d_phi)[(sin theta)^-s eta]
+for a spin-s quantity eta and Y_lm the Condon-Shortley harmonic (scipy.special.sph_harm_y).  For s = 2, (map0, map1) = (Q, U)
+and (G, C) = (E, B) in HEALPix's polarisation convention.  The analysis is plain quadrature, as healpy's (no iterations).
+
+Convergence to shear (Kaiser-Squires) on a shell map kappa:
+
+    klm = map2alm(kappa, iter=0)                      # or iter=3
+    l = l-index of every coefficient (healpy.Alm.getlm)
+    elm = sqrt((l + 2) (l - 1) / (l (l + 1))) klm     # 0 for l < 2
+    gamma1, gamma2 = alm2map_spin([elm, 0 * elm], nside, 2, lmax)
+
+and back: E, B = map2alm_spin([gamma1, gamma2], 2); alm2cl(E), alm2cl(B), alm2cl(E, B) are the E/B spectra.
 """
 import numpy as np
 
 from .. import engine
 from .io import npix2nside
 
-__all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'getlmax', 'getidx', 'getsize', 'UNSEEN']
+__all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'map2alm_spin', 'alm2map_spin', 'getlmax', 'getidx', 'getsize', 'UNSEEN']
 
 UNSEEN = -1.6375e30
 
@@ -188,3 +207,72 @@ def anafast(map1, map2=None, nspec=None, lmax=None, mmax=None, iter=3, alm=False
     if not on_dev:
         out = [x.cpu().numpy() for x in out]
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def _spin_check(spin, lmax):
+    spin = int(spin)
+    if spin < 1:
+        raise ValueError("spin must be >= 1 (got %d); spin-0 transforms are map2alm / alm2map" % spin)
+    if spin > lmax:
+        raise ValueError("spin must be <= lmax (got spin %d, lmax %d)" % (spin, lmax))
+    return spin
+
+
+def _pair(x, name):
+    """the two members of a map or alm pair: a (2, n) array or tensor, or a sequence of two 1-D ones"""
+    if _is_torch(x) or isinstance(x, np.ndarray):
+        if x.ndim != 2 or x.shape[0] != 2:
+            raise ValueError("%s must hold 2 %s (got shape %s)" % (name, 'maps' if name == 'maps' else 'sets of alm', tuple(x.shape)))
+        return x[0], x[1]
+    if isinstance(x, (list, tuple)):
+        if len(x) != 2:
+            raise ValueError("%s must hold 2 %s (got %d)" % (name, 'maps' if name == 'maps' else 'sets of alm', len(x)))
+        return x[0], x[1]
+    return _pair(np.asarray(x), name)
+
+
+def _size(x):
+    return x.numel() if _is_torch(x) else np.asarray(x).size
+
+
+def map2alm_spin(maps, spin, lmax=None, mmax=None):
+    """[G, C] (complex128 [2, nalm], healpy order) of a pair of RING maps [map0, map1] of spin `spin` >= 1 (plain quadrature:
+    G + i C = -4 pi / Npix sum_p (map0 + i map1)_p sY*_lm(p)).  Output alm with l < spin are 0.  UNSEEN pixels count as 0."""
+    m0, m1 = _pair(maps, 'maps')
+    if _size(m0) != _size(m1):
+        raise ValueError("maps: map0 and map1 have different sizes (%d, %d)" % (_size(m0), _size(m1)))
+    a, nside, on_dev = _map_input(m0, 'maps[0]')
+    b, _, d1 = _map_input(m1, 'maps[1]')
+    if d1 != on_dev:
+        raise ValueError("maps: map0 and map1 must both be on the host or both on the device")
+    lmax, mmax = _shape(nside, lmax, mmax)
+    spin = _spin_check(spin, lmax)
+    plan = engine.sht_plan(nside, lmax, mmax)
+    if on_dev:
+        import torch
+        alms = plan.map2alm_spin_device(torch.stack([a, b]), spin)
+        return alms
+    alms = plan.map2alm_spin_device(_to_device(np.stack([a, b]), plan), spin)
+    return alms.cpu().numpy()
+
+
+def alm2map_spin(alms, nside, spin, lmax, mmax=None):
+    """float64 RING maps [map0, map1] ([2, npix]) of [G, C] of spin `spin` >= 1:
+    map0 + i map1 = -sum_{l >= spin} sum_m (G_lm + i C_lm) sY_lm.  Input alm with l < spin are ignored."""
+    g, c = _pair(alms, 'alms')
+    if _size(g) != _size(c):
+        raise ValueError("alms: the two sets of alm have different sizes (%d, %d)" % (_size(g), _size(c)))
+    a, lmax, mmax, on_dev = _alm_input(g, lmax, mmax, 'alms[0]')
+    b, _, _, d1 = _alm_input(c, lmax, mmax, 'alms[1]')
+    if d1 != on_dev:
+        raise ValueError("alms: the two sets of alm must both be on the host or both on the device")
+    nside = int(nside)
+    if nside < 1:
+        raise ValueError("nside must be >= 1")
+    _shape(nside, lmax, mmax)
+    spin = _spin_check(spin, lmax)
+    plan = engine.sht_plan(nside, lmax, mmax)
+    if on_dev:
+        import torch
+        return plan.alm2map_spin_device(torch.stack([a, b]), spin)
+    return plan.alm2map_spin_device(_to_device(np.stack([a, b]), plan), spin).cpu().numpy()

@@ -637,6 +637,20 @@ int  bfgx_sht_alm2cl(int device, int32_t lmax, int32_t mmax, int32_t lmax_out, c
 int  bfgx_sht_anafast(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map1_host,
                       const double *map2_host, double *cl_host, double *alm1_out, double *alm2_out);
 
+/* ---- spin-weighted transforms of a pair of RING maps (healpy.map2alm_spin / alm2map_spin, HEALPix/libsharp convention) ---------
+ * map0 + i map1 = -sum_{l >= spin} sum_{m = -l..l} (G_lm + i C_lm) sY_lm, sY_lm = sqrt((l - s)! / (l + s)!) edth^s Y_lm; G and C are
+ * the coefficients of real fields, stored like the spin-0 alm.  maps = map0 | map1 (2 npix doubles), alms = G | C (2 x alm size
+ * complex128).  1 <= spin <= lmax; output alm with l < spin are 0, input alm with l < spin are ignored; no iterations (plain
+ * quadrature, as healpy).  Device entries: work_dev as for the spin-0 entries (prepared by bfgx_sht_prepare_device), spin_work_dev
+ * bfgx_sht_spin_work_doubles(nside, lmax, mmax) doubles of scratch (16-byte aligned; -1 = invalid shape); enqueue-only. */
+int64_t bfgx_sht_spin_work_doubles(int32_t nside, int32_t lmax, int32_t mmax);
+int  bfgx_sht_map2alm_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin,
+                                  const double *maps_dev, double *alms_dev, double *work_dev, double *spin_work_dev);
+int  bfgx_sht_alm2map_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin,
+                                  const double *alms_dev, double *maps_dev, double *work_dev, double *spin_work_dev);
+int  bfgx_sht_map2alm_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps_host, double *alms_host);
+int  bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms_host, double *maps_host);
+
 #ifdef __cplusplus
 }
 #endif
