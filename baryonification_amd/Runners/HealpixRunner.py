@@ -14,9 +14,19 @@ import numpy as np
 from .. import _lib
 from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
+from ..utils.pixelfunc import scatter_add
 from ._model import build_model, process_callable_exact, wants_exact
 
-__all__ = ['DefaultRunner', 'BaryonifyShell', 'PaintProfilesShell']
+__all__ = ['DefaultRunner', 'BaryonifyShell', 'PaintProfilesShell', 'regrid_pixels_hpix']
+
+
+def regrid_pixels_hpix(hmap, parent_pix_vals, child_pix, child_weights):
+    """hmap[child_pix[i, j]] += child_weights[i, j] * parent_pix_vals[i] for j < 4, IN PLACE, and returns hmap
+    (HealpixRunner.py:14-67).  hmap: a C-contiguous 1-D float64 numpy array or a CUDA float64 tensor.  child_pix (any integer dtype)
+    and child_weights have shape (N, 4): transpose what get_interp_weights returns.  Indices in [-npix, npix) wrap as Python indices
+    do; any other index raises IndexError before anything runs.  Duplicate targets accumulate, by fp64 atomic adds on the GPU, so
+    the last bits of a pixel's sum can differ from run to run."""
+    return scatter_add(hmap, parent_pix_vals, child_pix, child_weights)
 
 
 class DefaultRunner(object):

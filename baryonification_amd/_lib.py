@@ -242,6 +242,20 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p]),
     'bfgx_sht_map2alm_spin': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'bfgx_sht_alm2map_spin': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_ud_grade_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_ud_grade': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_interp_weights_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_interp_weights': (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    'bfgx_hpx_interp_val_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_interp_val': (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    'bfgx_hpx_scatter_add_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_scatter_add': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -44,6 +44,7 @@ template <typename T> static inline hipError_t bfgx_counted_malloc(T **p, size_t
 #include "bfgx_grid_gather.hpp"
 #include "bfgx_fftlog.hpp"
 #include "bfgx_sht.hpp"
+#include "bfgx_hpx.hpp"
 
 using namespace bfgx;
 
@@ -2466,6 +2467,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // spherical-harmonic transforms of HEALPix shells (map2alm / alm2map / alm2cl / anafast)
 #include "bfgx_sht_api.inc"
+
+// HEALPix pixel functions (ud_grade / get_interp_weights / get_interp_val / regrid_pixels_hpix)
+#include "bfgx_hpx_api.inc"
 
 extern "C" void bfgx_cache_clear(void)
 {

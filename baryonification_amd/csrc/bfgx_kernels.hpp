@@ -138,12 +138,10 @@ __device__ inline void pix2loc(const Hpx &h, int64_t pix, double &z, double &sth
     }
 }
 
-// healpix_cxx get_interpol (RING). want_w = false skips the ring colatitudes (pixels only).
+// healpix_cxx get_interpol (RING) with the ring above (ir1, 0..4 nside - 1) given. want_w = false skips the ring colatitudes (pixels only).
 template <bool WANT_W>
-__device__ inline void get_interpol(const Hpx &h, double theta, double phi, int64_t pix[4], double wgt[4])
+__device__ inline void get_interpol_ring(const Hpx &h, int64_t ir1, double theta, double phi, int64_t pix[4], double wgt[4])
 {
-    const double z = cos(theta);
-    const int64_t ir1 = ring_above(h, z);
     const int64_t ir2 = ir1 + 1;
     double theta1 = 0.0, theta2 = 0.0;
     pix[0] = pix[1] = pix[2] = pix[3] = 0;
@@ -187,6 +185,13 @@ __device__ inline void get_interpol(const Hpx &h, double theta, double phi, int6
         wgt[0] *= (1.0 - wtheta); wgt[1] *= (1.0 - wtheta);
         wgt[2] *= wtheta; wgt[3] *= wtheta;
     }
+}
+
+// healpix_cxx get_interpol (RING): the ring above from cos(theta)
+template <bool WANT_W>
+__device__ inline void get_interpol(const Hpx &h, double theta, double phi, int64_t pix[4], double wgt[4])
+{
+    get_interpol_ring<WANT_W>(h, ring_above(h, cos(theta)), theta, phi, pix, wgt);
 }
 
 

@@ -651,6 +651,42 @@ int  bfgx_sht_alm2map_spin_device(int device, void *hip_stream, int32_t nside, i
 int  bfgx_sht_map2alm_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps_host, double *alms_host);
 int  bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms_host, double *maps_host);
 
+/* ---- HEALPix pixel functions (healpy.ud_grade, get_interp_weights, get_interp_val; the reference's regrid_pixels_hpix) ------------
+ * Pixel indices are int64.  Map element types: dtype 0 = float32, 1 = float64.  Device entries take device pointers and enqueue on
+ * hip_stream; host entries copy in and out (PCIe included).  Every argument is checked before any device call (BFGX_ERR_INVALID
+ * names the limit); without a GPU the entries return BFGX_ERR_NO_DEVICE.
+ * ud_grade: nmaps maps of 12 nside_in^2 pixels (row after row) -> nmaps maps of 12 nside_out^2 pixels; both nsides powers of two in
+ *   [1, 8192]; nest_in / nest_out: 0 = RING, 1 = NEST.  Degrade: output = (sum of the good children) * ratio / (good children), where
+ *   a child is bad if it is within healpy.mask_bad's tolerance of UNSEEN (-1.6375e30) or not finite; UNSEEN where no child is good
+ *   (pess != 0: where any child is bad).  Sums are fp64 in a fixed order (bit-reproducible).  Upgrade: every child = parent * ratio.
+ *   ratio = (nside_out / nside_in)^power, 1 without a power.
+ * interp_weights: healpix_cxx get_interpol.  Points are (theta_dev[i], phi_dev[i]) in radians, or the centres of ipix_dev[i] (pixel
+ *   indices in the ordering of nest) when theta and phi are NULL.  pix[4][n], w[4][n]; nest != 0 returns NEST indices and needs a
+ *   power-of-two nside, RING takes any 1 <= nside <= 8192.  phi is reduced to [0, 2 pi).  Host entries refuse theta outside [0, pi],
+ *   a non-finite phi and pixel indices outside [0, npix); device entries give such points pixels -1 and weights NaN.
+ * interp_val: out[m][i] = sum_k maps[m][pix_k] w_k with the weights above (maps in the ordering of nest); NaN for invalid points
+ *   on the device entry.
+ * scatter_add: hmap[pix[i][j]] += w[i][j] * vals[i] for i < n, j < 4 (pix, w: [n][4]), fp64 atomic adds, so the last bits of a sum
+ *   can differ from run to run.  Indices in [-npix, 0) wrap; the host entry refuses any other index outside [0, npix), the device
+ *   entry skips it. */
+int  bfgx_hpx_ud_grade_device(int device, void *hip_stream, int64_t nside_in, int64_t nside_out, int64_t nmaps, int32_t nest_in,
+                              int32_t nest_out, int32_t pess, double ratio, int32_t dtype_in, int32_t dtype_out, const void *map_in_dev,
+                              void *map_out_dev);
+int  bfgx_hpx_ud_grade(int device, int64_t nside_in, int64_t nside_out, int64_t nmaps, int32_t nest_in, int32_t nest_out, int32_t pess,
+                       double ratio, int32_t dtype_in, int32_t dtype_out, const void *map_in_host, void *map_out_host);
+int  bfgx_hpx_interp_weights_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t n, const double *theta_dev,
+                                    const double *phi_dev, const int64_t *ipix_dev, int64_t *pix_dev, double *w_dev);
+int  bfgx_hpx_interp_weights(int device, int64_t nside, int32_t nest, int64_t n, const double *theta_host, const double *phi_host,
+                             const int64_t *ipix_host, int64_t *pix_host, double *w_host);
+int  bfgx_hpx_interp_val_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t nmaps, int32_t dtype, const void *maps_dev,
+                                int64_t n, const double *theta_dev, const double *phi_dev, double *out_dev);
+int  bfgx_hpx_interp_val(int device, int64_t nside, int32_t nest, int64_t nmaps, int32_t dtype, const void *maps_host, int64_t n,
+                         const double *theta_host, const double *phi_host, double *out_host);
+int  bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, double *hmap_dev, int64_t n, const double *vals_dev,
+                                 const int64_t *pix_dev, const double *w_dev);
+int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n, const double *vals_host, const int64_t *pix_host,
+                          const double *w_host);
+
 #ifdef __cplusplus
 }
 #endif
