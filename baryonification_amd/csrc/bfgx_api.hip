@@ -24,12 +24,9 @@
 
 #include "../../include/bfgx.h"
 
-// every device allocation the library makes is counted (bfgx_debug_alloc_count): a warm one-shot call must make none
 #include <atomic>
-static std::atomic<long long> g_bfgx_allocs{0};
 static std::atomic<long long> g_host_pinned_in_place{0}, g_host_staged{0}, g_host_pin_min_bytes{-1};      // HostSpan (bfgx_debug_host_spans)
-template <typename T> static inline hipError_t bfgx_counted_malloc(T **p, size_t bytes) { ++g_bfgx_allocs; return hipMalloc((void **)p, bytes); }
-#define hipMalloc(ptr, bytes) bfgx_counted_malloc(ptr, bytes)
+#include "bfgx_devmem.hpp"
 #include "bfgx_cosmo.hpp"
 #include "bfgx_kernels.hpp"
 #include "bfgx_scatter2.hpp"
@@ -62,6 +59,8 @@ int fail(int code, const char *fmt, ...)
     g_err = buf;
     return code;
 }
+
+int alloc_fail(const char *what) { return fail(BFGX_ERR_HIP, kDevAllocFailed, what); }
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -102,7 +101,7 @@ struct bfgx_plan {
     int64_t nside = 0, max_halos = 0;
     Hpx hpx;
     DevModel model;
-    std::vector<void *> owned;     // device allocations freed with the plan
+    DevList mem;                   // device allocations freed with the plan
     HaloRec *recs = nullptr;
     RowSetX *rowsx = nullptr;      // corner rows when the table has extra parameter axes (NC > 4)
     int NC = 4;
@@ -178,19 +177,17 @@ struct KernelTimerT {
 };
 using KernelTimer = KernelTimerT<bfgx_plan>;
 
-static int owned_upload(std::vector<void *> &owned, hipStream_t stream, const void *host, size_t bytes, const void **dev_out)
+// a device copy of host[count] (or of a vector), owned by mem, filled on the stream
+template <typename T>
+static int owned_upload(DevList &mem, hipStream_t stream, const T *host, size_t count, const T *&dev_out)
 {
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    owned.push_back(d);
-    HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream));
-    *dev_out = d;
+    HIP_TRY(mem.upload(dev_out, host, count, stream));
     return BFGX_OK;
 }
-
-static int plan_upload(bfgx_plan *p, const void *host, size_t bytes, const void **dev_out)
+template <typename T>
+static int owned_upload(DevList &mem, hipStream_t stream, const std::vector<T> &v, const T *&dev_out)
 {
-    return owned_upload(p->owned, p->stream, host, bytes, dev_out);
+    return owned_upload(mem, stream, v.data(), v.size(), dev_out);
 }
 
 static int validate_model(const bfgx_model *model)
@@ -206,7 +203,7 @@ static int validate_model(const bfgx_model *model)
 
 // device copy of the model: table axes + values (r innermost), backgrounds, mass definitions; `with_da` adds the
 // D_A(z) spline the lightcone runners need.  Synchronises the stream before returning (staging buffers are local).
-static int upload_model(std::vector<void *> &owned, hipStream_t stream, const bfgx_model *model, bool with_da, DevModel &m, int &NC)
+static int upload_model(DevList &mem, hipStream_t stream, const bfgx_model *model, bool with_da, DevModel &m, int &NC)
 {
     const bfgx_table &t = model->table;
     std::memset(&m, 0, sizeof(m));
@@ -215,9 +212,7 @@ static int upload_model(std::vector<void *> &owned, hipStream_t stream, const bf
     for (int d = 0; d < t.ndim; ++d) {
         m.tab.n[d] = t.n[d];
         nvals *= (size_t)t.n[d];
-        const void *dv = nullptr;
-        if (int rc = owned_upload(owned, stream, t.axis[d], sizeof(double) * t.n[d], &dv)) return rc;
-        m.tab.axis[d] = (const double *)dv;
+        if (int rc = owned_upload(mem, stream, t.axis[d], (size_t)t.n[d], m.tab.axis[d])) return rc;
     }
     {
         // device layout [z][M][p0][p1][r]: the radial row of every (z, M, params) corner is contiguous
@@ -235,13 +230,10 @@ static int upload_model(std::vector<void *> &owned, hipStream_t stream, const bf
                         tr[(zm * nx + q) * nr + ir] = t.values[(zm * nr + ir) * nx + q];
             src = tr.data();
         }
-        const void *dv = nullptr;
-        if (int rc = owned_upload(owned, stream, src, sizeof(double) * nvals, &dv)) return rc;
-        m.tab.values = (const double *)dv;
+        if (int rc = owned_upload(mem, stream, src, nvals, m.tab.values)) return rc;
         std::vector<float> v32(nvals);                 // fp32 copy for the mixed-precision pair path (pair_value_fast32)
         for (size_t q = 0; q < nvals; ++q) v32[q] = (float)src[q];
-        if (int rc = owned_upload(owned, stream, v32.data(), sizeof(float) * nvals, &dv)) return rc;
-        m.tab.values32 = (const float *)dv;
+        if (int rc = owned_upload(mem, stream, v32, m.tab.values32)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         NC = 4 << (t.ndim - 3);
     }
@@ -270,9 +262,7 @@ static int upload_model(std::vector<void *> &owned, hipStream_t stream, const bf
     if (with_da) {
         std::vector<double> knots, coef;
         da_spline(m.bg_runner, knots, coef);
-        const void *dv = nullptr;
-        if (int rc = owned_upload(owned, stream, coef.data(), sizeof(double) * coef.size(), &dv)) return rc;
-        m.da_coef = (const double *)dv;
+        if (int rc = owned_upload(mem, stream, coef, m.da_coef)) return rc;
         m.da_step = kDaZmax / (kDaKnots - 1);
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -552,10 +542,7 @@ static int ensure_entry_capacity(bfgx_plan *p, const bfgx_catalog *c)
     HIP_TRY(hipMemcpyAsync(&total, p->tile_start + p->tiling.ntiles, sizeof(total), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (!(ov & 1)) return BFGX_OK;             // (bit 2: the fluid kernel gave up -- bfgx_plan_status reports it)
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(int32_t) * ((size_t)total + 16)));
-    p->owned.push_back(d);                       // the old list is released with the plan
-    p->entries = (int32_t *)d;
+    HIP_TRY(p->mem.alloc(p->entries, (size_t)total + 16));     // the old list is released with the plan
     p->capacity = (int64_t)total + 16;
     HIP_TRY(hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream));
     HIP_TRY(hipMemsetAsync(p->tile_cursor, 0, sizeof(int32_t) * 2 * ((size_t)p->tiling.ntiles + 1), p->stream));   // cur_b, cur_w
@@ -745,21 +732,12 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
     auto bail = [&](int rc) { bfgx_plan_destroy(p); return rc; };
 
     const bfgx_table &t = model->table;
-    if (int rc = upload_model(p->owned, p->stream, model, true, p->model, p->NC)) return bail(rc);
+    if (int rc = upload_model(p->mem, p->stream, model, true, p->model, p->NC)) return bail(rc);
     plan_pick_precision(p, model);
-    {
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(HaloRec) * (size_t)(max_halos > 0 ? max_halos : 1)) != hipSuccess)
-            return bail(fail(BFGX_ERR_HIP, "hipMalloc(halo records) failed"));
-        p->owned.push_back(d);
-        p->recs = (HaloRec *)d;
-        if (p->NC > 4) {
-            if (hipMalloc(&d, sizeof(RowSetX) * (size_t)(max_halos > 0 ? max_halos : 1)) != hipSuccess)
-                return bail(fail(BFGX_ERR_HIP, "hipMalloc(corner rows) failed"));
-            p->owned.push_back(d);
-            p->rowsx = (RowSetX *)d;
-        }
-    }
+    DevList &mem = p->mem;
+    const size_t nh = (size_t)(max_halos > 0 ? max_halos : 1);
+    if (mem.alloc(p->recs, nh)) return bail(alloc_fail("halo records"));
+    if (p->NC > 4 && mem.alloc(p->rowsx, nh)) return bail(alloc_fail("corner rows"));
     {   // fast tiled scatter: possible for a 3-axis table with a uniform ln r axis whose interleaved copy stays small
         const size_t n8 = (size_t)(t.n[0] - 1) * (size_t)(t.n[1] - 1) * (size_t)(t.n[2] - 1) * 8;
         p->fast_ok = (t.ndim == 3) && p->model.tab.r_uniform && n8 * sizeof(double) <= ((size_t)256 << 20);
@@ -768,20 +746,14 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
             std::vector<double> v64;
             build_tab8<float>(t, v32);
             build_tab8<double>(t, v64);
-            const void *dv = nullptr;
-            if (int rc = plan_upload(p, v32.data(), sizeof(float) * v32.size(), &dv)) return bail(rc);
-            p->tab8f = (const float *)dv;
-            if (int rc = plan_upload(p, v64.data(), sizeof(double) * v64.size(), &dv)) return bail(rc);
-            p->tab8d = (const double *)dv;
+            if (int rc = owned_upload(mem, p->stream, v32, p->tab8f)) return bail(rc);
+            if (int rc = owned_upload(mem, p->stream, v64, p->tab8d)) return bail(rc);
             if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
-            const size_t nh = (size_t)(max_halos > 0 ? max_halos : 1);
-            void *d = nullptr;
-            if (hipMalloc(&d, sizeof(RowRec) * nh) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMalloc(row records) failed"));
-            p->owned.push_back(d); p->rowrec = (RowRec *)d;
-            if (hipMalloc(&d, sizeof(PairRecT<double>) * nh) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair records) failed"));
-            p->owned.push_back(d); p->pairrec = d;
-            if (hipMalloc(&d, sizeof(FbRec) * nh) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMalloc(fallback records) failed"));
-            p->owned.push_back(d); p->fbrec = (FbRec *)d;
+            PairRecT<double> *pairrec = nullptr;
+            if (mem.alloc(p->rowrec, nh)) return bail(alloc_fail("row records"));
+            if (mem.alloc(pairrec, nh)) return bail(alloc_fail("pair records"));
+            p->pairrec = pairrec;
+            if (mem.alloc(p->fbrec, nh)) return bail(alloc_fail("fallback records"));
         }
     }
     {   // tiling tables and halo -> tile binning workspace
@@ -790,35 +762,23 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
         build_tiling(nside, t.log_values != 0, BR, W, tile0, nphi, nrmin, tband);
         Tiling &T = p->tiling;
         T.BR = BR; T.W = W; T.nbands = (int)nphi.size(); T.ntiles = (int)tband.size();
-        const void *dv = nullptr;
-        if (int rc = plan_upload(p, tile0.data(), sizeof(int32_t) * tile0.size(), &dv)) return bail(rc);
-        T.band_tile0 = (const int32_t *)dv;
+        if (int rc = owned_upload(mem, p->stream, tile0, T.band_tile0)) return bail(rc);
         p->band_tile0_host = tile0;
-        if (int rc = plan_upload(p, nphi.data(), sizeof(int32_t) * nphi.size(), &dv)) return bail(rc);
-        T.band_nphi = (const int32_t *)dv;
-        if (int rc = plan_upload(p, nrmin.data(), sizeof(int32_t) * nrmin.size(), &dv)) return bail(rc);
-        T.band_nrmin = (const int32_t *)dv;
-        if (int rc = plan_upload(p, tband.data(), sizeof(int32_t) * tband.size(), &dv)) return bail(rc);
-        T.tile_band = (const int32_t *)dv;
+        if (int rc = owned_upload(mem, p->stream, nphi, T.band_nphi)) return bail(rc);
+        if (int rc = owned_upload(mem, p->stream, nrmin, T.band_nrmin)) return bail(rc);
+        if (int rc = owned_upload(mem, p->stream, tband, T.tile_band)) return bail(rc);
         std::vector<int32_t> order(tband.size());
         {   // launch order: tiles by their shortest ring / azimuth slices (~ pixels per tile), descending; stable
             std::vector<double> weight(tband.size());
             for (size_t q = 0; q < tband.size(); ++q) { order[q] = (int32_t)q; weight[q] = (double)nrmin[tband[q]] / (double)nphi[tband[q]]; }
             std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return weight[x] > weight[y]; });
         }
-        if (int rc = plan_upload(p, order.data(), sizeof(int32_t) * order.size(), &dv)) return bail(rc);
-        T.tile_order = (const int32_t *)dv;
+        if (int rc = owned_upload(mem, p->stream, order, T.tile_order)) return bail(rc);
         if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
         p->capacity = 8 * max_halos + 4096;
         if (const char *e = std::getenv("BFGX_K1_FLUID")) p->k1_fluid = std::max(0, std::min(2, std::atoi(e)));
         if (const char *e = std::getenv("BFGX_K1_WIDE")) p->k1_wide = std::atoi(e) != 0;
         if (const char *e = std::getenv("BFGX_ENTRY_CAP")) p->capacity = std::max<int64_t>(16, std::atoll(e));   // tests: force regrowth
-        auto dalloc = [&](size_t bytes, void **ptr) {
-            if (hipMalloc(ptr, bytes) != hipSuccess) return 1;
-            p->owned.push_back(*ptr);
-            return 0;
-        };
-        void *d0 = nullptr, *d1 = nullptr, *d3 = nullptr, *d4 = nullptr, *d5 = nullptr, *d6 = nullptr;
         // the binning counters and, right behind them (16-byte aligned), the control words of the regrid's far list: ONE memset per step
         // zeroes both (a length that is not a multiple of 16 bytes, or two buffers, cost a fill kernel each: 4.5 us)
         const size_t n7p = ((size_t)7 * (T.ntiles + 1) + 3) & ~(size_t)3;
@@ -826,16 +786,12 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
         p->cnt_pad = kCntPadMax;
         while (p->cnt_pad > 1 && (size_t)T.ntiles * p->cnt_pad * sizeof(int32_t) > ((size_t)4 << 20)) p->cnt_pad >>= 1;
         const size_t npad = (size_t)T.ntiles * p->cnt_pad;
-        if (dalloc(sizeof(int32_t) * (npad + n7p + (size_t)T.ntiles + 8), &d0) || dalloc(sizeof(int32_t) * (T.ntiles + 1), &d1) ||
-            dalloc(sizeof(int32_t) * (size_t)p->capacity, &d3) || dalloc(sizeof(int32_t), &d4) ||
-            dalloc(sizeof(unsigned long long), &d5) || dalloc(sizeof(TileRef) * (size_t)(max_halos > 0 ? max_halos : 1), &d6))
-            return bail(fail(BFGX_ERR_HIP, "hipMalloc(binning workspace) failed"));
-        p->tile_count_pad = (int32_t *)d0;
-        p->tile_count = (int32_t *)d0 + npad; p->tile_count_b = p->tile_count + (T.ntiles + 1);
+        if (mem.alloc(p->tile_count_pad, npad + n7p + (size_t)T.ntiles + 8) || mem.alloc(p->tile_start, (size_t)T.ntiles + 1) ||
+            mem.alloc(p->entries, (size_t)p->capacity) || mem.alloc(p->overflow, 1) || mem.alloc(p->pair_total, 1) || mem.alloc(p->tref, nh))
+            return bail(alloc_fail("binning workspace"));
+        p->tile_count = p->tile_count_pad + npad; p->tile_count_b = p->tile_count + (T.ntiles + 1);
         p->tile_count_w = p->tile_count + 2 * (T.ntiles + 1);
         p->tile_cursor = p->tile_count + 3 * (T.ntiles + 1); p->tile_cursor_w = p->tile_count + 4 * (T.ntiles + 1);
-        p->tile_start = (int32_t *)d1; p->tref = (TileRef *)d6;
-        p->entries = (int32_t *)d3; p->overflow = (int32_t *)d4; p->pair_total = (unsigned long long *)d5;
         {
             // capacity of a tile's fixed list: 16 x the mean entries per tile (a rank of an N-GPU run bins its share of the halos into 1 / N
             // of the tiles; a sky patch does the same), a power of two in [64, 32768] (4 x the mean above 512 entries per tile: a catalog of 1e7 small halos lists 4200 per tile, and what does not fit takes the slow route -- K3 3.7 against 1.4 ms), the whole array at most 1 GB
@@ -844,18 +800,14 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
             while (cap_a < 32768 && (double)cap_a < (mean > 512.0 ? 4.0 : 16.0) * mean + 64.0) cap_a <<= 1;
             while (cap_a > 64 && (size_t)T.ntiles * cap_a * sizeof(int32_t) > ((size_t)1 << 30)) cap_a >>= 1;
             if (const char *e = std::getenv("BFGX_TILE_LIST_CAP")) cap_a = std::max(1, std::atoi(e));        // tests: force the overflow into region B
-            void *da = nullptr, *ds = nullptr, *dc = nullptr;
-            const size_t nblk = ((size_t)std::max<int64_t>(max_halos, 1) + 255) / 256;
-            void *dw = nullptr, *df = nullptr;
-            if (dalloc(sizeof(float) * nblk, &dw) || dalloc(sizeof(int32_t) * 4, &df)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(work estimate) failed"));
-            p->k0_work_est = (float *)dw; p->k1_form = (int32_t *)df;
-            if (dalloc(sizeof(int32_t) * (size_t)T.ntiles * cap_a, &da) || dalloc(sizeof(int32_t) * nblk * 256, &ds) || dalloc(sizeof(int32_t) * nblk, &dc))
-                return bail(fail(BFGX_ERR_HIP, "hipMalloc(tile lists) failed"));
-            p->entries_a = (int32_t *)da; p->slow_list = (int32_t *)ds; p->slow_cnt = (int32_t *)dc; p->entries_a_cap = cap_a;
+            const size_t nblk = (nh + 255) / 256;
+            if (mem.alloc(p->k0_work_est, nblk) || mem.alloc(p->k1_form, 4)) return bail(alloc_fail("work estimate"));
+            if (mem.alloc(p->entries_a, (size_t)T.ntiles * cap_a) || mem.alloc(p->slow_list, nblk * 256) || mem.alloc(p->slow_cnt, nblk))
+                return bail(alloc_fail("tile lists"));
+            p->entries_a_cap = cap_a;
             p->tile_zeros = p->tile_count + 5 * ((size_t)T.ntiles + 1) + 1;      // the words behind K1's tile counter: zeroed with the counters, never written
         }
         {
-            void *f0 = nullptr, *f1 = nullptr, *f2 = nullptr, *f3 = nullptr;
             // deposits listed for the generic route: four per pixel that moves beyond the gathering reach (15 rings = 9.9 / NSIDE rad).  At NSIDE
             // 1024 on the S19 table that is 0.2 % of the pixels; at NSIDE 2048 the same field in radians sends 8 % there (16 M entries), and a
             // list that overflows costs a second pass with the generic evaluation under divergence (25 ms): room for half the pixels, 1 GB at most
@@ -873,35 +825,22 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
             if (const char *e = std::getenv("BFGX_FAR_CAP")) p->far.cap = std::max<int64_t>(1024, std::atoll(e));          // tests: force the overflow
             // control words in one allocation: [0..7] entries listed, [8..11] overflow (full-map regrid), [12..15] tiles left to
             // the walking kernel (followed by their numbers), ... ; the banded regrid's overflow flag lives after the tile list
-            void *f4 = nullptr;
-            f0 = p->tile_count + n7p;
-            if (dalloc(sizeof(int64_t) * (size_t)p->far.cap, &f1) ||
-                dalloc(sizeof(double) * (size_t)p->far.cap, &f2) ||
-                dalloc(sizeof(int32_t) * 2 * (size_t)(T.ntiles + 1), &f3))
-                return bail(fail(BFGX_ERR_HIP, "hipMalloc(far list) failed"));
-            p->tile_apron = (int32_t *)f3;
-            {
-                void *fl = nullptr;
-                if (dalloc(sizeof(int32_t) * (size_t)(T.ntiles + 4), &fl)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(lean tile list) failed"));
-                p->regrid_lean = (int32_t *)fl;
-                if (hipMemsetAsync(fl, 0, sizeof(int32_t) * 4, p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
-            }
-            int32_t *ctrl = (int32_t *)f0;
-            p->far.count = (unsigned long long *)ctrl; p->far.pix = (int64_t *)f1; p->far.val = (double *)f2;
+            if (mem.alloc(p->far.pix, (size_t)p->far.cap) || mem.alloc(p->far.val, (size_t)p->far.cap) ||
+                mem.alloc(p->tile_apron, 2 * (size_t)(T.ntiles + 1)))
+                return bail(alloc_fail("far list"));
+            if (mem.alloc(p->regrid_lean, (size_t)(T.ntiles + 4))) return bail(alloc_fail("lean tile list"));
+            if (hipMemsetAsync(p->regrid_lean, 0, sizeof(int32_t) * 4, p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
+            int32_t *ctrl = p->tile_count + n7p;
+            p->far.count = (unsigned long long *)ctrl;
             p->far_overflow_full = ctrl + 2;
             p->regrid_todo = ctrl + 3;                       // [0] count, [1 ..] tiles
             p->far.overflow = ctrl + 4 + T.ntiles;
             p->tile_omax = (float *)(p->tile_count + 6 * ((size_t)T.ntiles + 1));
-            (void)f4;
             if (hipMemsetAsync(ctrl, 0, sizeof(int32_t) * (size_t)(T.ntiles + 8), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
         }
-        void *d9 = nullptr;
         // (+ 4096 ints behind the list: per-block totals and offsets of the multi-workgroup tile scan)
-        if (dalloc(sizeof(int32_t) * (size_t)(T.ntiles + 1 + 4096), &d9)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(wide tile list) failed"));
-        p->wide_tiles = (int32_t *)d9;
-        void *d8 = nullptr;
-        if (dalloc(sizeof(double) * 2 * (size_t)(T.ntiles + 1), &d8)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(tile sums) failed"));
-        p->tile_sums = (double *)d8;
+        if (mem.alloc(p->wide_tiles, (size_t)(T.ntiles + 1 + 4096))) return bail(alloc_fail("wide tile list"));
+        if (mem.alloc(p->tile_sums, 2 * (size_t)(T.ntiles + 1))) return bail(alloc_fail("tile sums"));
         if (hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream) != hipSuccess)
             return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
     }
@@ -945,7 +884,7 @@ void bfgx_plan_destroy(bfgx_plan *p)
     for (int k = 0; k < BFGX_NUM_KERNELS; ++k)
         for (auto &e : p->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto &e : p->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (void *d : p->owned) (void)hipFree(d);
+    p->mem.release();
     delete p;
 }
 
@@ -1619,10 +1558,10 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
         return bfgx_plan_status(p);
     }
     int64_t *counts = counts_dev;
-    void *tmp = nullptr;
+    DevBuf tmp;
     if (!counts) {
-        HIP_TRY(hipMalloc(&tmp, sizeof(int64_t) * (size_t)(cat->n > 0 ? cat->n : 1)));
-        counts = (int64_t *)tmp;
+        HIP_TRY(tmp.alloc(sizeof(int64_t) * (size_t)(cat->n > 0 ? cat->n : 1)));
+        counts = tmp.as<int64_t>();
     }
     int rc = launch_prep(p, cat, fallback4, false, false, true);
     if (!rc) rc = launch_scatter<MODE_COUNT, float>(p, cat->n, (float *)nullptr, counts);
@@ -1639,7 +1578,6 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
     } else if (!rc) {
         if (hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(BFGX_ERR_HIP, "stream sync failed");
     }
-    if (tmp) (void)hipFree(tmp);
     return rc;
 }
 
@@ -1647,12 +1585,6 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
 
 // ------------------------------------------------------------------------------ one-shot host API
 namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? 0 : 1; }
-};
 
 // Every one-shot host entry leaves NOTHING in flight when it returns -- on success and on every error path: asynchronous copies read the
 // caller's arrays (page-locked for the call, or pinned on the fly by the runtime) and write into the caller's result; a copy that is
@@ -1769,7 +1701,7 @@ int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], b
     if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
     for (int i = 0; i < kCatCols; ++i) {
         if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
-        if (cols[i].alloc(sizeof(double) * (size_t)h->n)) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
+        if (cols[i].alloc(sizeof(double) * (size_t)h->n)) return alloc_fail("catalog");
         if (h->n > 0) HIP_TRY(hipMemcpyAsync(cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
         dp[i] = (const double *)cols[i].p;
     }
@@ -1782,27 +1714,6 @@ int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], b
 // ---- plan caches of the one-shot API: a process() call re-uses the plan (model on the device, tiling, binning workspace) and the
 // device buffers of the previous call with the same model, geometry and device, so that a warm call performs no hipMalloc
 namespace {
-
-// A grow-only device buffer: a request beyond its capacity reallocates it with a slack of bytes / div + add, after the device has
-// drained (an earlier call may still use the old buffer on another stream).  Only growth waits; a warm call finds the buffer large enough.
-struct PoolBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    PoolBuf() = default;
-    PoolBuf(const PoolBuf &) = delete;
-    PoolBuf &operator=(const PoolBuf &) = delete;
-    ~PoolBuf() { if (p) (void)hipFree(p); }
-    int need(size_t bytes, size_t div = 4, size_t add = 256)
-    {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); }
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / div + add;
-        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return 1; }
-        cap = want;
-        return 0;
-    }
-};
 
 // The key of a cached entry: two independent 64-bit hashes (an FNV-style basis and prime; another basis and odd multiplier) and the
 // model table's value count.  A hit needs all three to agree, so that one 64-bit collision cannot hand a model another model's table.
@@ -1972,7 +1883,7 @@ int upload_catalog_pooled(ShellEntry *e, const bfgx_catalog *h, bfgx_catalog *d,
     if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
     for (int i = 0; i < kCatCols; ++i) {
         if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
-        if (e->cols[i].need(sizeof(double) * (size_t)std::max<int64_t>(h->n, 1))) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
+        if (e->cols[i].need(sizeof(double) * (size_t)std::max<int64_t>(h->n, 1))) return alloc_fail("catalog");
         if (h->n > 0) HIP_TRY(hipMemcpyAsync(e->cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
         dp[i] = (const double *)e->cols[i].p;
     }
@@ -2062,7 +1973,7 @@ void bfgx_debug_host_spans(long long *pinned_in_place, long long *staged, long l
     if (smallest_pinned_bytes) *smallest_pinned_bytes = g_host_pin_min_bytes.load();
 }
 
-long long bfgx_debug_alloc_count(void) { return (long long)g_bfgx_allocs.load(); }
+long long bfgx_debug_alloc_count(void) { return (long long)g_dev_allocs.load(); }
 
 int bfgx_host_alloc(size_t bytes, void **out)
 {
@@ -2097,7 +2008,7 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     HIP_TRY(hipEventRecord(e->ev[0], p->stream));
     if (int rc = upload_catalog_pooled(e, cat, &dcat, hostlog, o.catalog_token)) return rc;
     if (e->in.need(npix * sizeof(double)) || e->out.need(npix * sizeof(double)) || e->off.need(acc_bytes) || e->sums.need(40 * sizeof(double)))
-        return fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed");
+        return alloc_fail("map buffers");
     if (o.algo == 0) {                                       // global-atomic kernels accumulate; the tiled ones store every element once
         HIP_TRY(hipMemsetAsync(e->off.p, 0, acc_bytes, p->stream));
         HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
@@ -2124,7 +2035,7 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     if (piped) { map_in = (const double *)hin.use; map_out = (double *)hout.use; }       // (from here on: the page-locked views)
     if (piped) {
         if (int rc = e->pools(kChunks, kChunks)) return rc;
-        if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(sums) failed");
+        if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return alloc_fail("sums");
         double *dsums = (double *)e->sums.p;
         float *domax = (float *)(dsums + 2 * kChunks);
         auto send = [&](int c) -> int {
@@ -2249,7 +2160,7 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     Timer t;
     t.start(p->stream);
     if (int rc = upload_catalog_pooled(e, cat, &dcat, hostlog, o.catalog_token)) return rc;
-    if (e->out.need(npix * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
+    if (e->out.need(npix * sizeof(double))) return alloc_fail("map");
     const double ms_h2d = t.stop(p->stream);
     t.start(p->stream);
     // Large fp64 maps are painted in band ranges (chunk_plan), each copied back while the next ones are painted (map_out page-locked for
@@ -2313,18 +2224,6 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 // ------------------------------------------------------------------------------ table builders (a6-a8)
 namespace {
 
-struct DevArr {
-    void *p = nullptr;
-    ~DevArr() { if (p) (void)hipFree(p); }
-    int up(const void *host, size_t bytes)
-    {
-        if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) return 1;
-        if (host && bytes && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return 1;
-        return 0;
-    }
-    template <typename T> T *as() { return (T *)p; }
-};
-
 int tables_begin(int device)
 {
     if (bfgx_device_count() <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
@@ -2342,7 +2241,7 @@ int bfgx_project_profile(int device, int64_t nrows, int32_t nl, const double *l,
     if (!l || !rho || !r || !sigma_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes (1 <= nrows <= 65535, 2 <= nl <= 2048)");
     if (int rc = tables_begin(device)) return rc;
-    DevArr dl, drho, dr, dout;
+    DevBuf dl, drho, dr, dout;
     if (dl.up(l, sizeof(double) * nl) || drho.up(rho, sizeof(double) * nrows * nl) || dr.up(r, sizeof(double) * nr) ||
         dout.up(nullptr, sizeof(double) * nrows * nr))
         return fail(BFGX_ERR_HIP, "device allocation/copy failed");
@@ -2359,7 +2258,7 @@ static int enclosed_mass_rows(int dim, int device, int64_t nrows, int64_t n_int,
     if (!r_int || !Sigma || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
     if (int rc = tables_begin(device)) return rc;
-    DevArr dri, dS, dr, dcx, dcy, dM;
+    DevBuf dri, dS, dr, dcx, dcy, dM;
     if (dri.up(r_int, sizeof(double) * n_int) || dS.up(Sigma, sizeof(double) * nrows * n_int) || dr.up(r, sizeof(double) * nr) ||
         dcx.up(nullptr, sizeof(double) * nrows * n_int) || dcy.up(nullptr, sizeof(double) * nrows * n_int) ||
         dM.up(nullptr, sizeof(double) * nrows * nr))
@@ -2389,7 +2288,7 @@ int bfgx_enclosed_mass_2d(int device, int64_t nrows, int32_t nl, const double *l
     if (!l || !rho || !r_int || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
     if (int rc = tables_begin(device)) return rc;
-    DevArr dl, drho, dri, dS, dr, dcx, dcy, dM;
+    DevBuf dl, drho, dri, dS, dr, dcx, dcy, dM;
     if (dl.up(l, sizeof(double) * nl) || drho.up(rho, sizeof(double) * nrows * nl) || dri.up(r_int, sizeof(double) * n_int) ||
         dS.up(nullptr, sizeof(double) * nrows * n_int) || dr.up(r, sizeof(double) * nr) ||
         dcx.up(nullptr, sizeof(double) * nrows * n_int) || dcy.up(nullptr, sizeof(double) * nrows * n_int) ||
@@ -2412,7 +2311,7 @@ int bfgx_displacement_rows(int device, int64_t nrows, int32_t nr, const double *
     if (!r || !M_dmo || !M_dmb || !d_out || !status) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nr < 3 || nr > kMaxNR) return fail(BFGX_ERR_INVALID, "N_samples_R must be in [3, %d]", kMaxNR);
     if (int rc = tables_begin(device)) return rc;
-    DevArr dr, da, db, dd, ds;
+    DevBuf dr, da, db, dd, ds;
     if (dr.up(r, sizeof(double) * nr) || da.up(M_dmo, sizeof(double) * nrows * nr) || db.up(M_dmb, sizeof(double) * nrows * nr) ||
         dd.up(nullptr, sizeof(double) * nrows * nr) || ds.up(nullptr, sizeof(int32_t) * nrows))
         return fail(BFGX_ERR_HIP, "device allocation/copy failed");
@@ -2432,7 +2331,7 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
     if (!r500 || !rho_tot || !rho_gas || !r_out || !P_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nr_out < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
     if (int rc = tables_begin(device)) return rc;
-    DevArr dg, dt, dgas, dr, dP;
+    DevBuf dg, dt, dgas, dr, dP;
     if (dg.up(r500, sizeof(double) * kPressureN) || dt.up(rho_tot, sizeof(double) * nrows * kPressureN) ||
         dgas.up(rho_gas, sizeof(double) * nrows * kPressureN) || dr.up(r_out, sizeof(double) * nr_out) ||
         dP.up(nullptr, sizeof(double) * nrows * nr_out))

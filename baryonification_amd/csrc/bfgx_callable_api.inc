@@ -25,7 +25,7 @@ struct bfgx_pairs {
     hipStream_t sstream = nullptr;
     SnapGeom sg;
     DevModel smodel;
-    std::vector<void *> sowned;
+    DevList smem;
     int64_t snp = 0;
     DevBuf sxyz[3], srecs, skeys, sacc;
 };
@@ -41,12 +41,9 @@ void bfgx_shell_pairs_end(bfgx_pairs *h)
     bfgx_plan *p = h->plan;
     bfgx_grid_plan *gp = h->gplan;
     hipStream_t ss = h->sstream;
-    std::vector<void *> sowned;
-    sowned.swap(h->sowned);
     delete h;                       // (device buffers first: they were allocated on the plan's device)
     if (p) bfgx_plan_destroy(p);
     if (gp) bfgx_grid_plan_destroy(gp);
-    for (void *d : sowned) (void)hipFree(d);
     if (ss) (void)hipStreamDestroy(ss);
 }
 
@@ -65,7 +62,7 @@ int bfgx_shell_pairs_begin(const bfgx_catalog *cat, const bfgx_model *model, int
     std::vector<double> hostlog;
     if (int rc = upload_catalog(p, cat, h->cols, &h->dcat, hostlog)) return bail(rc);
     if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));       // (hostlog leaves scope)
-    if (h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(cat->n, 1))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair counts) failed"));
+    if (h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(cat->n, 1))) return bail(alloc_fail("pair counts"));
     // per-halo records for the halo-centric kernels (the < 4-pixel fallback is BaryonifyShell's alone: HealpixRunner.py:309-310 against :432)
     if (int rc = launch_prep(p, &h->dcat, paint ? 0 : 1, false, false, true)) return bail(rc);
     if (int rc = launch_scatter<MODE_COUNT, double>(p, cat->n, (double *)nullptr, (int64_t *)h->counts.p)) return bail(rc);
@@ -79,7 +76,7 @@ int bfgx_shell_pairs_begin(const bfgx_catalog *cat, const bfgx_model *model, int
     }
     h->total = off[(size_t)cat->n];
     if (h->off.alloc(sizeof(int64_t) * off.size()) || h->vals.alloc(sizeof(double) * (size_t)std::max<int64_t>(h->total, 1)))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair arrays) failed"));
+        return bail(alloc_fail("pair arrays"));
     if (hipMemcpy(h->off.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "copy(pair offsets) failed"));
     *out = h;
     return BFGX_OK;
@@ -109,7 +106,7 @@ int bfgx_shell_pairs_apply(bfgx_pairs *h, const double *vals_host, const double 
     const size_t npix = (size_t)p->hpx.npix;
     const size_t acc_n = h->paint ? npix : 3 * npix;
     if (h->acc.need(acc_n * sizeof(double)) || (!h->paint && (h->in.need(npix * sizeof(double)) || h->out.need(npix * sizeof(double)) || h->sums.need(40 * sizeof(double)))))
-        return fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed");
+        return alloc_fail("map buffers");
     hipStream_t s = p->stream;
     HIP_TRY(hipMemsetAsync(h->acc.p, 0, acc_n * sizeof(double), s));
     if (h->total > 0) HIP_TRY(hipMemcpyAsync(h->vals.p, vals_host, sizeof(double) * (size_t)h->total, hipMemcpyHostToDevice, s));

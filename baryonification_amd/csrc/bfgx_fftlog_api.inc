@@ -102,7 +102,7 @@ int bfgx_fftlog_transform(int device, int64_t nrows, int32_t n, const double *r,
     FftlogStage s;
     if (int rc = fftlog_stage(n, r, dim, mu, plaw, s)) return rc;
     if (int rc = tables_begin(device)) return rc;
-    DevArr din, dpre, du, dpost, dout;
+    DevBuf din, dpre, du, dpost, dout;
     if (din.up(f, sizeof(double) * nrows * n) || dpre.up(s.pre.data(), sizeof(double) * n) || du.up(s.u.data(), sizeof(double) * s.u.size()) ||
         dpost.up(s.post.data(), sizeof(double) * n) || dout.up(nullptr, sizeof(double) * nrows * n))
         return fail(BFGX_ERR_HIP, "device allocation/copy failed");
@@ -129,7 +129,7 @@ int bfgx_fftlog_convolve(int device, int64_t nrows, int32_t n, const double *r_f
     }
     for (int i = 0; i < nq; ++i) lnq[i] = std::log(r_eval[i]);
     if (int rc = tables_begin(device)) return rc;
-    DevArr din, dpre, du1, dmid, dtmp, du2, dpost, dg, dx, dq, dout;
+    DevBuf din, dpre, du1, dmid, dtmp, du2, dpost, dg, dx, dq, dout;
     if (din.up(prof, sizeof(double) * nrows * n) || dpre.up(s1.pre.data(), sizeof(double) * n) || du1.up(s1.u.data(), sizeof(double) * s1.u.size()) ||
         dmid.up(mid.data(), sizeof(double) * n) || dtmp.up(nullptr, sizeof(double) * nrows * n) || du2.up(s2.u.data(), sizeof(double) * s2.u.size()) ||
         dpost.up(s2.post.data(), sizeof(double) * n) || dg.up(nullptr, sizeof(double) * nrows * n) || dx.up(lnr.data(), sizeof(double) * n) ||

@@ -8,7 +8,7 @@ struct bfgx_grid_plan {
     DevModel model;
     int NC = 4;
     int64_t max_halos = 0;
-    std::vector<void *> owned;
+    DevList mem;
     GridHaloRec *recs = nullptr;
     int32_t *chunk_halo = nullptr;        // work-item table (regrown on demand)
     int64_t capacity = 0;
@@ -110,11 +110,8 @@ int grid_halo_loop(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode, doub
         if (cnt[0] < 0) return fail(BFGX_ERR_INVALID, "more than 2^31 work items (%d-pixel chunks): catalog too large for one call", kGridChunk);
         if ((int64_t)cnt[0] <= p->capacity) break;
         // the work-item table was too small: grow it and redo the (deterministic) preparation
-        void *d = nullptr;
         const int64_t cap = (int64_t)cnt[0] + cnt[0] / 4 + 1024;
-        HIP_TRY(hipMalloc(&d, sizeof(int32_t) * (size_t)cap));
-        for (auto &o : p->owned) if (o == (void *)p->chunk_halo) { (void)hipFree(o); o = d; }
-        p->chunk_halo = (int32_t *)d;
+        HIP_TRY(p->mem.regrow(p->chunk_halo, (size_t)cap));
         p->capacity = cap;
     }
     if (cnt[1] & 1) return fail(BFGX_ERR_ASSERT, "Halo offsets are larger than res (Map2DRunner.py:516)");
@@ -148,7 +145,7 @@ struct GridHostCatalog {
         for (int i = 0; i < 6 + nex; ++i) {
             if (!src[i]) continue;
             const size_t bytes = sizeof(double) * (size_t)h->n * width[i];
-            if (cols[i].need(std::max<size_t>(bytes, 8))) return fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed");
+            if (cols[i].need(std::max<size_t>(bytes, 8))) return alloc_fail("catalog");
             if (h->n > 0) HIP_TRY(hipMemcpyAsync(cols[i].p, src[i], bytes, hipMemcpyHostToDevice, s));
             *dst[i] = (const double *)cols[i].p;
         }
@@ -178,13 +175,12 @@ int bfgx_grid_plan_create(int device, void *hip_stream, const bfgx_grid *grid, i
     p->stream = (hipStream_t)hip_stream;
     p->max_halos = max_halos;
     auto bail = [&](int rc) { bfgx_grid_plan_destroy(p); return rc; };
-    if (int rc = upload_model(p->owned, p->stream, model, false, p->model, p->NC)) return bail(rc);
+    if (int rc = upload_model(p->mem, p->stream, model, false, p->model, p->NC)) return bail(rc);
     {
-        const void *dv = nullptr;
-        if (int rc = owned_upload(p->owned, p->stream, grid->bins, sizeof(double) * grid->npix, &dv)) return bail(rc);
-        if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
         GridGeom &g = p->geom;
-        g.ndim = grid->ndim; g.npix = grid->npix; g.bins = (const double *)dv;
+        if (int rc = owned_upload(p->mem, p->stream, grid->bins, (size_t)grid->npix, g.bins)) return bail(rc);
+        if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
+        g.ndim = grid->ndim; g.npix = grid->npix;
         g.res = grid->bins[1] - grid->bins[0];                          // io.py:469
         double bmax = grid->bins[0];
         for (int i = 1; i < grid->npix; ++i) bmax = std::max(bmax, grid->bins[i]);
@@ -194,21 +190,13 @@ int bfgx_grid_plan_create(int device, void *hip_stream, const bfgx_grid *grid, i
         for (int d = 0; d < grid->ndim; ++d) g.ntot *= grid->npix;
         g.slab_lo = 0; g.slab_n = grid->npix;
     }
-    auto dalloc = [&](size_t bytes, void **ptr) {
-        if (hipMalloc(ptr, bytes ? bytes : 8) != hipSuccess) return 1;
-        p->owned.push_back(*ptr);
-        return 0;
-    };
     p->capacity = 4 * max_halos + 65536;
     if (const char *e = std::getenv("BFGX_GRID_ITEM_CAP")) p->capacity = std::max<int64_t>(1, std::atoll(e));   // tests: force regrowth
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr, *d4 = nullptr;
     // (at least 2048 entries: the cell-owned pass keeps the per-workgroup sums of its copy kernel here)
-    if (dalloc(sizeof(double) * std::max<size_t>(2 * (size_t)((p->geom.ntot + 255) / 256), 2048), &d4)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(block sums) failed"));
-    p->block_sums = (double *)d4;
-    if (dalloc(sizeof(GridHaloRec) * (size_t)std::max<int64_t>(max_halos, 1), &d0) || dalloc(sizeof(int32_t) * (size_t)p->capacity, &d1) ||
-        dalloc(2 * sizeof(int32_t), &d2) || dalloc(sizeof(unsigned long long), &d3))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(grid workspace) failed"));
-    p->recs = (GridHaloRec *)d0; p->chunk_halo = (int32_t *)d1; p->counters = (int32_t *)d2; p->pair_total = (unsigned long long *)d3;
+    if (p->mem.alloc(p->block_sums, std::max<size_t>(2 * (size_t)((p->geom.ntot + 255) / 256), 2048))) return bail(alloc_fail("block sums"));
+    if (p->mem.alloc(p->recs, (size_t)std::max<int64_t>(max_halos, 1)) || p->mem.alloc(p->chunk_halo, (size_t)p->capacity) ||
+        p->mem.alloc(p->counters, 2) || p->mem.alloc(p->pair_total, 1))
+        return bail(alloc_fail("grid workspace"));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) p->n_cu = prop.multiProcessorCount;
     *out = p;
@@ -220,7 +208,7 @@ void bfgx_grid_plan_destroy(bfgx_grid_plan *p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)hipStreamSynchronize(p->stream);
-    for (void *d : p->owned) (void)hipFree(d);
+    p->mem.release();
     for (int k = 0; k < BFGX_NUM_KERNELS; ++k)
         for (auto &e : p->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto &e : p->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -300,17 +288,14 @@ int gather_workspace(bfgx_grid_plan *p)
     p->nscan_blocks = (int)((p->nblk + 1 + kScanPerBlock - 1) / kScanPerBlock);
     p->list_capacity = 16 * p->max_halos + 65536;
     if (const char *e = std::getenv("BFGX_GRID_ITEM_CAP")) p->list_capacity = std::max<int64_t>(1, std::atoll(e));   // tests: force regrowth
-    void *d[8] = {nullptr};
-    const size_t bytes[8] = {sizeof(int32_t) * (size_t)(p->nblk + 1), sizeof(int32_t) * (size_t)(p->nblk + 1), sizeof(int32_t) * (size_t)p->nscan_blocks,
-                             sizeof(int64_t), sizeof(double) * 3 * (size_t)p->nblk, sizeof(int32_t) * (size_t)p->list_capacity,
-                             sizeof(int32_t) * (size_t)p->nblk, sizeof(int32_t) * (kGatherRangesMax + 4)};
-    for (int i = 0; i < 8; ++i) {
-        if (hipMalloc(&d[i], bytes[i]) != hipSuccess) return fail(BFGX_ERR_HIP, "hipMalloc(block lists) failed");
-        p->owned.push_back(d[i]);
-    }
-    p->blk_count = (int32_t *)d[0]; p->blk_start = (int32_t *)d[1]; p->blk_bsum = (int32_t *)d[2]; p->blk_total = (int64_t *)d[3];
-    p->blk_sums = (double *)d[4]; p->blk_list = (int32_t *)d[5];
-    p->blk_nz = (int32_t *)d[6]; p->blk_nzn = (int32_t *)d[7];
+    // (blk_count, which marks the workspace as present, last: a failure part-way leaves the next call to try again)
+    int32_t *count = nullptr;
+    DevList &mem = p->mem;
+    if (mem.alloc(count, (size_t)(p->nblk + 1)) || mem.alloc(p->blk_start, (size_t)(p->nblk + 1)) || mem.alloc(p->blk_bsum, (size_t)p->nscan_blocks) ||
+        mem.alloc(p->blk_total, 1) || mem.alloc(p->blk_sums, 3 * (size_t)p->nblk) || mem.alloc(p->blk_list, (size_t)p->list_capacity) ||
+        mem.alloc(p->blk_nz, (size_t)p->nblk) || mem.alloc(p->blk_nzn, (size_t)(kGatherRangesMax + 4)))
+        return alloc_fail("block lists");
+    p->blk_count = count;
     p->axis0_flag = p->blk_nzn + kGatherRangesMax;           // (the streamed host entry: a cell moved beyond what its plane ranges allow)
     return BFGX_OK;
 }
@@ -398,11 +383,8 @@ static int grid_lists_stage(bfgx_grid_plan *p, const bfgx_grid_catalog *c, Gathe
     if (cnt[1] & 1) return fail(BFGX_ERR_ASSERT, "Halo offsets are larger than res (Map2DRunner.py:516)");
     if (total > (int64_t)INT32_MAX) return fail(BFGX_ERR_INVALID, "block lists exceed 2^31 entries: split the catalog");
     if (total > p->list_capacity) {
-        void *d = nullptr;
         const int64_t cap = total + total / 4 + 1024;
-        HIP_TRY(hipMalloc(&d, sizeof(int32_t) * (size_t)cap));
-        for (auto &o : p->owned) if (o == (void *)p->blk_list) { (void)hipFree(o); o = d; }
-        p->blk_list = (int32_t *)d;
+        HIP_TRY(p->mem.regrow(p->blk_list, (size_t)cap));
         p->list_capacity = cap;
     }
     if (c->n > 0 && total > 0) {
@@ -523,7 +505,7 @@ int grid_acquire(int device, const bfgx_grid *grid, const bfgx_model *model, int
     auto make = [&](int64_t cap, bfgx_grid_plan **p) { return bfgx_grid_plan_create(device, nullptr, grid, cap, model, p); };
     auto setup = [](GridEntry *e) -> int {
         const size_t bytes = (size_t)e->plan->geom.ntot * sizeof(double);
-        if (!e->in.p && (e->in.alloc(bytes) || e->out.alloc(bytes) || e->sums.alloc(2 * sizeof(double)))) return fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed");
+        if (!e->in.p && (e->in.alloc(bytes) || e->out.alloc(bytes) || e->sums.alloc(2 * sizeof(double)))) return alloc_fail("map buffers");
         return BFGX_OK;
     };
     return g_grids.acquire(key, device, n, make, setup, out);
@@ -666,7 +648,7 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
         HIP_TRY(hipEventRecord(e->ev[1], s));
         if (scatter) {
             DevBuf d_off;
-            if (d_off.alloc(ntot * ndim * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(pix_offsets) failed");
+            if (d_off.alloc(ntot * ndim * sizeof(double))) return alloc_fail("pix_offsets");
             if (int rc = bfgx_grid_offsets_device(p, &hc.d, (double *)d_off.p, &npairs)) return rc;
             if (int rc = bfgx_grid_regrid_device(p, d_in, (const double *)d_off.p, d_out, d_sums)) return rc;
             HIP_TRY(hipStreamSynchronize(s));
@@ -707,7 +689,7 @@ int bfgx_paint_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, const
     Timer t;
     t.start(p->stream);
     if (int rc = hc.upload(cat, grid->ndim, p->model.tab.ndim - 3, p->stream)) return rc;
-    if (d_out.alloc(ntot * sizeof(double))) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
+    if (d_out.alloc(ntot * sizeof(double))) return alloc_fail("map");
     const double ms_h2d = t.stop(p->stream);
     t.start(p->stream);
     int64_t npairs = 0;
@@ -732,7 +714,7 @@ int bfgx_regrid_pixels(int device, int32_t ndim, int32_t npix, int64_t n, const 
     if (int rc = tables_begin(device)) return rc;
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)npix;
-    DevArr dp, dv, dg;
+    DevBuf dp, dv, dg;
     if (dp.up(positions, sizeof(double) * (size_t)n * ndim) || dv.up(values, sizeof(double) * (size_t)n) || dg.up(grid, sizeof(double) * ntot))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
     if (n > 0) {
@@ -751,11 +733,7 @@ namespace {
 
 // grow-only workspace of the tiled deposit, one per device (released by bfgx_cache_clear); one deposit in flight per device
 struct DepWork {
-    uint32_t *keys[2] = {nullptr, nullptr};
-    double *mass[2] = {nullptr, nullptr};
-    int32_t *ctr = nullptr, *bsum = nullptr;
-    int64_t *total = nullptr;
-    size_t cap_n = 0, cap_m = 0, cap_ctr = 0;
+    PoolBuf keys[2], mass[2], ctr, bsum, total;     // uint32_t keys, double masses, int32_t counters and block sums, one int64_t (slack: an eighth)
 };
 std::mutex g_dep_mu;
 std::map<int, DepWork> g_dep;
@@ -763,13 +741,10 @@ std::map<int, DepWork> g_dep;
 void dep_release_all()
 {
     std::lock_guard<std::mutex> lk(g_dep_mu);
-    for (auto &kv : g_dep) {
-        (void)hipSetDevice(kv.first);
-        DepWork &w = kv.second;
-        for (void *q : {(void *)w.keys[0], (void *)w.keys[1], (void *)w.mass[0], (void *)w.mass[1], (void *)w.ctr, (void *)w.bsum, (void *)w.total})
-            if (q) (void)hipFree(q);
+    while (!g_dep.empty()) {
+        (void)hipSetDevice(g_dep.begin()->first);
+        g_dep.erase(g_dep.begin());
     }
-    g_dep.clear();
 }
 
 // keys_by (optional): who writes the keys [n] and the per-chunk level-1 histograms [B1][chunks] instead of deposit_keys_kernel (the snapshot
@@ -785,29 +760,33 @@ int deposit_tiled(DepWork &w, const DepGeom &g, hipStream_t s, int64_t n, const 
     const unsigned chunks = (unsigned)((n + kDepChunk - 1) / kDepChunk);
     const size_t o_c2 = 0, o_s2 = o_c2 + g.T + 1, o_k2 = o_s2 + g.T + 1, o_wg = o_k2 + (size_t)g.T * kDepPad;
     const int64_t nwg = (int64_t)g.B1 * chunks + 1;
-    HIP_TRY(hipMemsetAsync(w.ctr, 0, sizeof(int32_t) * (o_wg + (size_t)nwg), s));
-    int32_t *c2 = w.ctr + o_c2, *s2 = w.ctr + o_s2, *k2 = w.ctr + o_k2, *wg = w.ctr + o_wg;
-    if (keys_by) { if (int rc = (*keys_by)(g, w.keys[0], wg, chunks)) return rc; }
-    else hipLaunchKernelGGL(deposit_keys_kernel<DIM>, dim3(chunks), dim3(256), 0, s, g, n, x, y, z, edges_dev, w.keys[0], wg, stride);
+    uint32_t *const keys[2] = {w.keys[0].as<uint32_t>(), w.keys[1].as<uint32_t>()};
+    double *const wmass[2] = {w.mass[0].as<double>(), w.mass[1].as<double>()};
+    int32_t *const ctr = w.ctr.as<int32_t>(), *const bsum = w.bsum.as<int32_t>();
+    int64_t *const total = w.total.as<int64_t>();
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(int32_t) * (o_wg + (size_t)nwg), s));
+    int32_t *c2 = ctr + o_c2, *s2 = ctr + o_s2, *k2 = ctr + o_k2, *wg = ctr + o_wg;
+    if (keys_by) { if (int rc = (*keys_by)(g, keys[0], wg, chunks)) return rc; }
+    else hipLaunchKernelGGL(deposit_keys_kernel<DIM>, dim3(chunks), dim3(256), 0, s, g, n, x, y, z, edges_dev, keys[0], wg, stride);
     {
         const int nb1 = (int)((nwg + kScanPerBlock - 1) / kScanPerBlock);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(nb1), dim3(kTabThreads), 0, s, nwg, (const int32_t *)wg, wg, w.bsum, 1);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nb1, w.bsum, w.total);
-        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, s, nwg, wg, (const int32_t *)w.bsum);
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(nb1), dim3(kTabThreads), 0, s, nwg, (const int32_t *)wg, wg, bsum, 1);
+        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nb1, bsum, total);
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, s, nwg, wg, (const int32_t *)bsum);
     }
-    hipLaunchKernelGGL((deposit_split_kernel<1, MASS>), dim3(chunks), dim3(256), 0, s, g, n, (const int32_t *)nullptr, (const uint32_t *)w.keys[0],
-                       mass, (const int32_t *)wg, (int32_t *)nullptr, w.keys[1], w.mass[0], stride);
+    hipLaunchKernelGGL((deposit_split_kernel<1, MASS>), dim3(chunks), dim3(256), 0, s, g, n, (const int32_t *)nullptr, (const uint32_t *)keys[0],
+                       mass, (const int32_t *)wg, (int32_t *)nullptr, keys[1], wmass[0], stride);
     const int32_t *nvalid = wg + (nwg - 1);             // particles inside the edges
-    hipLaunchKernelGGL(deposit_count_kernel, dim3(chunks), dim3(256), 0, s, g, nvalid, (const uint32_t *)w.keys[1], c2);
+    hipLaunchKernelGGL(deposit_count_kernel, dim3(chunks), dim3(256), 0, s, g, nvalid, (const uint32_t *)keys[1], c2);
     const int64_t nscan = (int64_t)g.T + 1;
     const int nblocks = (int)((nscan + kScanPerBlock - 1) / kScanPerBlock);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(nblocks), dim3(kTabThreads), 0, s, nscan, (const int32_t *)c2, s2, w.bsum, 1);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nblocks, w.bsum, w.total);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nscan + 255) / 256)), dim3(256), 0, s, nscan, s2, (const int32_t *)w.bsum);
-    hipLaunchKernelGGL((deposit_split_kernel<2, MASS>), dim3(chunks), dim3(256), 0, s, g, n, nvalid, (const uint32_t *)w.keys[1],
-                       (const double *)w.mass[0], (const int32_t *)s2, k2, w.keys[0], w.mass[1], (int64_t)1);
-    hipLaunchKernelGGL(deposit_tiles_kernel<MASS>, dim3(g.T), dim3(DepTileThreads<MASS>::n), 0, s, g, (const int32_t *)s2, (const uint32_t *)w.keys[0],
-                       (const double *)w.mass[1], map_out_dev, map_out2_dev, tile_sums_dev);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(nblocks), dim3(kTabThreads), 0, s, nscan, (const int32_t *)c2, s2, bsum, 1);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nblocks, bsum, total);
+    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nscan + 255) / 256)), dim3(256), 0, s, nscan, s2, (const int32_t *)bsum);
+    hipLaunchKernelGGL((deposit_split_kernel<2, MASS>), dim3(chunks), dim3(256), 0, s, g, n, nvalid, (const uint32_t *)keys[1],
+                       (const double *)wmass[0], (const int32_t *)s2, k2, keys[0], wmass[1], (int64_t)1);
+    hipLaunchKernelGGL(deposit_tiles_kernel<MASS>, dim3(g.T), dim3(DepTileThreads<MASS>::n), 0, s, g, (const int32_t *)s2, (const uint32_t *)keys[0],
+                       (const double *)wmass[1], map_out_dev, map_out2_dev, tile_sums_dev);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
@@ -889,25 +868,10 @@ static int deposit_impl(int device, void *hip_stream, int32_t ndim, int64_t n, c
         std::lock_guard<std::mutex> lk(g_dep_mu);
         DepWork &w = g_dep[device];
         const size_t nctr = (2 + (size_t)kDepPad) * ((size_t)g.T + 1) + (size_t)g.B1 * (size_t)((n + kDepChunk - 1) / kDepChunk) + 8;
-        auto grow = [&](void **ptr, size_t bytes) {
-            if (*ptr) { (void)hipDeviceSynchronize(); (void)hipFree(*ptr); *ptr = nullptr; }     // (an earlier deposit may have run on another stream)
-            return hipMalloc(ptr, bytes) != hipSuccess;
-        };
-        if ((size_t)n > w.cap_n) {
-            const size_t cap = (size_t)n + (size_t)n / 8;
-            if (grow((void **)&w.keys[0], sizeof(uint32_t) * cap) || grow((void **)&w.keys[1], sizeof(uint32_t) * cap)) return fail(BFGX_ERR_HIP, "hipMalloc(deposit keys) failed");
-            w.cap_n = cap;
-        }
-        if (mass && (size_t)n > w.cap_m) {
-            const size_t cap = (size_t)n + (size_t)n / 8;
-            if (grow((void **)&w.mass[0], sizeof(double) * cap) || grow((void **)&w.mass[1], sizeof(double) * cap)) return fail(BFGX_ERR_HIP, "hipMalloc(deposit masses) failed");
-            w.cap_m = cap;
-        }
-        if (nctr > w.cap_ctr) {
-            if (grow((void **)&w.ctr, sizeof(int32_t) * nctr) || grow((void **)&w.bsum, sizeof(int32_t) * (nctr / kScanPerBlock + 2)) ||
-                grow((void **)&w.total, sizeof(int64_t))) return fail(BFGX_ERR_HIP, "hipMalloc(deposit counters) failed");
-            w.cap_ctr = nctr;
-        }
+        if (w.keys[0].need(sizeof(uint32_t) * (size_t)n, 8, 0) || w.keys[1].need(sizeof(uint32_t) * (size_t)n, 8, 0)) return alloc_fail("deposit keys");
+        if (mass && (w.mass[0].need(sizeof(double) * (size_t)n, 8, 0) || w.mass[1].need(sizeof(double) * (size_t)n, 8, 0))) return alloc_fail("deposit masses");
+        if (w.ctr.need(sizeof(int32_t) * nctr, 8, 0) || w.bsum.need(sizeof(int32_t) * (nctr / kScanPerBlock + 2), 8, 0) || w.total.need(sizeof(int64_t), 8, 0))
+            return alloc_fail("deposit counters");
         if (ntiles) *ntiles = g.T;
         if (ndim == 3) return mass ? deposit_tiled<3, true>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by)
                                    : deposit_tiled<3, false>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by);
@@ -955,7 +919,7 @@ int bfgx_deposit_particles(int device, int32_t ndim, int64_t n, const double *x,
     if (int rc = tables_begin(device)) return rc;
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
-    DevArr dx, dy, dz, dm, de, dout;
+    DevBuf dx, dy, dz, dm, de, dout;
     const size_t nb = sizeof(double) * (size_t)n;
     if (dx.up(x, nb) || dy.up(y, nb) || (ndim == 3 && dz.up(z, nb)) || (mass && dm.up(mass, nb)) || de.up(edges, sizeof(double) * (n_grid + 1)) ||
         dout.up(nullptr, sizeof(double) * ntot))
@@ -1004,7 +968,7 @@ int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const vo
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
-    if (b.rec.need(rbytes, 8, 8) || b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return fail(BFGX_ERR_HIP, "hipMalloc(deposit records) failed");
+    if (b.rec.need(rbytes, 8, 8) || b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return alloc_fail("deposit records");
     if (!b.up) HIP_TRY(hipStreamCreateWithFlags(&b.up, hipStreamNonBlocking));
     DrainOnExit drain;
     drain.s[0] = &b.up;
@@ -1043,8 +1007,8 @@ namespace {
 
 // twiddles exp(-2 pi i k / N) and the notebook's k axis / bins (cells 12: fftfreq, linspace), built on the host
 struct FftSetup {
-    DevArr dtw, dkl;
-    DevArr dtab, dksb, dcnb;          // the tabulated bins (pk_table_build_kernel), built by the first binned pass when nk <= 254
+    DevBuf dtw, dkl;
+    DevBuf dtab, dksb, dcnb;          // the tabulated bins (pk_table_build_kernel), built by the first binned pass when nk <= 254
     bool tab_ready = false;
     int lg = 0, nz = 0, tile = 1, lt = 2, threads = 256;
     unsigned ztiles = 1;
@@ -1184,7 +1148,7 @@ int fft_axis0_pk(FftSetup &f, hipStream_t s, int N, int nb, int b0, double2 *F, 
     if (use_tab && !f.tab_ready) {
         if (f.dtab.up(nullptr, ((size_t)N * f.ztiles * N) << f.lt) || f.dksb.up(nullptr, sizeof(double) * (size_t)N * nk) ||
             f.dcnb.up(nullptr, sizeof(unsigned long long) * (size_t)N * nk))
-            return fail(BFGX_ERR_HIP, "hipMalloc(P(k) bin table) failed");
+            return alloc_fail("P(k) bin table");
         PkBins all = pb;
         all.b0 = 0;
         hipLaunchKernelGGL(pk_table_build_kernel, dim3((unsigned)N), dim3(kFftBlock), 16 * (size_t)nk, s, all, N, f.nz, f.lt, (int)f.ztiles, f.dtab.as<uint8_t>(),
@@ -1263,7 +1227,7 @@ int bfgx_power_spectrum(int device, int32_t n_grid, const double *map, double L,
     if (nk < 1 || nk > 2048) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048");
     if (int rc = tables_begin(device)) return rc;
     const size_t N = n_grid;
-    DevArr dm, dw, dp, dk, dc;
+    DevBuf dm, dw, dp, dk, dc;
     if (dm.up(map, sizeof(double) * N * N * N) || dw.up(nullptr, sizeof(double) * (size_t)bfgx_power_spectrum_work_doubles(n_grid)) || dp.up(nullptr, sizeof(double) * nk) ||
         dk.up(nullptr, sizeof(double) * nk) || dc.up(nullptr, sizeof(unsigned long long) * nk))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");

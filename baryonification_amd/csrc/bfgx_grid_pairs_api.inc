@@ -58,7 +58,7 @@ int bfgx_grid_pairs_begin(const bfgx_grid_catalog *cat, const bfgx_model *model,
     const int64_t n = cat->n;
     h->n = n; h->paint = paint ? 1 : 0;
     if (int rc = h->gcat.upload(cat, grid->ndim, 0, p->stream)) return bail(rc);
-    if (h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair counts) failed"));
+    if (h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1))) return bail(alloc_fail("pair counts"));
     int32_t flags = 0;
     if (hipMemsetAsync(p->counters, 0, 2 * sizeof(int32_t), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "memset failed"));
     if (n > 0) {
@@ -88,9 +88,9 @@ int bfgx_grid_pairs_begin(const bfgx_grid_catalog *cat, const bfgx_model *model,
     if (nitems > INT32_MAX) return bail(fail(BFGX_ERR_INVALID, "more than 2^31 work items (%d-pixel chunks): catalog too large for one call", kGridChunk));
     if (h->off.alloc(sizeof(int64_t) * ((size_t)n + 1)) || h->item0.alloc(sizeof(int64_t) * ((size_t)n + 1)) ||
         h->item_halo.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nitems, 1)))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair tables) failed"));
+        return bail(alloc_fail("pair tables"));
     const size_t ntot = (size_t)p->geom.ntot, acc_n = h->paint ? ntot : (size_t)p->geom.ndim * ntot;
-    if (h->acc.need(acc_n * sizeof(double))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(accumulator) failed"));
+    if (h->acc.need(acc_n * sizeof(double))) return bail(alloc_fail("accumulator"));
     if (hipMemcpyAsync(h->off.p, h->off_h.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(h->item0.p, h->item0_h.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemsetAsync(h->acc.p, 0, acc_n * sizeof(double), p->stream) != hipSuccess)
@@ -113,7 +113,7 @@ int bfgx_grid_pairs_radii(bfgx_pairs *h, int64_t j0, int64_t j1, double *r_host)
     bfgx_grid_plan *p = h->gplan;
     HIP_TRY(hipSetDevice(p->device));
     if (np > 0) {
-        if (h->batch.need(sizeof(double) * (size_t)np)) return fail(BFGX_ERR_HIP, "hipMalloc(pair batch) failed");
+        if (h->batch.need(sizeof(double) * (size_t)np)) return alloc_fail("pair batch");
         if (int rc = launch_grid_pairs<0>(h, j0, j1, nullptr, (double *)h->batch.p)) return rc;
         HIP_TRY(hipMemcpyAsync(r_host, h->batch.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, p->stream));
     }
@@ -129,7 +129,7 @@ int bfgx_grid_pairs_apply(bfgx_pairs *h, int64_t j0, int64_t j1, const double *v
     bfgx_grid_plan *p = h->gplan;
     HIP_TRY(hipSetDevice(p->device));
     if (np > 0) {
-        if (h->batch.need(sizeof(double) * (size_t)np)) return fail(BFGX_ERR_HIP, "hipMalloc(pair batch) failed");
+        if (h->batch.need(sizeof(double) * (size_t)np)) return alloc_fail("pair batch");
         HIP_TRY(hipMemcpyAsync(h->batch.p, vals_host, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, p->stream));
         const int rc = h->paint ? launch_grid_pairs<2>(h, j0, j1, (const double *)h->batch.p, (double *)h->acc.p)
                                 : launch_grid_pairs<1>(h, j0, j1, (const double *)h->batch.p, (double *)h->acc.p);
@@ -151,7 +151,7 @@ int bfgx_grid_pairs_finish(bfgx_pairs *h, const double *map_in, double *map_out,
         HIP_TRY(hipMemcpyAsync(map_out, h->acc.p, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
     } else {
         if (h->in.need(ntot * sizeof(double)) || h->out.need(ntot * sizeof(double)) || h->sums.need(2 * sizeof(double)))
-            return fail(BFGX_ERR_HIP, "hipMalloc(map buffers) failed");
+            return alloc_fail("map buffers");
         HIP_TRY(hipMemcpyAsync(h->in.p, map_in, ntot * sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(h->sums.p, 0, 2 * sizeof(double), s));
         if (int rc = bfgx_grid_regrid_device(p, (const double *)h->in.p, (const double *)h->acc.p, (double *)h->out.p, (double *)h->sums.p)) return rc;

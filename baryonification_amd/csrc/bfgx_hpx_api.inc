@@ -117,7 +117,7 @@ int bfgx_hpx_ud_grade(int device, int64_t nside_in, int64_t nside_out, int64_t n
     if (int rc = tables_begin(device)) return rc;
     const size_t bin = hpx_dsize(dtype_in) * (size_t)nmaps * 12 * nside_in * nside_in;
     const size_t bout = hpx_dsize(dtype_out) * (size_t)nmaps * 12 * nside_out * nside_out;
-    DevArr di, dout;
+    DevBuf di, dout;
     if (di.up(map_in, bin) || dout.up(nullptr, bout)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
     if (int rc = hpx_ud_grade_enqueue(nullptr, nside_in, nside_out, nmaps, nest_in, nest_out, pess, ratio, dtype_in, dtype_out, di.p, dout.p))
         return rc;
@@ -154,7 +154,7 @@ int bfgx_hpx_interp_weights(int device, int64_t nside, int32_t nest, int64_t n, 
     }
     if (int rc = tables_begin(device)) return rc;
     if (n == 0) return BFGX_OK;
-    DevArr dt, dp, di, dpix, dw;
+    DevBuf dt, dp, di, dpix, dw;
     if ((ipix ? di.up(ipix, sizeof(int64_t) * n) : (dt.up(theta, sizeof(double) * n) || dp.up(phi, sizeof(double) * n))) ||
         dpix.up(nullptr, sizeof(int64_t) * 4 * n) || dw.up(nullptr, sizeof(double) * 4 * n))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
@@ -197,7 +197,7 @@ int bfgx_hpx_interp_val(int device, int64_t nside, int32_t nest, int64_t nmaps, 
     if (int rc = hpx_check_angles(n, theta, phi)) return rc;
     if (int rc = tables_begin(device)) return rc;
     if (n == 0) return BFGX_OK;
-    DevArr dm, dt, dp, dout;
+    DevBuf dm, dt, dp, dout;
     if (dm.up(maps, hpx_dsize(dtype) * (size_t)nmaps * 12 * nside * nside) || dt.up(theta, sizeof(double) * n) || dp.up(phi, sizeof(double) * n) ||
         dout.up(nullptr, sizeof(double) * nmaps * n))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
@@ -231,7 +231,7 @@ int bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap, int64_t n, cons
                         (long long)npix);
     if (int rc = tables_begin(device)) return rc;
     if (n == 0) return BFGX_OK;
-    DevArr dh, dv, dp, dw;
+    DevBuf dh, dv, dp, dw;
     if (dh.up(hmap, sizeof(double) * npix) || dv.up(vals, sizeof(double) * n) || dp.up(pix, sizeof(int64_t) * 4 * n) ||
         dw.up(w, sizeof(double) * 4 * n))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");

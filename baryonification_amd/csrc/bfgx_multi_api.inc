@@ -31,9 +31,12 @@ struct MultiRank {
     hipEvent_t packed = nullptr;             // the rank's shard is packed by destination
     hipEvent_t done = nullptr;               // the rank's slice of pix_offsets / of the painted map is complete
     bfgx_plan *plan = nullptr;
-    void *cols[kCatCols] = {};
-    void *rings = nullptr, *counts = nullptr, *cursor = nullptr, *rows = nullptr, *recv = nullptr, *rcols = nullptr;
-    void *full = nullptr, *map = nullptr, *out = nullptr, *sums = nullptr, *omax = nullptr;
+    DevList mem;                             // the rank's device buffers, below
+    double *cols[kCatCols] = {};
+    int32_t *rings = nullptr, *counts = nullptr, *cursor = nullptr;
+    double *rows = nullptr, *recv = nullptr, *rcols = nullptr, *map = nullptr, *out = nullptr, *sums = nullptr;
+    char *full = nullptr;                    // pix_offsets / painted values of the rank's slice and its widest apron (fp32 or fp64)
+    float *omax = nullptr;
     int64_t n0 = 0, n1 = 0;                  // halo shard
     int64_t nrecv = 0;                       // halos routed to this rank
     int32_t b0 = 0, b1 = 0;                  // bands
@@ -44,8 +47,7 @@ struct MultiRank {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (plan) bfgx_plan_destroy(plan);
-        for (void *c : cols) if (c) (void)hipFree(c);
-        for (void *q : {rings, counts, cursor, rows, recv, rcols, full, map, out, sums, omax}) if (q) (void)hipFree(q);
+        mem.release();
         if (packed) (void)hipEventDestroy(packed);
         if (done) (void)hipEventDestroy(done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -134,7 +136,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         if (int rc = bfgx_plan_create(r.device, r.stream, nside, 16, model, &r.plan)) return rc;      // probe: bands, ring ranges, routing
         for (int q = 0; q < ncol; ++q) {
             const int i = colidx[q];
-            HIP_TRY(hipMalloc(&r.cols[i], sizeof(double) * (size_t)std::max<int64_t>(n, 1)));
+            HIP_TRY(r.mem.alloc(r.cols[i], (size_t)std::max<int64_t>(n, 1)));
             if (n > 0) HIP_TRY(hipMemcpyAsync(r.cols[i], src[i] + r.n0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, r.stream));
         }
     }
@@ -155,12 +157,12 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         HIP_TRY(hipSetDevice(r.device));
         const int64_t n = r.n1 - r.n0;
         bfgx_catalog dc;
-        catalog_view(n, nex, (const double *const *)r.cols, &dc);
-        HIP_TRY(hipMalloc(&r.rings, sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(n, 1)));
-        HIP_TRY(hipMalloc(&r.counts, sizeof(int32_t) * N));
-        HIP_TRY(hipMalloc(&r.cursor, sizeof(int32_t) * N));
-        if (int rc = bfgx_disc_rings_device(r.plan, &dc, (int32_t *)r.rings)) return rc;
-        if (int rc = bfgx_route_count_device(r.plan, n, (const int32_t *)r.rings, N, ring_bounds.data(), (int32_t *)r.counts)) return rc;
+        catalog_view(n, nex, r.cols, &dc);
+        HIP_TRY(r.mem.alloc(r.rings, 2 * (size_t)std::max<int64_t>(n, 1)));
+        HIP_TRY(r.mem.alloc(r.counts, (size_t)N));
+        HIP_TRY(r.mem.alloc(r.cursor, (size_t)N));
+        if (int rc = bfgx_disc_rings_device(r.plan, &dc, r.rings)) return rc;
+        if (int rc = bfgx_route_count_device(r.plan, n, r.rings, N, ring_bounds.data(), r.counts)) return rc;
     }
     std::vector<std::vector<int32_t>> cnt(N, std::vector<int32_t>(N, 0));          // cnt[i][j]: halos of shard i bound for rank j
     for (int d = 0; d < N; ++d) {
@@ -175,11 +177,10 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         HIP_TRY(hipSetDevice(r.device));
         r.start.assign(N + 1, 0);
         for (int j = 0; j < N; ++j) r.start[j + 1] = r.start[j] + cnt[d][j];
-        HIP_TRY(hipMalloc(&r.rows, sizeof(double) * (size_t)std::max<int64_t>(r.start[N] * ncol, 1)));
+        HIP_TRY(r.mem.alloc(r.rows, (size_t)std::max<int64_t>(r.start[N] * ncol, 1)));
         const double *cp[kCatCols];
-        for (int q = 0; q < ncol; ++q) cp[q] = (const double *)r.cols[colidx[q]];
-        if (int rc = bfgx_route_fill_device(r.plan, r.n1 - r.n0, (const int32_t *)r.rings, N, ring_bounds.data(), r.start.data(), ncol, cp,
-                                            (int32_t *)r.cursor, (double *)r.rows)) return rc;
+        for (int q = 0; q < ncol; ++q) cp[q] = r.cols[colidx[q]];
+        if (int rc = bfgx_route_fill_device(r.plan, r.n1 - r.n0, r.rings, N, ring_bounds.data(), r.start.data(), ncol, cp, r.cursor, r.rows)) return rc;
         HIP_TRY(hipEventRecord(r.packed, r.stream));
     }
     // ---- phase 3: pull the rows bound for this rank over xGMI, K0 + K1 / K3 for the rank's own tiles
@@ -195,23 +196,23 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         r.plan = nullptr;
         if (int rc = bfgx_plan_create(r.device, r.stream, nside, std::max<int64_t>(r.nrecv, 1), model, &r.plan)) return rc;
         r.plan->blocking_growth = true;
-        HIP_TRY(hipMalloc(&r.recv, sizeof(double) * (size_t)std::max<int64_t>(r.nrecv * ncol, 1)));
-        HIP_TRY(hipMalloc(&r.rcols, sizeof(double) * (size_t)std::max<int64_t>(r.nrecv * ncol, 1)));
+        HIP_TRY(r.mem.alloc(r.recv, (size_t)std::max<int64_t>(r.nrecv * ncol, 1)));
+        HIP_TRY(r.mem.alloc(r.rcols, (size_t)std::max<int64_t>(r.nrecv * ncol, 1)));
         int64_t at = 0;
         for (int i = 0; i < N; ++i) {
             HIP_TRY(hipStreamWaitEvent(r.stream, R[i].packed, 0));
-            if (int rc = copy_between((double *)r.recv + at * ncol, r.device, (const double *)R[i].rows + R[i].start[d] * ncol, R[i].device,
+            if (int rc = copy_between(r.recv + at * ncol, r.device, R[i].rows + R[i].start[d] * ncol, R[i].device,
                                       sizeof(double) * (size_t)cnt[i][d] * ncol, r.stream)) return rc;
             at += cnt[i][d];
         }
         if (r.nrecv > 0) {
             const unsigned grid = (unsigned)std::min<int64_t>((r.nrecv * ncol + 255) / 256, 4096);
-            hipLaunchKernelGGL(rows_to_cols_kernel, dim3(grid), dim3(256), 0, r.stream, r.nrecv, ncol, (const double *)r.recv, (double *)r.rcols);
+            hipLaunchKernelGGL(rows_to_cols_kernel, dim3(grid), dim3(256), 0, r.stream, r.nrecv, ncol, (const double *)r.recv, r.rcols);
             HIP_TRY(hipGetLastError());
         }
         bfgx_catalog dc;
         const double *colp[kCatCols] = {};
-        for (int q = 0; q < ncol; ++q) colp[colidx[q]] = (const double *)r.rcols + (int64_t)q * r.nrecv;
+        for (int q = 0; q < ncol; ++q) colp[colidx[q]] = r.rcols + (int64_t)q * r.nrecv;
         catalog_view(r.nrecv, nex, colp, &dc);
         // the slice is computed in place inside a buffer that also has room for the widest apron (16 rings either side)
         r.flo = r.p0; r.fhi = r.p1;
@@ -220,15 +221,15 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
             if (int rc = bfgx_plan_band_apron(r.plan, r.b0, r.b1, &r.flo, &r.fhi)) return rc;
         }
         const int64_t nown = r.p1 - r.p0;
-        HIP_TRY(hipMalloc(&r.full, (size_t)std::max<int64_t>((r.fhi - r.flo) * width, 1) * esz));
-        HIP_TRY(hipMalloc(&r.omax, sizeof(float)));
+        HIP_TRY(r.mem.alloc(r.full, (size_t)std::max<int64_t>((r.fhi - r.flo) * width, 1) * esz));
+        HIP_TRY(r.mem.alloc(r.omax, 1));
         HIP_TRY(hipMemsetAsync(r.omax, 0, sizeof(float), r.stream));
-        void *slice = (char *)r.full + (size_t)(r.p0 - r.flo) * width * esz;
+        void *slice = r.full + (size_t)(r.p0 - r.flo) * width * esz;
         if (nown > 0) {
             if (paint) { if (int rc = bfgx_paint_bands_device(r.plan, &dc, r.b0, r.b1, slice, 1)) return rc; }
             else {
                 if (int rc = bfgx_offsets_bands_device(r.plan, &dc, r.b0, r.b1, slice, dm.acc())) return rc;
-                if (int rc = bfgx_bands_max_offset2_device(r.plan, r.b0, r.b1, (float *)r.omax)) return rc;
+                if (int rc = bfgx_bands_max_offset2_device(r.plan, r.b0, r.b1, r.omax)) return rc;
             }
         }
         HIP_TRY(hipEventRecord(r.done, r.stream));
@@ -252,8 +253,8 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
         if (int rc = bfgx_plan_reach_rings(r.plan, std::sqrt((double)omax2), &rings)) return rc;
         if (int rc = bfgx_plan_set_band_reach(r.plan, rings)) return rc;
         if (int rc = bfgx_plan_band_apron(r.plan, r.b0, r.b1, &r.olo, &r.ohi)) return rc;
-        HIP_TRY(hipMalloc(&r.out, sizeof(double) * (size_t)std::max<int64_t>(nown, 1)));
-        HIP_TRY(hipMalloc(&r.sums, 2 * sizeof(double)));
+        HIP_TRY(r.mem.alloc(r.out, (size_t)std::max<int64_t>(nown, 1)));
+        HIP_TRY(r.mem.alloc(r.sums, 2));
         HIP_TRY(hipMemsetAsync(r.sums, 0, 2 * sizeof(double), r.stream));
         if (nown <= 0) continue;
         // the apron rings [olo, p0) and [p1, ohi) from whichever ranks own them (complete there: nothing is summed)
@@ -262,15 +263,15 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
             const int64_t a0 = std::max(r.olo, R[s].p0), a1 = std::min(r.ohi, R[s].p1);
             if (a1 <= a0) continue;
             HIP_TRY(hipStreamWaitEvent(r.stream, R[s].done, 0));
-            if (int rc = copy_between((char *)r.full + (size_t)(a0 - r.flo) * width * esz, r.device,
-                                      (const char *)R[s].full + (size_t)(a0 - R[s].flo) * width * esz, R[s].device, (size_t)(a1 - a0) * width * esz,
+            if (int rc = copy_between(r.full + (size_t)(a0 - r.flo) * width * esz, r.device,
+                                      R[s].full + (size_t)(a0 - R[s].flo) * width * esz, R[s].device, (size_t)(a1 - a0) * width * esz,
                                       r.stream)) return rc;
         }
-        HIP_TRY(hipMalloc(&r.map, sizeof(double) * (size_t)(r.ohi - r.olo)));
+        HIP_TRY(r.mem.alloc(r.map, (size_t)(r.ohi - r.olo)));
         HIP_TRY(hipMemcpyAsync(r.map, map_in + r.olo, sizeof(double) * (size_t)(r.ohi - r.olo), hipMemcpyHostToDevice, r.stream));
         // the kernel indexes the map by global pixel number: virtual base
-        if (int rc = bfgx_regrid_bands_device(r.plan, r.b0, r.b1, (const double *)r.map - r.olo, (const char *)r.full + (size_t)(r.olo - r.flo) * width * esz,
-                                              r.olo, r.ohi, dm.acc(), (double *)r.out, (double *)r.sums)) return rc;
+        if (int rc = bfgx_regrid_bands_device(r.plan, r.b0, r.b1, (const double *)r.map - r.olo, r.full + (size_t)(r.olo - r.flo) * width * esz,
+                                              r.olo, r.ohi, dm.acc(), r.out, r.sums)) return rc;
         HIP_TRY(hipMemcpyAsync(map_out + r.p0, r.out, sizeof(double) * (size_t)nown, hipMemcpyDeviceToHost, r.stream));
     }
     // ---- join: the slices are disjoint; far deposits (global pixel numbers, almost always none) are added on the host

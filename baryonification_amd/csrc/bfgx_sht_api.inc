@@ -281,7 +281,7 @@ int bfgx_sht_map2alm(int device, int32_t nside, int32_t lmax, int32_t mmax, int3
     if (int rc = tables_begin(device)) return rc;
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr dw, dm, da;
+    DevBuf dw, dm, da;
     if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(map, sizeof(double) * L.npix) || da.up(nullptr, sizeof(double2) * na))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
     if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
@@ -297,7 +297,7 @@ int bfgx_sht_alm2map(int device, int32_t nside, int32_t lmax, int32_t mmax, cons
     if (int rc = tables_begin(device)) return rc;
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr dw, dm, da;
+    DevBuf dw, dm, da;
     if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(nullptr, sizeof(double) * L.npix) || da.up(alm, sizeof(double2) * na))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
     if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
@@ -312,7 +312,7 @@ int bfgx_sht_alm2cl(int device, int32_t lmax, int32_t mmax, int32_t lmax_out, co
     if (lmax < 0 || mmax < 0 || mmax > lmax || lmax_out < 0) return fail(BFGX_ERR_INVALID, "alm2cl needs 0 <= mmax <= lmax, lmax_out >= 0");
     if (int rc = tables_begin(device)) return rc;
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr d1, d2, dc;
+    DevBuf d1, d2, dc;
     if (d1.up(alm1, sizeof(double2) * na) || (alm2 && d2.up(alm2, sizeof(double2) * na)) || dc.up(nullptr, sizeof(double) * (lmax_out + 1)))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
     if (int rc = bfgx_sht_alm2cl_device(device, nullptr, lmax, mmax, lmax_out, d1.as<double>(), alm2 ? d2.as<double>() : nullptr, dc.as<double>()))
@@ -331,7 +331,7 @@ int bfgx_sht_anafast(int device, int32_t nside, int32_t lmax, int32_t mmax, int3
     if (int rc = tables_begin(device)) return rc;
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr dw, dm, da1, da2, dc;
+    DevBuf dw, dm, da1, da2, dc;
     if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(map1, sizeof(double) * L.npix) || da1.up(nullptr, sizeof(double2) * na) ||
         (map2 && da2.up(nullptr, sizeof(double2) * na)) || dc.up(nullptr, sizeof(double) * (lmax + 1)))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
@@ -385,7 +385,7 @@ int bfgx_sht_map2alm_spin(int device, int32_t nside, int32_t lmax, int32_t mmax,
     if (int rc = tables_begin(device)) return rc;
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr dw, ds, dm, da;
+    DevBuf dw, ds, dm, da;
     if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(maps, sizeof(double) * 2 * L.npix) ||
         da.up(nullptr, sizeof(double2) * 2 * na))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
@@ -405,7 +405,7 @@ int bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax,
     if (int rc = tables_begin(device)) return rc;
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevArr dw, ds, dm, da;
+    DevBuf dw, ds, dm, da;
     if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(nullptr, sizeof(double) * 2 * L.npix) ||
         da.up(alms, sizeof(double2) * 2 * na))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");

@@ -3,17 +3,6 @@
 
 namespace {
 
-struct OwnedList {
-    std::vector<void *> v;
-    ~OwnedList() { for (void *d : v) (void)hipFree(d); }
-    int alloc(size_t bytes, void **out)
-    {
-        if (hipMalloc(out, bytes ? bytes : 8) != hipSuccess) return 1;
-        v.push_back(*out);
-        return 0;
-    }
-};
-
 int snapshot_cells(int ndim)
 {
     int nc = ndim == 3 ? 128 : 1024;
@@ -28,7 +17,7 @@ extern "C" void bfgx_snapshot_plan_destroy(struct bfgx_snapshot_plan *p);
 struct bfgx_snapshot_plan {
     int device = 0;
     hipStream_t stream = nullptr;
-    std::vector<void *> owned;
+    DevList mem;
     DevModel model;
     SnapGeom geom;
     int64_t max_halos = 0, nscan = 0, entry_capacity = 0;
@@ -58,7 +47,7 @@ int bfgx_snapshot_plan_create(int device, void *hip_stream, const bfgx_model *mo
     p->device = device; p->stream = (hipStream_t)hip_stream; p->max_halos = max_halos;
     auto bail = [&](int rc) { bfgx_snapshot_plan_destroy(p); return rc; };
     int NC = 4;
-    if (int rc = upload_model(p->owned, p->stream, model, false, p->model, NC)) return bail(rc);
+    if (int rc = upload_model(p->mem, p->stream, model, false, p->model, NC)) return bail(rc);
     SnapGeom &g = p->geom;
     g.ndim = ndim; g.nc = snapshot_cells(ndim); g.L = L; g.inv_cell = (double)g.nc / L;
     g.a = 1.0 / (1.0 + redshift);
@@ -66,22 +55,12 @@ int bfgx_snapshot_plan_create(int device, void *hip_stream, const bfgx_model *mo
     for (int d = 0; d < ndim; ++d) g.ncell *= g.nc;
     p->nscan = g.ncell + 1;
     p->nblocks = (int)((p->nscan + kScanPerBlock - 1) / kScanPerBlock);
-    auto dalloc = [&](size_t bytes, void **ptr) {
-        if (hipMalloc(ptr, bytes ? bytes : 8) != hipSuccess) return 1;
-        p->owned.push_back(*ptr);
-        return 0;
-    };
-    void *d[10] = {nullptr};
+    DevList &mem = p->mem;
     p->entry_capacity = 16 * max_halos + 65536;
-    if (dalloc(sizeof(SnapHaloRec) * (size_t)std::max<int64_t>(max_halos, 1), &d[0]) || dalloc(sizeof(int32_t) * (size_t)p->nscan, &d[1]) ||
-        dalloc(sizeof(int32_t) * (size_t)p->nscan, &d[2]) || dalloc(sizeof(int32_t) * (size_t)p->nscan, &d[3]) ||
-        dalloc(sizeof(int32_t) * (size_t)p->nblocks, &d[4]) || dalloc(sizeof(int64_t), &d[5]) || dalloc(sizeof(int32_t), &d[6]) ||
-        dalloc(sizeof(unsigned long long), &d[7]) || dalloc(sizeof(uint32_t) * (size_t)((g.ncell + 31) / 32), &d[8]) ||
-        dalloc(sizeof(SnapEntry) * (size_t)p->entry_capacity, &d[9]))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(snapshot workspace) failed"));
-    p->recs = (SnapHaloRec *)d[0]; p->count = (int32_t *)d[1]; p->start = (int32_t *)d[2]; p->cursor = (int32_t *)d[3];
-    p->bsum = (int32_t *)d[4]; p->total = (int64_t *)d[5]; p->flags = (int32_t *)d[6]; p->pairs = (unsigned long long *)d[7];
-    p->bitmap = (uint32_t *)d[8]; p->entries = (SnapEntry *)d[9];
+    if (mem.alloc(p->recs, (size_t)std::max<int64_t>(max_halos, 1)) || mem.alloc(p->count, (size_t)p->nscan) || mem.alloc(p->start, (size_t)p->nscan) ||
+        mem.alloc(p->cursor, (size_t)p->nscan) || mem.alloc(p->bsum, (size_t)p->nblocks) || mem.alloc(p->total, 1) || mem.alloc(p->flags, 1) ||
+        mem.alloc(p->pairs, 1) || mem.alloc(p->bitmap, (size_t)((g.ncell + 31) / 32)) || mem.alloc(p->entries, (size_t)p->entry_capacity))
+        return bail(alloc_fail("snapshot workspace"));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) p->n_cu = prop.multiProcessorCount;
     *out = p;
@@ -93,7 +72,7 @@ void bfgx_snapshot_plan_destroy(bfgx_snapshot_plan *p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)hipStreamSynchronize(p->stream);
-    for (void *d : p->owned) (void)hipFree(d);
+    p->mem.release();
     delete p;
 }
 
@@ -130,11 +109,8 @@ static int snap_lists_stage(bfgx_snapshot_plan *p, const bfgx_grid_catalog *halo
     HIP_TRY(hipStreamSynchronize(s));
     if (total > (int64_t)INT32_MAX) return fail(BFGX_ERR_INVALID, "halo-cell lists exceed 2^31 entries: use fewer cells (BFGX_SNAP_CELLS) or split the catalog");
     if (total > p->entry_capacity) {             // grow the list storage (rare: very large query balls)
-        void *d = nullptr;
         const int64_t cap = total + total / 4 + 1024;
-        HIP_TRY(hipMalloc(&d, sizeof(SnapEntry) * (size_t)cap));
-        for (auto &o : p->owned) if (o == (void *)p->entries) { (void)hipFree(o); o = d; }
-        p->entries = (SnapEntry *)d;
+        HIP_TRY(p->mem.regrow(p->entries, (size_t)cap));
         p->entry_capacity = cap;
     }
     if (halos->n > 0 && total > 0) {
@@ -247,7 +223,7 @@ int bfgx_baryonify_snapshot(const bfgx_grid_catalog *halos, const bfgx_model *mo
     Timer t;
     t.start(nullptr);
     if (int rc = hc.upload(halos, snap->ndim, 0, nullptr)) return rc;
-    DevArr dx, dy, dz, ox, oy, oz;
+    DevBuf dx, dy, dz, ox, oy, oz;
     const size_t nb = sizeof(double) * (size_t)snap->n;
     if (dx.up(snap->x, nb) || dy.up(snap->y, nb) || (snap->ndim == 3 && dz.up(snap->z, nb)) || ox.up(nullptr, nb) || oy.up(nullptr, nb) ||
         (snap->ndim == 3 && oz.up(nullptr, nb)))
@@ -292,7 +268,7 @@ int snap_acquire(int device, const bfgx_model *model, int32_t ndim, double L, do
     const int ncells = snapshot_cells(ndim);                 // (BFGX_SNAP_CELLS: a plan is built for one cell grid)
     key.add(ndim); key.add(L); key.add(redshift); key.add(ncells);
     auto make = [&](int64_t cap, bfgx_snapshot_plan **p) { return bfgx_snapshot_plan_create(device, nullptr, model, ndim, L, redshift, cap, p); };
-    auto setup = [&](RecordsEntry *e) -> int { return e->rec.need(bytes, 8, 0) ? fail(BFGX_ERR_HIP, "hipMalloc(particle records) failed") : BFGX_OK; };
+    auto setup = [&](RecordsEntry *e) -> int { return e->rec.need(bytes, 8, 0) ? alloc_fail("particle records") : BFGX_OK; };
     return g_snaps.acquire(key, device, nhalo, make, setup, out);
 }
 
@@ -400,7 +376,7 @@ int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bf
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
-    if (b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return fail(BFGX_ERR_HIP, "hipMalloc(map) failed");
+    if (b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return alloc_fail("map");
     hipStream_t s = p->stream;
     DrainOnExit drain;
     drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.null_stream = (p->stream == nullptr);

@@ -69,7 +69,7 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
     if (hipStreamCreateWithFlags(&h->sstream, hipStreamNonBlocking) != hipSuccess) { h->sstream = nullptr; return bail(fail(BFGX_ERR_HIP, "hipStreamCreate failed")); }
     hipStream_t st = h->sstream;
     int NC = 4;
-    if (int rc = upload_model(h->sowned, st, model, false, h->smodel, NC)) return bail(rc);
+    if (int rc = upload_model(h->smem, st, model, false, h->smodel, NC)) return bail(rc);
     const int64_t nh = c->n, np = s->n;
     h->n = nh; h->snp = np;
     SnapGeom &g = h->sg;
@@ -80,25 +80,25 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
     DevBuf hcol[4];
     const double *hsrc[4] = {c->M, c->x, c->y, s->ndim == 3 ? c->z : nullptr};
     for (int k = 0; k < 4; ++k) {
-        if (hcol[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(nh, 1))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(catalog) failed"));
+        if (hcol[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(nh, 1))) return bail(alloc_fail("catalog"));
         if (nh > 0 && hsrc[k] && hipMemcpyAsync(hcol[k].p, hsrc[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, st) != hipSuccess)
             return bail(fail(BFGX_ERR_HIP, "copy(catalog) failed"));
     }
     const double *psrc[3] = {s->x, s->y, s->ndim == 3 ? s->z : nullptr};
     for (int k = 0; k < 3; ++k) {
-        if (h->sxyz[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(np, 1))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(particles) failed"));
+        if (h->sxyz[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(np, 1))) return bail(alloc_fail("particles"));
         if (np > 0 && psrc[k] && hipMemcpyAsync(h->sxyz[k].p, psrc[k], sizeof(double) * (size_t)np, hipMemcpyHostToDevice, st) != hipSuccess)
             return bail(fail(BFGX_ERR_HIP, "copy(particles) failed"));
     }
     if (h->srecs.alloc(sizeof(SnapHaloRec) * (size_t)std::max<int64_t>(nh, 1)) || h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nh, 1)) ||
         h->off.alloc(sizeof(int64_t) * ((size_t)nh + 1)) || h->sacc.alloc(3 * sizeof(double) * (size_t)std::max<int64_t>(np, 1)))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(halo records) failed"));
+        return bail(alloc_fail("halo records"));
     // particle binning: per-cell counts -> exclusive scan -> stable radix sort of (cell, index): a cell's particles in ascending index
     DevBuf cell[2], idx[2], ccount, cstart, flags, tmp;
     const size_t npb = (size_t)std::max<int64_t>(np, 1);
     if (cell[0].alloc(4 * npb) || cell[1].alloc(4 * npb) || idx[0].alloc(4 * npb) || idx[1].alloc(4 * npb) ||
         ccount.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || cstart.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || flags.alloc(sizeof(int32_t)))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(particle bins) failed"));
+        return bail(alloc_fail("particle bins"));
     HIP_TRY(hipMemsetAsync(ccount.p, 0, sizeof(int32_t) * ((size_t)g.ncell + 1), st));
     HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(h->sacc.p, 0, 3 * sizeof(double) * npb, st));
@@ -123,7 +123,7 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
         while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)g.ncell) ++end_bit;
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, kb, vb, (int)np, 0, end_bit, st));
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t *)ccount.p, (int32_t *)cstart.p, (int)g.ncell + 1, st));
-        if (tmp.alloc(std::max(b1, b2))) return bail(fail(BFGX_ERR_HIP, "hipMalloc(sort workspace) failed"));
+        if (tmp.alloc(std::max(b1, b2))) return bail(alloc_fail("sort workspace"));
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, b1, kb, vb, (int)np, 0, end_bit, st));
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, b2, (const int32_t *)ccount.p, (int32_t *)cstart.p, (int)g.ncell + 1, st));
         sorted_idx = vb.Current();
@@ -154,7 +154,7 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
     const size_t nt = (size_t)std::max<int64_t>(h->total, 1);
     DevBuf cursor, keys2;
     if (h->skeys.alloc(sizeof(uint64_t) * nt) || keys2.alloc(sizeof(uint64_t) * nt) || cursor.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nh, 1)))
-        return bail(fail(BFGX_ERR_HIP, "hipMalloc(pair keys) failed"));
+        return bail(alloc_fail("pair keys"));
     HIP_TRY(hipMemcpyAsync(h->off.p, h->off_h.data(), sizeof(int64_t) * ((size_t)nh + 1), hipMemcpyHostToDevice, st));
     if (h->total > 0) {
         HIP_TRY(hipMemsetAsync(cursor.p, 0, sizeof(int64_t) * (size_t)nh, st));
@@ -171,7 +171,7 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
         hipcub::DoubleBuffer<uint64_t> pk((uint64_t *)h->skeys.p, (uint64_t *)keys2.p);
         HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b3, pk, (int)h->total, 0, 64, st));
         DevBuf tmp2;
-        if (tmp2.alloc(b3)) return bail(fail(BFGX_ERR_HIP, "hipMalloc(sort workspace) failed"));
+        if (tmp2.alloc(b3)) return bail(alloc_fail("sort workspace"));
         HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp2.p, b3, pk, (int)h->total, 0, 64, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (pk.Current() != (uint64_t *)h->skeys.p) std::swap(h->skeys.p, keys2.p);
@@ -188,7 +188,7 @@ int bfgx_snapshot_pairs_radii(bfgx_pairs *h, int64_t j0, int64_t j1, double *r_h
     if (np > 0 && !r_host) return fail(BFGX_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->sdev));
     if (np > 0) {
-        if (h->batch.need(sizeof(double) * (size_t)np)) return fail(BFGX_ERR_HIP, "hipMalloc(pair batch) failed");
+        if (h->batch.need(sizeof(double) * (size_t)np)) return alloc_fail("pair batch");
         if (int rc = launch_snap_pairs<0>(h, j0, j1, nullptr, (double *)h->batch.p)) return rc;
         HIP_TRY(hipMemcpyAsync(r_host, h->batch.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, h->sstream));
     }
@@ -203,7 +203,7 @@ int bfgx_snapshot_pairs_apply(bfgx_pairs *h, int64_t j0, int64_t j1, const doubl
     if (np > 0 && !vals_host) return fail(BFGX_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->sdev));
     if (np > 0) {
-        if (h->batch.need(sizeof(double) * (size_t)np)) return fail(BFGX_ERR_HIP, "hipMalloc(pair batch) failed");
+        if (h->batch.need(sizeof(double) * (size_t)np)) return alloc_fail("pair batch");
         HIP_TRY(hipMemcpyAsync(h->batch.p, vals_host, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, h->sstream));
         if (int rc = launch_snap_pairs<1>(h, j0, j1, (const double *)h->batch.p, (double *)h->sacc.p)) return rc;
     }
@@ -220,7 +220,7 @@ int bfgx_snapshot_pairs_finish(bfgx_pairs *h, double *x_out, double *y_out, doub
     if (np > 0) {
         DevBuf o[3];
         for (int k = 0; k < h->sg.ndim; ++k)
-            if (o[k].alloc(sizeof(double) * (size_t)np)) return fail(BFGX_ERR_HIP, "hipMalloc(positions) failed");
+            if (o[k].alloc(sizeof(double) * (size_t)np)) return alloc_fail("positions");
         hipLaunchKernelGGL(snap_pairs_finish_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, h->sg, np, (const double *)h->sacc.p,
                            (const double *)h->sxyz[0].p, (const double *)h->sxyz[1].p, (const double *)h->sxyz[2].p, (double *)o[0].p, (double *)o[1].p,
                            (double *)o[2].p);
