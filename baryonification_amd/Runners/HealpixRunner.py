@@ -15,9 +15,9 @@ from .. import _lib
 from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
 from ..utils.pixelfunc import scatter_add
-from ._model import build_model, process_callable_exact, wants_exact
+from ._model import _placeholder_model, build_model, cosmo_to_dict, process_callable_exact, wants_exact
 
-__all__ = ['DefaultRunner', 'BaryonifyShell', 'PaintProfilesShell', 'regrid_pixels_hpix']
+__all__ = ['DefaultRunner', 'BaryonifyShell', 'PaintProfilesShell', 'MeasureProfilesShell', 'regrid_pixels_hpix']
 
 
 def regrid_pixels_hpix(hmap, parent_pix_vals, child_pix, child_weights):
@@ -207,3 +207,138 @@ class PaintProfilesShell(DefaultRunner):
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep
         return new_map
+
+
+MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
+
+
+def _is_cuda_tensor(x):
+    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
+
+
+class ShellProfiles(object):
+    """What MeasureProfilesShell.process() returns: per (halo, bin) the counted pixels and the sums, shape (n_halo, nb); the shear fields
+    are None without a shear pair.  numpy arrays, or torch tensors on the maps' device when the maps were CUDA tensors."""
+
+    def __init__(self, r_edges, npix, sum, npix_shear=None, sum_t=None, sum_x=None, scaled=False):
+        self.r_edges, self.scaled = r_edges, scaled
+        self.npix, self.sum = npix, sum
+        self.npix_shear, self.sum_t, self.sum_x = npix_shear, sum_t, sum_x
+
+    @staticmethod
+    def _ratio(s, n):
+        if isinstance(s, np.ndarray):
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return np.where(n > 0, s / n, np.nan)
+        return (s / n).masked_fill(n == 0, float('nan'))
+
+    @property
+    def mean(self):
+        """sum / npix, NaN where npix is 0"""
+        return self._ratio(self.sum, self.npix)
+
+    @property
+    def mean_t(self):
+        return None if self.sum_t is None else self._ratio(self.sum_t, self.npix_shear)
+
+    @property
+    def mean_x(self):
+        return None if self.sum_x is None else self._ratio(self.sum_x, self.npix_shear)
+
+    def stack(self, select=None, weights=None):
+        """The pixel-weighted mean profile over the chosen halos, sum_j w_j sum[j] / sum_j w_j npix[j] per bin (NaN where the denominator
+        is 0): a dict with 'mean' and, with shear, 'mean_t' and 'mean_x'.  select: anything that indexes the halo axis; weights: one per
+        chosen halo (default 1)."""
+        sel = slice(None) if select is None else select
+        out = {}
+        for name, s, n in (('mean', self.sum, self.npix), ('mean_t', self.sum_t, self.npix_shear), ('mean_x', self.sum_x, self.npix_shear)):
+            if s is None:
+                continue
+            s, n = s[sel], n[sel].to(s.dtype) if not isinstance(n, np.ndarray) else n[sel].astype(np.float64)
+            if weights is not None:
+                w = weights if not isinstance(s, np.ndarray) else np.asarray(weights, dtype=np.float64)
+                s, n = s * w[:, None], n * w[:, None]
+            out[name] = self._ratio(s.sum(0), n.sum(0))
+        return out
+
+
+class MeasureProfilesShell(DefaultRunner):
+    """Measures halo-centred radial profiles of a shell map: the adjoint of PaintProfilesShell (same discs, same separations, a gather
+    where painting scatters).  For halo j the pixels of query_disc(NSIDE, vec_j, R_j epsilon_max / D_j) are binned in r_sep / a_j
+    (comoving Mpc, what the profile models are called with) or, scaled=True, in r_sep / R_j: bin b holds r_edges[b] <= x < r_edges[b + 1].
+    LightconeShell.map is the scalar map (y, kappa, density contrast); shear=(g1, g2) adds a spin-2 pair in the convention of
+    utils.sphtfunc (HEALPix: components on e_theta, e_phi) whose tangential and cross components about the halo,
+    gamma_t + i gamma_x = -(g1 + i g2) exp(-2 i phi), are summed too: a mass peak has gamma_t > 0, a pure E field gamma_x = 0.
+    Pixels that are not finite or UNSEEN are not counted.  fp64 throughout.  `model` must be None: there is nothing to tabulate."""
+
+    def __init__(self, HaloLightConeCatalog, LightconeShell, epsilon_max, model=None, use_ellipticity=False,
+                 mass_def=MassDef(200, 'critical'), verbose=True, *, r_edges, scaled=False, shear=None):
+        if model is not None:
+            raise TypeError("MeasureProfilesShell takes model=None: it measures the map, there is nothing to tabulate")
+        super().__init__(HaloLightConeCatalog, LightconeShell, epsilon_max, model, use_ellipticity, mass_def, verbose)
+        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 2:
+            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
+        if edges.size - 1 > MAX_PROFILE_BINS:
+            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
+        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
+        self.r_edges = edges
+        self.scaled = bool(scaled)
+        self.shear = self._shear_pair(shear, int(LightconeShell.NSIDE))
+
+    @staticmethod
+    def _shear_pair(shear, nside):
+        if shear is None:
+            return None
+        if len(shear) != 2:
+            raise ValueError("shear must be a pair of maps (g1, g2)")
+        for g in shear:
+            n = g.numel() if _is_cuda_tensor(g) else np.asarray(g).size
+            if n != 12 * nside * nside:
+                raise ValueError("shear maps must have the NSIDE of the shell (%d): got %d pixels" % (nside, n))
+        return tuple(shear)
+
+    def process(self, map=None, shear=None):
+        """ShellProfiles of the shell's map (and the constructor's shear pair), or of `map` / `shear` given here.  CUDA float64 torch tensors
+        given here are measured where they lie and the result arrays are tensors on that device."""
+        nside = int(self.LightconeShell.NSIDE)
+        m = self.LightconeShell.map if map is None else map
+        pair = self.shear if shear is None else self._shear_pair(shear, nside)
+        maps = [m] + list(pair or ())
+        on_dev = [_is_cuda_tensor(x) for x in maps]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("the map and the shear pair must all be numpy arrays or all CUDA tensors")
+        model, keep = _placeholder_model(self, cosmo_to_dict(self.cosmo))
+        edges, nb = self.r_edges, self.r_edges.size - 1
+        n = int(self.HaloLightConeCatalog.cat.size)
+        lib = _lib.load()
+        if all(on_dev):
+            import torch
+            dev = maps[0].device
+            for x in maps:
+                if x.dtype != torch.float64 or x.dim() != 1 or x.numel() != 12 * nside * nside or x.device != dev:
+                    raise ValueError("device maps must be 1-D float64 tensors of 12 NSIDE^2 pixels on one device")
+            maps = [x.contiguous() for x in maps]
+            outs = [torch.empty((n, nb), dtype=(torch.int64 if i in (0, 2) else torch.float64), device=dev) for i in range(5 if pair else 2)]
+            ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
+            optr = [C.c_void_p(o.data_ptr()) for o in outs] + [None] * (5 - len(outs))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
+
+            def call(cat):
+                _lib.check(lib.bfgx_shell_profiles_device(dev.index or 0, stream, C.byref(cat), C.byref(model), nside, ptr[0], ptr[1], ptr[2], nb,
+                                                          edges.ctypes.data, int(self.scaled), *optr))
+        else:
+            maps = [_lib.f8(x).reshape(-1) for x in maps]
+            if maps[0].size != 12 * nside * nside:
+                raise ValueError("the map must have 12 NSIDE^2 = %d pixels" % (12 * nside * nside))
+            outs = [np.zeros((n, nb), dtype=(np.int64 if i in (0, 2) else np.float64)) for i in range(5 if pair else 2)]
+            ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
+            optr = [o.ctypes.data for o in outs] + [None] * (5 - len(outs))
+
+            def call(cat):
+                _lib.check(lib.bfgx_shell_profiles(C.byref(cat), C.byref(model), nside, ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,
+                                                   int(self.scaled), int(self.device), *optr))
+        self._call_with_catalog([], call)
+        del keep
+        return ShellProfiles(edges.copy(), *outs, scaled=self.scaled)

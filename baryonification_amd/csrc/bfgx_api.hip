@@ -42,6 +42,7 @@ static std::atomic<long long> g_host_pinned_in_place{0}, g_host_staged{0}, g_hos
 #include "bfgx_fftlog.hpp"
 #include "bfgx_sht.hpp"
 #include "bfgx_hpx.hpp"
+#include "bfgx_stack.hpp"
 
 using namespace bfgx;
 
@@ -2369,6 +2370,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // HEALPix pixel functions (ud_grade / get_interp_weights / get_interp_val / regrid_pixels_hpix)
 #include "bfgx_hpx_api.inc"
+
+// halo-centred radial profiles of shell maps (MeasureProfilesShell)
+#include "bfgx_stack_api.inc"
 
 extern "C" void bfgx_cache_clear(void)
 {

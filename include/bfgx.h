@@ -687,6 +687,29 @@ int  bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, dou
 int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n, const double *vals_host, const int64_t *pix_host,
                           const double *w_host);
 
+/* ---- halo-centred radial profiles of shell maps (MeasureProfilesShell) ------------------------------
+ * The adjoint of PaintProfilesShell: for halo j the pixels of query_disc(nside, vec_j, R_j epsilon_max / D_j) (RING, no < 4-pixel fallback) at
+ * separation r_sep = D_j |vec_pix - vec_j| (HealpixRunner.py:418-438) are binned in x = r_sep / a_j (comoving Mpc, :441) or, scaled != 0,
+ * x = r_sep / R_j: pixel in bin b iff r_edges[b] <= x < r_edges[b + 1]; nb + 1 finite ascending edges >= 0, 1 <= nb <= 64.  A pixel counts
+ * if its value is finite and not UNSEEN (healpy's mask_bad rule); for the shear pair both maps must pass.  Outputs, [n][nb] each:
+ *   npix, sum                  counted pixels and the sum of map[pix]
+ *   npix_shear, sum_t, sum_x   (g1 != NULL) gamma_t + i gamma_x = -(g1 + i g2) e^{-2 i phi}, (g1, g2) on (e_theta, e_phi) as map2alm_spin takes
+ *                              them, phi the position angle of the direction towards the halo at the pixel; a pixel the halo sits on is left out
+ * Invalid halos (disc radius not positive / finite, colatitude outside [0, pi], M not positive / finite, z <= -1) and empty discs give
+ * all-zero rows.  `model` carries the runner's cosmology / mass definition / epsilon_max; its 3-axis table must be valid and is ignored.
+ * fp64 throughout; every cell is written once (no atomics on the outputs).  The plan behind both entries is cached: a second call with the
+ * same (device, nside, model) allocates nothing.
+ *   bfgx_shell_profiles          catalog, maps, edges and outputs in host memory: upload + kernels + download
+ *   bfgx_shell_profiles_device   maps and outputs are device pointers, the kernels run on hip_stream; catalog columns and r_edges are host
+ *                                arrays (copied before the call returns); no host synchronisation of its own */
+int  bfgx_shell_profiles(const bfgx_catalog *cat_host, const bfgx_model *model, int64_t nside, const double *map_host, const double *g1_host,
+                         const double *g2_host, int32_t nb, const double *r_edges, int32_t scaled, int32_t device, int64_t *npix_host,
+                         double *sum_host, int64_t *npix_shear_host, double *sum_t_host, double *sum_x_host);
+int  bfgx_shell_profiles_device(int32_t device, void *hip_stream, const bfgx_catalog *cat_host, const bfgx_model *model, int64_t nside,
+                                const double *map_dev, const double *g1_dev, const double *g2_dev, int32_t nb, const double *r_edges,
+                                int32_t scaled, int64_t *npix_dev, double *sum_dev, int64_t *npix_shear_dev, double *sum_t_dev,
+                                double *sum_x_dev);
+
 #ifdef __cplusplus
 }
 #endif
