@@ -165,9 +165,25 @@ __host__ __device__ inline size_t tile2_lds_bytes(int BR, int W, int ncomp)
 }
 
 // atan(t) for 0 <= t <= 7/16: fdlibm's kernel polynomial (s_atan.c, no argument reduction needed below 7/16), < 1 ulp
+// CMEM: the coefficients are read from constant memory (scalar loads) where they are used.  As literals the compiler keeps all twelve in vector
+// registers from the top of the kernel, across the pair loop; the parity-grade kernel, whose rotated pair loop holds the state of two pairs, has
+// no room for that (it spilled them to scratch).
+__constant__ double kAtanS1[6] = {1.62858201153657823623e-02, 4.97687799461593236017e-02, 6.66107313738753120669e-02,
+                                  9.09088713343650656196e-02, 1.42857142725034663711e-01, 3.33333333333329318027e-01};
+__constant__ double kAtanS2[5] = {-3.65315727442169155270e-02, -5.83357013379057348645e-02, -7.69187620504482999495e-02,
+                                  -1.11111104054623557880e-01, -1.99999999998764832476e-01};
+template <bool CMEM = false>
 __device__ inline double atan_lt_7_16(double t)
 {
     const double z = t * t, w = z * z;
+    if (CMEM) {
+        double s1 = kAtanS1[0], s2 = kAtanS2[0];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) s1 = __builtin_fma(s1, w, kAtanS1[k]);
+#pragma unroll
+        for (int k = 1; k < 5; ++k) s2 = __builtin_fma(s2, w, kAtanS2[k]);
+        return __builtin_fma(-t, __builtin_fma(z, s1, w * s2), t);
+    }
     double s1 = 1.62858201153657823623e-02;
     s1 = __builtin_fma(s1, w, 4.97687799461593236017e-02);
     s1 = __builtin_fma(s1, w, 6.66107313738753120669e-02);
@@ -187,6 +203,7 @@ __device__ inline double atan_lt_7_16(double t)
 // the half-width dphi = atan2(sqrt(ysq), x) of a narrow disc (0 < dphi <= 0.4, so x > 0 and sqrt(ysq) / x <= tan 0.4 < 7/16)
 // comes from an rsq seed + Newton and the fdlibm polynomial instead of libm's sqrt and atan2 (a few ulp either way: the
 // span changes only where fnr (phi0 +- dphi) lies within ~1e-13 of a pixel boundary).  Ring lengths are below 2^31.
+template <bool CMEM = false>
 __device__ inline void disc_row_span_narrow(int nr, bool shifted, double z, double fnr, double z0, double xa, double cosr,
                                             double phi0, int &lo, int &cnt)
 {
@@ -195,7 +212,7 @@ __device__ inline void disc_row_span_narrow(int nr, bool shifted, double z, doub
     const double ysq = 1.0 - z * z - x * x;
     if (!(ysq > 0.0) || !(x > 0.0)) return;
     const double t = ysq * fast_rsq(ysq) * fast_rcp(x);              // sqrt(ysq) / x
-    const double dphi = atan_lt_7_16(t);
+    const double dphi = atan_lt_7_16<CMEM>(t);
     if (!(dphi > 0.0)) return;
     const double sh = shifted ? 0.5 : 0.0;
     const int ip_lo = (int)floor(fnr * (phi0 - dphi) - sh) + 1;
@@ -253,11 +270,99 @@ struct PairEval {
     bool ok, ok_nocut, amb;       // contributes; the same without the model-side cut; fp32 cannot decide the cut
 };
 
+// The parity-grade pair (PM = 1: fp64 data path, PMathE) in two pieces cut at the table load, so that the pair loop can keep the gather of trip
+// T + 1 in flight under the back half of trip T (k1_chunk).  pair_front: everything up to the ISSUE of the four 16-byte loads of the table row, and
+// whatever else does not depend on the row (1 / |u|, the model-side cut, the pixel's x).  pair_back: the blend, the renormalised offset, the
+// rotation.  What is cheaper to read again from LDS than to carry over a trip (corner weights, a / D, the rotation, z of the ring, the plane
+// offset packed in pk) is read again.  The arithmetic is pair_eval's, expression for expression.
+struct PairMid {
+    double q[8];                  // the table row {A_c, B_c}
+    double tr, ux, uy, uz, u2, rinv, fx;
+    uint32_t pk;                  // RowC2.pk of the pair's row
+    bool ok, in;                  // active and inside the radial axis; inside the model-side cut
+};
+
+template <bool FAR>
+__device__ inline void pair_front(PairMid &s, const Tab8T<double> &tb, const RowC2<double> rc, const PairRecT<double> *pairs,
+                                  const RingC2<double> *ringc, int t, bool act)
+{
+    using PMt = PMathE;
+    const int jj = t - (int)(rc.pk & 0xFFFu);
+    const PairRecT<double> &ph = pairs[(rc.pk >> 24) & 31u];
+    const RingC2<double> &rg = ringc[(rc.pk >> 18) & 63u];
+    const double sth = rg.sth;
+    s.pk = rc.pk;
+    const double x = fma_((double)jj, rg.dphi, rc.x0);
+    double sn, omc;
+    PMt::sin_omc(x, sn, omc);
+    if (FAR) {
+        if (act && !(fabs(x) <= 0.5)) { const double2 w = sin_omc_wide(x); sn = w.x; omc = w.y; }
+    }
+    const double ux = fma_(-sth, omc, rc.ds), uy = sth * sn, uz = rc.dz;
+    const double u2 = ux * ux + uy * uy + uz * uz;
+    const double u2s = (u2 > 1e-37) ? u2 : 1e-37;
+    s.rinv = PMt::rsq(u2s);
+    const double lx = PMt::half_ln(u2s * ph.scale2);
+    s.ok = act && (lx >= tb.r0) && (lx <= tb.r1);
+    const double uu = (lx - tb.r0) * tb.inv_dr;
+    const double uc = PMt::med3(uu, 0.0, (double)(tb.nr - 2));
+    const int i = (int)uc;
+    s.tr = uu - (double)i;
+    const double *tp = tb.v + (unsigned)(ph.cell + i * 8);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double2 a = reinterpret_cast<const double2 *>(tp)[k];
+        s.q[2 * k] = a.x; s.q[2 * k + 1] = a.y;
+    }
+    const double tc = fma_(u2, ph.cut2, -1.0);
+    s.in = tc < 0.0;
+    s.fx = fma_(-sth, omc, sth);
+    s.ux = ux; s.uy = uy; s.uz = uz; s.u2 = u2;
+}
+
+__device__ inline void pair_back(PairEval<double> &o, const PairMid &s, const PairRecT<double> *pairs, const RingC2<double> *ringc, int t,
+                                 int wsh, int wmask)
+{
+    using PMt = PMathE;
+    const int jj = t - (int)(s.pk & 0xFFFu);
+    const int rl = (int)((s.pk >> 18) & 63u);
+    o.la = (rl << wsh) + (((int)((s.pk >> 12) & 63u) + jj) & wmask);
+    const PairRecT<double> &ph = pairs[(s.pk >> 24) & 31u];
+    o.hidx = ph.hidx;
+    double d = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d = fma_(ph.w[k], fma_(s.tr, s.q[2 * k + 1], s.q[2 * k]), d);
+    o.amb = false;
+    const bool ok = s.ok && PMt::finite(d) && d != 0.0;
+    o.ok_nocut = ok;
+    o.ok = ok && s.in;
+    const double sc = d * ph.aD * s.rinv;
+    const double fx = s.fx, fy = s.uy, fz = ringc[rl].zf;
+    const double tt = sc * s.u2 * (1.0 + sc);
+    double g = 35.0 / 128.0;
+    g = fma_(g, tt, -0.3125);
+    g = fma_(g, tt, 0.375);
+    g = fma_(g, tt, -0.5);
+    g = g * tt;
+    const double c1 = fma_(g, sc, sc);
+    const double ex = fma_(c1, s.ux, g * fx), ey = fma_(c1, s.uy, g * fy), ez = fma_(c1, s.uz, g * fz);
+    o.v0 = ex * ph.cph0 - ey * ph.sph0;
+    o.v1 = ex * ph.sph0 + ey * ph.cph0;
+    o.v2 = ez;
+}
+
 // Branch-free evaluation of pair t of the current row block.
 template <int MODE, typename real, bool FAR = false, int PM = 0>
 __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const RowC2<real> rc, const PairRecT<real> *pairs,
                                  const RingC2<real> *ringc, int t, bool act, int wsh, int wmask)
 {
+    if constexpr (PM == 1) {                                           // (the parity-grade pair, unpipelined: the WIDE copy of the row pass)
+        static_assert(MODE == MODE_OFFSETS && sizeof(real) == 8, "PM = 1: fp64 pair math of the displacement kernel");
+        PairMid s;
+        pair_front<FAR>(s, tb, rc, pairs, ringc, t, act);
+        pair_back(o, s, pairs, ringc, t, wsh, wmask);
+        return;
+    }
     using PMt = typename PMSel<real, PM>::type;
     const int jj = t - (int)(rc.pk & 0xFFFu);
     const int rl = (int)((rc.pk >> 18) & 63u);
@@ -335,10 +440,65 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
     o.v2 = ez;
 }
 
+// The parity-grade pair loop of one row pass (`total` pairs, row records and first-pair mask in L), rotated: the front half of trip T + 1 -- up
+// to the issue of its table-row loads -- runs BEFORE the back half of trip T, which covers the latency of the gather.  Two named state sets and
+// the loop unrolled by two: nothing is copied at the back edge (a copy there makes the compiler wait for the loads in front of the moves).  The
+// last trip -- the only one of a row pass of up to 64 pairs -- has no front half beside it.  The mask word of a trip is wave-uniform and is
+// fetched a trip ahead; the row record is read at the top of the front half.
+// (Tag: the caller's narrow / wide tag, which keeps the call dependent inside k1_chunk's generic lambda; only the narrow copy comes here.)
+template <typename Tag, typename real>
+__device__ __forceinline__ void k1_pairs_rotated(Tag, const Tab8T<real> &tb, Wave2Lds<real> &L, const RingC2<real> *ringc, double *acc, int PL,
+                                                 int total, int lane, int wsh, int wmask)
+{
+    static_assert(!Tag::value && sizeof(real) == 8, "the narrow copy of the fp64 pair phase");
+    int base = 0;                                              // rows started before the trip
+    unsigned long long m_nx = wave_uniform64(L.mask[0]);
+    auto front = [&](PairMid &s, int T) __attribute__((always_inline)) {
+        const unsigned long long m = m_nx;
+        if (T + kWave < total) m_nx = wave_uniform64(L.mask[(T >> 6) + 1]);
+        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int row = base + below + (int)((m >> lane) & 1ull) - 1;
+        base += __popcll(m);
+        const bool act = T + lane < total;
+        pair_front<false>(s, tb, L.rows[act ? row : 0], L.pair, ringc, T + lane, act);
+    };
+    auto back = [&](const PairMid &s, int T) __attribute__((always_inline)) {
+        PairEval<double> pv;
+        pair_back(pv, s, L.pair, ringc, T + lane, wsh, wmask);
+        if (pv.ok) {
+            atomicAdd(acc + pv.la, pv.v0);                     // ds_add_f64
+            atomicAdd(acc + PL + pv.la, pv.v1);
+            atomicAdd(acc + 2 * PL + pv.la, pv.v2);
+        }
+    };
+    // (No join between a front half and the back half it runs beside: a back half that can be reached both with and without newer loads in
+    // flight has to wait for all of them.  And one exit from the loop: the last one or two trips are code of their own behind it.)
+    PairMid sA, sB;
+    front(sA, 0);
+    int T0 = 0;
+    for (; T0 + 2 * kWave < total; T0 += 2 * kWave) {           // at least two more trips behind trip T0, whose front half is done
+        front(sB, T0 + kWave);
+        __builtin_amdgcn_sched_barrier(0);                     // (the halves are not interleaved: their temporaries do not add up)
+        back(sA, T0);
+        front(sA, T0 + 2 * kWave);
+        __builtin_amdgcn_sched_barrier(0);
+        back(sB, T0 + kWave);
+    }
+    if (T0 + kWave < total) {
+        front(sB, T0 + kWave);
+        asm volatile("" : "+v"(sA.tr));                        // (an empty statement: this back half is not the other branch's, so it stays behind the loads above)
+        __builtin_amdgcn_sched_barrier(0);
+        back(sA, T0);
+        back(sB, T0 + kWave);
+    } else {
+        back(sA, T0);
+    }
+}
+
 // ---------------------------------------------------------------------------------- one chunk of a tile's entry list
 // What a wave does with one chunk -- the entries [ebeg, ebeg + ecnt), ecnt <= kChunk2 -- of a tile's narrow-halo list: entries -> ring rows -> pairs, accumulated into the tile's
 // LDS planes `acc`.  Shared by the barrier-per-tile kernel (tile_scatter2_kernel) and the fluid kernel (tile_scatter2f_kernel).
-template <int MODE, typename real, int NP, int PM = 0>
+template <int MODE, typename real, int NP, int PM = 0, bool PIPE = (PM == 1)>
 __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__restrict__ rowrecs, const PairRecT<real> *__restrict__ pairrecs,
                                          const FbRec *__restrict__ fbrecs, const int32_t *__restrict__ ea, const int32_t *__restrict__ eb,
                                          int na, int ebeg, int ecnt, int estride, int i0, int i1, int nphi, int wsh, int wmask, int PL,
@@ -417,7 +577,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
                 const TileRow &tr = rowtab[ring - i0];
                 int slo, scnt;
                 if (WIDE && (efb & 2)) { const int2 sp = disc_row_span_wide(tr, ring, rowrecs[eh], fbrecs[eh]); slo = sp.x; scnt = sp.y; }
-                else disc_row_span_narrow(tr.nr, tr.shifted != 0, tr.z, tr.fnr, rr.z0, rr.xa, rr.cosr, rr.phi0, slo, scnt);
+                else disc_row_span_narrow<PIPE>(tr.nr, tr.shifted != 0, tr.z, tr.fnr, rr.z0, rr.xa, rr.cosr, rr.phi0, slo, scnt);
                 rloc = ring - i0;
                 dzv = tr.z - rr.z0; dsv = tr.sth - rr.s0;
                 const int nr = tr.nr, ks = tr.ks, ke = tr.ke;
@@ -466,61 +626,66 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
 
             // ---- lanes = (halo, pixel) pairs, NP per lane per trip: the evaluations are straight-line code so that
             // the LDS reads and table loads of the NP pairs are in flight together
-            int base = 0;                                      // rows started before the current 64 pairs
-            // the mask word and the row record of the NEXT trip are fetched while this trip computes
-            unsigned long long m_nx = wave_uniform64(L.mask[0]);
-            RowC2<real> rc_nx[NP];
-#pragma unroll
-            for (int u = 0; u < NP; ++u) {
-                const unsigned long long m = (u == 0) ? m_nx : wave_uniform64(L.mask[u]);
-                const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const int row = base + below + (int)((m >> lane) & 1ull) - 1;
-                base += __popcll(m);
-                rc_nx[u] = L.rows[(u * kWave + lane < total) ? row : 0];
-            }
-            for (int T0 = 0; T0 < total; T0 += NP * kWave) {
-                PairEval<real> pv[NP];
-                RowC2<real> rc_cur[NP];
-#pragma unroll
-                for (int u = 0; u < NP; ++u) rc_cur[u] = rc_nx[u];
-                const int T1 = T0 + NP * kWave;
-                if (T1 < total) {
-#pragma unroll
+            if constexpr (PIPE && !WIDE) {
+                static_assert(NP == 1 && MODE == MODE_OFFSETS, "the rotated pair loop takes one pair per lane and trip");
+                k1_pairs_rotated(wide_tag, tb, L, ringc, acc, PL, total, lane, wsh, wmask);
+            } else {
+                int base = 0;                                      // rows started before the current 64 pairs
+                // the mask word and the row record of the NEXT trip are fetched while this trip computes
+                unsigned long long m_nx = wave_uniform64(L.mask[0]);
+                RowC2<real> rc_nx[NP];
+    #pragma unroll
+                for (int u = 0; u < NP; ++u) {
+                    const unsigned long long m = (u == 0) ? m_nx : wave_uniform64(L.mask[u]);
+                    const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    const int row = base + below + (int)((m >> lane) & 1ull) - 1;
+                    base += __popcll(m);
+                    rc_nx[u] = L.rows[(u * kWave + lane < total) ? row : 0];
+                }
+                for (int T0 = 0; T0 < total; T0 += NP * kWave) {
+                    PairEval<real> pv[NP];
+                    RowC2<real> rc_cur[NP];
+    #pragma unroll
+                    for (int u = 0; u < NP; ++u) rc_cur[u] = rc_nx[u];
+                    const int T1 = T0 + NP * kWave;
+                    if (T1 < total) {
+    #pragma unroll
+                        for (int u = 0; u < NP; ++u) {
+                            const unsigned long long m = wave_uniform64(L.mask[(T1 >> 6) + u]);
+                            const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                            const int row = base + below + (int)((m >> lane) & 1ull) - 1;
+                            base += __popcll(m);
+                            rc_nx[u] = L.rows[(T1 + u * kWave + lane < total) ? row : 0];
+                        }
+                    }
+    #pragma unroll
                     for (int u = 0; u < NP; ++u) {
-                        const unsigned long long m = wave_uniform64(L.mask[(T1 >> 6) + u]);
-                        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        const int row = base + below + (int)((m >> lane) & 1ull) - 1;
-                        base += __popcll(m);
-                        rc_nx[u] = L.rows[(T1 + u * kWave + lane < total) ? row : 0];
+                        const int t = T0 + u * kWave + lane;
+                        pair_eval<MODE, real, WIDE, PM>(pv[u], tb, rc_cur[u], L.pair, ringc, t, t < total, wsh, wmask);
                     }
-                }
-#pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    const int t = T0 + u * kWave + lane;
-                    pair_eval<MODE, real, WIDE, PM>(pv[u], tb, rc_cur[u], L.pair, ringc, t, t < total, wsh, wmask);
-                }
-                if (MODE == MODE_OFFSETS && sizeof(real) == 4) {
-                    // pairs whose fp32 chord is within 4e-6 of the model-side cut (BaryonCorrection.py:381-382): decide in fp64 (rare)
-                    bool anyamb = false;
-#pragma unroll
-                    for (int u = 0; u < NP; ++u) anyamb = anyamb || pv[u].amb;
-                    if (__builtin_expect(__any(anyamb), 0)) {
-#pragma unroll
-                        for (int u = 0; u < NP; ++u)
-                            if (pv[u].amb) {
-                                const int rl = pv[u].la >> wsh;
-                                const bool in = exact_cut_test(rowtab[rl], rowrecs[pv[u].hidx], (pv[u].la - (((rl & 7) << wsh) >> 3)) & wmask);
-                                pv[u].ok = pv[u].ok_nocut && in;
+                    if (MODE == MODE_OFFSETS && sizeof(real) == 4) {
+                        // pairs whose fp32 chord is within 4e-6 of the model-side cut (BaryonCorrection.py:381-382): decide in fp64 (rare)
+                        bool anyamb = false;
+    #pragma unroll
+                        for (int u = 0; u < NP; ++u) anyamb = anyamb || pv[u].amb;
+                        if (__builtin_expect(__any(anyamb), 0)) {
+    #pragma unroll
+                            for (int u = 0; u < NP; ++u)
+                                if (pv[u].amb) {
+                                    const int rl = pv[u].la >> wsh;
+                                    const bool in = exact_cut_test(rowtab[rl], rowrecs[pv[u].hidx], (pv[u].la - (((rl & 7) << wsh) >> 3)) & wmask);
+                                    pv[u].ok = pv[u].ok_nocut && in;
+                                }
+                        }
+                    }
+    #pragma unroll
+                    for (int u = 0; u < NP; ++u) {
+                        if (pv[u].ok) {
+                            atomicAdd(acc + pv[u].la, (double)pv[u].v0);                         // ds_add_f64
+                            if (MODE == MODE_OFFSETS) {
+                                atomicAdd(acc + PL + pv[u].la, (double)pv[u].v1);
+                                atomicAdd(acc + 2 * PL + pv[u].la, (double)pv[u].v2);
                             }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    if (pv[u].ok) {
-                        atomicAdd(acc + pv[u].la, (double)pv[u].v0);                         // ds_add_f64
-                        if (MODE == MODE_OFFSETS) {
-                            atomicAdd(acc + PL + pv[u].la, (double)pv[u].v1);
-                            atomicAdd(acc + 2 * PL + pv[u].la, (double)pv[u].v2);
                         }
                     }
                 }
