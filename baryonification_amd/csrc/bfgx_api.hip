@@ -24,8 +24,6 @@
 
 #include "../../include/bfgx.h"
 
-#include <atomic>
-static std::atomic<long long> g_host_pinned_in_place{0}, g_host_staged{0}, g_host_pin_min_bytes{-1};      // HostSpan (bfgx_debug_host_spans)
 #include "bfgx_devmem.hpp"
 #include "bfgx_cosmo.hpp"
 #include "bfgx_kernels.hpp"
@@ -1585,79 +1583,9 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
 }  // extern "C"
 
 // ------------------------------------------------------------------------------ one-shot host API
+#include "bfgx_oneshot.hpp"
+
 namespace {
-
-// Every one-shot host entry leaves NOTHING in flight when it returns -- on success and on every error path: asynchronous copies read the
-// caller's arrays (page-locked for the call, or pinned on the fly by the runtime) and write into the caller's result; a copy that is
-// still running when the caller frees or reuses those arrays is a GPU memory fault at a host address.  Declared first in an entry, it
-// is destroyed last (after the Pin objects have unregistered): its streams are drained at scope exit whatever the return path.
-struct DrainOnExit {
-    hipStream_t *s[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool null_stream = false;
-    ~DrainOnExit()
-    {
-        for (hipStream_t *q : s) if (q && *q) (void)hipStreamSynchronize(*q);
-        if (null_stream) (void)hipStreamSynchronize(nullptr);
-    }
-};
-
-// A caller's host array as the source / destination of the ASYNCHRONOUS copies of a one-shot entry:
-//  * already page-locked by the caller (bfgx_host_alloc): used as it is;
-//  * >= 32 MiB -- beyond glibc's largest mmap threshold, i.e. a mapping of its own that shares no page with another object: page-locked in
-//    place for the call (hipHostRegister);
-//  * smaller: NEVER page-locked in place.  A small numpy array lives in the process heap next to other live objects; page-locking and
-//    unlocking those pages call after call left a later, ordinary pageable copy from the same heap region reading through a mapping that
-//    was gone (seen twice in round 4 as "Memory access fault by GPU ... on address <heap address>").  Small arrays take the entry's
-//    synchronous route; `stage` (tests force the streamed route on small maps: BFGX_PIPE_CHUNKS) goes through a page-locked buffer of ours.
-constexpr size_t kPinInPlaceMin = (size_t)32 << 20;
-struct HostSpan {
-    void *user = nullptr, *use = nullptr;
-    size_t bytes = 0;
-    bool registered = false, staged = false, is_out = false;
-    hipStream_t *streams[3] = {nullptr, nullptr, nullptr};       // copies of the span may be in flight on these when an error returns early
-    bool open(const void *q, size_t nb, bool out, bool stage)
-    {
-        user = (void *)q; bytes = nb; is_out = out;
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, q) == hipSuccess && at.type == hipMemoryTypeHost) { use = user; return true; }
-        (void)hipGetLastError();
-        if (nb >= kPinInPlaceMin) {
-            if (hipHostRegister(user, nb, hipHostRegisterDefault) == hipSuccess) {
-                registered = true; use = user;
-                ++g_host_pinned_in_place;
-                long long m = g_host_pin_min_bytes.load();
-                while ((m < 0 || (long long)nb < m) && !g_host_pin_min_bytes.compare_exchange_weak(m, (long long)nb)) {}
-                return true;
-            }
-            (void)hipGetLastError();
-            return false;
-        }
-        if (!stage) return false;
-        if (hipHostMalloc(&use, nb ? nb : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); use = nullptr; return false; }
-        staged = true;
-        ++g_host_staged;
-        if (!out) std::memcpy(use, q, nb);
-        return true;
-    }
-    void drain() const { for (hipStream_t *s : streams) if (s && *s) (void)hipStreamSynchronize(*s); }
-    // success path, after the entry has drained its streams: a staged result reaches the caller's array
-    void commit() { if (staged && is_out && use) { drain(); std::memcpy(user, use, bytes); } }
-    ~HostSpan()
-    {
-        if (!registered && !staged) return;
-        drain();                                             // never unlock / free a buffer a copy still uses
-        if (registered) (void)hipHostUnregister(user);
-        if (staged && use) (void)hipHostFree(use);
-    }
-};
-
-struct Timer {
-    hipEvent_t a = nullptr, b = nullptr;
-    Timer() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
-    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start(hipStream_t s) { (void)hipEventRecord(a, s); }
-    double stop(hipStream_t s) { (void)hipEventRecord(b, s); (void)hipEventSynchronize(b); float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
-};
 
 constexpr int kCatCols = 4 + BFGX_MAX_EXTRA + 2;       // M, z, ra, dec, extra[2], ln1pz, lnM
 
@@ -1710,155 +1638,6 @@ int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], b
     return BFGX_OK;
 }
 
-}  // namespace
-
-// ---- plan caches of the one-shot API: a process() call re-uses the plan (model on the device, tiling, binning workspace) and the
-// device buffers of the previous call with the same model, geometry and device, so that a warm call performs no hipMalloc
-namespace {
-
-// The key of a cached entry: two independent 64-bit hashes (an FNV-style basis and prime; another basis and odd multiplier) and the
-// model table's value count.  A hit needs all three to agree, so that one 64-bit collision cannot hand a model another model's table.
-struct CacheKey {
-    uint64_t h[2] = {0xcbf29ce484222325ull, 0x2545f4914f6cdd1dull};
-    int64_t values = 0;
-    void add(const void *data, size_t bytes)
-    {
-        constexpr uint64_t m0 = 0x100000001b3ull, m1 = 0x9e3779b97f4a7c15ull;
-        const unsigned char *c = (const unsigned char *)data;
-        uint64_t a = h[0], b = h[1];
-        size_t i = 0;
-        for (; i + 8 <= bytes; i += 8) {
-            uint64_t w;
-            std::memcpy(&w, c + i, 8);
-            a = (a ^ w) * m0; a ^= a >> 29;
-            b = (b ^ w) * m1; b ^= b >> 29;
-        }
-        for (; i < bytes; ++i) { a = (a ^ c[i]) * m0; b = (b ^ c[i]) * m1; }
-        h[0] = a; h[1] = b;
-    }
-    template <typename T> void add(const T &v) { add(&v, sizeof(v)); }
-    bool operator==(const CacheKey &o) const { return h[0] == o.h[0] && h[1] == o.h[1] && values == o.values; }
-};
-
-// (device, model contents); the model has been validated: its table pointers are readable.  Each cache adds its geometry.
-CacheKey model_key(int device, const bfgx_model *m)
-{
-    CacheKey k;
-    k.add(device);
-    const bfgx_table &t = m->table;
-    k.add(t.ndim);
-    k.add(t.n, sizeof(t.n));
-    size_t nv = 1;
-    for (int d = 0; d < t.ndim; ++d) { k.add(t.axis[d], sizeof(double) * (size_t)t.n[d]); nv *= (size_t)t.n[d]; }
-    k.add(t.values, sizeof(double) * nv);
-    k.add(&t.rdelta_sampling, sizeof(int32_t) * 2);
-    k.add(t.eps_model);
-    k.add(m->cosmo_runner); k.add(m->cosmo_model);
-    k.add(m->massdef_runner.Delta); k.add(m->massdef_runner.rho_type);
-    k.add(m->massdef_model.Delta); k.add(m->massdef_model.rho_type);
-    k.add(m->eps_runner);
-    k.values = (int64_t)nv;
-    return k;
-}
-
-// A cached entry: its key, its plan and its streams and events.  The data travels up and down on streams of its own while the plan's
-// stream computes; phase events (timed) for bfgx_stats; two pools of per-range events: a range has arrived (ev_up) / has been computed (ev_k).
-template <typename Plan> struct CacheEntry {
-    CacheKey key;
-    uint64_t stamp = 0;
-    int device = 0;
-    Plan *plan = nullptr;
-    hipStream_t up = nullptr, down = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> ev_up, ev_k;
-    int create()
-    {
-        HIP_TRY(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
-        for (auto &v : ev) HIP_TRY(hipEventCreate(&v));
-        return BFGX_OK;
-    }
-    // at least nup events in ev_up and nk in ev_k
-    int pools(int nup, int nk)
-    {
-        while ((int)ev_up.size() < nup || (int)ev_k.size() < nk) {
-            std::vector<hipEvent_t> &pool = (int)ev_up.size() < nup ? ev_up : ev_k;
-            hipEvent_t v;
-            HIP_TRY(hipEventCreateWithFlags(&v, hipEventDisableTiming));
-            pool.push_back(v);
-        }
-        return BFGX_OK;
-    }
-    ~CacheEntry()            // (the plan is destroyed by PlanCache::drop, before the entry's own buffers are freed)
-    {
-        if (up) (void)hipStreamDestroy(up);
-        if (down) (void)hipStreamDestroy(down);
-        for (auto &v : ev) if (v) (void)hipEventDestroy(v);
-        for (auto &v : ev_up) (void)hipEventDestroy(v);
-        for (auto &v : ev_k) (void)hipEventDestroy(v);
-    }
-};
-
-void plan_destroy(bfgx_plan *p) { bfgx_plan_destroy(p); }
-void plan_destroy(bfgx_grid_plan *p) { bfgx_grid_plan_destroy(p); }
-void plan_destroy(bfgx_snapshot_plan *p) { bfgx_snapshot_plan_destroy(p); }
-
-// A least-recently-used cache of at most kMax entries E (a CacheEntry<Plan> with the entry's own device buffers).  One call at a time
-// holds mu; the shell, grid and snapshot entries each have a cache (and a mutex) of their own.
-template <typename E, size_t kMax> struct PlanCache {
-    std::mutex mu;
-    std::vector<E *> v;
-    uint64_t stamp = 0;
-
-    static void drop(E *e)
-    {
-        (void)hipSetDevice(e->device);
-        if (e->plan) plan_destroy(e->plan);
-        delete e;
-    }
-    // the entry for key, with a plan for at least n halos (make(capacity, &plan) builds it) and its streams; setup(e) then readies the
-    // entry's own buffers.  An entry whose set-up fails is removed.  mu is held by the caller.
-    template <typename Make, typename Setup> int acquire(const CacheKey &key, int device, int64_t n, Make make, Setup setup, E **out)
-    {
-        auto it = std::find_if(v.begin(), v.end(), [&](E *c) { return c->key == key; });
-        E *e = it != v.end() ? *it : nullptr;
-        if (e && e->plan->max_halos < n) {                   // grew: rebuild the plan (its workspace scales with max_halos)
-            (void)hipSetDevice(device);
-            plan_destroy(e->plan);
-            e->plan = nullptr;
-        }
-        if (!e) {
-            if (v.size() >= kMax) {
-                auto lru = std::min_element(v.begin(), v.end(), [](E *a, E *b) { return a->stamp < b->stamp; });
-                drop(*lru);
-                v.erase(lru);
-            }
-            e = new E();
-            e->key = key; e->device = device;
-            v.push_back(e);
-        }
-        int rc = BFGX_OK;
-        if (!e->plan && (rc = make(std::max<int64_t>(n + n / 4, 1024), &e->plan))) e->plan = nullptr;
-        if (!rc && hipSetDevice(device) != hipSuccess) rc = fail(BFGX_ERR_HIP, "hipSetDevice(%d) failed", device);
-        if (!rc && !e->up) rc = e->create();
-        if (!rc) rc = setup(e);
-        if (rc) {
-            v.erase(std::find(v.begin(), v.end(), e));
-            drop(e);
-            return rc;
-        }
-        e->stamp = ++stamp;
-        *out = e;
-        return BFGX_OK;
-    }
-    void clear()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (E *e : v) drop(e);
-        v.clear();
-    }
-};
-
 struct ShellEntry : CacheEntry<bfgx_plan> {
     PoolBuf cols[kCatCols], in, out, off, sums;
     // the catalog columns of the last call stay on the device under the caller's token (bfgx_opts.catalog_token)
@@ -1894,25 +1673,8 @@ int upload_catalog_pooled(ShellEntry *e, const bfgx_catalog *h, bfgx_catalog *d,
     return BFGX_OK;
 }
 
-// np.isclose(new_sum, old_sum): rtol 1e-5, atol 1e-8  (HealpixRunner.py:344-346)
-int check_mass(double sum_in, double sum_out)
-{
-    if (!(std::fabs(sum_out - sum_in) <= 1e-8 + 1e-5 * std::fabs(sum_in)))
-        return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sum_out, sum_in);
-    return BFGX_OK;
-}
-
-// the options of a one-shot entry; NULL: the defaults (each entry reads only its own fields)
-bfgx_opts entry_opts(const bfgx_opts *opts)
-{
-    bfgx_opts o{};
-    o.check_mass = 1; o.algo = 1; o.acc_offsets_f64 = BFGX_ACC_AUTO; o.acc_paint_f64 = 1;
-    if (opts) o = *opts;
-    return o;
-}
-
-// the start of a one-shot entry (g_shells.mu held): the cached plan for (device, nside, model) set to o.algo, its streams drained at exit
-int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const bfgx_opts &o, ShellEntry **e, DrainOnExit &drain)
+// the start of a one-shot entry (g_shells.mu held): the cached plan for (device, nside, model) set to o.algo
+int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const bfgx_opts &o, ShellEntry **e)
 {
     if (o.algo != 0 && o.algo != 1) return fail(BFGX_ERR_INVALID, "opts.algo must be 0 or 1");
     if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
@@ -1925,14 +1687,12 @@ int shell_begin(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside,
         return BFGX_OK;
     };
     if (int rc = g_shells.acquire(key, o.device, cat->n, make, [](ShellEntry *) -> int { return BFGX_OK; }, e)) return rc;
-    bfgx_plan *p = (*e)->plan;
-    p->algo = o.algo;
-    drain.s[0] = &p->stream; drain.s[1] = &(*e)->up; drain.s[2] = &(*e)->down; drain.null_stream = (p->stream == nullptr);
+    (*e)->plan->algo = o.algo;
     return BFGX_OK;
 }
 
 // Large maps travel in band ranges (contiguous RING pixel ranges) of at least 16 MB (8 ranges of 12.6 MB: 4.0 ms per call, 6 of 16.8 MB: 3.3 ms),
-// at most kChunksMax.  BFGX_PIPE_CHUNKS sets the count (tests: small maps, staged: HostSpan), BFGX_NO_PIPELINE sends every call down one pass.
+// at most kChunksMax.  BFGX_PIPE_CHUNKS sets the count (tests: small maps, through a staging buffer), BFGX_NO_PIPELINE sends every call down one pass.
 constexpr int kChunksMax = 16;
 struct Chunks {
     int n = 0;
@@ -1941,14 +1701,13 @@ struct Chunks {
     std::vector<int64_t> bfp;        // first pixel of every band, then npix
 };
 
-void chunk_plan(bfgx_plan *p, bool eligible, Chunks &c)
+void chunk_plan(bfgx_plan *p, bool eligible, const PipeKnobs &knobs, Chunks &c)
 {
     const size_t npix = (size_t)p->hpx.npix;
     c.n = (int)std::min<size_t>(kChunksMax, npix * sizeof(double) / ((size_t)16 << 20));
-    const char *ce = std::getenv("BFGX_PIPE_CHUNKS");
-    if (ce) c.n = std::max(2, std::min(kChunksMax, std::atoi(ce)));
-    c.stage = ce != nullptr;
-    c.piped = eligible && c.n >= 2 && p->tiling.nbands >= 2 * c.n && !std::getenv("BFGX_NO_PIPELINE");
+    if (knobs.stage) c.n = std::max(2, std::min(kChunksMax, knobs.chunks));
+    c.stage = knobs.stage;
+    c.piped = eligible && c.n >= 2 && p->tiling.nbands >= 2 * c.n && !knobs.off;
     if (!c.piped) return;
     int nb = 0;
     c.bfp.resize((size_t)p->tiling.nbands + 1);
@@ -1959,6 +1718,132 @@ void chunk_plan(bfgx_plan *p, bool eligible, Chunks &c)
         const int b = (int)(std::lower_bound(c.bfp.begin(), c.bfp.end(), target) - c.bfp.begin());
         c.cb[k] = std::min(std::max(b, c.cb[k - 1] + 1), nb - (c.n - k));
     }
+}
+
+constexpr int kOnePass = 1;          // what a streamed route returns (no BFGX_ERR_*: those are negative) to send the call down the one-pass route
+
+// The streamed route of bfgx_baryonify_shell.  Large maps travel in band ranges (chunk_plan): a range is regridded as soon as it and its apron
+// have arrived and goes back to the host while the next ones are still coming in, so that the two directions of the link work at the same
+// time.  The gathering regrid stores every pixel of a range exactly once; the few deposits it cannot gather (next to a pole) are listed and
+// added on the host.  Both host buffers are page-locked for the duration of the call (hipHostRegister: 2 us here) -- from pageable memory
+// the copies in and out take turns on the host thread and the one-pass route is faster (4.3 against 4.5 ms), which is also where a map
+// goes that cannot be registered.  *first_unsent: the first pixel of the map that has not been uploaded (npix: all of it is on its way).
+int shell_streamed(OneShotCall &call, ShellEntry *e, const DispMode &m, const Chunks &ch, double sums[2], int64_t *first_unsent)
+{
+    bfgx_plan *p = e->plan;
+    const int64_t npix = p->hpx.npix;
+    const int kChunks = ch.n, *cb = ch.cb;
+    const std::vector<int64_t> &bfp = ch.bfp;
+    const double *map_in = call.src<double>(); double *map_out = call.dst<double>();
+    if (int rc = e->pools(kChunks, kChunks)) return rc;
+    if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return alloc_fail("sums");
+    double *dsums = (double *)e->sums.p;
+    float *domax = (float *)(dsums + 2 * kChunks);
+    int sent = 0;
+    auto send = [&]() -> int {                           // the next range
+        const int64_t lo = bfp[cb[sent]], n = bfp[cb[sent + 1]] - lo;
+        HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, e->up));
+        HIP_TRY(hipEventRecord(e->ev_up[sent], e->up));
+        *first_unsent = bfp[cb[++sent]];
+        return BFGX_OK;
+    };
+    if (int rc = send()) return rc;
+    if (int rc = send()) return rc;
+    // how many rings a deposit travels: from the largest displacement K1 has seen (by now K1 has finished underneath the two copies)
+    float m2 = 0.0f;
+    if (int rc = bfgx_bands_max_offset2_device(p, 0, p->tiling.nbands, domax)) return rc;
+    HIP_TRY(hipMemcpyAsync(&m2, domax, sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    int32_t rings = kReachMax;
+    if (std::isfinite(m2)) { if (int rc = bfgx_plan_reach_rings(p, std::sqrt((double)m2), &rings)) return rc; }
+    if (rings > 4) return kOnePass;                      // large displacements: the data-sized aprons and the in-stream repair of regrid_impl
+    Restore<int> reach{p->band_reach, p->band_reach};
+    p->band_reach = rings;
+    int next = 0;
+    auto run_ready = [&]() -> int {                      // regrid every range whose apron lies within the ranges sent so far
+        while (next < kChunks) {
+            int64_t olo = 0, ohi = 0;
+            if (int rc = bfgx_plan_band_apron(p, cb[next], cb[next + 1], &olo, &ohi)) return rc;
+            int need = next;
+            while (need < kChunks - 1 && bfp[cb[need + 1]] < ohi) ++need;
+            if (need >= sent) break;
+            HIP_TRY(hipStreamWaitEvent(p->stream, e->ev_up[need], 0));
+            const int64_t lo = bfp[cb[next]], n = bfp[cb[next + 1]] - lo;
+            if (int rc = regrid_bands_impl(p, cb[next], cb[next + 1], (const double *)e->in.p, e->off.p, 0, npix, m,
+                                           (double *)e->out.p + lo, dsums + 2 * next, next == 0)) return rc;
+            HIP_TRY(hipEventRecord(e->ev_k[next], p->stream));
+            HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[next], 0));
+            HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
+            ++next;
+        }
+        return BFGX_OK;
+    };
+    int rc = run_ready();
+    while (rc == BFGX_OK && sent < kChunks) {
+        rc = send();
+        if (rc == BFGX_OK) rc = run_ready();
+    }
+    if (rc) return rc;                                   // (what is in flight is drained by the call scope)
+    if ((rc = call.mark(1, e->up)) || (rc = call.mark(2, p->stream))) return rc;
+    double hs[2 * kChunksMax];
+    HIP_TRY(hipMemcpyAsync(hs, dsums, sizeof(double) * 2 * (size_t)kChunks, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipStreamSynchronize(e->down));
+    if ((rc = call.mark(3, p->stream))) return rc;
+    for (int c = 0; c < kChunks; ++c) { sums[0] += hs[2 * c]; sums[1] += hs[2 * c + 1]; }
+    // the listed deposits (pixels next to a pole): added on the host; an overflowing list sends the call down the one-pass route
+    int64_t nfar = 0;
+    if (bfgx_plan_far_fetch(p, 0, nullptr, nullptr, &nfar) != BFGX_OK) return kOnePass;
+    if (nfar > 0) {
+        std::vector<int64_t> fp((size_t)nfar);
+        std::vector<double> fv((size_t)nfar);
+        if (int rc = bfgx_plan_far_fetch(p, nfar, fp.data(), fv.data(), &nfar)) return rc;
+        for (int64_t i = 0; i < nfar; ++i) if (fp[(size_t)i] >= 0 && fp[(size_t)i] < npix) map_out[fp[(size_t)i]] += fv[(size_t)i];
+    }
+    return BFGX_OK;
+}
+
+// The one-pass route of bfgx_baryonify_shell: what is left of the map goes up on a second stream (a copy from pageable memory occupies the
+// host, K0 + K1 run meanwhile), K2 after both, the map -> host
+int shell_one_pass(OneShotCall &call, ShellEntry *e, const DispMode &m, bool tiled, const double *map_in, double *map_out, int64_t first_unsent, double sums[2])
+{
+    bfgx_plan *p = e->plan;
+    const size_t npix = (size_t)p->hpx.npix, lo = (size_t)first_unsent;
+    if (lo < npix) HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (npix - lo) * sizeof(double), hipMemcpyHostToDevice, e->up));
+    if (int rc = call.mark(1, e->up)) return rc;
+    HIP_TRY(hipStreamWaitEvent(p->stream, e->ev[1], 0));
+    if (int rc = regrid_impl(p, (const double *)e->in.p, e->off.p, m, (double *)e->out.p, (double *)e->sums.p, tiled)) return rc;
+    if (int rc = call.mark(2, p->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(sums, e->sums.p, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (int rc = call.mark(3, p->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return BFGX_OK;
+}
+
+// The streamed route of bfgx_paint_shell: large fp64 maps are painted in band ranges (chunk_plan), each copied back while the next ones
+// are painted (map_out page-locked for the call); K0 runs once, K3 on the tiles of each range
+int paint_streamed(ShellEntry *e, const bfgx_catalog *dcat, const PaintMode &m, const Chunks &ch, double *map_out)
+{
+    bfgx_plan *p = e->plan;
+    if (int rc = check_scatter(p, dcat, e->out.p, true)) return rc;
+    if (int rc = e->pools(ch.n, ch.n)) return rc;
+    if (int rc = launch_k0(p, dcat, 0, m.k0_f64())) return rc;
+    TileLaunch k3;
+    k3.paint_pair_f32 = m.pair_f32();
+    k3.spread_tiles = p->tiling.ntiles;                  // K0 has binned the WHOLE catalog; every range launch sees the same density (ADVICE, round 4)
+    for (int c = 0; c < ch.n; ++c) {
+        k3.tile_lo = p->band_tile0_host[ch.cb[c]];
+        k3.tile_n = p->band_tile0_host[ch.cb[c + 1]] - k3.tile_lo;
+        // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
+        if (c > 0) HIP_TRY(hipMemsetAsync(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1), 0, sizeof(unsigned int), p->stream));
+        if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
+        HIP_TRY(hipEventRecord(e->ev_k[c], p->stream));
+        HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
+        const int64_t lo = ch.bfp[ch.cb[c]], n = ch.bfp[ch.cb[c + 1]] - lo;
+        HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
+    }
+    return BFGX_OK;
 }
 
 }  // namespace
@@ -1993,20 +1878,18 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     if (!cat || !model || !map_in || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     const bfgx_opts o = entry_opts(opts);
     std::lock_guard<std::mutex> lk(g_shells.mu);             // one shell call at a time (they share the cached plans)
-    DrainOnExit drain;
     ShellEntry *e = nullptr;
-    if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
+    if (int rc = shell_begin(cat, model, nside, o, &e)) return rc;
     bfgx_plan *p = e->plan;
-
+    OneShotCall call(&p->stream, e);
     const size_t npix = (size_t)p->hpx.npix;
     DispMode m;
     if (int rc = disp_mode(p, o.acc_offsets_f64, false, m)) return rc;      // (BFGX_ACC_AUTO: what the plan chose from the model's table)
     const size_t acc_bytes = npix * m.pixel_bytes();
     std::vector<double> hostlog;
     bfgx_catalog dcat;
-    // phases: catalog -> device, K0 + K1 launched (enqueue-only), THEN the map -> device on a second stream (a copy from
-    // pageable memory occupies the host, the kernels run meanwhile), K2 after both, map -> host
-    HIP_TRY(hipEventRecord(e->ev[0], p->stream));
+    // phases: catalog -> device, K0 + K1 launched (enqueue-only), THEN the map -> device (in ranges, or in one piece on a second stream), K2, map -> host
+    if (int rc = call.mark(0, p->stream)) return rc;
     if (int rc = upload_catalog_pooled(e, cat, &dcat, hostlog, o.catalog_token)) return rc;
     if (e->in.need(npix * sizeof(double)) || e->out.need(npix * sizeof(double)) || e->off.need(acc_bytes) || e->sums.need(40 * sizeof(double)))
         return alloc_fail("map buffers");
@@ -2018,127 +1901,19 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
     if (o.algo == 1) k1.omax = p->tile_omax;                 // K1's flush leaves the largest |offset|^2 of every tile for K2's aprons
     if (int rc = offsets_impl(p, &dcat, e->off.p, m, k1)) return rc;
     double sums[2] = {0, 0};
-    // Large maps travel in band ranges (chunk_plan): a range is regridded as soon as it and its apron have arrived and goes back to the
-    // host while the next ones are still coming in, so that the two directions of the link work at the same time.  The gathering regrid
-    // stores every pixel of a range exactly once; the few deposits it cannot gather (next to a pole) are listed and added on the host.
-    // Both host buffers are page-locked for the duration of the call (hipHostRegister: 2 us here) -- from pageable memory the copies in
-    // and out take turns on the host thread and the one-pass route below is faster (4.3 against 4.5 ms), which is also where a map goes
-    // that cannot be registered.
     Chunks ch;
-    chunk_plan(p, o.algo == 1, ch);
-    const int kChunks = ch.n, *cb = ch.cb;
-    const std::vector<int64_t> &bfp = ch.bfp;
-    bool piped = ch.piped;
-    bool whole_map_sent = false;
-    HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &p->stream; hin.streams[2] = hout.streams[2] = &e->down;
-    if (piped) piped = hin.open(map_in, npix * sizeof(double), false, ch.stage) && hout.open(map_out, npix * sizeof(double), true, ch.stage);
-    if (piped) { map_in = (const double *)hin.use; map_out = (double *)hout.use; }       // (from here on: the page-locked views)
-    if (piped) {
-        if (int rc = e->pools(kChunks, kChunks)) return rc;
-        if (e->sums.need((2 * kChunks + 2) * sizeof(double))) return alloc_fail("sums");
-        double *dsums = (double *)e->sums.p;
-        float *domax = (float *)(dsums + 2 * kChunks);
-        auto send = [&](int c) -> int {
-            const int64_t lo = bfp[cb[c]], n = bfp[cb[c + 1]] - lo;
-            HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, e->up));
-            HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
-            return BFGX_OK;
-        };
-        if (int rc = send(0)) return rc;
-        if (int rc = send(1)) return rc;
-        // how many rings a deposit travels: from the largest displacement K1 has seen (by now K1 has finished underneath the two copies)
-        float m2 = 0.0f;
-        if (int rc = bfgx_bands_max_offset2_device(p, 0, p->tiling.nbands, domax)) return rc;
-        HIP_TRY(hipMemcpyAsync(&m2, domax, sizeof(float), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        int32_t rings = kReachMax;
-        if (std::isfinite(m2)) { if (int rc = bfgx_plan_reach_rings(p, std::sqrt((double)m2), &rings)) return rc; }
-        const int32_t reach_before = p->band_reach;
-        if (rings > 4) piped = false;                        // large displacements: the data-sized aprons and the in-stream repair of regrid_impl
-        int sent = 2;
-        if (piped) {
-            p->band_reach = rings;
-            int next = 0;
-            int rc_run = BFGX_OK;
-            auto run_ready = [&]() -> int {                  // regrid every range whose apron lies within the ranges sent so far
-                while (next < kChunks) {
-                    int64_t olo = 0, ohi = 0;
-                    if (int rc = bfgx_plan_band_apron(p, cb[next], cb[next + 1], &olo, &ohi)) return rc;
-                    int need = next;
-                    while (need < kChunks - 1 && bfp[cb[need + 1]] < ohi) ++need;
-                    if (need >= sent) break;
-                    HIP_TRY(hipStreamWaitEvent(p->stream, e->ev_up[need], 0));
-                    const int64_t lo = bfp[cb[next]], n = bfp[cb[next + 1]] - lo;
-                    if (int rc = regrid_bands_impl(p, cb[next], cb[next + 1], (const double *)e->in.p, e->off.p, 0, (int64_t)npix, m,
-                                                   (double *)e->out.p + lo, dsums + 2 * next, next == 0)) return rc;
-                    HIP_TRY(hipEventRecord(e->ev_k[next], p->stream));
-                    HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[next], 0));
-                    HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
-                    ++next;
-                }
-                return BFGX_OK;
-            };
-            rc_run = run_ready();
-            for (; rc_run == BFGX_OK && sent < kChunks; ) {
-                rc_run = send(sent);
-                ++sent;
-                if (rc_run == BFGX_OK) rc_run = run_ready();
-            }
-            p->band_reach = reach_before;
-            if (rc_run) { (void)hipStreamSynchronize(e->up); (void)hipStreamSynchronize(p->stream); (void)hipStreamSynchronize(e->down); return rc_run; }
-            HIP_TRY(hipEventRecord(e->ev[1], e->up));
-            HIP_TRY(hipEventRecord(e->ev[2], p->stream));
-            double hs[2 * kChunksMax];
-            HIP_TRY(hipMemcpyAsync(hs, dsums, sizeof(double) * 2 * (size_t)kChunks, hipMemcpyDeviceToHost, p->stream));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            HIP_TRY(hipStreamSynchronize(e->down));
-            HIP_TRY(hipEventRecord(e->ev[3], p->stream));
-            for (int c = 0; c < kChunks; ++c) { sums[0] += hs[2 * c]; sums[1] += hs[2 * c + 1]; }
-            // the listed deposits (pixels next to a pole): added on the host; an overflowing list sends the call down the one-pass route
-            int64_t nfar = 0;
-            if (bfgx_plan_far_fetch(p, 0, nullptr, nullptr, &nfar) != BFGX_OK) piped = false;
-            else if (nfar > 0) {
-                std::vector<int64_t> fp((size_t)nfar);
-                std::vector<double> fv((size_t)nfar);
-                if (int rc = bfgx_plan_far_fetch(p, nfar, fp.data(), fv.data(), &nfar)) return rc;
-                for (int64_t i = 0; i < nfar; ++i) if (fp[(size_t)i] >= 0 && fp[(size_t)i] < (int64_t)npix) map_out[fp[(size_t)i]] += fv[(size_t)i];
-            }
-            whole_map_sent = true;
-        }
-        if (!piped) {                                        // the rest of the map in one piece, then the one-pass route below
-            if (!whole_map_sent && sent < kChunks) {
-                const int64_t lo = bfp[cb[sent]];
-                HIP_TRY(hipMemcpyAsync((double *)e->in.p + lo, map_in + lo, (npix - (size_t)lo) * sizeof(double), hipMemcpyHostToDevice, e->up));
-            }
-            whole_map_sent = true;
-        }
+    chunk_plan(p, o.algo == 1, pipe_knobs(), ch);
+    int64_t first_unsent = 0;
+    int rc = kOnePass;
+    if (ch.piped && call.open(map_in, npix * sizeof(double), map_out, npix * sizeof(double), ch.stage)) {
+        map_in = call.src<double>(); map_out = call.dst<double>();       // (from here on: the page-locked views)
+        rc = shell_streamed(call, e, m, ch, sums, &first_unsent);
     }
-    if (!piped) {
-        if (!whole_map_sent) HIP_TRY(hipMemcpyAsync(e->in.p, map_in, npix * sizeof(double), hipMemcpyHostToDevice, e->up));
-        HIP_TRY(hipEventRecord(e->ev[1], e->up));
-        HIP_TRY(hipStreamWaitEvent(p->stream, e->ev[1], 0));
-        if (int rc = regrid_impl(p, (const double *)e->in.p, e->off.p, m, (double *)e->out.p, (double *)e->sums.p, o.algo == 1)) return rc;
-        HIP_TRY(hipEventRecord(e->ev[2], p->stream));
-        HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipMemcpyAsync(sums, e->sums.p, sizeof(sums), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipEventRecord(e->ev[3], p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-    float f_h2d = 0, f_k = 0, f_d2h = 0;
-    (void)hipEventElapsedTime(&f_h2d, e->ev[0], e->ev[1]);   // both uploads (K0 + K1 run underneath the second one)
-    (void)hipEventElapsedTime(&f_k, e->ev[1], e->ev[2]);     // what the kernels add after the last byte has arrived
-    (void)hipEventElapsedTime(&f_d2h, e->ev[2], e->ev[3]);
-    const double ms_h2d = f_h2d, ms_k = f_k, ms_d2h = f_d2h;
+    if (rc == kOnePass) rc = shell_one_pass(call, e, m, o.algo == 1, map_in, map_out, first_unsent, sums);
+    if (rc) return rc;
     if (int rc = bfgx_plan_status(p)) return rc;             // far-deposit list / entry list
-    hout.commit();                                           // (a staged result reaches the caller's array)
-
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->sum_in = sums[0]; stats->sum_out = sums[1];
-        stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
-        stats->n_pairs = -1;
-    }
+    call.commit();
+    if (int rc = call.finish(stats, sums, -1)) return rc;
     return o.check_mass ? check_mass(sums[0], sums[1]) : BFGX_OK;
 }
 
@@ -2148,10 +1923,10 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     if (!cat || !model || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     const bfgx_opts o = entry_opts(opts);
     std::lock_guard<std::mutex> lk(g_shells.mu);
-    DrainOnExit drain;
     ShellEntry *e = nullptr;
-    if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
+    if (int rc = shell_begin(cat, model, nside, o, &e)) return rc;
     bfgx_plan *p = e->plan;
+    OneShotCall call(&p->stream, e);
     PaintMode m;
     if (int rc = paint_mode(p, o.acc_paint_f64, m)) return rc;
 
@@ -2162,43 +1937,19 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     t.start(p->stream);
     if (int rc = upload_catalog_pooled(e, cat, &dcat, hostlog, o.catalog_token)) return rc;
     if (e->out.need(npix * sizeof(double))) return alloc_fail("map");
-    const double ms_h2d = t.stop(p->stream);
-    t.start(p->stream);
-    // Large fp64 maps are painted in band ranges (chunk_plan), each copied back while the next ones are painted (map_out page-locked for
-    // the call); K0 runs once, K3 on the tiles of each range
+    const double ms_h2d = t.lap(p->stream);
     Chunks ch;
-    chunk_plan(p, o.algo == 1 && m.map_f64(), ch);
-    HostSpan hout;
-    hout.streams[0] = &p->stream; hout.streams[1] = &e->down;
-    if (ch.piped) ch.piped = hout.open(map_out, npix * sizeof(double), true, ch.stage);
-    if (ch.piped) map_out = (double *)hout.use;              // (from here on: the page-locked view)
+    chunk_plan(p, o.algo == 1 && m.map_f64(), pipe_knobs(), ch);
     double ms_k = 0.0;
-    if (ch.piped) {
-        if (int rc = check_scatter(p, &dcat, e->out.p, true)) return rc;
-        if (int rc = e->pools(ch.n, ch.n)) return rc;
-        if (int rc = launch_k0(p, &dcat, 0, m.k0_f64())) return rc;
-        TileLaunch k3;
-        k3.paint_pair_f32 = m.pair_f32();
-        k3.spread_tiles = p->tiling.ntiles;              // K0 has binned the WHOLE catalog; every range launch sees the same density (ADVICE, round 4)
-        for (int c = 0; c < ch.n; ++c) {
-            k3.tile_lo = p->band_tile0_host[ch.cb[c]];
-            k3.tile_n = p->band_tile0_host[ch.cb[c + 1]] - k3.tile_lo;
-            // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
-            if (c > 0) HIP_TRY(hipMemsetAsync(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1), 0, sizeof(unsigned int), p->stream));
-            if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
-            HIP_TRY(hipEventRecord(e->ev_k[c], p->stream));
-            HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
-            const int64_t lo = ch.bfp[ch.cb[c]], n = ch.bfp[ch.cb[c + 1]] - lo;
-            HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
-        }
-        ms_k = t.stop(p->stream);
-        t.start(p->stream);
+    if (ch.piped && call.open_out(map_out, npix * sizeof(double), ch.stage)) {
+        map_out = call.dst<double>();                        // (from here on: the page-locked view)
+        if (int rc = paint_streamed(e, &dcat, m, ch, map_out)) return rc;
+        ms_k = t.lap(p->stream);
         HIP_TRY(hipStreamSynchronize(e->down));
     } else {
         if (o.algo == 0) HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
         if (int rc = paint_impl(p, &dcat, e->out.p, m)) return rc;
-        ms_k = t.stop(p->stream);
-        t.start(p->stream);
+        ms_k = t.lap(p->stream);
         if (m.map_f64()) {
             HIP_TRY(hipMemcpyAsync(map_out, e->out.p, npix * sizeof(double), hipMemcpyDeviceToHost, p->stream));
             HIP_TRY(hipStreamSynchronize(p->stream));
@@ -2211,12 +1962,8 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
     }
     const double ms_d2h = t.stop(p->stream);
     if (int rc = bfgx_plan_status(p)) return rc;
-    hout.commit();
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
-        stats->n_pairs = -1;
-    }
+    call.commit();
+    fill_stats(stats, nullptr, -1, ms_h2d, ms_k, ms_d2h);
     return BFGX_OK;
 }
 

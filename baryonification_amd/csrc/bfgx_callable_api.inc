@@ -131,16 +131,8 @@ int bfgx_shell_pairs_apply(bfgx_pairs *h, const double *vals_host, const double 
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (!h->paint) if (int rc = bfgx_plan_status(p)) return rc;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->sum_in = sums[0]; stats->sum_out = sums[1];
-        stats->n_pairs = h->total;
-    }
-    if (!h->paint && check_mass) {      // np.isclose(new_sum, old_sum): rtol 1e-5, atol 1e-8  (HealpixRunner.py:344-346)
-        if (!(std::fabs(sums[1] - sums[0]) <= 1e-8 + 1e-5 * std::fabs(sums[0])))
-            return fail(BFGX_ERR_MASS, "ERROR in pixel regridding, sum(new_map) [%0.14e] != sum(oldmap) [%0.14e]", sums[1], sums[0]);
-    }
-    return BFGX_OK;
+    fill_stats(stats, sums, h->total, 0, 0, 0);
+    return (!h->paint && check_mass) ? ::check_mass(sums[0], sums[1]) : BFGX_OK;      // (HealpixRunner.py:344-346)
 }
 
 }  // extern "C"

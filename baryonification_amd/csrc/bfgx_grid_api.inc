@@ -513,6 +513,139 @@ int grid_acquire(int device, const bfgx_grid *grid, const bfgx_model *model, int
 
 constexpr int kGridChunksMax = 32;
 
+// How bfgx_baryonify_grid cuts a map: ranges of whole rows of gather blocks (2^S planes of the first axis: 8 planes in 3-D, 16 rows in 2-D)
+// of at least 16 MB, at most kGridChunksMax of them (BFGX_PIPE_CHUNKS sets the count: tests, small maps).  Chunk c = block rows
+// [c rows_per, (c + 1) rows_per); gather range 0 = block row 0 alone, 1 = the rest of chunk 0, c + 1 = chunk c.
+struct GridRangePlan {
+    int C = 0, rows_per = 0, nbk = 0, S = 0, N = 0;
+    bool piped = false;                  // the map travels in ranges (needs 3 of them); gr is filled
+    size_t plane = 1;                    // cells per plane of the first axis
+    GatherRanges gr;
+    int row0(int c) const { return std::min(c * rows_per, nbk); }
+    size_t cell0(int c) const { return (size_t)std::min<int64_t>((int64_t)row0(c) << S, N) * plane; }
+};
+
+GridRangePlan grid_range_plan(int ndim, int N, int S, const PipeKnobs &knobs)
+{
+    GridRangePlan r;
+    r.S = S; r.N = N; r.nbk = gather_blocks_per_axis(N, S);
+    const int nbk = r.nbk;
+    for (int d = 1; d < ndim; ++d) r.plane *= (size_t)N;
+    const size_t row_bytes = ((size_t)1 << S) * r.plane * sizeof(double);
+    r.rows_per = (int)std::max<size_t>(2, (((size_t)16 << 20) + row_bytes - 1) / row_bytes);
+    r.C = (nbk + r.rows_per - 1) / r.rows_per;
+    if (r.C > kGridChunksMax) { r.rows_per = (nbk + kGridChunksMax - 1) / kGridChunksMax; r.C = (nbk + r.rows_per - 1) / r.rows_per; }
+    if (knobs.stage) {
+        const int want = std::max(3, std::min(kGridChunksMax, knobs.chunks));
+        r.rows_per = std::max(2, nbk / want); r.C = (nbk + r.rows_per - 1) / r.rows_per;
+        if (r.C > kGridChunksMax) r.C = 0;
+    }
+    r.piped = r.C >= 3 && r.C <= kGridChunksMax && !knobs.off;
+    if (!r.piped) return r;
+    const int64_t blocks_per_row = (ndim == 3) ? (int64_t)nbk * nbk : nbk;
+    r.gr.n = r.C + 1; r.gr.lo[0] = 0; r.gr.hi[0] = blocks_per_row;
+    r.gr.lo[1] = blocks_per_row; r.gr.hi[1] = (int64_t)r.row0(1) * blocks_per_row;
+    for (int c = 1; c < r.C; ++c) { r.gr.lo[c + 1] = (int64_t)r.row0(c) * blocks_per_row; r.gr.hi[c + 1] = (int64_t)r.row0(c + 1) * blocks_per_row; }
+    return r;
+}
+
+// The streamed route of bfgx_baryonify_grid (both host arrays are open in `call`): a range is copied into map_out and gathered as soon as
+// it and its neighbours have arrived, and travels back while the next ones are still coming.  The first block row is gathered last (the
+// grid is periodic: it deposits into the last plane), so the first range also leaves last.
+int grid_streamed(OneShotCall &call, GridEntry *e, GridRangePlan &rp, double sums[2], int64_t *npairs)
+{
+    bfgx_grid_plan *p = e->plan;
+    const double *map_in = call.src<double>();
+    double *map_out = call.dst<double>(), *d_in = (double *)e->in.p, *d_out = (double *)e->out.p, *d_sums = (double *)e->sums.p;
+    hipStream_t s = p->stream;
+    const int C = rp.C, nwg = std::max(1, 2048 / C);
+    if (int rc = grid_check_catalog(p, &e->hc.d)) return rc;
+    if (int rc = gather_workspace(p)) return rc;
+    if (int rc = e->pools(C, C + 1)) return rc;
+    // uploads first (they need nothing), in order, on their own stream; the halo lists are built underneath them
+    for (int c = 0; c < C; ++c) {
+        const size_t lo = rp.cell0(c), n = rp.cell0(c + 1) - lo;
+        HIP_TRY(hipMemcpyAsync(d_in + lo, map_in + lo, n * sizeof(double), hipMemcpyHostToDevice, e->up));
+        HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
+    }
+    if (int rc = call.mark(1, e->up)) return rc;                           // the last byte of the map has arrived
+    if (int rc = grid_lists_stage(p, &e->hc.d, rp.gr)) return rc;
+    // How far may a cell move along the first array axis in this route?  Range 1 (the rest of chunk 0) is gathered when only chunks 0 and 1
+    // hold their start values: a deposit that travels back through block row 0 and across the periodic face lands in the LAST chunk before
+    // that chunk has been copied, and the copy then overwrites it; block row 0, gathered last, must not reach chunk 1, which has left the
+    // device by then; a middle chunk's deposits stay within its two neighbours.  One block row (2^S planes) is the tightest of these: a move
+    // of up to 2^S - 1 cells (+ 1 for the second overlap cell) is safe.  The gather kernel flags anything beyond; the call then repeats
+    // the regrid in one pass on the map it has already uploaded (the mass check alone would not notice: the sums are arithmetic).
+    Restore<float> limit{p->axis0_limit, 3.0e38f};
+    p->axis0_limit = (float)((1 << rp.S) - 1);
+    auto download = [&](int c, hipEvent_t after) -> int {
+        const size_t lo = rp.cell0(c), n = rp.cell0(c + 1) - lo;
+        HIP_TRY(hipStreamWaitEvent(e->down, after, 0));
+        HIP_TRY(hipMemcpyAsync(map_out + lo, d_out + lo, n * sizeof(double), hipMemcpyDeviceToHost, e->down));
+        return BFGX_OK;
+    };
+    for (int c = 0; c < C; ++c) {
+        HIP_TRY(hipStreamWaitEvent(s, e->ev_up[c], 0));
+        if (int rc = grid_copy_stage(p, d_in, d_out, (int64_t)rp.cell0(c), (int64_t)(rp.cell0(c + 1) - rp.cell0(c)), c * nwg, nwg)) return rc;
+        if (c >= 1) {
+            // chunk c - 1 has its own cells and both neighbours' start values (chunk 0: all but its first block row, which needs the LAST chunk)
+            if (int rc = grid_gather_stage(p, d_in, d_out, rp.gr, c - 1 == 0 ? 1 : c)) return rc;
+            HIP_TRY(hipEventRecord(e->ev_k[c - 1], s));
+            if (c - 2 >= 1) if (int rc = download(c - 2, e->ev_k[c - 1])) return rc;      // nothing deposits into chunk c - 2 any more
+        }
+    }
+    if (int rc = grid_gather_stage(p, d_in, d_out, rp.gr, C)) return rc;                     // the last chunk (deposits into plane 0: chunk 0 is all there)
+    if (int rc = grid_gather_stage(p, d_in, d_out, rp.gr, 0)) return rc;                     // block row 0 (deposits into the last plane)
+    HIP_TRY(hipEventRecord(e->ev_k[C - 1], s));
+    if (int rc = grid_sums_stage(p, C * nwg, d_sums, npairs)) return rc;                     // (synchronises the plan's stream)
+    if (int rc = call.mark(2, s)) return rc;
+    if (C - 2 >= 1) if (int rc = download(C - 2, e->ev_k[C - 1])) return rc;
+    if (int rc = download(C - 1, e->ev_k[C - 1])) return rc;
+    if (int rc = download(0, e->ev_k[C - 1])) return rc;
+    int32_t moved_too_far = 0;
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&moved_too_far, p->axis0_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(e->down));
+    HIP_TRY(hipStreamSynchronize(e->up));
+    if (moved_too_far) {
+        // a cell moved further along the first axis than the plane ranges allow: the whole map is on the device -- regrid it in one pass
+        p->axis0_limit = 3.0e38f;
+        ++g_grid_pipe_fallbacks;
+        HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(double), s));
+        if (int rc = bfgx_grid_baryonify_device(p, &e->hc.d, d_in, d_out, d_sums, npairs)) return rc;
+        if (int rc = call.mark(2, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(map_out, d_out, (size_t)p->geom.ntot * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(sums, d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return call.mark(3, e->down);
+}
+
+// The one-pass route of bfgx_baryonify_grid: the whole map up, the cell-owned pass (or, BFGX_GRID_PATH=scatter, the halo-owned kernels),
+// the whole map down
+int grid_one_pass(OneShotCall &call, GridEntry *e, bool scatter, const double *map_in, double *map_out, double sums[2], int64_t *npairs)
+{
+    bfgx_grid_plan *p = e->plan;
+    const size_t ntot = (size_t)p->geom.ntot;
+    double *d_in = (double *)e->in.p, *d_out = (double *)e->out.p, *d_sums = (double *)e->sums.p;
+    hipStream_t s = p->stream;
+    HIP_TRY(hipMemcpyAsync(d_in, map_in, ntot * sizeof(double), hipMemcpyHostToDevice, s));
+    if (int rc = call.mark(1, s)) return rc;
+    if (scatter) {
+        DevBuf d_off;
+        if (d_off.alloc(ntot * p->geom.ndim * sizeof(double))) return alloc_fail("pix_offsets");
+        if (int rc = bfgx_grid_offsets_device(p, &e->hc.d, (double *)d_off.p, npairs)) return rc;
+        if (int rc = bfgx_grid_regrid_device(p, d_in, (const double *)d_off.p, d_out, d_sums)) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+    } else if (int rc = bfgx_grid_baryonify_device(p, &e->hc.d, d_in, d_out, d_sums, npairs)) return rc;
+    if (int rc = call.mark(2, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(map_out, d_out, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return call.mark(3, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -526,150 +659,23 @@ int bfgx_baryonify_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, c
     GridEntry *e = nullptr;
     if (int rc = grid_acquire(o.device, grid, model, cat->n, &e)) return rc;
     bfgx_grid_plan *p = e->plan;
-    DrainOnExit drain;                                       // (first: destroyed after the HostSpans)
-    drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.s[2] = &e->down; drain.null_stream = (p->stream == nullptr);
+    OneShotCall call(&p->stream, e);
     const size_t ntot = (size_t)p->geom.ntot;
-    const int ndim = p->geom.ndim, N = p->geom.npix;
-    GridHostCatalog &hc = e->hc;
+    const int ndim = p->geom.ndim;
     // BFGX_GRID_PATH=scatter keeps the halo-owned kernels (what the multi-GPU entry points use) reachable from the one-shot API for tests
     const char *path = std::getenv("BFGX_GRID_PATH");
     const bool scatter = path && std::strcmp(path, "scatter") == 0;
-    double *d_in = (double *)e->in.p, *d_out = (double *)e->out.p, *d_sums = (double *)e->sums.p;
-    hipStream_t s = p->stream;
-    HIP_TRY(hipEventRecord(e->ev[0], s));
-    if (int rc = hc.upload(cat, ndim, p->model.tab.ndim - 3, s)) return rc;
-    HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(double), s));
+    if (int rc = call.mark(0, p->stream)) return rc;
+    if (int rc = e->hc.upload(cat, ndim, p->model.tab.ndim - 3, p->stream)) return rc;
+    HIP_TRY(hipMemsetAsync(e->sums.p, 0, 2 * sizeof(double), p->stream));
     int64_t npairs = 0;
     double sums[2] = {0, 0};
-    float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
-
-    // ---- the map travels in ranges of whole rows of gather blocks (8 planes in 3-D, 16 rows in 2-D) of at least 16 MB: a range is copied
-    // into map_out and gathered as soon as it and its neighbours have arrived, and travels back while the next ones are still coming.
-    // The first block row is gathered last (the grid is periodic: it deposits into the last plane), so the first range also leaves last.
-    const int S = (ndim == 3) ? GatherBlk<3>::S : GatherBlk<2>::S, nbk = gather_blocks_per_axis(N, S);
-    size_t plane = 1;
-    for (int d = 1; d < ndim; ++d) plane *= (size_t)N;                       // cells per plane of the first axis
-    const size_t row_bytes = ((size_t)1 << S) * plane * sizeof(double);
-    int rows_per = (int)std::max<size_t>(2, (((size_t)16 << 20) + row_bytes - 1) / row_bytes);
-    int C = (nbk + rows_per - 1) / rows_per;
-    if (C > kGridChunksMax) { rows_per = (nbk + kGridChunksMax - 1) / kGridChunksMax; C = (nbk + rows_per - 1) / rows_per; }
-    if (const char *ce = std::getenv("BFGX_PIPE_CHUNKS")) {                  // (tests: small maps)
-        const int want = std::max(3, std::min(kGridChunksMax, std::atoi(ce)));
-        rows_per = std::max(2, nbk / want); C = (nbk + rows_per - 1) / rows_per;
-        if (C > kGridChunksMax) C = 0;
-    }
-    bool piped = !scatter && C >= 3 && C <= kGridChunksMax && !std::getenv("BFGX_NO_PIPELINE");
-    HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &e->down; hin.streams[2] = hout.streams[2] = &p->stream;
-    const bool stage_small = std::getenv("BFGX_PIPE_CHUNKS") != nullptr;
-    if (piped) piped = hin.open(map_in, ntot * sizeof(double), false, stage_small) && hout.open(map_out, ntot * sizeof(double), true, stage_small);
-    if (piped) { map_in = (const double *)hin.use; map_out = (double *)hout.use; }       // (from here on: the page-locked views)
-    if (piped) {
-        if (int rc = grid_check_catalog(p, &hc.d)) return rc;
-        if (int rc = gather_workspace(p)) return rc;
-        if (int rc = e->pools(C, C + 1)) return rc;
-        // ranges: chunk c = block rows [c rows_per, (c + 1) rows_per); gather range 0 = block row 0 alone, 1 = the rest of chunk 0, c + 1 = chunk c
-        const int64_t blocks_per_row = (ndim == 3) ? (int64_t)nbk * nbk : nbk;
-        auto row0 = [&](int c) { return std::min(c * rows_per, nbk); };
-        auto cell0 = [&](int c) { return (size_t)std::min<int64_t>((int64_t)row0(c) << S, N) * plane; };
-        GatherRanges gr;
-        gr.n = C + 1;
-        gr.lo[0] = 0; gr.hi[0] = blocks_per_row;
-        gr.lo[1] = blocks_per_row; gr.hi[1] = (int64_t)row0(1) * blocks_per_row;
-        for (int c = 1; c < C; ++c) { gr.lo[c + 1] = (int64_t)row0(c) * blocks_per_row; gr.hi[c + 1] = (int64_t)row0(c + 1) * blocks_per_row; }
-        // uploads first (they need nothing), in order, on their own stream; the halo lists are built underneath them
-        for (int c = 0; c < C; ++c) {
-            const size_t lo = cell0(c), n = cell0(c + 1) - lo;
-            HIP_TRY(hipMemcpyAsync(d_in + lo, map_in + lo, n * sizeof(double), hipMemcpyHostToDevice, e->up));
-            HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
-        }
-        HIP_TRY(hipEventRecord(e->ev[1], e->up));                          // the last byte of the map has arrived
-        if (int rc = grid_lists_stage(p, &hc.d, gr)) return rc;
-        // How far may a cell move along the first array axis in this route?  Range 1 (the rest of chunk 0) is gathered when only chunks 0 and 1
-        // hold their start values: a deposit that travels back through block row 0 and across the periodic face lands in the LAST chunk before
-        // that chunk has been copied, and the copy then overwrites it; block row 0, gathered last, must not reach chunk 1, which has left the
-        // device by then; a middle chunk's deposits stay within its two neighbours.  One block row (2^S planes) is the tightest of these: a move
-        // of up to 2^S - 1 cells (+ 1 for the second overlap cell) is safe.  The gather kernel flags anything beyond; the call then repeats
-        // the regrid in one pass on the map it has already uploaded (the mass check alone would not notice: the sums are arithmetic).
-        struct LimitGuard { bfgx_grid_plan *p; ~LimitGuard() { p->axis0_limit = 3.0e38f; } } limit_guard{p};
-        p->axis0_limit = (float)((1 << S) - 1);
-        const int nwg = std::max(1, 2048 / C);
-        auto download = [&](int c, hipEvent_t after) -> int {
-            const size_t lo = cell0(c), n = cell0(c + 1) - lo;
-            HIP_TRY(hipStreamWaitEvent(e->down, after, 0));
-            HIP_TRY(hipMemcpyAsync(map_out + lo, d_out + lo, n * sizeof(double), hipMemcpyDeviceToHost, e->down));
-            return BFGX_OK;
-        };
-        for (int c = 0; c < C; ++c) {
-            HIP_TRY(hipStreamWaitEvent(s, e->ev_up[c], 0));
-            if (int rc = grid_copy_stage(p, d_in, d_out, (int64_t)cell0(c), (int64_t)(cell0(c + 1) - cell0(c)), c * nwg, nwg)) return rc;
-            if (c >= 1) {
-                // chunk c - 1 has its own cells and both neighbours' start values (chunk 0: all but its first block row, which needs the LAST chunk)
-                if (int rc = grid_gather_stage(p, d_in, d_out, gr, c - 1 == 0 ? 1 : c)) return rc;
-                HIP_TRY(hipEventRecord(e->ev_k[c - 1], s));
-                if (c - 2 >= 1) if (int rc = download(c - 2, e->ev_k[c - 1])) return rc;      // nothing deposits into chunk c - 2 any more
-            }
-        }
-        if (int rc = grid_gather_stage(p, d_in, d_out, gr, C)) return rc;                      // the last chunk (deposits into plane 0: chunk 0 is all there)
-        if (int rc = grid_gather_stage(p, d_in, d_out, gr, 0)) return rc;                      // block row 0 (deposits into the last plane)
-        HIP_TRY(hipEventRecord(e->ev_k[C - 1], s));
-        if (int rc = grid_sums_stage(p, C * nwg, d_sums, &npairs)) return rc;                  // (synchronises the plan's stream)
-        HIP_TRY(hipEventRecord(e->ev[2], s));
-        if (C - 2 >= 1) if (int rc = download(C - 2, e->ev_k[C - 1])) return rc;
-        if (int rc = download(C - 1, e->ev_k[C - 1])) return rc;
-        if (int rc = download(0, e->ev_k[C - 1])) return rc;
-        int32_t moved_too_far = 0;
-        HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&moved_too_far, p->axis0_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipStreamSynchronize(e->down));
-        HIP_TRY(hipStreamSynchronize(e->up));
-        if (moved_too_far) {
-            // a cell moved further along the first axis than the plane ranges allow: the whole map is on the device -- regrid it in one pass
-            p->axis0_limit = 3.0e38f;
-            ++g_grid_pipe_fallbacks;
-            HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(double), s));
-            if (int rc = bfgx_grid_baryonify_device(p, &hc.d, d_in, d_out, d_sums, &npairs)) return rc;
-            HIP_TRY(hipEventRecord(e->ev[2], s));
-            HIP_TRY(hipMemcpyAsync(map_out, d_out, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        hipEvent_t endv = e->ev[0];                                          // reuse: phases are read before it is re-recorded
-        (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
-        (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
-        if (ms_k < 0) ms_k = 0;
-        HIP_TRY(hipEventRecord(endv, e->down));
-        HIP_TRY(hipEventSynchronize(endv));
-        (void)hipEventElapsedTime(&ms_d2h, e->ev[2], endv);
-    } else {
-        // one pass: the whole map up, the cell-owned pass (or the halo-owned kernels), the whole map down
-        HIP_TRY(hipMemcpyAsync(d_in, map_in, ntot * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(e->ev[1], s));
-        if (scatter) {
-            DevBuf d_off;
-            if (d_off.alloc(ntot * ndim * sizeof(double))) return alloc_fail("pix_offsets");
-            if (int rc = bfgx_grid_offsets_device(p, &hc.d, (double *)d_off.p, &npairs)) return rc;
-            if (int rc = bfgx_grid_regrid_device(p, d_in, (const double *)d_off.p, d_out, d_sums)) return rc;
-            HIP_TRY(hipStreamSynchronize(s));
-        } else if (int rc = bfgx_grid_baryonify_device(p, &hc.d, d_in, d_out, d_sums, &npairs)) return rc;
-        HIP_TRY(hipEventRecord(e->ev[2], s));
-        HIP_TRY(hipMemcpyAsync(map_out, d_out, ntot * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
-        (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
-        HIP_TRY(hipEventRecord(e->ev[0], s));
-        HIP_TRY(hipEventSynchronize(e->ev[0]));
-        (void)hipEventElapsedTime(&ms_d2h, e->ev[2], e->ev[0]);
-    }
-    hout.commit();                                           // (a staged result reaches the caller's array)
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->sum_in = sums[0]; stats->sum_out = sums[1];
-        stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
-        stats->n_pairs = npairs;
-    }
+    const PipeKnobs knobs = pipe_knobs();
+    GridRangePlan rp = grid_range_plan(ndim, p->geom.npix, (ndim == 3) ? GatherBlk<3>::S : GatherBlk<2>::S, knobs);
+    const bool piped = !scatter && rp.piped && call.open(map_in, ntot * sizeof(double), map_out, ntot * sizeof(double), knobs.stage);
+    if (int rc = piped ? grid_streamed(call, e, rp, sums, &npairs) : grid_one_pass(call, e, scatter, map_in, map_out, sums, &npairs)) return rc;
+    call.commit();                                           // (a staged result reaches the caller's array)
+    if (int rc = call.finish(stats, sums, npairs)) return rc;
     return o.check_mass ? check_mass(sums[0], sums[1]) : BFGX_OK;      // (Map2DRunner.py:601-605)
 }
 
@@ -690,20 +696,14 @@ int bfgx_paint_grid(const bfgx_grid_catalog *cat, const bfgx_model *model, const
     t.start(p->stream);
     if (int rc = hc.upload(cat, grid->ndim, p->model.tab.ndim - 3, p->stream)) return rc;
     if (d_out.alloc(ntot * sizeof(double))) return alloc_fail("map");
-    const double ms_h2d = t.stop(p->stream);
-    t.start(p->stream);
+    const double ms_h2d = t.lap(p->stream);
     int64_t npairs = 0;
     if (int rc = bfgx_grid_paint_device(p, &hc.d, (double *)d_out.p, &npairs)) return rc;
-    const double ms_k = t.stop(p->stream);
-    t.start(p->stream);
+    const double ms_k = t.lap(p->stream);
     HIP_TRY(hipMemcpyAsync(map_out, d_out.p, ntot * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     const double ms_d2h = t.stop(p->stream);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
-        stats->n_pairs = npairs;
-    }
+    fill_stats(stats, nullptr, npairs, ms_h2d, ms_k, ms_d2h);
     return BFGX_OK;
 }
 
@@ -970,14 +970,11 @@ int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const vo
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
     if (b.rec.need(rbytes, 8, 8) || b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return alloc_fail("deposit records");
     if (!b.up) HIP_TRY(hipStreamCreateWithFlags(&b.up, hipStreamNonBlocking));
-    DrainOnExit drain;
-    drain.s[0] = &b.up;
     // the records go up as they are (page-locked for the call when the host allows it: the copy then runs at the PCIe rate); the kernels
     // read the coordinate / mass fields at their stride -- no strided gather of four columns on the host
-    HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &b.up;
-    (void)hin.open(records, rbytes, false, false);           // (large arrays are page-locked for the call; small ones are copied from pageable memory)
-    (void)hout.open(map_out, mbytes, true, false);
+    OneShotCall call(&b.up);
+    (void)call.open_in(records, rbytes, false);              // (large arrays are page-locked for the call; small ones are copied from pageable memory)
+    (void)call.open_out(map_out, mbytes, false);
     hipStream_t s = b.up;
     HIP_TRY(hipMemcpyAsync(b.edges.p, edges, ebytes, hipMemcpyHostToDevice, s));
     if (rbytes) HIP_TRY(hipMemcpyAsync(b.rec.p, records, rbytes, hipMemcpyHostToDevice, s));

@@ -228,23 +228,18 @@ int bfgx_baryonify_snapshot(const bfgx_grid_catalog *halos, const bfgx_model *mo
     if (dx.up(snap->x, nb) || dy.up(snap->y, nb) || (snap->ndim == 3 && dz.up(snap->z, nb)) || ox.up(nullptr, nb) || oy.up(nullptr, nb) ||
         (snap->ndim == 3 && oz.up(nullptr, nb)))
         return fail(BFGX_ERR_HIP, "hipMalloc / copy(particles) failed");
-    const double ms_h2d = t.stop(nullptr);
+    const double ms_h2d = t.lap(nullptr);
     bfgx_snapshot ds = *snap;
     ds.x = dx.as<double>(); ds.y = dy.as<double>(); ds.z = snap->ndim == 3 ? dz.as<double>() : nullptr;
-    t.start(nullptr);
     int64_t npairs = 0;
     if (int rc = bfgx_baryonify_snapshot_device(device, nullptr, &hc.d, model, &ds, ox.as<double>(), oy.as<double>(),
                                                 snap->ndim == 3 ? oz.as<double>() : nullptr, &npairs)) return rc;
-    const double ms_k = t.stop(nullptr);
-    t.start(nullptr);
+    const double ms_k = t.lap(nullptr);
     HIP_TRY(hipMemcpy(x_out, ox.p, nb, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(y_out, oy.p, nb, hipMemcpyDeviceToHost));
     if (snap->ndim == 3) HIP_TRY(hipMemcpy(z_out, oz.p, nb, hipMemcpyDeviceToHost));
     const double ms_d2h = t.stop(nullptr);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_pairs = npairs; stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k; stats->ms_d2h = ms_d2h;
-    }
+    fill_stats(stats, nullptr, npairs, ms_h2d, ms_k, ms_d2h);
     return BFGX_OK;
 }
 
@@ -272,6 +267,15 @@ int snap_acquire(int device, const bfgx_model *model, int32_t ndim, double L, do
     return g_snaps.acquire(key, device, nhalo, make, setup, out);
 }
 
+// how many chunks n records of `bytes` in all travel in: pieces of at least 16 MB, at most kSnapChunksMax (BFGX_PIPE_CHUNKS sets the count)
+int snap_chunk_count(int64_t n, size_t bytes, const PipeKnobs &knobs)
+{
+    int C = (int)std::min<size_t>(kSnapChunksMax, std::max<size_t>(1, bytes / ((size_t)16 << 20)));
+    if (knobs.stage) C = std::max(1, std::min(kSnapChunksMax, knobs.chunks));
+    return (knobs.off || n < C) ? 1 : C;
+}
+int64_t snap_chunk_first(int64_t n, int C, int c) { return (int64_t)(((__int128)n * c) / C); }       // the first record of chunk c of C
+
 }  // namespace
 
 extern "C" {
@@ -294,35 +298,28 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
     bfgx_snapshot_plan *p = e->plan;
     const size_t bytes = (size_t)n * (size_t)itemsize;
     hipStream_t s = p->stream;
-    DrainOnExit drain;
-    drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.s[2] = &e->down; drain.null_stream = (p->stream == nullptr);
-    GridHostCatalog &hc = e->hc;
-    HIP_TRY(hipEventRecord(e->ev[0], s));
-    if (int rc = hc.upload(halos, ndim, 0, s)) return rc;
+    OneShotCall call(&p->stream, e);
+    if (int rc = call.mark(0, s)) return rc;
+    if (int rc = e->hc.upload(halos, ndim, 0, s)) return rc;
     // ---- the records travel in chunks of at least 16 MB: a chunk is displaced IN PLACE on the device as soon as it has arrived (the halo
     // lists are built underneath the first uploads) and travels back while the next ones arrive.  Page-locked on both sides for the call.
-    int C = (int)std::min<size_t>(kSnapChunksMax, std::max<size_t>(1, bytes / ((size_t)16 << 20)));
-    if (const char *ce = std::getenv("BFGX_PIPE_CHUNKS")) C = std::max(1, std::min(kSnapChunksMax, std::atoi(ce)));
-    if (std::getenv("BFGX_NO_PIPELINE") || n < C) C = 1;
-    HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &e->down; hin.streams[2] = hout.streams[2] = &p->stream;
-    const bool stage_small = std::getenv("BFGX_PIPE_CHUNKS") != nullptr;
-    if (C > 1 && !(hin.open(records_in, bytes, false, stage_small) && hout.open(records_out, bytes, true, stage_small))) C = 1;      // pageable memory: one piece
-    const char *src = (C > 1) ? (const char *)hin.use : (const char *)records_in;
-    char *dst = (C > 1) ? (char *)hout.use : (char *)records_out;
+    const PipeKnobs knobs = pipe_knobs();
+    int C = snap_chunk_count(n, bytes, knobs);
+    if (C > 1 && !call.open(records_in, bytes, records_out, bytes, knobs.stage)) C = 1;      // pageable memory: one piece
+    const char *src = (C > 1) ? call.src<char>() : (const char *)records_in;
+    char *dst = (C > 1) ? call.dst<char>() : (char *)records_out;
     if (int rc = e->pools(C, C)) return rc;
     char *d_rec = (char *)e->rec.p;
-    auto first = [&](int c) { return (int64_t)(((__int128)n * c) / C); };
     for (int c = 0; c < C; ++c) {
-        const int64_t lo = first(c), cnt = first(c + 1) - lo;
+        const int64_t lo = snap_chunk_first(n, C, c), cnt = snap_chunk_first(n, C, c + 1) - lo;
         if (cnt > 0) HIP_TRY(hipMemcpyAsync(d_rec + (size_t)lo * itemsize, src + (size_t)lo * itemsize, (size_t)cnt * itemsize, hipMemcpyHostToDevice, e->up));
         HIP_TRY(hipEventRecord(e->ev_up[c], e->up));
     }
-    HIP_TRY(hipEventRecord(e->ev[1], e->up));
-    if (int rc = snap_lists_stage(p, &hc.d)) return rc;
+    if (int rc = call.mark(1, e->up)) return rc;
+    if (int rc = snap_lists_stage(p, &e->hc.d)) return rc;
     const int64_t stride = itemsize / 8;
     for (int c = 0; c < C; ++c) {
-        const int64_t lo = first(c), cnt = first(c + 1) - lo;
+        const int64_t lo = snap_chunk_first(n, C, c), cnt = snap_chunk_first(n, C, c + 1) - lo;
         HIP_TRY(hipStreamWaitEvent(s, e->ev_up[c], 0));
         double *base = (double *)(d_rec + (size_t)lo * itemsize);
         double *cx = base + off_x / 8, *cy = base + off_y / 8, *cz = ndim == 3 ? base + off_z / 8 : nullptr;
@@ -331,24 +328,15 @@ int bfgx_baryonify_snapshot_records(const bfgx_grid_catalog *halos, const bfgx_m
         HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
         if (cnt > 0) HIP_TRY(hipMemcpyAsync(dst + (size_t)lo * itemsize, d_rec + (size_t)lo * itemsize, (size_t)cnt * itemsize, hipMemcpyDeviceToHost, e->down));
     }
-    HIP_TRY(hipEventRecord(e->ev[2], s));
+    if (int rc = call.mark(2, s)) return rc;
     int64_t npairs = 0;
     const int rc_fin = snap_finish_stage(p, &npairs);
     HIP_TRY(hipStreamSynchronize(e->down));
     HIP_TRY(hipStreamSynchronize(e->up));
     if (rc_fin) return rc_fin;
-    if (C > 1) hout.commit();
-    float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
-    (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
-    (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
-    HIP_TRY(hipEventRecord(e->ev[0], e->down));
-    HIP_TRY(hipEventSynchronize(e->ev[0]));
-    (void)hipEventElapsedTime(&ms_d2h, e->ev[2], e->ev[0]);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_pairs = npairs; stats->ms_h2d = ms_h2d; stats->ms_kernels = ms_k < 0 ? 0 : ms_k; stats->ms_d2h = ms_d2h < 0 ? 0 : ms_d2h;
-    }
-    return BFGX_OK;
+    if (C > 1) call.commit();
+    if (int rc = call.mark(3, e->down)) return rc;
+    return call.finish(stats, nullptr, npairs);
 }
 
 int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bfgx_model *model, int32_t ndim, double L, double redshift, int64_t n,
@@ -378,22 +366,18 @@ int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bf
     const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
     if (b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return alloc_fail("map");
     hipStream_t s = p->stream;
-    DrainOnExit drain;
-    drain.s[0] = &p->stream; drain.s[1] = &e->up; drain.null_stream = (p->stream == nullptr);
-    GridHostCatalog &hc = e->hc;
-    HIP_TRY(hipEventRecord(e->ev[0], s));
-    if (int rc = hc.upload(halos, ndim, 0, s)) return rc;
-    HostSpan hin, hout;
-    hin.streams[0] = hout.streams[0] = &e->up; hin.streams[1] = hout.streams[1] = &p->stream;
-    (void)hin.open(records_in, rbytes, false, false);        // (large arrays are page-locked for the call; small ones go up from pageable memory)
-    (void)hout.open(map_out, mbytes, true, false);
+    OneShotCall call(&p->stream, e);
+    if (int rc = call.mark(0, s)) return rc;
+    if (int rc = e->hc.upload(halos, ndim, 0, s)) return rc;
+    (void)call.open_in(records_in, rbytes, false);           // (large arrays are page-locked for the call; small ones go up from pageable memory)
+    (void)call.open_out(map_out, mbytes, false);
     // the records go up on their own stream while the halo lists are built
     HIP_TRY(hipMemcpyAsync(b.edges.p, edges, ebytes, hipMemcpyHostToDevice, e->up));
     if (rbytes) HIP_TRY(hipMemcpyAsync(e->rec.p, records_in, rbytes, hipMemcpyHostToDevice, e->up));
     if (int rc = e->pools(1, 0)) return rc;
     HIP_TRY(hipEventRecord(e->ev_up[0], e->up));
-    HIP_TRY(hipEventRecord(e->ev[1], e->up));
-    if (int rc = snap_lists_stage(p, &hc.d)) return rc;
+    if (int rc = call.mark(1, e->up)) return rc;
+    if (int rc = snap_lists_stage(p, &e->hc.d)) return rc;
     HIP_TRY(hipStreamWaitEvent(s, e->ev_up[0], 0));
     const double *base = (const double *)e->rec.p;
     const int64_t stride = itemsize / 8;
@@ -408,20 +392,13 @@ int bfgx_baryonify_snapshot_records_map(const bfgx_grid_catalog *halos, const bf
     }
     if (int rc = snap_displace_deposit_stage(p, n, base + off_x / 8, base + off_y / 8, ndim == 3 ? base + off_z / 8 : nullptr,
                                              off_mass >= 0 ? base + off_mass / 8 : nullptr, stride, n_grid, (const double *)b.edges.p, (double *)b.map.p)) return rc;
-    HIP_TRY(hipEventRecord(e->ev[2], s));
+    if (int rc = call.mark(2, s)) return rc;
     HIP_TRY(hipMemcpyAsync(map_out, b.map.p, mbytes, hipMemcpyDeviceToHost, s));
     int64_t npairs = 0;
     if (int rc = snap_finish_stage(p, &npairs)) return rc;                      // (synchronises the stream: the map has arrived)
     HIP_TRY(hipStreamSynchronize(e->up));
     if (nanflag) return fail(BFGX_ERR_ASSERT, "If you want to make a map, provide a value for the particle mass");
-    float ms_h2d = 0, ms_k = 0;
-    (void)hipEventElapsedTime(&ms_h2d, e->ev[0], e->ev[1]);
-    (void)hipEventElapsedTime(&ms_k, e->ev[1], e->ev[2]);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_pairs = npairs; stats->ms_h2d = ms_h2d < 0 ? 0 : ms_h2d; stats->ms_kernels = ms_k < 0 ? 0 : ms_k;
-    }
-    return BFGX_OK;
+    return call.finish(stats, nullptr, npairs);              // (no third phase: the map comes back underneath snap_finish_stage)
 }
 
 }  // extern "C"

@@ -229,10 +229,7 @@ int bfgx_snapshot_pairs_finish(bfgx_pairs *h, double *x_out, double *y_out, doub
         for (int k = 0; k < h->sg.ndim; ++k) HIP_TRY(hipMemcpyAsync(dst[k], o[k].p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_pairs = h->total;
-    }
+    fill_stats(stats, nullptr, h->total, 0, 0, 0);
     return BFGX_OK;
 }
 

@@ -69,10 +69,10 @@ int bfgx_shell_profiles(const bfgx_catalog *cat, const bfgx_model *model, int64_
     bfgx_opts o = entry_opts(nullptr);
     o.device = device;
     std::lock_guard<std::mutex> lk(g_shells.mu);
-    DrainOnExit drain;
     ShellEntry *e = nullptr;
-    if (int rc = shell_begin(cat, model, nside, o, &e, drain)) return rc;
+    if (int rc = shell_begin(cat, model, nside, o, &e)) return rc;
     bfgx_plan *p = e->plan;
+    OneShotCall call(&p->stream, e);                 // (its streams are drained at scope exit)
     const size_t npx = (size_t)p->hpx.npix, cells = (size_t)cat->n * (size_t)nb, nmaps = g1 ? 3 : 1, nout = g1 ? 5 : 2;
     std::vector<double> hostlog;
     bfgx_catalog dcat;
@@ -114,12 +114,8 @@ int bfgx_shell_profiles_device(int32_t device, void *hip_stream, const bfgx_cata
     o.device = device;
     std::lock_guard<std::mutex> lk(g_shells.mu);
     ShellEntry *e = nullptr;
-    {
-        // no drain: the host entries leave the cached plan idle, and an earlier call of this entry is waited for on the device (below)
-        DrainOnExit none;
-        if (int rc = shell_begin(cat, model, nside, o, &e, none)) return rc;
-        none = DrainOnExit();
-    }
+    // no call scope (nothing is drained): the host entries leave the cached plan idle, and an earlier call of this entry is waited for on the device (below)
+    if (int rc = shell_begin(cat, model, nside, o, &e)) return rc;
     bfgx_plan *p = e->plan;
     hipStream_t s = (hipStream_t)hip_stream;
     StreamSwap swap(p, s);                       // K0 and the catalog copies of this call go to the caller's stream

@@ -76,6 +76,11 @@ GRID_PARAM_CASES = ['grid2d_param1_paint', 'grid2d_param2_paint', 'grid2d_param1
                     'grid3d_param2_paint']
 
 
+def phases_ok(stats):
+    """the three phase times of a one-shot entry's bfgx_stats: present, finite, never negative"""
+    return all(np.isfinite(stats[k]) and stats[k] >= 0 for k in ('ms_h2d', 'ms_kernels', 'ms_d2h'))
+
+
 def load_grid_golden(name):
     f = np.load(os.path.join(GOLDEN, name + '.npz'))
     g = {k: f[k] for k in f.files}

@@ -749,6 +749,7 @@ def test_grid_host_entry_in_plane_ranges_equals_one_pass(gpu, monkeypatch, ndim,
     """BaryonifyGrid.process() streams the map in ranges of whole block rows (upload, copy + gather, download overlapped; the first block
     row gathered last because the grid is periodic) == the one-pass route == the oracle; plans and device maps are cached between calls"""
     import baryonification_amd as bfg
+    from test_host_api import phases_ok
     c = _big_case(ndim, N, nh, 31)
     cat = c['cat']
     # halos on the first / last planes so that deposits cross the periodic face and the range boundaries
@@ -763,10 +764,18 @@ def test_grid_host_entry_in_plane_ranges_equals_one_pass(gpu, monkeypatch, ndim,
     runner = bfg.Runners.BaryonifyGrid(HCat, GMap, 6.0, model, verbose=False)
     monkeypatch.setenv('BFGX_NO_PIPELINE', '1')
     one = runner.process().copy()
+    st_one = dict(runner.last_stats)
     monkeypatch.delenv('BFGX_NO_PIPELINE')
     monkeypatch.setenv('BFGX_PIPE_CHUNKS', str(chunks))
     piped = runner.process().copy()
+    st = dict(runner.last_stats)
     again = runner.process().copy()                                     # warm: cached plan, pooled pinned result
+    # bfgx_stats of both routes: phases present and never negative, the sums those of the maps (an fp64 sum of N^ndim non-negative terms in
+    # another order: within N^ndim * 2^-53 relative, 1e-10 for the largest case here), the same pairs
+    for s_, res in ((st_one, one), (st, piped)):
+        assert phases_ok(s_), s_
+        assert np.isclose(s_['sum_in'], c['map'].sum(), rtol=1e-10) and np.isclose(s_['sum_out'], res.sum(), rtol=1e-10), s_
+    assert st['n_pairs'] == st_one['n_pairs'] > 0
     assert np.abs(piped - one).max() <= 1e-12 * np.abs(one).max() and np.abs(again - one).max() <= 1e-12 * np.abs(one).max()
     assert not np.array_equal(one, c['map']) and np.isclose(piped.sum(), c['map'].sum())
     cos = dict(c['cosmo'], w0=-1.0)                                     # the grid runners drop w0 (Map2DRunner.py:456-459)

@@ -137,6 +137,7 @@ def test_snapshot_records_entry_streamed_equals_columns(gpu, monkeypatch, ndim, 
     field untouched, the input catalog unchanged"""
     import baryonification_amd as bfg
     from baryonification_amd import synthetic as syn
+    from test_host_api import phases_ok
     rng = np.random.default_rng(70 + ndim)
     L, nh, npart, zr = 250.0, 1200, 200_003, 0.1
     M = (10 ** rng.uniform(12.8, 15.0, nh)).astype(np.float32).astype(np.float64)
@@ -160,6 +161,7 @@ def test_snapshot_records_entry_streamed_equals_columns(gpu, monkeypatch, ndim, 
     monkeypatch.setenv('BFGX_PIPE_CHUNKS', str(chunks))
     recs = runner.process()
     assert recs.dtype == Snap.cat.dtype and recs is not Snap.cat and runner.last_stats['n_pairs'] == n_cols > 1000
+    assert phases_ok(runner.last_stats), runner.last_stats
     def same(a, b):          # (a particle inside several balls sums their offsets in the order the LDS adds arrive: last bits differ run to run)
         return np.array_equal(np.isnan(a), np.isnan(b)) and np.nanmax(np.abs(a - b), initial=0.0) <= 1e-13 * L
     for k in ('x', 'y', 'z', 'M'):
@@ -168,6 +170,10 @@ def test_snapshot_records_entry_streamed_equals_columns(gpu, monkeypatch, ndim, 
     assert 0.01 < np.mean(recs['x'] != before['x']) < 0.99             # (2-D: projected balls cover most of the box)
     again = runner.process()                                           # warm call: cached plan and device buffer, pooled result
     assert same(again['x'], cols['x'])
+    monkeypatch.setenv('BFGX_NO_PIPELINE', '1')                        # the same entry in one piece: same positions, same pairs, sane phases
+    whole = runner.process()
+    monkeypatch.delenv('BFGX_NO_PIPELINE')
+    assert all(same(whole[k], cols[k]) for k in ('x', 'y', 'z', 'M')) and runner.last_stats['n_pairs'] == n_cols and phases_ok(runner.last_stats)
     # a catalog whose records the library cannot take as they are (a float32 field in front: 4-byte offsets) falls back to the columns
     odd = np.zeros(npart, dtype=[('tag', np.float32), ('M', np.float64), ('x', np.float64), ('y', np.float64), ('z', np.float64)])
     for k in ('M', 'x', 'y', 'z'):

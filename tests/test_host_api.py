@@ -12,6 +12,11 @@ from baryonification_amd.Runners._model import build_model
 from helpers import load_golden, product_runner
 
 
+def phases_ok(stats):
+    """the three phase times of a one-shot entry's bfgx_stats: present, finite, never negative"""
+    return all(np.isfinite(stats[k]) and stats[k] >= 0 for k in ('ms_h2d', 'ms_kernels', 'ms_d2h'))
+
+
 def test_package_surface_matches_reference_names():
     for name in ('BaryonifyShell', 'PaintProfilesShell', 'DefaultRunner'):
         assert hasattr(bfg.Runners, name) and hasattr(bfg, name)
@@ -344,8 +349,15 @@ def test_host_entry_in_band_ranges_equals_one_pass(gpu, case, monkeypatch):
     st = dict(runner.last_stats)
     monkeypatch.setenv('BFGX_NO_PIPELINE', '1')
     whole = runner.process()
+    st_whole = dict(runner.last_stats)
     monkeypatch.delenv('BFGX_NO_PIPELINE')
     assert np.isfinite(piped).all() and np.isclose(piped.sum(), hmap.sum(), rtol=1e-12) and np.isclose(st['sum_out'], st['sum_in'], rtol=1e-12)
+    # bfgx_stats of both routes: phases present and never negative, the sums those of the maps (an fp64 sum of npix positive terms in
+    # another order: within npix * 2^-53 relative, 3.5e-10 here), no pair count from the shell entry
+    for s_, res in ((st, piped), (st_whole, whole)):
+        assert phases_ok(s_), s_
+        assert np.isclose(s_['sum_in'], hmap.sum(), rtol=3.5e-10) and np.isclose(s_['sum_out'], res.sum(), rtol=3.5e-10), s_
+    assert np.isclose(st_whole['sum_out'], st_whole['sum_in'], rtol=1e-12) and st['n_pairs'] == st_whole['n_pairs'] == -1
     assert np.abs(piped - hmap).max() > 0
     assert np.abs(piped - whole).max() <= 1e-12 * hmap.max()
     if case in ('subpixel', 'polar'):
@@ -525,6 +537,68 @@ def test_round4_fault_sequence_small_arrays_are_never_page_locked_in_place(gpu, 
     pinned2, _, smallest2 = spans()
     assert pinned2 == pinned0
     assert smallest2 < 0 or smallest2 >= (32 << 20)                # whatever this process page-locked in place before owned its pages
+
+
+@pytest.mark.gpu
+def test_streamed_entries_alternate_in_one_process_on_one_call_scaffold(gpu, monkeypatch):
+    """The three streamed one-shot entries share one call scope (csrc/bfgx_oneshot.hpp: stream drain, page-locked views, phase events).  Two
+    rounds of shell -> grid -> records in one process, each forced onto small data with BFGX_PIPE_CHUNKS (staged through the library's
+    page-locked buffers): every result equals the same entry's one-pass result (BFGX_NO_PIPELINE) within the tolerance of that entry's own
+    streamed-against-one-pass test (1e-12 max|map|; 1e-13 L on positions), the warm second round allocates nothing on the device, and no
+    small array is page-locked in place.  NSIDE 128 in 4 ranges is the smallest shell map with nbands >= 2 * ranges to spare; the golden
+    grid (28^3: 4 block rows) is too small for three ranges, so the grid is the 64^3 case of test_grid_host_entry_in_plane_ranges_equals_one_pass
+    in 4 ranges; the records are the snap3d_baryonify golden in 3 chunks."""
+    import ctypes as C
+    from baryonification_amd import _lib
+    import helpers as H
+    from test_gpu_grid import _big_case
+    lib = _lib.load()
+
+    def spans():
+        a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        lib.bfgx_debug_host_spans(C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value
+    cat = syn.make_catalog(4000, seed=3, logM_lo=13.0, logM_hi=14.5)
+    z, M, r = syn.table_grid(cat, pad=1e-3)
+    model = bfg.Profiles.Baryonification2D(None, None, bfg.utils.Cosmology.from_dict(syn.COSMO), epsilon_max=10.0)
+    model.set_table(z, M, r, syn.displacement_table(z, M, r))
+    Catalog = bfg.utils.HaloLightConeCatalog(ra=cat['ra'], dec=cat['dec'], M=cat['M'], z=cat['z'], cosmo=syn.COSMO)
+    shell = bfg.Runners.BaryonifyShell(Catalog, bfg.utils.LightconeShell(map=syn.make_map(128), cosmo=syn.COSMO), 10.0, model, verbose=False)
+    shell.acc_f64 = True
+    c = _big_case(3, 64, 700, 31)
+    gmodel = bfg.Profiles.Baryonification2D(None, None, bfg.utils.Cosmology.from_dict(c['cosmo']), epsilon_max=8.0)
+    gmodel.set_table(c['z'], c['Mt'], c['r'], c['d'])
+    HCat = bfg.utils.HaloNDCatalog(x=c['cat']['x'], y=c['cat']['y'], z=c['cat']['z'], M=c['cat']['M'], redshift=c['redshift'], cosmo=c['cosmo'])
+    grid = bfg.Runners.BaryonifyGrid(HCat, bfg.utils.GriddedMap(map=c['map'], redshift=c['redshift'], bins=c['bins'], cosmo=c['cosmo']), 6.0,
+                                     gmodel, verbose=False)
+    g = H.load_snapshot_golden('snap3d_baryonify')
+    records = H.snapshot_product_runner(g)
+    records.use_records = True
+    positions = lambda new_cat: np.stack([new_cat[k] for k in ('x', 'y', 'z')], axis=1)
+    entries = [(shell, '4', np.asarray, None), (grid, '4', np.asarray, None), (records, '3', positions, 1e-13 * g['L'])]
+    monkeypatch.setenv('BFGX_NO_PIPELINE', '1')
+    want = [get(runner.process()).copy() for runner, _, get, _ in entries]
+    monkeypatch.delenv('BFGX_NO_PIPELINE')
+    assert all(np.abs(w - np.asarray(src)).max() > 0 for w, src in ((want[0], shell.LightconeShell.map), (want[1], c['map'])))
+    (pinned0, staged0), allocs = spans(), None
+    for rnd in range(2):
+        for (runner, chunks, get, tol), ref in zip(entries, want):
+            monkeypatch.setenv('BFGX_PIPE_CHUNKS', chunks)
+            got = get(runner.process())
+            print(rnd, type(runner).__name__, 'max|streamed - one pass|', np.nanmax(np.abs(got - ref)), 'max|one pass|', np.nanmax(np.abs(ref)))
+            assert np.array_equal(np.isnan(got), np.isnan(ref)), (rnd, type(runner).__name__)
+            assert np.nanmax(np.abs(got - ref)) <= (tol if tol is not None else 1e-12 * np.abs(ref).max()), (rnd, type(runner).__name__)
+        if rnd == 0:
+            allocs = lib.bfgx_debug_alloc_count()
+    monkeypatch.delenv('BFGX_PIPE_CHUNKS')
+    assert lib.bfgx_debug_alloc_count() == allocs                  # the warm round: cached plans, pooled device buffers
+    pinned1, staged1 = spans()
+    print('allocs', allocs, lib.bfgx_debug_alloc_count(), 'pinned', pinned0, pinned1, 'staged', staged0, staged1)
+    assert pinned1 == pinned0, "a small array was page-locked in place"
+    # six streamed calls, each with its small input staged (the runners' results live in pooled page-locked memory, which is used as it
+    # is): none took the one-pass route
+    assert staged1 >= staged0 + 6
+    lib.bfgx_cache_clear()
 
 
 def test_which_route_a_callable_model_takes():
