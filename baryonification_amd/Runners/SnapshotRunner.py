@@ -9,16 +9,19 @@ A model that is a plain Python callable (displacement(r, M, a), no table) is tab
 `bfgx_exact = True`: then it is called once per halo, every halo, on the distances of the particles within R_q (ascending particle
 index within a halo), with M = cat['M'][j] and a = 1/(1+z), as the reference's loop does (:228, :245; bfgx_snapshot_pairs_*,
 csrc/bfgx_snapshot_pairs.hpp).
+
+`MeasureProfilesSnapshot` (not in the reference) measures what baryonification is defined by: the radial profile of the particles around the
+halos, before and after (csrc/bfgx_snapshot_stack.hpp).
 """
 import ctypes as C
 
 import numpy as np
 
 from .. import _lib
-from ..utils.cosmology import MassDef
-from ._model import build_model, process_snapshot_exact, wants_exact
+from ..utils.cosmology import Cosmology, MassDef, cosmo_to_dict, massdef_to_tuple
+from ._model import _placeholder_model, build_model, process_snapshot_exact, wants_exact
 
-__all__ = ['DefaultRunnerSnapshot', 'BaryonifySnapshot']
+__all__ = ['DefaultRunnerSnapshot', 'BaryonifySnapshot', 'MeasureProfilesSnapshot', 'SnapshotProfiles']
 
 
 class DefaultRunnerSnapshot(object):
@@ -146,3 +149,186 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
             new_cat['z'] = oz
         del keep, cols
         return new_cat
+
+
+MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
+
+
+def _is_cuda_tensor(x):
+    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
+
+
+class SnapshotProfiles(object):
+    """What MeasureProfilesSnapshot.process() returns.  Per (halo, bin), shape (n_halo, nb): `npart`, the particles with
+    r_edges[b] <= x < r_edges[b + 1] inside the halo's ball, and `sum`, the sum of their finite weights (None for a counts-only
+    measurement: `density`, `enclosed` and `stack` then work on the counts).  numpy arrays, or torch tensors on the particles' device when
+    the particles were CUDA tensors.  `R` is the comoving halo radius R_com = mass_def.get_radius(M, a) / a and `R_q` =
+    clip(epsilon_max R_com, 0, L / 2) the radius of the ball, per halo (numpy; NaN and 0 for an invalid halo); x is the comoving distance,
+    or distance / R_com when `scaled`."""
+
+    def __init__(self, r_edges, npart, sum=None, scaled=False, ndim=3, R=None, R_q=None):
+        self.r_edges, self.scaled, self.ndim = np.asarray(r_edges, dtype=np.float64), bool(scaled), int(ndim)
+        self.npart, self.sum = npart, sum
+        self.R, self.R_q = R, R_q
+
+    def _like(self, a):
+        """a host array as the kind of array the measurement came back as"""
+        if isinstance(self.npart, np.ndarray):
+            return a
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.npart.device)
+
+    @staticmethod
+    def _ratio(s, n):
+        """s / n, NaN where n is 0"""
+        if isinstance(s, np.ndarray):
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return np.where(n != 0, s / n, np.nan)
+        return (s / n).masked_fill(n == 0, float('nan'))
+
+    def _total(self):
+        if self.sum is not None:
+            return self.sum
+        return self.npart.astype(np.float64) if isinstance(self.npart, np.ndarray) else self.npart.double()
+
+    @property
+    def mean(self):
+        """sum / npart, NaN where npart is 0 (None for a counts-only measurement)"""
+        return None if self.sum is None else self._ratio(self.sum, self.npart)
+
+    @property
+    def volume(self):
+        """The part of bin b's spherical shell (3-D; annulus in 2-D) that lies inside the halo's ball:
+        V(min(hi s, R_q)) - V(min(lo s, R_q)), s = R_com when scaled, else 1, V = 4 pi r^3 / 3 or pi r^2."""
+        s = np.asarray(self.R, dtype=np.float64)[:, None] if self.scaled else 1.0
+        with np.errstate(invalid='ignore'):
+            r = np.minimum(self.r_edges[None, :] * s, np.asarray(self.R_q, dtype=np.float64)[:, None])
+        V = 4.0 * np.pi / 3.0 * r ** 3 if self.ndim == 3 else np.pi * r ** 2
+        return self._like(V[:, 1:] - V[:, :-1])
+
+    @property
+    def density(self):
+        """sum / volume (NaN where the bin lies outside the ball)"""
+        return self._ratio(self._total(), self.volume)
+
+    @property
+    def enclosed(self):
+        """cumsum(sum, axis=1): the sum over the bins up to b.  This is M(< r_edges[b + 1]) only when r_edges[0] == 0."""
+        return self._total().cumsum(1)
+
+    def stack(self, select=None, weights=None):
+        """The halo-weighted profile over the chosen halos per bin: 'mean' = sum_j w_j sum[j] / sum_j w_j npart[j] and 'density' =
+        sum_j w_j sum[j] / sum_j w_j volume[j] (NaN where the denominator is 0).  select: anything that indexes the halo axis; weights:
+        one per chosen halo (default 1)."""
+        sel = slice(None) if select is None else select
+        host = isinstance(self.npart, np.ndarray)
+        s, vol = self._total()[sel], self.volume[sel]
+        n = self.npart[sel].astype(np.float64) if host else self.npart[sel].to(s.dtype)
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64) if host else weights
+            s, n, vol = s * w[:, None], n * w[:, None], vol * w[:, None]
+        nansum = (lambda v: np.nansum(v, axis=0)) if host else (lambda v: v.nansum(0))
+        out = {'density': self._ratio(s.sum(0), nansum(vol))}              # (an invalid halo has an all-zero row and no volume)
+        if self.sum is not None:
+            out['mean'] = self._ratio(s.sum(0), n.sum(0))
+        return out
+
+
+class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
+    """Measures halo-centred radial profiles of the particles of a snapshot: the box counterpart of MeasureProfilesShell.  For halo j the
+    particles within BaryonifySnapshot's ball -- minimum-image distance d <= R_q = clip(epsilon_max R_com, 0, L / 2), R_com the comoving
+    radius of `mass_def` -- are binned in x = d (comoving Mpc) or, scaled=True, x = d / R_com: bin b holds r_edges[b] <= x < r_edges[b + 1].
+    A particle adds 1 to npart[j, b] and its weight (the 'M' column by default) to sum[j, b].  fp64 throughout; counts are exact.
+    `model` must be None: there is nothing to tabulate.  `process(cat=runner.process())` of a BaryonifySnapshot runner measures the
+    displaced particles with the same object."""
+
+    def __init__(self, HaloNDCatalog, ParticleSnapshot, epsilon_max, model=None, mass_def=MassDef(200, 'critical'), verbose=True,
+                 KDTree_kwargs={}, *, r_edges, scaled=False):
+        if model is not None:
+            raise TypeError("MeasureProfilesSnapshot takes model=None: it measures the particles, there is nothing to tabulate")
+        super().__init__(HaloNDCatalog, ParticleSnapshot, epsilon_max, model, mass_def, verbose, KDTree_kwargs)
+        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 2:
+            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
+        if edges.size - 1 > MAX_PROFILE_BINS:
+            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
+        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
+        self.r_edges = edges
+        self.scaled = bool(scaled)
+
+    def _cosmo_dict(self):
+        cosmo = dict(cosmo_to_dict(self.cosmo))
+        cosmo['w0'] = -1.0                                            # as BaryonifySnapshot: SnapshotRunner.py:204-207 does not pass w0
+        return cosmo
+
+    def radii(self):
+        """(R_com, R_q) per halo on the host: the comoving radius of the mass definition and the radius of the ball (SnapshotRunner.py:219-222);
+        NaN and 0 for a halo the measurement skips (M not positive / finite, a non-finite coordinate)."""
+        hcat = self.HaloNDCatalog.cat
+        M = np.asarray(hcat['M'], dtype=np.float64)
+        ok = (M > 0) & np.isfinite(M)
+        for k in ('x', 'y') if self.ParticleSnapshot.is2D else ('x', 'y', 'z'):
+            ok &= np.isfinite(np.asarray(hcat[k], dtype=np.float64))
+        a = 1.0 / (1.0 + float(self.HaloNDCatalog.redshift))
+        R = np.full(M.size, np.nan)
+        if ok.any():
+            R[ok] = MassDef(*massdef_to_tuple(self.mass_def)).get_radius(Cosmology.from_dict(self._cosmo_dict()), M[ok], a) / a
+        with np.errstate(invalid='ignore'):
+            R_q = np.where(ok, np.minimum(np.maximum(float(self.epsilon_max) * R, 0.0), float(self.ParticleSnapshot.L) / 2), 0.0)
+        return R, R_q
+
+    def process(self, cat=None, weights=None):
+        """SnapshotProfiles of the snapshot's own particles, or of `cat`: a structured array with the snapshot's fields (what
+        BaryonifySnapshot.process() returns), or a tuple (x, y[, z]) of 1-D CUDA float64 torch tensors, which are measured where they lie
+        (on torch's current stream) with tensors on that device as the result.  weights: None = the 'M' column of what is measured
+        (device tensors: counts only), an array / tensor of one weight per particle, or False = counts only."""
+        snap = self.ParticleSnapshot
+        is2D = snap.is2D
+        ndim = 2 if is2D else 3
+        hcat = self.HaloNDCatalog.cat
+        model, keep = _placeholder_model(self, self._cosmo_dict())
+        c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if is2D else hcat['z'])
+        edges, nb, n = self.r_edges, self.r_edges.size - 1, int(hcat.size)
+        L, zr = float(snap.L), float(self.HaloNDCatalog.redshift)
+        lib = _lib.load()
+        if isinstance(cat, (tuple, list)):
+            import torch
+            cols = list(cat)
+            if len(cols) != ndim or not all(_is_cuda_tensor(t) for t in cols):
+                raise ValueError("device particles are a tuple of %d CUDA tensors (x, y%s)" % (ndim, '' if is2D else ', z'))
+            dev, npart = cols[0].device, cols[0].numel()
+            if weights is not None and weights is not False:
+                if not _is_cuda_tensor(weights):
+                    raise ValueError("the weights of device particles must be a CUDA tensor")
+                cols.append(weights)
+            for t in cols:
+                if t.dtype != torch.float64 or t.dim() != 1 or t.numel() != npart or t.device != dev:
+                    raise ValueError("device particles and weights must be 1-D float64 tensors of one length on one device")
+            cols = [t.contiguous() for t in cols]
+            has_w = len(cols) > ndim
+            out_n = torch.empty((n, nb), dtype=torch.int64, device=dev)
+            out_s = torch.empty((n, nb), dtype=torch.float64, device=dev) if has_w else None
+            ptr = [C.c_void_p(t.data_ptr()) for t in cols[:ndim]] + [None] * (3 - ndim)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
+            _lib.check(lib.bfgx_snapshot_profiles_device(dev.index or 0, stream, C.byref(c), C.byref(model), ndim, L, zr, npart, ptr[0], ptr[1], ptr[2],
+                                                         C.c_void_p(cols[ndim].data_ptr()) if has_w else None, nb, edges.ctypes.data, int(self.scaled),
+                                                         C.c_void_p(out_n.data_ptr()), C.c_void_p(out_s.data_ptr()) if has_w else None))
+        else:
+            rec = snap.cat if cat is None else cat
+            x, y = _lib.f8(rec['x']), _lib.f8(rec['y'])
+            z = None if is2D else _lib.f8(rec['z'])
+            if weights is False:
+                w = None
+            else:
+                w = _lib.f8(rec['M'] if weights is None else weights).reshape(-1)
+                if w.size != x.size:
+                    raise ValueError("weights must hold one weight per particle (%d): got %d" % (x.size, w.size))
+            s = _lib.bfgx_snapshot(ndim, 0, x.size, x.ctypes.data, y.ctypes.data, None if is2D else z.ctypes.data, L, zr)
+            out_n = np.empty((n, nb), dtype=np.int64)                 # (every cell is written by the library: no zero-fill)
+            out_s = None if w is None else np.empty((n, nb), dtype=np.float64)
+            _lib.check(lib.bfgx_snapshot_profiles(C.byref(c), C.byref(model), C.byref(s), None if w is None else w.ctypes.data, nb, edges.ctypes.data,
+                                                  int(self.scaled), int(self.device), out_n.ctypes.data, None if w is None else out_s.ctypes.data))
+        del keep, ckeep
+        R, R_q = self.radii()
+        return SnapshotProfiles(edges.copy(), out_n, out_s, self.scaled, ndim, R, R_q)

@@ -41,6 +41,7 @@
 #include "bfgx_sht.hpp"
 #include "bfgx_hpx.hpp"
 #include "bfgx_stack.hpp"
+#include "bfgx_snapshot_stack.hpp"
 
 using namespace bfgx;
 
@@ -2120,6 +2121,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // halo-centred radial profiles of shell maps (MeasureProfilesShell)
 #include "bfgx_stack_api.inc"
+
+// halo-centred radial profiles of particle snapshots (MeasureProfilesSnapshot)
+#include "bfgx_snapshot_stack_api.inc"
 
 extern "C" void bfgx_cache_clear(void)
 {

@@ -23,6 +23,48 @@ int snap_pairs_cells(int ndim, int64_t np)
     return std::max(1, std::min(nc, ndim == 3 ? 512 : 8192));
 }
 
+// The particles of a snapshot binned into the periodic cell grid of g: per-cell counts -> exclusive scan (start[c] .. start[c + 1] are
+// cell c's slots) -> stable radix sort of (cell, index), so that a cell lists its particles in ascending index.  Everything is enqueued on
+// st; the stream is synchronised once, for the [0, L] check.  x / y / z are device pointers.  No particles: every start is 0.
+struct SnapBins {
+    DevBuf cell[2], idx[2], ccount, cstart, flags, tmp;
+    const uint32_t *sorted_idx = nullptr;         // particle index per slot
+    const int32_t *start() const { return (const int32_t *)cstart.p; }
+};
+
+int snap_bin_particles(hipStream_t st, const SnapGeom &g, int64_t np, const double *x, const double *y, const double *z, SnapBins &b)
+{
+    const size_t npb = (size_t)std::max<int64_t>(np, 1);
+    if (b.cell[0].alloc(4 * npb) || b.cell[1].alloc(4 * npb) || b.idx[0].alloc(4 * npb) || b.idx[1].alloc(4 * npb) ||
+        b.ccount.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || b.cstart.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || b.flags.alloc(sizeof(int32_t)))
+        return alloc_fail("particle bins");
+    HIP_TRY(hipMemsetAsync(b.ccount.p, 0, sizeof(int32_t) * ((size_t)g.ncell + 1), st));
+    HIP_TRY(hipMemsetAsync(b.flags.p, 0, sizeof(int32_t), st));
+    b.sorted_idx = (const uint32_t *)b.idx[0].p;
+    if (np == 0) {
+        HIP_TRY(hipMemsetAsync(b.cstart.p, 0, sizeof(int32_t) * ((size_t)g.ncell + 1), st));
+        return BFGX_OK;
+    }
+    int32_t hflags = 0;
+    hipLaunchKernelGGL(snap_pairs_bin_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, g, np, x, y, z, (uint32_t *)b.cell[0].p,
+                       (uint32_t *)b.idx[0].p, (int32_t *)b.ccount.p, (int32_t *)b.flags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&hflags, b.flags.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hflags & 2) return fail(BFGX_ERR_INVALID, "particle coordinates must lie in [0, L] (scipy's periodic KDTree refuses such data too)");
+    size_t b1 = 0, b2 = 0;
+    hipcub::DoubleBuffer<uint32_t> kb((uint32_t *)b.cell[0].p, (uint32_t *)b.cell[1].p), vb((uint32_t *)b.idx[0].p, (uint32_t *)b.idx[1].p);
+    int end_bit = 1;
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)g.ncell) ++end_bit;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, kb, vb, (int64_t)np, 0, end_bit, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t *)b.ccount.p, (int32_t *)b.cstart.p, (int)g.ncell + 1, st));
+    if (b.tmp.alloc(std::max(b1, b2))) return alloc_fail("sort workspace");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(b.tmp.p, b1, kb, vb, (int64_t)np, 0, end_bit, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(b.tmp.p, b2, (const int32_t *)b.ccount.p, (int32_t *)b.cstart.p, (int)g.ncell + 1, st));
+    b.sorted_idx = vb.Current();
+    return BFGX_OK;
+}
+
 template <int MODE>
 int launch_snap_pairs(bfgx_pairs *h, int64_t j0, int64_t j1, const double *vals, double *out)
 {
@@ -93,41 +135,16 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
     if (h->srecs.alloc(sizeof(SnapHaloRec) * (size_t)std::max<int64_t>(nh, 1)) || h->counts.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nh, 1)) ||
         h->off.alloc(sizeof(int64_t) * ((size_t)nh + 1)) || h->sacc.alloc(3 * sizeof(double) * (size_t)std::max<int64_t>(np, 1)))
         return bail(alloc_fail("halo records"));
-    // particle binning: per-cell counts -> exclusive scan -> stable radix sort of (cell, index): a cell's particles in ascending index
-    DevBuf cell[2], idx[2], ccount, cstart, flags, tmp;
-    const size_t npb = (size_t)std::max<int64_t>(np, 1);
-    if (cell[0].alloc(4 * npb) || cell[1].alloc(4 * npb) || idx[0].alloc(4 * npb) || idx[1].alloc(4 * npb) ||
-        ccount.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || cstart.alloc(sizeof(int32_t) * ((size_t)g.ncell + 1)) || flags.alloc(sizeof(int32_t)))
-        return bail(alloc_fail("particle bins"));
-    HIP_TRY(hipMemsetAsync(ccount.p, 0, sizeof(int32_t) * ((size_t)g.ncell + 1), st));
-    HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(h->sacc.p, 0, 3 * sizeof(double) * npb, st));
+    HIP_TRY(hipMemsetAsync(h->sacc.p, 0, 3 * sizeof(double) * (size_t)std::max<int64_t>(np, 1), st));
     if (nh > 0) {
         hipLaunchKernelGGL(snap_pairs_prep_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, st, h->smodel, g, nh, (const double *)hcol[0].p,
                            (const double *)hcol[1].p, (const double *)hcol[2].p, (const double *)hcol[3].p, (SnapHaloRec *)h->srecs.p);
         HIP_TRY(hipGetLastError());
     }
-    int32_t hflags = 0;
-    const uint32_t *sorted_idx = (const uint32_t *)idx[0].p;
-    if (np > 0) {
-        hipLaunchKernelGGL(snap_pairs_bin_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, g, np, (const double *)h->sxyz[0].p,
-                           (const double *)h->sxyz[1].p, (const double *)h->sxyz[2].p, (uint32_t *)cell[0].p, (uint32_t *)idx[0].p,
-                           (int32_t *)ccount.p, (int32_t *)flags.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&hflags, flags.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (hflags & 2) return bail(fail(BFGX_ERR_INVALID, "particle coordinates must lie in [0, L] (scipy's periodic KDTree refuses such data too)"));
-        size_t b1 = 0, b2 = 0;
-        hipcub::DoubleBuffer<uint32_t> kb((uint32_t *)cell[0].p, (uint32_t *)cell[1].p), vb((uint32_t *)idx[0].p, (uint32_t *)idx[1].p);
-        int end_bit = 1;
-        while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)g.ncell) ++end_bit;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, kb, vb, (int)np, 0, end_bit, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t *)ccount.p, (int32_t *)cstart.p, (int)g.ncell + 1, st));
-        if (tmp.alloc(std::max(b1, b2))) return bail(alloc_fail("sort workspace"));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, b1, kb, vb, (int)np, 0, end_bit, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, b2, (const int32_t *)ccount.p, (int32_t *)cstart.p, (int)g.ncell + 1, st));
-        sorted_idx = vb.Current();
-    }
+    SnapBins bins;
+    if (int rc = snap_bin_particles(st, g, np, (const double *)h->sxyz[0].p, (const double *)h->sxyz[1].p, (const double *)h->sxyz[2].p, bins)) return bail(rc);
+    const DevBuf &cstart = bins.cstart;
+    const uint32_t *sorted_idx = bins.sorted_idx;
     const unsigned wblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nh, 8192));
     const double *px = (const double *)h->sxyz[0].p, *py = (const double *)h->sxyz[1].p, *pz = (const double *)h->sxyz[2].p;
     if (nh > 0) {

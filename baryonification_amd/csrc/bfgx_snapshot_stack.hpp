@@ -1,0 +1,161 @@
+// bfgx_snapshot_stack.hpp -- halo-centred radial profiles of particle snapshots (MeasureProfilesSnapshot): the box counterpart of
+// bfgx_stack.hpp.
+//
+// Per halo j the particles of BaryonifySnapshot's query ball -- minimum-image separation d with the roundings of the reference's numpy
+// (snap_sep), d^2 <= R_q^2, R_q = clip(epsilon_max R_j / a, 0, L / 2) (snap_pairs_prep_kernel) -- are binned in x = d (comoving Mpc) or,
+// scaled, x = d / (R_j / a): a particle falls into bin b iff edges[b] <= x < edges[b + 1], adds 1 to npart[j, b] and, when its weight is
+// finite, its weight to sum[j, b].
+//
+// The particles are binned into the periodic cell grid of the per-pair route (snap_bin_particles: count, scan, stable sort by cell) and
+// gathered into cell order once (snap_stack_gather_kernel).  The cells of a halo's cube along the LAST axis are consecutive in the cell
+// index, so one (cx[, cy]) column of the cube is one contiguous run of sorted particles -- two where the column wraps around the box.
+//
+//   snap_stack_kernel   one workgroup per halo (grid-stride over halos).  256 columns at a time: thread t looks up the one or two runs of
+//                       column t, a workgroup scan turns the run lengths into the prefix of their concatenation, and thread t takes
+//                       particles t, t + 256, ... of it: lanes map to particles, consecutive lanes read consecutive records, and no
+//                       lane waits behind the fullest cell.  The (at most) 64 bins of the halo live in LDS while the particles stream
+//                       by: fp64 LDS adds (ds_add_f64, -munsafe-fp-atomics) for the sums, 32-bit LDS adds for the counts (a particle
+//                       is in a halo's ball at most once, R_q <= L / 2, so a count stays below the 2^32 particles of a call); when
+//                       the halo is done thread b stores bin b of each output once.  No global atomics and no zero-fill: every
+//                       (halo, bin) cell is written exactly once, also for invalid halos and halos without particles.  Counts are
+//                       exact and reproducible; fp64 throughout.
+#pragma once
+#include "bfgx_snapshot_pairs.hpp"
+#include "bfgx_stack.hpp"
+
+namespace bfgx {
+
+constexpr int kSnapStackThreads = 256;
+constexpr int kSnapStackSlots = 2 * kSnapStackThreads;       // two runs per column: a column that wraps around the box
+
+struct SnapStackArgs {
+    const double *x, *y, *z, *w;              // particle records in cell order (w == nullptr: counts only)
+    const uint32_t *cell_start;               // ncell + 1 exclusive prefix of the per-cell counts (32-bit sums, read unsigned)
+    const double *M;                          // halo masses (the scaled abscissa needs R_j)
+    const double *edges;                      // nb + 1 ascending bin edges
+    int32_t nb, scaled;
+    int64_t *npart;                           // [nhalo][nb]
+    double *sum;                              // [nhalo][nb], nullptr without weights
+};
+
+__global__ void __launch_bounds__(256)
+snap_stack_gather_kernel(int64_t np, const uint32_t *__restrict__ idx, const double *__restrict__ x, const double *__restrict__ y,
+                         const double *__restrict__ z, const double *__restrict__ w, double *__restrict__ xs, double *__restrict__ ys,
+                         double *__restrict__ zs, double *__restrict__ ws)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= np) return;
+    const uint32_t i = idx[s];
+    xs[s] = x[i];
+    ys[s] = y[i];
+    if (z) zs[s] = z[i];
+    if (w) ws[s] = w[i];
+}
+
+__device__ inline uint32_t wave_scan_incl_u32(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int s = 1; s < kWave; s <<= 1) {
+        const uint32_t u = __shfl_up(v, s, kWave);
+        if (lane >= s) v += u;
+    }
+    return v;
+}
+
+struct SnapStackLds {
+    uint32_t prefix[kSnapStackSlots];         // exclusive prefix of the run lengths of this round
+    uint32_t start[kSnapStackSlots];          // first sorted particle of each run
+    double sum[kStackMaxBins];
+    unsigned int n[kStackMaxBins];
+    uint32_t wtot[kSnapStackThreads / kWave];
+    double edges[kStackEdgeLds];              // the edges padded with +inf to a power of two: a branch-free search
+};
+
+template <int DIM, bool WEIGHTS>
+__global__ void __launch_bounds__(kSnapStackThreads)
+snap_stack_kernel(SnapGeom g, Background bg, bfgx_massdef md, int64_t nh, const SnapHaloRec *__restrict__ recs, SnapStackArgs a)
+{
+    __shared__ SnapStackLds S;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+    for (int i = tid; i < kStackEdgeLds; i += kSnapStackThreads) S.edges[i] = i <= a.nb ? a.edges[i] : __builtin_inf();
+    const int nb = a.nb, nc = g.nc;
+    for (int64_t j = blockIdx.x; j < nh; j += gridDim.x) {                  // (every branch on r or j below is uniform over the workgroup)
+        const SnapHaloRec &r = recs[j];
+        if (tid < kStackMaxBins) { S.sum[tid] = 0.0; S.n[tid] = 0u; }
+        __syncthreads();
+        const double e0 = S.edges[0];
+        // x = d / (R_j / a) or d: R_j / a as the prep kernel's R_q has it, before epsilon_max and the clipping
+        const double den = (a.scaled && r.valid) ? dev_radius(bg, md, a.M[j], g.a) / g.a : 1.0;
+        const int nlast = r.cn[DIM - 1], clast = r.clo[DIM - 1];
+        const int ncol = r.valid ? ((DIM == 3) ? r.cn[0] * r.cn[1] : r.cn[0]) : 0;
+        for (int base = 0; base < ncol; base += kSnapStackThreads) {
+            const int col = base + tid;
+            uint32_t sA = 0, cA = 0, sB = 0, cB = 0;
+            if (col < ncol) {
+                int64_t row;                                                    // cell index of the column's cell 0 on the last axis
+                if (DIM == 3) {
+                    const int iy = col % r.cn[1], ix = col / r.cn[1];
+                    int cx = r.clo[0] + ix; cx -= (cx >= nc) ? nc : 0;
+                    int cy = r.clo[1] + iy; cy -= (cy >= nc) ? nc : 0;
+                    row = ((int64_t)cx * nc + cy) * nc;
+                } else {
+                    int cx = r.clo[0] + col; cx -= (cx >= nc) ? nc : 0;
+                    row = (int64_t)cx * nc;
+                }
+                const int end = clast + nlast;                                  // (the whole axis: clast = 0, nlast = nc)
+                sA = a.cell_start[row + clast];
+                cA = a.cell_start[row + min(end, nc)] - sA;
+                if (end > nc) {                                                 // the column wraps: cells [0, end - nc) too
+                    sB = a.cell_start[row];
+                    cB = a.cell_start[row + (end - nc)] - sB;
+                }
+            }
+            const uint32_t mine = cA + cB;
+            const uint32_t incl = wave_scan_incl_u32(mine, lane);
+            if (lane == kWave - 1) S.wtot[wid] = incl;
+            __syncthreads();
+            uint32_t woff = 0, total = 0;
+#pragma unroll
+            for (int q = 0; q < kSnapStackThreads / kWave; ++q) {
+                const uint32_t t = S.wtot[q];
+                woff += (q < wid) ? t : 0u;
+                total += t;
+            }
+            const uint32_t excl = woff + incl - mine;
+            S.prefix[2 * tid] = excl; S.prefix[2 * tid + 1] = excl + cA;       // (an empty run shares its prefix with the next one: the search skips it)
+            S.start[2 * tid] = sA; S.start[2 * tid + 1] = sB;
+            __syncthreads();
+            for (uint64_t tt = tid; tt < total; tt += kSnapStackThreads) {
+                const uint32_t t = (uint32_t)tt;
+                int slot = 0;                                                   // largest slot with prefix[slot] <= t
+#pragma unroll
+                for (int st = kSnapStackSlots >> 1; st > 0; st >>= 1)
+                    if (S.prefix[slot + st] <= t) slot += st;
+                const int64_t p = (int64_t)S.start[slot] + (t - S.prefix[slot]);
+                double d[3];
+                const double d2 = snap_sep<DIM>(g, r, a.x, a.y, a.z, p, d);
+                if (!(d2 <= r.Rq2)) continue;
+                const double dd = __dsqrt_rn(d2);
+                const double xv = a.scaled ? dd / den : dd;
+                int b = 0;                                                      // largest b with edges[b] <= x (the padding is +inf)
+#pragma unroll
+                for (int st = kStackEdgeLds >> 1; st > 0; st >>= 1)
+                    if (S.edges[b + st] <= xv) b += st;
+                if (!(xv >= e0) || b >= nb) continue;                           // outside [edges[0], edges[nb]), or NaN
+                atomicAdd(&S.n[b], 1u);
+                if (WEIGHTS) {
+                    const double wv = a.w[p];
+                    if (isfinite(wv)) atomicAdd(&S.sum[b], wv);
+                }
+            }
+            __syncthreads();                                                    // the round's runs and the bins are settled
+        }
+        if (tid < nb) {
+            const int64_t o = j * nb + tid;
+            a.npart[o] = (int64_t)S.n[tid];
+            if (WEIGHTS) a.sum[o] = S.sum[tid];
+        }
+    }
+}
+
+}  // namespace bfgx

@@ -710,6 +710,29 @@ int  bfgx_shell_profiles_device(int32_t device, void *hip_stream, const bfgx_cat
                                 int32_t scaled, int64_t *npix_dev, double *sum_dev, int64_t *npix_shear_dev, double *sum_t_dev,
                                 double *sum_x_dev);
 
+/* ---- halo-centred radial profiles of particle snapshots (MeasureProfilesSnapshot) ------------------------------
+ * The box counterpart of bfgx_shell_profiles.  For halo j the particles of BaryonifySnapshot's query ball -- minimum-image separation d with
+ * the reference's roundings, d^2 <= R_q^2, R_q = clip(eps R_j / a, 0, L / 2), a = 1 / (1 + redshift), R_j / a the comoving radius of the mass
+ * definition (SnapshotRunner.py:217-228) -- are binned in x = d (comoving Mpc, the box's unit) or, scaled != 0, x = d / (R_j / a): a particle is
+ * in bin b iff r_edges[b] <= x < r_edges[b + 1]; nb + 1 finite ascending edges >= 0, 1 <= nb <= 64.  Outputs, row-major [n_halo][nb]:
+ *   npart   particles of the cell (a particle with a non-finite weight is counted)
+ *   sum     sum of the finite weights of the cell; NULL if and only if the weights are NULL (counts only)
+ * Every (halo, bin) cell is written exactly once -- also for invalid halos (M not positive / finite, a non-finite coordinate: all-zero rows), halos
+ * without particles and n_part = 0 -- so the outputs need no zero-fill; no atomics touch them: counts are exact and reproducible, sums are fp64 in
+ * an order that can differ from run to run.  halos_host as for bfgx_snapshot_pairs_begin (float32-valued columns; lnM / rmat / extra ignored);
+ * `model` carries the runner's cosmology (w0 = -1) / mass definition / epsilon_max, its 3-axis table must be valid and is ignored.  At most
+ * 2^31 - 1 halos and 2^32 - 1 particles.  Particles outside [0, L] (NaN included): BFGX_ERR_INVALID, as for bfgx_snapshot_pairs_begin.
+ *   bfgx_snapshot_profiles          everything in host memory: upload + kernels + download; nothing is in flight when it returns
+ *   bfgx_snapshot_profiles_device   particle columns x / y (/ z, ndim 3) / w [n_part] and the outputs are device pointers, the kernels run on
+ *                                   hip_stream; halo columns and r_edges are host arrays.  hip_stream is synchronised before the call returns
+ *                                   (once for the [0, L] check, once before the workspace is released): the outputs are complete on return */
+int  bfgx_snapshot_profiles(const bfgx_grid_catalog *halos_host, const bfgx_model *model, const bfgx_snapshot *snap_host,
+                            const double *w_host /* NULL: counts only */, int32_t nb, const double *r_edges, int32_t scaled, int32_t device,
+                            int64_t *npart /* [n_halo][nb] */, double *sum /* NULL iff w_host is NULL */);
+int  bfgx_snapshot_profiles_device(int32_t device, void *hip_stream, const bfgx_grid_catalog *halos_host, const bfgx_model *model, int32_t ndim,
+                                   double L, double redshift, int64_t n_part, const double *x_dev, const double *y_dev, const double *z_dev,
+                                   const double *w_dev, int32_t nb, const double *r_edges, int32_t scaled, int64_t *npart_dev, double *sum_dev);
+
 #ifdef __cplusplus
 }
 #endif
