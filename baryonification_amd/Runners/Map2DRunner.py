@@ -13,17 +13,22 @@ and applies the values (bfgx_grid_pairs_*, csrc/bfgx_grid_pairs.hpp); the host h
 (_model.EXACT_BATCH_PAIRS).
 
 Not built: `PaintProfilesAnisGrid` (:820-942).
+
+`MeasureProfilesGrid` (not in the reference) measures a gridded map where baryonification and painting are defined: the radial profile
+around the halos, with the constructor keywords, the (n_halo, n_bins) results and the `stack()` of MeasureProfilesShell and
+MeasureProfilesSnapshot (csrc/bfgx_grid_stack.hpp).
 """
 import ctypes as C
 
 import numpy as np
 
 from .. import _lib
-from ..utils.cosmology import MassDef
+from ..utils.cosmology import Cosmology, MassDef, massdef_to_tuple
 from ..utils.Tabulate import ParamTabulatedProfile
-from ._model import build_model, process_grid_exact, wants_exact
+from ._model import _placeholder_model, build_model, process_grid_exact, wants_exact
 
-__all__ = ['DefaultRunnerGrid', 'BaryonifyGrid', 'PaintProfilesGrid', 'regrid_pixels_2D', 'regrid_pixels_3D']
+__all__ = ['DefaultRunnerGrid', 'BaryonifyGrid', 'PaintProfilesGrid', 'MeasureProfilesGrid', 'GridProfiles', 'regrid_pixels_2D',
+           'regrid_pixels_3D']
 
 
 def _regrid(grid, pix_positions, pix_values, ndim, device=0):
@@ -202,3 +207,194 @@ class PaintProfilesGrid(DefaultRunnerGrid):
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep, cols, gkeep
         return new_map
+
+
+MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
+
+
+def _is_cuda_tensor(x):
+    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
+
+
+class GridProfiles(object):
+    """What MeasureProfilesGrid.process() returns.  Per (halo, bin), shape (n_halo, nb): `npix`, the pixels with a finite value and
+    r_edges[b] <= x < r_edges[b + 1] inside the halo's ball, and `sum`, the sum of their values; with a shear pair `npix_shear`, `sum_t`
+    and `sum_x` (None without one).  numpy arrays, or torch tensors on the maps' device when the maps were CUDA tensors.  `R` is the
+    comoving halo radius R_com = mass_def.get_radius(M, a) / a and `R_q` = clip(epsilon_max R_com, 0, max(bins) / 2) the radius of the ball,
+    per halo (numpy; NaN and 0 for an invalid halo); x is the comoving distance, or distance / R_com when `scaled`; `res` is the pixel size
+    and `ndim` the map's dimension."""
+
+    def __init__(self, r_edges, npix, sum, npix_shear=None, sum_t=None, sum_x=None, scaled=False, ndim=3, res=1.0, R=None, R_q=None):
+        self.r_edges, self.scaled, self.ndim, self.res = np.asarray(r_edges, dtype=np.float64), bool(scaled), int(ndim), float(res)
+        self.npix, self.sum = npix, sum
+        self.npix_shear, self.sum_t, self.sum_x = npix_shear, sum_t, sum_x
+        self.R, self.R_q = R, R_q
+
+    @staticmethod
+    def _ratio(s, n):
+        """s / n, NaN where n is 0"""
+        if isinstance(s, np.ndarray):
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return np.where(n != 0, s / n, np.nan)
+        return (s / n).masked_fill(n == 0, float('nan'))
+
+    @property
+    def mean(self):
+        """sum / npix, NaN where npix is 0"""
+        return self._ratio(self.sum, self.npix)
+
+    @property
+    def mean_t(self):
+        return None if self.sum_t is None else self._ratio(self.sum_t, self.npix_shear)
+
+    @property
+    def mean_x(self):
+        return None if self.sum_x is None else self._ratio(self.sum_x, self.npix_shear)
+
+    @property
+    def density(self):
+        """sum / (npix res^ndim), for maps that hold mass per pixel: the mean density of the counted pixels (NaN where npix is 0)"""
+        return self._ratio(self.sum, self.npix * self.res ** self.ndim)
+
+    @property
+    def enclosed(self):
+        """cumsum(sum, axis=1): the sum over the bins up to b.  This is M(< r_edges[b + 1]) only when r_edges[0] == 0."""
+        return self.sum.cumsum(1)
+
+    def stack(self, select=None, weights=None):
+        """The pixel-weighted profile over the chosen halos per bin, sum_j w_j sum[j] / sum_j w_j npix[j] (NaN where the denominator is 0):
+        a dict with 'mean', 'density' = 'mean' / res^ndim and, with shear, 'mean_t' and 'mean_x'.  select: anything that indexes the halo
+        axis; weights: one per chosen halo (default 1)."""
+        sel = slice(None) if select is None else select
+        out = {}
+        for name, s, n in (('mean', self.sum, self.npix), ('mean_t', self.sum_t, self.npix_shear), ('mean_x', self.sum_x, self.npix_shear)):
+            if s is None:
+                continue
+            s, n = s[sel], n[sel].to(s.dtype) if not isinstance(n, np.ndarray) else n[sel].astype(np.float64)
+            if weights is not None:
+                w = weights if not isinstance(s, np.ndarray) else np.asarray(weights, dtype=np.float64)
+                s, n = s * w[:, None], n * w[:, None]
+            out[name] = self._ratio(s.sum(0), n.sum(0))
+        out['density'] = out['mean'] / self.res ** self.ndim
+        return out
+
+
+class MeasureProfilesGrid(DefaultRunnerGrid):
+    """Measures halo-centred radial profiles of a gridded map: the regular-grid counterpart of MeasureProfilesShell and
+    MeasureProfilesSnapshot, for what BaryonifyGrid, PaintProfilesGrid and ParticleSnapshot.make_map produce.
+
+    Geometry.  map[i0, i1(, i2)] is the pixel whose centre is (x, y(, z)) = (bins[i0], bins[i1](, bins[i2])): where the grid runners put
+    a halo (inds[x_inds, :][:, y_inds]) and what make_map produces.  res = bins[1] - bins[0], period L = Npix res,
+    a = 1 / (1 + HaloNDCatalog.redshift); the cosmology is `_runner_cosmo()` (w0 is not passed on, as the grid runners have it).  A halo
+    is valid iff M > 0 and M and its coordinates in use are finite; R_com = mass_def.get_radius(M, a) / a and
+    R_q = clip(epsilon_max R_com, 0, max(bins) / 2), BaryonifyGrid's own clip.  Per axis Delta_k = bins[i_k] - x_k, minus L where
+    Delta_k > L / 2, plus L where Delta_k < -L / 2, and d = sqrt(sum Delta_k^2) in fp64: the TRUE minimum-image distance, deliberately not
+    the reference's cutout linspace(-N/2, N/2, N) res, which stretches radii by N / (N - 1) and swaps the sub-pixel dx and dy -- a
+    measurement inherits neither quirk.  A pixel belongs to halo j iff d^2 <= R_q^2 (R_q < L / 2: at most once).  x = d (comoving Mpc) or,
+    scaled=True, d / R_com; bin b holds r_edges[b] <= x < r_edges[b + 1].  A finite map value adds 1 to npix[j, b] and its value to
+    sum[j, b]; a non-finite one is not counted.  shear=(g1, g2), a pair of 2D maps of the GriddedMap's shape, adds for every pixel with
+    finite g1 and g2 and d > 0 one to npix_shear[j, b] and the flat-sky tangential and cross components about the halo,
+    gamma_t + i gamma_x = -(g1 + i g2) exp(-2 i phi) with phi measured from +x towards +y, to sum_t and sum_x: a mass peak has gamma_t > 0.
+    Invalid halos and halos without pixels get all-zero rows.  fp64 throughout; counts are exact.
+
+    `model` must be None: there is nothing to tabulate.  `m.process(map=BaryonifyGrid(...).process())` measures the displaced map with the
+    same object."""
+
+    def __init__(self, HaloNDCatalog, GriddedMap, epsilon_max, model=None, use_ellipticity=False,
+                 mass_def=MassDef(200, 'critical'), verbose=True, *, r_edges, scaled=False, shear=None):
+        if model is not None:
+            raise TypeError("MeasureProfilesGrid takes model=None: it measures the map, there is nothing to tabulate")
+        if use_ellipticity:
+            raise NotImplementedError("MeasureProfilesGrid measures in circular (spherical) bins: use_ellipticity is not implemented")
+        super().__init__(HaloNDCatalog, GriddedMap, epsilon_max, model, use_ellipticity, mass_def, verbose)
+        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 2:
+            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
+        if edges.size - 1 > MAX_PROFILE_BINS:
+            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
+        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
+        self.r_edges = edges
+        self.scaled = bool(scaled)
+        G = GriddedMap
+        bins = np.asarray(G.bins, dtype=np.float64)
+        if bins.ndim != 1 or bins.size != G.Npix:
+            raise ValueError("GriddedMap.bins must hold one pixel-centre coordinate per pixel (%d != %d)" % (bins.size, G.Npix))
+        res = bins[1] - bins[0]
+        if not (np.all(np.isfinite(bins)) and res > 0 and np.all(np.abs(np.diff(bins) - res) <= 1e-9 * res)):
+            raise ValueError("GriddedMap.bins must be uniformly spaced (to 1e-9 res): the minimum image needs a period")
+        self.shape = (int(G.Npix),) * (2 if G.is2D else 3)
+        self.shear = self._shear_pair(shear)
+
+    def _shear_pair(self, shear):
+        if shear is None:
+            return None
+        if len(shear) != 2:
+            raise ValueError("shear must be a pair of maps (g1, g2)")
+        if not self.GriddedMap.is2D:
+            raise ValueError("shear is the flat-sky pair of a 2D map: it is not accepted for 3D maps")
+        for g in shear:
+            if tuple(g.shape if _is_cuda_tensor(g) else np.shape(g)) != self.shape:
+                raise ValueError("shear maps must have the shape of the GriddedMap %s" % (self.shape,))
+        return tuple(shear)
+
+    def radii(self):
+        """(R_com, R_q) per halo on the host: the comoving radius of the mass definition and the radius of the ball; NaN and 0 for a halo
+        the measurement skips (M not positive / finite, a non-finite coordinate)."""
+        hcat = self.HaloNDCatalog.cat
+        M = np.asarray(hcat['M'], dtype=np.float64)
+        ok = (M > 0) & np.isfinite(M)
+        for k in ('x', 'y') if self.GriddedMap.is2D else ('x', 'y', 'z'):
+            ok &= np.isfinite(np.asarray(hcat[k], dtype=np.float64))
+        a = 1.0 / (1.0 + float(self.HaloNDCatalog.redshift))
+        R = np.full(M.size, np.nan)
+        if ok.any():
+            R[ok] = MassDef(*massdef_to_tuple(self.mass_def)).get_radius(Cosmology.from_dict(self._runner_cosmo()), M[ok], a) / a
+        half = float(np.max(np.asarray(self.GriddedMap.bins, dtype=np.float64))) / 2
+        with np.errstate(invalid='ignore'):
+            R_q = np.where(ok, np.minimum(np.maximum(float(self.epsilon_max) * R, 0.0), half), 0.0)
+        return R, R_q
+
+    def process(self, map=None, shear=None):
+        """GridProfiles of GriddedMap.map (and the constructor's shear pair), or of `map` / `shear` given here.  numpy in gives numpy out;
+        C-contiguous CUDA float64 torch tensors of the map's shape are measured where they lie (on torch's current stream) and the result
+        arrays are tensors on that device.  All inputs must be numpy arrays, or all CUDA tensors."""
+        G = self.GriddedMap
+        m = G.map if map is None else map
+        pair = self.shear if shear is None else self._shear_pair(shear)
+        maps = [m] + list(pair or ())
+        on_dev = [_is_cuda_tensor(x) for x in maps]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("the map and the shear pair must all be numpy arrays or all CUDA tensors")
+        hcat = self.HaloNDCatalog.cat
+        model, keep = _placeholder_model(self, self._runner_cosmo())
+        c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if G.is2D else hcat['z'])
+        grid, gkeep = self._grid()
+        edges, nb, n = self.r_edges, self.r_edges.size - 1, int(hcat.size)
+        lib = _lib.load()
+        if all(on_dev):
+            import torch
+            dev = maps[0].device
+            for x in maps:
+                if x.dtype != torch.float64 or tuple(x.shape) != self.shape or x.device != dev or not x.is_contiguous():
+                    raise ValueError("device maps must be C-contiguous float64 tensors of shape %s on one device" % (self.shape,))
+            outs = [torch.empty((n, nb), dtype=(torch.int64 if i in (0, 2) else torch.float64), device=dev) for i in range(5 if pair else 2)]
+            ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
+            optr = [C.c_void_p(o.data_ptr()) for o in outs] + [None] * (5 - len(outs))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
+            _lib.check(lib.bfgx_grid_profiles_device(dev.index or 0, stream, C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2],
+                                                     nb, edges.ctypes.data, int(self.scaled), *optr))
+        else:
+            maps = [_lib.f8(x) for x in maps]
+            for x in maps:
+                if x.shape != self.shape:
+                    raise ValueError("the map must have the shape of the GriddedMap %s: got %s" % (self.shape, x.shape))
+            outs = [np.empty((n, nb), dtype=(np.int64 if i in (0, 2) else np.float64)) for i in range(5 if pair else 2)]   # (every cell is written by the library)
+            ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
+            optr = [o.ctypes.data for o in outs] + [None] * (5 - len(outs))
+            _lib.check(lib.bfgx_grid_profiles(C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,
+                                              int(self.scaled), int(self.device), *optr))
+        del keep, ckeep, gkeep
+        R, R_q = self.radii()
+        return GridProfiles(edges.copy(), *outs, *([None] * (5 - len(outs))), scaled=self.scaled, ndim=len(self.shape), res=float(G.bins[1] - G.bins[0]),
+                            R=R, R_q=R_q)

@@ -266,6 +266,11 @@ SYMBOLS = {
     'bfgx_snapshot_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_grid_catalog), _P(bfgx_model), C.c_int32, C.c_double, C.c_double,
                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                 C.c_void_p, C.c_void_p]),
+    'bfgx_grid_profiles': (C.c_int, [_P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_grid_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_grid), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
 }
 
 _lib = None

@@ -42,6 +42,7 @@
 #include "bfgx_hpx.hpp"
 #include "bfgx_stack.hpp"
 #include "bfgx_snapshot_stack.hpp"
+#include "bfgx_grid_stack.hpp"
 
 using namespace bfgx;
 
@@ -2124,6 +2125,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // halo-centred radial profiles of particle snapshots (MeasureProfilesSnapshot)
 #include "bfgx_snapshot_stack_api.inc"
+
+// halo-centred radial profiles of gridded maps (MeasureProfilesGrid)
+#include "bfgx_grid_stack_api.inc"
 
 extern "C" void bfgx_cache_clear(void)
 {

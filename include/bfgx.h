@@ -733,6 +733,37 @@ int  bfgx_snapshot_profiles_device(int32_t device, void *hip_stream, const bfgx_
                                    double L, double redshift, int64_t n_part, const double *x_dev, const double *y_dev, const double *z_dev,
                                    const double *w_dev, int32_t nb, const double *r_edges, int32_t scaled, int64_t *npart_dev, double *sum_dev);
 
+/* ---- halo-centred radial profiles of gridded maps (MeasureProfilesGrid) ----------------------------------------
+ * The regular-grid counterpart of bfgx_shell_profiles and bfgx_snapshot_profiles.  map[i0, i1(, i2)] (C order, [npix]^ndim doubles) is the
+ * pixel whose centre is (x, y(, z)) = (bins[i0], bins[i1](, bins[i2])): where the grid runners put a halo, and what ParticleSnapshot.make_map
+ * produces.  res = bins[1] - bins[0]; the bins must be uniformly spaced (to 1e-9 res): the period is L = npix res.  a = 1 / (1 + redshift).
+ * A halo is valid iff M > 0 and M and its coordinates in use are finite; R_com = radius of the mass definition / a and
+ * R_q = clip(eps R_com, 0, max(bins) / 2), BaryonifyGrid's own clip.  Per axis Delta_k = bins[i_k] - x_k, minus L where Delta_k > L / 2, plus L
+ * where Delta_k < -L / 2; d = sqrt(sum Delta_k^2), the true minimum-image distance (NOT the reference's cutout linspace(-N/2, N/2, N) res,
+ * which stretches radii by N / (N - 1) and swaps the sub-pixel dx and dy).  A pixel belongs to halo j iff d^2 <= R_q^2 (at most once:
+ * R_q < L / 2); x = d (comoving Mpc) or, scaled != 0, d / R_com; it is in bin b iff r_edges[b] <= x < r_edges[b + 1]; nb + 1 finite ascending
+ * edges >= 0, 1 <= nb <= 64.  Outputs, row-major [n_halo][nb]:
+ *   npix, sum                  pixels of the cell whose map value is finite, and the sum of those values
+ *   npix_shear, sum_t, sum_x   2D grids with a pair (g1, g2): pixels with finite g1 and g2 and d > 0, and the sums of
+ *                              gamma_t = -(g1 c2 + g2 s2), gamma_x = g1 s2 - g2 c2, c2 = (Dx^2 - Dy^2) / d^2, s2 = 2 Dx Dy / d^2, i.e.
+ *                              gamma_t + i gamma_x = -(g1 + i g2) e^{-2 i phi}, phi from +x towards +y: a mass peak has gamma_t > 0.
+ *                              All three NULL if and only if g1 and g2 are NULL; a pair on a 3D grid is refused
+ * Every (halo, bin) cell of every output is written exactly once -- also for invalid halos (all-zero rows) and halos without pixels -- so the
+ * outputs need no zero-fill; no atomics touch them: counts are exact and reproducible, sums are fp64 in an order that can differ from run to
+ * run.  halos_host: float32-valued columns M, x, y(, z) (lnM / rmat / extra ignored); `model` carries the runner's cosmology (w0 = -1) / mass
+ * definition / epsilon_max, its 3-axis table must be valid and is ignored.  At most 2^31 - 1 halos.
+ *   bfgx_grid_profiles          everything in host memory: upload + kernels + download; nothing is in flight when it returns
+ *   bfgx_grid_profiles_device   the maps and the outputs are device pointers, the kernels run on hip_stream; halo columns, bins and r_edges
+ *                               are host arrays.  hip_stream is synchronised before the call returns (the workspace is released): the
+ *                               outputs are complete on return */
+int  bfgx_grid_profiles(const bfgx_grid_catalog *halos_host, const bfgx_model *model, const bfgx_grid *grid, const double *map_host,
+                        const double *g1_host, const double *g2_host, int32_t nb, const double *r_edges, int32_t scaled, int32_t device,
+                        int64_t *npix, double *sum, int64_t *npix_shear, double *sum_t, double *sum_x);
+int  bfgx_grid_profiles_device(int32_t device, void *hip_stream, const bfgx_grid_catalog *halos_host, const bfgx_model *model,
+                               const bfgx_grid *grid, const double *map_dev, const double *g1_dev, const double *g2_dev, int32_t nb,
+                               const double *r_edges, int32_t scaled, int64_t *npix_dev, double *sum_dev, int64_t *npix_shear_dev,
+                               double *sum_t_dev, double *sum_x_dev);
+
 #ifdef __cplusplus
 }
 #endif
