@@ -16,6 +16,7 @@ from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
 from ..utils.pixelfunc import scatter_add
 from ._model import _placeholder_model, build_model, cosmo_to_dict, process_callable_exact, wants_exact
+from ._profiles import MAX_PROFILE_BINS, _MapProfiles, _is_cuda_tensor, alloc_profile_outs, check_r_edges      # noqa: F401 (MAX_PROFILE_BINS: importable from here)
 
 __all__ = ['DefaultRunner', 'BaryonifyShell', 'PaintProfilesShell', 'MeasureProfilesShell', 'regrid_pixels_hpix']
 
@@ -209,57 +210,9 @@ class PaintProfilesShell(DefaultRunner):
         return new_map
 
 
-MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
-
-
-def _is_cuda_tensor(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
-
-
-class ShellProfiles(object):
+class ShellProfiles(_MapProfiles):
     """What MeasureProfilesShell.process() returns: per (halo, bin) the counted pixels and the sums, shape (n_halo, nb); the shear fields
     are None without a shear pair.  numpy arrays, or torch tensors on the maps' device when the maps were CUDA tensors."""
-
-    def __init__(self, r_edges, npix, sum, npix_shear=None, sum_t=None, sum_x=None, scaled=False):
-        self.r_edges, self.scaled = r_edges, scaled
-        self.npix, self.sum = npix, sum
-        self.npix_shear, self.sum_t, self.sum_x = npix_shear, sum_t, sum_x
-
-    @staticmethod
-    def _ratio(s, n):
-        if isinstance(s, np.ndarray):
-            with np.errstate(divide='ignore', invalid='ignore'):
-                return np.where(n > 0, s / n, np.nan)
-        return (s / n).masked_fill(n == 0, float('nan'))
-
-    @property
-    def mean(self):
-        """sum / npix, NaN where npix is 0"""
-        return self._ratio(self.sum, self.npix)
-
-    @property
-    def mean_t(self):
-        return None if self.sum_t is None else self._ratio(self.sum_t, self.npix_shear)
-
-    @property
-    def mean_x(self):
-        return None if self.sum_x is None else self._ratio(self.sum_x, self.npix_shear)
-
-    def stack(self, select=None, weights=None):
-        """The pixel-weighted mean profile over the chosen halos, sum_j w_j sum[j] / sum_j w_j npix[j] per bin (NaN where the denominator
-        is 0): a dict with 'mean' and, with shear, 'mean_t' and 'mean_x'.  select: anything that indexes the halo axis; weights: one per
-        chosen halo (default 1)."""
-        sel = slice(None) if select is None else select
-        out = {}
-        for name, s, n in (('mean', self.sum, self.npix), ('mean_t', self.sum_t, self.npix_shear), ('mean_x', self.sum_x, self.npix_shear)):
-            if s is None:
-                continue
-            s, n = s[sel], n[sel].to(s.dtype) if not isinstance(n, np.ndarray) else n[sel].astype(np.float64)
-            if weights is not None:
-                w = weights if not isinstance(s, np.ndarray) else np.asarray(weights, dtype=np.float64)
-                s, n = s * w[:, None], n * w[:, None]
-            out[name] = self._ratio(s.sum(0), n.sum(0))
-        return out
 
 
 class MeasureProfilesShell(DefaultRunner):
@@ -276,14 +229,7 @@ class MeasureProfilesShell(DefaultRunner):
         if model is not None:
             raise TypeError("MeasureProfilesShell takes model=None: it measures the map, there is nothing to tabulate")
         super().__init__(HaloLightConeCatalog, LightconeShell, epsilon_max, model, use_ellipticity, mass_def, verbose)
-        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
-        if edges.ndim != 1 or edges.size < 2:
-            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
-        if edges.size - 1 > MAX_PROFILE_BINS:
-            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
-        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
-            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
-        self.r_edges = edges
+        self.r_edges = check_r_edges(r_edges)
         self.scaled = bool(scaled)
         self.shear = self._shear_pair(shear, int(LightconeShell.NSIDE))
 
@@ -320,9 +266,8 @@ class MeasureProfilesShell(DefaultRunner):
                 if x.dtype != torch.float64 or x.dim() != 1 or x.numel() != 12 * nside * nside or x.device != dev:
                     raise ValueError("device maps must be 1-D float64 tensors of 12 NSIDE^2 pixels on one device")
             maps = [x.contiguous() for x in maps]
-            outs = [torch.empty((n, nb), dtype=(torch.int64 if i in (0, 2) else torch.float64), device=dev) for i in range(5 if pair else 2)]
+            outs, optr = alloc_profile_outs(n, nb, pair, dev)
             ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
-            optr = [C.c_void_p(o.data_ptr()) for o in outs] + [None] * (5 - len(outs))
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
 
             def call(cat):
@@ -332,9 +277,8 @@ class MeasureProfilesShell(DefaultRunner):
             maps = [_lib.f8(x).reshape(-1) for x in maps]
             if maps[0].size != 12 * nside * nside:
                 raise ValueError("the map must have 12 NSIDE^2 = %d pixels" % (12 * nside * nside))
-            outs = [np.zeros((n, nb), dtype=(np.int64 if i in (0, 2) else np.float64)) for i in range(5 if pair else 2)]
+            outs, optr = alloc_profile_outs(n, nb, pair)
             ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
-            optr = [o.ctypes.data for o in outs] + [None] * (5 - len(outs))
 
             def call(cat):
                 _lib.check(lib.bfgx_shell_profiles(C.byref(cat), C.byref(model), nside, ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,

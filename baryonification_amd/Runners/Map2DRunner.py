@@ -23,9 +23,11 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from ..utils.cosmology import Cosmology, MassDef, massdef_to_tuple
+from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
 from ._model import _placeholder_model, build_model, process_grid_exact, wants_exact
+from ._profiles import (MAX_PROFILE_BINS, _MapProfiles, _is_cuda_tensor, alloc_profile_outs, check_r_edges, halo_radii,      # noqa: F401
+                        ratio)                                       # (MAX_PROFILE_BINS: importable from here)
 
 __all__ = ['DefaultRunnerGrid', 'BaryonifyGrid', 'PaintProfilesGrid', 'MeasureProfilesGrid', 'GridProfiles', 'regrid_pixels_2D',
            'regrid_pixels_3D']
@@ -209,14 +211,7 @@ class PaintProfilesGrid(DefaultRunnerGrid):
         return new_map
 
 
-MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
-
-
-def _is_cuda_tensor(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
-
-
-class GridProfiles(object):
+class GridProfiles(_MapProfiles):
     """What MeasureProfilesGrid.process() returns.  Per (halo, bin), shape (n_halo, nb): `npix`, the pixels with a finite value and
     r_edges[b] <= x < r_edges[b + 1] inside the halo's ball, and `sum`, the sum of their values; with a shear pair `npix_shear`, `sum_t`
     and `sum_x` (None without one).  numpy arrays, or torch tensors on the maps' device when the maps were CUDA tensors.  `R` is the
@@ -225,36 +220,14 @@ class GridProfiles(object):
     and `ndim` the map's dimension."""
 
     def __init__(self, r_edges, npix, sum, npix_shear=None, sum_t=None, sum_x=None, scaled=False, ndim=3, res=1.0, R=None, R_q=None):
-        self.r_edges, self.scaled, self.ndim, self.res = np.asarray(r_edges, dtype=np.float64), bool(scaled), int(ndim), float(res)
-        self.npix, self.sum = npix, sum
-        self.npix_shear, self.sum_t, self.sum_x = npix_shear, sum_t, sum_x
+        super().__init__(np.asarray(r_edges, dtype=np.float64), npix, sum, npix_shear, sum_t, sum_x, bool(scaled))
+        self.ndim, self.res = int(ndim), float(res)
         self.R, self.R_q = R, R_q
-
-    @staticmethod
-    def _ratio(s, n):
-        """s / n, NaN where n is 0"""
-        if isinstance(s, np.ndarray):
-            with np.errstate(divide='ignore', invalid='ignore'):
-                return np.where(n != 0, s / n, np.nan)
-        return (s / n).masked_fill(n == 0, float('nan'))
-
-    @property
-    def mean(self):
-        """sum / npix, NaN where npix is 0"""
-        return self._ratio(self.sum, self.npix)
-
-    @property
-    def mean_t(self):
-        return None if self.sum_t is None else self._ratio(self.sum_t, self.npix_shear)
-
-    @property
-    def mean_x(self):
-        return None if self.sum_x is None else self._ratio(self.sum_x, self.npix_shear)
 
     @property
     def density(self):
         """sum / (npix res^ndim), for maps that hold mass per pixel: the mean density of the counted pixels (NaN where npix is 0)"""
-        return self._ratio(self.sum, self.npix * self.res ** self.ndim)
+        return ratio(self.sum, self.npix * self.res ** self.ndim)
 
     @property
     def enclosed(self):
@@ -265,16 +238,7 @@ class GridProfiles(object):
         """The pixel-weighted profile over the chosen halos per bin, sum_j w_j sum[j] / sum_j w_j npix[j] (NaN where the denominator is 0):
         a dict with 'mean', 'density' = 'mean' / res^ndim and, with shear, 'mean_t' and 'mean_x'.  select: anything that indexes the halo
         axis; weights: one per chosen halo (default 1)."""
-        sel = slice(None) if select is None else select
-        out = {}
-        for name, s, n in (('mean', self.sum, self.npix), ('mean_t', self.sum_t, self.npix_shear), ('mean_x', self.sum_x, self.npix_shear)):
-            if s is None:
-                continue
-            s, n = s[sel], n[sel].to(s.dtype) if not isinstance(n, np.ndarray) else n[sel].astype(np.float64)
-            if weights is not None:
-                w = weights if not isinstance(s, np.ndarray) else np.asarray(weights, dtype=np.float64)
-                s, n = s * w[:, None], n * w[:, None]
-            out[name] = self._ratio(s.sum(0), n.sum(0))
+        out = super().stack(select, weights)
         out['density'] = out['mean'] / self.res ** self.ndim
         return out
 
@@ -307,14 +271,7 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
         if use_ellipticity:
             raise NotImplementedError("MeasureProfilesGrid measures in circular (spherical) bins: use_ellipticity is not implemented")
         super().__init__(HaloNDCatalog, GriddedMap, epsilon_max, model, use_ellipticity, mass_def, verbose)
-        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
-        if edges.ndim != 1 or edges.size < 2:
-            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
-        if edges.size - 1 > MAX_PROFILE_BINS:
-            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
-        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
-            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
-        self.r_edges = edges
+        self.r_edges = check_r_edges(r_edges)
         self.scaled = bool(scaled)
         G = GriddedMap
         bins = np.asarray(G.bins, dtype=np.float64)
@@ -341,19 +298,8 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
     def radii(self):
         """(R_com, R_q) per halo on the host: the comoving radius of the mass definition and the radius of the ball; NaN and 0 for a halo
         the measurement skips (M not positive / finite, a non-finite coordinate)."""
-        hcat = self.HaloNDCatalog.cat
-        M = np.asarray(hcat['M'], dtype=np.float64)
-        ok = (M > 0) & np.isfinite(M)
-        for k in ('x', 'y') if self.GriddedMap.is2D else ('x', 'y', 'z'):
-            ok &= np.isfinite(np.asarray(hcat[k], dtype=np.float64))
-        a = 1.0 / (1.0 + float(self.HaloNDCatalog.redshift))
-        R = np.full(M.size, np.nan)
-        if ok.any():
-            R[ok] = MassDef(*massdef_to_tuple(self.mass_def)).get_radius(Cosmology.from_dict(self._runner_cosmo()), M[ok], a) / a
-        half = float(np.max(np.asarray(self.GriddedMap.bins, dtype=np.float64))) / 2
-        with np.errstate(invalid='ignore'):
-            R_q = np.where(ok, np.minimum(np.maximum(float(self.epsilon_max) * R, 0.0), half), 0.0)
-        return R, R_q
+        return halo_radii(self.HaloNDCatalog.cat, ('x', 'y') if self.GriddedMap.is2D else ('x', 'y', 'z'), self.HaloNDCatalog.redshift, self.mass_def,
+                          self._runner_cosmo(), self.epsilon_max, float(np.max(np.asarray(self.GriddedMap.bins, dtype=np.float64))) / 2)
 
     def process(self, map=None, shear=None):
         """GridProfiles of GriddedMap.map (and the constructor's shear pair), or of `map` / `shear` given here.  numpy in gives numpy out;
@@ -378,9 +324,8 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
             for x in maps:
                 if x.dtype != torch.float64 or tuple(x.shape) != self.shape or x.device != dev or not x.is_contiguous():
                     raise ValueError("device maps must be C-contiguous float64 tensors of shape %s on one device" % (self.shape,))
-            outs = [torch.empty((n, nb), dtype=(torch.int64 if i in (0, 2) else torch.float64), device=dev) for i in range(5 if pair else 2)]
+            outs, optr = alloc_profile_outs(n, nb, pair, dev)
             ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
-            optr = [C.c_void_p(o.data_ptr()) for o in outs] + [None] * (5 - len(outs))
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
             _lib.check(lib.bfgx_grid_profiles_device(dev.index or 0, stream, C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2],
                                                      nb, edges.ctypes.data, int(self.scaled), *optr))
@@ -389,9 +334,8 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
             for x in maps:
                 if x.shape != self.shape:
                     raise ValueError("the map must have the shape of the GriddedMap %s: got %s" % (self.shape, x.shape))
-            outs = [np.empty((n, nb), dtype=(np.int64 if i in (0, 2) else np.float64)) for i in range(5 if pair else 2)]   # (every cell is written by the library)
+            outs, optr = alloc_profile_outs(n, nb, pair)
             ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
-            optr = [o.ctypes.data for o in outs] + [None] * (5 - len(outs))
             _lib.check(lib.bfgx_grid_profiles(C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,
                                               int(self.scaled), int(self.device), *optr))
         del keep, ckeep, gkeep

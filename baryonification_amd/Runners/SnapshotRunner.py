@@ -18,8 +18,9 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from ..utils.cosmology import Cosmology, MassDef, cosmo_to_dict, massdef_to_tuple
+from ..utils.cosmology import MassDef, cosmo_to_dict
 from ._model import _placeholder_model, build_model, process_snapshot_exact, wants_exact
+from ._profiles import MAX_PROFILE_BINS, _is_cuda_tensor, check_r_edges, halo_radii, ratio      # noqa: F401 (MAX_PROFILE_BINS: importable from here)
 
 __all__ = ['DefaultRunnerSnapshot', 'BaryonifySnapshot', 'MeasureProfilesSnapshot', 'SnapshotProfiles']
 
@@ -151,13 +152,6 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
         return new_cat
 
 
-MAX_PROFILE_BINS = 64          # csrc/bfgx_stack.hpp kStackMaxBins: the bins of a halo live on chip
-
-
-def _is_cuda_tensor(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
-
-
 class SnapshotProfiles(object):
     """What MeasureProfilesSnapshot.process() returns.  Per (halo, bin), shape (n_halo, nb): `npart`, the particles with
     r_edges[b] <= x < r_edges[b + 1] inside the halo's ball, and `sum`, the sum of their finite weights (None for a counts-only
@@ -178,14 +172,6 @@ class SnapshotProfiles(object):
         import torch
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.npart.device)
 
-    @staticmethod
-    def _ratio(s, n):
-        """s / n, NaN where n is 0"""
-        if isinstance(s, np.ndarray):
-            with np.errstate(divide='ignore', invalid='ignore'):
-                return np.where(n != 0, s / n, np.nan)
-        return (s / n).masked_fill(n == 0, float('nan'))
-
     def _total(self):
         if self.sum is not None:
             return self.sum
@@ -194,7 +180,7 @@ class SnapshotProfiles(object):
     @property
     def mean(self):
         """sum / npart, NaN where npart is 0 (None for a counts-only measurement)"""
-        return None if self.sum is None else self._ratio(self.sum, self.npart)
+        return None if self.sum is None else ratio(self.sum, self.npart)
 
     @property
     def volume(self):
@@ -209,7 +195,7 @@ class SnapshotProfiles(object):
     @property
     def density(self):
         """sum / volume (NaN where the bin lies outside the ball)"""
-        return self._ratio(self._total(), self.volume)
+        return ratio(self._total(), self.volume)
 
     @property
     def enclosed(self):
@@ -228,9 +214,9 @@ class SnapshotProfiles(object):
             w = np.asarray(weights, dtype=np.float64) if host else weights
             s, n, vol = s * w[:, None], n * w[:, None], vol * w[:, None]
         nansum = (lambda v: np.nansum(v, axis=0)) if host else (lambda v: v.nansum(0))
-        out = {'density': self._ratio(s.sum(0), nansum(vol))}              # (an invalid halo has an all-zero row and no volume)
+        out = {'density': ratio(s.sum(0), nansum(vol))}              # (an invalid halo has an all-zero row and no volume)
         if self.sum is not None:
-            out['mean'] = self._ratio(s.sum(0), n.sum(0))
+            out['mean'] = ratio(s.sum(0), n.sum(0))
         return out
 
 
@@ -247,14 +233,7 @@ class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
         if model is not None:
             raise TypeError("MeasureProfilesSnapshot takes model=None: it measures the particles, there is nothing to tabulate")
         super().__init__(HaloNDCatalog, ParticleSnapshot, epsilon_max, model, mass_def, verbose, KDTree_kwargs)
-        edges = np.ascontiguousarray(r_edges, dtype=np.float64)
-        if edges.ndim != 1 or edges.size < 2:
-            raise ValueError("r_edges must be a 1-D array of at least 2 bin edges")
-        if edges.size - 1 > MAX_PROFILE_BINS:
-            raise ValueError("%d radial bins: at most %d are supported" % (edges.size - 1, MAX_PROFILE_BINS))
-        if not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
-            raise ValueError("r_edges must be finite, >= 0 and strictly ascending")
-        self.r_edges = edges
+        self.r_edges = check_r_edges(r_edges)
         self.scaled = bool(scaled)
 
     def _cosmo_dict(self):
@@ -265,18 +244,8 @@ class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
     def radii(self):
         """(R_com, R_q) per halo on the host: the comoving radius of the mass definition and the radius of the ball (SnapshotRunner.py:219-222);
         NaN and 0 for a halo the measurement skips (M not positive / finite, a non-finite coordinate)."""
-        hcat = self.HaloNDCatalog.cat
-        M = np.asarray(hcat['M'], dtype=np.float64)
-        ok = (M > 0) & np.isfinite(M)
-        for k in ('x', 'y') if self.ParticleSnapshot.is2D else ('x', 'y', 'z'):
-            ok &= np.isfinite(np.asarray(hcat[k], dtype=np.float64))
-        a = 1.0 / (1.0 + float(self.HaloNDCatalog.redshift))
-        R = np.full(M.size, np.nan)
-        if ok.any():
-            R[ok] = MassDef(*massdef_to_tuple(self.mass_def)).get_radius(Cosmology.from_dict(self._cosmo_dict()), M[ok], a) / a
-        with np.errstate(invalid='ignore'):
-            R_q = np.where(ok, np.minimum(np.maximum(float(self.epsilon_max) * R, 0.0), float(self.ParticleSnapshot.L) / 2), 0.0)
-        return R, R_q
+        return halo_radii(self.HaloNDCatalog.cat, ('x', 'y') if self.ParticleSnapshot.is2D else ('x', 'y', 'z'), self.HaloNDCatalog.redshift,
+                          self.mass_def, self._cosmo_dict(), self.epsilon_max, float(self.ParticleSnapshot.L) / 2)
 
     def process(self, cat=None, weights=None):
         """SnapshotProfiles of the snapshot's own particles, or of `cat`: a structured array with the snapshot's fields (what

@@ -22,13 +22,13 @@
 //                            pixel (no lanes for the cube's corners, 48 % of a 3-D cube); a workgroup scan turns the chord lengths
 //                            into the prefix of their concatenation and thread t takes pixels t, t + 256, ... of it: lanes run along
 //                            the last axis and no lane waits behind the longest row.  The exact d^2 <= R_q^2 test decides membership.
-//                            The (at most) 64 bins of the halo live in LDS: fp64 LDS adds (ds_add_f64, -munsafe-fp-atomics) for the sums,
-//                            32-bit LDS adds for the counts (a grid holds fewer than 2^32 pixels); when the halo is done thread b stores
-//                            bin b of each output once.  No global atomics and no zero-fill: every (halo, bin) cell of every output is
+//                            The bins of the halo live in LDS (one StackBins per workgroup; the scan, the edges, the bin rule, the bins
+//                            and their store are bfgx_stack_core.hpp's; a grid holds fewer than 2^32 pixels, so a 32-bit count cannot
+//                            overflow); when the halo is done thread b stores bin b of each output once.  No global atomics and no zero-fill: every (halo, bin) cell of every output is
 //                            written exactly once, also for invalid halos and halos without pixels.  int64 pixel indices, fp64 throughout.
 #pragma once
 #include "bfgx_grid.hpp"
-#include "bfgx_snapshot_stack.hpp"
+#include "bfgx_stack_core.hpp"
 
 namespace bfgx {
 
@@ -48,8 +48,7 @@ struct GridStackArgs {
     const double *map, *g1, *g2;      // [npix]^ndim, C order (g1 == nullptr: no shear pair)
     const double *edges;              // nb + 1 ascending bin edges
     int32_t nb, scaled;
-    int64_t *npix, *npix_shear;       // [nhalo][nb]
-    double *sum, *sum_t, *sum_x;
+    StackOut out;                     // [nhalo][nb]
 };
 
 __device__ inline double grid_min_image(double d, double L, double Lh)
@@ -93,16 +92,16 @@ grid_stack_prep_kernel(Background bg, bfgx_massdef md, double eps, GridGeom g, i
     recs[j] = r;
 }
 
+template <bool SHEAR>
 struct GridStackLds {
     uint32_t prefix[kGridStackThreads];       // exclusive prefix of the chord lengths of this round
     int32_t m0[kGridStackThreads];            // first offset of each chord on the last axis
     int64_t base[kGridStackThreads];          // pixel index of the row's pixel 0 on the last axis
     double s01[kGridStackThreads];            // sum of the other axes' Delta^2
     double d0[kGridStackThreads];             // Delta of axis 0 (the shear's Dx)
-    double sum[kStackMaxBins], sum_t[kStackMaxBins], sum_x[kStackMaxBins];
-    unsigned int n[kStackMaxBins], ns[kStackMaxBins];
+    StackBins<SHEAR> bins;
     uint32_t wtot[kGridStackThreads / kWave];
-    double edges[kStackEdgeLds];              // the edges padded with +inf to a power of two: a branch-free search
+    double edges[kStackEdgeLds];
 };
 
 template <int DIM, bool SHEAR>
@@ -111,15 +110,15 @@ grid_stack_kernel(GridGeom g, int64_t nh, const GridStackRec *__restrict__ recs,
 {
     static_assert(DIM == 3 || DIM == 2, "2-D or 3-D grids");
     static_assert(!SHEAR || DIM == 2, "the shear pair is flat-sky: 2-D grids only");
-    __shared__ GridStackLds S;
+    __shared__ GridStackLds<SHEAR> S;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    for (int i = tid; i < kStackEdgeLds; i += kGridStackThreads) S.edges[i] = i <= a.nb ? a.edges[i] : __builtin_inf();
+    stack_load_edges(S.edges, a.edges, a.nb, tid, kGridStackThreads);
     const int nb = a.nb, N = g.npix;
     const double L = (double)N * g.res, Lh = 0.5 * L;
     constexpr int LA = DIM - 1;                                                 // the last axis
     for (int64_t j = blockIdx.x; j < nh; j += gridDim.x) {                      // (every branch on r or j below is uniform over the workgroup)
         const GridStackRec &r = recs[j];
-        if (tid < kStackMaxBins) { S.sum[tid] = 0.0; S.n[tid] = 0u; S.sum_t[tid] = 0.0; S.sum_x[tid] = 0.0; S.ns[tid] = 0u; }
+        if (tid < kStackMaxBins) S.bins.clear(tid);
         __syncthreads();
         const double e0 = S.edges[0];
         const double den = (a.scaled && r.valid) ? r.R : 1.0;
@@ -152,23 +151,12 @@ grid_stack_kernel(GridGeom g, int64_t nh, const GridStackRec *__restrict__ recs,
                     S.m0[tid] = ml + kA; S.base[tid] = base; S.s01[tid] = s01; S.d0[tid] = D0;
                 }
             }
-            const uint32_t incl = wave_scan_incl_u32(cnt, lane);
-            if (lane == kWave - 1) S.wtot[wid] = incl;
-            __syncthreads();
-            uint32_t woff = 0, total = 0;
-#pragma unroll
-            for (int q = 0; q < kGridStackThreads / kWave; ++q) {
-                const uint32_t t = S.wtot[q];
-                woff += (q < wid) ? t : 0u;
-                total += t;
-            }
-            S.prefix[tid] = woff + incl - cnt;                                  // (an empty chord shares its prefix with the next one: the search skips it)
+            uint32_t excl, total;
+            block_ragged_prefix<kGridStackThreads>(cnt, lane, wid, S.wtot, excl, total);
+            S.prefix[tid] = excl;
             __syncthreads();
             for (uint32_t t = tid; t < total; t += kGridStackThreads) {
-                int slot = 0;                                                   // largest slot with prefix[slot] <= t
-#pragma unroll
-                for (int st = kGridStackThreads >> 1; st > 0; st >>= 1)
-                    if (S.prefix[slot + st] <= t) slot += st;
+                const int slot = ragged_find<kGridStackThreads>(S.prefix, t);
                 int p = cl + S.m0[slot] + (int)(t - S.prefix[slot]); p += (p < 0) ? N : 0; p -= (p >= N) ? N : 0;
                 const int64_t pix = S.base[slot] + p;
                 const double v = a.map[pix];
@@ -179,35 +167,18 @@ grid_stack_kernel(GridGeom g, int64_t nh, const GridStackRec *__restrict__ recs,
                 if (!(d2 <= Rq2)) continue;
                 const double dd = __dsqrt_rn(d2);
                 const double xv = a.scaled ? dd / den : dd;
-                int b = 0;                                                      // largest b with edges[b] <= x (the padding is +inf)
-#pragma unroll
-                for (int st = kStackEdgeLds >> 1; st > 0; st >>= 1)
-                    if (S.edges[b + st] <= xv) b += st;
-                if (!(xv >= e0) || b >= nb) continue;                           // outside [edges[0], edges[nb]), or NaN
-                if (isfinite(v)) {
-                    atomicAdd(&S.n[b], 1u);
-                    atomicAdd(&S.sum[b], v);
-                }
-                if (SHEAR && isfinite(ga) && isfinite(gb) && d2 > 0.0) {        // (the halo on the pixel centre has no position angle)
+                const int b = stack_find_bin(S.edges, e0, xv, nb);
+                if (b < 0) continue;
+                if (isfinite(v)) S.bins.add(b, v);
+                if constexpr (SHEAR) if (isfinite(ga) && isfinite(gb) && d2 > 0.0) {   // (the halo on the pixel centre has no position angle)
                     const double Dx = S.d0[slot], inv = 1.0 / d2;
                     const double c2 = (Dx - Dl) * (Dx + Dl) * inv, s2 = 2.0 * Dx * Dl * inv;
-                    atomicAdd(&S.ns[b], 1u);
-                    atomicAdd(&S.sum_t[b], -(ga * c2 + gb * s2));
-                    atomicAdd(&S.sum_x[b], ga * s2 - gb * c2);
+                    S.bins.add_shear(b, -(ga * c2 + gb * s2), ga * s2 - gb * c2);
                 }
             }
             __syncthreads();                                                    // the round's chords and the bins are settled
         }
-        if (tid < nb) {
-            const int64_t o = j * nb + tid;
-            a.npix[o] = (int64_t)S.n[tid];
-            a.sum[o] = S.sum[tid];
-            if (SHEAR) {
-                a.npix_shear[o] = (int64_t)S.ns[tid];
-                a.sum_t[o] = S.sum_t[tid];
-                a.sum_x[o] = S.sum_x[tid];
-            }
-        }
+        if (tid < nb) S.bins.store(tid, j * nb + tid, a.out);
     }
 }
 

@@ -1,5 +1,5 @@
-// bfgx_grid_stack_api.inc -- C ABI of the halo-centred profile measurement on gridded maps (included at the end of bfgx_api.hip, after
-// bfgx_snapshot_stack_api.inc whose CallStream it shares; declared in include/bfgx.h).
+// bfgx_grid_stack_api.inc -- C ABI of the halo-centred profile measurement on gridded maps (included at the end of bfgx_api.hip; declared
+// in include/bfgx.h).
 //
 // MeasureProfilesGrid is the third measurement: shell, box and grid share one interface.  The ball and its clipping are BaryonifyGrid's
 // (grid_pairs_prep_kernel's valid rule, GridGeom::half_box), the separations are true minimum-image distances between pixel centres and
@@ -8,21 +8,14 @@
 
 namespace {
 
-struct GridProfOut { int64_t *npix, *npix_shear; double *sum, *sum_t, *sum_x; };
-
 // everything that can be refused without a device, before anything is allocated
 int grid_profiles_validate(const bfgx_grid_catalog *c, const bfgx_model *model, const bfgx_grid *grid, const double *map, const double *g1,
-                           const double *g2, int32_t nb, const double *r_edges, const GridProfOut &o)
+                           const double *g2, int32_t nb, const double *r_edges, const StackOut &o)
 {
     if (!c || !model || !grid || !map || !r_edges || !o.npix || !o.sum) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if ((g1 == nullptr) != (g2 == nullptr)) return fail(BFGX_ERR_INVALID, "NULL argument: the shear pair needs both g1 and g2");
-    if (g1 && (!o.npix_shear || !o.sum_t || !o.sum_x)) return fail(BFGX_ERR_INVALID, "NULL argument: a shear pair needs npix_shear, sum_t and sum_x");
+    if (int rc = profiles_validate_shear(g1, g2, o)) return rc;
     if (!g1 && (o.npix_shear || o.sum_t || o.sum_x)) return fail(BFGX_ERR_INVALID, "npix_shear, sum_t and sum_x go with a shear pair: they must be NULL without one");
-    if (nb < 1 || nb > kStackMaxBins) return fail(BFGX_ERR_INVALID, "%d radial bins: must be 1 .. %d (the bins of a halo live on chip)", (int)nb, kStackMaxBins);
-    for (int i = 0; i <= nb; ++i)
-        if (!std::isfinite(r_edges[i]) || r_edges[i] < 0.0) return fail(BFGX_ERR_INVALID, "r_edges must be finite and >= 0");
-    for (int i = 0; i < nb; ++i)
-        if (!(r_edges[i + 1] > r_edges[i])) return fail(BFGX_ERR_INVALID, "r_edges must be strictly ascending");
+    if (int rc = profiles_validate_bins(nb, r_edges)) return rc;
     if (int rc = validate_grid(grid)) return rc;
     if (g1 && grid->ndim == 3) return fail(BFGX_ERR_INVALID, "the shear pair is flat-sky: it is accepted for 2D grids only");
     {
@@ -36,8 +29,7 @@ int grid_profiles_validate(const bfgx_grid_catalog *c, const bfgx_model *model, 
     if (c->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
     if (c->n > INT32_MAX) return fail(BFGX_ERR_INVALID, "more than 2^31 halos");
     if (c->n > 0 && (!c->M || !c->x || !c->y || (grid->ndim == 3 && !c->z))) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    if (model->table.ndim != 3) return fail(BFGX_ERR_INVALID, "the profile measurement takes a model with a (dummy) 3-axis table: there is nothing to tabulate");
-    if (int rc = validate_model(model)) return rc;
+    if (int rc = profiles_validate_placeholder(model, true)) return rc;
     if (bfgx_device_count() <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
     return BFGX_OK;
 }
@@ -45,7 +37,7 @@ int grid_profiles_validate(const bfgx_grid_catalog *c, const bfgx_model *model, 
 // The measurement on stream st: map / g1 / g2 and the outputs are DEVICE pointers; the halo columns, the bins and the edges are host arrays.
 // The stream is drained before this returns, on every path: the workspace is released at scope exit.
 int grid_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_model *model, const bfgx_grid *grid, const double *map, const double *g1,
-                      const double *g2, int32_t nb, const double *r_edges, int32_t scaled, const GridProfOut &o)
+                      const double *g2, int32_t nb, const double *r_edges, int32_t scaled, const StackOut &o)
 {
     const int64_t nh = c->n;
     if (nh == 0) return BFGX_OK;                   // (there is no cell to write)
@@ -53,12 +45,7 @@ int grid_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_mod
     hipStream_t stream = st;
     DrainOnExit drain;                             // (declared last: the stream is drained before the buffers above are released)
     drain.s[0] = &stream; drain.null_stream = (st == nullptr);
-    const double *hsrc[4] = {c->M, c->x, c->y, grid->ndim == 3 ? c->z : nullptr};
-    for (int k = 0; k < 4; ++k) {
-        if (hcol[k].alloc(sizeof(double) * (size_t)nh)) return alloc_fail("catalog");
-        // (a copy from pageable host memory has left the caller's array when hipMemcpyAsync returns)
-        if (hsrc[k]) HIP_TRY(hipMemcpyAsync(hcol[k].p, hsrc[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, st));
-    }
+    if (int rc = upload_halo_columns(st, c, grid->ndim, nh, hcol)) return rc;
     if (recs.alloc(sizeof(GridStackRec) * (size_t)nh) || edges.alloc(sizeof(double) * (kStackMaxBins + 1)) ||
         bins.alloc(sizeof(double) * (size_t)grid->npix))
         return alloc_fail("halo records");
@@ -79,8 +66,7 @@ int grid_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_mod
                        hcol[1].as<double>(), hcol[2].as<double>(), hcol[3].as<double>(), recs.as<GridStackRec>());
     HIP_TRY(hipGetLastError());
     GridStackArgs a;
-    a.map = map; a.g1 = g1; a.g2 = g2; a.edges = edges.as<double>(); a.nb = nb; a.scaled = scaled ? 1 : 0;
-    a.npix = o.npix; a.npix_shear = o.npix_shear; a.sum = o.sum; a.sum_t = o.sum_t; a.sum_x = o.sum_x;
+    a.map = map; a.g1 = g1; a.g2 = g2; a.edges = edges.as<double>(); a.nb = nb; a.scaled = scaled ? 1 : 0; a.out = o;
     const dim3 grd((unsigned)std::min<int64_t>(nh, 8192)), block(kGridStackThreads);
     const GridStackRec *rp = recs.as<GridStackRec>();
     if (g.ndim == 3) hipLaunchKernelGGL((grid_stack_kernel<3, false>), grd, block, 0, st, g, nh, rp, a);
@@ -99,7 +85,7 @@ int bfgx_grid_profiles(const bfgx_grid_catalog *halos_host, const bfgx_model *mo
                        const double *g1_host, const double *g2_host, int32_t nb, const double *r_edges, int32_t scaled, int32_t device,
                        int64_t *npix, double *sum, int64_t *npix_shear, double *sum_t, double *sum_x)
 {
-    const GridProfOut ho{npix, npix_shear, sum, sum_t, sum_x};
+    const StackOut ho{npix, npix_shear, sum, sum_t, sum_x};
     if (int rc = grid_profiles_validate(halos_host, model, grid, map_host, g1_host, g2_host, nb, r_edges, ho)) return rc;
     HIP_TRY(hipSetDevice(device));
     // nothing is left in flight on any return path: `drain` (declared after the device buffers, so destroyed before them) drains the call's
@@ -121,20 +107,12 @@ int bfgx_grid_profiles(const bfgx_grid_catalog *halos_host, const bfgx_model *mo
     }
     const size_t cb = std::max<size_t>(cells, 1) * 8;
     if (dn[0].alloc(cb) || ds[0].alloc(cb) || (g1_host && (dn[1].alloc(cb) || ds[1].alloc(cb) || ds[2].alloc(cb)))) return alloc_fail("profiles");
-    const GridProfOut dv{dn[0].as<int64_t>(), g1_host ? dn[1].as<int64_t>() : nullptr, ds[0].as<double>(), g1_host ? ds[1].as<double>() : nullptr,
+    const StackOut dv{dn[0].as<int64_t>(), g1_host ? dn[1].as<int64_t>() : nullptr, ds[0].as<double>(), g1_host ? ds[1].as<double>() : nullptr,
                          g1_host ? ds[2].as<double>() : nullptr};
     if (int rc = grid_profiles_run(st, halos_host, model, grid, dmap[0].as<double>(), g1_host ? dmap[1].as<double>() : nullptr,
                                    g1_host ? dmap[2].as<double>() : nullptr, nb, r_edges, scaled, dv))
         return rc;
-    if (cells > 0) {
-        HIP_TRY(hipMemcpyAsync(npix, dv.npix, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(sum, dv.sum, cells * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (g1_host) {
-            HIP_TRY(hipMemcpyAsync(npix_shear, dv.npix_shear, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(sum_t, dv.sum_t, cells * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(sum_x, dv.sum_x, cells * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-    }
+    if (int rc = profiles_copy_back(st, ho, dv, cells, g1_host != nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return BFGX_OK;
 }
@@ -143,7 +121,7 @@ int bfgx_grid_profiles_device(int32_t device, void *hip_stream, const bfgx_grid_
                               const double *map_dev, const double *g1_dev, const double *g2_dev, int32_t nb, const double *r_edges, int32_t scaled,
                               int64_t *npix_dev, double *sum_dev, int64_t *npix_shear_dev, double *sum_t_dev, double *sum_x_dev)
 {
-    const GridProfOut dv{npix_dev, npix_shear_dev, sum_dev, sum_t_dev, sum_x_dev};
+    const StackOut dv{npix_dev, npix_shear_dev, sum_dev, sum_t_dev, sum_x_dev};
     if (int rc = grid_profiles_validate(halos_host, model, grid, map_dev, g1_dev, g2_dev, nb, r_edges, dv)) return rc;
     HIP_TRY(hipSetDevice(device));
     return grid_profiles_run((hipStream_t)hip_stream, halos_host, model, grid, map_dev, g1_dev, g2_dev, nb, r_edges, scaled, dv);

@@ -1428,6 +1428,16 @@ __device__ inline int wave_scan_incl(int v, int lane)
     return v;
 }
 
+__device__ inline uint32_t wave_scan_incl_u32(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int s = 1; s < kWave; s <<= 1) {
+        const uint32_t u = __shfl_up(v, s, kWave);
+        if (lane >= s) v += u;
+    }
+    return v;
+}
+
 // Mixed-precision form of pair_value_fast for MODE_OFFSETS with fp32 pix_offsets output.  The chord -- a difference of
 // nearly equal unit vectors -- and the r < rcut decision stay fp64; everything downstream of r^2 runs in fp32: 1/r and
 // ln r from the hardware v_rsq_f32 / v_log_f32, the table read-out from an fp32 copy of the table, and the renormalised

@@ -20,6 +20,24 @@ struct DrainOnExit {
     }
 };
 
+// a stream of the call's own, drained and destroyed at scope exit
+struct CallStream {
+    hipStream_t s = nullptr;
+    ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+
+// The halo columns of a box or grid catalog on the device: hcol[0 .. 3] = M, x, y, z (z: allocated, not filled, for ndim 2) of the nh halos of a host catalog, on stream st; at least one element each
+int upload_halo_columns(hipStream_t st, const bfgx_grid_catalog *c, int32_t ndim, int64_t nh, DevBuf *hcol)
+{
+    const double *hsrc[4] = {c->M, c->x, c->y, ndim == 3 ? c->z : nullptr};
+    for (int k = 0; k < 4; ++k) {
+        if (hcol[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(nh, 1))) return alloc_fail("catalog");
+        // (a copy from pageable host memory has left the caller's array when hipMemcpyAsync returns)
+        if (nh > 0 && hsrc[k]) HIP_TRY(hipMemcpyAsync(hcol[k].p, hsrc[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, st));
+    }
+    return BFGX_OK;
+}
+
 // A caller's host array as the source / destination of the ASYNCHRONOUS copies of a one-shot entry:
 //  * already page-locked by the caller (bfgx_host_alloc): used as it is;
 //  * >= 32 MiB -- beyond glibc's largest mmap threshold, i.e. a mapping of its own that shares no page with another object: page-locked in

@@ -120,12 +120,7 @@ int bfgx_snapshot_pairs_begin(const bfgx_grid_catalog *halos_host, const bfgx_mo
     for (int d = 0; d < g.ndim; ++d) g.ncell *= g.nc;
     // uploads: halo columns (float32-valued, as HaloNDCatalog keeps them), particle coordinates
     DevBuf hcol[4];
-    const double *hsrc[4] = {c->M, c->x, c->y, s->ndim == 3 ? c->z : nullptr};
-    for (int k = 0; k < 4; ++k) {
-        if (hcol[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(nh, 1))) return bail(alloc_fail("catalog"));
-        if (nh > 0 && hsrc[k] && hipMemcpyAsync(hcol[k].p, hsrc[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, st) != hipSuccess)
-            return bail(fail(BFGX_ERR_HIP, "copy(catalog) failed"));
-    }
+    if (int rc = upload_halo_columns(st, c, s->ndim, nh, hcol)) return bail(rc);
     const double *psrc[3] = {s->x, s->y, s->ndim == 3 ? s->z : nullptr};
     for (int k = 0; k < 3; ++k) {
         if (h->sxyz[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(np, 1))) return bail(alloc_fail("particles"));

@@ -13,15 +13,15 @@
 //   snap_stack_kernel   one workgroup per halo (grid-stride over halos).  256 columns at a time: thread t looks up the one or two runs of
 //                       column t, a workgroup scan turns the run lengths into the prefix of their concatenation, and thread t takes
 //                       particles t, t + 256, ... of it: lanes map to particles, consecutive lanes read consecutive records, and no
-//                       lane waits behind the fullest cell.  The (at most) 64 bins of the halo live in LDS while the particles stream
-//                       by: fp64 LDS adds (ds_add_f64, -munsafe-fp-atomics) for the sums, 32-bit LDS adds for the counts (a particle
-//                       is in a halo's ball at most once, R_q <= L / 2, so a count stays below the 2^32 particles of a call); when
-//                       the halo is done thread b stores bin b of each output once.  No global atomics and no zero-fill: every
+//                       lane waits behind the fullest cell.  The bins of the halo live in LDS while the particles stream by (one
+//                       StackBins per workgroup; the scan, the edges, the bin rule, the bins and their store are
+//                       bfgx_stack_core.hpp's; a particle is in a halo's ball at most once, R_q <= L / 2, so a 32-bit count stays
+//                       below the 2^32 particles of a call); when the halo is done thread b stores bin b of each output once.  No global atomics and no zero-fill: every
 //                       (halo, bin) cell is written exactly once, also for invalid halos and halos without particles.  Counts are
 //                       exact and reproducible; fp64 throughout.
 #pragma once
 #include "bfgx_snapshot_pairs.hpp"
-#include "bfgx_stack.hpp"
+#include "bfgx_stack_core.hpp"
 
 namespace bfgx {
 
@@ -34,8 +34,7 @@ struct SnapStackArgs {
     const double *M;                          // halo masses (the scaled abscissa needs R_j)
     const double *edges;                      // nb + 1 ascending bin edges
     int32_t nb, scaled;
-    int64_t *npart;                           // [nhalo][nb]
-    double *sum;                              // [nhalo][nb], nullptr without weights
+    StackOut out;                             // [nhalo][nb]: npix = npart; sum is nullptr without weights; no shear members
 };
 
 __global__ void __launch_bounds__(256)
@@ -52,23 +51,12 @@ snap_stack_gather_kernel(int64_t np, const uint32_t *__restrict__ idx, const dou
     if (w) ws[s] = w[i];
 }
 
-__device__ inline uint32_t wave_scan_incl_u32(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {
-        const uint32_t u = __shfl_up(v, s, kWave);
-        if (lane >= s) v += u;
-    }
-    return v;
-}
-
 struct SnapStackLds {
     uint32_t prefix[kSnapStackSlots];         // exclusive prefix of the run lengths of this round
     uint32_t start[kSnapStackSlots];          // first sorted particle of each run
-    double sum[kStackMaxBins];
-    unsigned int n[kStackMaxBins];
+    StackBins<false> bins;
     uint32_t wtot[kSnapStackThreads / kWave];
-    double edges[kStackEdgeLds];              // the edges padded with +inf to a power of two: a branch-free search
+    double edges[kStackEdgeLds];
 };
 
 template <int DIM, bool WEIGHTS>
@@ -77,11 +65,11 @@ snap_stack_kernel(SnapGeom g, Background bg, bfgx_massdef md, int64_t nh, const 
 {
     __shared__ SnapStackLds S;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    for (int i = tid; i < kStackEdgeLds; i += kSnapStackThreads) S.edges[i] = i <= a.nb ? a.edges[i] : __builtin_inf();
+    stack_load_edges(S.edges, a.edges, a.nb, tid, kSnapStackThreads);
     const int nb = a.nb, nc = g.nc;
     for (int64_t j = blockIdx.x; j < nh; j += gridDim.x) {                  // (every branch on r or j below is uniform over the workgroup)
         const SnapHaloRec &r = recs[j];
-        if (tid < kStackMaxBins) { S.sum[tid] = 0.0; S.n[tid] = 0u; }
+        if (tid < kStackMaxBins) S.bins.clear(tid);
         __syncthreads();
         const double e0 = S.edges[0];
         // x = d / (R_j / a) or d: R_j / a as the prep kernel's R_q has it, before epsilon_max and the clipping
@@ -110,51 +98,31 @@ snap_stack_kernel(SnapGeom g, Background bg, bfgx_massdef md, int64_t nh, const 
                     cB = a.cell_start[row + (end - nc)] - sB;
                 }
             }
-            const uint32_t mine = cA + cB;
-            const uint32_t incl = wave_scan_incl_u32(mine, lane);
-            if (lane == kWave - 1) S.wtot[wid] = incl;
-            __syncthreads();
-            uint32_t woff = 0, total = 0;
-#pragma unroll
-            for (int q = 0; q < kSnapStackThreads / kWave; ++q) {
-                const uint32_t t = S.wtot[q];
-                woff += (q < wid) ? t : 0u;
-                total += t;
-            }
-            const uint32_t excl = woff + incl - mine;
-            S.prefix[2 * tid] = excl; S.prefix[2 * tid + 1] = excl + cA;       // (an empty run shares its prefix with the next one: the search skips it)
+            uint32_t excl, total;
+            block_ragged_prefix<kSnapStackThreads>(cA + cB, lane, wid, S.wtot, excl, total);
+            S.prefix[2 * tid] = excl; S.prefix[2 * tid + 1] = excl + cA;
             S.start[2 * tid] = sA; S.start[2 * tid + 1] = sB;
             __syncthreads();
             for (uint64_t tt = tid; tt < total; tt += kSnapStackThreads) {
                 const uint32_t t = (uint32_t)tt;
-                int slot = 0;                                                   // largest slot with prefix[slot] <= t
-#pragma unroll
-                for (int st = kSnapStackSlots >> 1; st > 0; st >>= 1)
-                    if (S.prefix[slot + st] <= t) slot += st;
+                const int slot = ragged_find<kSnapStackSlots>(S.prefix, t);
                 const int64_t p = (int64_t)S.start[slot] + (t - S.prefix[slot]);
                 double d[3];
                 const double d2 = snap_sep<DIM>(g, r, a.x, a.y, a.z, p, d);
                 if (!(d2 <= r.Rq2)) continue;
                 const double dd = __dsqrt_rn(d2);
                 const double xv = a.scaled ? dd / den : dd;
-                int b = 0;                                                      // largest b with edges[b] <= x (the padding is +inf)
-#pragma unroll
-                for (int st = kStackEdgeLds >> 1; st > 0; st >>= 1)
-                    if (S.edges[b + st] <= xv) b += st;
-                if (!(xv >= e0) || b >= nb) continue;                           // outside [edges[0], edges[nb]), or NaN
-                atomicAdd(&S.n[b], 1u);
+                const int b = stack_find_bin(S.edges, e0, xv, nb);
+                if (b < 0) continue;
+                S.bins.count(b);
                 if (WEIGHTS) {
                     const double wv = a.w[p];
-                    if (isfinite(wv)) atomicAdd(&S.sum[b], wv);
+                    if (isfinite(wv)) S.bins.add_sum(b, wv);
                 }
             }
             __syncthreads();                                                    // the round's runs and the bins are settled
         }
-        if (tid < nb) {
-            const int64_t o = j * nb + tid;
-            a.npart[o] = (int64_t)S.n[tid];
-            if (WEIGHTS) a.sum[o] = S.sum[tid];
-        }
+        if (tid < nb) S.bins.store(tid, j * nb + tid, a.out, WEIGHTS);
     }
 }
 

@@ -19,19 +19,14 @@ int snap_profiles_validate(const bfgx_grid_catalog *c, const bfgx_model *model, 
 {
     if (!c || !model || !r_edges || !npart) return fail(BFGX_ERR_INVALID, "NULL argument");
     if ((s.w == nullptr) != (sum == nullptr)) return fail(BFGX_ERR_INVALID, "NULL argument: sum goes with the weights (both, or neither for counts only)");
-    if (nb < 1 || nb > kStackMaxBins) return fail(BFGX_ERR_INVALID, "%d radial bins: must be 1 .. %d (the bins of a halo live on chip)", (int)nb, kStackMaxBins);
-    for (int i = 0; i <= nb; ++i)
-        if (!std::isfinite(r_edges[i]) || r_edges[i] < 0.0) return fail(BFGX_ERR_INVALID, "r_edges must be finite and >= 0");
-    for (int i = 0; i < nb; ++i)
-        if (!(r_edges[i + 1] > r_edges[i])) return fail(BFGX_ERR_INVALID, "r_edges must be strictly ascending");
+    if (int rc = profiles_validate_bins(nb, r_edges)) return rc;
     if (c->n < 0 || s.np < 0) return fail(BFGX_ERR_INVALID, "catalog / snapshot size < 0");
     if (c->n > INT32_MAX || s.np > (int64_t)UINT32_MAX) return fail(BFGX_ERR_INVALID, "more than 2^31 halos or 2^32 particles");
     if (s.ndim != 2 && s.ndim != 3) return fail(BFGX_ERR_INVALID, "snapshot ndim must be 2 or 3");
     if (!(s.L > 0.0) || !std::isfinite(s.L) || !(s.redshift > -1.0)) return fail(BFGX_ERR_INVALID, "snapshot L must be > 0 and redshift > -1");
     if (c->n > 0 && (!c->M || !c->x || !c->y || (s.ndim == 3 && !c->z))) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
     if (s.np > 0 && (!s.x || !s.y || (s.ndim == 3 && !s.z))) return fail(BFGX_ERR_INVALID, "snapshot coordinate pointer is NULL");
-    if (model->table.ndim != 3) return fail(BFGX_ERR_INVALID, "the profile measurement takes a model with a (dummy) 3-axis table: there is nothing to tabulate");
-    if (int rc = validate_model(model)) return rc;
+    if (int rc = profiles_validate_placeholder(model, true)) return rc;
     if (bfgx_device_count() <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
     return BFGX_OK;
 }
@@ -56,12 +51,7 @@ int snap_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_mod
     hipStream_t stream = st;
     DrainOnExit drain;                             // (declared last: the stream is drained before the buffers above are released)
     drain.s[0] = &stream; drain.null_stream = (st == nullptr);
-    const double *hsrc[4] = {c->M, c->x, c->y, s.ndim == 3 ? c->z : nullptr};
-    for (int k = 0; k < 4; ++k) {
-        if (hcol[k].alloc(sizeof(double) * (size_t)std::max<int64_t>(nh, 1))) return alloc_fail("catalog");
-        // (a copy from pageable host memory has left the caller's array when hipMemcpyAsync returns)
-        if (nh > 0 && hsrc[k]) HIP_TRY(hipMemcpyAsync(hcol[k].p, hsrc[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, st));
-    }
+    if (int rc = upload_halo_columns(st, c, s.ndim, nh, hcol)) return rc;
     if (recs.alloc(sizeof(SnapHaloRec) * (size_t)std::max<int64_t>(nh, 1)) || edges.alloc(sizeof(double) * (kStackMaxBins + 1))) return alloc_fail("halo records");
     HIP_TRY(hipMemcpyAsync(edges.p, r_edges, sizeof(double) * (size_t)(nb + 1), hipMemcpyHostToDevice, st));
     if (nh > 0) {
@@ -82,7 +72,7 @@ int snap_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_mod
     SnapStackArgs a;
     a.x = sorted[0].as<double>(); a.y = sorted[1].as<double>(); a.z = sorted[2].as<double>(); a.w = s.w ? sorted[3].as<double>() : nullptr;
     a.cell_start = (const uint32_t *)bins.cstart.p; a.M = hcol[0].as<double>(); a.edges = edges.as<double>();
-    a.nb = nb; a.scaled = scaled ? 1 : 0; a.npart = npart; a.sum = sum;
+    a.nb = nb; a.scaled = scaled ? 1 : 0; a.out = StackOut{npart, nullptr, sum, nullptr, nullptr};
     const dim3 grid((unsigned)std::min<int64_t>(nh, 8192)), block(kSnapStackThreads);
     const SnapHaloRec *rp = recs.as<SnapHaloRec>();
     if (g.ndim == 3) {
@@ -96,12 +86,6 @@ int snap_profiles_run(hipStream_t st, const bfgx_grid_catalog *c, const bfgx_mod
     HIP_TRY(hipStreamSynchronize(st));
     return BFGX_OK;
 }
-
-// a stream of the call's own, drained and destroyed at scope exit
-struct CallStream {
-    hipStream_t s = nullptr;
-    ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-};
 
 }  // namespace
 
@@ -134,10 +118,8 @@ int bfgx_snapshot_profiles(const bfgx_grid_catalog *halos_host, const bfgx_model
     SnapProfIn ds_in = hs;
     ds_in.x = col[0].as<double>(); ds_in.y = col[1].as<double>(); ds_in.z = col[2].as<double>(); ds_in.w = w_host ? col[3].as<double>() : nullptr;
     if (int rc = snap_profiles_run(st, halos_host, model, ds_in, nb, r_edges, scaled, dn.as<int64_t>(), w_host ? ds.as<double>() : nullptr)) return rc;
-    if (cells > 0) {
-        HIP_TRY(hipMemcpyAsync(npart, dn.p, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (w_host) HIP_TRY(hipMemcpyAsync(sum, ds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
+    const StackOut ho{npart, nullptr, sum, nullptr, nullptr}, dv{dn.as<int64_t>(), nullptr, ds.as<double>(), nullptr, nullptr};
+    if (int rc = profiles_copy_back(st, ho, dv, cells, false)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return BFGX_OK;
 }

@@ -7,30 +7,27 @@
 //     gamma_t + i gamma_x = -(g1 + i g2) e^{-2 i phi},
 // phi the position angle of the great circle towards the halo at the pixel, measured from e_theta towards e_phi.
 //
-// One wave per halo.  One enumeration, one r_sep and one bin search per pair serve every map of the call.  The (at most) 64 bins of the
-// halo live in the wave's LDS while its pixels stream by: fp64 LDS adds (ds_add_f64, -munsafe-fp-atomics) for the sums and 32-bit
-// LDS adds for the counts; when the disc is done lane b stores bin b of every output once.  No global atomics and no zero-fill: every
+// One wave per halo.  One enumeration, one r_sep and one bin search per pair serve every map of the call.  The bins of the halo live in
+// the wave's LDS while its pixels stream by (one StackBins per wave: the edges, the bin rule, the bins and their store are
+// bfgx_stack_core.hpp's); when the disc is done lane b stores bin b of every output once.  No global atomics and no zero-fill: every
 // (halo, bin) cell is written exactly once, also for a halo without pixels.  fp64 throughout.
 #pragma once
+#include "bfgx_stack_core.hpp"
 
 namespace bfgx {
-
-constexpr int kStackMaxBins = 64;
-constexpr int kStackEdgeLds = 128;            // the edges padded with +inf to a power of two: a branch-free search
 
 struct StackArgs {
     const double *map, *g1, *g2;              // RING maps (g1 == nullptr: no shear pair)
     const double *M, *z;                      // catalog columns: M <= 0 / non-finite or z <= -1 is an invalid halo (all-zero row)
     const double *edges;                      // nb + 1 ascending bin edges
     int32_t nb, scaled;                       // scaled: x = r_sep / R_j instead of r_sep / a_j
-    int64_t *npix, *npix_shear;               // [nhalo][nb]
-    double *sum, *sum_t, *sum_x;
+    StackOut out;                             // [nhalo][nb]
 };
 
+template <bool SHEAR>
 struct StackWaveLds {
     RowLds rows;
-    double sum[kStackMaxBins], sum_t[kStackMaxBins], sum_x[kStackMaxBins];
-    unsigned int n[kStackMaxBins], ns[kStackMaxBins];      // (a disc holds fewer than 2^31 pixels: 12 * 8192^2 = 8.1e8)
+    StackBins<SHEAR> bins;                    // (a disc holds fewer than 2^31 pixels: 12 * 8192^2 = 8.1e8)
 };
 
 // healpy.mask_bad's rule (what sht::unseen_to_zero applies), or not finite
@@ -43,17 +40,17 @@ template <bool SHEAR>
 __global__ void __launch_bounds__(kWave * kWavesPerBlock)
 stack_profiles_kernel(Hpx h, Background bg, bfgx_massdef md, int64_t nhalo, const HaloRec *__restrict__ recs, StackArgs a)
 {
-    __shared__ StackWaveLds lds[kWavesPerBlock];
+    __shared__ StackWaveLds<SHEAR> lds[kWavesPerBlock];
     __shared__ double s_edges[kStackEdgeLds];
-    for (int i = threadIdx.x; i < kStackEdgeLds; i += blockDim.x) s_edges[i] = i <= a.nb ? a.edges[i] : __builtin_inf();
+    stack_load_edges(s_edges, a.edges, a.nb, threadIdx.x, blockDim.x);
     __syncthreads();
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int64_t j = (int64_t)blockIdx.x * kWavesPerBlock + wid;
     if (j >= nhalo) return;                      // whole wave exits together (no workgroup barrier below)
-    StackWaveLds &W = lds[wid];
-    RowLds &L = W.rows;
-    W.sum[lane] = 0.0; W.sum_t[lane] = 0.0; W.sum_x[lane] = 0.0; W.n[lane] = 0u; W.ns[lane] = 0u;
+    RowLds &L = lds[wid].rows;
+    StackBins<SHEAR> &B = lds[wid].bins;
+    B.clear(lane);
     const HaloRec &r = recs[j];
     const double M_j = a.M[j], z_j = a.z[j];
     const bool bad = !(M_j > 0.0) || !isfinite(M_j) || !(z_j > -1.0);
@@ -72,16 +69,10 @@ stack_profiles_kernel(Hpx h, Background bg, bfgx_massdef md, int64_t nhalo, cons
         const double dx = r.D * (vx - r.s0), dy = r.D * vy, dz = r.D * (z - r.z0);      // :435-437
         const double r_sep = sqrt(dx * dx + dy * dy + dz * dz);                         // :438
         const double x = r_sep / den;
-        int b = 0;                                  // largest b with edges[b] <= x (the padding is +inf)
-#pragma unroll
-        for (int st = kStackEdgeLds >> 1; st > 0; st >>= 1)
-            if (s_edges[b + st] <= x) b += st;
-        if (!(x >= e0) || b >= nb) return;          // outside [edges[0], edges[nb]), or NaN
-        if (stack_counts(m)) {
-            atomicAdd(&W.n[b], 1u);
-            atomicAdd(&W.sum[b], m);
-        }
-        if (SHEAR && stack_counts(ga) && stack_counts(gb)) {
+        const int b = stack_find_bin(s_edges, e0, x, nb);
+        if (b < 0) return;
+        if (stack_counts(m)) B.add(b, m);
+        if constexpr (SHEAR) if (stack_counts(ga) && stack_counts(gb)) {
             // tangent at the pixel towards the halo, on (e_theta, e_phi) = ((z cd, z sd, -sth), (-sd, cd, 0)):
             //   t_th = s0 z cd - z0 sth,  t_ph = -s0 sd.   t_th is a difference of nearly equal products for a nearby pixel: the two
             //   products carry their rounding errors along (two-product by fma), so that what is left is the rounding of the inputs
@@ -93,9 +84,7 @@ stack_profiles_kernel(Hpx h, Background bg, bfgx_massdef md, int64_t nhalo, cons
             if (n2 > 0.0) {                         // (the halo on the pixel centre has no position angle)
                 const double inv = 1.0 / n2;
                 const double c2 = (t_th - t_ph) * (t_th + t_ph) * inv, s2 = 2.0 * t_th * t_ph * inv;
-                atomicAdd(&W.ns[b], 1u);
-                atomicAdd(&W.sum_t[b], -(ga * c2 + gb * s2));
-                atomicAdd(&W.sum_x[b], ga * s2 - gb * c2);
+                B.add_shear(b, -(ga * c2 + gb * s2), ga * s2 - gb * c2);
             }
         }
     };
@@ -126,16 +115,7 @@ stack_profiles_kernel(Hpx h, Background bg, bfgx_massdef md, int64_t nhalo, cons
         }
     }
     __builtin_amdgcn_wave_barrier();
-    if (lane < nb) {
-        const int64_t o = j * nb + lane;
-        a.npix[o] = (int64_t)W.n[lane];
-        a.sum[o] = W.sum[lane];
-        if (SHEAR) {
-            a.npix_shear[o] = (int64_t)W.ns[lane];
-            a.sum_t[o] = W.sum_t[lane];
-            a.sum_x[o] = W.sum_x[lane];
-        }
-    }
+    if (lane < nb) B.store(lane, j * nb + lane, a.out);
 }
 
 }  // namespace bfgx

@@ -7,26 +7,17 @@
 
 namespace {
 
-struct StackOut { int64_t *npix, *npix_shear; double *sum, *sum_t, *sum_x; };
-
 // everything that can be refused without a device, before anything is allocated
 int stack_validate(const bfgx_catalog *cat, const bfgx_model *model, int64_t nside, const double *map, const double *g1, const double *g2,
                    int32_t nb, const double *r_edges, const StackOut &o)
 {
     if (!cat || !model || !map || !r_edges || !o.npix || !o.sum) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if ((g1 == nullptr) != (g2 == nullptr)) return fail(BFGX_ERR_INVALID, "NULL argument: the shear pair needs both g1 and g2");
-    if (g1 && (!o.npix_shear || !o.sum_t || !o.sum_x)) return fail(BFGX_ERR_INVALID, "NULL argument: a shear pair needs npix_shear, sum_t and sum_x");
-    if (nb < 1 || nb > kStackMaxBins) return fail(BFGX_ERR_INVALID, "%d radial bins: must be 1 .. %d (the bins of a halo live on chip)", (int)nb, kStackMaxBins);
-    for (int i = 0; i <= nb; ++i)
-        if (!std::isfinite(r_edges[i]) || r_edges[i] < 0.0) return fail(BFGX_ERR_INVALID, "r_edges must be finite and >= 0");
-    for (int i = 0; i < nb; ++i)
-        if (!(r_edges[i + 1] > r_edges[i])) return fail(BFGX_ERR_INVALID, "r_edges must be strictly ascending");
+    if (int rc = profiles_validate_shear(g1, g2, o)) return rc;
+    if (int rc = profiles_validate_bins(nb, r_edges)) return rc;
     if (nside < 1 || nside > 8192) return fail(BFGX_ERR_INVALID, "nside must be 1 .. 8192 (the tile kernels index pixels with 32 bits inside a ring table)");
     if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
     if (cat->n > 0 && (!cat->M || !cat->z || !cat->ra || !cat->dec)) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    if (int rc = validate_model(model)) return rc;
-    if (model->table.ndim != 3) return fail(BFGX_ERR_INVALID, "the profile measurement takes a model with a (dummy) 3-axis table: there is nothing to tabulate");
-    return BFGX_OK;
+    return profiles_validate_placeholder(model, false);
 }
 
 // K0 (no fallback, full records) + the stacking kernel on p->stream; edges_dev: nb + 1 doubles on the device
@@ -36,8 +27,7 @@ int stack_launch(bfgx_plan *p, const bfgx_catalog *dcat, const double *map, cons
     if (dcat->n == 0) return BFGX_OK;
     if (int rc = launch_prep(p, dcat, 0, false, false, true)) return rc;
     StackArgs a;
-    a.map = map; a.g1 = g1; a.g2 = g2; a.M = dcat->M; a.z = dcat->z; a.edges = edges_dev; a.nb = nb; a.scaled = scaled ? 1 : 0;
-    a.npix = o.npix; a.npix_shear = o.npix_shear; a.sum = o.sum; a.sum_t = o.sum_t; a.sum_x = o.sum_x;
+    a.map = map; a.g1 = g1; a.g2 = g2; a.M = dcat->M; a.z = dcat->z; a.edges = edges_dev; a.nb = nb; a.scaled = scaled ? 1 : 0; a.out = o;
     const unsigned grid = (unsigned)((dcat->n + kWavesPerBlock - 1) / kWavesPerBlock);
     if (g1)
         hipLaunchKernelGGL(stack_profiles_kernel<true>, dim3(grid), dim3(kWave * kWavesPerBlock), 0, p->stream, p->hpx, p->model.bg_runner,
@@ -91,15 +81,7 @@ int bfgx_shell_profiles(const bfgx_catalog *cat, const bfgx_model *model, int64_
     // device outputs, cells each: npix, sum[, npix_shear, sum_t, sum_x]
     const StackOut dv{(int64_t *)dout, (int64_t *)(dout + 2 * cells), dout + cells, dout + 3 * cells, dout + 4 * cells};
     if (int rc = stack_launch(p, &dcat, dmap, g1 ? dmap + npx : nullptr, g1 ? dmap + 2 * npx : nullptr, nb, (const double *)e->sums.p, scaled, dv)) return rc;
-    if (cells > 0) {
-        HIP_TRY(hipMemcpyAsync(npix, dv.npix, cells * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(sum, dv.sum, cells * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (g1) {
-            HIP_TRY(hipMemcpyAsync(npix_shear, dv.npix_shear, cells * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(sum_t, dv.sum_t, cells * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(sum_x, dv.sum_x, cells * sizeof(double), hipMemcpyDeviceToHost, s));
-        }
-    }
+    if (int rc = profiles_copy_back(s, ho, dv, cells, g1 != nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return BFGX_OK;
 }
