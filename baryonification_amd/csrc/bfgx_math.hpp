@@ -7,6 +7,38 @@
 
 namespace bfgx {
 
+// ---------------------------------------------------------------------------------- fp64 multiply-add with a constant addend
+// A Horner step p = fma(p, u, C) whose constant C lives in a register pair across a hot loop comes out of the compiler as TWO instructions:
+// it selects the two-address v_fmac_f64, whose addend is also the destination, and so copies C in front of every step (v_mov_b64 +
+// v_fmac_f64; a 64-bit move issues like fp64 arithmetic).  The three-address v_fma_f64 needs no copy, and the compiler selects it wherever
+// an operand carries a source modifier, which v_fmac_f64 cannot encode.  So a KReg holds -C and fma_k negates it again with the modifier:
+// one instruction, the same fma on the same operands, bit for bit, and nothing around it that the scheduler has to pad.
+// The empty asm statement hides the value from constant folding, which would undo the negation.  It is volatile and therefore stays where
+// the KReg is constructed: construct the constants of a kernel ONCE at its top (as a statement inside the loop it would cost the copy it
+// is meant to remove), and pass them down by reference.  Every KReg holds a VGPR pair for the whole kernel.
+// Addends that are inline constants of the ISA (0.5, 1.0, 2.0, 4.0 and their negatives) need none of this: plain fma yields v_fma_f64.
+struct KReg {
+    double neg;
+    __device__ __forceinline__ KReg(double c) : neg(-c) { asm volatile("" : "+v"(neg)); }
+};
+__device__ __forceinline__ double fma_k(double a, double b, const KReg &c) { return __builtin_fma(a, b, -c.neg); }
+// (the same series with literal constants -- T = double -- is the code it was: K0, the row phases and every kernel that has no registers to spare)
+__device__ __forceinline__ double fma_k(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float fma_k(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// the constants of fast_log and sincos_small, as literals (T = double) or held in registers (T = KReg)
+template <typename T> struct LogK {
+    T c19, c17, c15, c13, c11, c9, c7, c5, c3;
+    __device__ __forceinline__ LogK() : c19(1.0 / 19.0), c17(1.0 / 17.0), c15(1.0 / 15.0), c13(1.0 / 13.0), c11(1.0 / 11.0), c9(1.0 / 9.0), c7(1.0 / 7.0),
+                                        c5(1.0 / 5.0), c3(1.0 / 3.0) {}
+};
+template <typename T> struct SinCosK {
+    T s13, s11, s9, s7, s5, s3, c14, c12, c10, c8, c6, c4;
+    __device__ __forceinline__ SinCosK() : s13(1.0 / 6227020800.0), s11(-1.0 / 39916800.0), s9(1.0 / 362880.0), s7(-1.0 / 5040.0), s5(1.0 / 120.0), s3(-1.0 / 6.0),
+                                           c14(-1.0 / 87178291200.0), c12(1.0 / 479001600.0), c10(-1.0 / 3628800.0), c8(1.0 / 40320.0), c6(-1.0 / 720.0),
+                                           c4(1.0 / 24.0) {}
+};
+
 // 1/x for normal x (2 Newton steps on the hardware seed)
 __device__ inline double fast_rcp(double x)
 {
@@ -30,7 +62,8 @@ __device__ inline double fast_rsq(double x)
 }
 
 // ln(x) for finite normal x > 0:  x = m 2^e, m in [sqrt(1/2), sqrt(2)),  ln m = 2 atanh((m-1)/(m+1))
-__device__ inline double fast_log(double x)
+template <typename T>
+__device__ inline double fast_log(double x, const LogK<T> &k)
 {
     double m = __builtin_amdgcn_frexp_mant(x);            // [0.5, 1)
     int e = __builtin_amdgcn_frexp_exp(x);
@@ -40,20 +73,21 @@ __device__ inline double fast_log(double x)
     const double s = (m - 1.0) * fast_rcp(m + 1.0);
     const double u = s * s;
     double p = 1.0 / 21.0;
-    p = __builtin_fma(p, u, 1.0 / 19.0);
-    p = __builtin_fma(p, u, 1.0 / 17.0);
-    p = __builtin_fma(p, u, 1.0 / 15.0);
-    p = __builtin_fma(p, u, 1.0 / 13.0);
-    p = __builtin_fma(p, u, 1.0 / 11.0);
-    p = __builtin_fma(p, u, 1.0 / 9.0);
-    p = __builtin_fma(p, u, 1.0 / 7.0);
-    p = __builtin_fma(p, u, 1.0 / 5.0);
-    p = __builtin_fma(p, u, 1.0 / 3.0);
+    p = fma_k(p, u, k.c19);
+    p = fma_k(p, u, k.c17);
+    p = fma_k(p, u, k.c15);
+    p = fma_k(p, u, k.c13);
+    p = fma_k(p, u, k.c11);
+    p = fma_k(p, u, k.c9);
+    p = fma_k(p, u, k.c7);
+    p = fma_k(p, u, k.c5);
+    p = fma_k(p, u, k.c3);
     const double lm = __builtin_fma(2.0 * s * u, p, 2.0 * s);
     const double fe = (double)e;
     // ln 2 split so that fe * hi is exact for |e| < 2^11
     return __builtin_fma(fe, 0.693147180369123816490, __builtin_fma(fe, 1.90821492927058770002e-10, lm));
 }
+__device__ inline double fast_log(double x) { return fast_log(x, LogK<double>()); }
 
 // exp(x) for any double: x = k ln2 + r, |r| <= ln2 / 2 (two-term ln 2, FMA), Taylor to r^13 (truncation < 3e-18 relative),
 // scaling by ldexp.  Branch-free; +inf above 709.78, 0 below -745.2, NaN stays NaN.  ~1 ulp.
@@ -84,27 +118,29 @@ __device__ inline double fast_exp(double x)
 }
 
 // sin/cos for |x| <= 0.5 (Taylor to x^15 / x^16: truncation < 3e-20)
-__device__ inline void sincos_small(double x, double &s, double &c)
+template <typename T>
+__device__ inline void sincos_small(double x, double &s, double &c, const SinCosK<T> &k)
 {
     const double u = x * x;
     double ps = -1.0 / 1307674368000.0;
-    ps = __builtin_fma(ps, u, 1.0 / 6227020800.0);
-    ps = __builtin_fma(ps, u, -1.0 / 39916800.0);
-    ps = __builtin_fma(ps, u, 1.0 / 362880.0);
-    ps = __builtin_fma(ps, u, -1.0 / 5040.0);
-    ps = __builtin_fma(ps, u, 1.0 / 120.0);
-    ps = __builtin_fma(ps, u, -1.0 / 6.0);
+    ps = fma_k(ps, u, k.s13);
+    ps = fma_k(ps, u, k.s11);
+    ps = fma_k(ps, u, k.s9);
+    ps = fma_k(ps, u, k.s7);
+    ps = fma_k(ps, u, k.s5);
+    ps = fma_k(ps, u, k.s3);
     s = __builtin_fma(x * u, ps, x);
     double pc = 1.0 / 20922789888000.0;
-    pc = __builtin_fma(pc, u, -1.0 / 87178291200.0);
-    pc = __builtin_fma(pc, u, 1.0 / 479001600.0);
-    pc = __builtin_fma(pc, u, -1.0 / 3628800.0);
-    pc = __builtin_fma(pc, u, 1.0 / 40320.0);
-    pc = __builtin_fma(pc, u, -1.0 / 720.0);
-    pc = __builtin_fma(pc, u, 1.0 / 24.0);
+    pc = fma_k(pc, u, k.c14);
+    pc = fma_k(pc, u, k.c12);
+    pc = fma_k(pc, u, k.c10);
+    pc = fma_k(pc, u, k.c8);
+    pc = fma_k(pc, u, k.c6);
+    pc = fma_k(pc, u, k.c4);
     pc = __builtin_fma(pc, u, -0.5);
     c = __builtin_fma(u, pc, 1.0);
 }
+__device__ inline void sincos_small(double x, double &s, double &c) { sincos_small(x, s, c, SinCosK<double>()); }
 
 // sin/cos for |x| <~ 1e3: Cody-Waite reduction by pi/2 (two-term, FMA) + Taylor on [-pi/4, pi/4]; branch-free
 __device__ inline void sincos_bounded(double x, double &s, double &c)

@@ -57,19 +57,33 @@ template <> struct PMath<float> {
     }
     static __device__ inline bool finite(float v) { return __builtin_isfinite(v); }
     static __device__ inline float med3(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
+    // the constants a kernel hands to its pair phase (see PMathE::KT): fp32 keeps its literals
+    struct K { float g2 = -0.3125f, g3 = 0.375f; };
+    using KLit = K;
+    static __device__ inline float half_ln(float x, const K &) { return half_ln(x); }
+    static __device__ inline void sin_omc(float x, float &sn, float &omc, const K &) { sin_omc(x, sn, omc); }
 };
 
 template <> struct PMath<double> {
     static constexpr double kHuge = 1.0e37;
     static __device__ inline double rsq(double x) { return fast_rsq(x); }
-    static __device__ inline double half_ln(double x) { return 0.5 * fast_log(x); }
-    static __device__ inline void sin_omc(double x, double &sn, double &omc)
+    // the constants of the pair phase: K = held in registers from the top of the kernel (fma_k, bfgx_math.hpp), KLit = literals
+    template <typename T> struct KT {
+        LogK<T> ln; SinCosK<T> sc; T g2, g3;
+        __device__ __forceinline__ KT() : g2(-0.3125), g3(0.375) {}
+    };
+    using K = KT<KReg>;
+    using KLit = KT<double>;
+    template <typename T> static __device__ inline double half_ln(double x, const KT<T> &k) { return 0.5 * fast_log(x, k.ln); }
+    template <typename T> static __device__ inline void sin_omc(double x, double &sn, double &omc, const KT<T> &k)
     {
         double sh, ch;
-        sincos_small(0.5 * x, sh, ch);                                     // half angle: 1 - cos x = 2 sin^2(x/2), no cancellation
+        sincos_small(0.5 * x, sh, ch, k.sc);                               // half angle: 1 - cos x = 2 sin^2(x/2), no cancellation
         sn = 2.0 * sh * ch;
         omc = 2.0 * sh * sh;
     }
+    static __device__ inline double half_ln(double x) { return half_ln(x, KLit()); }
+    static __device__ inline void sin_omc(double x, double &sn, double &omc) { sin_omc(x, sn, omc, KLit()); }
     static __device__ inline double expv(double d) { return fast_exp(d); }
     static __device__ inline bool finite(double v) { return __builtin_isfinite(v); }
     static __device__ inline double med3(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
@@ -88,7 +102,16 @@ struct PMathE {
         const double h = 0.5 * y, e = __builtin_fma(-x * y, h, 0.5);
         return __builtin_fma(y, e, y);                                   // 1.5 (1.5e-7)^2
     }
-    static __device__ inline double half_ln(double x)
+    // the constants of the series below and of the renormalisation series of pair_back: K = held in registers from the top of the kernel
+    // (fma_k, bfgx_math.hpp: the K1 pair loop), KLit = literals (K2, which has no registers to spare)
+    template <typename T> struct KT {
+        T l9, l7, l5, l3, s7, s5, s3, c8, c6, c4, g2, g3;
+        __device__ __forceinline__ KT() : l9(1.0 / 9.0), l7(1.0 / 7.0), l5(1.0 / 5.0), l3(1.0 / 3.0), s7(-1.0 / 5040.0), s5(1.0 / 120.0), s3(-1.0 / 6.0),
+                                          c8(-1.0 / 40320.0), c6(1.0 / 720.0), c4(-1.0 / 24.0), g2(-0.3125), g3(0.375) {}
+    };
+    using K = KT<KReg>;
+    using KLit = KT<double>;
+    template <typename T> static __device__ inline double half_ln(double x, const KT<T> &k)
     {
         double m = __builtin_amdgcn_frexp_mant(x);
         int e = __builtin_amdgcn_frexp_exp(x);
@@ -100,29 +123,31 @@ struct PMathE {
         y = __builtin_fma(y, __builtin_fma(-den, y, 1.0), y);
         const double s = (m - 1.0) * y, u = s * s;                       // |s| <= 0.1716: the series to s^11 leaves u^6 / 13 = 5e-11
         double p = 1.0 / 11.0;
-        p = __builtin_fma(p, u, 1.0 / 9.0);
-        p = __builtin_fma(p, u, 1.0 / 7.0);
-        p = __builtin_fma(p, u, 1.0 / 5.0);
-        p = __builtin_fma(p, u, 1.0 / 3.0);
+        p = fma_k(p, u, k.l9);
+        p = fma_k(p, u, k.l7);
+        p = fma_k(p, u, k.l5);
+        p = fma_k(p, u, k.l3);
         const double hl = __builtin_fma(s * u, p, s);                    // ln(m) / 2
         return __builtin_fma((double)e, 0.34657359027997264, hl);
     }
     static __device__ inline double expv(double d) { return fast_exp(d); }
-    static __device__ inline void sin_omc(double x, double &sn, double &omc)      // |x| <= 0.5: x^11 / 11! and x^12 / 12! dropped (2e-11, 4e-12)
+    template <typename T> static __device__ inline void sin_omc(double x, double &sn, double &omc, const KT<T> &k)      // |x| <= 0.5: x^11 / 11! and x^12 / 12! dropped (2e-11, 4e-12)
     {
         const double u = x * x;
         double ps = 1.0 / 362880.0;
-        ps = __builtin_fma(ps, u, -1.0 / 5040.0);
-        ps = __builtin_fma(ps, u, 1.0 / 120.0);
-        ps = __builtin_fma(ps, u, -1.0 / 6.0);
+        ps = fma_k(ps, u, k.s7);
+        ps = fma_k(ps, u, k.s5);
+        ps = fma_k(ps, u, k.s3);
         sn = __builtin_fma(x * u, ps, x);
         double pc = 1.0 / 3628800.0;
-        pc = __builtin_fma(pc, u, -1.0 / 40320.0);
-        pc = __builtin_fma(pc, u, 1.0 / 720.0);
-        pc = __builtin_fma(pc, u, -1.0 / 24.0);
+        pc = fma_k(pc, u, k.c8);
+        pc = fma_k(pc, u, k.c6);
+        pc = fma_k(pc, u, k.c4);
         pc = __builtin_fma(pc, u, 0.5);
         omc = u * pc;
     }
+    static __device__ inline double half_ln(double x) { return half_ln(x, KLit()); }
+    static __device__ inline void sin_omc(double x, double &sn, double &omc) { sin_omc(x, sn, omc, KLit()); }
     static __device__ inline bool finite(double v) { return __builtin_isfinite(v); }
     static __device__ inline double med3(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
 };
@@ -282,8 +307,8 @@ struct PairMid {
     bool ok, in;                  // active and inside the radial axis; inside the model-side cut
 };
 
-template <bool FAR>
-__device__ inline void pair_front(PairMid &s, const Tab8T<double> &tb, const RowC2<double> rc, const PairRecT<double> *pairs,
+template <bool FAR, typename KK>
+__device__ inline void pair_front(PairMid &s, const KK &kk, const Tab8T<double> &tb, const RowC2<double> rc, const PairRecT<double> *pairs,
                                   const RingC2<double> *ringc, int t, bool act)
 {
     using PMt = PMathE;
@@ -294,7 +319,7 @@ __device__ inline void pair_front(PairMid &s, const Tab8T<double> &tb, const Row
     s.pk = rc.pk;
     const double x = fma_((double)jj, rg.dphi, rc.x0);
     double sn, omc;
-    PMt::sin_omc(x, sn, omc);
+    PMt::sin_omc(x, sn, omc, kk);
     if (FAR) {
         if (act && !(fabs(x) <= 0.5)) { const double2 w = sin_omc_wide(x); sn = w.x; omc = w.y; }
     }
@@ -302,7 +327,7 @@ __device__ inline void pair_front(PairMid &s, const Tab8T<double> &tb, const Row
     const double u2 = ux * ux + uy * uy + uz * uz;
     const double u2s = (u2 > 1e-37) ? u2 : 1e-37;
     s.rinv = PMt::rsq(u2s);
-    const double lx = PMt::half_ln(u2s * ph.scale2);
+    const double lx = PMt::half_ln(u2s * ph.scale2, kk);
     s.ok = act && (lx >= tb.r0) && (lx <= tb.r1);
     const double uu = (lx - tb.r0) * tb.inv_dr;
     const double uc = PMt::med3(uu, 0.0, (double)(tb.nr - 2));
@@ -320,7 +345,8 @@ __device__ inline void pair_front(PairMid &s, const Tab8T<double> &tb, const Row
     s.ux = ux; s.uy = uy; s.uz = uz; s.u2 = u2;
 }
 
-__device__ inline void pair_back(PairEval<double> &o, const PairMid &s, const PairRecT<double> *pairs, const RingC2<double> *ringc, int t,
+template <typename KK>
+__device__ inline void pair_back(PairEval<double> &o, const PairMid &s, const KK &kk, const PairRecT<double> *pairs, const RingC2<double> *ringc, int t,
                                  int wsh, int wmask)
 {
     using PMt = PMathE;
@@ -340,8 +366,8 @@ __device__ inline void pair_back(PairEval<double> &o, const PairMid &s, const Pa
     const double fx = s.fx, fy = s.uy, fz = ringc[rl].zf;
     const double tt = sc * s.u2 * (1.0 + sc);
     double g = 35.0 / 128.0;
-    g = fma_(g, tt, -0.3125);
-    g = fma_(g, tt, 0.375);
+    g = fma_k(g, tt, kk.g2);
+    g = fma_k(g, tt, kk.g3);
     g = fma_(g, tt, -0.5);
     g = g * tt;
     const double c1 = fma_(g, sc, sc);
@@ -352,15 +378,15 @@ __device__ inline void pair_back(PairEval<double> &o, const PairMid &s, const Pa
 }
 
 // Branch-free evaluation of pair t of the current row block.
-template <int MODE, typename real, bool FAR = false, int PM = 0>
-__device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const RowC2<real> rc, const PairRecT<real> *pairs,
+template <int MODE, typename real, bool FAR = false, int PM = 0, typename KK>
+__device__ inline void pair_eval(PairEval<real> &o, const KK &kk, const Tab8T<real> &tb, const RowC2<real> rc, const PairRecT<real> *pairs,
                                  const RingC2<real> *ringc, int t, bool act, int wsh, int wmask)
 {
     if constexpr (PM == 1) {                                           // (the parity-grade pair, unpipelined: the WIDE copy of the row pass)
         static_assert(MODE == MODE_OFFSETS && sizeof(real) == 8, "PM = 1: fp64 pair math of the displacement kernel");
         PairMid s;
-        pair_front<FAR>(s, tb, rc, pairs, ringc, t, act);
-        pair_back(o, s, pairs, ringc, t, wsh, wmask);
+        pair_front<FAR>(s, kk, tb, rc, pairs, ringc, t, act);
+        pair_back(o, s, kk, pairs, ringc, t, wsh, wmask);
         return;
     }
     using PMt = typename PMSel<real, PM>::type;
@@ -372,7 +398,7 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
     o.hidx = ph.hidx;
     const real x = fma_((real)jj, rg.dphi, rc.x0);
     real sn, omc;
-    PMt::sin_omc(x, sn, omc);
+    PMt::sin_omc(x, sn, omc, kk);
     if (FAR) {                                                         // (a row pass that holds pairs beyond 0.5 rad of their halo's azimuth: k1_chunk)
         if (act && !(fabs((double)x) <= 0.5)) { const double2 w = sin_omc_wide((double)x); sn = (real)w.x; omc = (real)w.y; }
     }
@@ -387,7 +413,7 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
     bool ok = act;
     const real u2s = (u2 > (real)1e-37) ? u2 : (real)1e-37;
     const real rinv = PMt::rsq(u2s);                                // 1 / |u|
-    const real lx = PMt::half_ln(u2s * ph.scale2);                  // ln(r_sep / a) [- ln R when Rdelta]
+    const real lx = PMt::half_ln(u2s * ph.scale2, kk);              // ln(r_sep / a) [- ln R when Rdelta]
     ok = ok && (lx >= tb.r0) && (lx <= tb.r1);                     // RGI fill_value = nan
     const real uu = (lx - tb.r0) * tb.inv_dr;
     const real uc = PMt::med3(uu, (real)0, (real)(tb.nr - 2));      // (clamped BEFORE the conversion: uu may be +-huge)
@@ -429,8 +455,8 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
     // v.u = v.(v - v_halo) = 1 - v.v_halo = |u|^2 / 2 for unit vectors, so t = 2 v.e + e.e = sc |u|^2 (1 + sc): no dot products
     const real tt = sc * u2 * ((real)1 + sc);
     real g = (real)(35.0 / 128.0);
-    g = fma_(g, tt, (real)-0.3125);
-    g = fma_(g, tt, (real)0.375);
+    g = fma_k(g, tt, kk.g2);
+    g = fma_k(g, tt, kk.g3);
     g = fma_(g, tt, (real)-0.5);
     g = g * tt;
     const real c1 = fma_(g, sc, sc);                               // e + g (v + e) = (1 + g) sc u + g v
@@ -446,8 +472,8 @@ __device__ inline void pair_eval(PairEval<real> &o, const Tab8T<real> &tb, const
 // last trip -- the only one of a row pass of up to 64 pairs -- has no front half beside it.  The mask word of a trip is wave-uniform and is
 // fetched a trip ahead; the row record is read at the top of the front half.
 // (Tag: the caller's narrow / wide tag, which keeps the call dependent inside k1_chunk's generic lambda; only the narrow copy comes here.)
-template <typename Tag, typename real>
-__device__ __forceinline__ void k1_pairs_rotated(Tag, const Tab8T<real> &tb, Wave2Lds<real> &L, const RingC2<real> *ringc, double *acc, int PL,
+template <typename Tag, typename real, typename KK>
+__device__ __forceinline__ void k1_pairs_rotated(Tag, const KK &kk, const Tab8T<real> &tb, Wave2Lds<real> &L, const RingC2<real> *ringc, double *acc, int PL,
                                                  int total, int lane, int wsh, int wmask)
 {
     static_assert(!Tag::value && sizeof(real) == 8, "the narrow copy of the fp64 pair phase");
@@ -460,11 +486,11 @@ __device__ __forceinline__ void k1_pairs_rotated(Tag, const Tab8T<real> &tb, Wav
         const int row = base + below + (int)((m >> lane) & 1ull) - 1;
         base += __popcll(m);
         const bool act = T + lane < total;
-        pair_front<false>(s, tb, L.rows[act ? row : 0], L.pair, ringc, T + lane, act);
+        pair_front<false>(s, kk, tb, L.rows[act ? row : 0], L.pair, ringc, T + lane, act);
     };
     auto back = [&](const PairMid &s, int T) __attribute__((always_inline)) {
         PairEval<double> pv;
-        pair_back(pv, s, L.pair, ringc, T + lane, wsh, wmask);
+        pair_back(pv, s, kk, L.pair, ringc, T + lane, wsh, wmask);
         if (pv.ok) {
             atomicAdd(acc + pv.la, pv.v0);                     // ds_add_f64
             atomicAdd(acc + PL + pv.la, pv.v1);
@@ -498,8 +524,8 @@ __device__ __forceinline__ void k1_pairs_rotated(Tag, const Tab8T<real> &tb, Wav
 // ---------------------------------------------------------------------------------- one chunk of a tile's entry list
 // What a wave does with one chunk -- the entries [ebeg, ebeg + ecnt), ecnt <= kChunk2 -- of a tile's narrow-halo list: entries -> ring rows -> pairs, accumulated into the tile's
 // LDS planes `acc`.  Shared by the barrier-per-tile kernel (tile_scatter2_kernel) and the fluid kernel (tile_scatter2f_kernel).
-template <int MODE, typename real, int NP, int PM = 0, bool PIPE = (PM == 1)>
-__device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__restrict__ rowrecs, const PairRecT<real> *__restrict__ pairrecs,
+template <int MODE, typename real, int NP, int PM = 0, bool PIPE = (PM == 1), typename KK>
+__device__ __forceinline__ void k1_chunk(const KK &kk, const Tab8T<real> &tb, const RowRec *__restrict__ rowrecs, const PairRecT<real> *__restrict__ pairrecs,
                                          const FbRec *__restrict__ fbrecs, const int32_t *__restrict__ ea, const int32_t *__restrict__ eb,
                                          int na, int ebeg, int ecnt, int estride, int i0, int i1, int nphi, int wsh, int wmask, int PL,
                                          double *acc, Wave2Lds<real> &L, const TileRow *rowtab, const RingC2<real> *ringc, int lane,
@@ -628,7 +654,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
             // the LDS reads and table loads of the NP pairs are in flight together
             if constexpr (PIPE && !WIDE) {
                 static_assert(NP == 1 && MODE == MODE_OFFSETS, "the rotated pair loop takes one pair per lane and trip");
-                k1_pairs_rotated(wide_tag, tb, L, ringc, acc, PL, total, lane, wsh, wmask);
+                k1_pairs_rotated(wide_tag, kk, tb, L, ringc, acc, PL, total, lane, wsh, wmask);
             } else {
                 int base = 0;                                      // rows started before the current 64 pairs
                 // the mask word and the row record of the NEXT trip are fetched while this trip computes
@@ -661,7 +687,7 @@ __device__ __forceinline__ void k1_chunk(const Tab8T<real> &tb, const RowRec *__
     #pragma unroll
                     for (int u = 0; u < NP; ++u) {
                         const int t = T0 + u * kWave + lane;
-                        pair_eval<MODE, real, WIDE, PM>(pv[u], tb, rc_cur[u], L.pair, ringc, t, t < total, wsh, wmask);
+                        pair_eval<MODE, real, WIDE, PM>(pv[u], kk, tb, rc_cur[u], L.pair, ringc, t, t < total, wsh, wmask);
                     }
                     if (MODE == MODE_OFFSETS && sizeof(real) == 4) {
                         // pairs whose fp32 chord is within 4e-6 of the model-side cut (BaryonCorrection.py:381-382): decide in fp64 (rare)
@@ -714,6 +740,9 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
     static_assert(PM == 0 || (MODE == MODE_OFFSETS && sizeof(ACC) == 4 && sizeof(real) == 8), "PM = 1: fp64 pair math into split fp32 pix_offsets");
     // (form: which of the fast kernel's two forms runs was left to the device -- both are launched, the other one returns here)
     if (form != nullptr && *form != my_form) return;
+    // the fp64 constants of the pair phase, into registers once (the displacement kernels; painting and the census keep literals)
+    using KK = typename std::conditional<MODE == MODE_OFFSETS, typename PMSel<real, PM>::type::K, typename PMSel<real, PM>::type::KLit>::type;
+    const KK pk{};
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     // persistent workgroups (two per CU): tiles are drawn from a device counter in the order of T.tile_order -- heavy
@@ -795,7 +824,7 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
         c = __builtin_amdgcn_readfirstlane(c);
         if (c >= nchunks) break;
 
-        k1_chunk<MODE, real, NP, PM>(tb, rowrecs, pairrecs, fbrecs, ea, eb, na, c * csz, min(csz, ne - c * csz), 1, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
+        k1_chunk<MODE, real, NP, PM>(pk, tb, rowrecs, pairrecs, fbrecs, ea, eb, na, c * csz, min(csz, ne - c * csz), 1, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
                                      lane, npairs);
     }
     __syncthreads();
@@ -907,6 +936,9 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
     static_assert(MODE == MODE_OFFSETS || MODE == MODE_PAINT, "the census runs in tile_scatter2_kernel");
     static_assert(PM == 0 || (MODE == MODE_OFFSETS && sizeof(ACC) == 4 && sizeof(real) == 8), "PM = 1: fp64 pair math into split fp32 pix_offsets");
     constexpr int kWF = FluidWaves<real>::n;
+    // the fp64 constants of the pair phase, into registers once (the displacement kernels; painting and the census keep literals)
+    using KK = typename std::conditional<MODE == MODE_OFFSETS, typename PMSel<real, PM>::type::K, typename PMSel<real, PM>::type::KLit>::type;
+    const KK pk{};
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     const int PL = T.BR * T.W + kPlanePad;
@@ -1142,7 +1174,7 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             const int ebeg = c < nchb ? na + c * kChunkB : c - nchb;
             const int ecnt = c < nchb ? min(kChunkB, ne - ebeg) : (na - ebeg + ncha - 1) / ncha;
             const int estride = c < nchb ? 1 : ncha;
-            k1_chunk<MODE, real, (sizeof(real) == 4 ? kK1fNP : 1), PM>(tb, rowrecs, pairrecs, fbrecs, ea, eb, na, ebeg, ecnt, estride, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
+            k1_chunk<MODE, real, (sizeof(real) == 4 ? kK1fNP : 1), PM>(pk, tb, rowrecs, pairrecs, fbrecs, ea, eb, na, ebeg, ecnt, estride, i0, i1, nphi, wsh, wmask, PL, acc, L, rowtab, ringc,
                                     lane, npairs);
         }
         // leave tile k; the last wave out starts the flush, takes part in it, and refills the slot when the last row group is done
