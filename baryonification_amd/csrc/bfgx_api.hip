@@ -2066,7 +2066,7 @@ int bfgx_displacement_rows(int device, int64_t nrows, int32_t nr, const double *
     if (dr.up(r, sizeof(double) * nr) || da.up(M_dmo, sizeof(double) * nrows * nr) || db.up(M_dmb, sizeof(double) * nrows * nr) ||
         dd.up(nullptr, sizeof(double) * nrows * nr) || ds.up(nullptr, sizeof(int32_t) * nrows))
         return fail(BFGX_ERR_HIP, "device allocation/copy failed");
-    const size_t lds = sizeof(double) * 7 * nr + sizeof(int) * 2 * nr;
+    const size_t lds = kDisplacementLdsPerNode * nr;
     HIP_TRY(hipFuncSetAttribute((const void *)displacement_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(displacement_kernel, dim3((unsigned)nrows), dim3(256), lds, 0, nr, dr.as<double>(), da.as<double>(),
                        db.as<double>(), dd.as<double>(), ds.as<int32_t>());

@@ -31,7 +31,7 @@ __device__ inline double block_excl_scan_sum(double v, double *sh /*[kTabThreads
         __syncthreads();
     }
     total = sh[kTabThreads - 1];
-    const double r = sh[tid] - v;
+    const double r = tid ? sh[tid - 1] : 0.0;           // (not sh[tid] - v: inf - inf would poison the thread that holds an inf)
     __syncthreads();
     return r;
 }
@@ -190,7 +190,22 @@ enclosed_mass_kernel(int64_t n, const double *__restrict__ r_int, const double *
 
 // ------------------------------------------------------------------ K4b
 // one block (256) per row; N_R <= kMaxNR.  status: 0 ok, 1 iterate > 30, 2 fewer than 5 usable points.
-constexpr int kMaxNR = 4096;
+// The whole row lives in LDS: seven doubles and two ints per node (dynamic) behind the block's reduction arrays and
+// flags (static, DisplacementShared).  kMaxNR is the largest N_R for which both fit the 160 KiB a workgroup can have
+// on gfx950: (163 840 - 3104) / 64 = 2511.  The builder runs once per model; nobody asks for more radial nodes.
+struct DisplacementShared {
+    double red_d[256];
+    double min;
+    int red_i[256];
+    int cnt, iter, stat, na, nb;
+};
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;                                       // gfx950
+constexpr size_t kDisplacementLdsPerNode = 7 * sizeof(double) + 2 * sizeof(int);
+constexpr size_t kDisplacementLdsStatic = (sizeof(DisplacementShared) + 15) / 16 * 16;   // the dynamic part is 16-aligned
+constexpr int kMaxNR = (int)((kLdsPerWorkgroup - kDisplacementLdsStatic) / kDisplacementLdsPerNode);
+static_assert(kDisplacementLdsStatic + kDisplacementLdsPerNode * kMaxNR <= kLdsPerWorkgroup &&
+              kDisplacementLdsStatic + kDisplacementLdsPerNode * (kMaxNR + 1) > kLdsPerWorkgroup && kMaxNR == 2511,
+              "kMaxNR must be the largest N_R whose LDS layout fits one workgroup");
 
 __global__ void __launch_bounds__(256)
 displacement_kernel(int nr, const double *__restrict__ r, const double *__restrict__ M_dmo, const double *__restrict__ M_dmb,
@@ -204,10 +219,11 @@ displacement_kernel(int nr, const double *__restrict__ r, const double *__restri
     double *bx = ay + nr, *by = bx + nr;               // compacted DMO: (ln r, ln M_DMO)
     int *mask = reinterpret_cast<int *>(by + nr);
     int *prev = mask + nr;                             // previous masked index (-1: none)
-    __shared__ int s_cnt, s_iter, s_stat, s_na, s_nb;
-    __shared__ double s_min;
-    __shared__ int red_i[256];
-    __shared__ double red_d[256];
+    __shared__ DisplacementShared sh;
+    int &s_cnt = sh.cnt, &s_iter = sh.iter, &s_stat = sh.stat, &s_na = sh.na, &s_nb = sh.nb;
+    double &s_min = sh.min;
+    int *red_i = sh.red_i;
+    double *red_d = sh.red_d;
     const int row = blockIdx.x, tid = threadIdx.x;
     for (int i = tid; i < nr; i += 256) {
         lb[i] = log(M_dmb[(int64_t)row * nr + i]);

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 
 N_INT_2D = 50_000
+MAX_N_R = 2511          # displacement_rows: the most radial nodes whose row fits one workgroup's LDS (csrc/bfgx_tables.hpp)
 
 
 def los_grid(r, padding_lo=0.1, padding_hi=10.0, n_per_decade=10, proj_cutoff=None):

@@ -342,6 +342,8 @@ int  bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat_dev, int fall
  *                                 r_int = geomspace(min(r,1e-6)/1.2, max(r,1000)*1.2, 50 000), rho<0 -> 0,
  *                                 cumsum(4 pi r^3 rho dlnr), log-log PCHIP at r over the points with rho > 0
  *   bfgx_displacement_rows        setup_interpolator's per-mass loop body, BaryonCorrection.py:226-301;
+ *                                 3 <= N_R <= 2511 (a row is held in one workgroup's 160 KiB of LDS, 64 B per node
+ *                                 behind 3104 B of reduction arrays), anything else is BFGX_ERR_INVALID;
  *                                 status[row]: 0 ok, 1 mass profile nearly constant (iterate > 30),
  *                                 2 fewer than 5 usable points -- both give d = 0 and warrant the reference's warning
  *   bfgx_pressure_profile         Pressure._real, Profiles/Thermodynamic.py:240-271 (cgs), r500 = geomspace(1e-6,1e3,500) */

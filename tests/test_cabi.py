@@ -103,3 +103,22 @@ def test_round5_entries_refuse_bad_arguments_before_any_device_call():
     assert L.bfgx_baryonify_snapshot_records_map(None, None, 3, 100.0, 0.0, 0, None, 32, 8, 16, 24, 0, 8, None, None, None, C.byref(st)) == _lib.ERR_INVALID
     assert L.bfgx_offsets_regrid_bands_device(None, None, 0, 1, None, 0, 0, 1, None, None, None, None) == _lib.ERR_INVALID
     assert b'NULL' in L.bfgx_last_error()
+
+
+def test_displacement_rows_refuses_row_lengths_that_cannot_launch():
+    """displacement_kernel holds a row in one workgroup's LDS: 64 B per node (seven doubles, two ints) behind 3104 B of
+    reduction arrays, 163 840 B in all, so 2511 nodes at the most.  Longer and too short rows are refused with that
+    number before any device call (so also on a machine without a GPU)."""
+    import ctypes as C
+    from baryonification_amd import tables
+    assert tables.MAX_N_R == (160 * 1024 - 3104) // (7 * 8 + 2 * 4) == 2511
+    L = _lib.load()
+    for nr in (tables.MAX_N_R + 1, 4096, 2):
+        r = np.geomspace(1e-3, 1e2, nr)
+        M = np.ones((1, nr))
+        d, st = np.empty((1, nr)), np.empty(1, dtype=np.int32)
+        rc = L.bfgx_displacement_rows(0, 1, nr, r.ctypes.data, M.ctypes.data, M.ctypes.data, d.ctypes.data, st.ctypes.data)
+        assert rc == _lib.ERR_INVALID
+        assert b'[3, %d]' % tables.MAX_N_R in L.bfgx_last_error()
+    with pytest.raises(ValueError, match=str(tables.MAX_N_R)):
+        tables.displacement_rows(np.geomspace(1e-3, 1e2, tables.MAX_N_R + 1), np.ones((1, tables.MAX_N_R + 1)), np.ones((1, tables.MAX_N_R + 1)))
