@@ -25,6 +25,7 @@
 #include "../../include/bfgx.h"
 
 #include "bfgx_devmem.hpp"
+#include "bfgx_tile_arena.hpp"
 #include "bfgx_cosmo.hpp"
 #include "bfgx_kernels.hpp"
 #include "bfgx_scatter2.hpp"
@@ -116,20 +117,16 @@ struct bfgx_plan {
     int k1_wide = 1;                // the fast kernel takes the WIDE discs too (a pole inside, pixels beyond 0.40 rad of the halo's azimuth: RowRec.fb bit 1) and the generic kernel's wide pass is not launched; BFGX_K1_WIDE=0 at plan creation: they go through the wide pass (tests: the two must agree)
     int k1_fluid = 1;               // the fast kernel's fluid form (bfgx_scatter2.hpp): 1 = from 2 tiles per CU; BFGX_K1_FLUID at plan creation: 0 = never (the barrier-per-tile form), 2 = always (tests)
     Tiling tiling;
-    int32_t *tile_count = nullptr, *tile_count_b = nullptr, *tile_count_w = nullptr, *tile_start = nullptr, *tile_cursor = nullptr,
-            *tile_cursor_w = nullptr, *entries = nullptr, *overflow = nullptr;
+    TileArena arena;                 // everything a step resets, in one allocation: the binning counters, K1's tile counter, the per-tile largest |offset|^2, the regrid's control words (bfgx_tile_arena.hpp)
+    int32_t *tile_start = nullptr, *entries = nullptr, *overflow = nullptr;
     // narrow halos over <= 4 tiles are placed by K0 itself into fixed-capacity lists [ntiles][entries_a_cap]; the others are listed per K0
-    // workgroup for the placement pass; tile_zeros: ntiles zeros (the shared entry list holds only the regions [B | wide] of a tile)
-    int32_t *entries_a = nullptr, *slow_list = nullptr, *slow_cnt = nullptr, *tile_zeros = nullptr;
+    // workgroup for the placement pass
+    int32_t *entries_a = nullptr, *slow_list = nullptr, *slow_cnt = nullptr;
     int32_t entries_a_cap = 0;
-    int32_t *tile_count_pad = nullptr;      // region A's counters, cnt_pad words apart (a 128-byte line each up to 8192 tiles): see wave_run_issue
-    int32_t cnt_pad = 1;
+    int32_t cnt_pad = 1;             // words between region A's counters of two tiles (a 128-byte line each up to 8192 tiles): see wave_run_issue
     TileRef *tref = nullptr;
-    FarList far;                     // deposits of the gathering regrid that need the generic route (bfgx_regrid2.hpp)
-    int32_t *far_overflow_full = nullptr;   // full-map regrid: overflow of the list is repaired in-stream (pass 1), not an error
-    int32_t *regrid_todo = nullptr;  // [0] = count, then the tiles the lean gather kernel leaves to the one with the ring walk
+    FarList far;                     // deposits of the gathering regrid that need the generic route (bfgx_regrid2.hpp); count and overflow lie in the arena
     int32_t *regrid_lean = nullptr;  // [0] = count (zeroed by the regrid's last launch), then the tiles of the lean kernel (reach <= 1 ring)
-    float *tile_omax = nullptr;      // largest |offset|^2 of every tile (K1's flush or tile_reach_kernel): the reach of the gathering regrid
     // precision of the displacement path when the caller leaves it to the plan (BFGX_ACC_AUTO): chosen at plan creation from how far the
     // TABLE can move a pixel (plan_pick_precision): fp32 pair math holds SURVEY 8(d)'s 1e-6 mean(map) while one halo moves a pixel by less
     // than kAutoDispPixels; beyond that the parity-grade mode (BFGX_ACC_PARITY), or fp64 throughout where the fast kernel cannot take the table
@@ -139,7 +136,7 @@ struct bfgx_plan {
     int band_reach = 1;              // banded regrid: rings of apron every rank uses (bfgx_plan_set_band_reach)
     int route_margin = 0;            // rings by which bfgx_disc_rings_device widens every halo's range (bfgx_plan_set_route_margin)
     int64_t cat_blk_rows = 0, cat_blk_stride = 0;      // K0 reads a blocked catalog (bfgx_plan_set_catalog_blocks)
-    int32_t *wide_tiles = nullptr;   // [1 + ntiles]: number of tiles with wide entries, then those tiles (tile_scan_kernel)
+    WideTiles wide;                  // list: number of tiles with wide entries, then those tiles (tile_scan_kernel); behind it the scratch of the multi-workgroup scan
     // fast tiled scatter (bfgx_scatter2.hpp): slim per-halo records + interleaved copies of the table
     bool fast_ok = false;            // 3-axis table with a uniform ln r axis, small enough to interleave
     RowRec *rowrec = nullptr;
@@ -332,7 +329,7 @@ static int paint_mode(const bfgx_plan *p, int acc, PaintMode &m)
 struct TileLaunch {
     float *offsets_lo = nullptr;     // SPLIT pix_offsets: the low halves, indexed like the high ones
     bool paint_pair_f32 = false;     // PaintMode::MIXED
-    float *omax = nullptr;           // K1's flush stores the largest |offset|^2 of every tile here (p->tile_omax: the reach of the regrid)
+    float *omax = nullptr;           // K1's flush stores the largest |offset|^2 of every tile here (p->arena.omax: the reach of the regrid)
     int tile_lo = 0, tile_n = -1;    // tiles to process (-1: the whole sphere)
     int spread_tiles = -1;           // tiles the binned catalog covers when not the launch's (the density that picks the fast kernel's form)
 };
@@ -351,8 +348,8 @@ static int launch_prep(bfgx_plan *p, const bfgx_catalog *c, int fallback4, bool 
     o.rec_all = (rec_all || !o.fast) ? 1 : 0;
     o.rowrec = p->rowrec; o.pairrec = p->pairrec; o.fbrec = p->fbrec;
     if (bin) {
-        o.tref = p->tref; o.cnt_a = p->tile_count; o.cnt_b = p->tile_count_b; o.cnt_w = p->tile_count_w;
-        if (o.fast && p->entries_a) o.cnt_a = p->tile_count_pad;          // (direct placement: the padded counters, cnt_pad words apart)
+        o.tref = p->tref; o.cnt_a = p->arena.cnt_a; o.cnt_b = p->arena.cnt_b; o.cnt_w = p->arena.cnt_w;
+        if (o.fast && p->entries_a) o.cnt_a = p->arena.cnt_a_pad;          // (direct placement: the padded counters, cnt_pad words apart)
         o.cnt_pad = p->cnt_pad;
         o.work_est = o.fast ? p->k0_work_est : nullptr;
         o.entries_a = o.fast ? p->entries_a : nullptr; o.cap_a = p->entries_a_cap; o.slow_list = p->slow_list; o.slow_cnt = p->slow_cnt;
@@ -378,8 +375,8 @@ static int launch_place(bfgx_plan *p, const bfgx_catalog *c)
 {
     const unsigned grid = (unsigned)((c->n + 255) / 256);
     hipLaunchKernelGGL(tile_place_kernel, dim3(grid), dim3(256), 0, p->stream, p->hpx, p->tiling, c->n,
-                       (const TileRef *)p->tref, (const int32_t *)p->tile_start, (const int32_t *)p->tile_zeros,
-                       (const int32_t *)p->tile_count_b, p->tile_cursor, p->tile_cursor_w, p->entries, p->capacity, p->overflow,
+                       (const TileRef *)p->tref, (const int32_t *)p->tile_start, (const int32_t *)p->arena.zeros,
+                       (const int32_t *)p->arena.cnt_b, p->arena.cur_b, p->arena.cur_w, p->entries, p->capacity, p->overflow,
                        (const int32_t *)p->slow_list, (const int32_t *)p->slow_cnt);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
@@ -389,24 +386,21 @@ static int launch_place(bfgx_plan *p, const bfgx_catalog *c)
 static int launch_prep_and_bin(bfgx_plan *p, const bfgx_catalog *c, int fallback4, bool f64)
 {
     p->k1_nhalos = c->n;
-    const size_t nt = (size_t)p->tiling.ntiles;
-    // cnt_a, cnt_b, cnt_w, cur_b, cur_w, tile counter of the fast kernel, largest |offset|^2 per tile, and the
-    // four control words of the regrid's far list behind them (entries, overflow, tiles left to the walking kernel)
-    // (in front of them, in the same allocation: region A's counters padded to a line each)
-    HIP_TRY(hipMemsetAsync(p->tile_count_pad, 0, sizeof(int32_t) * (nt * (size_t)p->cnt_pad + (((size_t)7 * (nt + 1) + 3) & ~(size_t)3) + 4), p->stream));
+    // the step's one memset: the binning counters, K1's tile counter, the per-tile largest |offset|^2 and the regrid's control words
+    HIP_TRY(hipMemsetAsync(p->arena.base, 0, p->arena.zeroed_bytes, p->stream));
     if (int rc = launch_prep(p, c, fallback4, true, f64, false)) return rc;
     KernelTimer kt(p, BFGX_K_BIN);
     const int nt_i = p->tiling.ntiles, nsb = (nt_i + kScanTilesPerWg - 1) / kScanTilesPerWg;
     if (nsb <= 1 || nsb > 1024) {
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->tile_zeros,
-                           (const int32_t *)p->tile_count_b, (const int32_t *)p->tile_count_w, p->tile_start, p->wide_tiles);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros,
+                           (const int32_t *)p->arena.cnt_b, (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list);
     } else {        // NSIDE >= 2048: the scan spread over the tiles' blocks (three short launches instead of up to 48 serial rounds)
-        int32_t *tot = p->wide_tiles + nt_i + 1, *off = tot + 2048;
-        hipLaunchKernelGGL(tile_scan_part_kernel<0>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->tile_zeros, (const int32_t *)p->tile_count_b,
-                           (const int32_t *)p->tile_count_w, p->tile_start, p->wide_tiles, tot, (const int32_t *)off);
-        hipLaunchKernelGGL(tile_scan_blocks_kernel, dim3(1), dim3(1024), 0, p->stream, nsb, nt_i, (const int32_t *)tot, off, p->tile_start, p->wide_tiles);
-        hipLaunchKernelGGL(tile_scan_part_kernel<1>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->tile_zeros, (const int32_t *)p->tile_count_b,
-                           (const int32_t *)p->tile_count_w, p->tile_start, p->wide_tiles, tot, (const int32_t *)off);
+        int32_t *tot = p->wide.block_tot, *off = p->wide.block_off;
+        hipLaunchKernelGGL(tile_scan_part_kernel<0>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros, (const int32_t *)p->arena.cnt_b,
+                           (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list, tot, (const int32_t *)off);
+        hipLaunchKernelGGL(tile_scan_blocks_kernel, dim3(1), dim3(1024), 0, p->stream, nsb, nt_i, (const int32_t *)tot, off, p->tile_start, p->wide.list);
+        hipLaunchKernelGGL(tile_scan_part_kernel<1>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros, (const int32_t *)p->arena.cnt_b,
+                           (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list, tot, (const int32_t *)off);
     }
     HIP_TRY(hipGetLastError());
     if (c->n > 0) if (int rc = launch_place(p, c)) return rc;
@@ -438,9 +432,9 @@ static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, const TileLaunch &k, b
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * kWavesPerBlock), lds, p->stream,
                        make_pair_table(p->model.tab), p->hpx, p->tiling, (const HaloRec *)p->recs, (const RowSetX *)p->rowsx,
                        (const int32_t *)p->tile_start, (const int32_t *)p->entries, p->capacity, out, p->pair_total,
-                       wide_only ? (const int32_t *)p->tile_zeros : (const int32_t *)nullptr,
-                       wide_only ? (const int32_t *)p->tile_count_b : (const int32_t *)nullptr, wide_only ? 1 : 0,
-                       wide_only ? (const int32_t *)p->wide_tiles : (const int32_t *)nullptr, (unsigned int *)k.omax, k.tile_lo, k.tile_n);
+                       wide_only ? (const int32_t *)p->arena.zeros : (const int32_t *)nullptr,
+                       wide_only ? (const int32_t *)p->arena.cnt_b : (const int32_t *)nullptr, wide_only ? 1 : 0,
+                       wide_only ? (const int32_t *)p->wide.list : (const int32_t *)nullptr, (unsigned int *)k.omax, k.tile_lo, k.tile_n);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
@@ -459,8 +453,8 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC
     tb.r0 = (real)p->model.tab.r0; tb.r1 = (real)p->model.tab.r1; tb.inv_dr = (real)p->model.tab.inv_dr;
     tb.nr = p->model.tab.n[2]; tb._pad = 0;
     // persistent grid: two 512-thread workgroups per CU (LDS and registers allow exactly that) draw tiles from a counter that the
-    // binning step has reset (the sixth block of the counter array)
-    unsigned int *tile_counter = (unsigned int *)(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1));
+    // binning step has reset
+    unsigned int *tile_counter = p->arena.tile_counter;
     const int ntodo = k.tile_n < 0 ? p->tiling.ntiles : std::max(k.tile_n, 1);
     KernelTimer kt(p, MODE == MODE_OFFSETS ? BFGX_K_OFFSETS : (MODE == MODE_PAINT ? BFGX_K_PAINT : BFGX_K_COUNT));
     int32_t *form = nullptr;               // non-NULL: both forms are launched and this device word says which one works
@@ -491,7 +485,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC
             const int gridf = std::min(ntodo, p->num_cus);
             hipLaunchKernelGGL(kf, dim3(std::max(gridf, 1)), dim3(kWave * FluidWaves<real>::n), ldsf, p->stream, tb, p->hpx, p->tiling,
                                (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
-                               (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->tile_count_pad : p->tile_count), (const int32_t *)p->tile_count_b,
+                               (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->arena.cnt_a_pad : p->arena.cnt_a), (const int32_t *)p->arena.cnt_b,
                                (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, tile_counter,
                                (unsigned int *)k.omax, k.tile_lo, k.tile_n, p->overflow, (const int32_t *)form, 1);
             HIP_TRY(hipGetLastError());
@@ -501,7 +495,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC
     const int grid = std::min(ntodo, 2 * p->num_cus);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * kW2), lds, p->stream, tb, p->hpx, p->tiling,
                        (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
-                       (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->tile_count_pad : p->tile_count), (const int32_t *)p->tile_count_b,
+                       (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->arena.cnt_a_pad : p->arena.cnt_a), (const int32_t *)p->arena.cnt_b,
                        (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, p->pair_total, tile_counter,
                        (unsigned int *)k.omax, k.tile_lo, k.tile_n, (const int32_t *)form, 0);
     HIP_TRY(hipGetLastError());
@@ -544,10 +538,10 @@ static int ensure_entry_capacity(bfgx_plan *p, const bfgx_catalog *c)
     HIP_TRY(hipMemcpyAsync(&total, p->tile_start + p->tiling.ntiles, sizeof(total), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (!(ov & 1)) return BFGX_OK;             // (bit 2: the fluid kernel gave up -- bfgx_plan_status reports it)
-    HIP_TRY(p->mem.alloc(p->entries, (size_t)total + 16));     // the old list is released with the plan
+    HIP_TRY(p->mem.regrow(p->entries, (size_t)total + 16));    // (the stream has just been drained: the old list is freed at once)
     p->capacity = (int64_t)total + 16;
     HIP_TRY(hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream));
-    HIP_TRY(hipMemsetAsync(p->tile_cursor, 0, sizeof(int32_t) * 2 * ((size_t)p->tiling.ntiles + 1), p->stream));   // cur_b, cur_w
+    HIP_TRY(hipMemsetAsync(p->arena.cur_b, 0, p->arena.cursor_bytes, p->stream));   // cur_b, cur_w
     return launch_place(p, c);
 }
 
@@ -638,6 +632,110 @@ static void plan_pick_precision(bfgx_plan *p, const bfgx_model *model)
     }
     p->table_disp_pixels = worst;
     if (worst > kAutoDispPixels) p->auto_acc = BFGX_ACC_PARITY;
+}
+
+// the steps of bfgx_plan_create follow: each returns an error code, the caller destroys the plan
+// fast tiled scatter: possible for a 3-axis table with a uniform ln r axis whose interleaved copy stays small
+static int plan_init_fast(bfgx_plan *p, const bfgx_table &t, size_t nh)
+{
+    const size_t n8 = (size_t)(t.n[0] - 1) * (size_t)(t.n[1] - 1) * (size_t)(t.n[2] - 1) * 8;
+    p->fast_ok = (t.ndim == 3) && p->model.tab.r_uniform && n8 * sizeof(double) <= ((size_t)256 << 20);
+    if (!p->fast_ok) return BFGX_OK;
+    std::vector<float> v32;
+    std::vector<double> v64;
+    build_tab8<float>(t, v32);
+    build_tab8<double>(t, v64);
+    if (int rc = owned_upload(p->mem, p->stream, v32, p->tab8f)) return rc;
+    if (int rc = owned_upload(p->mem, p->stream, v64, p->tab8d)) return rc;
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "stream sync failed");
+    PairRecT<double> *pairrec = nullptr;
+    if (p->mem.alloc(p->rowrec, nh)) return alloc_fail("row records");
+    if (p->mem.alloc(pairrec, nh)) return alloc_fail("pair records");
+    p->pairrec = pairrec;
+    if (p->mem.alloc(p->fbrec, nh)) return alloc_fail("fallback records");
+    return BFGX_OK;
+}
+
+// tiling tables and halo -> tile binning workspace
+static int plan_init_binning(bfgx_plan *p, const bfgx_table &t, size_t nh)
+{
+    int BR, W;
+    std::vector<int32_t> tile0, nphi, nrmin, tband;
+    build_tiling(p->nside, t.log_values != 0, BR, W, tile0, nphi, nrmin, tband);
+    Tiling &T = p->tiling;
+    T.BR = BR; T.W = W; T.nbands = (int)nphi.size(); T.ntiles = (int)tband.size();
+    if (int rc = owned_upload(p->mem, p->stream, tile0, T.band_tile0)) return rc;
+    p->band_tile0_host = tile0;
+    if (int rc = owned_upload(p->mem, p->stream, nphi, T.band_nphi)) return rc;
+    if (int rc = owned_upload(p->mem, p->stream, nrmin, T.band_nrmin)) return rc;
+    if (int rc = owned_upload(p->mem, p->stream, tband, T.tile_band)) return rc;
+    std::vector<int32_t> order(tband.size());
+    {   // launch order: tiles by their shortest ring / azimuth slices (~ pixels per tile), descending; stable
+        std::vector<double> weight(tband.size());
+        for (size_t q = 0; q < tband.size(); ++q) { order[q] = (int32_t)q; weight[q] = (double)nrmin[tband[q]] / (double)nphi[tband[q]]; }
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return weight[x] > weight[y]; });
+    }
+    if (int rc = owned_upload(p->mem, p->stream, order, T.tile_order)) return rc;
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "stream sync failed");
+    p->capacity = 8 * p->max_halos + 4096;
+    if (const char *e = std::getenv("BFGX_K1_FLUID")) p->k1_fluid = std::max(0, std::min(2, std::atoi(e)));
+    if (const char *e = std::getenv("BFGX_K1_WIDE")) p->k1_wide = std::atoi(e) != 0;
+    if (const char *e = std::getenv("BFGX_ENTRY_CAP")) p->capacity = std::max<int64_t>(16, std::atoll(e));   // tests: force regrowth
+    // region A's counters: a line each while that array stays below 4 MB (atomics to one line serialise; a larger array costs misses)
+    p->cnt_pad = kCntPadMax;
+    while (p->cnt_pad > 1 && (size_t)T.ntiles * p->cnt_pad * sizeof(int32_t) > ((size_t)4 << 20)) p->cnt_pad >>= 1;
+    // the binning counters and, right behind them (16-byte aligned), the control words of the regrid's far list: ONE memset per step
+    // zeroes both (a length that is not a multiple of 16 bytes, or two buffers, cost a fill kernel each: 4.5 us)
+    const TileArenaLayout AL = tile_arena_layout((size_t)T.ntiles, (size_t)p->cnt_pad);
+    int32_t *arena = nullptr;
+    if (p->mem.alloc(arena, AL.total_words) || p->mem.alloc(p->tile_start, (size_t)T.ntiles + 1) ||
+        p->mem.alloc(p->entries, (size_t)p->capacity) || p->mem.alloc(p->overflow, 1) || p->mem.alloc(p->pair_total, 1) || p->mem.alloc(p->tref, nh))
+        return alloc_fail("binning workspace");
+    p->arena.bind(arena, AL);
+    // capacity of a tile's fixed list: 16 x the mean entries per tile (a rank of an N-GPU run bins its share of the halos into 1 / N
+    // of the tiles; a sky patch does the same), a power of two in [64, 32768] (4 x the mean above 512 entries per tile: a catalog of 1e7 small halos lists 4200 per tile, and what does not fit takes the slow route -- K3 3.7 against 1.4 ms), the whole array at most 1 GB
+    const double mean = 1.3 * (double)std::max<int64_t>(p->max_halos, 1) / (double)T.ntiles;
+    int cap_a = 64;
+    while (cap_a < 32768 && (double)cap_a < (mean > 512.0 ? 4.0 : 16.0) * mean + 64.0) cap_a <<= 1;
+    while (cap_a > 64 && (size_t)T.ntiles * cap_a * sizeof(int32_t) > ((size_t)1 << 30)) cap_a >>= 1;
+    if (const char *e = std::getenv("BFGX_TILE_LIST_CAP")) cap_a = std::max(1, std::atoi(e));        // tests: force the overflow into region B
+    const size_t nblk = (nh + 255) / 256;
+    if (p->mem.alloc(p->k0_work_est, nblk) || p->mem.alloc(p->k1_form, 4)) return alloc_fail("work estimate");
+    if (p->mem.alloc(p->entries_a, (size_t)T.ntiles * cap_a) || p->mem.alloc(p->slow_list, nblk * 256) || p->mem.alloc(p->slow_cnt, nblk))
+        return alloc_fail("tile lists");
+    p->entries_a_cap = cap_a;
+    return BFGX_OK;
+}
+
+// far list and regrid workspace
+static int plan_init_regrid(bfgx_plan *p)
+{
+    const Tiling &T = p->tiling;
+    // deposits listed for the generic route: four per pixel that moves beyond the gathering reach (15 rings = 9.9 / NSIDE rad).  At NSIDE
+    // 1024 on the S19 table that is 0.2 % of the pixels; at NSIDE 2048 the same field in radians sends 8 % there (16 M entries), and a
+    // list that overflows costs a second pass with the generic evaluation under divergence (25 ms): room for half the pixels, 1 GB at most
+    // (round 4, second half: at config 4's REAL density -- 1e7 halos on one NSIDE-2048 shell, 43 discs over every pixel -- the S19
+    // displacements add up to 15 pixels on average and 58 % of the pixels move beyond the 15-ring reach: 1.4e8 listed deposits,
+    // 2.8 per pixel.  A list for half the pixels overflowed into the repair pass: K2 35 ms; with room for four deposits of EVERY
+    // pixel, 4.3 GB at most, 10 ms.)
+    // Sized from the table (ADVICE, round 4): a listed deposit needs a pixel that moves beyond 9.7 pixel sides in total.  Tables that move a
+    // pixel by less than a quarter of a pixel per halo list the pole caps only (a few dozen entries): room for 1 / 16 of the pixels
+    // (16 B each: 13 MB at NSIDE 1024 instead of 0.8 GB); up to two pixels per halo: half the pixels; beyond: four deposits of every pixel.
+    // A list that overflows all the same (many overlapping discs) is repaired in-stream by the regrid's last pass.
+    const int64_t npx = p->hpx.npix;
+    const int64_t want = p->table_disp_pixels < 0.25 ? npx / 16 : (p->table_disp_pixels < 2.0 ? npx / 2 : 4 * npx);
+    p->far.cap = std::min<int64_t>(std::max<int64_t>((int64_t)1 << 20, want), (int64_t)1 << 28);
+    if (const char *e = std::getenv("BFGX_FAR_CAP")) p->far.cap = std::max<int64_t>(1024, std::atoll(e));          // tests: force the overflow
+    if (p->mem.alloc(p->far.pix, (size_t)p->far.cap) || p->mem.alloc(p->far.val, (size_t)p->far.cap) ||
+        p->mem.alloc(p->tile_apron, 2 * (size_t)(T.ntiles + 1)))
+        return alloc_fail("far list");
+    if (p->mem.alloc(p->regrid_lean, (size_t)(T.ntiles + 4))) return alloc_fail("lean tile list");
+    if (hipMemsetAsync(p->regrid_lean, 0, sizeof(int32_t) * 4, p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "hipMemset failed");
+    // the list's counter and its two overflow flags lie in the arena (the full-map regrid swaps far_overflow_full in: launch_regrid_gather)
+    p->far.count = &p->arena.ctrl->far_count;
+    p->far.overflow = p->arena.band_overflow;
+    if (hipMemsetAsync(p->arena.ctrl, 0, p->arena.tail_bytes, p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "hipMemset failed");
+    return BFGX_OK;
 }
 
 }  // namespace
@@ -736,116 +834,18 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
     const bfgx_table &t = model->table;
     if (int rc = upload_model(p->mem, p->stream, model, true, p->model, p->NC)) return bail(rc);
     plan_pick_precision(p, model);
-    DevList &mem = p->mem;
     const size_t nh = (size_t)(max_halos > 0 ? max_halos : 1);
-    if (mem.alloc(p->recs, nh)) return bail(alloc_fail("halo records"));
-    if (p->NC > 4 && mem.alloc(p->rowsx, nh)) return bail(alloc_fail("corner rows"));
-    {   // fast tiled scatter: possible for a 3-axis table with a uniform ln r axis whose interleaved copy stays small
-        const size_t n8 = (size_t)(t.n[0] - 1) * (size_t)(t.n[1] - 1) * (size_t)(t.n[2] - 1) * 8;
-        p->fast_ok = (t.ndim == 3) && p->model.tab.r_uniform && n8 * sizeof(double) <= ((size_t)256 << 20);
-        if (p->fast_ok) {
-            std::vector<float> v32;
-            std::vector<double> v64;
-            build_tab8<float>(t, v32);
-            build_tab8<double>(t, v64);
-            if (int rc = owned_upload(mem, p->stream, v32, p->tab8f)) return bail(rc);
-            if (int rc = owned_upload(mem, p->stream, v64, p->tab8d)) return bail(rc);
-            if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
-            PairRecT<double> *pairrec = nullptr;
-            if (mem.alloc(p->rowrec, nh)) return bail(alloc_fail("row records"));
-            if (mem.alloc(pairrec, nh)) return bail(alloc_fail("pair records"));
-            p->pairrec = pairrec;
-            if (mem.alloc(p->fbrec, nh)) return bail(alloc_fail("fallback records"));
-        }
-    }
-    {   // tiling tables and halo -> tile binning workspace
-        int BR, W;
-        std::vector<int32_t> tile0, nphi, nrmin, tband;
-        build_tiling(nside, t.log_values != 0, BR, W, tile0, nphi, nrmin, tband);
-        Tiling &T = p->tiling;
-        T.BR = BR; T.W = W; T.nbands = (int)nphi.size(); T.ntiles = (int)tband.size();
-        if (int rc = owned_upload(mem, p->stream, tile0, T.band_tile0)) return bail(rc);
-        p->band_tile0_host = tile0;
-        if (int rc = owned_upload(mem, p->stream, nphi, T.band_nphi)) return bail(rc);
-        if (int rc = owned_upload(mem, p->stream, nrmin, T.band_nrmin)) return bail(rc);
-        if (int rc = owned_upload(mem, p->stream, tband, T.tile_band)) return bail(rc);
-        std::vector<int32_t> order(tband.size());
-        {   // launch order: tiles by their shortest ring / azimuth slices (~ pixels per tile), descending; stable
-            std::vector<double> weight(tband.size());
-            for (size_t q = 0; q < tband.size(); ++q) { order[q] = (int32_t)q; weight[q] = (double)nrmin[tband[q]] / (double)nphi[tband[q]]; }
-            std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return weight[x] > weight[y]; });
-        }
-        if (int rc = owned_upload(mem, p->stream, order, T.tile_order)) return bail(rc);
-        if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
-        p->capacity = 8 * max_halos + 4096;
-        if (const char *e = std::getenv("BFGX_K1_FLUID")) p->k1_fluid = std::max(0, std::min(2, std::atoi(e)));
-        if (const char *e = std::getenv("BFGX_K1_WIDE")) p->k1_wide = std::atoi(e) != 0;
-        if (const char *e = std::getenv("BFGX_ENTRY_CAP")) p->capacity = std::max<int64_t>(16, std::atoll(e));   // tests: force regrowth
-        // the binning counters and, right behind them (16-byte aligned), the control words of the regrid's far list: ONE memset per step
-        // zeroes both (a length that is not a multiple of 16 bytes, or two buffers, cost a fill kernel each: 4.5 us)
-        const size_t n7p = ((size_t)7 * (T.ntiles + 1) + 3) & ~(size_t)3;
-        // region A's counters: a line each while that array stays below 4 MB (atomics to one line serialise; a larger array costs misses)
-        p->cnt_pad = kCntPadMax;
-        while (p->cnt_pad > 1 && (size_t)T.ntiles * p->cnt_pad * sizeof(int32_t) > ((size_t)4 << 20)) p->cnt_pad >>= 1;
-        const size_t npad = (size_t)T.ntiles * p->cnt_pad;
-        if (mem.alloc(p->tile_count_pad, npad + n7p + (size_t)T.ntiles + 8) || mem.alloc(p->tile_start, (size_t)T.ntiles + 1) ||
-            mem.alloc(p->entries, (size_t)p->capacity) || mem.alloc(p->overflow, 1) || mem.alloc(p->pair_total, 1) || mem.alloc(p->tref, nh))
-            return bail(alloc_fail("binning workspace"));
-        p->tile_count = p->tile_count_pad + npad; p->tile_count_b = p->tile_count + (T.ntiles + 1);
-        p->tile_count_w = p->tile_count + 2 * (T.ntiles + 1);
-        p->tile_cursor = p->tile_count + 3 * (T.ntiles + 1); p->tile_cursor_w = p->tile_count + 4 * (T.ntiles + 1);
-        {
-            // capacity of a tile's fixed list: 16 x the mean entries per tile (a rank of an N-GPU run bins its share of the halos into 1 / N
-            // of the tiles; a sky patch does the same), a power of two in [64, 32768] (4 x the mean above 512 entries per tile: a catalog of 1e7 small halos lists 4200 per tile, and what does not fit takes the slow route -- K3 3.7 against 1.4 ms), the whole array at most 1 GB
-            const double mean = 1.3 * (double)std::max<int64_t>(max_halos, 1) / (double)T.ntiles;
-            int cap_a = 64;
-            while (cap_a < 32768 && (double)cap_a < (mean > 512.0 ? 4.0 : 16.0) * mean + 64.0) cap_a <<= 1;
-            while (cap_a > 64 && (size_t)T.ntiles * cap_a * sizeof(int32_t) > ((size_t)1 << 30)) cap_a >>= 1;
-            if (const char *e = std::getenv("BFGX_TILE_LIST_CAP")) cap_a = std::max(1, std::atoi(e));        // tests: force the overflow into region B
-            const size_t nblk = (nh + 255) / 256;
-            if (mem.alloc(p->k0_work_est, nblk) || mem.alloc(p->k1_form, 4)) return bail(alloc_fail("work estimate"));
-            if (mem.alloc(p->entries_a, (size_t)T.ntiles * cap_a) || mem.alloc(p->slow_list, nblk * 256) || mem.alloc(p->slow_cnt, nblk))
-                return bail(alloc_fail("tile lists"));
-            p->entries_a_cap = cap_a;
-            p->tile_zeros = p->tile_count + 5 * ((size_t)T.ntiles + 1) + 1;      // the words behind K1's tile counter: zeroed with the counters, never written
-        }
-        {
-            // deposits listed for the generic route: four per pixel that moves beyond the gathering reach (15 rings = 9.9 / NSIDE rad).  At NSIDE
-            // 1024 on the S19 table that is 0.2 % of the pixels; at NSIDE 2048 the same field in radians sends 8 % there (16 M entries), and a
-            // list that overflows costs a second pass with the generic evaluation under divergence (25 ms): room for half the pixels, 1 GB at most
-            // (round 4, second half: at config 4's REAL density -- 1e7 halos on one NSIDE-2048 shell, 43 discs over every pixel -- the S19
-            // displacements add up to 15 pixels on average and 58 % of the pixels move beyond the 15-ring reach: 1.4e8 listed deposits,
-            // 2.8 per pixel.  A list for half the pixels overflowed into the repair pass: K2 35 ms; with room for four deposits of EVERY
-            // pixel, 4.3 GB at most, 10 ms.)
-            // Sized from the table (ADVICE, round 4): a listed deposit needs a pixel that moves beyond 9.7 pixel sides in total.  Tables that move a
-            // pixel by less than a quarter of a pixel per halo list the pole caps only (a few dozen entries): room for 1 / 16 of the pixels
-            // (16 B each: 13 MB at NSIDE 1024 instead of 0.8 GB); up to two pixels per halo: half the pixels; beyond: four deposits of every pixel.
-            // A list that overflows all the same (many overlapping discs) is repaired in-stream by the regrid's last pass.
-            const int64_t npx = p->hpx.npix;
-            const int64_t want = p->table_disp_pixels < 0.25 ? npx / 16 : (p->table_disp_pixels < 2.0 ? npx / 2 : 4 * npx);
-            p->far.cap = std::min<int64_t>(std::max<int64_t>((int64_t)1 << 20, want), (int64_t)1 << 28);
-            if (const char *e = std::getenv("BFGX_FAR_CAP")) p->far.cap = std::max<int64_t>(1024, std::atoll(e));          // tests: force the overflow
-            // control words in one allocation: [0..7] entries listed, [8..11] overflow (full-map regrid), [12..15] tiles left to
-            // the walking kernel (followed by their numbers), ... ; the banded regrid's overflow flag lives after the tile list
-            if (mem.alloc(p->far.pix, (size_t)p->far.cap) || mem.alloc(p->far.val, (size_t)p->far.cap) ||
-                mem.alloc(p->tile_apron, 2 * (size_t)(T.ntiles + 1)))
-                return bail(alloc_fail("far list"));
-            if (mem.alloc(p->regrid_lean, (size_t)(T.ntiles + 4))) return bail(alloc_fail("lean tile list"));
-            if (hipMemsetAsync(p->regrid_lean, 0, sizeof(int32_t) * 4, p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
-            int32_t *ctrl = p->tile_count + n7p;
-            p->far.count = (unsigned long long *)ctrl;
-            p->far_overflow_full = ctrl + 2;
-            p->regrid_todo = ctrl + 3;                       // [0] count, [1 ..] tiles
-            p->far.overflow = ctrl + 4 + T.ntiles;
-            p->tile_omax = (float *)(p->tile_count + 6 * ((size_t)T.ntiles + 1));
-            if (hipMemsetAsync(ctrl, 0, sizeof(int32_t) * (size_t)(T.ntiles + 8), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
-        }
-        // (+ 4096 ints behind the list: per-block totals and offsets of the multi-workgroup tile scan)
-        if (mem.alloc(p->wide_tiles, (size_t)(T.ntiles + 1 + 4096))) return bail(alloc_fail("wide tile list"));
-        if (mem.alloc(p->tile_sums, 2 * (size_t)(T.ntiles + 1))) return bail(alloc_fail("tile sums"));
-        if (hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream) != hipSuccess)
-            return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
-    }
+    if (p->mem.alloc(p->recs, nh)) return bail(alloc_fail("halo records"));
+    if (p->NC > 4 && p->mem.alloc(p->rowsx, nh)) return bail(alloc_fail("corner rows"));
+    if (int rc = plan_init_fast(p, t, nh)) return bail(rc);
+    if (int rc = plan_init_binning(p, t, nh)) return bail(rc);
+    if (int rc = plan_init_regrid(p)) return bail(rc);
+    const WideTilesLayout WL = wide_tiles_layout((size_t)p->tiling.ntiles);
+    int32_t *wide = nullptr;
+    if (p->mem.alloc(wide, WL.total_words)) return bail(alloc_fail("wide tile list"));
+    p->wide.bind(wide, WL);
+    if (p->mem.alloc(p->tile_sums, 2 * (size_t)(p->tiling.ntiles + 1))) return bail(alloc_fail("tile sums"));
+    if (hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
     if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
     *out = p;
     return BFGX_OK;
@@ -1105,19 +1105,17 @@ int bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_overf
     if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
     if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "regrid statistics exist for the tiled algorithm (algo 1) only");
     HIP_TRY(hipSetDevice(p->device));
-    int32_t ctrl[4] = {0, 0, 0, 0};                          // far count (64 bits), overflow of the full-map list, tiles left to the walking kernel
-    HIP_TRY(hipMemcpyAsync(ctrl, p->far.count, sizeof(ctrl), hipMemcpyDeviceToHost, p->stream));
+    RegridCtrl ctrl = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(&ctrl, p->arena.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, p->stream));
     std::vector<int32_t> apron;
     if (max_reach_rings) {
         apron.resize(2 * (size_t)p->tiling.ntiles);
         HIP_TRY(hipMemcpyAsync(apron.data(), p->tile_apron, sizeof(int32_t) * apron.size(), hipMemcpyDeviceToHost, p->stream));
     }
     HIP_TRY(hipStreamSynchronize(p->stream));
-    unsigned long long n = 0;
-    std::memcpy(&n, ctrl, sizeof(n));
-    if (far_listed) *far_listed = (int64_t)n;
-    if (far_overflowed) *far_overflowed = ctrl[2];
-    if (tiles_walked) *tiles_walked = ctrl[3];
+    if (far_listed) *far_listed = (int64_t)ctrl.far_count;
+    if (far_overflowed) *far_overflowed = ctrl.far_overflow_full;
+    if (tiles_walked) *tiles_walked = ctrl.todo_count;
     if (max_reach_rings) {
         int32_t m = 0;
         for (int t = 0; t < p->tiling.ntiles; ++t) m = std::max(m, apron[2 * (size_t)t]);
@@ -1185,7 +1183,7 @@ static int offsets_bands(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, i
     if (int rc = launch_k0(p, cat, 1, m.fp64())) return rc;
     // K1's flush leaves the largest |offset|^2 of every tile it stores (bfgx_bands_max_offset2_device reduces them: the reach of the
     // regrid then needs no second pass over the slice)
-    k1.omax = p->tile_omax;
+    k1.omax = p->arena.omax;
     return launch_offsets(p, m, slice, ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0),
                           ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band1), k1);
 }
@@ -1259,7 +1257,7 @@ int bfgx_bands_max_offset2_device(bfgx_plan *p, int32_t band0, int32_t band1, fl
     HIP_TRY(hipMemsetAsync(out_dev, 0, sizeof(float), p->stream));
     const int t0 = p->band_tile0_host[band0], nt = p->band_tile0_host[band1] - t0;
     if (nt > 0) {
-        hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(1024), 0, p->stream, nt, (const unsigned *)p->tile_omax + t0, (unsigned *)out_dev);
+        hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(1024), 0, p->stream, nt, (const unsigned *)p->arena.omax + t0, (unsigned *)out_dev);
         HIP_TRY(hipGetLastError());
     }
     return BFGX_OK;
@@ -1457,23 +1455,23 @@ static void launch_regrid_gather(bfgx_plan *p, const double *map_in_dev, const A
     const size_t lds = regrid3_lds_bytes(p->tiling.BR, p->tiling.W, sizeof(real)),
                  lds_walk = regrid3_lds_bytes(p->tiling.BR, p->tiling.W, sizeof(real), true, SPLIT ? sizeof(ACC) : sizeof(real));
     FarList far = p->far;
-    far.overflow = p->far_overflow_full;
+    far.overflow = p->arena.far_overflow_full;
     const int nt = p->tiling.ntiles, nfix = std::min(nt, 2 * p->num_cus), nwalk = std::min(nt, 4 * p->num_cus);
     const ReachArgs reach = reach_args(p, regrid_cap(p->hpx.nside));
     if (!from_k1)
-        hipLaunchKernelGGL(tile_reach_kernel<ACC>, dim3(nt), dim3(256), 0, p->stream, p->hpx, p->tiling, o, p->tile_omax);
-    hipLaunchKernelGGL(tile_apron_kernel, dim3((nt + 255) / 256), dim3(256), 0, p->stream, p->hpx, p->tiling, (const float *)p->tile_omax, 0,
-                       reach.cap, 0, nt, p->tile_apron, p->regrid_todo, p->regrid_lean);
+        hipLaunchKernelGGL(tile_reach_kernel<ACC>, dim3(nt), dim3(256), 0, p->stream, p->hpx, p->tiling, o, p->arena.omax);
+    hipLaunchKernelGGL(tile_apron_kernel, dim3((nt + 255) / 256), dim3(256), 0, p->stream, p->hpx, p->tiling, (const float *)p->arena.omax, 0,
+                       reach.cap, 0, nt, p->tile_apron, p->arena.todo, p->regrid_lean);
     // (the lean kernel: a persistent grid over the tiles whose reach is one ring -- all of them on a table of sub-pixel moves, none on the S19 table)
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 0, SPLIT>), dim3(std::min(nt, 8 * p->num_cus)), dim3(256), lds, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
                        map_out_dev, far, reach, ts, -1, nt, p->regrid_lean, (double *)nullptr);
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 2, SPLIT>), dim3(nwalk), dim3(256), lds_walk, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
-                       map_out_dev, far, reach, ts, -1, nt, p->regrid_todo, (double *)nullptr);
+                       map_out_dev, far, reach, ts, -1, nt, p->arena.todo, (double *)nullptr);
     // the two sums of the mass check: added up by the last launch, or -- above 16384 tiles, where that single workgroup's loop
     // takes 0.2 - 0.6 ms -- by 64 workgroups afterwards
     const bool many = nt > 16384 && sums_dev != nullptr && ts != nullptr;
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 1, SPLIT>), dim3(nfix), dim3(256), lds, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
-                       map_out_dev, far, reach, ts, -1, nt, p->regrid_todo, many ? (double *)nullptr : sums_dev, p->regrid_lean);
+                       map_out_dev, far, reach, ts, -1, nt, p->arena.todo, many ? (double *)nullptr : sums_dev, p->regrid_lean);
     if (many) {
         (void)hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream);
         hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, nt, (const double *)ts, sums_dev);
@@ -1491,8 +1489,8 @@ static int regrid_impl(bfgx_plan *p, const double *map_in_dev, const void *offse
     if (p->algo == 1) {
         // gathering form: every output pixel is stored once by the tile that owns it (no atomics, no zero-fill needed);
         // the few deposits that need the generic route are listed and added afterwards
-        // entries, overflow, tiles left to the walking kernel (the fused call's binning step has zeroed them with its counters)
-        if (!from_k1) HIP_TRY(hipMemsetAsync(p->far.count, 0, 4 * sizeof(int32_t), p->stream));
+        // the control words (the fused call's binning step has zeroed them with its counters)
+        if (!from_k1) HIP_TRY(hipMemsetAsync(p->arena.ctrl, 0, sizeof(RegridCtrl), p->stream));
         double *ts = sums_dev ? p->tile_sums : nullptr;
         if (m.split())      // pix_offsets as two fp32 arrays (hi, then lo behind the npix high triples), fp64 geometry
             launch_regrid_gather<float, double, true>(p, map_in_dev, (const float *)offsets_dev, m.lo(offsets_dev, p->hpx.npix),
@@ -1540,7 +1538,7 @@ int bfgx_baryonify_device(bfgx_plan *p, const bfgx_catalog *cat, const double *m
     if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
     TileLaunch k1;
     const bool fused = p->algo == 1;         // K1's flush leaves the largest |offset|^2 of every tile for the regrid's aprons
-    if (fused) k1.omax = p->tile_omax;
+    if (fused) k1.omax = p->arena.omax;
     if (int rc = offsets_impl(p, cat, offsets_work_dev, m, k1)) return rc;
     return regrid_impl(p, map_in_dev, offsets_work_dev, m, map_out_dev, sums_dev, fused);
 }
@@ -1839,7 +1837,7 @@ int paint_streamed(ShellEntry *e, const bfgx_catalog *dcat, const PaintMode &m, 
         k3.tile_lo = p->band_tile0_host[ch.cb[c]];
         k3.tile_n = p->band_tile0_host[ch.cb[c + 1]] - k3.tile_lo;
         // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
-        if (c > 0) HIP_TRY(hipMemsetAsync(p->tile_count + 5 * ((size_t)p->tiling.ntiles + 1), 0, sizeof(unsigned int), p->stream));
+        if (c > 0) HIP_TRY(hipMemsetAsync(p->arena.tile_counter, 0, sizeof(unsigned int), p->stream));
         if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
         HIP_TRY(hipEventRecord(e->ev_k[c], p->stream));
         HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
@@ -1901,7 +1899,7 @@ int bfgx_baryonify_shell(const bfgx_catalog *cat, const bfgx_model *model, int64
         HIP_TRY(hipMemsetAsync(e->out.p, 0, npix * sizeof(double), p->stream));
     }
     TileLaunch k1;
-    if (o.algo == 1) k1.omax = p->tile_omax;                 // K1's flush leaves the largest |offset|^2 of every tile for K2's aprons
+    if (o.algo == 1) k1.omax = p->arena.omax;                 // K1's flush leaves the largest |offset|^2 of every tile for K2's aprons
     if (int rc = offsets_impl(p, &dcat, e->off.p, m, k1)) return rc;
     double sums[2] = {0, 0};
     Chunks ch;

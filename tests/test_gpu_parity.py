@@ -218,6 +218,114 @@ def test_entry_list_regrowth(gpu, monkeypatch):
     plan.close()
 
 
+@pytest.mark.parametrize('nside', [8, 16])
+def test_resident_plan_entries_leave_nothing_stale(gpu, nside):
+    """Every entry of a resident plan zeroes what it needs of the plan's counter arena (binning counters, K1's tile counter, per-tile
+    largest |offset|^2, the regrid's control words: csrc/bfgx_tile_arena.hpp) and must leave nothing stale for the next one: a sequence
+    of different entries on ONE plan gives what each call gives on a fresh plan.  NSIDE 8 has 14 tiles (ntiles + 1 odd: every block
+    of the arena starts unaligned), NSIDE 16 has 52.  fp64 throughout: plan-to-plan differences are the order of LDS additions only
+    (1e-12 max|ref|, as test_entry_list_regrowth); pair totals and the regrid's statistics are integers and equal exactly."""
+    import torch
+    from baryonification_amd import _lib, engine, synthetic as syn
+    gd, gp = load_golden('lowz_baryonify'), load_golden('lowz_paint')
+    N, npix = 500, 12 * nside * nside
+    rng = np.random.default_rng(4200 + nside)
+    zt, Mt = gd['tab_z'], gd['tab_M']                      # (the two fixtures share their z and M axes)
+    cat = {'M': np.exp(rng.uniform(np.log(Mt.min() * 1.001), np.log(Mt.max() * 0.999), N)),
+           'z': rng.uniform(zt.min() * 1.001, zt.max() * 0.999, N),
+           'ra': rng.uniform(0.0, 360.0, N), 'dec': np.degrees(np.arcsin(rng.uniform(-1.0, 1.0, N)))}
+    dev = torch.device('cuda', 0)
+    t = {k: torch.from_numpy(v).to(dev) for k, v in cat.items()}
+    cd = _lib.make_catalog_dev(N, t['M'].data_ptr(), t['z'].data_ptr(), t['ra'].data_ptr(), t['dec'].data_ptr())
+    hmap = torch.from_numpy(syn.make_map(nside)).to(dev)
+
+    def new_plan(g):
+        paint = g['kind'] != 'baryonify'
+        axes = [np.log(1 + g['tab_z']), np.log(g['tab_M']), np.log(g['tab_r'])]
+        with np.errstate(divide='ignore'):
+            values = np.log(g['tab_values']) if paint else g['tab_values']
+        model, keep = engine.model_from_tables(axes, values, g['cosmo_runner'], g['eps_runner'], g['eps_model'], log_values=paint)
+        return engine.ShellPlan(model, keep, nside, N, 0, torch.cuda.current_stream().cuda_stream)
+
+    def done(plan, res):
+        torch.cuda.synchronize()
+        plan.status()
+        return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in res.items()}
+
+    def count(plan):
+        return done(plan, {'pairs': plan.count_pairs(cd)})
+
+    def offsets_regrid(plan):
+        off = torch.zeros(npix * 3, dtype=torch.float64, device=dev)
+        out = torch.full((npix,), np.nan, dtype=torch.float64, device=dev)
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        plan.offsets(cd, off.data_ptr(), acc_f64=True)
+        plan.regrid(hmap.data_ptr(), off.data_ptr(), out.data_ptr(), sums.data_ptr(), acc_f64=True)
+        return done(plan, dict(plan.regrid_stats(), off=off, out=out, sums=sums))
+
+    def fused(plan):
+        off = torch.zeros(npix * 3, dtype=torch.float64, device=dev)
+        out = torch.full((npix,), np.nan, dtype=torch.float64, device=dev)
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        plan.baryonify(cd, hmap.data_ptr(), off.data_ptr(), out.data_ptr(), sums.data_ptr(), acc_f64=True)
+        return done(plan, dict(plan.regrid_stats(), off=off, out=out, sums=sums))
+
+    def paint(plan):
+        out = torch.zeros(npix, dtype=torch.float64, device=dev)
+        plan.paint(cd, out.data_ptr(), acc_f64=True)
+        return done(plan, {'map': out})
+
+    def banded(plan, off_in):
+        first = plan.bands()
+        nb = first.size - 1
+        assert nb >= 2
+        acc = torch.full((npix,), np.nan, dtype=torch.float64, device=dev)
+        far_n = []
+        for b0, b1 in ((0, nb // 2), (nb // 2, nb)):
+            p0, p1 = int(first[b0]), int(first[b1])
+            olo, ohi = plan.band_apron(b0, b1)
+            my_off = off_in[3 * olo:3 * ohi].clone()
+            plan.regrid_bands(b0, b1, hmap.data_ptr(), my_off.data_ptr(), olo, ohi, acc[p0:p1].data_ptr(), acc_f64=True)
+            fp, fv = plan.far_fetch()
+            far_n.append(int(fp.size))
+            if fp.size:
+                acc.index_add_(0, torch.from_numpy(fp).to(dev), torch.from_numpy(fv).to(dev))
+        return done(plan, {'out': acc, 'far_0': far_n[0], 'far_1': far_n[1]})
+
+    def fresh(g, step, *args):
+        plan = new_plan(g)
+        res = step(plan, *args)
+        plan.close()
+        return res
+
+    def same(got, ref, what):
+        assert got.keys() == ref.keys()
+        for k, r in ref.items():
+            if isinstance(r, np.ndarray):
+                assert np.isfinite(got[k]).all() and np.abs(r).max() > 0, (what, k)
+                err = np.abs(got[k] - r).max() / np.abs(r).max()
+                print("%s %s: max|resident - fresh| = %.3e max|fresh|" % (what, k, err))
+                assert err <= 1e-12, (what, k, err)
+            else:
+                assert got[k] == r, (what, k, got[k], r)
+
+    ref_count, ref_sep, ref_fused, ref_paint = fresh(gd, count), fresh(gd, offsets_regrid), fresh(gd, fused), fresh(gp, paint)
+    assert ref_count['pairs'] > 0
+    off_in = torch.from_numpy(ref_sep['off']).to(dev)
+    ref_banded = fresh(gd, banded, off_in)
+    plan, plan_p = new_plan(gd), new_plan(gp)
+    same(count(plan), ref_count, '1 count_pairs')
+    same(offsets_regrid(plan), ref_sep, '2 offsets + regrid')
+    same(fused(plan), ref_fused, '3 fused baryonify')
+    same(paint(plan_p), ref_paint, '4 paint')
+    same(banded(plan, off_in), ref_banded, '5 banded regrid')
+    same(fused(plan), ref_fused, '6 fused baryonify')
+    same(offsets_regrid(plan), ref_sep, '7 offsets + regrid')
+    same(paint(plan_p), ref_paint, '8 paint again')
+    plan.close()
+    plan_p.close()
+
+
 @pytest.mark.parametrize('seed,nside,zr,logM,eps', [
     (1, 1, (0.01, 0.05), (14.0, 15.5), 8.0),       # 12 pixels: every disc takes the <4-pixel fallback or covers whole rings
     (2, 2, (0.005, 0.02), (14.5, 15.8), 30.0),     # discs of tens of degrees, poles inside, radius > pi/2 for some
