@@ -271,7 +271,14 @@ SYMBOLS = {
     'bfgx_grid_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_grid), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    'bfgx_math_probe': (C.c_int, [C.c_int, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+# include/bfgx.h enum bfgx_math_fn: the functions of csrc/bfgx_math.hpp that bfgx_math_probe evaluates
+MATH_FN = {'rcp': 0, 'rsq': 1, 'sqrt': 2, 'log': 3, 'log_kreg': 4, 'exp': 5, 'sincos_small': 6, 'sincos_small_kreg': 7,
+           'sincos_bounded': 8, 'sincos_dphi': 9, 'atan_small': 10, 'asin_small': 11, 'atan2': 12, 'mul_add_nc': 13, 'ring_theta': 14}
+MATH_FN_TWO_ARGS = ('atan2', 'mul_add_nc', 'ring_theta')
+MATH_FN_TWO_RESULTS = ('sincos_small', 'sincos_small_kreg', 'sincos_bounded', 'sincos_dphi')
 
 _lib = None
 

@@ -45,6 +45,7 @@
 #include "bfgx_stack.hpp"
 #include "bfgx_snapshot_stack.hpp"
 #include "bfgx_grid_stack.hpp"
+#include "bfgx_math_probe.hpp"
 
 using namespace bfgx;
 
@@ -2130,6 +2131,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // halo-centred radial profiles of gridded maps (MeasureProfilesGrid)
 #include "bfgx_grid_stack_api.inc"
+
+// device-math probe: one function of bfgx_math.hpp elementwise (test infrastructure)
+#include "bfgx_math_probe_api.inc"
 
 extern "C" void bfgx_cache_clear(void)
 {

@@ -1,7 +1,11 @@
 // fp64 device math tuned for the per-pair loop: straight-line (branch-free) sequences built on the
 // gfx950 hardware seeds v_rcp_f64 / v_rsq_f64 plus Newton steps, a frexp + atanh-series log and a
-// Taylor sincos for the small azimuth differences inside a disc.  All are accurate to a few ulp
-// (|rel err| <~ 4e-16), well inside the 1e-10 parity budget of the fp64-accumulator tests.
+// Taylor sincos for the small azimuth differences inside a disc.  Inside the domain stated at each function
+// the error is |rel err| <= 4e-16, with these exceptions: atan2_generic, whose half-angle steps each add an
+// rcp, an rsq and a product, is held to 1e-15 relative; sincos_bounded beyond |x| = 7, and sincos_dphi where
+// it folds by the double 2 pi, are held to an absolute error (4e-16 and 6.5e-16).  tests/test_gpu_math.py
+// enforces exactly these bounds against mpmath, function by function (table in DESIGN.md); all are well
+// inside the 1e-10 parity budget of the fp64-accumulator tests.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,7 +74,14 @@ __device__ inline double fast_log(double x, const LogK<T> &k)
     const bool lowm = m < 0.70710678118654752440;
     m = lowm ? 2.0 * m : m;
     e = lowm ? e - 1 : e;
-    const double s = (m - 1.0) * fast_rcp(m + 1.0);
+    // s = (m - 1) / (m + 1) as a corrected quotient: one Newton step on the seed (|rel err| ~ 2^-46), then the residual of the
+    // quotient itself, so that s carries one rounding.  (m - 1) * fast_rcp(m + 1) carried three -- the reciprocal's, the product's
+    // and that of m + 1 -- which with the final rounding reached 3.2e-16 near x = 1.3; same number of instructions.
+    const double f = m - 1.0, d = m + 1.0;
+    double y = __builtin_amdgcn_rcp(d);
+    y = __builtin_fma(y, __builtin_fma(-d, y, 1.0), y);
+    const double s0 = f * y;
+    const double s = __builtin_fma(__builtin_fma(-s0, d, f), y, s0);
     const double u = s * s;
     double p = 1.0 / 21.0;
     p = fma_k(p, u, k.c19);
@@ -230,34 +241,6 @@ __device__ inline double atan2_generic(double y, double x)
     a = swap ? 1.570796326794896619231321691639751442099 - a : a;
     a = (x < 0.0) ? 3.141592653589793238462643383279502884197 - a : a;
     return (y < 0.0) ? -a : a;
-}
-
-// acos(c) for |c| <= 1, branch-free: fdlibm's rational approximation of asin on [0, 0.5] with the
-// half-angle identity acos(c) = 2 asin(sqrt((1 - c) / 2)) beyond (a few ulp)
-__device__ inline double acos_fast(double c)
-{
-    const double ac = fabs(c);
-    const bool big = ac > 0.5;
-    const double z = big ? 0.5 * (1.0 - ac) : c * c;
-    double p = 3.47933107596021167570e-05;
-    p = __builtin_fma(p, z, 7.91534994289814532176e-04);
-    p = __builtin_fma(p, z, -4.00555345006794114027e-02);
-    p = __builtin_fma(p, z, 2.01212532134862925881e-01);
-    p = __builtin_fma(p, z, -3.25565818622400915405e-01);
-    p = __builtin_fma(p, z, 1.66666666666666657415e-01);
-    double q = 7.70381505559019352791e-02;
-    q = __builtin_fma(q, z, -6.88283971605453293030e-01);
-    q = __builtin_fma(q, z, 2.02094576023350569471e+00);
-    q = __builtin_fma(q, z, -2.40339491173441421878e+00);
-    q = __builtin_fma(q, z, 1.0);
-    const double R = z * p * fast_rcp(q);
-    const double zs = z > 0.0 ? z : 1.0;
-    const double s = big ? zs * fast_rsq(zs) : c;                           // sqrt(z) or c
-    const double as = __builtin_fma(s, R, s);                               // asin(s)
-    const double kHalfPi_ = 1.570796326794896619231321691639751442099, kPi_ = 3.141592653589793238462643383279502884197;
-    const double r_small = kHalfPi_ - as;
-    const double r_big = (c > 0.0) ? 2.0 * as : kPi_ - 2.0 * as;
-    return big ? ((z > 0.0) ? r_big : (c > 0.0 ? 0.0 : kPi_)) : r_small;
 }
 
 // sqrt(x) for normal x > 0 via the rsq seed; returns 0 for x <= 0

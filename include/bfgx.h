@@ -766,6 +766,31 @@ int  bfgx_grid_profiles_device(int32_t device, void *hip_stream, const bfgx_grid
                                const double *r_edges, int32_t scaled, int64_t *npix_dev, double *sum_dev, int64_t *npix_shear_dev,
                                double *sum_t_dev, double *sum_x_dev);
 
+/* ---- device math probe (test infrastructure) --------------------------------------------------------
+ * Evaluates ONE of the fp64 device functions of csrc/bfgx_math.hpp elementwise, one thread per element, every argument loaded from
+ * memory, so that tests can hold each function to its stated bound against a high-precision reference.  No product path calls it.
+ * a, b, out0, out1: host arrays of n doubles.  b is needed by the two-argument functions only (NULL otherwise), out1 by the
+ * sincos functions only (out0 = sin, out1 = cos).  Checked before any device call, BFGX_ERR_INVALID: a NULL pointer among those
+ * the function needs, an unknown fn, n < 0 or n > 2^22.  n == 0 returns BFGX_OK and launches nothing. */
+enum bfgx_math_fn {
+    BFGX_MATH_RCP = 0,               /* fast_rcp(a) */
+    BFGX_MATH_RSQ = 1,               /* fast_rsq(a) */
+    BFGX_MATH_SQRT = 2,              /* fast_sqrt(a) */
+    BFGX_MATH_LOG = 3,               /* fast_log(a), literal constants */
+    BFGX_MATH_LOG_KREG = 4,          /* fast_log(a), constants held in registers */
+    BFGX_MATH_EXP = 5,               /* fast_exp(a) */
+    BFGX_MATH_SINCOS_SMALL = 6,      /* sincos_small(a), literal constants */
+    BFGX_MATH_SINCOS_SMALL_KREG = 7, /* sincos_small(a), constants held in registers */
+    BFGX_MATH_SINCOS_BOUNDED = 8,    /* sincos_bounded(a) */
+    BFGX_MATH_SINCOS_DPHI = 9,       /* sincos_dphi(a) */
+    BFGX_MATH_ATAN_SMALL = 10,       /* atan_small(a) */
+    BFGX_MATH_ASIN_SMALL = 11,       /* asin_small(a) */
+    BFGX_MATH_ATAN2 = 12,            /* atan2_generic(y = a, x = b) */
+    BFGX_MATH_MUL_ADD_NC = 13,       /* add_nc(mul_nc(a, b), c), c = out0 on input */
+    BFGX_MATH_RING_THETA = 14        /* ring_theta_nolibm(nside = a, ring = b), 1 <= ring <= 4 nside - 1 */
+};
+int  bfgx_math_probe(int device, int32_t fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
+
 #ifdef __cplusplus
 }
 #endif

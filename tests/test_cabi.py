@@ -122,3 +122,29 @@ def test_displacement_rows_refuses_row_lengths_that_cannot_launch():
         assert b'[3, %d]' % tables.MAX_N_R in L.bfgx_last_error()
     with pytest.raises(ValueError, match=str(tables.MAX_N_R)):
         tables.displacement_rows(np.geomspace(1e-3, 1e2, tables.MAX_N_R + 1), np.ones((1, tables.MAX_N_R + 1)), np.ones((1, tables.MAX_N_R + 1)))
+
+
+def test_math_probe_refuses_bad_arguments_before_any_device_call():
+    """bfgx_math_probe (the per-function probe of csrc/bfgx_math.hpp) checks pointers, the function id and n first: the same answers
+    with and without a GPU"""
+    L = _lib.load()
+    x, y = np.ones(4), np.empty(4)
+    fn = _lib.MATH_FN
+    assert sorted(fn.values()) == list(range(15))
+    assert L.bfgx_math_probe(0, fn['rcp'], 4, None, None, y.ctypes.data, None) == _lib.ERR_INVALID             # NULL a
+    assert b'NULL' in L.bfgx_last_error()
+    assert L.bfgx_math_probe(0, fn['rcp'], 4, x.ctypes.data, None, None, None) == _lib.ERR_INVALID             # NULL out0
+    assert L.bfgx_math_probe(0, fn['atan2'], 4, x.ctypes.data, None, y.ctypes.data, None) == _lib.ERR_INVALID  # two arguments, NULL b
+    assert L.bfgx_math_probe(0, fn['sincos_small'], 4, x.ctypes.data, None, y.ctypes.data, None) == _lib.ERR_INVALID   # two results, NULL out1
+    for bad in (-1, 15, 1000):
+        assert L.bfgx_math_probe(0, bad, 4, x.ctypes.data, x.ctypes.data, y.ctypes.data, y.ctypes.data) == _lib.ERR_INVALID
+        assert b'unknown function' in L.bfgx_last_error()
+    for n in (-1, (1 << 22) + 1):
+        assert L.bfgx_math_probe(0, fn['rcp'], n, x.ctypes.data, None, y.ctypes.data, None) == _lib.ERR_INVALID
+        assert b'[0, 4194304]' in L.bfgx_last_error()
+    assert L.bfgx_math_probe(0, fn['rcp'], 0, x.ctypes.data, None, y.ctypes.data, None) == _lib.OK             # nothing to do, nothing launched
+    from baryonification_amd import engine
+    with pytest.raises(ValueError, match="unknown function"):
+        engine.math_probe('acos_fast', x)
+    with pytest.raises(ValueError, match="takes"):
+        engine.math_probe('atan2', x)
