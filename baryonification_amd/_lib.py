@@ -12,6 +12,7 @@ import numpy as np
 
 BFGX_MAX_EXTRA = 4
 BFGX_MAX_DIM = 3 + BFGX_MAX_EXTRA
+MAPSTATS_WORK_DOUBLES = 32768      # include/bfgx.h BFGX_MAPSTATS_WORK_DOUBLES
 KERNEL_KINDS = ('prep', 'offsets', 'regrid', 'paint', 'sum', 'count', 'bin', 'wide')
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -235,6 +236,8 @@ SYMBOLS = {
     'bfgx_sht_alm2cl': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_sht_anafast': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    'bfgx_sht_almxfl_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_sht_almxfl': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_sht_spin_work_doubles': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'bfgx_sht_map2alm_spin_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
@@ -256,6 +259,13 @@ SYMBOLS = {
                                       C.c_void_p]),
     'bfgx_hpx_scatter_add_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_hpx_scatter_add': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_neighbours_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    'bfgx_hpx_neighbours': (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    'bfgx_mapstats_moment_terms': (C.c_int32, [C.c_int32, C.c_int32]),
+    'bfgx_mapstats_moments_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    'bfgx_mapstats_peaks_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     'bfgx_shell_profiles': (C.c_int, [_P(bfgx_catalog), _P(bfgx_model), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_shell_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_catalog), _P(bfgx_model), C.c_int64, C.c_void_p, C.c_void_p,

@@ -41,6 +41,7 @@
 #include "bfgx_fftlog.hpp"
 #include "bfgx_sht.hpp"
 #include "bfgx_hpx.hpp"
+#include "bfgx_mapstats.hpp"
 #include "bfgx_stack_core.hpp"
 #include "bfgx_stack.hpp"
 #include "bfgx_snapshot_stack.hpp"
@@ -2119,6 +2120,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // HEALPix pixel functions (ud_grade / get_interp_weights / get_interp_val / regrid_pixels_hpix)
 #include "bfgx_hpx_api.inc"
+
+// map reductions: moments / cross-moments and peak counts of HEALPix maps
+#include "bfgx_mapstats_api.inc"
 
 // halo-centred radial profiles: what the three measurements below share on the host
 #include "bfgx_profiles_common.inc"

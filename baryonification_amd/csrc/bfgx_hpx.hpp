@@ -6,6 +6,7 @@
 //   hpx_interp_weights_kernel get_interp_weights: one lane per point (healpix_cxx get_interpol, bfgx_kernels.hpp)
 //   hpx_interp_val_kernel     get_interp_val: one lane per point, every map of the point in the same lane
 //   hpx_scatter_add_kernel    regrid_pixels_hpix: one lane per (i, j), fp64 global atomic add
+//   hpx_neighbours_kernel     get_all_neighbours: one lane per pixel index (pix_neighbours, also the stencil of bfgx_mapstats.hpp)
 //
 // NEST <-> RING follows Gorski et al. 2005 (healpix_cxx xyf2ring / ring2xyf / xyf2nest / nest2xyf): a pixel is its base face f
 // plus (ix, iy) in [0, nside)^2 within the face, and the NEST index is f nside^2 + the bit interleave of ix (even bits) and iy
@@ -92,7 +93,9 @@ __host__ __device__ inline int64_t isqrt_pix(int64_t v)
     return r;
 }
 
-__host__ __device__ inline void ring2xyf(int64_t nside, int order, int64_t pix, int64_t &ix, int64_t &iy, int &f)
+// kPow2: nside = 2^order and the belt divides by shifts; otherwise order is unused and any nside >= 1 is taken
+template <bool kPow2>
+__host__ __device__ inline void ring2xyf_t(int64_t nside, int order, int64_t pix, int64_t &ix, int64_t &iy, int &f)
 {
     const int64_t nl2 = 2 * nside, ncap = 2 * nside * (nside - 1), npix = 12 * nside * nside;
     int64_t iring, iphi, kshift, nr;
@@ -103,14 +106,15 @@ __host__ __device__ inline void ring2xyf(int64_t nside, int order, int64_t pix, 
         f = (int)((iphi - 1) / nr);
     } else if (pix < npix - ncap) {
         const int64_t ip = pix - ncap;
-        const int64_t tmp = ip >> (order + 2);
+        const int64_t tmp = kPow2 ? ip >> (order + 2) : ip / (4 * nside);
         iring = tmp + nside;
         iphi = ip - tmp * 4 * nside + 1;
         kshift = (iring + nside) & 1;
         nr = nside;
         const int64_t ire = tmp + 1, irm = nl2 + 1 - tmp;
-        const int64_t ifm = (iphi - (ire >> 1) + nside - 1) >> order;
-        const int64_t ifp = (iphi - (irm >> 1) + nside - 1) >> order;
+        const int64_t jm = iphi - (ire >> 1) + nside - 1, jp = iphi - (irm >> 1) + nside - 1;      // both >= 0
+        const int64_t ifm = kPow2 ? jm >> order : jm / nside;
+        const int64_t ifp = kPow2 ? jp >> order : jp / nside;
         f = (int)((ifp == ifm) ? (ifp | 4) : ((ifp < ifm) ? ifp : (ifm + 8)));
     } else {
         const int64_t ip = npix - pix;
@@ -127,6 +131,11 @@ __host__ __device__ inline void ring2xyf(int64_t nside, int order, int64_t pix, 
     iy = (-ipt - irt) >> 1;
 }
 
+__host__ __device__ inline void ring2xyf(int64_t nside, int order, int64_t pix, int64_t &ix, int64_t &iy, int &f)
+{
+    ring2xyf_t<true>(nside, order, pix, ix, iy, f);
+}
+
 // nside must be 2^order
 __host__ __device__ inline int64_t ring2nest(int64_t nside, int order, int64_t pix)
 {
@@ -140,6 +149,56 @@ __host__ __device__ inline int64_t nest2ring(int64_t nside, int order, int64_t p
     int64_t ix, iy; int f;
     nest2xyf(order, pix, ix, iy, f);
     return xyf2ring(nside, ix, iy, f);
+}
+
+// The 8 neighbours of a pixel in healpy.get_all_neighbours' order SW, W, NW, N, NE, E, SE, S; -1 where there is none (the E and W
+// corners of the 8 polar faces lack their E / W neighbour, the N and S corners of the 4 equatorial faces their N / S one: 24 in every
+// map).  A step (dx, dy) that leaves the face [0, nside)^2 lands in the face across that edge or corner (healpix_cxx neighbors(): the
+// face table, then the mirror / swap of (x, y) that a polar face's rotated neighbour asks for).  kNest: NEST indices, nside = 2^order.
+// RING with kPow2 = false takes any nside.
+template <bool kNest, bool kPow2>
+__host__ __device__ inline void pix_neighbours(int64_t nside, int order, int64_t pix, int64_t out[8])
+{
+    const int xoff[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, yoff[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+    // face across the edge / corner nbnum = 4 + (x over ? 1 : x under ? -1 : 0) + 3 (the same for y), for base face 0..11
+    const signed char face[9][12] = {{8, 9, 10, 11, -1, -1, -1, -1, 10, 11, 8, 9},      // S
+                                     {5, 6, 7, 4, 8, 9, 10, 11, 9, 10, 11, 8},          // SE
+                                     {-1, -1, -1, -1, 5, 6, 7, 4, -1, -1, -1, -1},      // E
+                                     {4, 5, 6, 7, 11, 8, 9, 10, 11, 8, 9, 10},          // SW
+                                     {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11},            // the face itself
+                                     {1, 2, 3, 0, 0, 1, 2, 3, 5, 6, 7, 4},              // NE
+                                     {-1, -1, -1, -1, 7, 4, 5, 6, -1, -1, -1, -1},      // W
+                                     {3, 0, 1, 2, 3, 0, 1, 2, 4, 5, 6, 7},              // NW
+                                     {2, 3, 0, 1, -1, -1, -1, -1, 0, 1, 2, 3}};         // N
+    // bit 0: x -> nside - 1 - x, bit 1: the same for y, bit 2: swap x and y; by face row (north, equatorial, south)
+    const unsigned char swap[9][3] = {{0, 0, 3}, {0, 0, 6}, {0, 0, 0}, {0, 0, 5}, {0, 0, 0}, {5, 0, 0}, {0, 0, 0}, {6, 0, 0}, {3, 0, 0}};
+    int64_t ix, iy; int f;
+    if (kNest) nest2xyf(order, pix, ix, iy, f);
+    else ring2xyf_t<kPow2>(nside, order, pix, ix, iy, f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int64_t x = ix + xoff[k], y = iy + yoff[k];
+        int nbnum = 4;
+        if (x < 0) { x += nside; nbnum -= 1; } else if (x >= nside) { x -= nside; nbnum += 1; }
+        if (y < 0) { y += nside; nbnum -= 3; } else if (y >= nside) { y -= nside; nbnum += 3; }
+        const int nf = face[nbnum][f];
+        if (nf < 0) { out[k] = -1; continue; }
+        const int bits = swap[nbnum][f >> 2];
+        if (bits & 1) x = nside - 1 - x;
+        if (bits & 2) y = nside - 1 - y;
+        if (bits & 4) { const int64_t t = x; x = y; y = t; }
+        out[k] = kNest ? xyf2nest(order, x, y, nf) : xyf2ring(nside, x, y, nf);
+    }
+}
+
+// order = log2 nside, or -1 when nside is no power of two (RING only)
+__host__ __device__ inline int nbr_order(int64_t nside) { return (nside & (nside - 1)) == 0 ? ilog2(nside) : -1; }
+
+__host__ __device__ inline void pix_neighbours(int64_t nside, int order, int nest, int64_t pix, int64_t out[8])
+{
+    if (nest) pix_neighbours<true, true>(nside, order, pix, out);
+    else if (order >= 0) pix_neighbours<false, true>(nside, order, pix, out);
+    else pix_neighbours<false, false>(nside, order, pix, out);
 }
 
 // child c (0 <= c < r^2) in run order: rows t = u + v ascending, u ascending along a row (the ring index ascending)
@@ -324,6 +383,25 @@ hpx_scatter_add_kernel(int64_t npix, double *__restrict__ hmap, int64_t n, const
         int64_t p = pix[e];
         if (p < 0) p += npix;
         if (p >= 0 && p < npix) atomicAdd(hmap + p, w[e] * vals[e >> 2]);
+    }
+}
+
+// out[8][n]: the neighbours of ipix[i] (pix_neighbours); -1 throughout for an index outside [0, npix)
+__global__ void __launch_bounds__(kThreads)
+hpx_neighbours_kernel(int64_t nside, int order, int nest, int64_t n, const int64_t *__restrict__ ipix, int64_t *__restrict__ out)
+{
+    const int64_t npix = 12 * nside * nside;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const int64_t p = ipix[i];
+        int64_t nb[8];
+        if (p >= 0 && p < npix) {
+            pix_neighbours(nside, order, nest, p, nb);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) nb[k] = -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k * n + i] = nb[k];
     }
 }
 

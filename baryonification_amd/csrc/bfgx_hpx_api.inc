@@ -207,6 +207,36 @@ int bfgx_hpx_interp_val(int device, int64_t nside, int32_t nest, int64_t nmaps, 
     return BFGX_OK;
 }
 
+int bfgx_hpx_neighbours_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix_dev, int64_t *out_dev)
+{
+    if (!ipix_dev || !out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
+    if (n > (INT64_MAX >> 4)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
+    if (int rc = tables_begin(device)) return rc;
+    if (n == 0) return BFGX_OK;
+    hipLaunchKernelGGL(hpx::hpx_neighbours_kernel, dim3(hpx_blocks(n)), dim3(hpx::kThreads), 0, (hipStream_t)hip_stream, nside,
+                       hpx::nbr_order(nside), nest ? 1 : 0, n, ipix_dev, out_dev);
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
+int bfgx_hpx_neighbours(int device, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix, int64_t *out)
+{
+    if (!ipix || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
+    if (n > (INT64_MAX >> 4)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
+    const int64_t npix = 12 * nside * nside;
+    for (int64_t i = 0; i < n; ++i)
+        if (ipix[i] < 0 || ipix[i] >= npix) return fail(BFGX_ERR_INVALID, "ipix[%lld] = %lld is outside [0, %lld)", (long long)i, (long long)ipix[i], (long long)npix);
+    if (int rc = tables_begin(device)) return rc;
+    if (n == 0) return BFGX_OK;
+    DevBuf di, dout;
+    if (di.up(ipix, sizeof(int64_t) * n) || dout.up(nullptr, sizeof(int64_t) * 8 * n)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+    if (int rc = bfgx_hpx_neighbours_device(device, nullptr, nside, nest, n, di.as<int64_t>(), dout.as<int64_t>())) return rc;
+    HIP_TRY(hipMemcpy(out, dout.p, sizeof(int64_t) * 8 * n, hipMemcpyDeviceToHost));
+    return BFGX_OK;
+}
+
 int bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, double *hmap_dev, int64_t n, const double *vals_dev,
                                 const int64_t *pix_dev, const double *w_dev)
 {

@@ -692,5 +692,18 @@ sht_alm2cl_kernel(const double2 *__restrict__ a, const double2 *__restrict__ b, 
     cl[l] = (a0.x * b0.x + a0.y * b0.y + 2.0 * s) / (2.0 * l + 1.0);
 }
 
+// healpy.almxfl: out_lm = in_lm * fl[l] (fl[l] = 0 for l >= nfl); column m = blockIdx.y, one lane per l.  in == out is allowed (each
+// lane reads and writes its own coefficient only)
+__global__ void __launch_bounds__(256)
+sht_almxfl_kernel(const double2 *in, double2 *out, int lmax, int nfl, const double *__restrict__ fl)
+{
+    const int m = blockIdx.y, l = blockIdx.x * 256 + threadIdx.x;
+    if (l < m || l > lmax) return;
+    const int64_t i = alm_index(lmax, l, m);
+    const double f = l < nfl ? fl[l] : 0.0;
+    const double2 a = in[i];
+    out[i] = make_double2(a.x * f, a.y * f);
+}
+
 }  // namespace sht
 }  // namespace bfgx

@@ -272,7 +272,40 @@ int bfgx_sht_alm2cl_device(int device, void *hip_stream, int32_t lmax, int32_t m
     return sht_alm2cl((hipStream_t)hip_stream, lmax, mmax, lmax_out, a, b, cl_dev);
 }
 
+int sht_almxfl_check(int32_t lmax, int32_t mmax, int64_t nfl, const void *fl, const void *in, const void *out)
+{
+    if (!fl || !in || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (lmax < 0 || lmax > 32767 || mmax < 0 || mmax > lmax) return fail(BFGX_ERR_INVALID, "almxfl needs 0 <= mmax <= lmax <= 32767 (got mmax %d, lmax %d)", mmax, lmax);
+    if (nfl < 0) return fail(BFGX_ERR_INVALID, "nfl must be >= 0 (got %lld)", (long long)nfl);
+    return BFGX_OK;
+}
+
+int bfgx_sht_almxfl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl_dev, const double *alm_in_dev,
+                           double *alm_out_dev)
+{
+    if (int rc = sht_almxfl_check(lmax, mmax, nfl, fl_dev, alm_in_dev, alm_out_dev)) return rc;
+    if (int rc = tables_begin(device)) return rc;
+    hipLaunchKernelGGL(sht::sht_almxfl_kernel, dim3((unsigned)(lmax / 256 + 1), (unsigned)(mmax + 1)), dim3(256), 0, (hipStream_t)hip_stream,
+                       reinterpret_cast<const double2 *>(alm_in_dev), reinterpret_cast<double2 *>(alm_out_dev), lmax,
+                       (int)std::min<int64_t>(nfl, (int64_t)lmax + 1), fl_dev);
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
 // one-shot host entries: numpy in, numpy out (PCIe included); alm are complex128 in healpy order
+int bfgx_sht_almxfl(int device, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl, const double *alm_in, double *alm_out)
+{
+    if (int rc = sht_almxfl_check(lmax, mmax, nfl, fl, alm_in, alm_out)) return rc;
+    if (int rc = tables_begin(device)) return rc;
+    const int64_t na = sht_alm_size(lmax, mmax), nf = std::min<int64_t>(nfl, (int64_t)lmax + 1);
+    DevBuf df, da;
+    if (df.up(nf ? fl : nullptr, sizeof(double) * std::max<int64_t>(nf, 1)) || da.up(alm_in, sizeof(double2) * na))
+        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+    if (int rc = bfgx_sht_almxfl_device(device, nullptr, lmax, mmax, nf, df.as<double>(), da.as<double>(), da.as<double>())) return rc;
+    HIP_TRY(hipMemcpy(alm_out, da.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
+    return BFGX_OK;
+}
+
 int bfgx_sht_map2alm(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map, double *alm)
 {
     if (!map || !alm) return fail(BFGX_ERR_INVALID, "NULL argument");

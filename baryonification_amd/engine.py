@@ -511,6 +511,10 @@ class ShtPlan(object):
                                                       C.c_void_p(self.work.data_ptr())))
         return m
 
+    def almxfl_device(self, alm_dev, fl_dev, out=None):
+        """alm [nalm] times fl[l] (a float64 device tensor; fl[l] = 0 beyond its end): healpy.almxfl.  out=alm_dev filters in place"""
+        return almxfl_device(alm_dev, fl_dev, self.lmax, self.mmax, out=out, device=self.device)
+
     def alm2cl_device(self, alm1_dev, alm2_dev=None, lmax_out=None, out=None):
         """cl [lmax_out + 1] (auto- or cross-spectrum) of device alm"""
         return alm2cl_device(alm1_dev, alm2_dev, self.lmax, self.mmax, lmax_out, out=out, device=self.device)
@@ -550,6 +554,16 @@ def alm2cl_device(alm1_dev, alm2_dev, lmax, mmax, lmax_out=None, out=None, devic
                                                  C.c_void_p(alm2_dev.data_ptr()) if alm2_dev is not None else None,
                                                  C.c_void_p(cl.data_ptr())))
     return cl
+
+
+def almxfl_device(alm_dev, fl_dev, lmax, mmax, out=None, device=0):
+    import torch
+    res = out if out is not None else torch.empty_like(alm_dev)
+    stream = torch.cuda.current_stream(alm_dev.device).cuda_stream
+    _lib.check(_lib.load().bfgx_sht_almxfl_device(int(device), C.c_void_p(stream or None), int(lmax), int(mmax), int(fl_dev.numel()),
+                                                 C.c_void_p(fl_dev.data_ptr()), C.c_void_p(alm_dev.data_ptr()),
+                                                 C.c_void_p(res.data_ptr())))
+    return res
 
 
 _SHT_PLANS = {}
@@ -592,6 +606,13 @@ def sht_alm2map_spin_host(alms, nside, lmax, mmax, spin, device=0):
     m = np.empty((2, 12 * int(nside) ** 2))
     _lib.check(_lib.load().bfgx_sht_alm2map_spin(int(device), int(nside), int(lmax), int(mmax), int(spin), a.ctypes.data, m.ctypes.data))
     return m
+
+
+def sht_almxfl_host(alm, fl, lmax, mmax, out=None, device=0):
+    """one-shot host entry of almxfl: complex128 alm and float64 fl in, the filtered alm out (`out` may be `alm`)"""
+    res = out if out is not None else np.empty(sht_alm_size(lmax, mmax), dtype=np.complex128)
+    _lib.check(_lib.load().bfgx_sht_almxfl(int(device), int(lmax), int(mmax), int(fl.size), fl.ctypes.data, alm.ctypes.data, res.ctypes.data))
+    return res
 
 
 def sht_alm2cl_host(alm1, alm2, lmax, mmax, lmax_out, device=0):

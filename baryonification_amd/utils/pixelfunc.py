@@ -3,6 +3,7 @@
     ud_grade(map_in, nside_out, pess=False, order_in='RING', order_out=None, power=None, dtype=None)
     get_interp_weights(nside, theta, phi=None, nest=False, lonlat=False)
     get_interp_val(m, theta, phi, nest=False, lonlat=False)
+    get_all_neighbours(nside, theta, phi=None, nest=False, lonlat=False)       (pixel indices only)
 
 plus UNSEEN (shared with sphtfunc).  `anafast(ud_grade(shell, 2048))` takes the C_l of a shell finer than the transforms accept.
 
@@ -26,7 +27,7 @@ from .. import _lib
 from .io import npix2nside
 from .sphtfunc import UNSEEN
 
-__all__ = ['ud_grade', 'get_interp_weights', 'get_interp_val', 'UNSEEN']
+__all__ = ['ud_grade', 'get_interp_weights', 'get_interp_val', 'get_all_neighbours', 'UNSEEN']
 
 MAX_NSIDE = 8192
 
@@ -261,6 +262,45 @@ def get_interp_val(m, theta, phi, nest=False, lonlat=False):
     if n:
         _lib.check(L.bfgx_hpx_interp_val(0, nside, int(bool(nest)), nmaps, dt, _ptr(mm), n, _ptr(t), _ptr(p), _ptr(out)))
     return out[()] if out.ndim == 0 else out
+
+
+# ------------------------------------------------------------------------------------------------------------- neighbours
+def get_all_neighbours(nside, theta, phi=None, nest=False, lonlat=False):
+    """healpy.get_all_neighbours of pixel indices: int64 of shape (8,) for one index or (8, N) for N, in healpy's order SW, W, NW,
+    N, NE, E, SE, S, with -1 where a neighbour does not exist (24 entries of a whole map).  `theta` holds the indices (RING, or
+    NEST if nest); angles (phi given) are not supported, as this package has no ang2pix.  nest=True needs a power-of-two nside;
+    RING takes 1 <= nside <= 8192."""
+    if phi is not None:
+        raise NotImplementedError("get_all_neighbours takes pixel indices only (phi must be None: there is no ang2pix here)")
+    nside = check_nside(nside, bool(nest))
+    npix = 12 * nside * nside
+    L = _lib.load()
+    if _is_torch(theta):
+        import torch
+        ip = theta
+        if ip.dtype.is_floating_point or ip.dtype.is_complex or ip.dtype == torch.bool:
+            raise ValueError("theta must hold integer pixel indices")
+        if ip.dim() > 1:
+            raise ValueError("theta must be one pixel index or a 1-D array of them (got shape %s)" % (tuple(ip.shape),))
+        ip = ip.to(torch.int64).contiguous()
+        if ip.numel() and (int(ip.min()) < 0 or int(ip.max()) >= npix):
+            raise ValueError("pixel indices must be in [0, %d)" % npix)
+        out = torch.empty((8,) + tuple(ip.shape), dtype=torch.int64, device=ip.device)
+        if ip.numel():
+            _lib.check(L.bfgx_hpx_neighbours_device(_dev(ip), _stream(ip), nside, int(bool(nest)), ip.numel(), _ptr(ip), _ptr(out)))
+        return out
+    ip = np.asarray(theta)
+    if ip.dtype.kind not in 'iu':
+        raise ValueError("theta must hold integer pixel indices")
+    if ip.ndim > 1:
+        raise ValueError("theta must be one pixel index or a 1-D array of them (got shape %s)" % (ip.shape,))
+    ip = np.asarray(ip, dtype=np.int64, order='C')
+    if ip.size and (ip.min() < 0 or ip.max() >= npix):
+        raise ValueError("pixel indices must be in [0, %d)" % npix)
+    out = np.empty((8,) + ip.shape, dtype=np.int64)
+    if ip.size:
+        _lib.check(L.bfgx_hpx_neighbours(0, nside, int(bool(nest)), ip.size, _ptr(ip), _ptr(out)))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- regrid_pixels_hpix

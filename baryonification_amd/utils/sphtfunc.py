@@ -23,13 +23,17 @@ Convergence to shear (Kaiser-Squires) on a shell map kappa:
     gamma1, gamma2 = alm2map_spin([elm, 0 * elm], nside, 2, lmax)
 
 and back: E, B = map2alm_spin([gamma1, gamma2], 2); alm2cl(E), alm2cl(B), alm2cl(E, B) are the E/B spectra.
+
+Filters in harmonic space: gauss_beam / tophat_beam are windows W_l (host numpy), almxfl multiplies alm by one on the GPU, and
+smoothalm / smoothing are healpy's (smoothing = map2alm, almxfl, alm2map on the cached plan of the shape; a single RING map).
 """
 import numpy as np
 
 from .. import engine
 from .io import npix2nside
 
-__all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'map2alm_spin', 'alm2map_spin', 'getlmax', 'getidx', 'getsize', 'UNSEEN']
+__all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'map2alm_spin', 'alm2map_spin', 'getlmax', 'getidx', 'getsize', 'UNSEEN',
+           'gauss_beam', 'tophat_beam', 'almxfl', 'smoothalm', 'smoothing']
 
 UNSEEN = -1.6375e30
 
@@ -276,3 +280,124 @@ def alm2map_spin(alms, nside, spin, lmax, mmax=None):
         import torch
         return plan.alm2map_spin_device(torch.stack([a, b]), spin)
     return plan.alm2map_spin_device(_to_device(np.stack([a, b]), plan), spin).cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------- harmonic filters
+def gauss_beam(fwhm, lmax=512, pol=False):
+    """healpy.gauss_beam: exp(-l (l + 1) sigma^2 / 2), l = 0..lmax, sigma = fwhm / sqrt(8 ln 2) (fwhm in radians)"""
+    if pol:
+        raise NotImplementedError("pol=True is not supported (spin-0 window only)")
+    lmax = int(lmax)
+    if lmax < 0:
+        raise ValueError("lmax must be >= 0 (got %d)" % lmax)
+    return _gauss_window(float(fwhm) / np.sqrt(8.0 * np.log(2.0)), lmax)
+
+
+def _gauss_window(sigma, lmax):
+    ell = np.arange(lmax + 1, dtype=np.float64)
+    return np.exp(-0.5 * ell * (ell + 1.0) * sigma * sigma)
+
+
+def tophat_beam(radius, lmax):
+    """The harmonic window of a disc of angular radius `radius` (radians, in [0, pi]): W_0 = 1 and, with mu = cos(radius),
+    W_l = (1 + mu) P'_l(mu) / (l (l + 1)), which equals the textbook (P_{l-1} - P_{l+1}) / ((2l + 1) (1 - mu)) without its
+    cancellation at small radii.  P'_l comes from the upward recurrence l P'_{l+1} = (2l + 1) mu P'_l - (l + 1) P'_{l-1}, run on
+    the differences D_l = P'_l - P'_{l-1} with t = 1 - mu = 2 sin^2(radius / 2):  l D_{l+1} = (l + 1) D_l - (2l + 1) t P'_l, so an
+    arc-minute radius is not lost in the rounding of cos(radius) to fp64.  Host numpy, fp64; radius 0 gives all ones."""
+    lmax = int(lmax)
+    radius = float(radius)
+    if lmax < 0:
+        raise ValueError("lmax must be >= 0 (got %d)" % lmax)
+    if not 0.0 <= radius <= np.pi:
+        raise ValueError("radius must be in [0, pi] (got %r)" % radius)
+    t = 2.0 * np.sin(0.5 * radius) ** 2
+    onepmu = 2.0 * np.cos(0.5 * radius) ** 2
+    w = np.ones(lmax + 1)
+    dp, d = 1.0, 1.0                                       # P'_1, D_1
+    for l in range(1, lmax + 1):
+        w[l] = onepmu * dp / (l * (l + 1.0))
+        d = ((l + 1.0) * d - (2.0 * l + 1.0) * t * dp) / l
+        dp = dp + d
+    return w
+
+
+def _window(lmax, fwhm, sigma, beam_window):
+    """fl[0..lmax] of smoothalm / smoothing: beam_window wins over sigma, sigma over fwhm"""
+    if beam_window is not None:
+        fl = np.asarray(beam_window, dtype=np.float64)
+        if fl.ndim != 1:
+            raise ValueError("beam_window must be 1-D (got shape %s)" % (fl.shape,))
+        return np.ascontiguousarray(fl)
+    return gauss_beam(fwhm, lmax) if sigma is None else _gauss_window(float(sigma), lmax)
+
+
+def _fl_input(fl):
+    if _is_torch(fl):
+        if fl.dim() != 1 or fl.dtype.is_complex:
+            raise ValueError("fl must be a 1-D real array")
+        return fl
+    f = np.asarray(fl)
+    if f.ndim != 1 or not (np.issubdtype(f.dtype, np.floating) or np.issubdtype(f.dtype, np.integer)):
+        raise ValueError("fl must be a 1-D real array (got dtype %s, shape %s)" % (f.dtype, f.shape))
+    return np.ascontiguousarray(f, dtype=np.float64)
+
+
+def _fl_device(fl, dev):
+    """fl as a float64 tensor on dev with at least one element (an empty fl filters everything to 0)"""
+    import torch
+    f = fl if _is_torch(fl) else torch.from_numpy(fl)
+    f = f.to(device=dev, dtype=torch.float64).contiguous()
+    return f if f.numel() else torch.zeros(1, dtype=torch.float64, device=dev)
+
+
+def almxfl(alm, fl, mmax=None, inplace=False):
+    """healpy.almxfl: alm[idx(l, m)] * fl[l] on the GPU.  fl is real; fl[l] counts as 0 for l >= len(fl), entries beyond lmax are
+    ignored.  A CUDA complex128 tensor is filtered where it lies (in place with inplace=True); a numpy array goes through the
+    one-shot host entry (inplace=True needs a C-contiguous complex128 array, as healpy does)."""
+    f = _fl_input(fl)
+    a, lmax, mmax, on_dev = _alm_input(alm, None, mmax, 'alm')
+    if on_dev:
+        if inplace and (a is not alm and a.data_ptr() != alm.data_ptr()):
+            raise ValueError("inplace=True needs a contiguous 1-D complex128 tensor")
+        out = engine.almxfl_device(a, _fl_device(f, a.device), lmax, mmax, out=a if inplace else None, device=a.device.index or 0)
+        return alm if inplace else out
+    if inplace and not (isinstance(alm, np.ndarray) and np.shares_memory(a, alm)):
+        raise ValueError("inplace=True needs a C-contiguous 1-D complex128 numpy array")
+    if _is_torch(f):
+        f = f.cpu().numpy().astype(np.float64)
+    if f.size == 0:
+        f = np.zeros(1)
+    res = engine.sht_almxfl_host(a, f, lmax, mmax, out=a if inplace else None)
+    return alm if inplace else res
+
+
+def smoothalm(alms, fwhm=0.0, sigma=None, beam_window=None, pol=True, mmax=None, verbose=True, inplace=True):
+    """healpy.smoothalm of one set of alm: almxfl with beam_window, else the Gaussian of sigma, else that of fwhm (radians)"""
+    a, lmax, mmax, on_dev = _alm_input(alms, None, mmax)
+    return almxfl(alms, _window(lmax, fwhm, sigma, beam_window), mmax=mmax, inplace=inplace)
+
+
+def unseen_mask(m):
+    """healpy.mask_bad: |m - UNSEEN| <= 1e-8 + 1e-5 |UNSEEN| (numpy array or torch tensor)"""
+    return abs(m - UNSEEN) <= 1e-8 + 1e-5 * abs(UNSEEN)
+
+
+def smoothing(map_in, fwhm=0.0, sigma=None, beam_window=None, pol=True, iter=3, lmax=None, mmax=None, use_weights=False,
+              use_pixel_weights=False, datapath=None, verbose=True, nest=False):
+    """healpy.smoothing of a single RING map (nside <= 2048): alm2map(almxfl(map2alm(map_in, iter), W)) on the cached plan of the
+    shape, W = beam_window, else the Gaussian of sigma, else that of fwhm (radians).  UNSEEN pixels count as 0 on the way in and
+    are UNSEEN again in the result.  A CUDA tensor stays on its device."""
+    _unsupported(nest=(nest, False), use_weights=(use_weights, False), use_pixel_weights=(use_pixel_weights, False),
+                 datapath=(datapath, None))
+    m, nside, on_dev = _map_input(map_in, 'map_in')
+    lmax, mmax = _shape(nside, lmax, mmax)
+    if int(iter) < 0:
+        raise ValueError("iter must be >= 0")
+    fl = _window(lmax, fwhm, sigma, beam_window)
+    plan = engine.sht_plan(nside, lmax, mmax)
+    md = m if on_dev else _to_device(m, plan)
+    alm = plan.map2alm_device(md, iter=int(iter))
+    plan.almxfl_device(alm, _fl_device(fl, plan.dev), out=alm)
+    out = plan.alm2map_device(alm)
+    out.masked_fill_(unseen_mask(md), UNSEEN)
+    return out if on_dev else out.cpu().numpy()

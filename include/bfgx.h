@@ -631,6 +631,12 @@ int  bfgx_sht_alm2map_device(int device, void *hip_stream, int32_t nside, int32_
                              double *map_dev, double *work_dev);
 int  bfgx_sht_alm2cl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int32_t lmax_out, const double *alm1_dev,
                             const double *alm2_dev, double *cl_dev);
+/* almxfl (healpy.almxfl): alm_out[idx(l, m)] = alm_in[idx(l, m)] * fl[l], fl real, fl[l] = 0 for l >= nfl (entries beyond lmax are
+ * ignored); one fp64 multiply per component.  alm_out may be alm_in.  0 <= mmax <= lmax <= 32767, nfl >= 0. */
+int  bfgx_sht_almxfl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl_dev,
+                            const double *alm_in_dev, double *alm_out_dev);
+int  bfgx_sht_almxfl(int device, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl_host, const double *alm_in_host,
+                     double *alm_out_host);
 /* one-shot host entries (host arrays, PCIe included).  anafast: cl[lmax + 1]; alm1_out / alm2_out (optional) receive the alm */
 int  bfgx_sht_map2alm(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map_host, double *alm_host);
 int  bfgx_sht_alm2map(int device, int32_t nside, int32_t lmax, int32_t mmax, const double *alm_host, double *map_host);
@@ -670,7 +676,13 @@ int  bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax
  *   on the device entry.
  * scatter_add: hmap[pix[i][j]] += w[i][j] * vals[i] for i < n, j < 4 (pix, w: [n][4]), fp64 atomic adds, so the last bits of a sum
  *   can differ from run to run.  Indices in [-npix, 0) wrap; the host entry refuses any other index outside [0, npix), the device
- *   entry skips it. */
+ *   entry skips it.
+ * neighbours (healpy.get_all_neighbours of pixel indices): out[8][n], the neighbours of ipix[i] in the order SW, W, NW, N, NE, E, SE, S
+ *   (healpix_cxx neighbors()), -1 where there is none (24 entries of a whole map).  nest / nside as for interp_weights.  The host entry
+ *   refuses an index outside [0, npix); the device entry writes -1 for all 8. */
+int  bfgx_hpx_neighbours_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix_dev,
+                                int64_t *out_dev);
+int  bfgx_hpx_neighbours(int device, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix_host, int64_t *out_host);
 int  bfgx_hpx_ud_grade_device(int device, void *hip_stream, int64_t nside_in, int64_t nside_out, int64_t nmaps, int32_t nest_in,
                               int32_t nest_out, int32_t pess, double ratio, int32_t dtype_in, int32_t dtype_out, const void *map_in_dev,
                               void *map_out_dev);
@@ -688,6 +700,29 @@ int  bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, dou
                                  const int64_t *pix_dev, const double *w_dev);
 int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n, const double *vals_host, const int64_t *pix_host,
                           const double *w_host);
+
+/* ---- reductions over HEALPix maps: moments, cross-moments and peak counts (device entries, enqueue-only on hip_stream) -------------
+ * A pixel is good if every map is finite and not UNSEEN there (healpy.mask_bad's tolerance) and mask_dev (optional, one byte per
+ * pixel) is nonzero.
+ * moments: maps_dev = nmaps maps of npix doubles, row after row, 1 <= nmaps <= 3, 2 <= order <= 4.  *n_dev = good pixels (exact);
+ *   out_dev = mean[nmaps] | central[bfgx_mapstats_moment_terms(nmaps, order)], central = mean over the good pixels of
+ *   prod_a (x_a - mean_a)^{e_a}.  THE ORDER of the exponent tuples (e_0, .., e_{nmaps-1}): total degree d = 2, 3, .., order; within a
+ *   degree e_0 descending, then e_1 descending (e_{nmaps-1} = d - the rest).  nmaps = 2, order = 3: (2,0) (1,1) (0,2) (3,0) (2,1)
+ *   (1,2) (0,3).  That is 3 values for nmaps = 1, 12 for 2 and 31 for 3 at order 4; bfgx_mapstats_moment_terms returns the number
+ *   (-1 = invalid nmaps / order).  Two passes (means, then central products), fp64 block partials combined in a fixed order over a grid
+ *   that depends on npix alone, no float atomics: a repeated call gives the same bits.  No good pixel: n = 0, every value NaN.
+ *   work_dev: BFGX_MAPSTATS_WORK_DOUBLES doubles of scratch.
+ * peaks: a pixel of a map (RING, or NEST with nest != 0 and a power-of-two nside; 1 <= nside <= 8192) is a maximum if it is strictly
+ *   greater than every existing neighbour (bfgx_hpx_neighbours), a minimum if strictly less, and only if it and all of them are good.
+ *   counts_dev[2][nb] (zeroed by the entry) = maxima | minima with edges[b] <= value < edges[b + 1]; values outside the edges are not
+ *   counted.  edges_dev: nb + 1 ascending finite doubles on the device (1 <= nb <= 4096; the order is the caller's to check).
+ *   flags_dev (optional, one int8 per pixel): +1 maximum, -1 minimum, 0 neither.  Integer atomics: the counts are exact. */
+#define BFGX_MAPSTATS_WORK_DOUBLES 32768
+int32_t bfgx_mapstats_moment_terms(int32_t nmaps, int32_t order);
+int  bfgx_mapstats_moments_device(int device, void *hip_stream, int64_t npix, int32_t nmaps, int32_t order, const double *maps_dev,
+                                  const uint8_t *mask_dev, int64_t *n_dev, double *out_dev, double *work_dev);
+int  bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int32_t nest, const double *map_dev, const uint8_t *mask_dev,
+                                int32_t nb, const double *edges_dev, int64_t *counts_dev, int8_t *flags_dev);
 
 /* ---- halo-centred radial profiles of shell maps (MeasureProfilesShell) ------------------------------
  * The adjoint of PaintProfilesShell: for halo j the pixels of query_disc(nside, vec_j, R_j epsilon_max / D_j) (RING, no < 4-pixel fallback) at
