@@ -266,6 +266,9 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p]),
     'bfgx_mapstats_peaks_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    'bfgx_mapstats_minkowski_work_doubles': (C.c_int64, [C.c_int64, C.c_int32]),
+    'bfgx_mapstats_minkowski_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     'bfgx_shell_profiles': (C.c_int, [_P(bfgx_catalog), _P(bfgx_model), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_shell_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_catalog), _P(bfgx_model), C.c_int64, C.c_void_p, C.c_void_p,

@@ -1,11 +1,14 @@
 // bfgx_mapstats.hpp -- reductions over whole HEALPix maps for gfx950: the higher-order statistics of shells (moments and
-// cross-moments of up to three maps, counts of local maxima and minima).
+// cross-moments of up to three maps, counts of local maxima and minima, Minkowski functionals of the excursion sets).
 //
 //   mapstats_sum_kernel<K>      pass 1: per-block fp64 sums of the K maps over the good pixels, and their number
 //   mapstats_central_kernel<K>  pass 2: per-block fp64 sums of prod_a (x_a - mean_a)^{e_a} for every exponent tuple of degree 2..4
 //   mapstats_combine_kernel     one workgroup: the block partials of a pass added in a fixed order, divided by n
 //   mapstats_peaks_kernel       one lane per pixel: the 8 neighbours (hpx::pix_neighbours), strict maximum / minimum, a histogram of
 //                               the extrema's values per workgroup in LDS, integer atomics to the result
+//   mapstats_minkowski_kernel   one lane per pixel: the bin of u, sqrt(g2) and c / g2 from the six derivative maps, per-block fp64
+//                               sums per bin in a fixed order (below), integer counts per bin
+//   mapstats_minkowski_combine_kernel   one lane per (sum, bin): the block partials added in block order
 //
 // A pixel is good if every map is finite and not UNSEEN there (hpx::good_value) and the mask, if there is one, is nonzero.
 //
@@ -13,9 +16,16 @@
 // its lanes by a shuffle tree, lane 0 of wave 0 adds the four waves in order, and mapstats_combine_kernel adds the block partials the
 // same way.  No float atomics: a repeated call gives the same bits.  The peak counts are integers, so their atomics are exact.
 //
+// Determinism of the Minkowski sums.  The same grid; every step of a workgroup takes 256 consecutive pixels, so what a wave holds
+// depends on npix alone.  A wave serves the bin of its lowest unserved lane: the lanes holding that bin contribute their two terms to a
+// fixed tree of lane-to-lane moves (half_sum; the others 0), lanes 31 and 63 add the results to the wave's own LDS slots
+// [wave][2][nb]; then the next unserved lane's bin.  At the end the four waves' slots are added in order into work[block][2][nb], and
+// the combine kernel adds the blocks in order.  The order of every addition is a function of the input alone: no float atomics, a
+// repeated call gives the same bits.
+//
 // Per pixel: pass 1 and pass 2 each read K doubles (+ 1 mask byte) and write nothing; the peaks kernel reads 1 double (+ 1 byte),
 // gathers 8 neighbour values (+ 8 bytes) that mostly hit L2 (neighbours lie on the same and the two adjacent rings), and writes 1
-// flag byte when asked to.
+// flag byte when asked to; the Minkowski kernel reads 6 doubles (+ 1 byte) = 49 B and writes nothing.
 #pragma once
 #include "bfgx_hpx.hpp"
 
@@ -206,6 +216,138 @@ mapstats_peaks_kernel(Peaks a, const double *__restrict__ map, const uint8_t *__
     __syncthreads();
     for (int b = threadIdx.x; b < 2 * a.nb; b += kThreads)
         if (s_hist[b]) atomicAdd(&counts[b], (unsigned long long)s_hist[b]);
+}
+
+constexpr int kMaxMfBins = 512;
+
+// LDS of mapstats_minkowski_kernel: edges[nb + 1] and sums[kWaves][2][nb] doubles, counts[nb + 3] ints: 38 932 B at nb = 512, so four
+// workgroups still share a CU's 160 KiB (the grid has at most kMaxBlocks = 4 x 256 of them)
+__host__ __device__ constexpr size_t minkowski_lds_bytes(int nb)
+{
+    return sizeof(double) * (size_t)(nb + 1 + kWaves * 2 * nb) + sizeof(int) * (size_t)(nb + 3);
+}
+static_assert(minkowski_lds_bytes(kMaxMfBins) <= 160 * 1024 / 4, "four workgroups per CU");
+
+// v of the lane that kCtrl names (a DPP control: row_shr:n = 0x110 + n, row_bcast15 = 0x142), 0.0 where there is no such lane or the
+// row (16 lanes) is not in kRowMask
+template <int kCtrl, int kRowMask>
+__device__ inline double dpp_fetch(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, kRowMask, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, kRowMask, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// lane 31 returns the sum of v over lanes 0..31 and lane 63 that over lanes 32..63, in one fixed order: within every row of 16 lanes
+// lane i adds the lanes 1, 2, 4 and 8 below it in turn (lane 15 then holds the row), then rows 1 and 3 add lane 15 of the row below.
+// DPP moves run on the vector unit; the same tree through __shfl_down would be 10 LDS-crossbar operations
+__device__ inline double half_sum(double v)
+{
+    v += dpp_fetch<0x111, 0xf>(v);
+    v += dpp_fetch<0x112, 0xf>(v);
+    v += dpp_fetch<0x114, 0xf>(v);
+    v += dpp_fetch<0x118, 0xf>(v);
+    v += dpp_fetch<0x142, 0xa>(v);
+    return v;
+}
+
+// the two summed terms of a pixel from x = [u, u_t, u_p, lap, q_plus, q_cross]: t1 = sqrt(g2), t2 = c / g2 (0 where g2 = 0).  Every product
+// is rounded (no fused multiply-add), so the terms are those of the same expressions in IEEE arithmetic anywhere else
+__device__ inline void minkowski_terms(const double x[6], double &t1, double &t2)
+{
+#pragma clang fp contract(off)
+    const double a2 = x[1] * x[1], b2 = x[2] * x[2], g2 = a2 + b2;
+    const double c = x[1] * x[2] * x[5] - 0.5 * x[3] * g2 + 0.5 * x[4] * (a2 - b2);
+    t1 = sqrt(g2);
+    t2 = g2 > 0.0 ? c / g2 : 0.0;
+}
+
+// ders = [u, u_t, u_p, lap, q_plus, q_cross][npix]; a pixel is good if all six are finite, u is not UNSEEN and the mask, if there is one, is
+// nonzero.  Over the good pixels with edges[b] <= u < edges[b + 1]:
+// part[blockIdx.x][0][b] = sum sqrt(g2), part[blockIdx.x][1][b] = sum c / g2 (0 where g2 = 0), g2 = u_t^2 + u_p^2,
+// c = u_t u_p q_cross - lap g2 / 2 + q_plus (u_t^2 - u_p^2) / 2; counts[b] pixels in bin b, counts[nb] below edges[0],
+// counts[nb + 1] at or above edges[nb], counts[nb + 2] good pixels.  Dynamic LDS: minkowski_lds_bytes(nb).
+__global__ void __launch_bounds__(kThreads)
+mapstats_minkowski_kernel(int64_t npix, int nb, const double *__restrict__ ders, const uint8_t *__restrict__ mask,
+                          const double *__restrict__ edges, unsigned long long *__restrict__ counts, double *__restrict__ part)
+{
+    extern __shared__ double s_mf[];
+    double *s_edges = s_mf;                                                // [nb + 1]
+    double *s_sum = s_mf + nb + 1;                                         // [kWaves][2][nb]
+    int *s_cnt = reinterpret_cast<int *>(s_sum + kWaves * 2 * nb);         // [nb + 3]
+    for (int b = threadIdx.x; b <= nb; b += kThreads) s_edges[b] = edges[b];
+    for (int b = threadIdx.x; b < kWaves * 2 * nb; b += kThreads) s_sum[b] = 0.0;
+    for (int b = threadIdx.x; b < nb + 3; b += kThreads) s_cnt[b] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const bool upper = lane >= 32;
+    double *w_sum = s_sum + (threadIdx.x >> 6) * 2 * nb;
+    const double e_lo = s_edges[0], e_hi = s_edges[nb];
+    // base is the same for every lane of the workgroup: no lane leaves the loop before the shuffles of its wave
+    for (int64_t base = (int64_t)blockIdx.x * kThreads; base < npix; base += (int64_t)gridDim.x * kThreads) {
+        const int64_t i = base + threadIdx.x;
+        int bin = -1;
+        double t1 = 0.0, t2 = 0.0;
+        if (i < npix) {
+            double x[6];
+            bool ok = !mask || mask[i] != 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                x[a] = ders[a * npix + i];
+                ok = ok && isfinite(x[a]);
+            }
+            if (ok && hpx::good_value(x[0])) {
+                const double u = x[0];
+                if (u < e_lo) bin = nb;
+                else if (!(u < e_hi)) bin = nb + 1;
+                else {
+                    int lo = 0, hi = nb;                                   // edges[lo] <= u < edges[hi]
+                    while (hi - lo > 1) {
+                        const int mid = (lo + hi) >> 1;
+                        if (u >= s_edges[mid]) lo = mid; else hi = mid;
+                    }
+                    bin = lo;
+                    minkowski_terms(x, t1, t2);
+                }
+                atomicAdd(&s_cnt[bin], 1);
+                atomicAdd(&s_cnt[nb + 2], 1);
+                if (bin >= nb) bin = -1;
+            }
+        }
+        // lanes 0..31 reduce the first term and lanes 32..63 the second: each half first takes its term from the other half, then one
+        // tree of 5 steps (half_sum) serves both sums, which end in lanes 31 and 63
+        const double keep = upper ? t2 : t1, give = upper ? t1 : t2;
+        unsigned long long pending = __ballot(bin >= 0);
+        while (pending) {
+            const int b = __builtin_amdgcn_readlane(bin, __ffsll((long long)pending) - 1);   // the bin of the lowest unserved lane
+            const bool mine = bin == b;
+            const double v = half_sum((mine ? keep : 0.0) + __shfl_xor(mine ? give : 0.0, 32, 64));
+            if ((lane & 31) == 31) w_sum[(upper ? nb : 0) + b] += v;
+            pending &= ~__ballot(mine);
+        }
+    }
+    __syncthreads();
+    double *dst = part + (int64_t)blockIdx.x * 2 * nb;
+    for (int v = threadIdx.x; v < 2 * nb; v += kThreads) {
+        double t = s_sum[v];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) t += s_sum[w * 2 * nb + v];
+        dst[v] = t;
+    }
+    for (int b = threadIdx.x; b < nb + 3; b += kThreads)
+        if (s_cnt[b]) atomicAdd(&counts[b], (unsigned long long)s_cnt[b]);
+}
+
+// sums[v] = part[0][v] + part[1][v] + ... in block order, v < nvals (= 2 nb): one lane per value
+__global__ void __launch_bounds__(kThreads)
+mapstats_minkowski_combine_kernel(int nblocks, int nvals, const double *__restrict__ part, double *__restrict__ sums)
+{
+    const int v = blockIdx.x * kThreads + threadIdx.x;
+    if (v >= nvals) return;
+    double t = part[v];
+#pragma unroll 8
+    for (int b = 1; b < nblocks; ++b) t += part[(int64_t)b * nvals + v];
+    sums[v] = t;
 }
 
 }  // namespace mapstats

@@ -1,5 +1,5 @@
 // bfgx_mapstats_api.inc -- C ABI of the map reductions (bfgx_mapstats.hpp); included from bfgx_api.hip.
-// Every argument is checked before any device call.  Both entries are enqueue-only on hip_stream.
+// Every argument is checked before any device call.  The device entries are enqueue-only on hip_stream.
 namespace {
 
 static_assert(BFGX_MAPSTATS_WORK_DOUBLES == mapstats::kMaxBlocks * mapstats::kSlots, "work array of bfgx_mapstats_moments_device");
@@ -57,6 +57,30 @@ int bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int3
     HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 2 * nb, s));
     hipLaunchKernelGGL(mapstats::mapstats_peaks_kernel, dim3((unsigned)std::min<int64_t>((a.npix + mapstats::kThreads - 1) / mapstats::kThreads, 8192)), dim3(mapstats::kThreads), sizeof(int) * 2 * nb, s, a, map_dev,
                        mask_dev, edges_dev, reinterpret_cast<unsigned long long *>(counts_dev), flags_dev);
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
+int64_t bfgx_mapstats_minkowski_work_doubles(int64_t npix, int32_t nb)
+{
+    if (npix < 1 || npix > 12 * kHpxMaxNside * kHpxMaxNside || nb < 1 || nb > mapstats::kMaxMfBins) return -1;
+    return (int64_t)mapstats::moment_blocks(npix) * 2 * nb;
+}
+
+int bfgx_mapstats_minkowski_device(int device, void *hip_stream, int64_t npix, const double *ders_dev, const uint8_t *mask_dev, int32_t nb,
+                                   const double *edges_dev, int64_t *counts_dev, double *sums_dev, double *work_dev)
+{
+    if (!ders_dev || !edges_dev || !counts_dev || !sums_dev || !work_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (npix < 1 || npix > 12 * kHpxMaxNside * kHpxMaxNside) return fail(BFGX_ERR_INVALID, "npix must be in [1, %lld] (got %lld)", (long long)(12 * kHpxMaxNside * kHpxMaxNside), (long long)npix);
+    if (nb < 1 || nb > mapstats::kMaxMfBins) return fail(BFGX_ERR_INVALID, "nb must be in [1, %d] (got %d)", mapstats::kMaxMfBins, nb);
+    if (int rc = tables_begin(device)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int nblocks = mapstats::moment_blocks(npix);
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * (nb + 3), s));
+    hipLaunchKernelGGL(mapstats::mapstats_minkowski_kernel, dim3(nblocks), dim3(mapstats::kThreads), mapstats::minkowski_lds_bytes(nb), s, npix,
+                       (int)nb, ders_dev, mask_dev, edges_dev, reinterpret_cast<unsigned long long *>(counts_dev), work_dev);
+    hipLaunchKernelGGL(mapstats::mapstats_minkowski_combine_kernel, dim3((2 * nb + mapstats::kThreads - 1) / mapstats::kThreads),
+                       dim3(mapstats::kThreads), 0, s, nblocks, 2 * (int)nb, (const double *)work_dev, sums_dev);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }

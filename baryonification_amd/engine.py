@@ -487,6 +487,7 @@ class ShtPlan(object):
         self.dev = torch.device('cuda', self.device)
         self.work = torch.empty(nw, dtype=torch.float64, device=self.dev)
         self.spin_work = None                                 # F of a spin transform's second map, on the first spin call
+        self.der_scratch = None                               # l-factors and scaled alm of alm2map_der_device, on its first call
         _lib.check(L.bfgx_sht_prepare_device(self.device, self._stream(), self.nside, self.lmax, self.mmax, C.c_void_p(self.work.data_ptr())))
 
     def _stream(self):
@@ -542,6 +543,38 @@ class ShtPlan(object):
                                                            C.c_void_p(alms_dev.data_ptr()), C.c_void_p(maps.data_ptr()),
                                                            C.c_void_p(self.work.data_ptr()), C.c_void_p(self._spin_work().data_ptr())))
         return maps
+
+    def _der_scratch(self):
+        """(fl [3, lmax + 1], alms [2, nalm]): the factors sqrt(l(l+1)), -l(l+1), -sqrt((l+2)(l+1)l(l-1)) that turn the alm of u into
+        those of its gradient, Laplacian and trace-free Hessian, and one [G, C] pair whose C stays 0; made on the first call"""
+        if self.der_scratch is None:
+            import torch
+            l = np.arange(self.lmax + 1, dtype=np.float64)
+            fl = np.stack([np.sqrt(l * (l + 1.0)), -l * (l + 1.0), -np.sqrt((l + 2.0) * (l + 1.0) * l * np.maximum(l - 1.0, 0.0))])
+            self.der_scratch = (torch.from_numpy(fl).to(self.dev), torch.zeros((2, self.nalm), dtype=torch.complex128, device=self.dev))
+        return self.der_scratch
+
+    def alm2map_der_device(self, alm_dev, out):
+        """the derivatives of the map u of complex128 alm [nalm] in the orthonormal basis (e_theta, e_phi), written into the float64
+        RING maps out [3, npix] = [u, u_t, u_p] (u_t = d_theta u, u_p = d_phi u / sin theta) or out [6, npix] = those and the second
+        covariant derivatives in spin form, lap = u;tt + u;pp, q_plus = u;tt - u;pp, q_cross = 2 u;tp: one spin-0, one spin-1 and,
+        for six maps, another spin-0 and one spin-2 synthesis of the scaled alm.  Nothing is allocated after the first call."""
+        fl, pair = self._der_scratch()
+        self.alm2map_device(alm_dev, out=out[0])
+        if self.lmax >= 1:
+            self.almxfl_device(alm_dev, fl[0], out=pair[0])
+            self.alm2map_spin_device(pair, 1, out=out[1:3])
+        else:
+            out[1:3].zero_()
+        if out.shape[0] == 6:
+            self.almxfl_device(alm_dev, fl[1], out=pair[0])
+            self.alm2map_device(pair[0], out=out[3])
+            if self.lmax >= 2:
+                self.almxfl_device(alm_dev, fl[2], out=pair[0])
+                self.alm2map_spin_device(pair, 2, out=out[4:6])
+            else:
+                out[4:6].zero_()
+        return out
 
 
 def alm2cl_device(alm1_dev, alm2_dev, lmax, mmax, lmax_out=None, out=None, device=0):

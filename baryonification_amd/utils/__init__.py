@@ -3,6 +3,7 @@ from .cosmology import *
 from .Tabulate import *
 from .Parallelize import *
 from .Pixel import *
-from .sphtfunc import map2alm, alm2map, alm2cl, anafast, map2alm_spin, alm2map_spin, gauss_beam, tophat_beam, almxfl, smoothalm, smoothing
+from .sphtfunc import map2alm, alm2map, alm2cl, anafast, map2alm_spin, alm2map_spin, gauss_beam, tophat_beam, almxfl, smoothalm, smoothing, alm2map_der1, alm2map_der2
 from .pixelfunc import ud_grade, get_interp_weights, get_interp_val, get_all_neighbours, UNSEEN
-from .mapstats import map_moments, peak_counts, shell_statistics, moment_exponents
+from .mapstats import (map_moments, peak_counts, shell_statistics, moment_exponents, minkowski_functionals,
+                       minkowski_from_derivatives, minkowski_gaussian)

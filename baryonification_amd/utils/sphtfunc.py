@@ -26,6 +26,12 @@ and back: E, B = map2alm_spin([gamma1, gamma2], 2); alm2cl(E), alm2cl(B), alm2cl
 
 Filters in harmonic space: gauss_beam / tophat_beam are windows W_l (host numpy), almxfl multiplies alm by one on the GPU, and
 smoothalm / smoothing are healpy's (smoothing = map2alm, almxfl, alm2map on the cached plan of the shape; a single RING map).
+
+Derivatives of the band-limited map u of a set of alm, in the orthonormal basis (e_theta, e_phi): alm2map_der1 is healpy's
+([u, d_theta u, d_phi u / sin theta]); alm2map_der2 adds the second covariant derivatives
+    u;tt = d_theta^2 u,   u;tp = d_theta d_phi u / sin - cos d_phi u / sin^2,   u;pp = d_phi^2 u / sin^2 + cos d_theta u / sin.
+They are syntheses of scaled alm in the spin convention above: spin 1 of [sqrt(l(l+1)) a, 0] is (u_t, u_p), spin 2 of
+[-sqrt((l+2)(l+1)l(l-1)) a, 0] is (u;tt - u;pp, 2 u;tp), and spin 0 of -l(l+1) a is the Laplacian u;tt + u;pp.
 """
 import numpy as np
 
@@ -33,7 +39,7 @@ from .. import engine
 from .io import npix2nside
 
 __all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'map2alm_spin', 'alm2map_spin', 'getlmax', 'getidx', 'getsize', 'UNSEEN',
-           'gauss_beam', 'tophat_beam', 'almxfl', 'smoothalm', 'smoothing']
+           'gauss_beam', 'tophat_beam', 'almxfl', 'smoothalm', 'smoothing', 'alm2map_der1', 'alm2map_der2']
 
 UNSEEN = -1.6375e30
 
@@ -280,6 +286,38 @@ def alm2map_spin(alms, nside, spin, lmax, mmax=None):
         import torch
         return plan.alm2map_spin_device(torch.stack([a, b]), spin)
     return plan.alm2map_spin_device(_to_device(np.stack([a, b]), plan), spin).cpu().numpy()
+
+
+# -------------------------------------------------------------------------------------------------------------- derivatives
+def _alm2map_der(alm, nside, lmax, mmax, nmaps):
+    a, lmax, mmax, on_dev = _alm_input(alm, lmax, mmax, 'alm')
+    nside = int(nside)
+    if nside < 1:
+        raise ValueError("nside must be >= 1")
+    _shape(nside, lmax, mmax)
+    plan = engine.sht_plan(nside, lmax, mmax, device=(a.device.index or 0) if on_dev else 0)
+    import torch
+    out = torch.empty((nmaps, plan.npix), dtype=torch.float64, device=plan.dev)
+    return plan.alm2map_der_device(a if on_dev else _to_device(a, plan), out), on_dev
+
+
+def alm2map_der1(alm, nside, lmax=None, mmax=None):
+    """healpy.alm2map_der1: float64 RING maps [3, npix] = [m, d_theta m, d_phi m / sin(theta)] of one set of alm (nside <= 2048).
+    A CUDA complex128 tensor gives a CUDA result."""
+    out, on_dev = _alm2map_der(alm, nside, lmax, mmax, 3)
+    return out if on_dev else out.cpu().numpy()
+
+
+def alm2map_der2(alm, nside, lmax=None, mmax=None, spin_form=False):
+    """float64 RING maps [6, npix] = [u, u_t, u_p, u;tt, u;tp, u;pp] of one set of alm (nside <= 2048): the map, its gradient
+    (u_t = d_theta u, u_p = d_phi u / sin theta) and its second covariant derivatives in the orthonormal basis (e_theta, e_phi).
+    With spin_form=True the last three are, as synthesised, lap = u;tt + u;pp, q_plus = u;tt - u;pp and q_cross = 2 u;tp (what
+    minkowski_from_derivatives(spin_form=True) reads).  A CUDA complex128 tensor gives a CUDA result."""
+    out, on_dev = _alm2map_der(alm, nside, lmax, mmax, 6)
+    if not spin_form:
+        lap, qp = out[3].clone(), out[4].clone()
+        out[3], out[4], out[5] = 0.5 * (lap + qp), 0.5 * out[5], 0.5 * (lap - qp)
+    return out if on_dev else out.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------- harmonic filters

@@ -701,7 +701,7 @@ int  bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, dou
 int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n, const double *vals_host, const int64_t *pix_host,
                           const double *w_host);
 
-/* ---- reductions over HEALPix maps: moments, cross-moments and peak counts (device entries, enqueue-only on hip_stream) -------------
+/* ---- reductions over HEALPix maps: moments, cross-moments, peak counts, Minkowski sums (device entries, enqueue-only on hip_stream) -------------
  * A pixel is good if every map is finite and not UNSEEN there (healpy.mask_bad's tolerance) and mask_dev (optional, one byte per
  * pixel) is nonzero.
  * moments: maps_dev = nmaps maps of npix doubles, row after row, 1 <= nmaps <= 3, 2 <= order <= 4.  *n_dev = good pixels (exact);
@@ -716,13 +716,25 @@ int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n
  *   greater than every existing neighbour (bfgx_hpx_neighbours), a minimum if strictly less, and only if it and all of them are good.
  *   counts_dev[2][nb] (zeroed by the entry) = maxima | minima with edges[b] <= value < edges[b + 1]; values outside the edges are not
  *   counted.  edges_dev: nb + 1 ascending finite doubles on the device (1 <= nb <= 4096; the order is the caller's to check).
- *   flags_dev (optional, one int8 per pixel): +1 maximum, -1 minimum, 0 neither.  Integer atomics: the counts are exact. */
+ *   flags_dev (optional, one int8 per pixel): +1 maximum, -1 minimum, 0 neither.  Integer atomics: the counts are exact.
+ * minkowski: ders_dev = six maps of npix doubles, row after row, the derivatives of a map u in the orthonormal basis (e_theta, e_phi) in
+ *   spin form: u, u_t, u_p, lap = u;tt + u;pp, q_plus = u;tt - u;pp, q_cross = 2 u;tp.  A pixel is good if all six are finite, u is not UNSEEN and the mask is nonzero.  With
+ *   g2 = u_t^2 + u_p^2 and c = u_t u_p q_cross - lap g2 / 2 + q_plus (u_t^2 - u_p^2) / 2 (= 2 u_t u_p u;tp - u_t^2 u;pp - u_p^2 u;tt),
+ *   over the good pixels with edges[b] <= u < edges[b + 1]:  counts_dev[b] = their number, sums_dev[0][b] = sum sqrt(g2),
+ *   sums_dev[1][b] = sum c / g2 (a pixel with g2 = 0 adds 0); counts_dev[nb] = good pixels below edges[0], counts_dev[nb + 1] = at or
+ *   above edges[nb], counts_dev[nb + 2] = all good pixels (int64 [nb + 3], zeroed by the entry; double [2][nb]).  edges_dev: nb + 1
+ *   ascending finite doubles on the device, 1 <= nb <= 512.  The sums are fp64 block partials over a grid that depends on npix alone,
+ *   added in a fixed order, no float atomics: a repeated call gives the same bits.  work_dev:
+ *   bfgx_mapstats_minkowski_work_doubles(npix, nb) doubles of scratch (host arithmetic; -1 = invalid npix / nb). */
 #define BFGX_MAPSTATS_WORK_DOUBLES 32768
 int32_t bfgx_mapstats_moment_terms(int32_t nmaps, int32_t order);
 int  bfgx_mapstats_moments_device(int device, void *hip_stream, int64_t npix, int32_t nmaps, int32_t order, const double *maps_dev,
                                   const uint8_t *mask_dev, int64_t *n_dev, double *out_dev, double *work_dev);
 int  bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int32_t nest, const double *map_dev, const uint8_t *mask_dev,
                                 int32_t nb, const double *edges_dev, int64_t *counts_dev, int8_t *flags_dev);
+int64_t bfgx_mapstats_minkowski_work_doubles(int64_t npix, int32_t nb);
+int  bfgx_mapstats_minkowski_device(int device, void *hip_stream, int64_t npix, const double *ders_dev, const uint8_t *mask_dev, int32_t nb,
+                                    const double *edges_dev, int64_t *counts_dev, double *sums_dev, double *work_dev);
 
 /* ---- halo-centred radial profiles of shell maps (MeasureProfilesShell) ------------------------------
  * The adjoint of PaintProfilesShell: for halo j the pixels of query_disc(nside, vec_j, R_j epsilon_max / D_j) (RING, no < 4-pixel fallback) at
