@@ -74,6 +74,14 @@ int alloc_fail(const char *what) { return fail(BFGX_ERR_HIP, kDevAllocFailed, wh
             return fail(BFGX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// every entry that takes a device number starts here: libbfgx has no CPU fallback
+int select_device(int device)
+{
+    if (bfgx_device_count() <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
+    HIP_TRY(hipSetDevice(device));
+    return BFGX_OK;
+}
+
 int validate_cosmo(const bfgx_cosmo &c)
 {
     if (!(c.Omega_m > 0) || !(c.h > 0) || !(c.Omega_b >= 0) || c.w0 != c.w0)
@@ -1972,18 +1980,10 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------ synchronous host entries: the call scaffold
+#include "bfgx_hostcall.hpp"
+
 // ------------------------------------------------------------------------------ table builders (a6-a8)
-namespace {
-
-int tables_begin(int device)
-{
-    if (bfgx_device_count() <= 0) return fail(BFGX_ERR_NO_DEVICE, "no HIP device visible: libbfgx has no CPU fallback");
-    HIP_TRY(hipSetDevice(device));
-    return BFGX_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int bfgx_project_profile(int device, int64_t nrows, int32_t nl, const double *l, const double *rho,
@@ -1991,16 +1991,13 @@ int bfgx_project_profile(int device, int64_t nrows, int32_t nl, const double *l,
 {
     if (!l || !rho || !r || !sigma_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes (1 <= nrows <= 65535, 2 <= nl <= 2048)");
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf dl, drho, dr, dout;
-    if (dl.up(l, sizeof(double) * nl) || drho.up(rho, sizeof(double) * nrows * nl) || dr.up(r, sizeof(double) * nr) ||
-        dout.up(nullptr, sizeof(double) * nrows * nr))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
+    HostCall c(device);
+    const double *dl = c.in(l, nl), *drho = c.in(rho, nrows * nl), *dr = c.in(r, nr);
+    double *dout = c.out(sigma_out, nrows * nr);
+    if (int rc = c.ready()) return rc;
     hipLaunchKernelGGL(project_kernel, dim3((unsigned)((nr + 255) / 256), (unsigned)nrows), dim3(256), 3 * sizeof(double) * nl, 0,
-                       nl, dl.as<double>(), drho.as<double>(), nr, dr.as<double>(), scale, dout.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(sigma_out, dout.p, sizeof(double) * nrows * nr, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+                       nl, dl, drho, nr, dr, scale, dout);
+    return c.finish();
 }
 
 static int enclosed_mass_rows(int dim, int device, int64_t nrows, int64_t n_int, const double *r_int, const double *Sigma,
@@ -2008,17 +2005,12 @@ static int enclosed_mass_rows(int dim, int device, int64_t nrows, int64_t n_int,
 {
     if (!r_int || !Sigma || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf dri, dS, dr, dcx, dcy, dM;
-    if (dri.up(r_int, sizeof(double) * n_int) || dS.up(Sigma, sizeof(double) * nrows * n_int) || dr.up(r, sizeof(double) * nr) ||
-        dcx.up(nullptr, sizeof(double) * nrows * n_int) || dcy.up(nullptr, sizeof(double) * nrows * n_int) ||
-        dM.up(nullptr, sizeof(double) * nrows * nr))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
-    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri.as<double>(),
-                       dS.as<double>(), nr, dr.as<double>(), dcx.as<double>(), dcy.as<double>(), dM.as<double>(), dim);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(M_f, dM.p, sizeof(double) * nrows * nr, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    HostCall c(device);
+    const double *dri = c.in(r_int, n_int), *dS = c.in(Sigma, nrows * n_int), *dr = c.in(r, nr);
+    double *dcx = c.scratch<double>(nrows * n_int), *dcy = c.scratch<double>(nrows * n_int), *dM = c.out(M_f, nrows * nr);
+    if (int rc = c.ready()) return rc;
+    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri, dS, nr, dr, dcx, dcy, dM, dim);
+    return c.finish();
 }
 
 int bfgx_enclosed_mass_from_sigma(int device, int64_t nrows, int64_t n_int, const double *r_int, const double *Sigma,
@@ -2038,22 +2030,18 @@ int bfgx_enclosed_mass_2d(int device, int64_t nrows, int32_t nl, const double *l
 {
     if (!l || !rho || !r_int || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf dl, drho, dri, dS, dr, dcx, dcy, dM;
-    if (dl.up(l, sizeof(double) * nl) || drho.up(rho, sizeof(double) * nrows * nl) || dri.up(r_int, sizeof(double) * n_int) ||
-        dS.up(nullptr, sizeof(double) * nrows * n_int) || dr.up(r, sizeof(double) * nr) ||
-        dcx.up(nullptr, sizeof(double) * nrows * n_int) || dcy.up(nullptr, sizeof(double) * nrows * n_int) ||
-        dM.up(nullptr, sizeof(double) * nrows * nr))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
+    HostCall c(device);
+    const double *dl = c.in(l, nl), *drho = c.in(rho, nrows * nl), *dri = c.in(r_int, n_int);
+    double *dS = c.scratch<double>(nrows * n_int);
+    const double *dr = c.in(r, nr);
+    double *dcx = c.scratch<double>(nrows * n_int), *dcy = c.scratch<double>(nrows * n_int), *dM = c.out(M_f, nrows * nr);
+    if (int rc = c.ready()) return rc;
     // Sigma = model.projected(r_int) * a   (BaryonCorrection.py:646), then the prefix sum + log-log PCHIP
     hipLaunchKernelGGL(project_kernel, dim3((unsigned)((n_int + 255) / 256), (unsigned)nrows), dim3(256), 3 * sizeof(double) * nl, 0,
-                       nl, dl.as<double>(), drho.as<double>(), n_int, dri.as<double>(), a, dS.as<double>());
+                       nl, dl, drho, n_int, dri, a, dS);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri.as<double>(),
-                       dS.as<double>(), nr, dr.as<double>(), dcx.as<double>(), dcy.as<double>(), dM.as<double>(), 2);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(M_f, dM.p, sizeof(double) * nrows * nr, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri, dS, nr, dr, dcx, dcy, dM, 2);
+    return c.finish();
 }
 
 int bfgx_displacement_rows(int device, int64_t nrows, int32_t nr, const double *r, const double *M_dmo, const double *M_dmb,
@@ -2061,19 +2049,15 @@ int bfgx_displacement_rows(int device, int64_t nrows, int32_t nr, const double *
 {
     if (!r || !M_dmo || !M_dmb || !d_out || !status) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nr < 3 || nr > kMaxNR) return fail(BFGX_ERR_INVALID, "N_samples_R must be in [3, %d]", kMaxNR);
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf dr, da, db, dd, ds;
-    if (dr.up(r, sizeof(double) * nr) || da.up(M_dmo, sizeof(double) * nrows * nr) || db.up(M_dmb, sizeof(double) * nrows * nr) ||
-        dd.up(nullptr, sizeof(double) * nrows * nr) || ds.up(nullptr, sizeof(int32_t) * nrows))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
+    HostCall c(device);
+    const double *dr = c.in(r, nr), *da = c.in(M_dmo, nrows * nr), *db = c.in(M_dmb, nrows * nr);
+    double *dd = c.out(d_out, nrows * nr);
+    int32_t *ds = c.out(status, nrows);
+    if (int rc = c.ready()) return rc;
     const size_t lds = kDisplacementLdsPerNode * nr;
     HIP_TRY(hipFuncSetAttribute((const void *)displacement_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(displacement_kernel, dim3((unsigned)nrows), dim3(256), lds, 0, nr, dr.as<double>(), da.as<double>(),
-                       db.as<double>(), dd.as<double>(), ds.as<int32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(d_out, dd.p, sizeof(double) * nrows * nr, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status, ds.p, sizeof(int32_t) * nrows, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    hipLaunchKernelGGL(displacement_kernel, dim3((unsigned)nrows), dim3(256), lds, 0, nr, dr, da, db, dd, ds);
+    return c.finish();
 }
 
 int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const double *rho_tot, const double *rho_gas,
@@ -2081,19 +2065,15 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 {
     if (!r500 || !rho_tot || !rho_gas || !r_out || !P_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nrows < 1 || nr_out < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf dg, dt, dgas, dr, dP;
-    if (dg.up(r500, sizeof(double) * kPressureN) || dt.up(rho_tot, sizeof(double) * nrows * kPressureN) ||
-        dgas.up(rho_gas, sizeof(double) * nrows * kPressureN) || dr.up(r_out, sizeof(double) * nr_out) ||
-        dP.up(nullptr, sizeof(double) * nrows * nr_out))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
+    HostCall c(device);
+    const double *dg = c.in(r500, kPressureN), *dt = c.in(rho_tot, nrows * kPressureN), *dgas = c.in(rho_gas, nrows * kPressureN);
+    const double *dr = c.in(r_out, nr_out);
+    double *dP = c.out(P_out, nrows * nr_out);
+    if (int rc = c.ready()) return rc;
     const double G = kGnewt / (kMpcToMeter * kMpcToMeter * kMpcToMeter) * kSolarMass;       // Thermodynamic.py:11
     const double unit = (kSolarMass * 1e3) / (kMpcToMeter * 1e2);                           // :265
-    hipLaunchKernelGGL(pressure_kernel, dim3((unsigned)nrows), dim3(256), 0, 0, dg.as<double>(), dt.as<double>(),
-                       dgas.as<double>(), nr_out, dr.as<double>(), G, unit, cutoff, dP.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(P_out, dP.p, sizeof(double) * nrows * nr_out, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    hipLaunchKernelGGL(pressure_kernel, dim3((unsigned)nrows), dim3(256), 0, 0, dg, dt, dgas, nr_out, dr, G, unit, cutoff, dP);
+    return c.finish();
 }
 
 }  // extern "C"

@@ -101,13 +101,12 @@ int bfgx_fftlog_transform(int device, int64_t nrows, int32_t n, const double *r,
     if (nrows < 1 || nrows > 65535) return fail(BFGX_ERR_INVALID, "fftlog: 1 <= nrows <= 65535");
     FftlogStage s;
     if (int rc = fftlog_stage(n, r, dim, mu, plaw, s)) return rc;
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf din, dpre, du, dpost, dout;
-    if (din.up(f, sizeof(double) * nrows * n) || dpre.up(s.pre.data(), sizeof(double) * n) || du.up(s.u.data(), sizeof(double) * s.u.size()) ||
-        dpost.up(s.post.data(), sizeof(double) * n) || dout.up(nullptr, sizeof(double) * nrows * n))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
-    if (int rc = launch_fht((int)nrows, n, din.as<double>(), dpre.as<double>(), du.as<double>(), dpost.as<double>(), dout.as<double>())) return rc;
-    HIP_TRY(hipMemcpy(F_out, dout.p, sizeof(double) * nrows * n, hipMemcpyDeviceToHost));
+    HostCall c(device);
+    const double *din = c.in(f, nrows * n), *dpre = c.in(s.pre.data(), n), *du = c.in(s.u.data(), s.u.size()), *dpost = c.in(s.post.data(), n);
+    double *dout = c.out(F_out, nrows * n);
+    if (int rc = c.ready()) return rc;
+    if (int rc = launch_fht((int)nrows, n, din, dpre, du, dpost, dout)) return rc;
+    if (int rc = c.finish()) return rc;
     std::memcpy(k_out, s.k.data(), sizeof(double) * n);
     return BFGX_OK;
 }
@@ -128,21 +127,19 @@ int bfgx_fftlog_convolve(int device, int64_t nrows, int32_t n, const double *r_f
         lnr[j] = std::log(s2.k[j] * r_scale);                                        // np.log(r_out) (r_out * D_A when harmonic, :216)
     }
     for (int i = 0; i < nq; ++i) lnq[i] = std::log(r_eval[i]);
-    if (int rc = tables_begin(device)) return rc;
-    DevBuf din, dpre, du1, dmid, dtmp, du2, dpost, dg, dx, dq, dout;
-    if (din.up(prof, sizeof(double) * nrows * n) || dpre.up(s1.pre.data(), sizeof(double) * n) || du1.up(s1.u.data(), sizeof(double) * s1.u.size()) ||
-        dmid.up(mid.data(), sizeof(double) * n) || dtmp.up(nullptr, sizeof(double) * nrows * n) || du2.up(s2.u.data(), sizeof(double) * s2.u.size()) ||
-        dpost.up(s2.post.data(), sizeof(double) * n) || dg.up(nullptr, sizeof(double) * nrows * n) || dx.up(lnr.data(), sizeof(double) * n) ||
-        dq.up(lnq.data(), sizeof(double) * nq) || dout.up(nullptr, sizeof(double) * nrows * nq))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
-    if (int rc = launch_fht((int)nrows, n, din.as<double>(), dpre.as<double>(), du1.as<double>(), dmid.as<double>(), dtmp.as<double>())) return rc;
-    if (int rc = launch_fht((int)nrows, n, dtmp.as<double>(), nullptr, du2.as<double>(), dpost.as<double>(), dg.as<double>())) return rc;
+    HostCall c(device);
+    const double *din = c.in(prof, nrows * n), *dpre = c.in(s1.pre.data(), n), *du1 = c.in(s1.u.data(), s1.u.size()), *dmid = c.in(mid.data(), n);
+    double *dtmp = c.scratch<double>(nrows * n);
+    const double *du2 = c.in(s2.u.data(), s2.u.size()), *dpost = c.in(s2.post.data(), n);
+    double *dg = c.scratch<double>(nrows * n);
+    const double *dx = c.in(lnr.data(), n), *dq = c.in(lnq.data(), nq);
+    double *dout = c.out(out, nrows * nq);
+    if (int rc = c.ready()) return rc;
+    if (int rc = launch_fht((int)nrows, n, din, dpre, du1, dmid, dtmp)) return rc;
+    if (int rc = launch_fht((int)nrows, n, dtmp, nullptr, du2, dpost, dg)) return rc;
     const double scale = (dim == 3) ? 8 * M_PI * M_PI * M_PI : 4 * M_PI * M_PI;      // (2 pi)^dim, :155 / :222
-    hipLaunchKernelGGL(pchip_rows_kernel, dim3((unsigned)((nq + 255) / 256), (unsigned)nrows), dim3(256), 0, 0, n, dx.as<double>(),
-                       dg.as<double>(), nq, dq.as<double>(), scale, dout.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * nrows * nq, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    hipLaunchKernelGGL(pchip_rows_kernel, dim3((unsigned)((nq + 255) / 256), (unsigned)nrows), dim3(256), 0, 0, n, dx, dg, nq, dq, scale, dout);
+    return c.finish();
 }
 
 }  // extern "C"

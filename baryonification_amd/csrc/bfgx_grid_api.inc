@@ -711,20 +711,18 @@ int bfgx_regrid_pixels(int device, int32_t ndim, int32_t npix, int64_t n, const 
 {
     if (!positions || !values || !grid) return fail(BFGX_ERR_INVALID, "NULL argument");
     if ((ndim != 2 && ndim != 3) || npix < 5 || n < 0) return fail(BFGX_ERR_INVALID, "regrid_pixels needs ndim in {2, 3}, npix >= 5");
-    if (int rc = tables_begin(device)) return rc;
+    HostCall c(device);
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)npix;
-    DevBuf dp, dv, dg;
-    if (dp.up(positions, sizeof(double) * (size_t)n * ndim) || dv.up(values, sizeof(double) * (size_t)n) || dg.up(grid, sizeof(double) * ntot))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+    const double *dp = c.in(positions, (size_t)n * ndim), *dv = c.in(values, n);
+    double *dg = c.inout(grid, ntot);
+    if (int rc = c.ready()) return rc;
     if (n > 0) {
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (ndim == 3) hipLaunchKernelGGL(pixel_deposit_kernel<3>, dim3(blocks), dim3(256), 0, 0, npix, n, dp.as<double>(), dv.as<double>(), dg.as<double>());
-        else hipLaunchKernelGGL(pixel_deposit_kernel<2>, dim3(blocks), dim3(256), 0, 0, npix, n, dp.as<double>(), dv.as<double>(), dg.as<double>());
-        HIP_TRY(hipGetLastError());
+        if (ndim == 3) hipLaunchKernelGGL(pixel_deposit_kernel<3>, dim3(blocks), dim3(256), 0, 0, npix, n, dp, dv, dg);
+        else hipLaunchKernelGGL(pixel_deposit_kernel<2>, dim3(blocks), dim3(256), 0, 0, npix, n, dp, dv, dg);
     }
-    HIP_TRY(hipMemcpy(grid, dg.p, sizeof(double) * ntot, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    return c.finish();
 }
 
 }  // extern "C"
@@ -800,7 +798,7 @@ int bfgx_route_particles_count_device(int device, void *hip_stream, int64_t n, c
 {
     if ((n > 0 && (!x || !owner_dev)) || !edges_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (n < 0 || n_grid < 1 || world < 1 || world > kPartRouteMaxRanks || n_grid % world) return fail(BFGX_ERR_INVALID, "particle routing needs 1 <= world <= %d ranks that divide n_grid", kPartRouteMaxRanks);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int32_t) * world, s));
     if (n > 0) {
@@ -816,7 +814,7 @@ int bfgx_route_particles_fill_device(int device, void *hip_stream, int64_t n, in
 {
     if (!cols || !start_host || !cursor_dev || (n > 0 && !owner_dev) || (total > 0 && !cols_out_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (n < 0 || total < 0 || total > n || ncols < 1 || ncols > 4 || world < 1 || world > kPartRouteMaxRanks) return fail(BFGX_ERR_INVALID, "bad particle routing arguments");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     PartRouteArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -849,7 +847,7 @@ static int deposit_impl(int device, void *hip_stream, int32_t ndim, int64_t n, c
     if ((n > 0 && (!x || !y || (ndim == 3 && !z))) || !edges_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1");
     if (plane_lo < 0 || plane_n < 1 || plane_lo + plane_n > n_grid) return fail(BFGX_ERR_INVALID, "slab [%d, %d) outside the grid", plane_lo, plane_lo + plane_n);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     size_t ntot = (size_t)plane_n;
     for (int d = 1; d < ndim; ++d) ntot *= (size_t)n_grid;
@@ -916,18 +914,15 @@ int bfgx_deposit_particles(int device, int32_t ndim, int64_t n, const double *x,
     if (!x || !y || (ndim == 3 && !z) || !edges || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
     if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1");
     for (int i = 1; i <= n_grid; ++i) if (!(edges[i] > edges[i - 1])) return fail(BFGX_ERR_INVALID, "edges must be strictly ascending");
-    if (int rc = tables_begin(device)) return rc;
+    HostCall c(device);
     size_t ntot = 1;
     for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
-    DevBuf dx, dy, dz, dm, de, dout;
-    const size_t nb = sizeof(double) * (size_t)n;
-    if (dx.up(x, nb) || dy.up(y, nb) || (ndim == 3 && dz.up(z, nb)) || (mass && dm.up(mass, nb)) || de.up(edges, sizeof(double) * (n_grid + 1)) ||
-        dout.up(nullptr, sizeof(double) * ntot))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_deposit_particles_device(device, nullptr, ndim, n, dx.as<double>(), dy.as<double>(), ndim == 3 ? dz.as<double>() : nullptr,
-                                               mass ? dm.as<double>() : nullptr, n_grid, de.as<double>(), dout.as<double>())) return rc;
-    HIP_TRY(hipMemcpy(map_out, dout.p, sizeof(double) * ntot, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    const double *dx = c.in(x, n), *dy = c.in(y, n), *dz = ndim == 3 ? c.in(z, n) : nullptr, *dm = mass ? c.in(mass, n) : nullptr;
+    const double *de = c.in(edges, n_grid + 1);
+    double *dout = c.out(map_out, ntot);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_deposit_particles_device(device, nullptr, ndim, n, dx, dy, dz, dm, n_grid, de, dout)) return rc;
+    return c.finish();
 }
 
 }  // extern "C"
@@ -962,7 +957,7 @@ int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const vo
     if (itemsize < 16 || itemsize % 8 || bad(off_x) || bad(off_y) || (ndim == 3 && bad(off_z)) || (off_mass >= 0 && bad(off_mass)))
         return fail(BFGX_ERR_INVALID, "records must be a multiple of 8 bytes with 8-byte aligned float64 fields");
     for (int i = 1; i <= n_grid; ++i) if (!(edges[i] > edges[i - 1])) return fail(BFGX_ERR_INVALID, "edges must be strictly ascending");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     std::lock_guard<std::mutex> lk(g_deprec_mu);
     DepRecBuf &b = g_deprec[device];
     size_t ntot = 1;
@@ -1052,7 +1047,7 @@ struct FftSetup {
         const double step = (k_hi - k_lo) / nk;
         const double kb1 = (nk == 1) ? k_hi : (1.0 * step + k_lo);
         dk = kb1 - k_lo;
-        if (dtw.up(tw.data(), sizeof(double) * N) || dkl.up(klin.data(), sizeof(double) * N)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
+        if (dtw.up(tw.data(), sizeof(double) * N) || dkl.up(klin.data(), sizeof(double) * N)) return alloc_fail("fft tables");
         lt = kFftTileLog2;
         while (((size_t)N << lt) > 4096 && lt > 2) --lt;                                              // at most 64 KB of tile per workgroup
         tile = 1 << lt;
@@ -1184,7 +1179,7 @@ int bfgx_power_spectrum_device(int device, void *hip_stream, int32_t n_grid, con
     if (!map_dev || !work_dev || !pk_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nk < 1 || nk > 2048 || !(L > 0)) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048, L > 0");
     if (reinterpret_cast<uintptr_t>(work_dev) & 15) return fail(BFGX_ERR_INVALID, "work_dev must be 16-byte aligned (complex values)");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     if (int rc = fft_setup(device, n_grid, L, nk, &f)) return rc;
@@ -1197,7 +1192,7 @@ int bfgx_fft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, in
 {
     if (!map_dev || !work_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (planes < 1 || planes > n_grid || ((int64_t)planes * n_grid) % 2) return fail(BFGX_ERR_INVALID, "slab of %d planes", planes);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     if (int rc = fft_setup(device, n_grid, 1.0, 1, &f)) return rc;
@@ -1210,7 +1205,7 @@ int bfgx_fft_slab_axis0_pk_device(int device, void *hip_stream, int32_t n_grid, 
     if (!work_dev || !pk_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (nk < 1 || nk > 2048 || !(L > 0)) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048, L > 0");
     if (ncols < 1 || col0 < 0 || col0 + ncols > n_grid) return fail(BFGX_ERR_INVALID, "columns [%d, %d) outside the grid", col0, col0 + ncols);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     if (int rc = fft_setup(device, n_grid, L, nk, &f)) return rc;
@@ -1222,19 +1217,16 @@ int bfgx_power_spectrum(int device, int32_t n_grid, const double *map, double L,
     if (!map || !pk || !kcen || !counts) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (ilog2_exact(n_grid) < 3 || n_grid > 1024) return fail(BFGX_ERR_UNSUPPORTED, "power spectrum needs n_grid = 2^m with 8 <= n_grid <= 1024");
     if (nk < 1 || nk > 2048) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048");
-    if (int rc = tables_begin(device)) return rc;
+    HostCall c(device);
     const size_t N = n_grid;
-    DevBuf dm, dw, dp, dk, dc;
-    if (dm.up(map, sizeof(double) * N * N * N) || dw.up(nullptr, sizeof(double) * (size_t)bfgx_power_spectrum_work_doubles(n_grid)) || dp.up(nullptr, sizeof(double) * nk) ||
-        dk.up(nullptr, sizeof(double) * nk) || dc.up(nullptr, sizeof(unsigned long long) * nk))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_power_spectrum_device(device, nullptr, n_grid, dm.as<double>(), L, nk, dw.as<double>(), dp.as<double>(), dk.as<double>(),
-                                            dc.as<unsigned long long>())) return rc;
-    std::vector<double> hp(nk), hk(nk);
+    std::vector<double> hp(nk), hk(nk);                      // the bins' sums, divided by their counts below
     std::vector<unsigned long long> hc(nk);
-    HIP_TRY(hipMemcpy(hp.data(), dp.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hk.data(), dk.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hc.data(), dc.p, sizeof(unsigned long long) * nk, hipMemcpyDeviceToHost));
+    const double *dm = c.in(map, N * N * N);
+    double *dw = c.scratch<double>(bfgx_power_spectrum_work_doubles(n_grid)), *dp = c.out(hp.data(), nk), *dk = c.out(hk.data(), nk);
+    unsigned long long *dc = c.out(hc.data(), nk);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_power_spectrum_device(device, nullptr, n_grid, dm, L, nk, dw, dp, dk, dc)) return rc;
+    if (int rc = c.finish()) return rc;
     for (int i = 0; i < nk; ++i) {
         counts[i] = (int64_t)hc[i];
         pk[i] = hp[i] / (double)hc[i];           // 0 / 0 -> NaN for empty bins, as np.bincount(...) / k_c gives

@@ -74,7 +74,59 @@ int hpx_interp_check(int64_t nside, int32_t nest, int64_t n)
     return BFGX_OK;
 }
 
-// theta in [0, pi], phi finite (host arrays)
+// the argument checks of each operation, shared by its host entry and its _device entry (with hpx_ud_grade_check above)
+int hpx_interp_weights_check(int64_t nside, int32_t nest, int64_t n, const void *theta, const void *phi, const void *ipix, const void *pix,
+                             const void *w)
+{
+    if (!pix || !w || (ipix ? (theta || phi) : (!theta || !phi)))
+        return fail(BFGX_ERR_INVALID, "NULL argument (give theta and phi, or ipix alone)");
+    return hpx_interp_check(nside, nest, n);
+}
+
+int hpx_interp_val_check(int64_t nside, int32_t nest, int64_t nmaps, int32_t dtype, const void *maps, int64_t n, const void *theta,
+                         const void *phi, const void *out)
+{
+    if (!maps || !theta || !phi || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
+    if (nmaps < 1) return fail(BFGX_ERR_INVALID, "nmaps must be >= 1 (got %lld)", (long long)nmaps);
+    return hpx_check_dtype(dtype, "dtype");
+}
+
+int hpx_neighbours_check(int64_t nside, int32_t nest, int64_t n, const void *ipix, const void *out)
+{
+    if (!ipix || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
+    if (n > (INT64_MAX >> 4)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
+    return BFGX_OK;
+}
+
+int hpx_scatter_add_check(int64_t npix, int64_t n, const void *hmap, const void *vals, const void *pix, const void *w)
+{
+    if (!hmap || !vals || !pix || !w) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (npix < 1 || n < 0) return fail(BFGX_ERR_INVALID, "npix must be >= 1 and n >= 0 (got npix %lld, n %lld)", (long long)npix, (long long)n);
+    if (n > (INT64_MAX >> 3)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
+    return BFGX_OK;
+}
+
+// checks that read host arrays: the host entries only.  Pixel numbers in [0, npix)
+int hpx_check_pixels(int64_t n, const int64_t *ipix, int64_t npix)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (ipix[i] < 0 || ipix[i] >= npix) return fail(BFGX_ERR_INVALID, "ipix[%lld] = %lld is outside [0, %lld)", (long long)i, (long long)ipix[i], (long long)npix);
+    return BFGX_OK;
+}
+
+// scatter_add's indices (4 per entry) in [-npix, npix)
+int hpx_check_scatter_indices(int64_t n, const int64_t *pix, int64_t npix)
+{
+    for (int64_t e = 0; e < 4 * n; ++e)
+        if (pix[e] < -npix || pix[e] >= npix)
+            return fail(BFGX_ERR_INVALID, "index %lld (entry %lld) is outside [-%lld, %lld)", (long long)pix[e], (long long)e, (long long)npix,
+                        (long long)npix);
+    return BFGX_OK;
+}
+
+// theta in [0, pi], phi finite
 int hpx_check_angles(int64_t n, const double *theta, const double *phi)
 {
     for (int64_t i = 0; i < n; ++i) {
@@ -105,7 +157,7 @@ int bfgx_hpx_ud_grade_device(int device, void *hip_stream, int64_t nside_in, int
                              void *map_out_dev)
 {
     if (int rc = hpx_ud_grade_check(nside_in, nside_out, nmaps, dtype_in, dtype_out, ratio, map_in_dev, map_out_dev)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     return hpx_ud_grade_enqueue((hipStream_t)hip_stream, nside_in, nside_out, nmaps, nest_in, nest_out, pess, ratio, dtype_in, dtype_out,
                                 map_in_dev, map_out_dev);
 }
@@ -114,24 +166,20 @@ int bfgx_hpx_ud_grade(int device, int64_t nside_in, int64_t nside_out, int64_t n
                       double ratio, int32_t dtype_in, int32_t dtype_out, const void *map_in, void *map_out)
 {
     if (int rc = hpx_ud_grade_check(nside_in, nside_out, nmaps, dtype_in, dtype_out, ratio, map_in, map_out)) return rc;
-    if (int rc = tables_begin(device)) return rc;
-    const size_t bin = hpx_dsize(dtype_in) * (size_t)nmaps * 12 * nside_in * nside_in;
-    const size_t bout = hpx_dsize(dtype_out) * (size_t)nmaps * 12 * nside_out * nside_out;
-    DevBuf di, dout;
-    if (di.up(map_in, bin) || dout.up(nullptr, bout)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = hpx_ud_grade_enqueue(nullptr, nside_in, nside_out, nmaps, nest_in, nest_out, pess, ratio, dtype_in, dtype_out, di.p, dout.p))
-        return rc;
-    HIP_TRY(hipMemcpy(map_out, dout.p, bout, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    HostCall c(device);
+    // (maps of either dtype: counted in bytes)
+    const char *di = c.in((const char *)map_in, hpx_dsize(dtype_in) * (size_t)nmaps * 12 * nside_in * nside_in);
+    char *dout = c.out((char *)map_out, hpx_dsize(dtype_out) * (size_t)nmaps * 12 * nside_out * nside_out);
+    if (int rc = c.ready()) return rc;
+    if (int rc = hpx_ud_grade_enqueue(nullptr, nside_in, nside_out, nmaps, nest_in, nest_out, pess, ratio, dtype_in, dtype_out, di, dout)) return rc;
+    return c.finish();
 }
 
 int bfgx_hpx_interp_weights_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t n, const double *theta_dev,
                                    const double *phi_dev, const int64_t *ipix_dev, int64_t *pix_dev, double *w_dev)
 {
-    if (!pix_dev || !w_dev || (ipix_dev ? (theta_dev || phi_dev) : (!theta_dev || !phi_dev)))
-        return fail(BFGX_ERR_INVALID, "NULL argument (give theta and phi, or ipix alone)");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = hpx_interp_weights_check(nside, nest, n, theta_dev, phi_dev, ipix_dev, pix_dev, w_dev)) return rc;
+    if (int rc = select_device(device)) return rc;
     if (n == 0) return BFGX_OK;
     hipLaunchKernelGGL(hpx::hpx_interp_weights_kernel, dim3(hpx_blocks(n)), dim3(hpx::kThreads), 0, (hipStream_t)hip_stream,
                        hpx_interp_args(nside, nest, n), theta_dev, phi_dev, ipix_dev, pix_dev, w_dev);
@@ -142,38 +190,24 @@ int bfgx_hpx_interp_weights_device(int device, void *hip_stream, int64_t nside, 
 int bfgx_hpx_interp_weights(int device, int64_t nside, int32_t nest, int64_t n, const double *theta, const double *phi, const int64_t *ipix,
                             int64_t *pix_out, double *w_out)
 {
-    if (!pix_out || !w_out || (ipix ? (theta || phi) : (!theta || !phi)))
-        return fail(BFGX_ERR_INVALID, "NULL argument (give theta and phi, or ipix alone)");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (ipix) {
-        const int64_t npix = 12 * nside * nside;
-        for (int64_t i = 0; i < n; ++i)
-            if (ipix[i] < 0 || ipix[i] >= npix) return fail(BFGX_ERR_INVALID, "ipix[%lld] = %lld is outside [0, %lld)", (long long)i, (long long)ipix[i], (long long)npix);
-    } else if (int rc = hpx_check_angles(n, theta, phi)) {
-        return rc;
-    }
-    if (int rc = tables_begin(device)) return rc;
-    if (n == 0) return BFGX_OK;
-    DevBuf dt, dp, di, dpix, dw;
-    if ((ipix ? di.up(ipix, sizeof(int64_t) * n) : (dt.up(theta, sizeof(double) * n) || dp.up(phi, sizeof(double) * n))) ||
-        dpix.up(nullptr, sizeof(int64_t) * 4 * n) || dw.up(nullptr, sizeof(double) * 4 * n))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_hpx_interp_weights_device(device, nullptr, nside, nest, n, dt.as<double>(), dp.as<double>(), di.as<int64_t>(),
-                                                dpix.as<int64_t>(), dw.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(pix_out, dpix.p, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(w_out, dw.p, sizeof(double) * 4 * n, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    if (int rc = hpx_interp_weights_check(nside, nest, n, theta, phi, ipix, pix_out, w_out)) return rc;
+    if (int rc = ipix ? hpx_check_pixels(n, ipix, 12 * nside * nside) : hpx_check_angles(n, theta, phi)) return rc;
+    HostCall c(device);
+    if (c.rc || n == 0) return c.rc;
+    const double *dt = ipix ? nullptr : c.in(theta, n), *dp = ipix ? nullptr : c.in(phi, n);
+    const int64_t *di = ipix ? c.in(ipix, n) : nullptr;
+    int64_t *dpix = c.out(pix_out, 4 * n);
+    double *dw = c.out(w_out, 4 * n);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_hpx_interp_weights_device(device, nullptr, nside, nest, n, dt, dp, di, dpix, dw)) return rc;
+    return c.finish();
 }
 
 int bfgx_hpx_interp_val_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t nmaps, int32_t dtype, const void *maps_dev,
                                int64_t n, const double *theta_dev, const double *phi_dev, double *out_dev)
 {
-    if (!maps_dev || !theta_dev || !phi_dev || !out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (nmaps < 1) return fail(BFGX_ERR_INVALID, "nmaps must be >= 1 (got %lld)", (long long)nmaps);
-    if (int rc = hpx_check_dtype(dtype, "dtype")) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = hpx_interp_val_check(nside, nest, nmaps, dtype, maps_dev, n, theta_dev, phi_dev, out_dev)) return rc;
+    if (int rc = select_device(device)) return rc;
     if (n == 0) return BFGX_OK;
     const hpx::Interp a = hpx_interp_args(nside, nest, n);
     hipStream_t s = (hipStream_t)hip_stream;
@@ -190,29 +224,22 @@ int bfgx_hpx_interp_val_device(int device, void *hip_stream, int64_t nside, int3
 int bfgx_hpx_interp_val(int device, int64_t nside, int32_t nest, int64_t nmaps, int32_t dtype, const void *maps, int64_t n, const double *theta,
                         const double *phi, double *out)
 {
-    if (!maps || !theta || !phi || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (nmaps < 1) return fail(BFGX_ERR_INVALID, "nmaps must be >= 1 (got %lld)", (long long)nmaps);
-    if (int rc = hpx_check_dtype(dtype, "dtype")) return rc;
+    if (int rc = hpx_interp_val_check(nside, nest, nmaps, dtype, maps, n, theta, phi, out)) return rc;
     if (int rc = hpx_check_angles(n, theta, phi)) return rc;
-    if (int rc = tables_begin(device)) return rc;
-    if (n == 0) return BFGX_OK;
-    DevBuf dm, dt, dp, dout;
-    if (dm.up(maps, hpx_dsize(dtype) * (size_t)nmaps * 12 * nside * nside) || dt.up(theta, sizeof(double) * n) || dp.up(phi, sizeof(double) * n) ||
-        dout.up(nullptr, sizeof(double) * nmaps * n))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_hpx_interp_val_device(device, nullptr, nside, nest, nmaps, dtype, dm.p, n, dt.as<double>(), dp.as<double>(), dout.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * nmaps * n, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    HostCall c(device);
+    if (c.rc || n == 0) return c.rc;
+    const char *dm = c.in((const char *)maps, hpx_dsize(dtype) * (size_t)nmaps * 12 * nside * nside);      // (either dtype: in bytes)
+    const double *dt = c.in(theta, n), *dp = c.in(phi, n);
+    double *dout = c.out(out, nmaps * n);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_hpx_interp_val_device(device, nullptr, nside, nest, nmaps, dtype, dm, n, dt, dp, dout)) return rc;
+    return c.finish();
 }
 
 int bfgx_hpx_neighbours_device(int device, void *hip_stream, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix_dev, int64_t *out_dev)
 {
-    if (!ipix_dev || !out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (n > (INT64_MAX >> 4)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = hpx_neighbours_check(nside, nest, n, ipix_dev, out_dev)) return rc;
+    if (int rc = select_device(device)) return rc;
     if (n == 0) return BFGX_OK;
     hipLaunchKernelGGL(hpx::hpx_neighbours_kernel, dim3(hpx_blocks(n)), dim3(hpx::kThreads), 0, (hipStream_t)hip_stream, nside,
                        hpx::nbr_order(nside), nest ? 1 : 0, n, ipix_dev, out_dev);
@@ -222,28 +249,22 @@ int bfgx_hpx_neighbours_device(int device, void *hip_stream, int64_t nside, int3
 
 int bfgx_hpx_neighbours(int device, int64_t nside, int32_t nest, int64_t n, const int64_t *ipix, int64_t *out)
 {
-    if (!ipix || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = hpx_interp_check(nside, nest, n)) return rc;
-    if (n > (INT64_MAX >> 4)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
-    const int64_t npix = 12 * nside * nside;
-    for (int64_t i = 0; i < n; ++i)
-        if (ipix[i] < 0 || ipix[i] >= npix) return fail(BFGX_ERR_INVALID, "ipix[%lld] = %lld is outside [0, %lld)", (long long)i, (long long)ipix[i], (long long)npix);
-    if (int rc = tables_begin(device)) return rc;
-    if (n == 0) return BFGX_OK;
-    DevBuf di, dout;
-    if (di.up(ipix, sizeof(int64_t) * n) || dout.up(nullptr, sizeof(int64_t) * 8 * n)) return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_hpx_neighbours_device(device, nullptr, nside, nest, n, di.as<int64_t>(), dout.as<int64_t>())) return rc;
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(int64_t) * 8 * n, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    if (int rc = hpx_neighbours_check(nside, nest, n, ipix, out)) return rc;
+    if (int rc = hpx_check_pixels(n, ipix, 12 * nside * nside)) return rc;
+    HostCall c(device);
+    if (c.rc || n == 0) return c.rc;
+    const int64_t *di = c.in(ipix, n);
+    int64_t *dout = c.out(out, 8 * n);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_hpx_neighbours_device(device, nullptr, nside, nest, n, di, dout)) return rc;
+    return c.finish();
 }
 
 int bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, double *hmap_dev, int64_t n, const double *vals_dev,
                                 const int64_t *pix_dev, const double *w_dev)
 {
-    if (!hmap_dev || !vals_dev || !pix_dev || !w_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (npix < 1 || n < 0) return fail(BFGX_ERR_INVALID, "npix must be >= 1 and n >= 0 (got npix %lld, n %lld)", (long long)npix, (long long)n);
-    if (n > (INT64_MAX >> 3)) return fail(BFGX_ERR_INVALID, "n is too large (%lld)", (long long)n);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = hpx_scatter_add_check(npix, n, hmap_dev, vals_dev, pix_dev, w_dev)) return rc;
+    if (int rc = select_device(device)) return rc;
     if (n == 0) return BFGX_OK;
     hipLaunchKernelGGL(hpx::hpx_scatter_add_kernel, dim3(hpx_blocks(4 * n)), dim3(hpx::kThreads), 0, (hipStream_t)hip_stream, npix, hmap_dev, n,
                        vals_dev, pix_dev, w_dev);
@@ -253,22 +274,17 @@ int bfgx_hpx_scatter_add_device(int device, void *hip_stream, int64_t npix, doub
 
 int bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap, int64_t n, const double *vals, const int64_t *pix, const double *w)
 {
-    if (!hmap || !vals || !pix || !w) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (npix < 1 || n < 0) return fail(BFGX_ERR_INVALID, "npix must be >= 1 and n >= 0 (got npix %lld, n %lld)", (long long)npix, (long long)n);
-    for (int64_t e = 0; e < 4 * n; ++e)
-        if (pix[e] < -npix || pix[e] >= npix)
-            return fail(BFGX_ERR_INVALID, "index %lld (entry %lld) is outside [-%lld, %lld)", (long long)pix[e], (long long)e, (long long)npix,
-                        (long long)npix);
-    if (int rc = tables_begin(device)) return rc;
-    if (n == 0) return BFGX_OK;
-    DevBuf dh, dv, dp, dw;
-    if (dh.up(hmap, sizeof(double) * npix) || dv.up(vals, sizeof(double) * n) || dp.up(pix, sizeof(int64_t) * 4 * n) ||
-        dw.up(w, sizeof(double) * 4 * n))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_hpx_scatter_add_device(device, nullptr, npix, dh.as<double>(), n, dv.as<double>(), dp.as<int64_t>(), dw.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(hmap, dh.p, sizeof(double) * npix, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    if (int rc = hpx_scatter_add_check(npix, n, hmap, vals, pix, w)) return rc;
+    if (int rc = hpx_check_scatter_indices(n, pix, npix)) return rc;
+    HostCall c(device);
+    if (c.rc || n == 0) return c.rc;
+    double *dh = c.inout(hmap, npix);
+    const double *dv = c.in(vals, n);
+    const int64_t *dp = c.in(pix, 4 * n);
+    const double *dw = c.in(w, 4 * n);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_hpx_scatter_add_device(device, nullptr, npix, dh, n, dv, dp, dw)) return rc;
+    return c.finish();
 }
 
 }  // extern "C"

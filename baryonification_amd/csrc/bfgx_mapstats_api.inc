@@ -33,7 +33,7 @@ int bfgx_mapstats_moments_device(int device, void *hip_stream, int64_t npix, int
     if (npix < 1 || npix > 12 * kHpxMaxNside * kHpxMaxNside) return fail(BFGX_ERR_INVALID, "npix must be in [1, %lld] (got %lld)", (long long)(12 * kHpxMaxNside * kHpxMaxNside), (long long)npix);
     if (nmaps < 1 || nmaps > mapstats::kMaxMaps) return fail(BFGX_ERR_INVALID, "nmaps must be in [1, %d] (got %d)", mapstats::kMaxMaps, nmaps);
     if (order < 2 || order > mapstats::kMaxOrder) return fail(BFGX_ERR_INVALID, "order must be in [2, %d] (got %d)", mapstats::kMaxOrder, order);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     const int nt = mapstats::moment_terms(nmaps, order);
     if (nmaps == 1) mapstats_moments_launch<1>(s, npix, nt, maps_dev, mask_dev, n_dev, out_dev, work_dev);
@@ -49,7 +49,7 @@ int bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int3
     if (!map_dev || !edges_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (int rc = hpx_check_nside(nside, nest != 0, "nside")) return rc;
     if (nb < 1 || nb > mapstats::kMaxBins) return fail(BFGX_ERR_INVALID, "nb must be in [1, %d] (got %d)", mapstats::kMaxBins, nb);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     mapstats::Peaks a;
     a.nside = nside; a.npix = 12 * nside * nside;
@@ -73,7 +73,7 @@ int bfgx_mapstats_minkowski_device(int device, void *hip_stream, int64_t npix, c
     if (!ders_dev || !edges_dev || !counts_dev || !sums_dev || !work_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (npix < 1 || npix > 12 * kHpxMaxNside * kHpxMaxNside) return fail(BFGX_ERR_INVALID, "npix must be in [1, %lld] (got %lld)", (long long)(12 * kHpxMaxNside * kHpxMaxNside), (long long)npix);
     if (nb < 1 || nb > mapstats::kMaxMfBins) return fail(BFGX_ERR_INVALID, "nb must be in [1, %d] (got %d)", mapstats::kMaxMfBins, nb);
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     const int nblocks = mapstats::moment_blocks(npix);
     HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * (nb + 3), s));

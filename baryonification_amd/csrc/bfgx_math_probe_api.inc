@@ -6,16 +6,12 @@ extern "C" int bfgx_math_probe(int device, int32_t fn, int64_t n, const double *
     if (!a || !out0 || (probe_two_args(fn) && !b) || (probe_two_results(fn) && !out1)) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (n < 0 || n > kProbeMaxN) return fail(BFGX_ERR_INVALID, "math probe: n must be in [0, %lld]", (long long)kProbeMaxN);
     if (n == 0) return BFGX_OK;
-    if (int rc = tables_begin(device)) return rc;
-    const size_t bytes = sizeof(double) * (size_t)n;
-    DevBuf da, db, d0, d1;
-    if (da.up(a, bytes) || db.up(probe_two_args(fn) ? b : nullptr, bytes) || d0.up(fn == kProbeMulAddNc ? out0 : nullptr, bytes) ||
-        d1.up(nullptr, bytes))
-        return fail(BFGX_ERR_HIP, "device allocation/copy failed");
+    HostCall c(device);
+    const double *da = c.in(a, n), *db = c.in(probe_two_args(fn) ? b : nullptr, n);
+    double *d0 = fn == kProbeMulAddNc ? c.inout(out0, n) : c.out(out0, n);            // mul_add_nc reads its third argument from out0
+    double *d1 = c.out(probe_two_results(fn) ? out1 : nullptr, n);
+    if (int rc = c.ready()) return rc;
     hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + kProbeThreads - 1) / kProbeThreads)), dim3(kProbeThreads), 0, 0, fn, n,
-                       da.as<double>(), db.as<double>(), d0.as<double>(), d1.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out0, d0.p, bytes, hipMemcpyDeviceToHost));
-    if (probe_two_results(fn)) HIP_TRY(hipMemcpy(out1, d1.p, bytes, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+                       da, db, d0, d1);
+    return c.finish();
 }

@@ -74,12 +74,55 @@ ShtPtrs sht_ptrs(const ShtLayout &L, double *work)
     return p;
 }
 
-int sht_begin(int device, int32_t nside, int32_t lmax, int32_t mmax, const void *work)
+// a work array of the caller's, on the device
+int sht_work_check(const void *work, const char *name)
 {
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
     if (!work) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(work) & 15) return fail(BFGX_ERR_INVALID, "work_dev must be 16-byte aligned (complex values)");
-    return tables_begin(device);
+    if (reinterpret_cast<uintptr_t>(work) & 15) return fail(BFGX_ERR_INVALID, "%s must be 16-byte aligned (complex values)", name);
+    return BFGX_OK;
+}
+
+// The prologue of the _device entries, after their argument checks.  First half (all that bfgx_sht_prepare_device needs): the work array,
+// the device, the layout ...
+int sht_begin(int device, int32_t nside, int32_t lmax, int32_t mmax, const void *work, ShtLayout &L)
+{
+    if (int rc = sht_work_check(work, "work_dev")) return rc;
+    if (int rc = select_device(device)) return rc;
+    L = sht_layout(nside, lmax, mmax);
+    return BFGX_OK;
+}
+
+// ... and for a transform also the LDS limit of the ring kernels and the pointers into the work array
+int sht_begin(int device, int32_t nside, int32_t lmax, int32_t mmax, double *work, ShtLayout &L, ShtPtrs &p)
+{
+    if (int rc = sht_begin(device, nside, lmax, mmax, work, L)) return rc;
+    if (int rc = sht_set_lds(L)) return rc;
+    p = sht_ptrs(L, work);
+    return BFGX_OK;
+}
+
+// the argument checks of each operation, shared by its host entry and its _device entry
+// (map2alm, anafast and, with iter = 0, alm2map: `in` and `out` are the map and the alm, either way round)
+int sht_transform_check(int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const void *in, const void *out)
+{
+    if (!in || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (iter < 0) return fail(BFGX_ERR_INVALID, "iter must be >= 0 (got %d)", iter);
+    return sht_check(nside, lmax, mmax);
+}
+
+int sht_alm2cl_check(int32_t lmax, int32_t mmax, int32_t lmax_out, const void *alm1, const void *cl)
+{
+    if (!alm1 || !cl) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (lmax < 0 || mmax < 0 || mmax > lmax || lmax_out < 0) return fail(BFGX_ERR_INVALID, "alm2cl needs 0 <= mmax <= lmax, lmax_out >= 0");
+    return BFGX_OK;
+}
+
+int sht_almxfl_check(int32_t lmax, int32_t mmax, int64_t nfl, const void *fl, const void *in, const void *out)
+{
+    if (!fl || !in || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (lmax < 0 || lmax > 32767 || mmax < 0 || mmax > lmax) return fail(BFGX_ERR_INVALID, "almxfl needs 0 <= mmax <= lmax <= 32767 (got mmax %d, lmax %d)", mmax, lmax);
+    if (nfl < 0) return fail(BFGX_ERR_INVALID, "nfl must be >= 0 (got %lld)", (long long)nfl);
+    return BFGX_OK;
 }
 
 // alm = A(map) (accumulate: alm += A(map))
@@ -128,21 +171,14 @@ int64_t sht_alm_size(int lmax, int mmax) { return (int64_t)(mmax + 1) * (2 * (in
 // spin transforms: a second F buffer (F of map1), [mmax + 1][4 nside - 1] complex, outside the spin-0 work array
 int64_t sht_spin_work(const ShtLayout &L) { return 2 * (int64_t)(L.mmax + 1) * L.nrings; }
 
-int sht_spin_check(int32_t lmax, int32_t spin)
+// (both spin transforms: `in` and `out` are the maps and the alms, either way round)
+int sht_spin_check(int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const void *in, const void *out)
 {
+    if (!in || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = sht_check(nside, lmax, mmax)) return rc;
     if (spin < 1) return fail(BFGX_ERR_INVALID, "spin must be >= 1 (got %d; spin 0 is bfgx_sht_map2alm / bfgx_sht_alm2map)", spin);
     if (spin > lmax) return fail(BFGX_ERR_INVALID, "spin must be <= lmax (got spin %d, lmax %d)", spin, lmax);
     return BFGX_OK;
-}
-
-int sht_spin_begin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const void *in, const void *out, const void *work,
-                   const void *spin_work)
-{
-    if (!in || !out || !spin_work) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(spin_work) & 15) return fail(BFGX_ERR_INVALID, "spin_work_dev must be 16-byte aligned (complex values)");
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = sht_spin_check(lmax, spin)) return rc;
-    return sht_begin(device, nside, lmax, mmax, work);
 }
 
 // [G | C] = A_s(map0, map1): maps = map0 | map1 (npix each), alms = G | C (alm size each)
@@ -184,8 +220,9 @@ int64_t bfgx_sht_work_doubles(int32_t nside, int32_t lmax, int32_t mmax)
 
 int bfgx_sht_prepare_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, double *work_dev)
 {
-    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev)) return rc;
-    const ShtLayout L = sht_layout(nside, lmax, mmax);
+    if (int rc = sht_check(nside, lmax, mmax)) return rc;
+    ShtLayout L;
+    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev, L)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     // twiddles e^{-2 pi i j / M}, j < M/2, of every power of two M <= Mmax
     std::vector<double> tw(L.o_btab - L.o_tw, 0.0);
@@ -244,47 +281,35 @@ int bfgx_sht_prepare_device(int device, void *hip_stream, int32_t nside, int32_t
 int bfgx_sht_map2alm_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map_dev,
                             double *alm_dev, double *work_dev)
 {
-    if (!map_dev || !alm_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (iter < 0) return fail(BFGX_ERR_INVALID, "iter must be >= 0 (got %d)", iter);
-    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev)) return rc;
-    const ShtLayout L = sht_layout(nside, lmax, mmax);
-    if (int rc = sht_set_lds(L)) return rc;
-    return sht_map2alm(L, sht_ptrs(L, work_dev), (hipStream_t)hip_stream, map_dev, reinterpret_cast<double2 *>(alm_dev), iter);
+    if (int rc = sht_transform_check(nside, lmax, mmax, iter, map_dev, alm_dev)) return rc;
+    ShtLayout L; ShtPtrs p;
+    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev, L, p)) return rc;
+    return sht_map2alm(L, p, (hipStream_t)hip_stream, map_dev, reinterpret_cast<double2 *>(alm_dev), iter);
 }
 
 int bfgx_sht_alm2map_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, const double *alm_dev, double *map_dev,
                             double *work_dev)
 {
-    if (!map_dev || !alm_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev)) return rc;
-    const ShtLayout L = sht_layout(nside, lmax, mmax);
-    if (int rc = sht_set_lds(L)) return rc;
-    return sht_synthesis(L, sht_ptrs(L, work_dev), (hipStream_t)hip_stream, reinterpret_cast<const double2 *>(alm_dev), map_dev);
+    if (int rc = sht_transform_check(nside, lmax, mmax, 0, alm_dev, map_dev)) return rc;
+    ShtLayout L; ShtPtrs p;
+    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev, L, p)) return rc;
+    return sht_synthesis(L, p, (hipStream_t)hip_stream, reinterpret_cast<const double2 *>(alm_dev), map_dev);
 }
 
 int bfgx_sht_alm2cl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int32_t lmax_out, const double *alm1_dev,
                            const double *alm2_dev, double *cl_dev)
 {
-    if (!alm1_dev || !cl_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (lmax < 0 || mmax < 0 || mmax > lmax || lmax_out < 0) return fail(BFGX_ERR_INVALID, "alm2cl needs 0 <= mmax <= lmax, lmax_out >= 0");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_alm2cl_check(lmax, mmax, lmax_out, alm1_dev, cl_dev)) return rc;
+    if (int rc = select_device(device)) return rc;
     const double2 *a = reinterpret_cast<const double2 *>(alm1_dev), *b = alm2_dev ? reinterpret_cast<const double2 *>(alm2_dev) : a;
     return sht_alm2cl((hipStream_t)hip_stream, lmax, mmax, lmax_out, a, b, cl_dev);
-}
-
-int sht_almxfl_check(int32_t lmax, int32_t mmax, int64_t nfl, const void *fl, const void *in, const void *out)
-{
-    if (!fl || !in || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (lmax < 0 || lmax > 32767 || mmax < 0 || mmax > lmax) return fail(BFGX_ERR_INVALID, "almxfl needs 0 <= mmax <= lmax <= 32767 (got mmax %d, lmax %d)", mmax, lmax);
-    if (nfl < 0) return fail(BFGX_ERR_INVALID, "nfl must be >= 0 (got %lld)", (long long)nfl);
-    return BFGX_OK;
 }
 
 int bfgx_sht_almxfl_device(int device, void *hip_stream, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl_dev, const double *alm_in_dev,
                            double *alm_out_dev)
 {
     if (int rc = sht_almxfl_check(lmax, mmax, nfl, fl_dev, alm_in_dev, alm_out_dev)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     hipLaunchKernelGGL(sht::sht_almxfl_kernel, dim3((unsigned)(lmax / 256 + 1), (unsigned)(mmax + 1)), dim3(256), 0, (hipStream_t)hip_stream,
                        reinterpret_cast<const double2 *>(alm_in_dev), reinterpret_cast<double2 *>(alm_out_dev), lmax,
                        (int)std::min<int64_t>(nfl, (int64_t)lmax + 1), fl_dev);
@@ -292,94 +317,80 @@ int bfgx_sht_almxfl_device(int device, void *hip_stream, int32_t lmax, int32_t m
     return BFGX_OK;
 }
 
-// one-shot host entries: numpy in, numpy out (PCIe included); alm are complex128 in healpy order
+// host entries: numpy in, numpy out (PCIe included); alm are complex128 in healpy order, counted here in doubles
 int bfgx_sht_almxfl(int device, int32_t lmax, int32_t mmax, int64_t nfl, const double *fl, const double *alm_in, double *alm_out)
 {
     if (int rc = sht_almxfl_check(lmax, mmax, nfl, fl, alm_in, alm_out)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    HostCall c(device);
     const int64_t na = sht_alm_size(lmax, mmax), nf = std::min<int64_t>(nfl, (int64_t)lmax + 1);
-    DevBuf df, da;
-    if (df.up(nf ? fl : nullptr, sizeof(double) * std::max<int64_t>(nf, 1)) || da.up(alm_in, sizeof(double2) * na))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_almxfl_device(device, nullptr, lmax, mmax, nf, df.as<double>(), da.as<double>(), da.as<double>())) return rc;
-    HIP_TRY(hipMemcpy(alm_out, da.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    const double *df = c.in(fl, nf);
+    double *da = c.inout(alm_in, alm_out, 2 * na);                                   // multiplied in place on the device
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_almxfl_device(device, nullptr, lmax, mmax, nf, df, da, da)) return rc;
+    return c.finish();
 }
 
 int bfgx_sht_map2alm(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map, double *alm)
 {
-    if (!map || !alm) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (iter < 0) return fail(BFGX_ERR_INVALID, "iter must be >= 0 (got %d)", iter);
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_transform_check(nside, lmax, mmax, iter, map, alm)) return rc;
+    HostCall c(device);
     const ShtLayout L = sht_layout(nside, lmax, mmax);
-    const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf dw, dm, da;
-    if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(map, sizeof(double) * L.npix) || da.up(nullptr, sizeof(double2) * na))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
-    if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm.as<double>(), da.as<double>(), dw.as<double>())) return rc;
-    HIP_TRY(hipMemcpy(alm, da.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    double *dw = c.scratch<double>(L.total);
+    const double *dm = c.in(map, L.npix);
+    double *da = c.out(alm, 2 * sht_alm_size(lmax, mmax));
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw)) return rc;
+    if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm, da, dw)) return rc;
+    return c.finish();
 }
 
 int bfgx_sht_alm2map(int device, int32_t nside, int32_t lmax, int32_t mmax, const double *alm, double *map)
 {
-    if (!map || !alm) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_transform_check(nside, lmax, mmax, 0, alm, map)) return rc;
+    HostCall c(device);
     const ShtLayout L = sht_layout(nside, lmax, mmax);
-    const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf dw, dm, da;
-    if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(nullptr, sizeof(double) * L.npix) || da.up(alm, sizeof(double2) * na))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
-    if (int rc = bfgx_sht_alm2map_device(device, nullptr, nside, lmax, mmax, da.as<double>(), dm.as<double>(), dw.as<double>())) return rc;
-    HIP_TRY(hipMemcpy(map, dm.p, sizeof(double) * L.npix, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    double *dw = c.scratch<double>(L.total), *dm = c.out(map, L.npix);
+    const double *da = c.in(alm, 2 * sht_alm_size(lmax, mmax));
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw)) return rc;
+    if (int rc = bfgx_sht_alm2map_device(device, nullptr, nside, lmax, mmax, da, dm, dw)) return rc;
+    return c.finish();
 }
 
 int bfgx_sht_alm2cl(int device, int32_t lmax, int32_t mmax, int32_t lmax_out, const double *alm1, const double *alm2, double *cl)
 {
-    if (!alm1 || !cl) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (lmax < 0 || mmax < 0 || mmax > lmax || lmax_out < 0) return fail(BFGX_ERR_INVALID, "alm2cl needs 0 <= mmax <= lmax, lmax_out >= 0");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_alm2cl_check(lmax, mmax, lmax_out, alm1, cl)) return rc;
+    HostCall c(device);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf d1, d2, dc;
-    if (d1.up(alm1, sizeof(double2) * na) || (alm2 && d2.up(alm2, sizeof(double2) * na)) || dc.up(nullptr, sizeof(double) * (lmax_out + 1)))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_alm2cl_device(device, nullptr, lmax, mmax, lmax_out, d1.as<double>(), alm2 ? d2.as<double>() : nullptr, dc.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(cl, dc.p, sizeof(double) * (lmax_out + 1), hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    const double *d1 = c.in(alm1, 2 * na), *d2 = alm2 ? c.in(alm2, 2 * na) : nullptr;
+    double *dc = c.out(cl, lmax_out + 1);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_alm2cl_device(device, nullptr, lmax, mmax, lmax_out, d1, d2, dc)) return rc;
+    return c.finish();
 }
 
 // anafast: map2alm of one or two maps, alm2cl on the device; only cl (and the alm when alm1_out / alm2_out are given) come back
 int bfgx_sht_anafast(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t iter, const double *map1, const double *map2,
                      double *cl, double *alm1_out, double *alm2_out)
 {
-    if (!map1 || !cl) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (iter < 0) return fail(BFGX_ERR_INVALID, "iter must be >= 0 (got %d)", iter);
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_transform_check(nside, lmax, mmax, iter, map1, cl)) return rc;
+    HostCall c(device);
     const ShtLayout L = sht_layout(nside, lmax, mmax);
     const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf dw, dm, da1, da2, dc;
-    if (dw.up(nullptr, sizeof(double) * L.total) || dm.up(map1, sizeof(double) * L.npix) || da1.up(nullptr, sizeof(double2) * na) ||
-        (map2 && da2.up(nullptr, sizeof(double2) * na)) || dc.up(nullptr, sizeof(double) * (lmax + 1)))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
-    if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm.as<double>(), da1.as<double>(), dw.as<double>())) return rc;
+    double *dw = c.scratch<double>(L.total);
+    double *dm = const_cast<double *>(c.in(map1, L.npix));                           // (filled a second time below)
+    double *da1 = c.out(alm1_out, 2 * na), *da2 = map2 ? c.out(alm2_out, 2 * na) : nullptr, *dc = c.out(cl, lmax + 1);
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw)) return rc;
+    if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm, da1, dw)) return rc;
     if (map2) {
-        HIP_TRY(hipMemcpy(dm.p, map2, sizeof(double) * L.npix, hipMemcpyHostToDevice));
-        if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm.as<double>(), da2.as<double>(), dw.as<double>())) return rc;
+        // the one copy the scaffold does not make: map2 takes the place of map1 in the same buffer once the first transform has been queued
+        // (the blocking copy waits for it)
+        HIP_TRY(hipMemcpy(dm, map2, sizeof(double) * L.npix, hipMemcpyHostToDevice));
+        if (int rc = bfgx_sht_map2alm_device(device, nullptr, nside, lmax, mmax, iter, dm, da2, dw)) return rc;
     }
-    if (int rc = bfgx_sht_alm2cl_device(device, nullptr, lmax, mmax, lmax, da1.as<double>(), map2 ? da2.as<double>() : nullptr, dc.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(cl, dc.p, sizeof(double) * (lmax + 1), hipMemcpyDeviceToHost));
-    if (alm1_out) HIP_TRY(hipMemcpy(alm1_out, da1.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
-    if (alm2_out && map2) HIP_TRY(hipMemcpy(alm2_out, da2.p, sizeof(double2) * na, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    if (int rc = bfgx_sht_alm2cl_device(device, nullptr, lmax, mmax, lmax, da1, da2, dc)) return rc;
+    return c.finish();
 }
 
 
@@ -393,61 +404,50 @@ int64_t bfgx_sht_spin_work_doubles(int32_t nside, int32_t lmax, int32_t mmax)
 int bfgx_sht_map2alm_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps_dev,
                                  double *alms_dev, double *work_dev, double *spin_work_dev)
 {
-    if (int rc = sht_spin_begin(device, nside, lmax, mmax, spin, maps_dev, alms_dev, work_dev, spin_work_dev)) return rc;
-    const ShtLayout L = sht_layout(nside, lmax, mmax);
-    if (int rc = sht_set_lds(L)) return rc;
-    return sht_spin_analysis(L, sht_ptrs(L, work_dev), reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin, maps_dev,
+    if (int rc = sht_work_check(spin_work_dev, "spin_work_dev")) return rc;
+    if (int rc = sht_spin_check(nside, lmax, mmax, spin, maps_dev, alms_dev)) return rc;
+    ShtLayout L; ShtPtrs p;
+    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev, L, p)) return rc;
+    return sht_spin_analysis(L, p, reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin, maps_dev,
                              reinterpret_cast<double2 *>(alms_dev));
 }
 
 int bfgx_sht_alm2map_spin_device(int device, void *hip_stream, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms_dev,
                                  double *maps_dev, double *work_dev, double *spin_work_dev)
 {
-    if (int rc = sht_spin_begin(device, nside, lmax, mmax, spin, alms_dev, maps_dev, work_dev, spin_work_dev)) return rc;
-    const ShtLayout L = sht_layout(nside, lmax, mmax);
-    if (int rc = sht_set_lds(L)) return rc;
-    return sht_spin_synthesis(L, sht_ptrs(L, work_dev), reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin,
+    if (int rc = sht_work_check(spin_work_dev, "spin_work_dev")) return rc;
+    if (int rc = sht_spin_check(nside, lmax, mmax, spin, alms_dev, maps_dev)) return rc;
+    ShtLayout L; ShtPtrs p;
+    if (int rc = sht_begin(device, nside, lmax, mmax, work_dev, L, p)) return rc;
+    return sht_spin_synthesis(L, p, reinterpret_cast<double2 *>(spin_work_dev), (hipStream_t)hip_stream, spin,
                               reinterpret_cast<const double2 *>(alms_dev), maps_dev);
 }
 
 int bfgx_sht_map2alm_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *maps, double *alms)
 {
-    if (!maps || !alms) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = sht_spin_check(lmax, spin)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_spin_check(nside, lmax, mmax, spin, maps, alms)) return rc;
+    HostCall c(device);
     const ShtLayout L = sht_layout(nside, lmax, mmax);
-    const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf dw, ds, dm, da;
-    if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(maps, sizeof(double) * 2 * L.npix) ||
-        da.up(nullptr, sizeof(double2) * 2 * na))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
-    if (int rc = bfgx_sht_map2alm_spin_device(device, nullptr, nside, lmax, mmax, spin, dm.as<double>(), da.as<double>(), dw.as<double>(),
-                                              ds.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(alms, da.p, sizeof(double2) * 2 * na, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    double *dw = c.scratch<double>(L.total), *ds = c.scratch<double>(sht_spin_work(L));
+    const double *dm = c.in(maps, 2 * L.npix);
+    double *da = c.out(alms, 4 * sht_alm_size(lmax, mmax));
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw)) return rc;
+    if (int rc = bfgx_sht_map2alm_spin_device(device, nullptr, nside, lmax, mmax, spin, dm, da, dw, ds)) return rc;
+    return c.finish();
 }
 
 int bfgx_sht_alm2map_spin(int device, int32_t nside, int32_t lmax, int32_t mmax, int32_t spin, const double *alms, double *maps)
 {
-    if (!maps || !alms) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = sht_check(nside, lmax, mmax)) return rc;
-    if (int rc = sht_spin_check(lmax, spin)) return rc;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = sht_spin_check(nside, lmax, mmax, spin, alms, maps)) return rc;
+    HostCall c(device);
     const ShtLayout L = sht_layout(nside, lmax, mmax);
-    const int64_t na = sht_alm_size(lmax, mmax);
-    DevBuf dw, ds, dm, da;
-    if (dw.up(nullptr, sizeof(double) * L.total) || ds.up(nullptr, sizeof(double) * sht_spin_work(L)) || dm.up(nullptr, sizeof(double) * 2 * L.npix) ||
-        da.up(alms, sizeof(double2) * 2 * na))
-        return fail(BFGX_ERR_HIP, "hipMalloc / copy failed");
-    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw.as<double>())) return rc;
-    if (int rc = bfgx_sht_alm2map_spin_device(device, nullptr, nside, lmax, mmax, spin, da.as<double>(), dm.as<double>(), dw.as<double>(),
-                                              ds.as<double>()))
-        return rc;
-    HIP_TRY(hipMemcpy(maps, dm.p, sizeof(double) * 2 * L.npix, hipMemcpyDeviceToHost));
-    return BFGX_OK;
+    double *dw = c.scratch<double>(L.total), *ds = c.scratch<double>(sht_spin_work(L)), *dm = c.out(maps, 2 * L.npix);
+    const double *da = c.in(alms, 4 * sht_alm_size(lmax, mmax));
+    if (int rc = c.ready()) return rc;
+    if (int rc = bfgx_sht_prepare_device(device, nullptr, nside, lmax, mmax, dw)) return rc;
+    if (int rc = bfgx_sht_alm2map_spin_device(device, nullptr, nside, lmax, mmax, spin, da, dm, dw, ds)) return rc;
+    return c.finish();
 }
 
 }  // extern "C"

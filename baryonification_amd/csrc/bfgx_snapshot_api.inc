@@ -42,7 +42,7 @@ int bfgx_snapshot_plan_create(int device, void *hip_stream, const bfgx_model *mo
     if (int rc = validate_model(model)) return rc;
     if (model->table.ndim != 3) return fail(BFGX_ERR_UNSUPPORTED, "BaryonifySnapshot passes no halo properties to the model (SnapshotRunner.py:240): 3-axis tables only");
     if (model->table.log_values) return fail(BFGX_ERR_INVALID, "BaryonifySnapshot needs a displacement table");
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     bfgx_snapshot_plan *p = new bfgx_snapshot_plan();
     p->device = device; p->stream = (hipStream_t)hip_stream; p->max_halos = max_halos;
     auto bail = [&](int rc) { bfgx_snapshot_plan_destroy(p); return rc; };
@@ -218,7 +218,7 @@ int bfgx_baryonify_snapshot(const bfgx_grid_catalog *halos, const bfgx_model *mo
     if (snap->ndim != 2 && snap->ndim != 3) return fail(BFGX_ERR_INVALID, "snapshot ndim must be 2 or 3");
     if (snap->n < 0) return fail(BFGX_ERR_INVALID, "negative particle count");
     const int device = opts ? opts->device : 0;
-    if (int rc = tables_begin(device)) return rc;
+    if (int rc = select_device(device)) return rc;
     GridHostCatalog hc;
     Timer t;
     t.start(nullptr);
