@@ -34,6 +34,9 @@ def acc_mode(acc_f64):
     return ACC_F64 if bool(acc_f64) else ACC_F32
 
 c_double_p = C.POINTER(C.c_double)
+# one record of a plan's ring table (csrc/bfgx_kernels.hpp RingRec, include/bfgx.h bfgx_debug_ring_table): 80 bytes
+RING_REC = np.dtype({'names': ['theta', 'z', 'sth', 'dphi', 'inv_dphi', 'inv_dth_up', 'inv_dth_dn', 'start', 'nr', 'shifted'],
+                     'formats': ['<f8'] * 7 + ['<i8', '<i4', '<i4'], 'offsets': [0, 8, 16, 24, 32, 40, 48, 56, 64, 68], 'itemsize': 80})
 
 
 class bfgx_cosmo(C.Structure):
@@ -109,6 +112,7 @@ SYMBOLS = {
     'bfgx_debug_catalog_uploads': (C.c_longlong, []),
     'bfgx_debug_grid_pipe_fallbacks': (C.c_longlong, []),
     'bfgx_debug_host_spans': (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    'bfgx_debug_ring_table': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     'bfgx_host_alloc': (C.c_int, [C.c_size_t, _P(C.c_void_p)]),
     'bfgx_host_free': (None, [C.c_void_p]),
     'bfgx_plan_create': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, _P(bfgx_model), _P(C.c_void_p)]),

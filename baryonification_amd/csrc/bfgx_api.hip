@@ -686,6 +686,14 @@ static int plan_init_binning(bfgx_plan *p, const bfgx_table &t, size_t nh)
         std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return weight[x] > weight[y]; });
     }
     if (int rc = owned_upload(p->mem, p->stream, order, T.tile_order)) return rc;
+    {   // the ring table: geometry of every ring, derived once per plan (NSIDE never changes) instead of per tile and step by K1 and K2
+        RingRec *rings = nullptr;
+        const size_t nrec = (size_t)(4 * p->nside + 1);
+        if (p->mem.alloc(rings, nrec)) return alloc_fail("ring table");
+        hipLaunchKernelGGL(ring_table_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, p->stream, p->hpx, rings);
+        if (hipGetLastError() != hipSuccess) return fail(BFGX_ERR_HIP, "ring table launch failed");
+        T.rings = rings;
+    }
     if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "stream sync failed");
     p->capacity = 8 * p->max_halos + 4096;
     if (const char *e = std::getenv("BFGX_K1_FLUID")) p->k1_fluid = std::max(0, std::min(2, std::atoi(e)));
@@ -1871,6 +1879,28 @@ void bfgx_debug_host_spans(long long *pinned_in_place, long long *staged, long l
 }
 
 long long bfgx_debug_alloc_count(void) { return (long long)g_dev_allocs.load(); }
+
+int bfgx_debug_ring_table(bfgx_plan *p, int from_functions, int64_t first, int64_t count, void *out)
+{
+    if (!p || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
+    const int64_t nl4 = 4 * p->hpx.nside;
+    // (the functions are defined for rings 1 .. 4 nside - 1; the table also holds the two "no such ring" records)
+    const int64_t lo = from_functions ? 1 : 0, hi = from_functions ? nl4 - 1 : nl4;
+    if (count < 0 || first < lo || first + count - 1 > hi) return fail(BFGX_ERR_INVALID, "ring table: rings [%lld, %lld] only", (long long)lo, (long long)hi);
+    if (count == 0) return BFGX_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    const RingRec *src = p->tiling.rings + first;
+    DevBuf tmp;
+    if (from_functions) {
+        if (tmp.alloc(sizeof(RingRec) * (size_t)count)) return alloc_fail("ring records");
+        hipLaunchKernelGGL(ring_functions_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, p->stream, p->hpx, (int)first, (int)count, tmp.as<RingRec>());
+        HIP_TRY(hipGetLastError());
+        src = tmp.as<RingRec>();
+    }
+    HIP_TRY(hipMemcpyAsync(out, src, sizeof(RingRec) * (size_t)count, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return BFGX_OK;
+}
 
 int bfgx_host_alloc(size_t bytes, void **out)
 {

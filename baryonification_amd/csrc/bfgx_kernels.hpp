@@ -428,6 +428,7 @@ struct Tiling {
     const int32_t *band_nrmin;            // [nbands] shortest ring of the band
     const int32_t *tile_band;             // [ntiles]
     const int32_t *tile_order;            // [ntiles] launch order of the scatter kernel: largest tiles (in pixels) first
+    const struct RingRec *rings;          // [4 nside + 1] the plan's ring table (below, beside RegRow): geometry of every ring, filled once at plan creation
 };
 
 // first ring-local pixel of azimuth slice j: ceil(j nr / nphi); j nr < 2^31 for nside <= 8192
@@ -1976,6 +1977,61 @@ __device__ inline double ring_theta_nolibm(const Hpx &h, int ring)
     double z, sth;
     ring_z_sth(h, ring, z, sth);
     return atan2_generic(sth, z);
+}
+
+// The plan's ring table (Tiling.rings): what depends on NSIDE alone of ring 0 .. 4 nside, computed ONCE at plan creation by ring_table_kernel
+// with the very functions above, so that every field holds the bits a tile kernel would derive itself.  K1 (TileRow / RingC2, the flush's first
+// pixels) and K2 (RegRow / RegRowC / RowScan, the rings beyond a tile's window) read a record instead of re-deriving it per tile and step.
+// Rings 0 and 4 nside are the "no such ring" records of the regrid window: theta = -1e300 / +1e300, everything else 0 (nr == 0).
+struct alignas(16) RingRec {
+    double theta, z, sth;                 // colatitude, cos, sin
+    double dphi, inv_dphi;                // 2 pi / nr and nr / (2 pi)
+    double inv_dth_up, inv_dth_dn;        // 1 / (theta_r - theta_{r-1}), 1 / (theta_{r+1} - theta_r); 0 where there is no such neighbour
+    int64_t start;                        // first pixel of the ring
+    int32_t nr, shifted;                  // ring length (0: no such ring), half-pixel shift flag
+};
+static_assert(sizeof(RingRec) == 80, "RingRec: five 16-byte loads");
+
+__global__ void __launch_bounds__(256)
+ring_table_kernel(Hpx h, RingRec *__restrict__ rings)
+{
+    const int nl4 = (int)(4 * h.nside);
+    const int ring = blockIdx.x * 256 + threadIdx.x;
+    if (ring > nl4) return;
+    RingRec g;
+    g.theta = (ring < 1) ? -1.0e300 : 1.0e300;
+    g.z = g.sth = g.dphi = g.inv_dphi = g.inv_dth_up = g.inv_dth_dn = 0.0;
+    g.start = 0; g.nr = 0; g.shifted = 0;
+    if (ring >= 1 && ring <= nl4 - 1) {
+        int64_t st, nr64; bool shf;
+        ring_info_small(h, ring, st, nr64, shf);
+        ring_z_sth(h, ring, g.z, g.sth);
+        g.theta = atan2_generic(g.sth, g.z);
+        g.start = st; g.nr = (int)nr64; g.shifted = shf ? 1 : 0;
+        g.dphi = kTwoPi / (double)g.nr;
+        g.inv_dphi = (double)g.nr * kInvTwoPi;
+        if (ring > 1) g.inv_dth_up = 1.0 / (g.theta - ring_theta_nolibm(h, ring - 1));
+        if (ring < nl4 - 1) g.inv_dth_dn = 1.0 / (ring_theta_nolibm(h, ring + 1) - g.theta);
+    }
+    rings[ring] = g;
+}
+
+// tests (bfgx_debug_ring_table): what ring_info_small, ring_z_sth and ring_theta_nolibm give for n rings, each called on its own; the
+// quotients (dphi, inv_dphi, the spacings) are left 0 -- the caller forms them in IEEE arithmetic
+__global__ void __launch_bounds__(256)
+ring_functions_kernel(Hpx h, int first, int n, RingRec *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int ring = first + i;
+    RingRec g;
+    g.dphi = g.inv_dphi = g.inv_dth_up = g.inv_dth_dn = 0.0;
+    int64_t nr64; bool shf;
+    ring_info_small(h, ring, g.start, nr64, shf);
+    g.nr = (int)nr64; g.shifted = shf ? 1 : 0;
+    ring_z_sth(h, ring, g.z, g.sth);
+    g.theta = ring_theta_nolibm(h, ring);
+    out[i] = g;
 }
 
 // sums[0] = sum of tile_sums[2 t], sums[1] = sum of tile_sums[2 t + 1]   (one workgroup)

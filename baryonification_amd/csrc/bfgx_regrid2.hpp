@@ -48,7 +48,7 @@ __device__ inline double row_inv_dphi(const RegRow *rows, const RegRowC<double> 
 __host__ __device__ inline size_t regrowc_bytes(size_t real_size) { return real_size == 4 ? sizeof(RegRowC<float>) : sizeof(RegRowC<double>); }
 
 // the 4 targets of one displaced pixel by the generic route: get_interpol (healpix_cxx) on (theta, phi) of v + o, fp64
-__device__ inline void regrid_targets_generic(const Hpx &h, const RegRow *rows, int LR, int rth0, int ti, int x,
+__device__ inline void regrid_targets_generic(const Hpx &h, const RingRec *__restrict__ rings, const RegRow *rows, int LR, int rth0, int ti, int x,
                                                     double o0, double o1, double o2, int tr[4], int tk[4], double w[4])
 {
     const int nl4 = (int)(4 * h.nside);
@@ -92,9 +92,8 @@ __device__ inline void regrid_targets_generic(const Hpx &h, const RegRow *rows, 
                 const RegRow &r2 = rows[t2];
                 n2 = r2.nr; shd = r2.shf ? 0.5 : 0.0; invd = r2.inv_dphi; th = r2.theta;
             } else {
-                n2 = ring_len(h, ir);
-                const bool sh2 = (ir < h.nside) || (ir >= 3 * h.nside) || (((ir - (int)h.nside) & 1) == 0);
-                shd = sh2 ? 0.5 : 0.0; invd = (double)n2 * kInvTwoPi; th = ring_theta_nolibm(h, ir);
+                const RingRec &g2 = rings[ir];                          // a ring beyond the window: from the plan's ring table
+                n2 = g2.nr; shd = g2.shifted ? 0.5 : 0.0; invd = g2.inv_dphi; th = g2.theta;
             }
             const double tmp = ph * invd - shd;
             int j1 = (int)floor(tmp);
@@ -489,12 +488,12 @@ __device__ inline bool regrid_gather_targets(const RegRow *rows, const RegRowC<r
 // one source pixel by the generic route, its four deposits appended to the far list; returns the sum of the deposits.  (Out of line it costs
 // the walking kernel 23 spilled registers around the call and 3 % of its time, the lean kernel 20 %: inlined.)
 __device__ inline double regrid_far_pixel(
-    const Hpx &h, const RegRow *rows, int LR, int rth0, int ti, int x, double o0, double o1, double o2,
+    const Hpx &h, const RingRec *__restrict__ rings, const RegRow *rows, int LR, int rth0, int ti, int x, double o0, double o1, double o2,
                                                 double val, FarList far)
 {
     int tr[4], tk[4];
     double w[4], tot = 0.0;
-    regrid_targets_generic(h, rows, LR, rth0, ti, x, o0, o1, o2, tr, tk, w);
+    regrid_targets_generic(h, rings, rows, LR, rth0, ti, x, o0, o1, o2, tr, tk, w);
     // ONE returning atomic per wave reserves the four entries of every active lane (one per deposit would be tens of millions of atomics on
     // a single address where the field moves far: they serialise at ~5 ns each)
     const unsigned long long act = __ballot(1);
@@ -504,11 +503,9 @@ __device__ inline double regrid_far_pixel(
     if (rank == 0) base = atomicAdd(far.count, 4ull * (unsigned long long)__popcll(act));
     base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), leader, kWave) << 32) | (unsigned)__shfl((int)base, leader, kWave);
     for (int q4 = 0; q4 < 4; ++q4) {
-        int64_t st_t, nr64; bool sh_t;
-        ring_info_small(h, tr[q4], st_t, nr64, sh_t);
         const double v = w[q4] * val;
         const unsigned long long i = base + 4ull * (unsigned long long)rank + (unsigned long long)q4;
-        if ((int64_t)i < far.cap) { far.pix[i] = st_t + tk[q4]; far.val[i] = v; } else atomicOr(far.overflow, 1);
+        if ((int64_t)i < far.cap) { far.pix[i] = rings[tr[q4]].start + tk[q4]; far.val[i] = v; } else atomicOr(far.overflow, 1);
         tot += v;
     }
     return tot;
@@ -588,9 +585,8 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
         // so its pixels deposit into themselves -- a copy, with the reference's rule that only positive pixels are regridded
         const int lane = tid & (kWave - 1), wid = tid / kWave;
         for (int rr = wid; rr < i1 - i0; rr += 256 / kWave) {
-            int64_t st; int64_t nr64; bool shf_;
-            ring_info_small(h, i0 + rr, st, nr64, shf_);
-            const int ks = tile_ks(tj, (int)nr64, nphi), ke = tile_ks(tj + 1, (int)nr64, nphi);
+            const int64_t st = T.rings[i0 + rr].start;
+            const int nr = T.rings[i0 + rr].nr, ks = tile_ks(tj, nr, nphi), ke = tile_ks(tj + 1, nr, nphi);
             for (int k = ks + lane; k < ke; k += kWave) {
                 const double v = map_in[st + k];
                 const double dep = (v > 0.0) ? v : 0.0;                       // HealpixRunner.py:335
@@ -615,41 +611,31 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
     const int NT = T.BR + 2 * R + 2;                           // rings rth0 .. rth0 + NT - 1 in the ring tables
     const int rth0 = i0 - R - 1;
     if (tid < NT) {
+        // one record of the plan's ring table (everything that depends on NSIDE alone, the spacings to the neighbouring rings included: no
+        // second phase over the neighbours' theta); per tile only the column span, the azimuth of its first pixel and the thresholds
         const int ring = rth0 + tid;
+        const RingRec g = T.rings[min(max(ring, 0), nl4)];
         RegRow rw;
-        rw.theta = (ring < 1) ? -1.0e300 : 1.0e300;
-        rw.z = rw.sth = rw.dphi = rw.inv_dphi = rw.c0 = rw.s0 = 0.0;
-        rw.start = 0; rw.nr = 0; rw.ks = 0; rw.ke = 0; rw.shf = 0; rw.lim2 = 0.0;
-        if (ring >= 1 && ring <= nl4 - 1) {
-            int64_t st, nr64; bool shf_;
-            ring_info_small(h, ring, st, nr64, shf_);
-            ring_z_sth(h, ring, rw.z, rw.sth);
-            rw.theta = atan2_generic(rw.sth, rw.z);
-            rw.start = st; rw.nr = (int)nr64; rw.shf = shf_ ? 1 : 0;
-            rw.dphi = kTwoPi / (double)rw.nr;
-            rw.inv_dphi = (double)rw.nr * kInvTwoPi;
+        rw.theta = g.theta; rw.z = g.z; rw.sth = g.sth; rw.dphi = g.dphi; rw.inv_dphi = g.inv_dphi;
+        rw.c0 = rw.s0 = 0.0;
+        rw.start = g.start; rw.nr = g.nr; rw.ks = 0; rw.ke = 0; rw.shf = g.shifted; rw.lim2 = 0.0;
+        if (g.nr > 0) {
             rw.ks = tile_ks(tj, rw.nr, nphi);
             rw.ke = tile_ks(tj + 1, rw.nr, nphi);
-            sincos_bounded(((double)rw.ks + (shf_ ? 0.5 : 0.0)) * rw.dphi, rw.s0, rw.c0);
+            sincos_bounded(((double)rw.ks + (g.shifted ? 0.5 : 0.0)) * rw.dphi, rw.s0, rw.c0);
             // gathered <=> |o|^2 < lim2
             const double lim = fmin(fmin(reach.cap, 0.09 * rw.sth), 0.999 * fmin(rw.theta - reach.theta_first, reach.theta_last - rw.theta));
             rw.lim2 = (lim > 0.0 && ring > 1 && ring < nl4 - 1) ? (double)(float)(lim * lim) : 0.0;      // (a float: the walking kernel's scan compares in fp32)
         }
         rows[tid] = rw;
-    }
-    __syncthreads();
-    if (tid < NT) {
-        const RegRow &rw = rows[tid];
         RegRowC<real> rc;
         if constexpr (sizeof(real) == 4) {
             rc.z = (real)rw.z; rc.sth = (real)rw.sth; rc.dphi = (real)rw.dphi; rc.inv_dphi = (real)rw.inv_dphi;
             rc.c0 = (real)rw.c0; rc.s0 = (real)rw.s0;
         }
-        rc.inv_dth_up = (real)0; rc.inv_dth_dn = (real)0;
-        if (rw.nr > 0) {
-            if (tid > 0 && rows[tid - 1].nr > 0) rc.inv_dth_up = (real)(1.0 / (rw.theta - rows[tid - 1].theta));
-            if (tid < NT - 1 && rows[tid + 1].nr > 0) rc.inv_dth_dn = (real)(1.0 / (rows[tid + 1].theta - rw.theta));
-        }
+        // (the window's first / last row has no neighbour IN the window: no spacing, as before)
+        rc.inv_dth_up = (tid > 0) ? (real)g.inv_dth_up : (real)0;
+        rc.inv_dth_dn = (tid < NT - 1) ? (real)g.inv_dth_dn : (real)0;
         rowc[tid] = rc;
         if (PASS == 2) {
             // thresholds of the scan (below): a pixel of this ring reaches the tile only if it moves (a) beyond the ring next to the
@@ -658,9 +644,10 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             // |o| is at most |o| / (sth - lim) nr / 2 pi columns (the arithmetic of tile_apron_kernel, per pixel instead of per tile)
             RowScan *scan = reinterpret_cast<RowScan *>(rowc + NTmax);
             const int T0 = R + 1, T1 = R + (i1 - i0);                          // first / last own ring of the tile in the ring tables
+            const RingRec &gup = T.rings[i0 - 1], &gdn = T.rings[i1];          // the rings next to the tile's first / last own ring (rows T0 - 1, T1 + 1)
             double need = 0.0;
-            if (tid < T0 - 1 && rows[T0 - 1].nr > 0) need = rows[T0 - 1].theta - rw.theta;
-            else if (tid > T1 + 1 && rows[T1 + 1].nr > 0) need = rw.theta - rows[T1 + 1].theta;
+            if (tid < T0 - 1 && gup.nr > 0) need = gup.theta - rw.theta;
+            else if (tid > T1 + 1 && gdn.nr > 0) need = rw.theta - gdn.theta;
             const float nf = (rw.nr > 0 && need > 0.0) ? (float)(0.999 * need) : 0.0f;
             const double den = rw.sth - fast_sqrt(rw.lim2);
             const float cf = (rw.nr > 0 && den > 0.0) ? (float)(1.02 * rw.inv_dphi / den) : 3.0e18f;
@@ -778,7 +765,7 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             const int64_t p = rw.start + k;
             double f0 = (double)offsets[3 * p + 0], f1 = (double)offsets[3 * p + 1], f2 = (double)offsets[3 * p + 2];
             if (SPLIT) { f0 += (double)offsets_lo[3 * p + 0]; f1 += (double)offsets_lo[3 * p + 1]; f2 += (double)offsets_lo[3 * p + 2]; }
-            sum_out += regrid_far_pixel(h, rows, NT - 2, rth0, ti, x, f0, f1, f2, map_in[p], far);
+            sum_out += regrid_far_pixel(h, T.rings, rows, NT - 2, rth0, ti, x, f0, f1, f2, map_in[p], far);
         };
         int32_t *fq = farq + wid * kWalkQ;
         int fn = 0;                                                            // entries in this wave's queue of generic-route pixels
@@ -886,12 +873,8 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
         } else if (cur.own) {                                                // rare: the owner of the source pixel lists its deposits
             int tr[4], tk[4];
             double w[4];
-            regrid_targets_generic(h, rows, NT - 2, rth0, cur.ti, cur.x, (double)cur.o0, (double)cur.o1, (double)cur.o2, tr, tk, w);
-            for (int q4 = 0; q4 < 4; ++q4) {
-                int64_t st_t, nr64; bool sh_t;
-                ring_info_small(h, tr[q4], st_t, nr64, sh_t);
-                far_add(st_t + tk[q4], w[q4] * val);
-            }
+            regrid_targets_generic(h, T.rings, rows, NT - 2, rth0, cur.ti, cur.x, (double)cur.o0, (double)cur.o1, (double)cur.o2, tr, tk, w);
+            for (int q4 = 0; q4 < 4; ++q4) far_add(T.rings[tr[q4]].start + tk[q4], w[q4] * val);
         }
     };
     // two window pixels per lane and trip: the four loads are in flight before either pixel is evaluated

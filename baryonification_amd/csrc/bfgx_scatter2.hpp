@@ -726,6 +726,36 @@ __device__ __forceinline__ void k1_chunk(const KK &kk, const Tab8T<real> &tb, co
     if (__builtin_expect(__any((en.fb & 2) != 0), 0)) rows_and_pairs(std::true_type{}); else rows_and_pairs(std::false_type{});
 }
 
+// Geometry of one ring for a tile's TileRow, and the ring's first pixel for the flush.  FROM_TABLE: read from the plan's ring table (T.rings:
+// the same functions, evaluated once per plan) -- the kernels with fp32 pair math, where it is worth 3.5 us of K1's 0.39 ms at config 2; the
+// kernels with fp64 pair math keep deriving it (with the table their K1 measured 3 us SLOWER, parity-grade and fp64 alike, four runs of each
+// build alternating; the values are the same bits either way).
+template <typename real> struct K1RingTable { static constexpr bool value = sizeof(real) == 4; };
+template <bool FROM_TABLE>
+__device__ inline void k1_ring_geometry(const Hpx &h, const Tiling &T, int ring, TileRow &tr)
+{
+    if constexpr (FROM_TABLE) {
+        const RingRec g = T.rings[ring];
+        tr.z = g.z; tr.sth = g.sth; tr.dphi = g.dphi; tr.fnr = g.inv_dphi;
+        tr.nr = g.nr; tr.shifted = g.shifted;
+    } else {
+        int64_t st, n64; bool shf;
+        ring_info_small(h, ring, st, n64, shf);
+        ring_z_sth(h, ring, tr.z, tr.sth);
+        tr.nr = (int)n64; tr.shifted = shf ? 1 : 0;
+        tr.dphi = kTwoPi / (double)tr.nr;
+        tr.fnr = (double)n64 * kInvTwoPi;
+    }
+}
+template <bool FROM_TABLE>
+__device__ inline int64_t k1_ring_start(const Hpx &h, const Tiling &T, int ring)
+{
+    if constexpr (FROM_TABLE) return T.rings[ring].start;      // (wave-uniform: a scalar load instead of the 64-bit multiply chain)
+    int64_t st, n64; bool shf;
+    ring_info_small(h, ring, st, n64, shf);
+    return st;
+}
+
 // ---------------------------------------------------------------------------------- the kernel
 template <int MODE, typename ACC, typename real, int NP, int PM = 0>
 __global__ void __launch_bounds__(kWave * kW2, (sizeof(real) == 4 ? 4 : 2))
@@ -783,14 +813,8 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
         for (int i = tid; i < NCOMP * PL; i += kWave * kW2) acc[i] = 0.0;
     if (tid == 0) *next_chunk = 0;
     if (tid < T.BR && i0 + tid < i1) {
-        const int ring = i0 + tid;
-        int64_t st, n64; bool shf;
         TileRow tr;
-        ring_info_small(h, ring, st, n64, shf);
-        ring_z_sth(h, ring, tr.z, tr.sth);
-        tr.nr = (int)n64; tr.shifted = shf ? 1 : 0;
-        tr.dphi = kTwoPi / (double)tr.nr;
-        tr.fnr = (double)n64 * kInvTwoPi;
+        k1_ring_geometry<K1RingTable<real>::value>(h, T, i0 + tid, tr);
         tr.ks = tile_ks(tj, tr.nr, nphi); tr.ke = tile_ks(tj + 1, tr.nr, nphi);
         rowtab[tid] = tr;
         RingC2<real> rg;
@@ -836,9 +860,7 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
     // ---- flush: every pixel of the tile is stored exactly once (plain, row-contiguous stores of [pixel][component])
     float om2 = 0.0f;
     for (int rr = wid; rr < i1 - i0; rr += kW2) {
-        const int ring = i0 + rr;
-        int64_t st, n64; bool shf;
-        ring_info_small(h, ring, st, n64, shf);
+        const int64_t st = k1_ring_start<K1RingTable<real>::value>(h, T, i0 + rr);
         const TileRow &tr = rowtab[rr];
         const int n = (tr.ke - tr.ks) * NCOMP;
         ACC *dst = out + NCOMP * (st + tr.ks);
@@ -1002,14 +1024,8 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             TileRow *rowtab = rowtab_all + (size_t)(2 * s + par) * T.BR;
             RingC2<real> *ringc = ringc_all + (size_t)(2 * s + par) * T.BR;
             if (lane < T.BR && i0 + lane < i1) {
-                const int ring = i0 + lane;
-                int64_t st, n64; bool shf;
                 TileRow tr;
-                ring_info_small(h, ring, st, n64, shf);
-                ring_z_sth(h, ring, tr.z, tr.sth);
-                tr.nr = (int)n64; tr.shifted = shf ? 1 : 0;
-                tr.dphi = kTwoPi / (double)tr.nr;
-                tr.fnr = (double)n64 * kInvTwoPi;
+                k1_ring_geometry<K1RingTable<real>::value>(h, T, i0 + lane, tr);
                 tr.ks = tile_ks(d.tj, tr.nr, d.nphi); tr.ke = tile_ks(d.tj + 1, tr.nr, d.nphi);
                 rowtab[lane] = tr;
                 RingC2<real> rg;
@@ -1090,8 +1106,7 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int rr = min(4 * g + q, nrow - 1);
-                int64_t st, n64; bool shf;
-                ring_info_small(h, i0 + rr, st, n64, shf);
+                const int64_t st = k1_ring_start<K1RingTable<real>::value>(h, T, i0 + rr);
                 const TileRow &tr = rowtab[rr];
                 const int ks = tr.ks, npx = tr.ke - tr.ks;
                 double *src = acc + (rr << wsh);

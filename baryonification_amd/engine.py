@@ -204,6 +204,15 @@ class ShellPlan(object):
         _lib.check(_lib.load().bfgx_plan_regrid_stats(self._h, C.byref(far), C.byref(ovf), C.byref(walked), C.byref(reach)))
         return {"far_listed": int(far.value), "far_overflowed": bool(ovf.value), "tiles_walked": int(walked.value), "max_reach_rings": int(reach.value)}
 
+    def ring_table(self, first=0, count=None, from_functions=False):
+        """records [first, first + count) of the plan's ring table (bfgx_debug_ring_table; blocking) as a structured array; from_functions:
+        the same rings evaluated afresh by the device functions the table was built from, the quotients (dphi .. inv_dth_dn) left 0"""
+        if count is None:
+            count = 4 * self.nside + 1 - first
+        out = np.zeros(int(count), dtype=_lib.RING_REC)
+        _lib.check(_lib.load().bfgx_debug_ring_table(self._h, int(bool(from_functions)), int(first), int(count), out.ctypes.data))
+        return out
+
     def timing_enable(self, on=True):
         _lib.check(_lib.load().bfgx_plan_timing_enable(self._h, int(on)))
 

@@ -198,6 +198,11 @@ void bfgx_debug_host_spans(long long *pinned_in_place, long long *staged, long l
 /* streamed bfgx_baryonify_grid calls so far that found a cell moving further along the first array axis than their plane ranges allow (2^S - 1 cells:
  * 7 in 3-D, 15 in 2-D) and repeated the regrid in one pass on the uploaded map (tests) */
 long long bfgx_debug_grid_pipe_fallbacks(void);
+/* the plan's ring table (tests): `count` records of 80 bytes from ring `first` on, copied to `out` -- { double theta, z, sin_theta, dphi, inv_dphi,
+ * inv_dtheta_up, inv_dtheta_down; int64 start; int32 nr, shifted }, one per ring 0 .. 4 nside, rings 0 and 4 nside being the "no such ring"
+ * records (nr = 0, theta = -1e300 / +1e300).  from_functions != 0: the same records for rings within 1 .. 4 nside - 1 evaluated afresh by the
+ * device functions the table was built from, the four quotients (dphi .. inv_dtheta_down) left 0.  Waits for the plan's stream. */
+int       bfgx_debug_ring_table(bfgx_plan *plan, int from_functions, int64_t first, int64_t count, void *out);
 int       bfgx_host_alloc(size_t bytes, void **out);
 void      bfgx_host_free(void *p);
 
