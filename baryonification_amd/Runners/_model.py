@@ -184,6 +184,33 @@ def _placeholder_model(runner, cosmo_dict):
     return m, keep
 
 
+class _Pairs(object):
+    """One handle of the per-halo entries bfgx_<family>_pairs_* (family: 'shell', 'grid' or 'snapshot') as a context manager: begin on entry
+    (begin_args: what the family's begin takes before the handle and the counts), end on exit, whatever happened in between.  `off` is the
+    exclusive prefix sum of the n halos' pair counts; p(step, ...) calls bfgx_<family>_pairs_<step>(handle, ...) and checks its status."""
+
+    def __init__(self, family, n, *begin_args):
+        self.family, self.n, self.begin_args = family, n, begin_args
+        self.lib = _lib.load()
+
+    def _entry(self, step):
+        return getattr(self.lib, 'bfgx_%s_pairs_%s' % (self.family, step))
+
+    def __enter__(self):
+        import ctypes as C
+        self.h = C.c_void_p()
+        counts = np.zeros(max(self.n, 1), dtype=np.int64)
+        _lib.check(self._entry('begin')(*self.begin_args, C.byref(self.h), counts.ctypes.data))
+        self.off = np.concatenate([[0], np.cumsum(counts[:self.n])]).astype(np.int64)
+        return self
+
+    def __exit__(self, *exc):
+        self._entry('end')(self.h)
+
+    def __call__(self, step, *args):
+        _lib.check(self._entry(step)(self.h, *args))
+
+
 def process_callable_exact(runner, kind, orig_map=None):
     """BaryonifyShell / PaintProfilesShell .process() for a model that is a plain Python callable, evaluated exactly as the reference does:
     once per halo, on the separations r_sep / a_j of that halo's own pixels (HealpixRunner.py:314-331, :436-445).  The device finds the discs
@@ -199,14 +226,10 @@ def process_callable_exact(runner, kind, orig_map=None):
     cols = [_lib.f8(cat[k]) for k in ('M', 'z', 'ra', 'dec')]
     c, ckeep = _lib.make_catalog_host(cols[0], cols[1], cols[2], cols[3], [])
     nside = int(runner.LightconeShell.NSIDE)
-    lib = _lib.load()
-    h = C.c_void_p()
-    counts = np.zeros(max(cat.size, 1), dtype=np.int64)
-    _lib.check(lib.bfgx_shell_pairs_begin(C.byref(c), C.byref(m), nside, int(paint), int(runner.device), C.byref(h), counts.ctypes.data))
-    try:
-        off = np.concatenate([[0], np.cumsum(counts[:cat.size])]).astype(np.int64)
+    with _Pairs('shell', cat.size, C.byref(c), C.byref(m), nside, int(paint), int(runner.device)) as p:
+        off = p.off
         r = np.empty(max(int(off[-1]), 1))
-        _lib.check(lib.bfgx_shell_pairs_radii(h, r.ctypes.data))
+        p('radii', r.ctypes.data)
         vals = np.zeros_like(r)
         cosmo = getattr(model, 'cosmo', None) or runner.cosmo
         cosmo_obj = cosmo if isinstance(cosmo, Cosmology) else Cosmology.from_dict(cosmo_to_dict(cosmo))
@@ -223,9 +246,7 @@ def process_callable_exact(runner, kind, orig_map=None):
         new_map = _lib.pinned_empty(npix)
         stats = _lib.bfgx_stats()
         src = None if paint else _lib.f8(orig_map)
-        _lib.check(lib.bfgx_shell_pairs_apply(h, vals.ctypes.data, None if paint else src.ctypes.data, new_map.ctypes.data, 1, C.byref(stats)))
-    finally:
-        lib.bfgx_shell_pairs_end(h)
+        p('apply', vals.ctypes.data, None if paint else src.ctypes.data, new_map.ctypes.data, 1, C.byref(stats))
     runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
     del keep, ckeep
     return new_map
@@ -241,6 +262,28 @@ def _halo_batches(off, budget):
         j1 = max(int(np.searchsorted(off, off[j0] + budget, side='right')) - 1, j0 + 1)
         yield j0, min(j1, n)
         j0 = min(j1, n)
+
+
+def _apply_in_batches(p, fn, cosmo_obj, Mcol, a_j, skip_empty):
+    """The batch loop of the grid and snapshot routes on the handle p: for each range of halos of at most EXACT_BATCH_PAIRS pairs, fetch the
+    radii, call the model for halo j on its slice -- fn(r_j, Mcol[j], a_j), or fn(cosmo_obj, r_j, Mcol[j], a_j) where a cosmology is
+    given; r_j is float64, and empty for a halo without pairs, which skip_empty leaves out altogether -- broadcast its answer over the
+    slice and apply the batch."""
+    off = p.off
+    for j0, j1 in _halo_batches(off, int(EXACT_BATCH_PAIRS)):
+        base, npairs = int(off[j0]), int(off[j1] - off[j0])
+        r = np.empty(max(npairs, 1))
+        p('radii', j0, j1, r.ctypes.data)
+        vals = np.empty_like(r)
+        for j in range(j0, j1):
+            lo, hi = int(off[j]) - base, int(off[j + 1]) - base
+            if hi == lo and skip_empty:
+                continue
+            v = fn(r[lo:hi], Mcol[j], a_j) if cosmo_obj is None else fn(cosmo_obj, r[lo:hi], Mcol[j], a_j)
+            if hi > lo:
+                vals[lo:hi] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (hi - lo,))
+        p('apply', j0, j1, vals.ctypes.data)
+        del r, vals
 
 
 def process_grid_exact(runner, kind, rmat=None):
@@ -260,39 +303,19 @@ def process_grid_exact(runner, kind, rmat=None):
     G = runner.GriddedMap
     c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if G.is2D else hcat['z'], None, rmat)
     grid, gkeep = runner._grid()
-    lib = _lib.load()
-    h = C.c_void_p()
-    n = hcat.size
-    counts = np.zeros(max(n, 1), dtype=np.int64)
-    _lib.check(lib.bfgx_grid_pairs_begin(C.byref(c), C.byref(m), C.byref(grid), int(paint), int(runner.device), C.byref(h), counts.ctypes.data))
-    try:
-        off = np.concatenate([[0], np.cumsum(counts[:n])]).astype(np.int64)
+    with _Pairs('grid', hcat.size, C.byref(c), C.byref(m), C.byref(grid), int(paint), int(runner.device)) as p:
         Mcol = hcat['M']
         a_j = 1 / (1 + runner.HaloNDCatalog.redshift)                                   # :485, :717
-        if paint:
+        if paint:                               # PaintProfilesGrid calls every halo; one with an invalid mass or position has no pixels
             profile = model.projected if G.is2D else model.real                        # :752, :781
             cosmo_obj = Cosmology.from_dict(cosmo_dict)
-        for j0, j1 in _halo_batches(off, int(EXACT_BATCH_PAIRS)):
-            base, npairs = int(off[j0]), int(off[j1] - off[j0])
-            r = np.empty(max(npairs, 1))
-            _lib.check(lib.bfgx_grid_pairs_radii(h, j0, j1, r.ctypes.data))
-            vals = np.empty_like(r)
-            for j in range(j0, j1):
-                lo, hi = int(off[j]) - base, int(off[j + 1]) - base
-                if hi == lo and not paint:                                              # Nsize < 2: skipped (:498)
-                    continue
-                rj = r[lo:hi]
-                v = profile(cosmo_obj, rj, Mcol[j], a_j) if paint else model.displacement(rj, Mcol[j], a_j)
-                if hi > lo:                         # (PaintProfilesGrid calls every halo; one with an invalid mass or position has no pixels)
-                    vals[lo:hi] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (hi - lo,))
-            _lib.check(lib.bfgx_grid_pairs_apply(h, j0, j1, vals.ctypes.data))
-            del r, vals
+            _apply_in_batches(p, profile, cosmo_obj, Mcol, a_j, False)
+        else:                                   # BaryonifyGrid skips a halo with Nsize < 2 (:498)
+            _apply_in_batches(p, model.displacement, None, Mcol, a_j, True)
         new_map = _lib.pinned_empty(int(np.prod(G.map.shape))).reshape(G.map.shape)
         src = None if paint else _lib.f8(G.map)
         stats = _lib.bfgx_stats()
-        _lib.check(lib.bfgx_grid_pairs_finish(h, None if paint else src.ctypes.data, new_map.ctypes.data, 1, C.byref(stats)))
-    finally:
-        lib.bfgx_grid_pairs_end(h)
+        p('finish', None if paint else src.ctypes.data, new_map.ctypes.data, 1, C.byref(stats))
     runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
     del keep, ckeep, gkeep
     return new_map
@@ -319,33 +342,14 @@ def process_snapshot_exact(runner):
     z = None if is2D else _lib.f8(snap.cat['z'])
     s = _lib.bfgx_snapshot(2 if is2D else 3, 0, x.size, x.ctypes.data, y.ctypes.data, None if is2D else z.ctypes.data,
                            float(snap.L), float(runner.HaloNDCatalog.redshift))
-    lib = _lib.load()
-    h = C.c_void_p()
-    n = hcat.size
-    counts = np.zeros(max(n, 1), dtype=np.int64)
-    _lib.check(lib.bfgx_snapshot_pairs_begin(C.byref(c), C.byref(m), C.byref(s), int(runner.device), C.byref(h), counts.ctypes.data))
-    try:
-        off = np.concatenate([[0], np.cumsum(counts[:n])]).astype(np.int64)
+    with _Pairs('snapshot', hcat.size, C.byref(c), C.byref(m), C.byref(s), int(runner.device)) as p:
         Mcol = hcat['M']
         a_j = 1 / (1 + runner.HaloNDCatalog.redshift)                                   # :219
-        for j0, j1 in _halo_batches(off, int(EXACT_BATCH_PAIRS)):
-            base, npairs = int(off[j0]), int(off[j1] - off[j0])
-            d = np.empty(max(npairs, 1))
-            _lib.check(lib.bfgx_snapshot_pairs_radii(h, j0, j1, d.ctypes.data))
-            vals = np.empty_like(d)
-            for j in range(j0, j1):
-                lo, hi = int(off[j]) - base, int(off[j + 1]) - base
-                v = model.displacement(d[lo:hi], Mcol[j], a_j)                          # :228, :245 (every halo)
-                if hi > lo:
-                    vals[lo:hi] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (hi - lo,))
-            _lib.check(lib.bfgx_snapshot_pairs_apply(h, j0, j1, vals.ctypes.data))
-            del d, vals
+        _apply_in_batches(p, model.displacement, None, Mcol, a_j, False)                # :228, :245 (every halo)
         ox, oy = np.empty_like(x), np.empty_like(y)
         oz = None if is2D else np.empty_like(z)
         stats = _lib.bfgx_stats()
-        _lib.check(lib.bfgx_snapshot_pairs_finish(h, ox.ctypes.data, oy.ctypes.data, None if is2D else oz.ctypes.data, C.byref(stats)))
-    finally:
-        lib.bfgx_snapshot_pairs_end(h)
+        p('finish', ox.ctypes.data, oy.ctypes.data, None if is2D else oz.ctypes.data, C.byref(stats))
     runner.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
     new_cat = snap.cat.copy()
     new_cat['x'], new_cat['y'] = ox, oy

@@ -109,6 +109,7 @@ SYMBOLS = {
                                          _P(bfgx_opts), _P(bfgx_stats)]),
     'bfgx_cache_clear': (None, []),
     'bfgx_debug_alloc_count': (C.c_longlong, []),
+    'bfgx_debug_live_allocs': (C.c_longlong, []),
     'bfgx_debug_catalog_uploads': (C.c_longlong, []),
     'bfgx_debug_grid_pipe_fallbacks': (C.c_longlong, []),
     'bfgx_debug_host_spans': (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),

@@ -1879,6 +1879,7 @@ void bfgx_debug_host_spans(long long *pinned_in_place, long long *staged, long l
 }
 
 long long bfgx_debug_alloc_count(void) { return (long long)g_dev_allocs.load(); }
+long long bfgx_debug_live_allocs(void) { return (long long)g_dev_live.load(); }
 
 int bfgx_debug_ring_table(bfgx_plan *p, int from_functions, int64_t first, int64_t count, void *out)
 {
@@ -2121,6 +2122,7 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 #include "bfgx_snapshot_api.inc"
 
 // ------------------------------------------------------------------------------ models that are Python callables
+#include "bfgx_pairs.hpp"
 #include "bfgx_callable_api.inc"
 #include "bfgx_grid_pairs_api.inc"
 #include "bfgx_snapshot_pairs_api.inc"

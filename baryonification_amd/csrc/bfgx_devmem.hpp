@@ -15,13 +15,21 @@ namespace bfgx {
 
 // every device allocation the library makes is counted (bfgx_debug_alloc_count): a warm one-shot call must make none
 inline std::atomic<long long> g_dev_allocs{0};
+// ... and those not yet freed (bfgx_debug_live_allocs): what a handle allocated, its `end` gives back
+inline std::atomic<long long> g_dev_live{0};
 
 // the message of a failed allocation: fail(BFGX_ERR_HIP, kDevAllocFailed, "catalog")
 constexpr const char *kDevAllocFailed = "hipMalloc(%s) failed";
 
 // (an empty request still gets a distinct, valid pointer)
-inline hipError_t dev_malloc(void **p, size_t bytes) { ++g_dev_allocs; return hipMalloc(p, bytes ? bytes : 8); }
-inline void dev_free(void *p) { if (p) (void)hipFree(p); }
+inline hipError_t dev_malloc(void **p, size_t bytes)
+{
+    ++g_dev_allocs;
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 8);
+    if (e == hipSuccess) ++g_dev_live;
+    return e;
+}
+inline void dev_free(void *p) { if (p) { --g_dev_live; (void)hipFree(p); } }
 
 struct DevBuf {
     void *p = nullptr;

@@ -1,5 +1,5 @@
 // bfgx_snapshot_stack_api.inc -- C ABI of the halo-centred profile measurement on particle snapshots (included at the end of bfgx_api.hip,
-// after bfgx_snapshot_pairs_api.inc whose particle binning it shares; declared in include/bfgx.h).
+// after bfgx_pairs.hpp whose particle binning it shares; declared in include/bfgx.h).
 //
 // MeasureProfilesSnapshot looks at the particles where baryonification is defined: the radial profile around the halos.  The ball, its
 // clipping and the separations are those of BaryonifySnapshot (snap_pairs_prep_kernel, snap_sep); as for the per-pair entries the bfgx_model

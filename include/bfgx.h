@@ -185,10 +185,12 @@ int bfgx_paint_shell_multi(const bfgx_catalog *cat_host, const bfgx_model *model
 /* The one-shot calls keep the plan (model on the device, tiling, binning workspace) and their device buffers in small
  * process-wide caches keyed by (device, model contents, nside / grid / box): a repeated call with the same model performs no
  * device allocation.  The shell, grid and snapshot-records entries each have a cache and a lock of their own.
- * bfgx_cache_clear frees the caches; bfgx_debug_alloc_count = device allocations made so far (tests).
+ * bfgx_cache_clear frees the caches; bfgx_debug_alloc_count = device allocations made so far, bfgx_debug_live_allocs = those of them
+ * not yet freed (tests).
  * bfgx_host_alloc / bfgx_host_free: page-locked host memory for map_out (D2H at full PCIe rate; plain memory works too). */
 void      bfgx_cache_clear(void);
 long long bfgx_debug_alloc_count(void);
+long long bfgx_debug_live_allocs(void);
 /* catalog copies host -> device made by the one-shot entries so far (tests: a call that repeats bfgx_opts.catalog_token makes none) */
 long long bfgx_debug_catalog_uploads(void);
 /* how the one-shot host entries have treated the caller's arrays so far (tests): arrays page-locked IN PLACE for a call (hipHostRegister; only
