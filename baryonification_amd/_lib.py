@@ -289,6 +289,8 @@ SYMBOLS = {
     'bfgx_grid_profiles_device': (C.c_int, [C.c_int32, C.c_void_p, _P(bfgx_grid_catalog), _P(bfgx_model), _P(bfgx_grid), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    'bfgx_pcl_coupling_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_pcl_coupling': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_math_probe': (C.c_int, [C.c_int, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 

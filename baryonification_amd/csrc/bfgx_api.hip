@@ -42,6 +42,7 @@
 #include "bfgx_sht.hpp"
 #include "bfgx_hpx.hpp"
 #include "bfgx_mapstats.hpp"
+#include "bfgx_pcl.hpp"
 #include "bfgx_stack_core.hpp"
 #include "bfgx_stack.hpp"
 #include "bfgx_snapshot_stack.hpp"
@@ -2135,6 +2136,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 
 // map reductions: moments / cross-moments and peak counts of HEALPix maps
 #include "bfgx_mapstats_api.inc"
+
+// mode-coupling matrices of a mask: pseudo-C_l of masked spin-0 and spin-2 shells
+#include "bfgx_pcl_api.inc"
 
 // halo-centred radial profiles: what the three measurements below share on the host
 #include "bfgx_profiles_common.inc"

@@ -677,6 +677,36 @@ def sht_anafast_host(map1, map2, nside, lmax, mmax, iter, want_alm=False, device
     return cl, a1, a2
 
 
+# ---------------------------------------------------------------------------------------------- mode-coupling matrices of a mask
+PCL_MAX_LMAX, PCL_MAX_LW = 8191, 16383      # include/bfgx.h bfgx_pcl_coupling
+
+
+def pcl_coupling_host(wl, lmax, kind, device=0):
+    """one-shot host entry: float64 wl [lw + 1] in, the matrix [lmax + 1, lmax + 1] of kind 0 (M00) or 1 (M0+), or the pair (M++, M--) of
+    kind 2, out (PCIe included)"""
+    w = np.ascontiguousarray(wl, dtype=np.float64)
+    n = int(lmax) + 1
+    m0 = np.empty((n, n))
+    m1 = np.empty_like(m0) if int(kind) == 2 else None
+    _lib.check(_lib.load().bfgx_pcl_coupling(int(device), int(lmax), w.size - 1, int(kind), w.ctypes.data, m0.ctypes.data,
+                                            None if m1 is None else m1.ctypes.data))
+    return m0 if m1 is None else (m0, m1)
+
+
+def pcl_coupling_device(wl_dev, lmax, kind, device=0):
+    """the same on the device: wl_dev a contiguous float64 CUDA tensor, the matrices CUDA tensors; enqueued on torch's current stream.
+    (utils.pseudocl checks lmax against PCL_MAX_LMAX before it comes here, so that a call the C entry refuses allocates nothing.)"""
+    import torch
+    n = int(lmax) + 1
+    m0 = torch.empty((n, n), dtype=torch.float64, device=wl_dev.device)
+    m1 = torch.empty_like(m0) if int(kind) == 2 else None
+    stream = torch.cuda.current_stream(wl_dev.device).cuda_stream
+    _lib.check(_lib.load().bfgx_pcl_coupling_device(int(device), C.c_void_p(stream or None), int(lmax), wl_dev.numel() - 1, int(kind),
+                                                   C.c_void_p(wl_dev.data_ptr()), C.c_void_p(m0.data_ptr()),
+                                                   None if m1 is None else C.c_void_p(m1.data_ptr())))
+    return m0 if m1 is None else (m0, m1)
+
+
 def math_probe(fn_name, a, b=None, c=None, device=0):
     """One function of csrc/bfgx_math.hpp evaluated elementwise on the GPU (bfgx_math_probe; names in _lib.MATH_FN).  Returns one array,
     or (sin, cos) for the sincos functions.  'atan2' takes (a, b) = (y, x), 'mul_add_nc' computes a * b + c without contraction,

@@ -7,3 +7,4 @@ from .sphtfunc import map2alm, alm2map, alm2cl, anafast, map2alm_spin, alm2map_s
 from .pixelfunc import ud_grade, get_interp_weights, get_interp_val, get_all_neighbours, UNSEEN
 from .mapstats import (map_moments, peak_counts, shell_statistics, moment_exponents, minkowski_functionals,
                        minkowski_from_derivatives, minkowski_gaussian)
+from .pseudocl import mode_coupling_matrix, mask_spectrum, ClBins, pseudo_cl, PseudoClWorkspace, decoupled_cl

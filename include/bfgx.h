@@ -743,6 +743,22 @@ int64_t bfgx_mapstats_minkowski_work_doubles(int64_t npix, int32_t nb);
 int  bfgx_mapstats_minkowski_device(int device, void *hip_stream, int64_t npix, const double *ders_dev, const uint8_t *mask_dev, int32_t nb,
                                     const double *edges_dev, int64_t *counts_dev, double *sums_dev, double *work_dev);
 
+/* ---- mode-coupling matrices of a mask: pseudo-C_l of masked spin-0 and spin-2 maps ------------------------------
+ * wl = W_0 .. W_lw, the (cross-)spectrum of the mask(s), 0 beyond lw.  With (l l' j; a b c) the Wigner 3j symbol, L = l + l' + j and
+ * j from |l - l'| to min(l + l', lw):
+ *   kind 0:  m0 = M00[l,l'] = (2l'+1)/(4 pi) sum (2j+1) W_j (l l' j; 0 0 0)^2
+ *   kind 1:  m0 = M0+[l,l'] = (2l'+1)/(4 pi) sum (2j+1) W_j (l l' j; 0 0 0) (l l' j; 2 -2 0)
+ *   kind 2:  m0 = M++[l,l'] = (2l'+1)/(4 pi) sum (2j+1) W_j (l l' j; 2 -2 0)^2 over even L,  m1 = M--: the same over odd L
+ * so that <pseudo C^00> = M00 C^00, <C^0E> = M0+ C^0E, <C^EE> = M++ C^EE + M-- C^BB, <C^BB> = M-- C^EE + M++ C^BB and
+ * <C^EB> = (M++ - M--) C^EB.  The matrices are (lmax + 1) x (lmax + 1) doubles, row-major; entries with |l - l'| > lw, and for kinds 1
+ * and 2 rows and columns below 2, are exactly 0.  0 <= lmax <= 8191, 0 <= lw <= 16383; m1 is used by kind 2 alone (NULL otherwise).
+ * fp64; every entry is computed once in a fixed order (no atomics): a repeated call gives the same bits.
+ *   bfgx_pcl_coupling_device   wl and the matrices are device pointers; enqueue-only on hip_stream
+ *   bfgx_pcl_coupling          host arrays: upload + kernel + download */
+int  bfgx_pcl_coupling_device(int device, void *hip_stream, int32_t lmax, int32_t lw, int32_t kind, const double *wl_dev, double *m0_dev,
+                              double *m1_dev);
+int  bfgx_pcl_coupling(int device, int32_t lmax, int32_t lw, int32_t kind, const double *wl, double *m0, double *m1);
+
 /* ---- halo-centred radial profiles of shell maps (MeasureProfilesShell) ------------------------------
  * The adjoint of PaintProfilesShell: for halo j the pixels of query_disc(nside, vec_j, R_j epsilon_max / D_j) (RING, no < 4-pixel fallback) at
  * separation r_sep = D_j |vec_pix - vec_j| (HealpixRunner.py:418-438) are binned in x = r_sep / a_j (comoving Mpc, :441) or, scaled != 0,
