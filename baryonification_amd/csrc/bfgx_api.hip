@@ -125,13 +125,12 @@ struct bfgx_plan {
     float *k0_work_est = nullptr;   // per K0 workgroup: estimated pixels of its narrow halos (k1_form_kernel)
     int32_t *k1_form = nullptr;     // device word: the fast kernel's form when the halo count does not decide it (1 fluid, 0 barrier per tile)
     int64_t k1_nhalos = 0;          // halos of the catalog the binning step has just listed (the fast kernel's form follows their density)
-    int k1_wide = 1;                // the fast kernel takes the WIDE discs too (a pole inside, pixels beyond 0.40 rad of the halo's azimuth: RowRec.fb bit 1) and the generic kernel's wide pass is not launched; BFGX_K1_WIDE=0 at plan creation: they go through the wide pass (tests: the two must agree)
     int k1_fluid = 1;               // the fast kernel's fluid form (bfgx_scatter2.hpp): 1 = from 2 tiles per CU; BFGX_K1_FLUID at plan creation: 0 = never (the barrier-per-tile form), 2 = always (tests)
     Tiling tiling;
     TileArena arena;                 // everything a step resets, in one allocation: the binning counters, K1's tile counter, the per-tile largest |offset|^2, the regrid's control words (bfgx_tile_arena.hpp)
     int32_t *tile_start = nullptr, *entries = nullptr, *overflow = nullptr;
-    // narrow halos over <= 4 tiles are placed by K0 itself into fixed-capacity lists [ntiles][entries_a_cap]; the others are listed per K0
-    // workgroup for the placement pass
+    // a fast plan's halos over <= 4 tiles are placed by K0 itself into fixed-capacity lists [ntiles][entries_a_cap]; the others (and every
+    // halo of a generic plan) are listed per K0 workgroup for the placement pass
     int32_t *entries_a = nullptr, *slow_list = nullptr, *slow_cnt = nullptr;
     int32_t entries_a_cap = 0;
     int32_t cnt_pad = 1;             // words between region A's counters of two tiles (a 128-byte line each up to 8192 tiles): see wave_run_issue
@@ -147,7 +146,7 @@ struct bfgx_plan {
     int band_reach = 1;              // banded regrid: rings of apron every rank uses (bfgx_plan_set_band_reach)
     int route_margin = 0;            // rings by which bfgx_disc_rings_device widens every halo's range (bfgx_plan_set_route_margin)
     int64_t cat_blk_rows = 0, cat_blk_stride = 0;      // K0 reads a blocked catalog (bfgx_plan_set_catalog_blocks)
-    WideTiles wide;                  // list: number of tiles with wide entries, then those tiles (tile_scan_kernel); behind it the scratch of the multi-workgroup scan
+    ScanScratch scan;                // per-block totals and offsets of the multi-workgroup tile scan
     // fast tiled scatter (bfgx_scatter2.hpp): slim per-halo records + interleaved copies of the table
     bool fast_ok = false;            // 3-axis table with a uniform ln r axis, small enough to interleave
     RowRec *rowrec = nullptr;
@@ -305,8 +304,8 @@ struct DispMode {
     int acc() const { return kind == F32 ? BFGX_ACC_F32 : kind == F64 ? BFGX_ACC_F64 : BFGX_ACC_PARITY; }
 };
 
-// BFGX_ACC_AUTO -> what the plan chose from its table; BFGX_ACC_PARITY needs the fast tile kernel (3-axis table, uniform ln r) with the wide
-// discs in it and falls back to fp64 throughout (a superset of its accuracy) elsewhere.  one_array: the caller's pix_offsets are ONE array
+// BFGX_ACC_AUTO -> what the plan chose from its table; BFGX_ACC_PARITY needs the fast tile kernel (3-axis table, uniform ln r)
+// and falls back to fp64 throughout (a superset of its accuracy) elsewhere.  one_array: the caller's pix_offsets are ONE array
 // (the band entries, whose slices travel between ranks): the parity-grade mode is served by fp64 throughout there
 static int disp_mode(const bfgx_plan *p, int acc, bool one_array, DispMode &m)
 {
@@ -314,7 +313,7 @@ static int disp_mode(const bfgx_plan *p, int acc, bool one_array, DispMode &m)
     if (acc != BFGX_ACC_AUTO && acc != BFGX_ACC_F32 && acc != BFGX_ACC_F64 && acc != BFGX_ACC_PARITY)
         return fail(BFGX_ERR_INVALID, "acc_f64 = %d: must be BFGX_ACC_AUTO (-1), 0 (f32), 1 (f64) or BFGX_ACC_PARITY (3)", acc);
     if (acc == BFGX_ACC_AUTO) acc = p->auto_acc;
-    const bool parity = acc == BFGX_ACC_PARITY && use_fast(p) && p->k1_wide;
+    const bool parity = acc == BFGX_ACC_PARITY && use_fast(p);
     m.kind = acc == BFGX_ACC_F32 ? DispMode::F32 : (parity && !one_array) ? DispMode::SPLIT : DispMode::F64;
     return BFGX_OK;
 }
@@ -346,7 +345,7 @@ struct TileLaunch {
 };
 
 // K0.  bin: also reserve the halo's slots in the tile entry lists; f64: precision of the fast kernel's pair records;
-// rec_all: write the full HaloRec of every halo (halo-centric kernels), otherwise only of the wide ones
+// rec_all: write the full HaloRec of every halo (halo-centric kernels), otherwise only of those the generic tile kernel takes
 static int launch_prep(bfgx_plan *p, const bfgx_catalog *c, int fallback4, bool bin, bool f64, bool rec_all)
 {
     if (c->n == 0) return BFGX_OK;
@@ -355,15 +354,14 @@ static int launch_prep(bfgx_plan *p, const bfgx_catalog *c, int fallback4, bool 
     PrepOut o;
     std::memset(&o, 0, sizeof(o));
     o.rec = p->recs; o.rowsx = p->rowsx;
-    o.fast = (bin && use_fast(p)) ? (p->k1_wide ? 2 : 1) : 0;
+    o.fast = (bin && use_fast(p)) ? 1 : 0;
     o.rec_all = (rec_all || !o.fast) ? 1 : 0;
     o.rowrec = p->rowrec; o.pairrec = p->pairrec; o.fbrec = p->fbrec;
     if (bin) {
-        o.tref = p->tref; o.cnt_a = p->arena.cnt_a; o.cnt_b = p->arena.cnt_b; o.cnt_w = p->arena.cnt_w;
-        if (o.fast && p->entries_a) o.cnt_a = p->arena.cnt_a_pad;          // (direct placement: the padded counters, cnt_pad words apart)
+        o.tref = p->tref; o.cnt_a = p->arena.cnt_a_pad; o.cnt_b = p->arena.cnt_b;
         o.cnt_pad = p->cnt_pad;
         o.work_est = o.fast ? p->k0_work_est : nullptr;
-        o.entries_a = o.fast ? p->entries_a : nullptr; o.cap_a = p->entries_a_cap; o.slow_list = p->slow_list; o.slow_cnt = p->slow_cnt;
+        o.entries_a = p->entries_a; o.cap_a = p->entries_a_cap; o.slow_list = p->slow_list; o.slow_cnt = p->slow_cnt;
     }
     o.ncell_m = p->model.tab.n[1] - 1; o.nrm1 = p->model.tab.n[2] - 1;
     o.blk_rows = p->cat_blk_rows; o.blk_stride = p->cat_blk_stride;
@@ -386,8 +384,7 @@ static int launch_place(bfgx_plan *p, const bfgx_catalog *c)
 {
     const unsigned grid = (unsigned)((c->n + 255) / 256);
     hipLaunchKernelGGL(tile_place_kernel, dim3(grid), dim3(256), 0, p->stream, p->hpx, p->tiling, c->n,
-                       (const TileRef *)p->tref, (const int32_t *)p->tile_start, (const int32_t *)p->arena.zeros,
-                       (const int32_t *)p->arena.cnt_b, p->arena.cur_b, p->arena.cur_w, p->entries, p->capacity, p->overflow,
+                       (const TileRef *)p->tref, (const int32_t *)p->tile_start, p->arena.cur_b, p->entries, p->capacity, p->overflow,
                        (const int32_t *)p->slow_list, (const int32_t *)p->slow_cnt);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
@@ -402,16 +399,14 @@ static int launch_prep_and_bin(bfgx_plan *p, const bfgx_catalog *c, int fallback
     if (int rc = launch_prep(p, c, fallback4, true, f64, false)) return rc;
     KernelTimer kt(p, BFGX_K_BIN);
     const int nt_i = p->tiling.ntiles, nsb = (nt_i + kScanTilesPerWg - 1) / kScanTilesPerWg;
+    const int32_t *cnt = p->arena.cnt_b;
     if (nsb <= 1 || nsb > 1024) {
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros,
-                           (const int32_t *)p->arena.cnt_b, (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, p->stream, nt_i, cnt, p->tile_start);
     } else {        // NSIDE >= 2048: the scan spread over the tiles' blocks (three short launches instead of up to 48 serial rounds)
-        int32_t *tot = p->wide.block_tot, *off = p->wide.block_off;
-        hipLaunchKernelGGL(tile_scan_part_kernel<0>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros, (const int32_t *)p->arena.cnt_b,
-                           (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list, tot, (const int32_t *)off);
-        hipLaunchKernelGGL(tile_scan_blocks_kernel, dim3(1), dim3(1024), 0, p->stream, nsb, nt_i, (const int32_t *)tot, off, p->tile_start, p->wide.list);
-        hipLaunchKernelGGL(tile_scan_part_kernel<1>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, (const int32_t *)p->arena.zeros, (const int32_t *)p->arena.cnt_b,
-                           (const int32_t *)p->arena.cnt_w, p->tile_start, p->wide.list, tot, (const int32_t *)off);
+        int32_t *tot = p->scan.block_tot, *off = p->scan.block_off;
+        hipLaunchKernelGGL(tile_scan_part_kernel<0>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, cnt, p->tile_start, tot, (const int32_t *)off);
+        hipLaunchKernelGGL(tile_scan_blocks_kernel, dim3(1), dim3(1024), 0, p->stream, nsb, nt_i, (const int32_t *)tot, off, p->tile_start);
+        hipLaunchKernelGGL(tile_scan_part_kernel<1>, dim3(nsb), dim3(1024), 0, p->stream, nt_i, cnt, p->tile_start, tot, (const int32_t *)off);
     }
     HIP_TRY(hipGetLastError());
     if (c->n > 0) if (int rc = launch_place(p, c)) return rc;
@@ -431,26 +426,23 @@ static int launch_scatter(bfgx_plan *p, int64_t n, ACC *out, int64_t *counts)
 }
 
 template <int MODE, typename ACC, int NC>
-static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, const TileLaunch &k, bool wide_only)
+static int launch_tile_scatter_nc(bfgx_plan *p, ACC *out, const TileLaunch &k)
 {
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     const size_t lds = tile_lds_bytes<NC>(p->tiling.BR, p->tiling.W, NCOMP);
     auto kern = tile_scatter_kernel<MODE, ACC, NC>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    KernelTimer kt(p, wide_only ? BFGX_K_WIDE : (MODE == MODE_OFFSETS ? BFGX_K_OFFSETS : (MODE == MODE_PAINT ? BFGX_K_PAINT : BFGX_K_COUNT)));
-    // wide pass: a small fixed grid walks the list of tiles that have wide entries (usually empty or a few polar tiles)
-    const int grid = wide_only ? std::min(p->tiling.ntiles, 512) : (k.tile_n < 0 ? p->tiling.ntiles : std::max(k.tile_n, 1));
+    KernelTimer kt(p, MODE == MODE_OFFSETS ? BFGX_K_OFFSETS : (MODE == MODE_PAINT ? BFGX_K_PAINT : BFGX_K_COUNT));
+    const int grid = k.tile_n < 0 ? p->tiling.ntiles : std::max(k.tile_n, 1);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * kWavesPerBlock), lds, p->stream,
                        make_pair_table(p->model.tab), p->hpx, p->tiling, (const HaloRec *)p->recs, (const RowSetX *)p->rowsx,
                        (const int32_t *)p->tile_start, (const int32_t *)p->entries, p->capacity, out, p->pair_total,
-                       wide_only ? (const int32_t *)p->arena.zeros : (const int32_t *)nullptr,
-                       wide_only ? (const int32_t *)p->arena.cnt_b : (const int32_t *)nullptr, wide_only ? 1 : 0,
-                       wide_only ? (const int32_t *)p->wide.list : (const int32_t *)nullptr, (unsigned int *)k.omax, k.tile_lo, k.tile_n);
+                       (unsigned int *)k.omax, k.tile_lo, k.tile_n);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
 
-// fast kernel over the narrow-halo region of every tile (stores the tile)
+// fast kernel: every halo of a fast plan, from the tile's fixed list and its part of the shared list
 template <int MODE, typename ACC, typename real, int PM = 0>
 static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC *out_lo = nullptr)
 {
@@ -496,7 +488,7 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC
             const int gridf = std::min(ntodo, p->num_cus);
             hipLaunchKernelGGL(kf, dim3(std::max(gridf, 1)), dim3(kWave * FluidWaves<real>::n), ldsf, p->stream, tb, p->hpx, p->tiling,
                                (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
-                               (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->arena.cnt_a_pad : p->arena.cnt_a), (const int32_t *)p->arena.cnt_b,
+                               (const int32_t *)p->tile_start, (const int32_t *)p->arena.cnt_a_pad, (const int32_t *)p->arena.cnt_b,
                                (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, tile_counter,
                                (unsigned int *)k.omax, k.tile_lo, k.tile_n, p->overflow, (const int32_t *)form, 1);
             HIP_TRY(hipGetLastError());
@@ -506,14 +498,14 @@ static int launch_tile_scatter2(bfgx_plan *p, ACC *out, const TileLaunch &k, ACC
     const int grid = std::min(ntodo, 2 * p->num_cus);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kWave * kW2), lds, p->stream, tb, p->hpx, p->tiling,
                        (const RowRec *)p->rowrec, (const PairRecT<real> *)p->pairrec, (const FbRec *)p->fbrec,
-                       (const int32_t *)p->tile_start, (const int32_t *)(p->entries_a ? p->arena.cnt_a_pad : p->arena.cnt_a), (const int32_t *)p->arena.cnt_b,
+                       (const int32_t *)p->tile_start, (const int32_t *)p->arena.cnt_a_pad, (const int32_t *)p->arena.cnt_b,
                        (const int32_t *)p->entries, p->capacity, (const int32_t *)p->entries_a, (int)p->entries_a_cap, (int)p->cnt_pad, out, out_lo, p->pair_total, tile_counter,
                        (unsigned int *)k.omax, k.tile_lo, k.tile_n, (const int32_t *)form, 0);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
 
-// the tiled scatter: fast kernel for the narrow halos (if the table allows) + generic kernel for the rest
+// the tiled scatter: the fast kernel if the table allows, the generic kernel otherwise
 template <int MODE, typename ACC>
 static int launch_tile_scatter(bfgx_plan *p, ACC *out, const TileLaunch &k)
 {
@@ -525,20 +517,16 @@ static int launch_tile_scatter(bfgx_plan *p, ACC *out, const TileLaunch &k)
         }
         if constexpr (MODE == MODE_PAINT && sizeof(ACC) == 8) {
             // acc_f64 = 2: the pair phase in fp32 (K0 wrote fp32 pair records), LDS accumulation and the stored map in fp64
-            if (k.paint_pair_f32) {
-                if (int rc = launch_tile_scatter2<MODE, ACC, float>(p, out, k)) return rc;
-                return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, true);
-            }
+            if (k.paint_pair_f32) return launch_tile_scatter2<MODE, ACC, float>(p, out, k);
         }
-        if (int rc = launch_tile_scatter2<MODE, ACC, real>(p, out, k)) return rc;
-        return p->k1_wide ? BFGX_OK : launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, true);      // (k1_wide: K0 classed no halo as wide)
+        return launch_tile_scatter2<MODE, ACC, real>(p, out, k);
     }
-    if (p->NC == 4) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, false);
-    if (MODE == MODE_COUNT) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k, false);      // census never reads the rows
-    if (p->NC == 8) return launch_tile_scatter_nc<MODE, ACC, 8>(p, out, k, false);
-    if (p->NC == 16) return launch_tile_scatter_nc<MODE, ACC, 16>(p, out, k, false);
-    if (p->NC == 32) return launch_tile_scatter_nc<MODE, ACC, 32>(p, out, k, false);       // three / four property axes (Tabulate.py:524-561)
-    return launch_tile_scatter_nc<MODE, ACC, 64>(p, out, k, false);
+    if (p->NC == 4) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k);
+    if (MODE == MODE_COUNT) return launch_tile_scatter_nc<MODE, ACC, 4>(p, out, k);      // census never reads the rows
+    if (p->NC == 8) return launch_tile_scatter_nc<MODE, ACC, 8>(p, out, k);
+    if (p->NC == 16) return launch_tile_scatter_nc<MODE, ACC, 16>(p, out, k);
+    if (p->NC == 32) return launch_tile_scatter_nc<MODE, ACC, 32>(p, out, k);       // three / four property axes (Tabulate.py:524-561)
+    return launch_tile_scatter_nc<MODE, ACC, 64>(p, out, k);
 }
 
 // blocking: if the entry list overflowed, grow it to the exact size and redo the fill pass
@@ -552,7 +540,7 @@ static int ensure_entry_capacity(bfgx_plan *p, const bfgx_catalog *c)
     HIP_TRY(p->mem.regrow(p->entries, (size_t)total + 16));    // (the stream has just been drained: the old list is freed at once)
     p->capacity = (int64_t)total + 16;
     HIP_TRY(hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream));
-    HIP_TRY(hipMemsetAsync(p->arena.cur_b, 0, p->arena.cursor_bytes, p->stream));   // cur_b, cur_w
+    HIP_TRY(hipMemsetAsync(p->arena.cur_b, 0, p->arena.cursor_bytes, p->stream));
     return launch_place(p, c);
 }
 
@@ -698,7 +686,6 @@ static int plan_init_binning(bfgx_plan *p, const bfgx_table &t, size_t nh)
     if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "stream sync failed");
     p->capacity = 8 * p->max_halos + 4096;
     if (const char *e = std::getenv("BFGX_K1_FLUID")) p->k1_fluid = std::max(0, std::min(2, std::atoi(e)));
-    if (const char *e = std::getenv("BFGX_K1_WIDE")) p->k1_wide = std::atoi(e) != 0;
     if (const char *e = std::getenv("BFGX_ENTRY_CAP")) p->capacity = std::max<int64_t>(16, std::atoll(e));   // tests: force regrowth
     // region A's counters: a line each while that array stays below 4 MB (atomics to one line serialise; a larger array costs misses)
     p->cnt_pad = kCntPadMax;
@@ -859,10 +846,10 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
     if (int rc = plan_init_fast(p, t, nh)) return bail(rc);
     if (int rc = plan_init_binning(p, t, nh)) return bail(rc);
     if (int rc = plan_init_regrid(p)) return bail(rc);
-    const WideTilesLayout WL = wide_tiles_layout((size_t)p->tiling.ntiles);
-    int32_t *wide = nullptr;
-    if (p->mem.alloc(wide, WL.total_words)) return bail(alloc_fail("wide tile list"));
-    p->wide.bind(wide, WL);
+    const ScanScratchLayout SL = scan_scratch_layout();
+    int32_t *scan = nullptr;
+    if (p->mem.alloc(scan, SL.total_words)) return bail(alloc_fail("tile scan scratch"));
+    p->scan.bind(scan, SL);
     if (p->mem.alloc(p->tile_sums, 2 * (size_t)(p->tiling.ntiles + 1))) return bail(alloc_fail("tile sums"));
     if (hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
     if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));

@@ -440,8 +440,8 @@ __device__ inline int ring_len(const Hpx &h, int ring)
     return (int)(4 * (ring < n ? ring : (ring > 3 * n ? 4 * n - ring : n)));
 }
 
-// where K0 already reserved this halo's slots in its tiles' entry lists (n <= kRefMax), or n > kRefMax: the
-// placement pass enumerates the tiles again (from the span kept in the same bytes) and takes slots by cursor
+// what the placement pass needs of a halo K0 left to it: its tiles (n <= kRefMax; slot < 0: to be placed by cursor, otherwise K0 has
+// stored it in the tile's fixed list), or n > kRefMax: the pass enumerates the tiles again from the span kept in the same bytes
 constexpr int kRefMax = 4;
 struct TileRef {
     union {
@@ -449,13 +449,13 @@ struct TileRef {
         struct { int32_t rfirst, rlast, allphi, _p; double flo, fhi; } many;        // n >  kRefMax (never a fallback halo)
     };
     int32_t n;
-    int32_t cls;                           // kClsNone / kClsNarrow / kClsWide
+    int32_t live;                          // 0: the halo contributes nothing (K0's class kClsNone)
     int32_t _pad[2];
 };
 
-// halo classes of the tiled scatter: narrow discs (|azimuth difference| <= 0.45 for every pixel, no pole inside) go to the
-// fast kernel (bfgx_scatter2.hpp), everything else (polar caps, very low z) to the generic tile kernel below
-enum { kClsNone = 0, kClsNarrow = 1, kClsWide = 2 };
+// K0's halo classes, a property of the plan for every halo that can touch a pixel: a fast plan's halos go to the fast kernel
+// (bfgx_scatter2.hpp), a generic plan's (property axes, non-uniform ln r axis) to the generic tile kernel below
+enum { kClsNone = 0, kClsFast = 1, kClsGeneric = 2 };
 
 // what the tile enumeration needs of a disc
 struct DiscSpan {
@@ -576,18 +576,18 @@ struct PrepOut {
     void *pairrec;                // PairRecT<real> *
     FbRec *fbrec;
     TileRef *tref;                // tile binning (nullptr: no binning)
-    int32_t *cnt_a, *cnt_b, *cnt_w;
-    // direct placement of the narrow halos that touch <= kRefMax tiles (almost all of them): their slot in a tile's FIXED-CAPACITY list
+    int32_t *cnt_a, *cnt_b;       // entries per tile: of its fixed list (fast plans; cnt_pad words apart) and of the shared list
+    // direct placement of a fast plan's halos that touch <= kRefMax tiles (almost all of them): their slot in a tile's FIXED-CAPACITY list
     // entries_a[tile][cap_a] is the value the counting atomic returns, so K0 stores the halo index there itself -- no TileRef, no placement
-    // pass.  Only the others (wide discs, discs over more than kRefMax tiles, slots beyond cap_a) are listed per K0 workgroup
-    // (slow_list[block][256], slow_cnt[block]) for tile_place_kernel, which draws their slots from cursors after the scan.
+    // pass.  Only the others (discs over more than kRefMax tiles, slots beyond cap_a, every halo of a generic plan) are listed per K0
+    // workgroup (slow_list[block][256], slow_cnt[block]) for tile_place_kernel, which draws their slots from cursors after the scan.
     int32_t *entries_a, *slow_list, *slow_cnt;
     float *work_est;              // per K0 workgroup: the sum of its narrow halos' estimated pixels (pi radius^2 / pixel area): what the fast
                                   // kernel's form is chosen by when the halo count alone does not say (nullptr: not wanted)
     int32_t cap_a;
-    int32_t cnt_pad;              // words between two tiles' counters in cnt_a when entries_a is set (direct placement)
-    int32_t fast;                 // 1: narrow halos are class kClsNarrow (fast kernel), 0: every halo is kClsWide (generic kernel), 2: the fast kernel
-                                  // takes the wide discs too (RowRec.fb bit 1): no halo is left to the generic kernel's wide pass
+    int32_t cnt_pad;              // words between two tiles' counters in cnt_a
+    int32_t fast;                 // 1: a fast plan -- every halo goes to the fast kernel (kClsFast; the wide discs marked by RowRec.fb bit 1);
+                                  // 0: a generic plan -- every halo goes to the generic kernel (kClsGeneric)
     int32_t rec_all;              // 1: HaloRec for every halo (halo-centric algo 0)
     int32_t ncell_m, nrm1;        // (nm - 1), (nr - 1) of the interleaved table
     // a BLOCKED catalog (the rows an all_to_all has just delivered, [block][column][blk_rows]): halo j reads its columns at
@@ -756,22 +756,22 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
         }
     }
 
-    // class: the fast kernel takes discs without a pole inside whose pixels all lie within 0.40 rad of the halo's azimuth
-    // (fallback pixels: within one pixel of it, so rings of at least 64 pixels are narrow enough)
-    int cls = kClsWide;
-    bool geo_wide = false;                 // (o.fast == 2) a disc the fast kernel takes through its general row spans and full-range sin / cos
-    if (bad) cls = kClsNone;
-    else if (o.fast && NC == 4 && !r.allphi && dmax <= 0.40) {
-        cls = kClsNarrow;
-        if (r.fb) for (int q = 0; q < 4; ++q) if (r.fb_ring[q] < 16 || r.fb_ring[q] > (int)nl4 - 16) cls = kClsWide;
+    // class: bad -> none; a fast plan -> the fast kernel, which takes a disc through its general row spans and full-range sin / cos
+    // (geo_wide) unless it is narrow: no pole inside and every pixel within 0.40 rad of the halo's azimuth (fallback pixels: within one
+    // pixel of it, so rings of at least 64 pixels are narrow enough); a generic plan -> the generic kernel
+    const bool to_fast = o.fast && NC == 4;
+    const int cls = bad ? kClsNone : (to_fast ? kClsFast : kClsGeneric);
+    bool geo_wide = false;
+    if (cls == kClsFast) {
+        geo_wide = r.allphi || !(dmax <= 0.40);
+        if (r.fb) for (int q = 0; q < 4; ++q) if (r.fb_ring[q] < 16 || r.fb_ring[q] > (int)nl4 - 16) geo_wide = true;
     }
-    if (o.fast == 2 && NC == 4 && cls == kClsWide) { cls = kClsNarrow; geo_wide = true; }
     // tile binning, pass 1: reserve one slot per touched tile.  Issued HERE, before the model-side arithmetic and the record
     // stores, so that the returning atomics (the longest latency of this kernel) are in flight while the rest is computed;
     // the TileRef that holds the slots is stored last.
     if (o.work_est) {
         // pixels of the disc: pi radius^2 / (4 pi / npix); one add per wave (the waves of a workgroup share one LDS word)
-        float w = (cls == kClsNarrow) ? (r.fb ? 4.0f : (float)(radius * radius) * 0.25f * (float)h.npix) : 0.0f;
+        float w = (cls == kClsFast) ? (r.fb ? 4.0f : (float)(radius * radius) * 0.25f * (float)h.npix) : 0.0f;
 #pragma unroll
         for (int sft = kWave >> 1; sft > 0; sft >>= 1) w += __shfl_xor(w, sft, kWave);
         if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(s_work, w);
@@ -779,7 +779,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     TileRef ref;
     RunSlot run[kRefMax];
     for (int i = 0; i < kRefMax; ++i) { run[i].base = 0; run[i].hr = 0; }
-    ref.n = 0; ref.cls = cls; ref._pad[0] = ref._pad[1] = 0;
+    ref.n = 0; ref.live = cls != kClsNone; ref._pad[0] = ref._pad[1] = 0;
     for (int i = 0; i < kRefMax; ++i) { ref.few.tile[i] = 0; ref.few.slot[i] = 0; }
     if (o.tref) {
         DiscSpan ds;
@@ -788,23 +788,22 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
         int tl[kRefMax] = {0, 0, 0, 0};
         int nt = 0;
         if (cls != kClsNone) for_each_tile(h, T, ds, [&](int t) { if (nt < kRefMax) tl[nt] = t; ++nt; });
-        ref.n = nt; ref.cls = cls; ref._pad[0] = ref._pad[1] = 0;
-        // narrow halos over at most kRefMax tiles take their slots now (returning atomics, one per run of lanes that name the same tile; the
-        // halo index is stored into the slot at the end of this function, when the atomic has long returned) -- every lane of the wave goes
-        // through wave_run_slot; wide ones are placed by cursor after the scan
+        ref.n = nt;
+        // a fast plan's halos over at most kRefMax tiles take their slots now (returning atomics, one per run of lanes that name the same
+        // tile; the halo index is stored into the slot at the end of this function, when the atomic has long returned) -- every lane of the
+        // wave goes through wave_run_issue; all others count into the shared list and are placed by cursor after the scan
 #pragma unroll
         for (int i = 0; i < kRefMax; ++i) {
-            run[i] = wave_run_issue(o.cnt_a, o.entries_a ? tl[i] * o.cnt_pad : tl[i], nt <= kRefMax && i < nt && cls == kClsNarrow);
+            run[i] = wave_run_issue(o.cnt_a, tl[i] * o.cnt_pad, nt <= kRefMax && i < nt && cls == kClsFast);
             if (nt <= kRefMax) { ref.few.tile[i] = (i < nt) ? tl[i] : 0; ref.few.slot[i] = 0; }
         }
         if (nt <= kRefMax) {
             for (int i = 0; i < kRefMax; ++i)
-                if (i < nt && cls != kClsNarrow) atomicAdd(o.cnt_w + tl[i], 1);
+                if (i < nt && cls == kClsGeneric) { ref.few.slot[i] = -1; atomicAdd(o.cnt_b + tl[i], 1); }
         } else {
             ref.many.rfirst = r.rfirst; ref.many.rlast = r.rlast; ref.many.allphi = r.allphi; ref.many._p = 0;
             ref.many.flo = r.flo; ref.many.fhi = r.fhi;
-            int32_t *cnt = (cls == kClsNarrow) ? o.cnt_b : o.cnt_w;
-            for_each_tile(h, T, ds, [&](int t) { atomicAdd(cnt + t, 1); });
+            for_each_tile(h, T, ds, [&](int t) { atomicAdd(o.cnt_b + t, 1); });
         }
     }
     // model-side radius and table coordinates (BaryonCorrection.py:364-370, Tabulate.py:279-283)
@@ -829,8 +828,8 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
         if (live) o.rowsx[j] = rx;
     }
 
-    if (live && o.rec && (o.rec_all || cls == kClsWide)) o.rec[j] = r;
-    if (cls == kClsNarrow) {
+    if (live && o.rec && (o.rec_all || cls == kClsGeneric)) o.rec[j] = r;
+    if (cls == kClsFast) {
         RowRec rr;
         rr.z0 = r.z0; rr.s0 = r.s0; rr.xa = r.xa; rr.cosr = r.cosr; rr.phi0 = r.phi0;
         rr.rfirst = r.rfirst; rr.rlast = r.rlast; rr.fb = (r.fb ? 1 : 0) | (geo_wide ? 2 : 0); rr._pad = 0;
@@ -873,19 +872,18 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
 #pragma unroll
         for (int i = 0; i < kRefMax; ++i) {
             const int sl = wave_run_resolve(run[i]);
-            if (ref.n <= kRefMax && ref.cls == kClsNarrow && i < ref.n) ref.few.slot[i] = sl;
+            if (ref.n <= kRefMax && cls == kClsFast && i < ref.n) ref.few.slot[i] = sl;
         }
-        bool slow = (ref.cls != kClsNone) && (ref.n > kRefMax || ref.cls != kClsNarrow);
-        if (ref.cls == kClsNarrow && ref.n <= kRefMax) {
+        bool slow = (cls != kClsNone) && (ref.n > kRefMax || cls != kClsFast);
+        if (cls == kClsFast && ref.n <= kRefMax) {
             for (int i = 0; i < kRefMax; ++i) if (i < ref.n) {
                 const int sl = ref.few.slot[i];
-                if (o.entries_a && sl < o.cap_a) o.entries_a[(int64_t)ref.few.tile[i] * o.cap_a + sl] = (int32_t)j;
-                else if (o.entries_a) { ref.few.slot[i] = -1; atomicAdd(o.cnt_b + ref.few.tile[i], 1); slow = true; }      // the tile's fixed list is full: region B
-                else slow = true;                                                                                         // (no direct placement: every halo is listed)
+                if (sl < o.cap_a) o.entries_a[(int64_t)ref.few.tile[i] * o.cap_a + sl] = (int32_t)j;
+                else { ref.few.slot[i] = -1; atomicAdd(o.cnt_b + ref.few.tile[i], 1); slow = true; }      // the tile's fixed list is full: the shared list
             }
         }
-        if (live && (slow || !o.slow_list)) o.tref[j] = ref;
-        if (slow && o.slow_list) o.slow_list[(int64_t)blockIdx.x * 256 + atomicAdd(s_nslow, 1)] = (int32_t)j;
+        if (live && slow) o.tref[j] = ref;
+        if (slow) o.slow_list[(int64_t)blockIdx.x * 256 + atomicAdd(s_nslow, 1)] = (int32_t)j;
     }
 }
 
@@ -1111,159 +1109,135 @@ k1_form_kernel(int nblk, const float *__restrict__ work_est, float thr_total, in
     }
 }
 
-// exclusive scan of the per-tile entry counts (one workgroup); start[ntiles] = total.  A tile's list is laid out as
-// [narrow, slots reserved by K0 | narrow, many-tile halos | wide]
+// exclusive scan of the per-tile entry counts of the shared list (one workgroup); start[ntiles] = total
 __global__ void __launch_bounds__(1024)
-tile_scan_kernel(int ntiles, const int32_t *__restrict__ cnt_a, const int32_t *__restrict__ cnt_b, const int32_t *__restrict__ cnt_w,
-                 int32_t *__restrict__ start, int32_t *__restrict__ wide_tiles)
+tile_scan_kernel(int ntiles, const int32_t *__restrict__ cnt, int32_t *__restrict__ start)
 {
-    // both exclusive scans (entries per tile; tiles that have wide entries) in one pass: per-thread run of consecutive tiles,
-    // wave scan by shuffles, one barrier, the 16 wave totals scanned by every thread from LDS
+    // per-thread run of consecutive tiles, wave scan by shuffles, one barrier, the 16 wave totals scanned by every thread from LDS
     constexpr int kPer = 8;                              // tiles per thread and round (8192 tiles per round)
-    __shared__ int32_t wtot[2][1024 / kWave];
-    __shared__ int32_t carry[2];
+    __shared__ int32_t wtot[1024 / kWave];
+    __shared__ int32_t carry;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    if (tid < 2) carry[tid] = 0;
+    if (tid == 0) carry = 0;
     __syncthreads();
     for (int base = 0; base < ntiles; base += 1024 * kPer) {
         const int lo = min(base + tid * kPer, ntiles), hi = min(lo + kPer, ntiles);
-        int32_t c[kPer], wv[kPer], s = 0, nw = 0;
+        int32_t c[kPer], s = 0;
 #pragma unroll
         for (int q = 0; q < kPer; ++q) {
             const int i = lo + q;
-            c[q] = 0; wv[q] = 0;
-            if (i < hi) { const int32_t w = cnt_w[i]; c[q] = cnt_a[i] + cnt_b[i] + w; wv[q] = w > 0 ? 1 : 0; }
-            s += c[q]; nw += wv[q];
+            c[q] = i < hi ? cnt[i] : 0;
+            s += c[q];
         }
-        int32_t is = s, iw = nw;                         // inclusive scans inside the wave
+        int32_t is = s;                                  // inclusive scan inside the wave
 #pragma unroll
         for (int off = 1; off < kWave; off <<= 1) {
-            const int32_t us = __shfl_up(is, off, kWave), uw = __shfl_up(iw, off, kWave);
-            if (lane >= off) { is += us; iw += uw; }
+            const int32_t us = __shfl_up(is, off, kWave);
+            if (lane >= off) is += us;
         }
-        if (lane == kWave - 1) { wtot[0][wid] = is; wtot[1][wid] = iw; }
+        if (lane == kWave - 1) wtot[wid] = is;
         __syncthreads();
-        int32_t ps = carry[0], pw = carry[1];
-        for (int w = 0; w < wid; ++w) { ps += wtot[0][w]; pw += wtot[1][w]; }
-        int32_t run = ps + is - s, pos = pw + iw - nw;
+        int32_t ps = carry;
+        for (int w = 0; w < wid; ++w) ps += wtot[w];
+        int32_t run = ps + is - s;
 #pragma unroll
         for (int q = 0; q < kPer; ++q) {
             const int i = lo + q;
-            if (i < hi) {
-                start[i] = run; run += c[q];
-                if (wv[q]) wide_tiles[1 + pos++] = i;    // the tiles that have wide entries: [0] = their number, [1..] = the tiles
-            }
+            if (i < hi) { start[i] = run; run += c[q]; }
         }
         __syncthreads();
-        if (tid == 1023) { carry[0] = run; carry[1] = pos; }
+        if (tid == 1023) carry = run;
         __syncthreads();
     }
-    if (tid == 0) { start[ntiles] = carry[0]; wide_tiles[0] = carry[1]; }
+    if (tid == 0) start[ntiles] = carry;
 }
 
 // The same scan for shells with more tiles than one workgroup covers in a round (NSIDE >= 2048: 2.4e4 .. 3.9e5 tiles, where the
 // single workgroup above spends up to 1 ms in 48 serial rounds): PHASE 0 = every workgroup sums its 8192 tiles into
-// block_tot[2 b .. 2 b + 1]; tile_scan_blocks_kernel scans those (<= 1024 blocks) into block_off and writes the two totals;
-// PHASE 1 = every workgroup scans its tiles starting from its offsets.
+// block_tot[b]; tile_scan_blocks_kernel scans those (<= 1024 blocks) into block_off and writes the total;
+// PHASE 1 = every workgroup scans its tiles starting from its offset.
 constexpr int kScanTilesPerWg = 1024 * 8;
 template <int PHASE>
 __global__ void __launch_bounds__(1024)
-tile_scan_part_kernel(int ntiles, const int32_t *__restrict__ cnt_a, const int32_t *__restrict__ cnt_b, const int32_t *__restrict__ cnt_w,
-                      int32_t *__restrict__ start, int32_t *__restrict__ wide_tiles, int32_t *__restrict__ block_tot, const int32_t *__restrict__ block_off)
+tile_scan_part_kernel(int ntiles, const int32_t *__restrict__ cnt, int32_t *__restrict__ start,
+                      int32_t *__restrict__ block_tot, const int32_t *__restrict__ block_off)
 {
     constexpr int kPer = 8;
-    __shared__ int32_t wtot[2][1024 / kWave];
+    __shared__ int32_t wtot[1024 / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
     const int base = blockIdx.x * kScanTilesPerWg;
     const int lo = min(base + tid * kPer, ntiles), hi = min(lo + kPer, ntiles);
-    int32_t c[kPer], wv[kPer], s = 0, nw = 0;
+    int32_t c[kPer], s = 0;
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
         const int i = lo + q;
-        c[q] = 0; wv[q] = 0;
-        if (i < hi) { const int32_t w = cnt_w[i]; c[q] = cnt_a[i] + cnt_b[i] + w; wv[q] = w > 0 ? 1 : 0; }
-        s += c[q]; nw += wv[q];
+        c[q] = i < hi ? cnt[i] : 0;
+        s += c[q];
     }
-    int32_t is = s, iw = nw;
+    int32_t is = s;
 #pragma unroll
     for (int off = 1; off < kWave; off <<= 1) {
-        const int32_t us = __shfl_up(is, off, kWave), uw = __shfl_up(iw, off, kWave);
-        if (lane >= off) { is += us; iw += uw; }
+        const int32_t us = __shfl_up(is, off, kWave);
+        if (lane >= off) is += us;
     }
-    if (lane == kWave - 1) { wtot[0][wid] = is; wtot[1][wid] = iw; }
+    if (lane == kWave - 1) wtot[wid] = is;
     __syncthreads();
-    int32_t ps = 0, pw = 0;
-    for (int w = 0; w < wid; ++w) { ps += wtot[0][w]; pw += wtot[1][w]; }
+    int32_t ps = 0;
+    for (int w = 0; w < wid; ++w) ps += wtot[w];
     if (PHASE == 0) {
-        if (tid == 1023) { block_tot[2 * blockIdx.x] = ps + is; block_tot[2 * blockIdx.x + 1] = pw + iw; }
+        if (tid == 1023) block_tot[blockIdx.x] = ps + is;
         return;
     }
-    int32_t run = block_off[2 * blockIdx.x] + ps + is - s, pos = block_off[2 * blockIdx.x + 1] + pw + iw - nw;
+    int32_t run = block_off[blockIdx.x] + ps + is - s;
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
         const int i = lo + q;
-        if (i < hi) {
-            start[i] = run; run += c[q];
-            if (wv[q]) wide_tiles[1 + pos++] = i;
-        }
+        if (i < hi) { start[i] = run; run += c[q]; }
     }
 }
 
-// exclusive scan of the per-block totals (nblocks <= 1024); start[ntiles] = all entries, wide_tiles[0] = tiles with wide entries
+// exclusive scan of the per-block totals (nblocks <= 1024); start[ntiles] = all entries
 __global__ void __launch_bounds__(1024)
 tile_scan_blocks_kernel(int nblocks, int ntiles, const int32_t *__restrict__ block_tot, int32_t *__restrict__ block_off,
-                        int32_t *__restrict__ start, int32_t *__restrict__ wide_tiles)
+                        int32_t *__restrict__ start)
 {
-    __shared__ int32_t sa[1024], sb[1024];
+    __shared__ int32_t sa[1024];
     const int tid = threadIdx.x;
-    sa[tid] = tid < nblocks ? block_tot[2 * tid] : 0;
-    sb[tid] = tid < nblocks ? block_tot[2 * tid + 1] : 0;
+    sa[tid] = tid < nblocks ? block_tot[tid] : 0;
     __syncthreads();
     if (tid == 0) {
-        int32_t ra = 0, rb = 0;
-        for (int b = 0; b < nblocks; ++b) { const int32_t ta = sa[b], tb = sb[b]; block_off[2 * b] = ra; block_off[2 * b + 1] = rb; ra += ta; rb += tb; }
-        start[ntiles] = ra; wide_tiles[0] = rb;
+        int32_t ra = 0;
+        for (int b = 0; b < nblocks; ++b) { block_off[b] = ra; ra += sa[b]; }
+        start[ntiles] = ra;
     }
 }
 
-// tile binning, pass 2 (thread per halo): narrow halos with reserved slots are a plain scatter of halo indices; the others
-// draw slots from their region's cursor (many-tile halos enumerate their tiles again from the span kept in the TileRef)
+// tile binning, pass 2: workgroup b places the halos K0's workgroup b left to it (slow_list[b][256], slow_cnt[b]), a thread per halo,
+// into the tiles' shared lists by cursor (many-tile halos enumerate their tiles again from the span kept in the TileRef)
 __global__ void __launch_bounds__(256)
 tile_place_kernel(Hpx h, Tiling T, int64_t nhalo, const TileRef *__restrict__ tref,
-                  const int32_t *__restrict__ start, const int32_t *__restrict__ cnt_a, const int32_t *__restrict__ cnt_b,
-                  int32_t *__restrict__ cur_b, int32_t *__restrict__ cur_w,
+                  const int32_t *__restrict__ start, int32_t *__restrict__ cur_b,
                   int32_t *__restrict__ entries, int64_t capacity, int32_t *__restrict__ overflow,
                   const int32_t *__restrict__ slow_list, const int32_t *__restrict__ slow_cnt)
 {
-    // workgroup b = the halos K0's workgroup b left to this pass (slow_list[b][256], slow_cnt[b]); cnt_a is an array of zeros when region
-    // A lives in the fixed-capacity lists K0 fills itself (the shared list then holds [B | wide] per tile)
-    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slow_list) {
-        if ((int)threadIdx.x >= slow_cnt[blockIdx.x]) return;
-        j = slow_list[j];
-    }
+    if ((int)threadIdx.x >= slow_cnt[blockIdx.x]) return;
+    const int64_t j = slow_list[(int64_t)blockIdx.x * blockDim.x + threadIdx.x];
     if (j >= nhalo) return;
     const TileRef ref = tref[j];
-    if (ref.cls == kClsNone) return;
-    auto put = [&](int64_t pos) { if (pos < capacity) entries[pos] = (int32_t)j; else *overflow = 1; };
+    if (!ref.live) return;
+    auto put = [&](int t) {
+        const int64_t pos = (int64_t)start[t] + atomicAdd(cur_b + t, 1);
+        if (pos < capacity) entries[pos] = (int32_t)j; else *overflow = 1;
+    };
     if (ref.n <= kRefMax) {
-        for (int i = 0; i < kRefMax; ++i) if (i < ref.n) {
-            const int t = ref.few.tile[i];
-            if (ref.cls == kClsNarrow) {
-                if (!slow_list) put((int64_t)start[t] + ref.few.slot[i]);
-                else if (ref.few.slot[i] < 0) put((int64_t)start[t] + cnt_a[t] + atomicAdd(cur_b + t, 1));      // its tile's fixed list was full
-            }
-            else put((int64_t)start[t] + cnt_a[t] + cnt_b[t] + atomicAdd(cur_w + t, 1));
-        }
+        for (int i = 0; i < kRefMax; ++i)
+            if (i < ref.n && ref.few.slot[i] < 0) put(ref.few.tile[i]);       // (slot >= 0: K0 stored it in the tile's fixed list)
     } else {
         DiscSpan ds;
         ds.fb = 0; ds.rfirst = ref.many.rfirst; ds.rlast = ref.many.rlast; ds.allphi = ref.many.allphi;
         ds.flo = ref.many.flo; ds.fhi = ref.many.fhi;
         for (int q = 0; q < 4; ++q) { ds.fb_ring[q] = 0; ds.fb_k[q] = 0; }
-        for_each_tile(h, T, ds, [&](int t) {
-            if (ref.cls == kClsNarrow) put((int64_t)start[t] + cnt_a[t] + atomicAdd(cur_b + t, 1));
-            else put((int64_t)start[t] + cnt_a[t] + cnt_b[t] + atomicAdd(cur_w + t, 1));
-        });
+        for_each_tile(h, T, ds, put);
     }
 }
 
@@ -1676,21 +1650,15 @@ __global__ void __launch_bounds__(kWave * kWavesPerBlock)
 tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ recs, const RowSetX *__restrict__ rowsx,
                     const int32_t *__restrict__ tile_start, const int32_t *__restrict__ entries, int64_t capacity,
                     ACC *__restrict__ out, unsigned long long *__restrict__ pair_total,
-                    const int32_t *__restrict__ cnt_a, const int32_t *__restrict__ cnt_b, int addmode,
-                    const int32_t *__restrict__ wide_tiles, unsigned int *__restrict__ omax2, int tile_lo, int tile_n)
+                    unsigned int *__restrict__ omax2, int tile_lo, int tile_n)
 {
-    // wide_tiles != nullptr ("wide pass"): only the wide-halo region of every tile's entry list is processed (the narrow
-    // halos went through the fast kernel, bfgx_scatter2.hpp, which has stored the tile: addmode) and only the tiles that
-    // have wide entries are visited: wide_tiles[0] = their number, wide_tiles[1..] = the tiles (tile_scan_kernel); the grid
-    // is small and fixed, so a catalog without wide halos costs a few microseconds
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NCOMP = (MODE == MODE_OFFSETS) ? 3 : 1;
     // tile_n >= 0: only the tiles [tile_lo, tile_lo + tile_n) (a rank that owns a range of bands)
-    const int nvisit = wide_tiles ? wide_tiles[0] : (tile_n < 0 ? T.ntiles : tile_n);
+    const int nvisit = tile_n < 0 ? T.ntiles : tile_n;
     for (int bi = blockIdx.x; bi < nvisit; bi += gridDim.x) {
-    // full pass: heavy (equatorial) tiles are dispatched first, the light polar ones fill the tail
-    const int tile = wide_tiles ? wide_tiles[1 + bi] : (tile_n < 0 ? T.tile_order[bi] : tile_lo + bi);
-    if (tile_n >= 0 && (tile < tile_lo || tile >= tile_lo + tile_n)) continue;       // (wide pass: the list covers the sphere)
+    // heavy (equatorial) tiles are dispatched first, the light polar ones fill the tail
+    const int tile = tile_n < 0 ? T.tile_order[bi] : tile_lo + bi;
     const int band = T.tile_band[tile];
     const int nphi = T.band_nphi[band];
     const int tj = tile - T.band_tile0[band];
@@ -1727,14 +1695,12 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
     }
     __syncthreads();
 
-    const int64_t e0 = (int64_t)tile_start[tile] + (cnt_a ? (int64_t)cnt_a[tile] + cnt_b[tile] : 0);
+    const int e0 = tile_start[tile];
     int64_t e1 = tile_start[tile + 1];
     if (e1 > capacity) e1 = capacity;
     const int ne = (int)(e1 > e0 ? e1 - e0 : 0);
-    // entries a wave takes at a time: the wide pass visits a few polar tiles with a handful of entries each (and thousands of
-    // pixels per entry), so small chunks keep all four waves of the tile busy
-    // (full pass: one chunk per wave when the tile's list is short, as in the fast kernel)
-    const int chunk = wide_tiles ? 2 : max(1, min(kChunk, (ne + kWavesPerBlock - 1) / kWavesPerBlock));
+    // entries a wave takes at a time: one chunk per wave when the tile's list is short, as in the fast kernel
+    const int chunk = max(1, min(kChunk, (ne + kWavesPerBlock - 1) / kWavesPerBlock));
     const int nchunks = (ne + chunk - 1) / chunk;
     TileWaveLds &L = wl[wid];
     unsigned long long npairs = 0;
@@ -1908,8 +1874,7 @@ tile_scatter_kernel(PairTable pt, Hpx h, Tiling T, const HaloRec *__restrict__ r
         const int n = (ke - ks) * NCOMP;
         ACC *dst = out + NCOMP * (st + ks);
         const double *src = acc + NCOMP * rr * T.W;
-        if (addmode) { for (int x = lane; x < n; x += kWave) { const ACC v = (ACC)((double)dst[x] + src[x]); dst[x] = v; mcomp = fmaxf(mcomp, fabsf((float)v)); } }
-        else { for (int x = lane; x < n; x += kWave) { const ACC v = (ACC)src[x]; dst[x] = v; mcomp = fmaxf(mcomp, fabsf((float)v)); } }
+        for (int x = lane; x < n; x += kWave) { const ACC v = (ACC)src[x]; dst[x] = v; mcomp = fmaxf(mcomp, fabsf((float)v)); }
     }
     if (MODE == MODE_OFFSETS && omax2 != nullptr) {
         // largest |offset|^2 of the tile as float bits, bounded by 3 max|component|^2 (zeroed with the binning counters)

@@ -3,8 +3,7 @@
 // written for "narrow" discs (no pole inside, every pixel within 0.40 rad of the halo's azimuth); a chunk that lists a WIDE disc
 // (a pole inside, very low redshift: a handful of halos in a full-sky catalog) takes a second copy of the row and pair phases
 // with the generic kernel's row spans and full-range sin / cos (k1_chunk, rows_and_pairs).  Property-axis tables and non-uniform
-// radial axes stay on the generic tile kernel of bfgx_kernels.hpp (which, with BFGX_K1_WIDE=0, also takes the wide discs in a
-// "wide pass" that adds into the stored tiles: the arrangement up to round 4, kept for the tests).
+// radial axes stay on the generic tile kernel of bfgx_kernels.hpp, which then takes every halo of the plan.
 //
 // One 512-thread workgroup owns one tile (BR rings x <= W pixels) of the output: its accumulators are fp64 planes in LDS
 // (one plane per component, so that consecutive pixels hit consecutive banks), every pixel is stored exactly once.
@@ -823,17 +822,15 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
     }
     __syncthreads();
 
-    // the narrow halos of the tile: region A = the tile's fixed-capacity list K0 filled directly (entries_a[tile][cap_a]; without it: the
-    // head of the shared list), region B = discs over more than kRefMax tiles and what did not fit A, at tile_start in the shared list
+    // the halos of the tile: region A = the tile's fixed-capacity list K0 filled directly (entries_a[tile][cap_a], padded counters),
+    // region B = discs over more than kRefMax tiles and what did not fit A, at tile_start in the shared list
     const int64_t e0 = tile_start[tile];
-    const int na = entries_a ? min(cnt_a[(int64_t)tile * cnt_pad], cap_a) : cnt_a[tile];      // (direct placement: padded counters)
-    const int32_t *ea = entries_a ? entries_a + (int64_t)tile * cap_a : entries + e0;
-    const int64_t eb0 = e0 + (entries_a ? 0 : na);
+    const int na = min(cnt_a[(int64_t)tile * cnt_pad], cap_a);
+    const int32_t *ea = entries_a + (int64_t)tile * cap_a;
     int64_t nb64 = cnt_b[tile];
-    if (eb0 + nb64 > capacity) nb64 = capacity > eb0 ? capacity - eb0 : 0;
-    if (!entries_a && e0 + na > capacity) nb64 = 0;
-    const int32_t *eb = entries + eb0;
-    const int ne = (!entries_a && e0 + na > capacity) ? (int)(capacity > e0 ? capacity - e0 : 0) : na + (int)nb64;
+    if (e0 + nb64 > capacity) nb64 = capacity > e0 ? capacity - e0 : 0;
+    const int32_t *eb = entries + e0;
+    const int ne = na + (int)nb64;
     // entries per chunk: at most kChunk2, fewer when the tile's list is short, so that every wave of the workgroup gets a chunk (a
     // large-NSIDE tile lists ~20 halos with hundreds of pixels each: in chunks of 16 entries two of the eight waves did all the
     // work).  One chunk per wave measured best (NSIDE 2048: K1 1.91 -> 1.56 ms, 8192: 56.8 -> 24.0 ms; 16 or 32 chunks per tile pack worse)
@@ -889,7 +886,7 @@ tile_scatter2_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict__
             for (int x = lane; x < n; x += kWave) dst[x] = (ACC)src[(x + rot) & wmask];
         }
     }
-    if (MODE == MODE_OFFSETS && omax2 != nullptr) {      // (the array was zeroed with the binning counters; the wide pass may raise it)
+    if (MODE == MODE_OFFSETS && omax2 != nullptr) {      // (the array was zeroed with the binning counters)
 #pragma unroll
         for (int sft = kWave >> 1; sft > 0; sft >>= 1) om2 = fmaxf(om2, __shfl_down(om2, sft, kWave));
         if (lane == 0 && om2 > 0.0f) atomicMax(omax2 + tile, __float_as_uint(om2 * 1.000001f));
@@ -997,15 +994,13 @@ tile_scatter2f_kernel(Tab8T<real> tb, Hpx h, Tiling T, const RowRec *__restrict_
             d.tj = tile - T.band_tile0[d.band];
             // (the same list arithmetic as tile_scatter2_kernel: region A = the tile's fixed-capacity list, region B in the shared list)
             const int64_t e0 = tile_start[tile];
-            const int na = entries_a ? min(cnt_a[(int64_t)tile * cnt_pad], cap_a) : cnt_a[tile];      // (direct placement: padded counters)
-            d.ea = entries_a ? entries_a + (int64_t)tile * cap_a : entries + e0;
-            const int64_t eb0 = e0 + (entries_a ? 0 : na);
+            const int na = min(cnt_a[(int64_t)tile * cnt_pad], cap_a);
+            d.ea = entries_a + (int64_t)tile * cap_a;
             int64_t nb64 = cnt_b[tile];
-            if (eb0 + nb64 > capacity) nb64 = capacity > eb0 ? capacity - eb0 : 0;
-            if (!entries_a && e0 + na > capacity) nb64 = 0;
+            if (e0 + nb64 > capacity) nb64 = capacity > e0 ? capacity - e0 : 0;
             d.na = na;
-            d.ne = (!entries_a && e0 + na > capacity) ? (int)(capacity > e0 ? capacity - e0 : 0) : na + (int)nb64;
-            d.eb = entries + eb0;
+            d.ne = na + (int)nb64;
+            d.eb = entries + e0;
         }
         return d;
     };

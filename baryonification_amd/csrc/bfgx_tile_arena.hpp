@@ -1,15 +1,12 @@
 // bfgx_tile_arena.hpp -- the counter arena of the shell plan (host code only): the ONE device allocation that holds everything a step
 // resets, and the one place where its layout is written down.  In 32-bit words from the base:
 //
-//   cnt_a_pad     ntiles * cnt_pad, rounded up to 4   region A's counters, cnt_pad words apart (see wave_run_issue)
-//   cnt_a         ntiles + 1     } counts of a tile's narrow-A, narrow-B and wide entries (K0)
-//   cnt_b         ntiles + 1     }
-//   cnt_w         ntiles + 1     }
-//   cur_b         ntiles + 1     } cursors of the placement pass; adjacent: ensure_entry_capacity resets both with one memset
-//   cur_w         ntiles + 1     }
+//   cnt_a_pad     ntiles * cnt_pad, rounded up to 4   counters of the tiles' fixed lists entries_a[tile][cap_a] (K0 places the few-tile halos
+//                                of a fast plan there itself), cnt_pad words apart (see wave_run_issue)
+//   cnt_b         ntiles + 1     entries of every tile in the shared list (K0): what did not fit the fixed list, halos over more than
+//                                kRefMax tiles, and every halo of a generic plan
+//   cur_b         ntiles + 1     cursors of the placement pass (ensure_entry_capacity resets them for a second pass)
 //   tile_counter  1              the counter the persistent K1 / K3 grids draw their tiles from
-//   zeros         ntiles         zeroed with the rest and NEVER written: the scan, the placement pass and the wide pass read them as
-//                                a cnt_a of zeros (the shared entry list holds only the regions [B | wide] of a tile)
 //   omax          ntiles + 1     largest |offset|^2 of every tile (K1's flush or tile_reach_kernel): the reach of the gathering regrid
 //   (rounded up to 4 words)
 //   ctrl          4              RegridCtrl: entries of the far list, overflow of the full-map regrid, tiles left to the walking kernel
@@ -42,8 +39,8 @@ constexpr size_t round_up4(size_t words) { return (words + 3) & ~(size_t)3; }
 
 // word offsets of the regions from the base, and the lengths the host needs
 struct TileArenaLayout {
-    size_t cnt_a_pad, cnt_a, cnt_b, cnt_w, cur_b, cur_w, tile_counter, zeros, omax, ctrl, far_overflow_full, todo, todo_list, band_overflow;
-    size_t cursor_words;     // cur_b and cur_w together
+    size_t cnt_a_pad, cnt_b, cur_b, tile_counter, omax, ctrl, far_overflow_full, todo, todo_list, band_overflow;
+    size_t cursor_words;     // cur_b
     size_t zeroed_words;     // the per-step memset: [base, end of ctrl)
     size_t tail_words;       // ctrl and everything behind it (zeroed once, at plan creation)
     size_t total_words;
@@ -54,15 +51,11 @@ constexpr TileArenaLayout tile_arena_layout(size_t ntiles, size_t cnt_pad)
     const size_t blk = ntiles + 1;
     TileArenaLayout L{};
     L.cnt_a_pad = 0;
-    L.cnt_a = round_up4(ntiles * cnt_pad);
-    L.cnt_b = L.cnt_a + blk;
-    L.cnt_w = L.cnt_b + blk;
-    L.cur_b = L.cnt_w + blk;
-    L.cur_w = L.cur_b + blk;
-    L.tile_counter = L.cur_w + blk;
-    L.zeros = L.tile_counter + 1;
-    L.omax = L.zeros + ntiles;
-    L.ctrl = L.cnt_a + round_up4(L.omax + blk - L.cnt_a);
+    L.cnt_b = round_up4(ntiles * cnt_pad);
+    L.cur_b = L.cnt_b + blk;
+    L.tile_counter = L.cur_b + blk;
+    L.omax = L.tile_counter + 1;
+    L.ctrl = L.cnt_b + round_up4(L.omax + blk - L.cnt_b);
     L.far_overflow_full = L.ctrl + offsetof(RegridCtrl, far_overflow_full) / sizeof(int32_t);
     L.todo = L.ctrl + offsetof(RegridCtrl, todo_count) / sizeof(int32_t);
     L.todo_list = L.ctrl + kCtrlWords;
@@ -77,9 +70,8 @@ constexpr TileArenaLayout tile_arena_layout(size_t ntiles, size_t cnt_pad)
 // the arena as the launches see it
 struct TileArena {
     int32_t *base = nullptr;           // == cnt_a_pad: what the step's memset starts at
-    int32_t *cnt_a_pad = nullptr, *cnt_a = nullptr, *cnt_b = nullptr, *cnt_w = nullptr, *cur_b = nullptr, *cur_w = nullptr;
+    int32_t *cnt_a_pad = nullptr, *cnt_b = nullptr, *cur_b = nullptr;
     unsigned int *tile_counter = nullptr;
-    int32_t *zeros = nullptr;
     float *omax = nullptr;
     RegridCtrl *ctrl = nullptr;
     int32_t *far_overflow_full = nullptr;
@@ -90,9 +82,8 @@ struct TileArena {
     void bind(int32_t *b, const TileArenaLayout &L)
     {
         base = b;
-        cnt_a_pad = b + L.cnt_a_pad; cnt_a = b + L.cnt_a; cnt_b = b + L.cnt_b; cnt_w = b + L.cnt_w; cur_b = b + L.cur_b; cur_w = b + L.cur_w;
+        cnt_a_pad = b + L.cnt_a_pad; cnt_b = b + L.cnt_b; cur_b = b + L.cur_b;
         tile_counter = (unsigned int *)(b + L.tile_counter);
-        zeros = b + L.zeros;
         omax = (float *)(b + L.omax);
         ctrl = (RegridCtrl *)(b + L.ctrl);
         far_overflow_full = b + L.far_overflow_full;
@@ -104,22 +95,21 @@ struct TileArena {
     }
 };
 
-// the list of tiles with wide entries ([0] = their number) and, behind it, the scratch of the multi-workgroup tile scan: one total and
-// one offset per scan block (tile_scan_part_kernel, tile_scan_blocks_kernel; the launch takes that route up to 1024 blocks)
-constexpr size_t kScanBlocksRoom = 2048;
-struct WideTilesLayout { size_t list, block_tot, block_off, total_words; };
-constexpr WideTilesLayout wide_tiles_layout(size_t ntiles)
+// the scratch of the multi-workgroup tile scan: one total and one offset per scan block (tile_scan_part_kernel, tile_scan_blocks_kernel;
+// the launch takes that route up to 1024 blocks)
+constexpr size_t kScanBlocksRoom = 1024;
+struct ScanScratchLayout { size_t block_tot, block_off, total_words; };
+constexpr ScanScratchLayout scan_scratch_layout()
 {
-    WideTilesLayout L{};
-    L.list = 0;
-    L.block_tot = ntiles + 1;
+    ScanScratchLayout L{};
+    L.block_tot = 0;
     L.block_off = L.block_tot + kScanBlocksRoom;
     L.total_words = L.block_off + kScanBlocksRoom;
     return L;
 }
-struct WideTiles {
-    int32_t *list = nullptr, *block_tot = nullptr, *block_off = nullptr;
-    void bind(int32_t *b, const WideTilesLayout &L) { list = b + L.list; block_tot = b + L.block_tot; block_off = b + L.block_off; }
+struct ScanScratch {
+    int32_t *block_tot = nullptr, *block_off = nullptr;
+    void bind(int32_t *b, const ScanScratchLayout &L) { block_tot = b + L.block_tot; block_off = b + L.block_off; }
 };
 
 // ---- the facts the kernels and the launches rely on, checked where the layout is computed
@@ -128,14 +118,13 @@ struct TileArenaCheck {
     static constexpr TileArenaLayout L = tile_arena_layout(NT, PAD);
     static constexpr size_t blk = NT + 1;
     static constexpr bool unrounded = (NT * PAD) % 4 == 0;
-    static constexpr size_t n7p = (7 * blk + 3) & ~(size_t)3;      // the seven blocks of ntiles + 1 words, rounded up to four words
+    static constexpr size_t n3p = round_up4(3 * blk + 1);          // the three blocks of ntiles + 1 words and the tile counter, rounded up to four words
     // regions in the documented order, none overlapping the next
-    static_assert(L.cnt_a_pad == 0 && L.cnt_a >= NT * PAD, "the padded counters start the arena and hold ntiles * cnt_pad words");
-    static_assert(L.cnt_b == L.cnt_a + blk && L.cnt_w == L.cnt_b + blk && L.cur_b == L.cnt_w + blk, "cnt_a, cnt_b, cnt_w: ntiles + 1 words each");
-    static_assert(L.cur_w == L.cur_b + blk && L.cursor_words == 2 * blk && L.tile_counter == L.cur_b + L.cursor_words,
-                  "cur_b and cur_w are adjacent and nothing else lies in their span");
-    static_assert(L.zeros == L.tile_counter + 1 && L.omax == L.zeros + NT, "ntiles zero words follow the tile counter and precede the |offset|^2 block");
-    static_assert(L.ctrl >= L.omax + blk && L.ctrl - (L.omax + blk) < 4, "the control words follow the seven blocks, rounded up to four words");
+    static_assert(L.cnt_a_pad == 0 && L.cnt_b >= NT * PAD, "the padded counters start the arena and hold ntiles * cnt_pad words");
+    static_assert(L.cur_b == L.cnt_b + blk && L.cursor_words == blk && L.tile_counter == L.cur_b + L.cursor_words,
+                  "cnt_b and cur_b: ntiles + 1 words each, and nothing else lies in the cursors' span");
+    static_assert(L.omax == L.tile_counter + 1, "the |offset|^2 block follows the tile counter");
+    static_assert(L.ctrl >= L.omax + blk && L.ctrl - (L.omax + blk) < 4, "the control words follow the three blocks and the tile counter, rounded up to four words");
     static_assert(L.far_overflow_full == L.ctrl + 2 && L.todo == L.ctrl + 3 && L.todo_list == L.todo + 1, "count (64 bits), overflow, todo count, todo tiles");
     static_assert(L.band_overflow == L.todo_list + NT && L.total_words > L.band_overflow, "the banded overflow flag follows the todo tiles, inside the allocation");
     // the step's memset
@@ -145,9 +134,9 @@ struct TileArenaCheck {
     static_assert(L.ctrl % 2 == 0, "RegridCtrl's 64-bit counter is 8-byte aligned (the base is a device allocation)");
     static_assert(L.tail_words == L.total_words - L.ctrl && L.tail_words == NT + 8, "plan creation zeroes the control words and all behind them");
     // packed: the padded region holds exactly ntiles * cnt_pad words wherever that is a multiple of four, and the lengths follow from it
-    static_assert(L.cnt_a == round_up4(NT * PAD) && (!unrounded || L.cnt_a == NT * PAD), "only a padded region that is no multiple of four words is rounded up");
-    static_assert(L.tile_counter == L.cnt_a + 5 * blk && L.omax == L.cnt_a + 6 * blk && L.ctrl == L.cnt_a + n7p, "the seven blocks");
-    static_assert(L.zeroed_words == L.cnt_a + n7p + 4 && L.total_words == L.cnt_a + n7p + NT + 8, "lengths of the memset and of the allocation");
+    static_assert(L.cnt_b == round_up4(NT * PAD) && (!unrounded || L.cnt_b == NT * PAD), "only a padded region that is no multiple of four words is rounded up");
+    static_assert(L.tile_counter == L.cnt_b + 2 * blk && L.omax == L.cnt_b + 2 * blk + 1 && L.ctrl == L.cnt_b + n3p, "the three blocks, the tile counter between the second and the third");
+    static_assert(L.zeroed_words == L.cnt_b + n3p + 4 && L.total_words == L.cnt_b + n3p + NT + 8, "lengths of the memset and of the allocation");
     static constexpr bool ok = true;
 };
 // one scan block (NSIDE 1, 2, 8, 16), the benchmark's NSIDE 1024, NSIDE 4096 and 8192 with their narrower padding, and two tilings
@@ -156,7 +145,7 @@ static_assert(TileArenaCheck<1, 32>::ok && TileArenaCheck<2, 32>::ok && TileAren
               TileArenaCheck<6208, 32>::ok && TileArenaCheck<98560, 8>::ok && TileArenaCheck<393728, 2>::ok &&
               TileArenaCheck<3, 1>::ok && TileArenaCheck<12289, 1>::ok, "tile arena layout");
 
-static_assert(wide_tiles_layout(24704).block_tot == 24705 && wide_tiles_layout(24704).block_off == 24705 + 2048 &&
-              wide_tiles_layout(24704).total_words == 24704 + 1 + 4096, "scan scratch: 2048 totals, then 2048 offsets, behind the wide tile list");
+static_assert(scan_scratch_layout().block_tot == 0 && scan_scratch_layout().block_off == 1024 && scan_scratch_layout().total_words == 2048,
+              "scan scratch: 1024 totals, then 1024 offsets: one word each per scan block");
 
 }  // namespace bfgx

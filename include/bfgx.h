@@ -142,7 +142,7 @@ typedef struct bfgx_stats {
 /* kernel kinds reported by bfgx_plan_timing_read */
 enum { BFGX_K_PREP = 0, BFGX_K_OFFSETS = 1, BFGX_K_REGRID = 2, BFGX_K_PAINT = 3, BFGX_K_SUM = 4, BFGX_K_COUNT = 5,
        BFGX_K_BIN = 6, BFGX_K_WIDE = 7, BFGX_NUM_KERNELS = 8 };
-/* OFFSETS / PAINT: the fast tile kernel (narrow discs); WIDE: the generic tile kernel over the wide discs (polar caps, very low z) */
+/* OFFSETS / PAINT: the tile kernel of the plan, fast or generic; WIDE: never recorded (its slot stays in ABI version 4 and reads 0) */
 /* the grid plan reports its kernels under the same kinds: PREP, OFFSETS (halo loop), PAINT, REGRID, SUM */
 
 typedef struct bfgx_plan bfgx_plan;       /* opaque: device, stream, resident model + workspace */

@@ -84,8 +84,8 @@ for c in range(cases):
             pl.status()
             sl.append(t)
         db = (sl[0] - sl[1]).abs().max().item() / scale
-    # (fp32 pix_offsets: each form rounds a pixel once, and the wide pass -- shared -- rounds a polar / low-z tile again at every visit, from
-    # starting values that may differ by an ulp: a few 1e-7 of the scale for catalogs with many wide discs)
+    # (fp32 pix_offsets: each form rounds a pixel once, from fp64 LDS sums in a different order: a few 1e-7 of the scale where hundreds of
+    # wide discs cancel on a pixel)
     # (fp64 sums in a different order: 1e-16 of the partial sums, which near the poles -- hundreds of discs on a pixel, offsets that cancel -- are
     # tens of times the result)
     tol = 1e-13 if paint else (1e-11 if f64 else 1e-6)

@@ -1,6 +1,6 @@
-"""GPU box: randomised cross-check of the two routes of WIDE discs (a pole inside, pixels beyond 0.40 rad of the halo's azimuth, fallback pixels on the
-first rings): through the fast kernel's second copy of the row / pair phases (default) and through the generic kernel's wide pass (BFGX_K1_WIDE=0 at
-plan creation) -- NSIDE, catalog size, tile shape, displacement / paint, fp32 / fp64 pair math, both forms of K1, halos on and around the poles and
+"""GPU box: randomised cross-check of WIDE discs (a pole inside, pixels beyond 0.40 rad of the halo's azimuth, fallback pixels on the first rings)
+through the fast kernel's second copy of the row / pair phases against the generic tile kernel, which a twin plan with the same interpolant on a
+non-uniform ln r axis (one knot more, at the midpoint of an interval) runs for every halo -- NSIDE, catalog size, tile shape, displacement / paint, fp32 / fp64 pair math, both forms of K1, halos on and around the poles and
 discs of 0.05 .. pi rad; the same census, outputs equal to the rounding of the two pair arithmetics.   python3 scripts/stress_wide_discs.py [cases] [seed]"""
 import os
 import sys
@@ -40,10 +40,14 @@ for c in range(cases):
         os.environ['BFGX_TILE_W'] = str(int(rng.choice([16, 32, 64])))
     os.environ['BFGX_K1_FLUID'] = fluid
     plans = []
-    for wide in ('1', '0'):
-        os.environ['BFGX_K1_WIDE'] = wide
-        with np.errstate(divide='ignore'):
-            model, keep = engine.model_from_tables(axes, np.log(table) if paint else table, syn.COSMO, 10.0, 10.0, log_values=paint)
+    with np.errstate(divide='ignore'):
+        values = np.log(table) if paint else table
+    kn = len(r) // 2
+    axes_t = axes[:2] + [np.insert(axes[2], kn + 1, 0.5 * (axes[2][kn] + axes[2][kn + 1]))]
+    with np.errstate(invalid='ignore'):
+        values_t = np.insert(values, kn + 1, 0.5 * (values[..., kn] + values[..., kn + 1]), axis=-1)
+    for ax, v in ((axes, values), (axes_t, values_t)):
+        model, keep = engine.model_from_tables(ax, v, syn.COSMO, 10.0, 10.0, log_values=paint)
         plans.append((engine.ShellPlan(model, keep, nside, N, 0, torch.cuda.current_stream().cuda_stream), keep))
     cols = {kk: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for kk, v in cat.items()}
     cd = _lib.make_catalog_dev(N, cols['M'].data_ptr(), cols['z'].data_ptr(), cols['ra'].data_ptr(), cols['dec'].data_ptr())
@@ -96,7 +100,7 @@ for c in range(cases):
         worst64 = max(worst64, d, db)
     else:
         worst32 = max(worst32, d, db)
-    print("case %2d  nside %4d  N %6d  %s  %s  fluid=%s  poles %3d  big %2d  tile %s x %s  pairs %11d  |fast - pass| / max %.1e  bands [%d, %d) %.1e  %s"
+    print("case %2d  nside %4d  N %6d  %s  %s  fluid=%s  poles %3d  big %2d  tile %s x %s  pairs %11d  |fast - generic| / max %.1e  bands [%d, %d) %.1e  %s"
           % (c, nside, N, 'paint' if paint else 'displ', 'f64' if f64 else 'f32', fluid, k, nbig, os.environ.get('BFGX_TILE_BR', '-'), os.environ.get('BFGX_TILE_W', '-'),
              counts[0], d, b0, b1, db, 'ok' if ok else 'MISMATCH (census %d / %d)' % (counts[0], counts[1])), flush=True)
     for pl, _ in plans:

@@ -343,14 +343,13 @@ def test_fused_baryonify_equals_offsets_then_regrid(gpu):
             pl.baryonify(cd, hmap.data_ptr(), off_b.data_ptr(), out_b.data_ptr(), s_b.data_ptr(), acc_f64=f64)
             torch.cuda.synchronize()
             pl.status()
-            # (K1 adds in LDS with atomics, and the wide pass rounds to the accumulator type once per visit of a tile: the order,
-            # hence the last bits, differ from run to run)
+            # (K1 adds in LDS with atomics: the order, hence the last bits, differ from run to run)
             assert (off_a - off_b).abs().max().item() <= (1e-12 if f64 else 2e-6) * off_a.abs().max().item()
             pix = np.sqrt(4 * np.pi / npix)
             reach = off_a.view(-1, 3).double().norm(dim=1).max().item() / pix
             assert (reach < 0.2) if scale == 1.0 else (2.0 < reach < 40.0), reach
             assert torch.isfinite(out_b).all().item() and np.isclose(s_b[1].item(), s_b[0].item(), rtol=(1e-12 if f64 else 1e-6))
-            # the aprons may differ (K1's bound on |offset| for the few tiles of the wide pass is looser): same deposits, other order
+            # the aprons may differ (K1's bound on |offset| from the largest stored component is looser than K2's own pass): same deposits, other order
             assert (out_a - out_b).abs().max().item() <= (1e-10 if f64 else 1e-5) * max(1.0, reach) * out_a.abs().max().item()
         pl.close()
     plan.close()
@@ -840,14 +839,39 @@ def test_k1_fluid_form_equals_barrier_form(gpu, monkeypatch, paint, f64):
     plan.close(); barrier.close()
 
 
+def _twin_tables(axes, values):
+    """the same interpolant on a NON-uniform ln r axis: one knot more, at the midpoint of an interior interval, whose values are the mean of
+    the two neighbouring nodes (of the array model_from_tables gets: ln(table) for painting).  Linear interpolation is unchanged, but the
+    plan cannot take the fast kernel: the generic tile kernel takes every halo, in fp64."""
+    lr = axes[2]
+    k = len(lr) // 2
+    lr_t = np.insert(lr, k + 1, 0.5 * (lr[k] + lr[k + 1]))
+    return [axes[0], axes[1], lr_t], np.insert(values, k + 1, 0.5 * (values[..., k] + values[..., k + 1]), axis=-1)
+
+
 @pytest.mark.parametrize('f64', [False, True])
 @pytest.mark.parametrize('paint', [False, True])
 def test_wide_discs_in_the_fast_kernel_equal_the_wide_pass(gpu, monkeypatch, paint, f64):
     """wide discs -- a pole inside, pixels further than 0.40 rad from the halo's azimuth, the 4 fallback pixels on the first rings -- go
-    through the fast kernel's chunk (general row spans, full-range sin / cos; default) instead of the generic kernel's wide pass
-    (BFGX_K1_WIDE=0 at plan creation).  Same pair census; outputs equal to fp32 / fp64 rounding of the different pair arithmetic.  The catalog
-    holds halos on and around both poles, discs of 0.3 - 2.5 rad (z = 0.0003 .. 0.003: thousands of tiles each), a disc over the whole sphere and
-    tiny discs on the first rings, among 2e5 ordinary ones; both forms of the fast kernel."""
+    through the fast kernel's chunk (general row spans, full-range sin / cos) and must equal what the generic tile kernel, whose row and
+    pair code for such discs is the older one, gives for the same interpolant on a TWIN plan (_twin_tables: fp64 throughout).  Same pair
+    census; outputs equal to fp32 / fp64 rounding of the different pair arithmetic.  The catalog holds halos on and around both poles,
+    discs of 0.3 - 2.5 rad (z = 0.0003 .. 0.003: thousands of tiles each), a disc over the whole sphere and tiny discs on the first rings,
+    among 2e5 ordinary ones; both forms of the fast kernel.
+
+    (The name is from when the comparison was the generic kernel's WIDE PASS, which revisited the tiles with wide entries after the fast
+    kernel; that pass is gone, its row and pair code is what the twin plan runs.)
+
+    fp32 bounds, from max |difference| / scale measured on the last commit that had the wide pass (default route, wide-pass route and twin
+    side by side, two runs each, the same to three digits):
+                                         displacement (fp32)   painting (fp32 pairs, fp64 map)
+      wide discs alone: default - pass        1.08e-6               2.19e-7       <= 1.5e-6, so the old 3e-6 stays for default - twin
+                        default - twin        6.95e-7               2.22e-7
+                        pass - twin           8.50e-7               1.94e-7
+      full catalog:     default - pass        1.08e-6               2.19e-7
+                        default - twin        6.95e-7               9.05e-7       bound: twice that (fp32 results move with the order
+                        pass - twin           8.50e-7               9.27e-7       of the LDS additions): 1.39e-6 / 1.81e-6
+    fp64: 1.6e-12 / 1.3e-12 against the twin on the full catalog; 1e-10 stays."""
     import torch
     from baryonification_amd import _lib, engine, synthetic as syn
     N, nside = 200_000, 512
@@ -865,42 +889,48 @@ def test_wide_discs_in_the_fast_kernel_equal_the_wide_pass(gpu, monkeypatch, pai
     z, M, r = syn.table_grid(cat, pad=1e-9)
     table = syn.paint_table(z, M, r) if paint else syn.displacement_table(z, M, r)
     axes = [np.log(1 + z), np.log(M), np.log(r)]
+    values = np.log(table) if paint else table
     dev = torch.device('cuda', 0)
     npix = 12 * nside * nside
     cd, keep1 = _cat_dev(torch, _lib, dev, cat)
+    cd_wide, keep2 = _cat_dev(torch, _lib, dev, cat, idx=np.arange(k + 12))         # the wide discs alone
     keeps = []
 
-    def make_plan():
-        model, keep = engine.model_from_tables(axes, np.log(table) if paint else table, syn.COSMO, 10.0, 10.0, log_values=paint)
+    def make_plan(ax, v):
+        model, keep = engine.model_from_tables(ax, v, syn.COSMO, 10.0, 10.0, log_values=paint)
         keeps.append(keep)
         return engine.ShellPlan(model, keep, nside, N, 0, torch.cuda.current_stream().cuda_stream)
 
-    plan = make_plan()
-    monkeypatch.setenv('BFGX_K1_WIDE', '0')
-    passed = make_plan()
-    monkeypatch.delenv('BFGX_K1_WIDE')
+    plan = make_plan(axes, values)
+    twin = make_plan(*_twin_tables(axes, values))
+    assert plan.precision(_lib.ACC_PARITY)[0] == _lib.ACC_PARITY and twin.precision(_lib.ACC_PARITY)[0] == _lib.ACC_F64    # fast / generic kernel
     monkeypatch.setenv('BFGX_K1_FLUID', '0')
-    barrier = make_plan()
+    barrier = make_plan(axes, values)
     monkeypatch.delenv('BFGX_K1_FLUID')
 
-    def full(pl):
+    def full(pl, c=cd):
         out = torch.zeros(npix * (1 if paint else 3), dtype=torch.float64 if (paint or f64) else torch.float32, device=dev)
         if paint:
-            pl.paint(cd, out.data_ptr(), acc_f64=(1 if f64 else 2))
+            pl.paint(c, out.data_ptr(), acc_f64=(1 if f64 else 2))
         else:
-            pl.offsets(cd, out.data_ptr(), f64)
+            pl.offsets(c, out.data_ptr(), f64)
         torch.cuda.synchronize()
         pl.status()
         return out
 
-    a, b, c = full(plan), full(passed), full(barrier)
+    a, b, c = full(plan), full(twin), full(barrier)
     scale = b.abs().max().item()
-    tol = 1e-10 if f64 else 3e-6          # (fp32 pair math in both, arranged differently; fp64: the two routes' libm-free / libm trigonometry)
+    tol = 1e-10 if f64 else 3e-6          # (fp32 pair math arranged differently; fp64: the two routes' libm-free / libm trigonometry)
+    tol_full = 1e-10 if f64 else (2 * 9.05e-7 if paint else 2 * 6.95e-7)
     assert scale > 0
-    assert (a - b).abs().max().item() <= tol * scale, ((a - b).abs().max().item(), scale)
-    assert (c - b).abs().max().item() <= tol * scale
-    n_wide = passed.count_pairs(cd, not paint)
-    assert plan.count_pairs(cd, not paint) == n_wide == barrier.count_pairs(cd, not paint) > 2e6
+    err_wide = (full(plan, cd_wide) - full(twin, cd_wide)).abs().max().item()
+    err_full, err_form = (a - b).abs().max().item(), (c - a).abs().max().item()
+    print('wide discs alone %.3e, full catalog %.3e, barrier form vs default %.3e (of scale)' % (err_wide / scale, err_full / scale, err_form / scale))
+    assert err_wide <= tol * scale, (err_wide, scale)
+    assert err_full <= tol_full * scale, (err_full, scale)
+    assert err_form <= tol * scale
+    n_twin = twin.count_pairs(cd, not paint)
+    assert plan.count_pairs(cd, not paint) == n_twin == barrier.count_pairs(cd, not paint) > 2e6
     # band-restricted passes (what a rank of a spatially sharded run computes): the polar bands, a belt, the cap / belt boundary
     bounds = plan.bands()
     nb = len(bounds) - 1
@@ -908,7 +938,7 @@ def test_wide_discs_in_the_fast_kernel_equal_the_wide_pass(gpu, monkeypatch, pai
     for b0, b1 in ((0, 2), (nb - 1, nb), (nb // 2 - 1, nb // 2 + 2), (nb // 4, nb // 4 + 3)):
         p0, p1 = int(bounds[b0]), int(bounds[b1])
         got = []
-        for pl in (plan, passed):
+        for pl in (plan, twin):
             sl = torch.full(((p1 - p0) * comp,), 7.0, dtype=a.dtype, device=dev)
             if paint:
                 pl.paint_bands(cd, b0, b1, sl.data_ptr(), acc_f64=(1 if f64 else 2))
@@ -917,9 +947,72 @@ def test_wide_discs_in_the_fast_kernel_equal_the_wide_pass(gpu, monkeypatch, pai
             torch.cuda.synchronize()
             pl.status()
             got.append(sl)
-        assert (got[0] - got[1]).abs().max().item() <= tol * scale
+        assert (got[0] - got[1]).abs().max().item() <= tol_full * scale
         assert (got[0] - a[p0 * comp:p1 * comp]).abs().max().item() <= tol * scale
-    plan.close(); passed.close(); barrier.close()
+    plan.close(); twin.close(); barrier.close()
+
+
+def _fast_and_twin_plans(torch, engine, syn, cat, nside, **grid):
+    z, M, r = syn.table_grid(cat, pad=1e-9, **grid)
+    axes, table = [np.log(1 + z), np.log(M), np.log(r)], syn.displacement_table(z, M, r)
+    plans = []
+    for ax, v in ((axes, table), _twin_tables(axes, table)):
+        model, keep = engine.model_from_tables(ax, v, syn.COSMO, 10.0, 10.0)
+        plans.append((engine.ShellPlan(model, keep, nside, cat['M'].size, 0, torch.cuda.current_stream().cuda_stream), keep))
+    return plans
+
+
+def _tiled_equals_per_halo(torch, _lib, dev, plans, cat, nside):
+    """fp64 pix_offsets of the tile-owned path (algo 1) against the per-halo path (algo 0) within 2e-14 absolute; the same pair census"""
+    cd, cols = _cat_dev(torch, _lib, dev, cat)
+    kinds = []
+    for plan, keep in plans:
+        got = []
+        for algo in (0, 1):
+            off = torch.zeros(12 * nside * nside * 3, dtype=torch.float64, device=dev)
+            plan.set_algo(algo)
+            plan.offsets(cd, off.data_ptr(), True)
+            torch.cuda.synchronize()
+            plan.status()
+            got.append((off, plan.count_pairs(cd, True)))
+        plan.set_algo(1)
+        kinds.append(plan.precision(_lib.ACC_PARITY)[0])
+        err = (got[0][0] - got[1][0]).abs().max().item()
+        print('algo 1 - algo 0: %.3e, pairs %d' % (err, got[1][1]))
+        assert got[0][0].abs().max().item() > 0 and err <= 2e-14
+        assert got[0][1] == got[1][1] > 0
+        del got
+        plan.close()
+    assert kinds == [_lib.ACC_PARITY, _lib.ACC_F64]          # the fast kernel, then the generic one
+
+
+def test_generic_plan_lists_are_placed_by_cursor(gpu):
+    """a generic plan (here: a non-uniform ln r axis) lists every halo in the tiles' shared lists: halos over at most kRefMax tiles with
+    slot -1, the others through the tile enumeration, all placed by the one cursor of the placement pass.  Four halos within 1e-7 .. 1
+    degree of the poles and two discs over more than kRefMax tiles among 3000; the same on the fast plan of the uniform table"""
+    import torch
+    from baryonification_amd import _lib, engine, synthetic as syn
+    N, nside = 3000, 32
+    cat = syn.make_catalog(N, seed=321)
+    cat['dec'][:4] = [90.0 - 1e-7, -90.0 + 1e-3, 89.0, -89.9]
+    cat['ra'][:4] = [0.0, 123.0, 359.9999, 1e-9]
+    cat['z'][4:6] = [0.01, 0.008]
+    cat['M'][4:6] = 3e15
+    cat['dec'][4:6] = [12.0, -47.0]
+    plans = _fast_and_twin_plans(torch, engine, syn, cat, nside)
+    _tiled_equals_per_halo(torch, _lib, torch.device('cuda', 0), plans, cat, nside)
+
+
+def test_tile_scan_over_several_workgroups(gpu):
+    """above 8192 tiles the scan of the tiles' entry counts is spread over workgroups (block totals, their scan, block offsets): NSIDE 2048
+    with its 24 704 tiles is the smallest default tiling that takes it.  2000 halos, the two poles among them; a fast and a generic plan"""
+    import torch
+    from baryonification_amd import _lib, engine, synthetic as syn
+    N, nside = 2000, 2048
+    cat = syn.make_catalog(N, seed=654)
+    cat['dec'][:2] = [90.0 - 1e-7, -90.0 + 1e-7]
+    plans = _fast_and_twin_plans(torch, engine, syn, cat, nside)
+    _tiled_equals_per_halo(torch, _lib, torch.device('cuda', 0), plans, cat, nside)
 
 
 def test_catalog_written_patch_by_patch_equals_shuffled(gpu):

@@ -196,13 +196,17 @@ def test_invalid_halos_are_ignored(gpu):
         assert np.isfinite(out).all() and np.abs(out - ref).max() <= 1e-12 * np.abs(ref).max()
 
 
-def test_entry_list_regrowth(gpu, monkeypatch):
-    """a deliberately tiny halo->tile entry list must be regrown (one-shot API) or reported (resident API)"""
-    g = load_golden('lowz_baryonify')
+@pytest.mark.parametrize('name', ['lowz_baryonify', 'param1_paint'])
+def test_entry_list_regrowth(gpu, monkeypatch, name):
+    """a deliberately tiny halo->tile entry list must be regrown (one-shot API; the fast kernel's plan and, with a property axis, the
+    generic kernel's) or reported (resident API)"""
+    g = load_golden(name)
     ref = run(g, True, 1)
     monkeypatch.setenv('BFGX_ENTRY_CAP', '64')
     out = run(g, True, 1)                                   # host API: overflow -> exact regrowth -> same answer
     assert np.abs(out - ref).max() <= 1e-12 * np.abs(ref).max()
+    if g['p_keys']:
+        return
     import torch
     from baryonification_amd import _lib, engine
     axes = [np.log(1 + g['tab_z']), np.log(g['tab_M']), np.log(g['tab_r'])]
