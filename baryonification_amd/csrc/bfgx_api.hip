@@ -34,6 +34,7 @@
 #include "bfgx_grid.hpp"
 #include "bfgx_grid_pairs.hpp"
 #include "bfgx_fft.hpp"
+#include "bfgx_bispec.hpp"
 #include "bfgx_deposit.hpp"
 #include "bfgx_snapshot.hpp"
 #include "bfgx_snapshot_pairs.hpp"
@@ -2106,6 +2107,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 // ------------------------------------------------------------------------------ regular-grid path (8f-1)
 #include "bfgx_grid_api.inc"
 
+// bispectrum of gridded 3-D maps: inverse slab transforms, k-shell fields, triangle sums
+#include "bfgx_bispec_api.inc"
+
 // ------------------------------------------------------------------------------ particle snapshots (8f-2)
 #include "bfgx_snapshot_api.inc"
 
@@ -2147,6 +2151,7 @@ extern "C" void bfgx_cache_clear(void)
     g_shells.clear();            // plans + device buffers of the one-shot shell entries
     dep_release_all();           // workspace of the tiled particle deposit (bfgx_grid_api.inc)
     fft_release_all();           // twiddle / wavenumber tables of the power spectrum
+    bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries
     g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
     deprec_release_all();        // device buffers of the deposit's records entry

@@ -400,6 +400,109 @@ def power_spectrum(Map, Lbox, Nk=180, device=0):
     return kc, pk, cnt
 
 
+def fft_slab_axis0_device(work_ptr, n_grid, ncols, inverse=0, device=0, stream=0):
+    """in-place complex transforms along the first axis of work [n][ncols][fft_pitch(n)]; inverse: exponent +i, unnormalised"""
+    _lib.check(_lib.load().bfgx_fft_slab_axis0_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), int(ncols),
+                                                     C.c_void_p(int(work_ptr)), int(inverse)))
+
+
+def ifft_slab_planes_device(work_ptr, n_grid, planes, map_out_ptr, device=0, stream=0):
+    """the inverse of fft_slab_planes_device, unnormalised: complex work [planes][n][fft_pitch(n)] -> real map_out [planes][n][n];
+    work is scratch afterwards"""
+    _lib.check(_lib.load().bfgx_ifft_slab_planes_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), int(planes),
+                                                       C.c_void_p(int(work_ptr)), C.c_void_p(int(map_out_ptr))))
+
+
+def bispectrum_work_doubles(n_grid, nbins):
+    """doubles of scratch bispectrum_device needs (two half spectra, nbins real fields, partial sums); 0 outside the limits"""
+    return int(_lib.load().bfgx_bispectrum_work_doubles(int(n_grid), int(nbins)))
+
+
+def bispectrum_shell_fields_device(spec_ptr, n_grid, L, k_edges, unit, scratch_spec_ptr, fields_ptr, device=0, stream=0):
+    """fields [nbins][n][n][n] = the unnormalised inverse transforms of the half spectrum spec [n][n][fft_pitch(n)] restricted to each
+    k-bin (unit: of a spectrum of ones); scratch_spec: another half spectrum"""
+    e = _lib.f8(k_edges)
+    _lib.check(_lib.load().bfgx_bispectrum_shell_fields_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), float(L), e.size - 1,
+                                                              e.ctypes.data, C.c_void_p(int(spec_ptr)), int(unit),
+                                                              C.c_void_p(int(scratch_spec_ptr)), C.c_void_p(int(fields_ptr))))
+
+
+def bispectrum_device(map_ptr, n_grid, L, k_edges, triangles, work_ptr, b_sum_ptr, n_tri_ptr, pk_sum_ptr, n_modes_ptr, device=0, stream=0):
+    """FFT bispectrum estimator on a device-resident map: b_sum[ntri], n_tri[ntri], pk_sum[nbins], n_modes[nbins] (device arrays);
+    work = bispectrum_work_doubles(n_grid, nbins) doubles of scratch; k_edges and triangles [ntri][3] are host arrays"""
+    e = _lib.f8(k_edges)
+    t = np.ascontiguousarray(triangles, dtype=np.int32)
+    _lib.check(_lib.load().bfgx_bispectrum_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), C.c_void_p(int(map_ptr)), float(L),
+                                                 e.size - 1, e.ctypes.data, t.size // 3, t.ctypes.data, C.c_void_p(int(work_ptr)),
+                                                 C.c_void_p(int(b_sum_ptr)), C.c_void_p(int(n_tri_ptr)), C.c_void_p(int(pk_sum_ptr)),
+                                                 C.c_void_p(int(n_modes_ptr))))
+
+
+BISPECTRUM_MAX_BINS, BISPECTRUM_MAX_TRIANGLES = 32, 8192
+
+
+def bispectrum_triangles(k_edges, kind='all'):
+    """The bin triples i <= j <= l (int32 [ntri][3]) whose bins can hold a closed triangle: k_edges[l] < k_edges[i + 1] + k_edges[j + 1].
+    kind: 'all', 'equilateral' (i = j = l) or 'isosceles' (i = j <= l)."""
+    if kind not in ('all', 'equilateral', 'isosceles'):
+        raise ValueError("bispectrum_triangles: kind must be 'all', 'equilateral' or 'isosceles'")
+    e = _lib.f8(k_edges)
+    nb = e.size - 1
+    out = [(i, j, l) for i in range(nb) for j in range(i, nb) for l in range(j, nb)
+           if e[l] < e[i + 1] + e[j + 1] and (kind == 'all' or (i == j and (kind == 'isosceles' or j == l)))]
+    return np.array(out, dtype=np.int32).reshape(-1, 3)
+
+
+def bispectrum(Map, Lbox, k_edges, triangles='all', normalize=False, device=0):
+    """Bispectrum of a cubic 3-D map in the k-bins k_edges (FFT estimator; units of power_spectrum: the unnormalised fftn, no volume
+    factors, unless normalize).  Map: a numpy array, or a CUDA float64 torch tensor, which is analysed where it lies.  triangles: a kind
+    of bispectrum_triangles or an integer array [ntri][3] of bin indices.  Returns a dict of numpy arrays: k (bin centres), triangles,
+    B = b_sum / n_tri (NaN where no closed triangle exists), n_tri, pk = pk_sum / n_modes (NaN for empty bins), n_modes.
+    normalize: B times L^6 / N^9, pk times L^3 / N^6."""
+    e = _lib.f8(k_edges)
+    if e.ndim != 1 or e.size < 2:
+        raise ValueError("bispectrum needs at least two bin edges")
+    nb = e.size - 1
+    if nb > BISPECTRUM_MAX_BINS:
+        raise ValueError("bispectrum needs 1 <= nbins <= %d" % BISPECTRUM_MAX_BINS)
+    tri = bispectrum_triangles(e, triangles) if isinstance(triangles, str) else np.ascontiguousarray(triangles, dtype=np.int32)
+    if tri.ndim != 2 or tri.shape[1] != 3 or not 1 <= tri.shape[0] <= BISPECTRUM_MAX_TRIANGLES:
+        raise ValueError("bispectrum needs triangles [ntri][3] with 1 <= ntri <= %d" % BISPECTRUM_MAX_TRIANGLES)
+    on_device = hasattr(Map, 'data_ptr') and not isinstance(Map, np.ndarray)
+    if not on_device:
+        Map = _lib.f8(Map)
+    if len(Map.shape) != 3 or len(set(Map.shape)) != 1:
+        raise ValueError("bispectrum needs a cubic 3-D map")
+    N, ntri = int(Map.shape[0]), tri.shape[0]
+    if not on_device:
+        b_sum, n_tri, pk_sum, n_modes = np.empty(ntri), np.empty(ntri), np.empty(nb), np.empty(nb)
+        _lib.check(_lib.load().bfgx_bispectrum(int(device), N, Map.ctypes.data, float(Lbox), nb, e.ctypes.data, ntri, tri.ctypes.data,
+                                              b_sum.ctypes.data, n_tri.ctypes.data, pk_sum.ctypes.data, n_modes.ctypes.data))
+    else:
+        import torch
+        if not Map.is_cuda or Map.dtype != torch.float64:
+            raise ValueError("bispectrum needs a numpy array or a CUDA float64 tensor")
+        Map = Map.contiguous()
+        nw = bispectrum_work_doubles(N, nb)
+        if nw <= 0:
+            raise NotImplementedError("n_grid must be a power of two with 8 <= n_grid <= 1024")
+        work = torch.empty(nw, dtype=torch.float64, device=Map.device)
+        res = torch.empty(2 * ntri + 2 * nb, dtype=torch.float64, device=Map.device)
+        bispectrum_device(Map.data_ptr(), N, Lbox, e, tri, work.data_ptr(), res[:ntri].data_ptr(), res[ntri:2 * ntri].data_ptr(),
+                          res[2 * ntri:2 * ntri + nb].data_ptr(), res[2 * ntri + nb:].data_ptr(), device=Map.device.index or 0,
+                          stream=torch.cuda.current_stream(Map.device).cuda_stream)
+        r = res.cpu().numpy()
+        b_sum, n_tri, pk_sum, n_modes = r[:ntri], r[ntri:2 * ntri], r[2 * ntri:2 * ntri + nb], r[2 * ntri + nb:]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        # (the counts are integers up to the rounding of the transforms: "none" is less than half a triangle)
+        B = np.where(np.abs(n_tri) < 0.5, np.nan, b_sum / n_tri)
+        pk = np.where(np.abs(n_modes) < 0.5, np.nan, pk_sum / n_modes)
+    if normalize:
+        B = B * (float(Lbox) ** 6 / float(N) ** 9)
+        pk = pk * (float(Lbox) ** 3 / float(N) ** 6)
+    return {'k': 0.5 * (e[:-1] + e[1:]), 'triangles': tri, 'B': B, 'n_tri': n_tri, 'pk': pk, 'n_modes': n_modes}
+
+
 def baryonify_snapshot_device(model, halos_dev, part_ptrs, n_part, L, redshift, out_ptrs, device=0, stream=0):
     """BaryonifySnapshot on device-resident columns: part_ptrs / out_ptrs = (x, y[, z]) device pointers.
     Returns the number of displaced (halo, particle) pairs."""

@@ -509,6 +509,41 @@ int  bfgx_fft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, i
 int  bfgx_fft_slab_axis0_pk_device(int device, void *hip_stream, int32_t n_grid, int32_t ncols, int32_t col0, double *work_dev, double L,
                                    int32_t nk, double *pk_sum_dev, double *k_sum_dev, unsigned long long *counts_dev);
 
+/* ---- bispectrum of a gridded 3-D map (FFT estimator of Scoccimarro 2000) ---------------------------------
+ * Units of bfgx_power_spectrum: F = the unnormalised np.fft.fftn(map), no volume factors.  A mode with integer wavevector n (fftfreq(N) N
+ * per axis) has k = 2 pi / L sqrt(n^2) and lies in bin i when k_edges[i] <= k < k_edges[i + 1] (k_edges[nbins + 1] finite, non-negative,
+ * strictly ascending; the rule is evaluated once per n^2 on the host, np.searchsorted(k_edges, k, 'right') - 1; modes outside every bin are
+ * dropped).  With the unnormalised inverse transforms I_i(x) = sum_{k in i} F(k) e^{+ikx} and U_i(x) = sum_{k in i} e^{+ikx}, a triangle
+ * (i, j, l) of bin indices gets
+ *   b_sum = sum_x I_i I_j I_l / N^3 = the sum of F(k1) F(k2) F(k3) over the closed triples k1 + k2 + k3 = 0, k1 in i, k2 in j, k3 in l,
+ *   n_tri = sum_x U_i U_j U_l / N^3 = their number (an integer up to the rounding of the fp64 transforms),
+ * and a bin pk_sum = sum_x I_i^2 / N^3 = sum_{k in i} |F|^2 and n_modes = sum_x U_i^2 / N^3.  B = b_sum / n_tri, P = pk_sum / n_modes.
+ * Limits: n_grid a power of two in [8, 1024] (else BFGX_ERR_UNSUPPORTED), 1 <= nbins <= 32, 1 <= ntri <= 8192.  Results are bitwise
+ * reproducible from call to call (fixed-order sums, no floating-point atomics).  Tables are kept per (device, n_grid, L, k_edges) until
+ * bfgx_cache_clear.  All complex arrays are half spectra with rows of bfgx_fft_pitch(n_grid) values and must be 16-byte aligned. */
+/* in-place complex transforms along the FIRST axis of work [n][ncols][pitch]; inverse != 0: exponent +i, unnormalised.  Pad columns are
+ * transformed as lines of their own. */
+int  bfgx_fft_slab_axis0_device(int device, void *hip_stream, int32_t n_grid, int32_t ncols, double *work_dev, int32_t inverse);
+/* inverse along the middle axis, then complex-to-real along the last: work [planes][n][pitch] -> map_out [planes][n][n], unnormalised
+ * (planes * n even); pad columns are never read, the imaginary parts of the columns 0 and n/2 are ignored as numpy.irfft ignores them;
+ * work is scratch afterwards */
+int  bfgx_ifft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, int32_t planes, double *work_dev, double *map_out_dev);
+/* doubles of scratch bfgx_bispectrum_device needs: two half spectra, nbins real fields, the partial sums of the triangle kernel
+ * (host arithmetic; 0 for sizes outside the limits) */
+int64_t bfgx_bispectrum_work_doubles(int32_t n_grid, int32_t nbins);
+/* the filtered fields alone: spec_dev = the full half spectrum [n][n][pitch] (kept), scratch_spec_dev another one, fields_dev
+ * [nbins][n][n][n]; unit != 0: U_i instead of I_i */
+int  bfgx_bispectrum_shell_fields_device(int device, void *hip_stream, int32_t n_grid, double L, int32_t nbins, const double *k_edges_host,
+                                         const double *spec_dev, int32_t unit, double *scratch_spec_dev, double *fields_dev);
+/* map_dev [n][n][n] -> b_sum_dev[ntri], n_tri_dev[ntri], pk_sum_dev[nbins], n_modes_dev[nbins]; tri_host[ntri][3] bin indices;
+ * work_dev: bfgx_bispectrum_work_doubles(n_grid, nbins) doubles.  Enqueue-only once the tables of (n_grid, L, k_edges) exist. */
+int  bfgx_bispectrum_device(int device, void *hip_stream, int32_t n_grid, const double *map_dev, double L, int32_t nbins,
+                            const double *k_edges_host, int32_t ntri, const int32_t *tri_host, double *work_dev, double *b_sum_dev,
+                            double *n_tri_dev, double *pk_sum_dev, double *n_modes_dev);
+/* the same on host arrays (synchronous) */
+int  bfgx_bispectrum(int device, int32_t n_grid, const double *map_host, double L, int32_t nbins, const double *k_edges, int32_t ntri,
+                     const int32_t *tri, double *b_sum, double *n_tri, double *pk_sum, double *n_modes);
+
 /* ---- particle-snapshot path ----------------------------------------------------------
  * Replaces BaryonifySnapshot.process, BaryonForge/Runners/SnapshotRunner.py:173-262: every particle within
  * R_q = clip(epsilon_max R200c / a, 0, L/2) of a halo (periodic box) moves radially by displacement(d, M, a) * a;
