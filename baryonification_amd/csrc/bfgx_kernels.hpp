@@ -464,39 +464,60 @@ struct DiscSpan {
     double flo, fhi;
 };
 
+// the tiles of ONE band that may hold pixels of a disc without fallback pixels: the cnt azimuth slices (jlo + k) mod nphi, k in [0, cnt).
+// for_each_tile walks the bands of the disc in order and every band's slices in this order; the placement pass indexes the same order.
+struct BandSpan { int32_t t0, nphi, jlo, cnt; };
+__device__ inline BandSpan band_span(const Tiling &T, const DiscSpan &r, int b)
+{
+    BandSpan s;
+    s.nphi = T.band_nphi[b]; s.t0 = T.band_tile0[b];
+    bool all = r.allphi || s.nphi == 1;
+    int jlo = 0, jhi = s.nphi - 1;
+    if (!all) {
+        const double margin = 2.0 * (double)s.nphi / (double)T.band_nrmin[b] + 1e-6;
+        jlo = (int)floor((double)s.nphi * r.flo - margin);
+        jhi = (int)floor((double)s.nphi * r.fhi + margin);
+        if (jhi - jlo + 1 >= s.nphi) { all = true; jlo = 0; jhi = s.nphi - 1; }
+    }
+    s.jlo = jlo; s.cnt = jhi - jlo + 1;
+    return s;
+}
+__device__ inline int band_span_tile(const BandSpan &s, int k)
+{
+    int j = (s.jlo + k) % s.nphi;
+    if (j < 0) j += s.nphi;
+    return s.t0 + j;
+}
+
 // calls f(tile) once for every tile that may hold pixels of the halo's disc (conservative superset)
 template <typename F>
 __device__ inline void for_each_tile(const Hpx &h, const Tiling &T, const DiscSpan &r, F &&f)
 {
     if (r.fb) {
-        int seen[4], ns = 0;
+        // (seen[] is indexed by unrolled selects only, so that it stays in registers: a dynamic index puts it into scratch memory)
+        int seen[4] = {0, 0, 0, 0}, ns = 0;
+#pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int b = (r.fb_ring[q] - 1) / T.BR;
             const int nphi = T.band_nphi[b];
             const int t = T.band_tile0[b] + (int)(((int64_t)r.fb_k[q] * nphi) / ring_len(h, r.fb_ring[q]));
             bool dup = false;
-            for (int i = 0; i < ns; ++i) dup |= (seen[i] == t);
-            if (!dup) { seen[ns++] = t; f(t); }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dup |= (i < ns) && (seen[i] == t);
+            if (!dup) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) seen[i] = (i == ns) ? t : seen[i];
+                ++ns;
+                f(t);
+            }
         }
         return;
     }
     if (r.rlast < r.rfirst) return;
     const int b0 = (r.rfirst - 1) / T.BR, b1 = (r.rlast - 1) / T.BR;
     for (int b = b0; b <= b1; ++b) {
-        const int nphi = T.band_nphi[b], t0 = T.band_tile0[b];
-        bool all = r.allphi || nphi == 1;
-        int jlo = 0, jhi = nphi - 1;
-        if (!all) {
-            const double margin = 2.0 * (double)nphi / (double)T.band_nrmin[b] + 1e-6;
-            jlo = (int)floor((double)nphi * r.flo - margin);
-            jhi = (int)floor((double)nphi * r.fhi + margin);
-            if (jhi - jlo + 1 >= nphi) { all = true; jlo = 0; jhi = nphi - 1; }
-        }
-        for (int jj = jlo; jj <= jhi; ++jj) {
-            int j = jj % nphi;
-            if (j < 0) j += nphi;
-            f(t0 + j);
-        }
+        const BandSpan s = band_span(T, r, b);
+        for (int k = 0; k < s.cnt; ++k) f(band_span_tile(s, k));
     }
 }
 
@@ -787,7 +808,12 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
         for (int q = 0; q < 4; ++q) { ds.fb_ring[q] = r.fb_ring[q]; ds.fb_k[q] = r.fb_k[q]; }
         int tl[kRefMax] = {0, 0, 0, 0};
         int nt = 0;
-        if (cls != kClsNone) for_each_tile(h, T, ds, [&](int t) { if (nt < kRefMax) tl[nt] = t; ++nt; });
+        // (tl[] takes its tiles through unrolled selects and is read at constant indices: registers, not scratch memory)
+        if (cls != kClsNone) for_each_tile(h, T, ds, [&](int t) {
+#pragma unroll
+            for (int i = 0; i < kRefMax; ++i) tl[i] = (i == nt) ? t : tl[i];
+            ++nt;
+        });
         ref.n = nt;
         // a fast plan's halos over at most kRefMax tiles take their slots now (returning atomics, one per run of lanes that name the same
         // tile; the halo index is stored into the slot at the end of this function, when the atomic has long returned) -- every lane of the
@@ -1212,32 +1238,74 @@ tile_scan_blocks_kernel(int nblocks, int ntiles, const int32_t *__restrict__ blo
     }
 }
 
-// tile binning, pass 2: workgroup b places the halos K0's workgroup b left to it (slow_list[b][256], slow_cnt[b]), a thread per halo,
-// into the tiles' shared lists by cursor (many-tile halos enumerate their tiles again from the span kept in the TileRef)
+// tile binning, pass 2: workgroup b places the halos K0's workgroup b left to it (slow_list[b][256], slow_cnt[b]) into the tiles' shared
+// lists by cursor: a thread per halo of at most kRefMax tiles, the wave per many-tile halo (its tiles enumerated again from the span kept
+// in the TileRef, a lane per tile)
 __global__ void __launch_bounds__(256)
 tile_place_kernel(Hpx h, Tiling T, int64_t nhalo, const TileRef *__restrict__ tref,
                   const int32_t *__restrict__ start, int32_t *__restrict__ cur_b,
                   int32_t *__restrict__ entries, int64_t capacity, int32_t *__restrict__ overflow,
                   const int32_t *__restrict__ slow_list, const int32_t *__restrict__ slow_cnt)
 {
-    if ((int)threadIdx.x >= slow_cnt[blockIdx.x]) return;
-    const int64_t j = slow_list[(int64_t)blockIdx.x * blockDim.x + threadIdx.x];
-    if (j >= nhalo) return;
-    const TileRef ref = tref[j];
-    if (!ref.live) return;
-    auto put = [&](int t) {
+    const int nslow = slow_cnt[blockIdx.x];
+    if (nslow == 0) return;                                                    // (the whole workgroup)
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const bool mine = (int)threadIdx.x < nslow;
+    const int64_t j = mine ? (int64_t)slow_list[(int64_t)blockIdx.x * blockDim.x + threadIdx.x] : nhalo;
+    TileRef ref;
+    ref.n = 0; ref.live = 0;
+    for (int i = 0; i < kRefMax; ++i) { ref.few.tile[i] = 0; ref.few.slot[i] = 0; }
+    if (j < nhalo) ref = tref[j];
+    const bool act = j < nhalo && ref.live != 0;
+    auto put = [&](int t, int32_t halo) {
         const int64_t pos = (int64_t)start[t] + atomicAdd(cur_b + t, 1);
-        if (pos < capacity) entries[pos] = (int32_t)j; else *overflow = 1;
+        if (pos < capacity) entries[pos] = halo; else *overflow = 1;
     };
-    if (ref.n <= kRefMax) {
+    if (act && ref.n <= kRefMax) {
         for (int i = 0; i < kRefMax; ++i)
-            if (i < ref.n && ref.few.slot[i] < 0) put(ref.few.tile[i]);       // (slot >= 0: K0 stored it in the tile's fixed list)
-    } else {
+            if (i < ref.n && ref.few.slot[i] < 0) put(ref.few.tile[i], (int32_t)j);       // (slot >= 0: K0 stored it in the tile's fixed list)
+    }
+    // many-tile halos: the wave takes those of its lanes one at a time, a lane per TILE.  64 bands at a time, a lane each, give their slice
+    // counts (band_span); their prefix sum makes the tiles one index space in for_each_tile's order, and lane i finds the band of tile i by
+    // a binary search over the lanes' prefix sums.  (a thread of its own per halo places its tiles one returning atomic after the other)
+    unsigned long long many = __ballot(act && ref.n > kRefMax);
+    while (many) {                                                             // (wave-uniform)
+        const int src = __ffsll((long long)many) - 1;
+        many &= many - 1ull;
         DiscSpan ds;
-        ds.fb = 0; ds.rfirst = ref.many.rfirst; ds.rlast = ref.many.rlast; ds.allphi = ref.many.allphi;
-        ds.flo = ref.many.flo; ds.fhi = ref.many.fhi;
+        ds.fb = 0; ds.rfirst = __shfl(ref.many.rfirst, src, kWave); ds.rlast = __shfl(ref.many.rlast, src, kWave);
+        ds.allphi = __shfl(ref.many.allphi, src, kWave);
+        ds.flo = __shfl(ref.many.flo, src, kWave); ds.fhi = __shfl(ref.many.fhi, src, kWave);
         for (int q = 0; q < 4; ++q) { ds.fb_ring[q] = 0; ds.fb_k[q] = 0; }
-        for_each_tile(h, T, ds, put);
+        const int32_t halo = __shfl((int32_t)j, src, kWave);
+        if (ds.rlast < ds.rfirst) continue;
+        const int b0 = (ds.rfirst - 1) / T.BR, b1 = (ds.rlast - 1) / T.BR;
+        for (int bb = b0; bb <= b1; bb += kWave) {
+            BandSpan s;
+            s.t0 = 0; s.nphi = 1; s.jlo = 0; s.cnt = 0;
+            if (bb + lane <= b1) s = band_span(T, ds, bb + lane);
+            if (s.cnt < 0) s.cnt = 0;
+            int incl = s.cnt;
+#pragma unroll
+            for (int off = 1; off < kWave; off <<= 1) {
+                const int up = __shfl_up(incl, off, kWave);
+                if (lane >= off) incl += up;
+            }
+            const int total = __shfl(incl, kWave - 1, kWave), excl = incl - s.cnt;
+            for (int base = 0; base < total; base += kWave) {
+                const int i = base + lane;
+                int kb = 0;                                                    // the last lane whose first tile is at or before i
+#pragma unroll
+                for (int step = kWave >> 1; step > 0; step >>= 1) {
+                    const int e = __shfl(excl, kb + step, kWave);
+                    if (e <= i) kb += step;
+                }
+                BandSpan sb;
+                sb.t0 = __shfl(s.t0, kb, kWave); sb.nphi = __shfl(s.nphi, kb, kWave); sb.jlo = __shfl(s.jlo, kb, kWave); sb.cnt = 0;
+                const int k = i - __shfl(excl, kb, kWave);
+                if (i < total) put(band_span_tile(sb, k), halo);
+            }
+        }
     }
 }
 
