@@ -35,6 +35,28 @@ def fftlog_transform(rs, frs, dim, mu, power_law_index, device=0):
     return k, (out[0] if np.ndim(frs) == 1 else out)
 
 
+def fftlog_u(rs, dim, mu, power_law_index):
+    """u[n // 2 + 1] complex, ln(k r): the coefficients `fftlog_transform` multiplies the half spectrum by, and its low-ringing
+    ln(k_c r_c) (host only)"""
+    rs = _lib.f8(rs)
+    u = np.empty(rs.size // 2 + 1, dtype=np.complex128)
+    lnkr = C.c_double()
+    _lib.check(_lib.load().bfgx_fftlog_u(rs.size, rs.ctypes.data, int(dim), float(mu), float(power_law_index), u.ctypes.data,
+                                         C.addressof(lnkr)))
+    return u, lnkr.value
+
+
+def pchip_rows(x, y, q, device=0):
+    """scipy.interpolate.PchipInterpolator(x, y, axis=-1, extrapolate=False)(q) with 0 for NaN, on the GPU"""
+    x, y2, q = _lib.f8(x), _lib.f8(np.atleast_2d(y)), _lib.f8(np.atleast_1d(q))
+    if x.ndim != 1 or y2.shape[1] != x.size:
+        raise ValueError("x should be a 1D array and y should have len(x) columns")
+    out = np.empty((y2.shape[0], q.size))
+    _lib.check(_lib.load().bfgx_pchip_rows(int(device), y2.shape[0], x.size, x.ctypes.data, y2.ctypes.data, q.size, q.ctypes.data,
+                                           out.ctypes.data))
+    return out[0] if np.ndim(y) == 1 else out
+
+
 def _kgrid(r, dim, mu, plaw):
     r = _lib.f8(r)
     k = np.empty_like(r)

@@ -376,6 +376,12 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
  * Host arrays in / out; f and prof are [nrows][n] on the log grid r (positive, ascending, log-uniform). */
 /* the output grid of one transform (pure CPU): k_j = (k r)_lowring / r[n-1-j] */
 int bfgx_fftlog_kgrid(int32_t n, const double *r, int32_t dim, double mu, double plaw, double *k_out);
+/* the coefficients of that transform (pure CPU): u_out holds u_m, m = 0 .. n/2, as (re, im) pairs -- exactly what the kernel
+ * multiplies the half spectrum by -- and *lnkr_out = ln(k r)_lowring */
+int bfgx_fftlog_u(int32_t n, const double *r, int32_t dim, double mu, double plaw, double *u_out, double *lnkr_out);
+/* out[row][i] = scipy PchipInterpolator(x[n], y[row][n], extrapolate=False)(q[i]), and 0 where q[i] is outside [x[0], x[n-1]] or NaN
+ * (the last step of bfgx_fftlog_convolve, alone).  x strictly ascending, n >= 2, nq >= 1, 1 <= nrows <= 65535 */
+int bfgx_pchip_rows(int device, int64_t nrows, int32_t n, const double *x, const double *y, int32_t nq, const double *q, double *out);
 /* ks, fks = _fftlog_transform(rs, frs, dim, mu, plaw) */
 int bfgx_fftlog_transform(int device, int64_t nrows, int32_t n, const double *r, const double *f, int32_t dim, double mu,
                           double plaw, double *k_out, double *F_out);

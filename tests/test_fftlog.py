@@ -216,10 +216,13 @@ def test_hip_convolved_profile_vs_reference_pixel_py(gpu):
 
 # ------------------------------------------------------------------------------------------ GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize('dim,plaw', [(3, -1.5), (3, -0.5), (2, -1.0), (2, -0.5)])
-def test_hip_fftlog_transform_vs_oracle(gpu, dim, plaw):
+@pytest.mark.parametrize('dim,plaw,per_decade', [(3, -1.5, None), (3, -0.5, None), (2, -1.0, None), (2, -0.5, None), (3, -0.5, 400)],
+                         ids=['3--1.5', '3--0.5', '2--1.0', '2--0.5', '3--0.5-400-per-decade'])
+def test_hip_fftlog_transform_vs_oracle(gpu, dim, plaw, per_decade):
+    """(400 points per decade with q = 1 > mu_b: Im z reaches 273 in the reflection of ln Gamma, where sin(pi z) overflowed and the
+    transform came back inf)"""
     from baryonification_amd.utils.Pixel import fftlog_transform
-    r = np.geomspace(1e-8, 3e3, 1100)
+    r = np.geomspace(1e-8, 3e3, 1100) if per_decade is None else 1e-7 * 10.0 ** (np.arange(4001) / float(per_decade))
     rng = np.random.default_rng(3)
     rows = np.stack([np.exp(-(r / s) ** 1.3) / (1 + (r / 0.05) ** rng.uniform(0.5, 1.5)) for s in (0.3, 1.0, 7.0)])
     k, T = fftlog_transform(r, rows, dim, 0, plaw)

@@ -37,6 +37,7 @@ def entries():
         'bfgx_pressure_profile': ([1, _f(500), _f(500), _f(500), 1, _f(1), 4.0, _out(1)], [7]),
         'bfgx_fftlog_transform': ([1, 4, r4, _f(4), 3, 0.0, 0.0, _out(4), _out(4)], [7, 8]),
         'bfgx_fftlog_convolve': ([1, 4, r4, _f(4), 3, 0.0, 0.0, 0.0, _f(4), 1, _f(1), 1.0, _out(1)], [12]),
+        'bfgx_pchip_rows': ([1, 4, r4, _f(4), 1, _f(1), _out(1)], [6]),
         'bfgx_math_probe': ([_lib.MATH_FN['mul_add_nc'], 1, _f(1), _f(1), _out(1), None], [4]),
         'bfgx_regrid_pixels': ([2, 5, 1, _f(2), _f(1), _out(25)], [5]),
         'bfgx_deposit_particles': ([3, 1, _f(1), _f(1), _f(1), None, 1, _f(2), _out(1)], [8]),
