@@ -31,6 +31,7 @@
 #include "bfgx_scatter2.hpp"
 #include "bfgx_regrid2.hpp"
 #include "bfgx_tables.hpp"
+#include "bfgx_scan.hpp"
 #include "bfgx_grid.hpp"
 #include "bfgx_grid_pairs.hpp"
 #include "bfgx_fft.hpp"
@@ -108,6 +109,46 @@ int validate_table(const bfgx_table &t)
     return BFGX_OK;
 }
 
+// compute units of a device (256, the MI355X's, when the runtime does not say)
+int device_cu_count(int device)
+{
+    hipDeviceProp_t prop;
+    return (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+}
+
+// optional per-kernel HIP-event timing of a plan: KernelTimerT brackets a launch with a pair of events, read() sums the pairs per kernel kind
+struct KernelEvents {
+    using Pair = std::pair<hipEvent_t, hipEvent_t>;
+    bool timing = false;
+    std::vector<Pair> ev[BFGX_NUM_KERNELS], ev_free;
+    int enable(int on) { timing = on != 0; return BFGX_OK; }
+    int read(int device, hipStream_t stream, double *ms_sum, int64_t *launches)
+    {
+        if (!ms_sum || !launches) return fail(BFGX_ERR_INVALID, "NULL argument");
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int k = 0; k < BFGX_NUM_KERNELS; ++k) {
+            double tot = 0.0;
+            for (auto &e : ev[k]) {
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
+                tot += ms;
+                ev_free.push_back(e);
+            }
+            ms_sum[k] = tot;
+            launches[k] = (int64_t)ev[k].size();
+            ev[k].clear();
+        }
+        return BFGX_OK;
+    }
+    void destroy()
+    {
+        for (int k = 0; k < BFGX_NUM_KERNELS; ++k)
+            for (auto &e : ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+        for (auto &e : ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    }
+};
+
 }  // namespace
 
 struct bfgx_plan {
@@ -159,10 +200,7 @@ struct bfgx_plan {
     double *tile_sums = nullptr;     // [ntiles][2] per-tile {sum of source values, sum of deposits} of the tiled regrid
     std::vector<int32_t> band_tile0_host;   // first tile of every band (+ total)
     int64_t capacity = 0;
-    // optional per-kernel HIP-event timing (bfgx_plan_timing_*)
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[BFGX_NUM_KERNELS];
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+    KernelEvents events;             // optional per-kernel HIP-event timing (bfgx_plan_timing_*)
 };
 
 namespace {
@@ -170,19 +208,20 @@ namespace {
 // brackets one kernel launch with a pair of events on the plan's stream when timing is enabled
 template <class Plan>
 struct KernelTimerT {
-    Plan *p; int kind; std::pair<hipEvent_t, hipEvent_t> e{nullptr, nullptr};
+    Plan *p; int kind; KernelEvents::Pair e{nullptr, nullptr};
     KernelTimerT(Plan *p_, int kind_) : p(p_), kind(kind_)
     {
-        if (!p->timing) return;
-        if (!p->ev_free.empty()) { e = p->ev_free.back(); p->ev_free.pop_back(); }
+        KernelEvents &k = p->events;
+        if (!k.timing) return;
+        if (!k.ev_free.empty()) { e = k.ev_free.back(); k.ev_free.pop_back(); }
         else { (void)hipEventCreate(&e.first); (void)hipEventCreate(&e.second); }
         (void)hipEventRecord(e.first, p->stream);
     }
     ~KernelTimerT()
     {
-        if (!p->timing) return;
+        if (!p->events.timing) return;
         (void)hipEventRecord(e.second, p->stream);
-        p->ev[kind].push_back(e);
+        p->events.ev[kind].push_back(e);
     }
 };
 using KernelTimer = KernelTimerT<bfgx_plan>;
@@ -198,6 +237,16 @@ template <typename T>
 static int owned_upload(DevList &mem, hipStream_t stream, const std::vector<T> &v, const T *&dev_out)
 {
     return owned_upload(mem, stream, v.data(), v.size(), dev_out);
+}
+
+// a list too small for `needed` entries: a new one with a quarter + 1024 to spare (contents are not kept; the caller has drained the stream)
+template <typename T>
+static int grow_list(DevList &mem, T *&ptr, int64_t &capacity, int64_t needed)
+{
+    const int64_t cap = needed + needed / 4 + 1024;
+    HIP_TRY(mem.regrow(ptr, (size_t)cap));
+    capacity = cap;
+    return BFGX_OK;
 }
 
 static int validate_model(const bfgx_model *model)
@@ -860,29 +909,12 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
 
 int bfgx_plan_timing_enable(bfgx_plan *p, int on)
 {
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    p->timing = on != 0;
-    return BFGX_OK;
+    return p ? p->events.enable(on) : fail(BFGX_ERR_INVALID, "NULL plan");
 }
 
 int bfgx_plan_timing_read(bfgx_plan *p, double *ms_sum, int64_t *launches)
 {
-    if (!p || !ms_sum || !launches) return fail(BFGX_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    for (int k = 0; k < BFGX_NUM_KERNELS; ++k) {
-        double tot = 0.0;
-        for (auto &e : p->ev[k]) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-            tot += ms;
-            p->ev_free.push_back(e);
-        }
-        ms_sum[k] = tot;
-        launches[k] = (int64_t)p->ev[k].size();
-        p->ev[k].clear();
-    }
-    return BFGX_OK;
+    return p ? p->events.read(p->device, p->stream, ms_sum, launches) : fail(BFGX_ERR_INVALID, "NULL argument");
 }
 
 void bfgx_plan_destroy(bfgx_plan *p)
@@ -890,9 +922,7 @@ void bfgx_plan_destroy(bfgx_plan *p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)hipStreamSynchronize(p->stream);
-    for (int k = 0; k < BFGX_NUM_KERNELS; ++k)
-        for (auto &e : p->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto &e : p->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    p->events.destroy();
     p->mem.release();
     delete p;
 }
@@ -2107,6 +2137,12 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 // ------------------------------------------------------------------------------ regular-grid path (8f-1)
 #include "bfgx_grid_api.inc"
 
+// particle deposit (ParticleSnapshot.make_map) and particle routing; the fused deposit + regrid needs the grid plan
+#include "bfgx_deposit_api.inc"
+
+// 3-D FFT and power spectrum of gridded maps
+#include "bfgx_fft_api.inc"
+
 // bispectrum of gridded 3-D maps: inverse slab transforms, k-shell fields, triangle sums
 #include "bfgx_bispec_api.inc"
 
@@ -2149,7 +2185,7 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 extern "C" void bfgx_cache_clear(void)
 {
     g_shells.clear();            // plans + device buffers of the one-shot shell entries
-    dep_release_all();           // workspace of the tiled particle deposit (bfgx_grid_api.inc)
+    dep_release_all();           // workspace of the tiled particle deposit (bfgx_deposit_api.inc)
     fft_release_all();           // twiddle / wavenumber tables of the power spectrum
     bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries

@@ -1,5 +1,5 @@
 // C ABI of the bispectrum of gridded 3-D maps and of the inverse slab transforms it is built on (include/bfgx.h, "bispectrum");
-// included by bfgx_api.hip after bfgx_grid_api.inc (FftSetup, fft_planes, fft_pitch).  Kernels: bfgx_bispec.hpp.
+// included by bfgx_api.hip after bfgx_fft_api.inc (FftSetup, fft_planes, fft_pitch).  Kernels: bfgx_bispec.hpp.
 
 namespace {
 

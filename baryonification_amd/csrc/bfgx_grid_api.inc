@@ -1,4 +1,6 @@
-// bfgx_grid_api.inc -- C ABI of the regular-grid path (included at the end of bfgx_api.hip: one translation unit).
+// bfgx_grid_api.inc -- C ABI of the regular-grid path (included at the end of bfgx_api.hip: one translation unit): the grid plan, its
+// halo-owned and cell-owned device entries, the one-shot grid entries and bfgx_regrid_pixels.  The particle deposit follows in
+// bfgx_deposit_api.inc, the 3-D FFT / P(k) in bfgx_fft_api.inc.
 // Declarations and the reference lines each entry point replaces: include/bfgx.h, "regular-grid path".
 
 struct bfgx_grid_plan {
@@ -25,14 +27,18 @@ struct bfgx_grid_plan {
     int32_t *axis0_flag = nullptr;        // device word the gather kernel sets when a cell moves further than axis0_limit cells along the first array axis
     float axis0_limit = 3.0e38f;          // (set by the streamed host entry for the duration of its gathers; 3e38: no check)
     double *blk_sums = nullptr;           // [nblk][3]: sum of sources, sum of deposits, contributing pairs
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[BFGX_NUM_KERNELS];
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+    KernelEvents events;                  // optional per-kernel HIP-event timing (bfgx_grid_plan_timing_*)
 };
 
 namespace {
 
 using GridTimer = KernelTimerT<bfgx_grid_plan>;
+
+// The grid family's kernels are templates over the corner count of the table read-out (4, 8 or 16) and over the grid's dimensions (2 or 3):
+// f receives the run-time value as a tag, [&](auto nc) { ... kernel<decltype(nc)::value> ... }
+template <int V> using GridTag = std::integral_constant<int, V>;
+template <class F> auto grid_nc(int NC, F &&f) { return NC == 4 ? f(GridTag<4>{}) : NC == 8 ? f(GridTag<8>{}) : f(GridTag<16>{}); }
+template <class F> auto grid_dim(int ndim, F &&f) { return ndim == 3 ? f(GridTag<3>{}) : f(GridTag<2>{}); }
 
 int validate_grid(const bfgx_grid *g)
 {
@@ -46,45 +52,54 @@ int validate_grid(const bfgx_grid *g)
     return BFGX_OK;
 }
 
-template <int NC>
-int launch_grid_prep_nc(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode)
-{
-    GridCatalog gc;
-    gc.n = c->n; gc.M = c->M; gc.x = c->x; gc.y = c->y; gc.z = c->z; gc.lnM = c->lnM; gc.rmat = c->rmat;
-    for (int k = 0; k < BFGX_MAX_EXTRA; ++k) gc.extra[k] = c->extra[k];
-    const int blocks = (int)((c->n + kGridBlock - 1) / kGridBlock);
-    hipLaunchKernelGGL(grid_prep_kernel<NC>, dim3(blocks), dim3(kGridBlock), 0, p->stream, p->model, p->geom, gc, mode,
-                       p->recs, p->chunk_halo, p->capacity, p->counters);
-    return BFGX_OK;
-}
-
 int launch_grid_prep(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode)
 {
     HIP_TRY(hipMemsetAsync(p->counters, 0, 2 * sizeof(int32_t), p->stream));
     if (c->n == 0) return BFGX_OK;
+    GridCatalog gc;
+    gc.n = c->n; gc.M = c->M; gc.x = c->x; gc.y = c->y; gc.z = c->z; gc.lnM = c->lnM; gc.rmat = c->rmat;
+    for (int k = 0; k < BFGX_MAX_EXTRA; ++k) gc.extra[k] = c->extra[k];
+    const int blocks = (int)((c->n + kGridBlock - 1) / kGridBlock);
     GridTimer kt(p, BFGX_K_PREP);
-    if (p->NC == 4) launch_grid_prep_nc<4>(p, c, mode);
-    else if (p->NC == 8) launch_grid_prep_nc<8>(p, c, mode);
-    else launch_grid_prep_nc<16>(p, c, mode);
+    grid_nc(p->NC, [&](auto nc) {
+        hipLaunchKernelGGL((grid_prep_kernel<decltype(nc)::value>), dim3(blocks), dim3(kGridBlock), 0, p->stream, p->model, p->geom, gc, mode,
+                           p->recs, p->chunk_halo, p->capacity, p->counters);
+    });
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
 
-template <int DIM, int MODE, int NC>
-void launch_grid_scatter_t(bfgx_grid_plan *p, int blocks, double *out)
-{
-    hipLaunchKernelGGL((grid_scatter_kernel<DIM, MODE, NC>), dim3(blocks), dim3(kGridBlock), 0, p->stream,
-                       make_pair_table(p->model.tab), p->geom, p->recs, p->chunk_halo, p->counters, out, p->pair_total);
-}
-
-template <int DIM, int MODE>
+template <int MODE>
 int launch_grid_scatter(bfgx_grid_plan *p, int blocks, double *out)
 {
     GridTimer kt(p, MODE == 0 ? BFGX_K_OFFSETS : BFGX_K_PAINT);
-    if (p->NC == 4) launch_grid_scatter_t<DIM, MODE, 4>(p, blocks, out);
-    else if (p->NC == 8) launch_grid_scatter_t<DIM, MODE, 8>(p, blocks, out);
-    else launch_grid_scatter_t<DIM, MODE, 16>(p, blocks, out);
+    grid_dim(p->geom.ndim, [&](auto dim) { grid_nc(p->NC, [&](auto nc) {
+        hipLaunchKernelGGL((grid_scatter_kernel<decltype(dim)::value, MODE, decltype(nc)::value>), dim3(blocks), dim3(kGridBlock), 0, p->stream,
+                           make_pair_table(p->model.tab), p->geom, p->recs, p->chunk_halo, p->counters, out, p->pair_total);
+    }); });
     HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
+// what every entry that takes a catalog asks of it: it fits the plan, the columns the grid and the table need are there
+int grid_check_columns(const bfgx_grid_plan *p, const bfgx_grid_catalog *c)
+{
+    if (c->n < 0 || c->n > p->max_halos) return fail(BFGX_ERR_INVALID, "catalog size %lld exceeds plan max_halos %lld",
+                                                     (long long)c->n, (long long)p->max_halos);
+    const int nex = p->model.tab.ndim - 3;
+    if (c->n > 0 && (!c->M || !c->x || !c->y || (p->geom.ndim == 3 && !c->z))) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
+    for (int k = 0; k < nex; ++k) if (c->n > 0 && !c->extra[k]) return fail(BFGX_ERR_INVALID, "catalog misses a property column of the table");
+    if (c->rmat && p->geom.ndim == 3) return fail(BFGX_ERR_UNSUPPORTED, "use_ellipticity is not implemented for 3D maps");
+    return BFGX_OK;
+}
+
+// the pair count of the call so far, on the host (synchronises the stream)
+int read_pair_total(hipStream_t stream, const unsigned long long *dev, int64_t *out)
+{
+    unsigned long long np = 0;
+    HIP_TRY(hipMemcpyAsync(&np, dev, sizeof(np), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *out = (int64_t)np;
     return BFGX_OK;
 }
 
@@ -92,12 +107,7 @@ int launch_grid_scatter(bfgx_grid_plan *p, int blocks, double *out)
 int grid_halo_loop(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode, double *out, int64_t *n_pairs_host)
 {
     if (!p || !c || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (c->n < 0 || c->n > p->max_halos) return fail(BFGX_ERR_INVALID, "catalog size %lld exceeds plan max_halos %lld",
-                                                     (long long)c->n, (long long)p->max_halos);
-    const int nex = p->model.tab.ndim - 3;
-    if (c->n > 0 && (!c->M || !c->x || !c->y || (p->geom.ndim == 3 && !c->z))) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    for (int k = 0; k < nex; ++k) if (c->n > 0 && !c->extra[k]) return fail(BFGX_ERR_INVALID, "catalog misses a property column of the table");
-    if (c->rmat && p->geom.ndim == 3) return fail(BFGX_ERR_UNSUPPORTED, "use_ellipticity is not implemented for 3D maps");
+    if (int rc = grid_check_columns(p, c)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const size_t out_bytes = sizeof(double) * (size_t)(p->geom.ntot / p->geom.npix * p->geom.slab_n) * (mode == 0 ? p->geom.ndim : 1);
     HIP_TRY(hipMemsetAsync(out, 0, out_bytes, p->stream));
@@ -110,25 +120,14 @@ int grid_halo_loop(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int mode, doub
         if (cnt[0] < 0) return fail(BFGX_ERR_INVALID, "more than 2^31 work items (%d-pixel chunks): catalog too large for one call", kGridChunk);
         if ((int64_t)cnt[0] <= p->capacity) break;
         // the work-item table was too small: grow it and redo the (deterministic) preparation
-        const int64_t cap = (int64_t)cnt[0] + cnt[0] / 4 + 1024;
-        HIP_TRY(p->mem.regrow(p->chunk_halo, (size_t)cap));
-        p->capacity = cap;
+        if (int rc = grow_list(p->mem, p->chunk_halo, p->capacity, (int64_t)cnt[0])) return rc;
     }
     if (cnt[1] & 1) return fail(BFGX_ERR_ASSERT, "Halo offsets are larger than res (Map2DRunner.py:516)");
     if (cnt[0] > 0) {
         const int blocks = (int)std::min<int64_t>(cnt[0], (int64_t)p->n_cu * 8);
-        int rc;
-        if (p->geom.ndim == 3) rc = mode == 0 ? launch_grid_scatter<3, 0>(p, blocks, out) : launch_grid_scatter<3, 1>(p, blocks, out);
-        else rc = mode == 0 ? launch_grid_scatter<2, 0>(p, blocks, out) : launch_grid_scatter<2, 1>(p, blocks, out);
-        if (rc) return rc;
+        if (int rc = mode == 0 ? launch_grid_scatter<0>(p, blocks, out) : launch_grid_scatter<1>(p, blocks, out)) return rc;
     }
-    if (n_pairs_host) {
-        unsigned long long np = 0;
-        HIP_TRY(hipMemcpyAsync(&np, p->pair_total, sizeof(np), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        *n_pairs_host = (int64_t)np;
-    }
-    return BFGX_OK;
+    return n_pairs_host ? read_pair_total(p->stream, p->pair_total, n_pairs_host) : BFGX_OK;
 }
 
 struct GridHostCatalog {
@@ -152,8 +151,6 @@ struct GridHostCatalog {
         return BFGX_OK;
     }
 };
-
-int ilog2_exact(int n) { int l = 0; while ((1 << l) < n) ++l; return ((1 << l) == n) ? l : -1; }
 
 }  // namespace
 
@@ -197,8 +194,7 @@ int bfgx_grid_plan_create(int device, void *hip_stream, const bfgx_grid *grid, i
     if (p->mem.alloc(p->recs, (size_t)std::max<int64_t>(max_halos, 1)) || p->mem.alloc(p->chunk_halo, (size_t)p->capacity) ||
         p->mem.alloc(p->counters, 2) || p->mem.alloc(p->pair_total, 1))
         return bail(alloc_fail("grid workspace"));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) p->n_cu = prop.multiProcessorCount;
+    p->n_cu = device_cu_count(device);
     *out = p;
     return BFGX_OK;
 }
@@ -209,9 +205,7 @@ void bfgx_grid_plan_destroy(bfgx_grid_plan *p)
     (void)hipSetDevice(p->device);
     (void)hipStreamSynchronize(p->stream);
     p->mem.release();
-    for (int k = 0; k < BFGX_NUM_KERNELS; ++k)
-        for (auto &e : p->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto &e : p->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    p->events.destroy();
     delete p;
 }
 
@@ -250,10 +244,9 @@ int bfgx_grid_regrid_slab_device(bfgx_grid_plan *p, const double *map_in, const 
     {
         GridTimer kt(p, BFGX_K_REGRID);
         double *bs = sums_dev ? p->block_sums : nullptr;
-        if (g.ndim == 3)
-            hipLaunchKernelGGL(grid_regrid_kernel<3>, dim3(blocks), dim3(256), 0, p->stream, g.npix, ntot, offsets, map_in, map_out, bs, sw, missed_dev);
-        else
-            hipLaunchKernelGGL(grid_regrid_kernel<2>, dim3(blocks), dim3(256), 0, p->stream, g.npix, ntot, offsets, map_in, map_out, bs, sw, missed_dev);
+        grid_dim(g.ndim, [&](auto dim) {
+            hipLaunchKernelGGL((grid_regrid_kernel<decltype(dim)::value>), dim3(blocks), dim3(256), 0, p->stream, g.npix, ntot, offsets, map_in, map_out, bs, sw, missed_dev);
+        });
         HIP_TRY(hipGetLastError());
     }
     if (sums_dev) {         // the regrid left per-workgroup {sum of source values, sum of deposits}: no second pass over the maps
@@ -285,7 +278,7 @@ int gather_workspace(bfgx_grid_plan *p)
     const GridGeom &g = p->geom;
     const int nbk = gather_blocks_per_axis(g.npix, g.ndim == 3 ? GatherBlk<3>::S : GatherBlk<2>::S);
     p->nblk = (g.ndim == 3) ? (int64_t)nbk * nbk * nbk : (int64_t)nbk * nbk;
-    p->nscan_blocks = (int)((p->nblk + 1 + kScanPerBlock - 1) / kScanPerBlock);
+    p->nscan_blocks = scan_block_count(p->nblk + 1);
     p->list_capacity = 16 * p->max_halos + 65536;
     if (const char *e = std::getenv("BFGX_GRID_ITEM_CAP")) p->list_capacity = std::max<int64_t>(1, std::atoll(e));   // tests: force regrowth
     // (blk_count, which marks the workspace as present, last: a failure part-way leaves the next call to try again)
@@ -300,30 +293,23 @@ int gather_workspace(bfgx_grid_plan *p)
     return BFGX_OK;
 }
 
-template <int DIM, int FILL>
+template <int FILL>
 void launch_block_lists(bfgx_grid_plan *p, int64_t nh)
 {
-    hipLaunchKernelGGL((grid_block_lists_kernel<DIM, FILL>), dim3((unsigned)((nh + 256 / kWave - 1) / (256 / kWave))), dim3(256), 0, p->stream, p->geom, nh,
-                       (const GridHaloRec *)p->recs, p->blk_count, (const int32_t *)p->blk_start, p->blk_list);
+    grid_dim(p->geom.ndim, [&](auto dim) {
+        hipLaunchKernelGGL((grid_block_lists_kernel<decltype(dim)::value, FILL>), dim3((unsigned)((nh + 256 / kWave - 1) / (256 / kWave))), dim3(256), 0, p->stream,
+                           p->geom, nh, (const GridHaloRec *)p->recs, p->blk_count, (const int32_t *)p->blk_start, p->blk_list);
+    });
 }
 
-template <int DIM>
-void launch_gather(bfgx_grid_plan *p, const double *map_in, double *map_out, int64_t nnz, int64_t nz_off = 0)
+void launch_gather(bfgx_grid_plan *p, const double *map_in, double *map_out, int64_t nnz, int64_t nz_off)
 {
     const PairTable pt = make_pair_table(p->model.tab);
-    const dim3 grid((unsigned)nnz), block(256);
-    if (p->NC == 4)
-        hipLaunchKernelGGL((grid_gather_regrid_kernel<DIM, 4>), grid, block, 0, p->stream, pt, p->geom, (const GridHaloRec *)p->recs, (const int32_t *)p->blk_start,
-                           (const int32_t *)p->blk_list, (const int32_t *)p->blk_nz + nz_off, map_in, map_out, p->blk_sums, p->axis0_limit,
-                           p->axis0_limit < 1.0e30f ? p->axis0_flag : (int32_t *)nullptr);
-    else if (p->NC == 8)
-        hipLaunchKernelGGL((grid_gather_regrid_kernel<DIM, 8>), grid, block, 0, p->stream, pt, p->geom, (const GridHaloRec *)p->recs, (const int32_t *)p->blk_start,
-                           (const int32_t *)p->blk_list, (const int32_t *)p->blk_nz + nz_off, map_in, map_out, p->blk_sums, p->axis0_limit,
-                           p->axis0_limit < 1.0e30f ? p->axis0_flag : (int32_t *)nullptr);
-    else
-        hipLaunchKernelGGL((grid_gather_regrid_kernel<DIM, 16>), grid, block, 0, p->stream, pt, p->geom, (const GridHaloRec *)p->recs, (const int32_t *)p->blk_start,
-                           (const int32_t *)p->blk_list, (const int32_t *)p->blk_nz + nz_off, map_in, map_out, p->blk_sums, p->axis0_limit,
-                           p->axis0_limit < 1.0e30f ? p->axis0_flag : (int32_t *)nullptr);
+    grid_dim(p->geom.ndim, [&](auto dim) { grid_nc(p->NC, [&](auto nc) {
+        hipLaunchKernelGGL((grid_gather_regrid_kernel<decltype(dim)::value, decltype(nc)::value>), dim3((unsigned)nnz), dim3(256), 0, p->stream, pt, p->geom,
+                           (const GridHaloRec *)p->recs, (const int32_t *)p->blk_start, (const int32_t *)p->blk_list, (const int32_t *)p->blk_nz + nz_off,
+                           map_in, map_out, p->blk_sums, p->axis0_limit, p->axis0_limit < 1.0e30f ? p->axis0_flag : (int32_t *)nullptr);
+    }); });
 }
 
 }  // namespace
@@ -339,18 +325,12 @@ static int grid_check_catalog(bfgx_grid_plan *p, const bfgx_grid_catalog *c)
 {
     if (p->model.tab.logv) return fail(BFGX_ERR_INVALID, "the plan holds a log (profile) table: use bfgx_grid_paint_device");
     if (p->geom.slab_n != p->geom.npix) return fail(BFGX_ERR_INVALID, "the plan owns a slab: use the slab entry points");
-    if (c->n < 0 || c->n > p->max_halos) return fail(BFGX_ERR_INVALID, "catalog size %lld exceeds plan max_halos %lld", (long long)c->n, (long long)p->max_halos);
-    const int nex = p->model.tab.ndim - 3;
-    if (c->n > 0 && (!c->M || !c->x || !c->y || (p->geom.ndim == 3 && !c->z))) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    for (int k = 0; k < nex; ++k) if (c->n > 0 && !c->extra[k]) return fail(BFGX_ERR_INVALID, "catalog misses a property column of the table");
-    if (c->rmat && p->geom.ndim == 3) return fail(BFGX_ERR_UNSUPPORTED, "use_ellipticity is not implemented for 3D maps");
-    return BFGX_OK;
+    return grid_check_columns(p, c);
 }
 
 static int grid_lists_stage(bfgx_grid_plan *p, const bfgx_grid_catalog *c, GatherRanges &gr)
 {
     hipStream_t s = p->stream;
-    const bool d3 = p->geom.ndim == 3;
     HIP_TRY(hipMemsetAsync(p->pair_total, 0, sizeof(unsigned long long), s));
     HIP_TRY(hipMemsetAsync(p->blk_count, 0, sizeof(int32_t) * (size_t)(p->nblk + 1), s));
     if (int rc = launch_grid_prep(p, c, 0)) return rc;                  // (its work-item table is not used here)
@@ -358,10 +338,8 @@ static int grid_lists_stage(bfgx_grid_plan *p, const bfgx_grid_catalog *c, Gathe
     int32_t cnt[2] = {0, 0};
     {
         GridTimer kt(p, BFGX_K_BIN);
-        if (c->n > 0) { if (d3) launch_block_lists<3, 0>(p, c->n); else launch_block_lists<2, 0>(p, c->n); }
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(p->nscan_blocks), dim3(kTabThreads), 0, s, p->nblk + 1, (const int32_t *)p->blk_count, p->blk_start, p->blk_bsum, 1);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, p->nscan_blocks, p->blk_bsum, p->blk_total);
-        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((p->nblk + 1 + 255) / 256)), dim3(256), 0, s, p->nblk + 1, p->blk_start, (const int32_t *)p->blk_bsum);
+        if (c->n > 0) launch_block_lists<0>(p, c->n);
+        exclusive_scan(s, p->nblk + 1, p->blk_count, p->blk_start, p->blk_bsum, p->blk_total);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemsetAsync(p->blk_count, 0, sizeof(int32_t) * (size_t)(p->nblk + 1), s));      // reused as the fill cursors
@@ -382,14 +360,10 @@ static int grid_lists_stage(bfgx_grid_plan *p, const bfgx_grid_catalog *c, Gathe
     HIP_TRY(hipStreamSynchronize(s));
     if (cnt[1] & 1) return fail(BFGX_ERR_ASSERT, "Halo offsets are larger than res (Map2DRunner.py:516)");
     if (total > (int64_t)INT32_MAX) return fail(BFGX_ERR_INVALID, "block lists exceed 2^31 entries: split the catalog");
-    if (total > p->list_capacity) {
-        const int64_t cap = total + total / 4 + 1024;
-        HIP_TRY(p->mem.regrow(p->blk_list, (size_t)cap));
-        p->list_capacity = cap;
-    }
+    if (total > p->list_capacity) if (int rc = grow_list(p->mem, p->blk_list, p->list_capacity, total)) return rc;
     if (c->n > 0 && total > 0) {
         GridTimer kt(p, BFGX_K_BIN);
-        if (d3) launch_block_lists<3, 1>(p, c->n); else launch_block_lists<2, 1>(p, c->n);
+        launch_block_lists<1>(p, c->n);
         HIP_TRY(hipGetLastError());
     }
     return BFGX_OK;
@@ -407,7 +381,7 @@ static int grid_copy_stage(bfgx_grid_plan *p, const double *map_in, double *map_
 static int grid_gather_stage(bfgx_grid_plan *p, const double *map_in, double *map_out, const GatherRanges &gr, int r)
 {
     GridTimer kt(p, BFGX_K_OFFSETS);
-    if (gr.nnz[r] > 0) { if (p->geom.ndim == 3) launch_gather<3>(p, map_in, map_out, gr.nnz[r], gr.lo[r]); else launch_gather<2>(p, map_in, map_out, gr.nnz[r], gr.lo[r]); }
+    if (gr.nnz[r] > 0) launch_gather(p, map_in, map_out, gr.nnz[r], gr.lo[r]);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
@@ -420,13 +394,7 @@ static int grid_sums_stage(bfgx_grid_plan *p, int ncopy, double *sums_dev, int64
         hipLaunchKernelGGL(gather_sums_kernel, dim3(64), dim3(256), 0, s, p->nblk, (const double *)p->blk_sums, ncopy, (const double *)p->block_sums, sums_dev, p->pair_total);
         HIP_TRY(hipGetLastError());
     }
-    if (n_pairs_host) {
-        unsigned long long np = 0;
-        HIP_TRY(hipMemcpyAsync(&np, p->pair_total, sizeof(np), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *n_pairs_host = (int64_t)np;
-    }
-    return BFGX_OK;
+    return n_pairs_host ? read_pair_total(s, p->pair_total, n_pairs_host) : BFGX_OK;
 }
 
 // ncopy_done > 0: map_out already holds a copy of map_in and p->block_sums[0 .. ncopy_done) its partial sums (the fused deposit)
@@ -455,29 +423,12 @@ int bfgx_grid_baryonify_device(bfgx_grid_plan *p, const bfgx_grid_catalog *c, co
 
 int bfgx_grid_plan_timing_enable(bfgx_grid_plan *p, int on)
 {
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    p->timing = on != 0;
-    return BFGX_OK;
+    return p ? p->events.enable(on) : fail(BFGX_ERR_INVALID, "NULL plan");
 }
 
 int bfgx_grid_plan_timing_read(bfgx_grid_plan *p, double *ms_sum, int64_t *launches)
 {
-    if (!p || !ms_sum || !launches) return fail(BFGX_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    for (int k = 0; k < BFGX_NUM_KERNELS; ++k) {
-        double tot = 0.0;
-        for (auto &e : p->ev[k]) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-            tot += ms;
-            p->ev_free.push_back(e);
-        }
-        ms_sum[k] = tot;
-        launches[k] = (int64_t)p->ev[k].size();
-        p->ev[k].clear();
-    }
-    return BFGX_OK;
+    return p ? p->events.read(p->device, p->stream, ms_sum, launches) : fail(BFGX_ERR_INVALID, "NULL argument");
 }
 
 // ---------------------------------------------------------------- one-shot host API
@@ -719,520 +670,9 @@ int bfgx_regrid_pixels(int device, int32_t ndim, int32_t npix, int64_t n, const 
     if (int rc = c.ready()) return rc;
     if (n > 0) {
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (ndim == 3) hipLaunchKernelGGL(pixel_deposit_kernel<3>, dim3(blocks), dim3(256), 0, 0, npix, n, dp, dv, dg);
-        else hipLaunchKernelGGL(pixel_deposit_kernel<2>, dim3(blocks), dim3(256), 0, 0, npix, n, dp, dv, dg);
+        grid_dim(ndim, [&](auto dim) { hipLaunchKernelGGL((pixel_deposit_kernel<decltype(dim)::value>), dim3(blocks), dim3(256), 0, 0, npix, n, dp, dv, dg); });
     }
     return c.finish();
-}
-
-}  // extern "C"
-
-namespace {
-
-// grow-only workspace of the tiled deposit, one per device (released by bfgx_cache_clear); one deposit in flight per device
-struct DepWork {
-    PoolBuf keys[2], mass[2], ctr, bsum, total;     // uint32_t keys, double masses, int32_t counters and block sums, one int64_t (slack: an eighth)
-};
-std::mutex g_dep_mu;
-std::map<int, DepWork> g_dep;
-
-void dep_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_dep_mu);
-    while (!g_dep.empty()) {
-        (void)hipSetDevice(g_dep.begin()->first);
-        g_dep.erase(g_dep.begin());
-    }
-}
-
-// keys_by (optional): who writes the keys [n] and the per-chunk level-1 histograms [B1][chunks] instead of deposit_keys_kernel (the snapshot
-// path's displacement kernel does, for the particles it has just moved)
-using DepKeysBy = std::function<int(const DepGeom &, uint32_t *, int32_t *, unsigned)>;
-
-template <int DIM, bool MASS>
-int deposit_tiled(DepWork &w, const DepGeom &g, hipStream_t s, int64_t n, const double *x, const double *y, const double *z,
-                  const double *mass, const double *edges_dev, double *map_out_dev, double *map_out2_dev = nullptr, double *tile_sums_dev = nullptr,
-                  int64_t stride = 1, const DepKeysBy *keys_by = nullptr)
-{
-    // counters: count2[T + 1] start2[T + 1] cursor2[T], kDepPad words apart | per-workgroup level-1 histograms [B1][chunks] + 1, scanned in place
-    const unsigned chunks = (unsigned)((n + kDepChunk - 1) / kDepChunk);
-    const size_t o_c2 = 0, o_s2 = o_c2 + g.T + 1, o_k2 = o_s2 + g.T + 1, o_wg = o_k2 + (size_t)g.T * kDepPad;
-    const int64_t nwg = (int64_t)g.B1 * chunks + 1;
-    uint32_t *const keys[2] = {w.keys[0].as<uint32_t>(), w.keys[1].as<uint32_t>()};
-    double *const wmass[2] = {w.mass[0].as<double>(), w.mass[1].as<double>()};
-    int32_t *const ctr = w.ctr.as<int32_t>(), *const bsum = w.bsum.as<int32_t>();
-    int64_t *const total = w.total.as<int64_t>();
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(int32_t) * (o_wg + (size_t)nwg), s));
-    int32_t *c2 = ctr + o_c2, *s2 = ctr + o_s2, *k2 = ctr + o_k2, *wg = ctr + o_wg;
-    if (keys_by) { if (int rc = (*keys_by)(g, keys[0], wg, chunks)) return rc; }
-    else hipLaunchKernelGGL(deposit_keys_kernel<DIM>, dim3(chunks), dim3(256), 0, s, g, n, x, y, z, edges_dev, keys[0], wg, stride);
-    {
-        const int nb1 = (int)((nwg + kScanPerBlock - 1) / kScanPerBlock);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(nb1), dim3(kTabThreads), 0, s, nwg, (const int32_t *)wg, wg, bsum, 1);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nb1, bsum, total);
-        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, s, nwg, wg, (const int32_t *)bsum);
-    }
-    hipLaunchKernelGGL((deposit_split_kernel<1, MASS>), dim3(chunks), dim3(256), 0, s, g, n, (const int32_t *)nullptr, (const uint32_t *)keys[0],
-                       mass, (const int32_t *)wg, (int32_t *)nullptr, keys[1], wmass[0], stride);
-    const int32_t *nvalid = wg + (nwg - 1);             // particles inside the edges
-    hipLaunchKernelGGL(deposit_count_kernel, dim3(chunks), dim3(256), 0, s, g, nvalid, (const uint32_t *)keys[1], c2);
-    const int64_t nscan = (int64_t)g.T + 1;
-    const int nblocks = (int)((nscan + kScanPerBlock - 1) / kScanPerBlock);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(nblocks), dim3(kTabThreads), 0, s, nscan, (const int32_t *)c2, s2, bsum, 1);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, nblocks, bsum, total);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((nscan + 255) / 256)), dim3(256), 0, s, nscan, s2, (const int32_t *)bsum);
-    hipLaunchKernelGGL((deposit_split_kernel<2, MASS>), dim3(chunks), dim3(256), 0, s, g, n, nvalid, (const uint32_t *)keys[1],
-                       (const double *)wmass[0], (const int32_t *)s2, k2, keys[0], wmass[1], (int64_t)1);
-    hipLaunchKernelGGL(deposit_tiles_kernel<MASS>, dim3(g.T), dim3(DepTileThreads<MASS>::n), 0, s, g, (const int32_t *)s2, (const uint32_t *)keys[0],
-                       (const double *)wmass[1], map_out_dev, map_out2_dev, tile_sums_dev);
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bfgx_route_particles_count_device(int device, void *hip_stream, int64_t n, const double *x, int32_t n_grid, const double *edges_dev,
-                                      int32_t world, uint8_t *owner_dev, int32_t *counts_dev)
-{
-    if ((n > 0 && (!x || !owner_dev)) || !edges_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (n < 0 || n_grid < 1 || world < 1 || world > kPartRouteMaxRanks || n_grid % world) return fail(BFGX_ERR_INVALID, "particle routing needs 1 <= world <= %d ranks that divide n_grid", kPartRouteMaxRanks);
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int32_t) * world, s));
-    if (n > 0) {
-        hipLaunchKernelGGL(route_particles_count_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, kPartRouteGrid)), dim3(256), 0, s, n, x, edges_dev,
-                           n_grid, n_grid / world, world, owner_dev, counts_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_route_particles_fill_device(int device, void *hip_stream, int64_t n, int32_t ncols, const double *const *cols, const uint8_t *owner_dev,
-                                     int32_t world, const int64_t *start_host, int64_t total, int32_t *cursor_dev, double *cols_out_dev)
-{
-    if (!cols || !start_host || !cursor_dev || (n > 0 && !owner_dev) || (total > 0 && !cols_out_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (n < 0 || total < 0 || total > n || ncols < 1 || ncols > 4 || world < 1 || world > kPartRouteMaxRanks) return fail(BFGX_ERR_INVALID, "bad particle routing arguments");
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    PartRouteArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.world = world; a.ncols = ncols;
-    for (int d = 0; d < world; ++d) a.start[d] = start_host[d];
-    for (int c = 0; c < ncols; ++c) { if (n > 0 && !cols[c]) return fail(BFGX_ERR_INVALID, "column pointer is NULL"); a.col[c] = cols[c]; }
-    HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(int32_t) * world, s));
-    if (n > 0 && total > 0) {
-        hipLaunchKernelGGL(route_particles_fill_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, kPartRouteGrid)), dim3(256), 0, s, a, n, total, owner_dev,
-                           cursor_dev, cols_out_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_deposit_particles_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
-                                  const double *mass, int32_t n_grid, const double *edges_dev, double *map_out_dev)
-{
-    return bfgx_deposit_particles_slab_device(device, hip_stream, ndim, n, x, y, z, mass, n_grid, edges_dev, 0, n_grid, map_out_dev);
-}
-
-// map_out2_dev / tile_sums_dev / *ntiles (optional): the tile-owned form also stores a second copy of the map and the tiles' totals
-// (*ntiles of them); *ntiles = 0 when the atomic form ran (small inputs), which stores neither
-static int deposit_impl(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
-                        const double *mass, int32_t n_grid, const double *edges_dev, int32_t plane_lo, int32_t plane_n,
-                        double *map_out_dev, double *map_out2_dev, double *tile_sums_dev, int32_t *ntiles, int64_t stride = 1,
-                        const DepKeysBy *keys_by = nullptr)
-{
-    if (ntiles) *ntiles = 0;
-    if ((n > 0 && (!x || !y || (ndim == 3 && !z))) || !edges_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1");
-    if (plane_lo < 0 || plane_n < 1 || plane_lo + plane_n > n_grid) return fail(BFGX_ERR_INVALID, "slab [%d, %d) outside the grid", plane_lo, plane_lo + plane_n);
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    size_t ntot = (size_t)plane_n;
-    for (int d = 1; d < ndim; ++d) ntot *= (size_t)n_grid;
-    // tile-owned form (bfgx_deposit.hpp) when there is enough work to sort; BFGX_DEPOSIT=atomic / tiled forces one of the two
-    const DepGeom g = dep_geom(ndim, n_grid, plane_lo, plane_n);
-    bool tiled = n >= (int64_t)1 << 20 && n < ((int64_t)1 << 31) - kDepChunk && g.T < (1 << (32 - kDepLocalBits)) && g.B1 <= 1024 && g.B2 <= kDepHist;
-    if (const char *e = std::getenv("BFGX_DEPOSIT")) {
-        if (!std::strcmp(e, "atomic")) tiled = false;
-        else if (!std::strcmp(e, "tiled")) tiled = n > 0 && n < ((int64_t)1 << 31) - kDepChunk && g.T < (1 << (32 - kDepLocalBits)) && g.B1 <= 1024 && g.B2 <= kDepHist;
-    }
-    if (keys_by) {             // the keys come from another kernel: the sort is the only form there is
-        tiled = n > 0 && n < ((int64_t)1 << 31) - kDepChunk && g.T < (1 << (32 - kDepLocalBits)) && g.B1 <= 1024 && g.B2 <= kDepHist;
-        if (n > 0 && !tiled) return fail(BFGX_ERR_UNSUPPORTED, "the fused displace + deposit needs a grid the tile-owned deposit takes (%d tiles): call the displacement and the deposit one after the other", g.T);
-    }
-    if (tiled) {
-        std::lock_guard<std::mutex> lk(g_dep_mu);
-        DepWork &w = g_dep[device];
-        const size_t nctr = (2 + (size_t)kDepPad) * ((size_t)g.T + 1) + (size_t)g.B1 * (size_t)((n + kDepChunk - 1) / kDepChunk) + 8;
-        if (w.keys[0].need(sizeof(uint32_t) * (size_t)n, 8, 0) || w.keys[1].need(sizeof(uint32_t) * (size_t)n, 8, 0)) return alloc_fail("deposit keys");
-        if (mass && (w.mass[0].need(sizeof(double) * (size_t)n, 8, 0) || w.mass[1].need(sizeof(double) * (size_t)n, 8, 0))) return alloc_fail("deposit masses");
-        if (w.ctr.need(sizeof(int32_t) * nctr, 8, 0) || w.bsum.need(sizeof(int32_t) * (nctr / kScanPerBlock + 2), 8, 0) || w.total.need(sizeof(int64_t), 8, 0))
-            return alloc_fail("deposit counters");
-        if (ntiles) *ntiles = g.T;
-        if (ndim == 3) return mass ? deposit_tiled<3, true>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by)
-                                   : deposit_tiled<3, false>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by);
-        return mass ? deposit_tiled<2, true>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by)
-                    : deposit_tiled<2, false>(w, g, s, n, x, y, z, mass, edges_dev, map_out_dev, map_out2_dev, tile_sums_dev, stride, keys_by);
-    }
-    HIP_TRY(hipMemsetAsync(map_out_dev, 0, sizeof(double) * ntot, s));
-    if (n > 0) {
-        const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (ndim == 3) hipLaunchKernelGGL(particle_deposit_kernel<3>, dim3(blocks), dim3(256), 0, s, n, x, y, z, mass, n_grid, edges_dev, map_out_dev, plane_lo, plane_n, stride);
-        else hipLaunchKernelGGL(particle_deposit_kernel<2>, dim3(blocks), dim3(256), 0, s, n, x, y, z, mass, n_grid, edges_dev, map_out_dev, plane_lo, plane_n, stride);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_deposit_particles_slab_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
-                                       const double *mass, int32_t n_grid, const double *edges_dev, int32_t plane_lo, int32_t plane_n,
-                                       double *map_out_dev)
-{
-    return deposit_impl(device, hip_stream, ndim, n, x, y, z, mass, n_grid, edges_dev, plane_lo, plane_n, map_out_dev, nullptr, nullptr, nullptr);
-}
-
-int bfgx_grid_deposit_baryonify_device(bfgx_grid_plan *p, const bfgx_grid_catalog *c, int64_t n_particles, const double *x, const double *y,
-                                       const double *z, const double *mass, const double *edges_dev, double *map_in_dev, double *map_out_dev,
-                                       double *sums_dev, int64_t *n_pairs_host)
-{
-    if (!p || !map_in_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (p->geom.slab_n != p->geom.npix) return fail(BFGX_ERR_INVALID, "the plan owns a slab: use the slab entry points");
-    // ParticleSnapshot.make_map (io.py:622-670) straight into BaryonifyGrid.process (Map2DRunner.py:431-607): the deposit's last kernel
-    // stores every cell of the histogram twice -- map_in and the start value of map_out -- and leaves the tiles' totals, so the pass
-    // that copies map_in into map_out and sums it (1.07 GB read + 1.07 GB written at 512^3) does not run
-    int32_t ntiles = 0;
-    if (int rc = deposit_impl(p->device, (void *)p->stream, p->geom.ndim, n_particles, x, y, z, mass, p->geom.npix, edges_dev, 0, p->geom.npix,
-                              map_in_dev, map_out_dev, p->block_sums, &ntiles)) return rc;
-    return grid_baryonify_impl(p, c, map_in_dev, map_out_dev, sums_dev, n_pairs_host, ntiles);
-}
-
-int bfgx_deposit_particles(int device, int32_t ndim, int64_t n, const double *x, const double *y, const double *z, const double *mass,
-                           int32_t n_grid, const double *edges, double *map_out)
-{
-    if (!x || !y || (ndim == 3 && !z) || !edges || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1");
-    for (int i = 1; i <= n_grid; ++i) if (!(edges[i] > edges[i - 1])) return fail(BFGX_ERR_INVALID, "edges must be strictly ascending");
-    HostCall c(device);
-    size_t ntot = 1;
-    for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
-    const double *dx = c.in(x, n), *dy = c.in(y, n), *dz = ndim == 3 ? c.in(z, n) : nullptr, *dm = mass ? c.in(mass, n) : nullptr;
-    const double *de = c.in(edges, n_grid + 1);
-    double *dout = c.out(map_out, ntot);
-    if (int rc = c.ready()) return rc;
-    if (int rc = bfgx_deposit_particles_device(device, nullptr, ndim, n, dx, dy, dz, dm, n_grid, de, dout)) return rc;
-    return c.finish();
-}
-
-}  // extern "C"
-
-namespace {
-// device buffers of the records entry below, kept between calls per device (bfgx_cache_clear frees them)
-struct DepRecBuf {
-    PoolBuf rec, map, edges;                   // (slack: an eighth + 8 bytes)
-    hipStream_t up = nullptr;
-    ~DepRecBuf() { if (up) (void)hipStreamDestroy(up); }
-};
-std::mutex g_deprec_mu;
-std::map<int, DepRecBuf> g_deprec;
-void deprec_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_deprec_mu);
-    while (!g_deprec.empty()) {
-        (void)hipSetDevice(g_deprec.begin()->first);
-        g_deprec.erase(g_deprec.begin());
-    }
-}
-}  // namespace
-
-extern "C" {
-
-int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const void *records, int32_t itemsize, int32_t off_x, int32_t off_y,
-                                   int32_t off_z, int32_t off_mass, int32_t n_grid, const double *edges, double *map_out)
-{
-    if ((n > 0 && !records) || !edges || !map_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1");
-    auto bad = [&](int off) { return off < 0 || off % 8 || off + 8 > itemsize; };
-    if (itemsize < 16 || itemsize % 8 || bad(off_x) || bad(off_y) || (ndim == 3 && bad(off_z)) || (off_mass >= 0 && bad(off_mass)))
-        return fail(BFGX_ERR_INVALID, "records must be a multiple of 8 bytes with 8-byte aligned float64 fields");
-    for (int i = 1; i <= n_grid; ++i) if (!(edges[i] > edges[i - 1])) return fail(BFGX_ERR_INVALID, "edges must be strictly ascending");
-    if (int rc = select_device(device)) return rc;
-    std::lock_guard<std::mutex> lk(g_deprec_mu);
-    DepRecBuf &b = g_deprec[device];
-    size_t ntot = 1;
-    for (int d = 0; d < ndim; ++d) ntot *= (size_t)n_grid;
-    const size_t rbytes = (size_t)n * (size_t)itemsize, mbytes = ntot * sizeof(double), ebytes = sizeof(double) * (size_t)(n_grid + 1);
-    if (b.rec.need(rbytes, 8, 8) || b.map.need(mbytes, 8, 8) || b.edges.need(ebytes + 16, 8, 8)) return alloc_fail("deposit records");
-    if (!b.up) HIP_TRY(hipStreamCreateWithFlags(&b.up, hipStreamNonBlocking));
-    // the records go up as they are (page-locked for the call when the host allows it: the copy then runs at the PCIe rate); the kernels
-    // read the coordinate / mass fields at their stride -- no strided gather of four columns on the host
-    OneShotCall call(&b.up);
-    (void)call.open_in(records, rbytes, false);              // (large arrays are page-locked for the call; small ones are copied from pageable memory)
-    (void)call.open_out(map_out, mbytes, false);
-    hipStream_t s = b.up;
-    HIP_TRY(hipMemcpyAsync(b.edges.p, edges, ebytes, hipMemcpyHostToDevice, s));
-    if (rbytes) HIP_TRY(hipMemcpyAsync(b.rec.p, records, rbytes, hipMemcpyHostToDevice, s));
-    const double *base = (const double *)b.rec.p;
-    const int64_t stride = itemsize / 8;
-    int32_t nanflag = 0;
-    if (off_mass >= 0 && n > 0) {
-        // "If you want to make a map, provide a value for the particle mass" (io.py:636): the NaN test of the masses, on the device
-        int32_t *dflag = (int32_t *)((char *)b.edges.p + ebytes);
-        HIP_TRY(hipMemsetAsync(dflag, 0, sizeof(int32_t), s));
-        hipLaunchKernelGGL(nan_scan_strided_kernel, dim3(2048), dim3(256), 0, s, n, base + off_mass / 8, stride, dflag);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&nanflag, dflag, sizeof(nanflag), hipMemcpyDeviceToHost, s));
-    }
-    if (int rc = deposit_impl(device, (void *)s, ndim, n, base + off_x / 8, base + off_y / 8, ndim == 3 ? base + off_z / 8 : nullptr,
-                              off_mass >= 0 ? base + off_mass / 8 : nullptr, n_grid, (const double *)b.edges.p, 0, n_grid, (double *)b.map.p, nullptr, nullptr, nullptr,
-                              stride)) return rc;
-    HIP_TRY(hipMemcpyAsync(map_out, b.map.p, mbytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (nanflag) return fail(BFGX_ERR_ASSERT, "If you want to make a map, provide a value for the particle mass");
-    return BFGX_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// twiddles exp(-2 pi i k / N) and the notebook's k axis / bins (cells 12: fftfreq, linspace), built on the host
-struct FftSetup {
-    DevBuf dtw, dkl;
-    DevBuf dtab, dksb, dcnb;          // the tabulated bins (pk_table_build_kernel), built by the first binned pass when nk <= 254
-    bool tab_ready = false;
-    int lg = 0, nz = 0, tile = 1, lt = 2, threads = 256;
-    unsigned ztiles = 1;
-    size_t lds = 0, lds_bin1 = 0, lds_bin2 = 0;
-    // the instantiation of the strided kernel for this setup's (lines per tile, threads)
-    template <int BIN> const void *strided_fn()
-    {
-        if (lt == 3) return threads == 1024 ? (const void *)fft_c2c_strided_kernel<BIN, 3, 1024> : threads == 512 ? (const void *)fft_c2c_strided_kernel<BIN, 3, 512> : (const void *)fft_c2c_strided_kernel<BIN, 3, 256>;
-        return threads == 1024 ? (const void *)fft_c2c_strided_kernel<BIN, 2, 1024> : threads == 512 ? (const void *)fft_c2c_strided_kernel<BIN, 2, 512> : (const void *)fft_c2c_strided_kernel<BIN, 2, 256>;
-    }
-    template <int BIN> int strided_attr(size_t bytes)
-    {
-        HIP_TRY(hipFuncSetAttribute(strided_fn<BIN>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        return BFGX_OK;
-    }
-    template <int BIN> int strided_launch(hipStream_t s, unsigned wgs, size_t bytes, double2 *F, int N, int64_t stride, int64_t outer_stride, int nouter,
-                                          const PkBins &pb)
-    {
-        const double2 *twp = dtw.as<double2>();
-        int lg_ = lg, nz_ = nz, nzt_ = (int)ztiles;
-        PkBins pbv = pb;
-        void *args[] = {&F, &N, &lg_, &nz_, &stride, &outer_stride, &twp, &nzt_, &nouter, &pbv};
-        HIP_TRY(hipLaunchKernel(strided_fn<BIN>(), dim3(wgs), dim3((unsigned)threads), args, bytes, s));
-        return BFGX_OK;
-    }
-    int n_cu = 256;
-    double k_lo = 0, dk = 0;
-    int init(int N, double L, int nk)
-    {
-        lg = ilog2_exact(N);
-        if (lg < 3 || N > 1024) return fail(BFGX_ERR_UNSUPPORTED, "power spectrum needs n_grid = 2^m with 8 <= n_grid <= 1024");
-        nz = N / 2 + 1;
-        std::vector<double> tw(N), klin(N);
-        for (int k = 0; k < N / 2; ++k) {
-            const long double ang = -2.0L * 3.141592653589793238462643383279502884L * (long double)k / (long double)N;
-            tw[2 * k] = (double)cosl(ang); tw[2 * k + 1] = (double)sinl(ang);
-        }
-        const double two_pi = 2 * 3.141592653589793;
-        const double d = 1 / (two_pi / (L)) / N;                       // np.fft.fftfreq(Ngrd, 1 / (2 pi / Lbox) / Ngrd)
-        const double val = 1.0 / (N * d);
-        for (int i = 0; i < N; ++i) klin[i] = (double)(i < (N + 1) / 2 ? i : i - N) * val;
-        k_lo = two_pi / L;
-        const double k_hi = two_pi / L * N / 2;                        // np.linspace(k_lo, k_hi, nk + 1)
-        const double step = (k_hi - k_lo) / nk;
-        const double kb1 = (nk == 1) ? k_hi : (1.0 * step + k_lo);
-        dk = kb1 - k_lo;
-        if (dtw.up(tw.data(), sizeof(double) * N) || dkl.up(klin.data(), sizeof(double) * N)) return alloc_fail("fft tables");
-        lt = kFftTileLog2;
-        while (((size_t)N << lt) > 4096 && lt > 2) --lt;                                              // at most 64 KB of tile per workgroup
-        tile = 1 << lt;
-        // two radix-4 quads per thread and pass where the tile has that many (N = 512, 8 lines)
-        const int nq = (N >> 2) << lt;
-        threads = nq >= 512 ? 512 : 256;       // (1024 threads: one workgroup per CU, measured 15 % slower at N = 512)
-        ztiles = (unsigned)((nz + tile - 1) / tile);
-        lds = fft_c2c_lds_bytes(N, lt, 0, 0);
-        lds_bin1 = fft_c2c_lds_bytes(N, lt, nk, 1);
-        lds_bin2 = fft_c2c_lds_bytes(N, lt, nk, 2);
-        if (int rc = strided_attr<0>(lds)) return rc;
-        if (int rc = strided_attr<1>(lds_bin1)) return rc;
-        if (int rc = strided_attr<2>(lds_bin2)) return rc;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        return BFGX_OK;
-    }
-};
-
-// twiddle / wavenumber tables per (device, n_grid, L, nk): built by the first call, kept until bfgx_cache_clear, so that the
-// power-spectrum entry points only enqueue
-std::mutex g_fft_mu;
-std::map<std::tuple<int, int, double, int>, FftSetup *> g_fft;
-
-int fft_setup(int device, int N, double L, int nk, FftSetup **out)
-{
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    const auto key = std::make_tuple(device, N, L, nk);
-    auto it = g_fft.find(key);
-    if (it == g_fft.end()) {
-        FftSetup *f = new FftSetup();
-        if (int rc = f->init(N, L, nk)) { delete f; return rc; }
-        it = g_fft.emplace(key, f).first;
-    }
-    *out = it->second;
-    return BFGX_OK;
-}
-
-void fft_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    for (auto &kv : g_fft) { (void)hipSetDevice(std::get<0>(kv.first)); delete kv.second; }
-    g_fft.clear();
-}
-
-// rows of the half spectrum padded to whole 128-byte lines (8 complex values): a tile of 8 adjacent lines of a strided pass then
-// moves exactly one line per row.  nz = 257 unpadded rows start at every multiple of 16 bytes and a 64-byte tile drags in 2.7x
-// the bytes it uses (FETCH_SIZE, profiles/r02i_grid3d_summary.txt).
-inline int fft_pitch(int N) { return (N / 2 + 1 + 7) & ~7; }
-
-// real lines along the last axis + complex transforms along the middle axis of `planes` planes: map [planes][N][N] -> F [planes][N][pitch]
-int fft_planes(FftSetup &f, hipStream_t s, int N, int planes, const double *map_dev, double2 *F, int pitch)
-{
-    {
-        // two line pairs per workgroup of 2 x 128 threads up to N = 512 (a workgroup per pair is launch-bound there: 0.51 -> 0.47 ms at
-        // 512^3; 4 pairs, or 64 / 256 threads per pair: 0.52 - 0.60), one pair x 256 threads above (N = 1024: 3.5 ms; 2 x 128: 4.7)
-        const size_t npairs = (size_t)planes * N / 2;
-        const bool two = N <= 512 && npairs % 2 == 0;
-        const unsigned wg = (unsigned)(two ? npairs / 2 : npairs);
-        const size_t ldsb = (two ? 2 : 1) * sizeof(double2) * N;
-#define BFGX_R2C(P, T) hipLaunchKernelGGL((fft_r2c_lines_kernel<P, T>), dim3(wg), dim3(P * T), ldsb, s, map_dev, F, N, f.lg, f.dtw.as<double2>(), pitch)
-        if (two) BFGX_R2C(2, 128);
-        else BFGX_R2C(1, 256);
-#undef BFGX_R2C
-    }
-    HIP_TRY(hipGetLastError());
-    // axis 1: element (a, i, c) at (a * N + i) * pitch + c
-    const unsigned wgs = f.ztiles * (unsigned)planes;
-    if (int rc = f.strided_launch<0>(s, wgs, f.lds, F, N, (int64_t)pitch, (int64_t)N * pitch, planes, PkBins{})) return rc;
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-// complex transforms along the FIRST axis of F [N][nb][pitch] (the columns b0 .. b0 + nb of the middle axis) fused with the P(k)
-// sums: the transformed tiles are binned from LDS and never written back (F is scratch afterwards)
-int fft_axis0_pk(FftSetup &f, hipStream_t s, int N, int nb, int b0, double2 *F, int pitch, int nk, double *pk_sum_dev, double *k_sum_dev,
-                 unsigned long long *counts_dev)
-{
-    HIP_TRY(hipMemsetAsync(pk_sum_dev, 0, sizeof(double) * nk, s));
-    HIP_TRY(hipMemsetAsync(k_sum_dev, 0, sizeof(double) * nk, s));
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(unsigned long long) * nk, s));
-    // axis 0: element (i, b, c) at (i * nb + b) * pitch + c.  A fixed number of workgroups strides over the tiles, each flushing
-    // its histogram once (3 nk global atomics per workgroup, not per tile)
-    const int64_t ntiles = (int64_t)f.ztiles * nb;
-    const unsigned wgs = (unsigned)std::min<int64_t>(ntiles, (int64_t)f.n_cu * std::max<size_t>(1, (size_t)(160 * 1024) / f.lds_bin2));
-    PkBins pb{f.dkl.as<double>(), f.k_lo, f.dk, 1.0 / f.dk, nk, b0, pk_sum_dev, k_sum_dev, counts_dev, nullptr, pitch};
-    // bins, counts and |k| sums are functions of (N, L, nk) alone: tabulated by the first call (one byte per mode), looked up afterwards
-    const bool use_tab = nk <= 254;
-    if (use_tab && !f.tab_ready) {
-        if (f.dtab.up(nullptr, ((size_t)N * f.ztiles * N) << f.lt) || f.dksb.up(nullptr, sizeof(double) * (size_t)N * nk) ||
-            f.dcnb.up(nullptr, sizeof(unsigned long long) * (size_t)N * nk))
-            return alloc_fail("P(k) bin table");
-        PkBins all = pb;
-        all.b0 = 0;
-        hipLaunchKernelGGL(pk_table_build_kernel, dim3((unsigned)N), dim3(kFftBlock), 16 * (size_t)nk, s, all, N, f.nz, f.lt, (int)f.ztiles, f.dtab.as<uint8_t>(),
-                           f.dksb.as<double>(), f.dcnb.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));                    // (built once; later calls on any stream find it complete)
-        f.tab_ready = true;
-    }
-    if (use_tab) {
-        pb.tab = f.dtab.as<uint8_t>();
-        if (int rc = f.strided_launch<2>(s, wgs, f.lds_bin2, F, N, (int64_t)nb * pitch, (int64_t)pitch, nb, pb)) return rc;
-        hipLaunchKernelGGL(pk_table_sums_kernel, dim3((unsigned)nk), dim3(256), 0, s, nk, b0, nb, f.dksb.as<double>(),
-                           f.dcnb.as<unsigned long long>(), k_sum_dev, counts_dev);
-        HIP_TRY(hipGetLastError());
-        return BFGX_OK;
-    }
-    if (int rc = f.strided_launch<1>(s, wgs, f.lds_bin1, F, N, (int64_t)nb * pitch, (int64_t)pitch, nb, pb)) return rc;
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t bfgx_fft_pitch(int32_t n_grid) { return fft_pitch(n_grid); }
-
-int64_t bfgx_power_spectrum_work_doubles(int32_t n_grid)
-{
-    return 2 * (int64_t)n_grid * n_grid * fft_pitch(n_grid);
-}
-
-int bfgx_power_spectrum_device(int device, void *hip_stream, int32_t n_grid, const double *map_dev, double L, int32_t nk,
-                               double *work_dev, double *pk_sum_dev, double *k_sum_dev, unsigned long long *counts_dev)
-{
-    if (!map_dev || !work_dev || !pk_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nk < 1 || nk > 2048 || !(L > 0)) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048, L > 0");
-    if (reinterpret_cast<uintptr_t>(work_dev) & 15) return fail(BFGX_ERR_INVALID, "work_dev must be 16-byte aligned (complex values)");
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    FftSetup *f = nullptr;
-    if (int rc = fft_setup(device, n_grid, L, nk, &f)) return rc;
-    const int pitch = fft_pitch(n_grid);
-    if (int rc = fft_planes(*f, s, n_grid, n_grid, map_dev, (double2 *)work_dev, pitch)) return rc;
-    return fft_axis0_pk(*f, s, n_grid, n_grid, 0, (double2 *)work_dev, pitch, nk, pk_sum_dev, k_sum_dev, counts_dev);
-}
-
-int bfgx_fft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, int32_t planes, const double *map_dev, double *work_dev)
-{
-    if (!map_dev || !work_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (planes < 1 || planes > n_grid || ((int64_t)planes * n_grid) % 2) return fail(BFGX_ERR_INVALID, "slab of %d planes", planes);
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    FftSetup *f = nullptr;
-    if (int rc = fft_setup(device, n_grid, 1.0, 1, &f)) return rc;
-    return fft_planes(*f, s, n_grid, planes, map_dev, (double2 *)work_dev, fft_pitch(n_grid));
-}
-
-int bfgx_fft_slab_axis0_pk_device(int device, void *hip_stream, int32_t n_grid, int32_t ncols, int32_t col0, double *work_dev, double L,
-                                  int32_t nk, double *pk_sum_dev, double *k_sum_dev, unsigned long long *counts_dev)
-{
-    if (!work_dev || !pk_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nk < 1 || nk > 2048 || !(L > 0)) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048, L > 0");
-    if (ncols < 1 || col0 < 0 || col0 + ncols > n_grid) return fail(BFGX_ERR_INVALID, "columns [%d, %d) outside the grid", col0, col0 + ncols);
-    if (int rc = select_device(device)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    FftSetup *f = nullptr;
-    if (int rc = fft_setup(device, n_grid, L, nk, &f)) return rc;
-    return fft_axis0_pk(*f, s, n_grid, ncols, col0, (double2 *)work_dev, fft_pitch(n_grid), nk, pk_sum_dev, k_sum_dev, counts_dev);
-}
-
-int bfgx_power_spectrum(int device, int32_t n_grid, const double *map, double L, int32_t nk, double *pk, double *kcen, int64_t *counts)
-{
-    if (!map || !pk || !kcen || !counts) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (ilog2_exact(n_grid) < 3 || n_grid > 1024) return fail(BFGX_ERR_UNSUPPORTED, "power spectrum needs n_grid = 2^m with 8 <= n_grid <= 1024");
-    if (nk < 1 || nk > 2048) return fail(BFGX_ERR_INVALID, "power spectrum needs 1 <= nk <= 2048");
-    HostCall c(device);
-    const size_t N = n_grid;
-    std::vector<double> hp(nk), hk(nk);                      // the bins' sums, divided by their counts below
-    std::vector<unsigned long long> hc(nk);
-    const double *dm = c.in(map, N * N * N);
-    double *dw = c.scratch<double>(bfgx_power_spectrum_work_doubles(n_grid)), *dp = c.out(hp.data(), nk), *dk = c.out(hk.data(), nk);
-    unsigned long long *dc = c.out(hc.data(), nk);
-    if (int rc = c.ready()) return rc;
-    if (int rc = bfgx_power_spectrum_device(device, nullptr, n_grid, dm, L, nk, dw, dp, dk, dc)) return rc;
-    if (int rc = c.finish()) return rc;
-    for (int i = 0; i < nk; ++i) {
-        counts[i] = (int64_t)hc[i];
-        pk[i] = hp[i] / (double)hc[i];           // 0 / 0 -> NaN for empty bins, as np.bincount(...) / k_c gives
-        kcen[i] = hk[i] / (double)hc[i];
-    }
-    return BFGX_OK;
 }
 
 }  // extern "C"

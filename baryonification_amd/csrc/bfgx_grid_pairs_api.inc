@@ -8,22 +8,17 @@
 
 namespace {
 
-template <int DIM, int MODE>
-void launch_grid_pairs_t(GridPairs *h, int64_t j0, int64_t j1, const double *vals, double *out)
-{
-    bfgx_grid_plan *p = h->plan.get();
-    const int64_t it0 = h->item0_h[(size_t)j0], it1 = h->item0_h[(size_t)j1];
-    const unsigned blocks = (unsigned)std::min<int64_t>(it1 - it0, (int64_t)p->n_cu * 8);
-    hipLaunchKernelGGL((grid_pairs_kernel<DIM, MODE>), dim3(blocks), dim3(kGridBlock), 0, p->stream, p->geom, (const GridHaloRec *)p->recs,
-                       (const int32_t *)h->item_halo.p, (const int64_t *)h->item0.p, (const int64_t *)h->off.p, it0, it1, h->off_h[(size_t)j0], vals, out);
-}
-
 template <int MODE>
 int launch_grid_pairs(GridPairs *h, int64_t j0, int64_t j1, const double *vals, double *out)
 {
-    if (h->item0_h[(size_t)j1] == h->item0_h[(size_t)j0]) return BFGX_OK;
-    if (h->plan->geom.ndim == 3) launch_grid_pairs_t<3, MODE>(h, j0, j1, vals, out);
-    else launch_grid_pairs_t<2, MODE>(h, j0, j1, vals, out);
+    bfgx_grid_plan *p = h->plan.get();
+    const int64_t it0 = h->item0_h[(size_t)j0], it1 = h->item0_h[(size_t)j1];
+    if (it1 == it0) return BFGX_OK;
+    const unsigned blocks = (unsigned)std::min<int64_t>(it1 - it0, (int64_t)p->n_cu * 8);
+    grid_dim(p->geom.ndim, [&](auto dim) {
+        hipLaunchKernelGGL((grid_pairs_kernel<decltype(dim)::value, MODE>), dim3(blocks), dim3(kGridBlock), 0, p->stream, p->geom, (const GridHaloRec *)p->recs,
+                           (const int32_t *)h->item_halo.p, (const int64_t *)h->item0.p, (const int64_t *)h->off.p, it0, it1, h->off_h[(size_t)j0], vals, out);
+    });
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }

@@ -8,7 +8,7 @@
 // structure over the 10^8 particles, every particle read and written exactly once.
 //
 //   snap_halo_prep_kernel    per-halo scalars (:217-222) + cell range + per-cell counts
-//   scan_* kernels           exclusive scan of the per-cell counts
+//   exclusive_scan           of the per-cell counts (bfgx_scan.hpp)
 //   snap_halo_fill_kernel    halo index into each touched cell's list
 //   snap_displace_kernel     per particle: min-image separation (:67-92), displacement read-out, offset (:225-252),
 //                            periodic re-wrap (:254-262).  KEYS = true (BaryonifySnapshot.process() followed by
@@ -18,6 +18,7 @@
 #pragma once
 #include "bfgx_kernels.hpp"
 #include "bfgx_tables.hpp"
+#include "bfgx_scan.hpp"
 #include "bfgx_deposit.hpp"
 
 namespace bfgx {
@@ -202,52 +203,6 @@ snap_halo_fill_kernel(SnapGeom g, int64_t nh, const SnapHaloRec *__restrict__ re
         const int64_t cell = snap_cube_cell(g, r, c);
         entries[cell_start[cell] + atomicAdd(cell_cursor + cell, 1)] = en;
     }
-}
-
-// ---- exclusive scan of int32 counts (n up to 2^31): 4096 elements per block, block sums scanned by one block
-constexpr int kScanPerBlock = 4 * kTabThreads;
-
-__global__ void __launch_bounds__(kTabThreads)
-scan_blocks_kernel(int64_t n, const int32_t *__restrict__ in, int32_t *__restrict__ out, int32_t *__restrict__ block_sums, int in_stride)
-{
-    // in_stride: words between two counts (counters that many workgroups add to sit a cache line apart)
-    __shared__ int sh[kTabThreads];
-    const int64_t base = (int64_t)blockIdx.x * kScanPerBlock + 4 * (int64_t)threadIdx.x;
-    int v[4], s = 0;
-    for (int q = 0; q < 4; ++q) { v[q] = (base + q < n) ? in[(base + q) * in_stride] : 0; s += v[q]; }
-    int tot;
-    int pre = block_excl_scan_int(s, sh, tot);
-    for (int q = 0; q < 4; ++q) { if (base + q < n) out[base + q] = pre; pre += v[q]; }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-// one block: exclusive scan of up to kScanPerBlock block sums, in place; total -> *total_out
-__global__ void __launch_bounds__(kTabThreads)
-scan_sums_kernel(int nb, int32_t *__restrict__ block_sums, int64_t *__restrict__ total_out)
-{
-    __shared__ int sh[kTabThreads];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nb; c0 += kScanPerBlock) {
-        const int base = c0 + 4 * threadIdx.x;
-        int v[4], s = 0;
-        for (int q = 0; q < 4; ++q) { v[q] = (base + q < nb) ? block_sums[base + q] : 0; s += v[q]; }
-        int tot;
-        int pre = block_excl_scan_int(s, sh, tot) + (int)carry;
-        for (int q = 0; q < 4; ++q) { if (base + q < nb) block_sums[base + q] = pre; pre += v[q]; }
-        __syncthreads();
-        if (threadIdx.x == 0) carry += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ void __launch_bounds__(256)
-scan_add_kernel(int64_t n, int32_t *__restrict__ out, const int32_t *__restrict__ block_sums)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] += block_sums[i / kScanPerBlock];
 }
 
 // one bit per cell: does any halo list the cell?  nc^3 bits (256 KB at 128^3) stay cache-resident, so the ~60 % of the

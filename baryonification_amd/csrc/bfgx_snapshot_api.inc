@@ -54,15 +54,14 @@ int bfgx_snapshot_plan_create(int device, void *hip_stream, const bfgx_model *mo
     g.ncell = 1;
     for (int d = 0; d < ndim; ++d) g.ncell *= g.nc;
     p->nscan = g.ncell + 1;
-    p->nblocks = (int)((p->nscan + kScanPerBlock - 1) / kScanPerBlock);
+    p->nblocks = scan_block_count(p->nscan);
     DevList &mem = p->mem;
     p->entry_capacity = 16 * max_halos + 65536;
     if (mem.alloc(p->recs, (size_t)std::max<int64_t>(max_halos, 1)) || mem.alloc(p->count, (size_t)p->nscan) || mem.alloc(p->start, (size_t)p->nscan) ||
         mem.alloc(p->cursor, (size_t)p->nscan) || mem.alloc(p->bsum, (size_t)p->nblocks) || mem.alloc(p->total, 1) || mem.alloc(p->flags, 1) ||
         mem.alloc(p->pairs, 1) || mem.alloc(p->bitmap, (size_t)((g.ncell + 31) / 32)) || mem.alloc(p->entries, (size_t)p->entry_capacity))
         return bail(alloc_fail("snapshot workspace"));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) p->n_cu = prop.multiProcessorCount;
+    p->n_cu = device_cu_count(device);
     *out = p;
     return BFGX_OK;
 }
@@ -100,19 +99,13 @@ static int snap_lists_stage(bfgx_snapshot_plan *p, const bfgx_grid_catalog *halo
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(cell_bitmap_kernel, dim3((unsigned)(((g.ncell + 31) / 32 + 255) / 256)), dim3(256), 0, s, g.ncell, (const int32_t *)p->count, p->bitmap);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(p->nblocks), dim3(kTabThreads), 0, s, p->nscan, (const int32_t *)p->count, p->start, p->bsum, 1);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kTabThreads), 0, s, p->nblocks, p->bsum, p->total);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((p->nscan + 255) / 256)), dim3(256), 0, s, p->nscan, p->start, (const int32_t *)p->bsum);
+    exclusive_scan(s, p->nscan, p->count, p->start, p->bsum, p->total);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, p->total, sizeof(total), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (total > (int64_t)INT32_MAX) return fail(BFGX_ERR_INVALID, "halo-cell lists exceed 2^31 entries: use fewer cells (BFGX_SNAP_CELLS) or split the catalog");
-    if (total > p->entry_capacity) {             // grow the list storage (rare: very large query balls)
-        const int64_t cap = total + total / 4 + 1024;
-        HIP_TRY(p->mem.regrow(p->entries, (size_t)cap));
-        p->entry_capacity = cap;
-    }
+    if (total > p->entry_capacity) if (int rc = grow_list(p->mem, p->entries, p->entry_capacity, total)) return rc;   // (rare: very large query balls)
     if (halos->n > 0 && total > 0) {
         hipLaunchKernelGGL(snap_halo_fill_kernel, dim3((unsigned)((halos->n + 256 / kWave - 1) / (256 / kWave))), dim3(256), 0, s, g, halos->n, (const SnapHaloRec *)p->recs, (const int32_t *)p->start,
                            p->cursor, p->entries);
