@@ -231,6 +231,13 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_bispectrum': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_cross_power_spectrum_work_doubles': (C.c_int64, [C.c_int32]),
+    'bfgx_cross_power_spectrum_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_fft_slab_axis0_xpk_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_cross_power_spectrum': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_grid_plan_timing_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'bfgx_grid_plan_timing_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_deposit_particles_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -2146,6 +2146,9 @@ int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const d
 // bispectrum of gridded 3-D maps: inverse slab transforms, k-shell fields, triangle sums
 #include "bfgx_bispec_api.inc"
 
+// cross power spectrum of two gridded 3-D maps: the cross modes of the last FFT pass, window weights
+#include "bfgx_xpk_api.inc"
+
 // ------------------------------------------------------------------------------ particle snapshots (8f-2)
 #include "bfgx_snapshot_api.inc"
 
@@ -2188,6 +2191,7 @@ extern "C" void bfgx_cache_clear(void)
     dep_release_all();           // workspace of the tiled particle deposit (bfgx_deposit_api.inc)
     fft_release_all();           // twiddle / wavenumber tables of the power spectrum
     bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
+    xpk_release_all();           // window tables of the cross power spectrum (bfgx_xpk_api.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries
     g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
     deprec_release_all();        // device buffers of the deposit's records entry

@@ -10,6 +10,10 @@
 // 128-byte lines, do their first radix-4 pass on the way into LDS and their last pass on the way out (fft_c2c_strided_kernel).
 // The LAST strided pass writes nothing back: its results are binned as they leave the butterflies (|F|^2, |k|, counts per linear
 // k-bin), so the spectrum crosses HBM 5 times instead of 8.
+// The CROSS modes of that last pass (BIN 3, 4 of fft_c2c_strided_kernel) bin two maps at once: as a coefficient of map B leaves the
+// butterflies it meets map A's finished coefficient, read from memory at the same address, and |F_A|^2, |F_B|^2 and Re(F_A conj F_B)
+// go into three histograms, optionally divided by the mass-assignment window.  Like the auto spectrum they are sums by atomics (into
+// LDS, then once per workgroup into the nk-sized outputs): correct to rounding, not bitwise reproducible from call to call.
 // N must be a power of two, 8 <= N <= 1024.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -105,6 +109,14 @@ struct PkBins {
     int tab_pitch;
 };
 
+// what the cross modes of the last pass need besides: map A's finished spectrum (the layout of the pass's own data, read-only), the
+// window weights win[i] = s(n_i)^(-2p), i < N (all 1 without a window), and the two further sums (|F_A|^2 goes to PkBins::pk_sum)
+struct XpkArgs {
+    const double2 *spec_a;
+    const double *win;
+    double *pbb_sum, *pab_sum;
+};
+
 // the k-bin of mode (a, b, c): k = sqrt(klin[a]^2 + klin[c]^2 + klin[b]^2) (the notebook's summation order), bin = floor((k - kb0) / dk);
 // -1 outside [0, nk)
 __device__ inline int pk_bin_of(const PkBins &pb, int a, int b, int c, double &k)
@@ -115,6 +127,17 @@ __device__ inline int pk_bin_of(const PkBins &pb, int a, int b, int c, double &k
     const double ue = (k - pb.kb0) * pb.inv_dk;
     double u = floor(ue);
     if (fabs(ue - rint(ue)) < 1e-6 * (fabs(ue) + 1.0)) u = floor((k - pb.kb0) / pb.dk);
+    if (!(u >= 0.0) || !(u < (double)pb.nk)) return -1;
+    return (int)u;
+}
+
+// the same bin by the division alone, which is what pk_bin_of's floor is made to agree with.  The cross modes use it: they hold four more
+// pointers than the auto pass and have no scalar registers left for the reciprocal and its test.
+__device__ inline int pk_bin_div(const PkBins &pb, int a, int b, int c, double &k)
+{
+    const double ka = pb.klin[a], kb = pb.klin[b], kc = pb.klin[c];
+    k = sqrt(add_nc(add_nc(mul_nc(ka, ka), mul_nc(kc, kc)), mul_nc(kb, kb)));
+    const double u = floor((k - pb.kb0) / pb.dk);
     if (!(u >= 0.0) || !(u < (double)pb.nk)) return -1;
     return (int)u;
 }
@@ -199,12 +222,14 @@ pk_table_sums_kernel(int nk, int b0, int nb, const double *__restrict__ ksum_b, 
 __device__ inline int fft_swz(int p) { return p ^ ((p >> 2) & 3); }
 
 // LDS of one workgroup of the strided passes: the tile, the twiddles, then the histogram (BIN 1: |F|^2, |k|, counts; BIN 2: |F|^2 and
-// the tile's slice of the bin table)
+// the tile's slice of the bin table; BIN 3: the three sums of a cross spectrum and the slice; BIN 4: the three sums, |k|, counts)
 __host__ __device__ inline size_t fft_c2c_lds_bytes(int N, int lt, int nk, int bin)
 {
     size_t a = sizeof(double2) * (((size_t)N << lt) + (size_t)(N >> 1));
     if (bin == 1) a += sizeof(double) * 3 * (size_t)nk;
     if (bin == 2) a += sizeof(double) * (size_t)nk + ((size_t)N << lt);
+    if (bin == 3) a += sizeof(double) * 3 * (size_t)nk + ((size_t)N << lt);
+    if (bin == 4) a += sizeof(double) * 5 * (size_t)nk;
     return a;
 }
 
@@ -221,23 +246,46 @@ __host__ __device__ inline size_t fft_c2c_lds_bytes(int N, int lt, int nk, int b
 // BIN: 0 = in place; 1 = binned, bins computed per mode; 2 = binned, bins from the table (PkBins::tab, [b][kz tile][row][line], whose
 // slice for the tile is fetched into LDS together with the tile).  Binned passes write nothing back: the spectrum itself is not an
 // output; the histogram is flushed once at the end; the line index is then the FIRST array axis and o the column b0 + o of the middle axis.
-template <int BIN, int LT, int NT>
+// BIN 3 and 4 are the cross forms of 2 and 1: `data` is map B's spectrum before this pass and is only read;
+// every coefficient f_b that leaves the last butterflies is paired with f_a = xa.spec_a[o * outer_stride + row * stride + kz0 + l], map
+// A's finished coefficient of the same mode, and w m |f_a|^2, w m |f_b|^2, w m Re(f_a conj f_b) go into three histograms (m: the mirror
+// weight; w = win[a] win[b] win[c]).  A thread issues its loads of f_a -- the access pattern of the BIN 0 store -- before the LDS reads and
+// the arithmetic of its butterfly, so that they are in flight under it.  The pad columns of spec_a are loaded with the tile and, like
+// those of `data`, never binned: table byte 255 (BIN 3), kz0 + l < nz (BIN 4).  Bins, counts and sums of |k| are those of BIN 2 and 1.
+// The cross modes take one more kernel argument, XA = XpkArgs; BIN 0, 1, 2 are instantiated with the pack empty, which is the kernel
+// as it was before the cross modes existed, argument for argument (one body inlined into two kernels instead changed the register
+// allocation of BIN 0: 62 -> 78 VGPRs at LT = 2).
+__host__ __device__ inline XpkArgs xpk_args() { return XpkArgs{nullptr, nullptr, nullptr, nullptr}; }
+__host__ __device__ inline XpkArgs xpk_args(const XpkArgs &a) { return a; }
+
+template <int BIN, int LT, int NT, typename... XA>
 __global__ void __launch_bounds__(NT, NT == 1024 ? 8 : 4)       // (1024 threads: 64 VGPRs, so that the two workgroups LDS holds both run)
 fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int64_t stride, int64_t outer_stride,
-                       const double2 *__restrict__ tw, int nzt, int nouter, PkBins pb)
+                       const double2 *__restrict__ tw, int nzt, int nouter, PkBins pb, XA... xargs)
 {
+    static_assert(sizeof...(XA) == (BIN >= 3 ? 1 : 0) && BIN >= 0 && BIN <= 4, "BIN 3 and 4 take XpkArgs, the others nothing");
+    const XpkArgs xa = xpk_args(xargs...);
+
+    constexpr bool XPK = BIN >= 3;                                    // cross modes
+    constexpr bool TAB = BIN == 2 || BIN == 3;                        // bins from the table
     // a tile = the (1 << LT) adjacent lines kz0 .. kz0 + (1 << LT) of one `o`; rows are padded (fft_pitch), so the last tile of
     // a row reads up to 7 pad columns: lines of their own, transformed like the others and never binned or looked at
     constexpr int NL = 1 << LT;
     extern __shared__ double2 fbuf[];
     double2 *twl = fbuf + ((size_t)N << LT);
-    double *hp = reinterpret_cast<double *>(twl + (N >> 1)), *hk = hp + pb.nk;
+    const int nsum = XPK ? 3 * pb.nk : pb.nk;                         // the |F|^2 histograms: one, or |F_A|^2, |F_B|^2, Re(F_A conj F_B)
+    double *hp = reinterpret_cast<double *>(twl + (N >> 1)), *hk = hp + nsum;
     unsigned long long *hc = reinterpret_cast<unsigned long long *>(hk + pb.nk);
-    uint8_t *tb8 = reinterpret_cast<uint8_t *>(hp + pb.nk);           // (BIN 2; BIN 1 has hk there)
+    uint8_t *tb8 = reinterpret_cast<uint8_t *>(hp + nsum);            // (BIN 2, 3; BIN 1 and 4 have hk there)
+    double *hbb = hp + pb.nk, *hab = hbb + pb.nk;                     // (BIN 3, 4)
     const int tid = threadIdx.x;
     for (int i = tid; i < (N >> 1); i += NT) twl[i] = tw[i];
     if (BIN) {
-        for (int i = tid; i < pb.nk; i += NT) { hp[i] = 0.0; if (BIN == 1) { hk[i] = 0.0; hc[i] = 0ull; } }
+        for (int i = tid; i < pb.nk; i += NT) {
+            hp[i] = 0.0;
+            if (!TAB) { hk[i] = 0.0; hc[i] = 0ull; }
+            if (XPK) { hbb[i] = 0.0; hab[i] = 0.0; }
+        }
     }
     const int rem = log2n - 2;                                       // bits left after the first pass (N >= 8)
     const int last_bits = (rem & 1) ? 1 : 2;
@@ -249,7 +297,7 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
         const int kz0 = (int)(tl % nzt) << LT, o = (int)(tl / nzt);
         double2 *base = data + (int64_t)o * outer_stride + kz0;
         __syncthreads();                                             // (the previous tile's readers are done with fbuf and tb8)
-        if (BIN == 2) {
+        if (TAB) {
             const uint32_t *src = reinterpret_cast<const uint32_t *>(pb.tab + ((((size_t)(pb.b0 + o) * nzt + (kz0 >> LT)) * N) << LT));
             for (int t = tid; t < (N << LT) / 4; t += NT) reinterpret_cast<uint32_t *>(tb8)[t] = src[t];
         }
@@ -303,6 +351,28 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
                 }
             } else if (kz0 + l < nz) pk_bin_sample(pb, N, row, pb.b0 + o, kz0 + l, f, hp, hk, hc);
         };
+        // cross modes: f_b with map A's f_a of the same (row, line, column); wr = win[row], wl = win[column] win[line]
+        const double2 *base_a = XPK ? xa.spec_a + (int64_t)o * outer_stride + kz0 : nullptr;
+        const double wcol = XPK ? xa.win[pb.b0 + o] : 1.0;
+        auto emit_x = [&](int row, int l, double2 fb, double2 fa, double wr, double wl) {
+            const int cc = kz0 + l;
+            int bin;
+            double k = 0.0;
+            if (TAB) {
+                bin = tb8[(row << LT) + l];                                        // (pad columns carry 255)
+                if (bin == 255) return;
+            } else {
+                if (cc >= nz) return;
+                bin = pk_bin_div(pb, row, pb.b0 + o, cc, k);
+                if (bin < 0) return;
+            }
+            const int mult = (cc > 0 && cc < (N >> 1)) ? 2 : 1;
+            const double w = (double)mult * (wr * wl);
+            atomicAdd(hp + bin, w * (fa.x * fa.x + fa.y * fa.y));
+            atomicAdd(hbb + bin, w * (fb.x * fb.x + fb.y * fb.y));
+            atomicAdd(hab + bin, w * (fa.x * fb.x + fa.y * fb.y));
+            if (!TAB) { atomicAdd(hk + bin, mult * k); atomicAdd(hc + bin, (unsigned long long)mult); }
+        };
         if (last_bits == 1) {
             const int h = N >> 1;
             for (int t = tid; t < (h << LT); t += NT) {
@@ -310,7 +380,19 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
                 // binned: neighbouring lanes take rows 37 apart (an odd multiplier permutes the rows): rows next to each other have
                 // almost the same |k| and would serialise on one histogram cell
                 const int i = BIN ? ((i0 * 37) & (h - 1)) : i0;
+                double2 fa0 = {}, fa1 = {};
+                double wr0 = 1.0, wr1 = 1.0, wl = 1.0;
+                if (XPK) {                                                         // issued first: in flight under the butterfly
+                    const double2 *sa = base_a + (int64_t)i * stride + l;
+                    fa0 = sa[0]; fa1 = sa[(int64_t)h * stride];
+                    wr0 = xa.win[i]; wr1 = xa.win[i + h]; wl = wcol * xa.win[kz0 + l];
+                }
                 const double2 u = fbuf[(fft_swz(i) << LT) + l], v = cmul(twl[i], fbuf[(fft_swz(i + h) << LT) + l]);
+                if (XPK) {
+                    emit_x(i, l, make_double2(u.x + v.x, u.y + v.y), fa0, wr0, wl);
+                    emit_x(i + h, l, make_double2(u.x - v.x, u.y - v.y), fa1, wr1, wl);
+                    continue;
+                }
                 emit(i, l, make_double2(u.x + v.x, u.y + v.y));
                 emit(i + h, l, make_double2(u.x - v.x, u.y - v.y));
             }
@@ -319,6 +401,14 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
             for (int t = tid; t < (mq << LT); t += NT) {
                 const int l = t & (NL - 1), b0_ = t >> LT;
                 const int p = BIN ? ((b0_ * 37) & (mq - 1)) : b0_;
+                double2 fa0 = {}, fa1 = {}, fa2 = {}, fa3 = {};
+                double wr0 = 1.0, wr1 = 1.0, wr2 = 1.0, wr3 = 1.0, wl = 1.0;
+                if (XPK) {                                                         // issued first: in flight under the butterfly
+                    const double2 *sa = base_a + (int64_t)p * stride + l;
+                    fa0 = sa[0]; fa1 = sa[qs]; fa2 = sa[2 * qs]; fa3 = sa[3 * qs];     // rows p, p + mq, p + 2 mq, p + 3 mq
+                    wr0 = xa.win[p]; wr1 = xa.win[p + mq]; wr2 = xa.win[p + 2 * mq]; wr3 = xa.win[p + 3 * mq];
+                    wl = wcol * xa.win[kz0 + l];
+                }
                 const double2 w1 = twl[p * 2], w2 = twl[p];
                 const double2 w3 = make_double2(w2.y, -w2.x);
                 const double2 a0 = fbuf[(fft_swz(p) << LT) + l], a1 = fbuf[(fft_swz(p + mq) << LT) + l];
@@ -327,6 +417,13 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
                 const double2 b0 = make_double2(a0.x + t1.x, a0.y + t1.y), b1 = make_double2(a0.x - t1.x, a0.y - t1.y);
                 const double2 b2 = make_double2(a2.x + t3.x, a2.y + t3.y), b3 = make_double2(a2.x - t3.x, a2.y - t3.y);
                 const double2 u2 = cmul(w2, b2), u3 = cmul(w3, b3);
+                if (XPK) {
+                    emit_x(p, l, make_double2(b0.x + u2.x, b0.y + u2.y), fa0, wr0, wl);
+                    emit_x(p + 2 * mq, l, make_double2(b0.x - u2.x, b0.y - u2.y), fa2, wr2, wl);
+                    emit_x(p + mq, l, make_double2(b1.x + u3.x, b1.y + u3.y), fa1, wr1, wl);
+                    emit_x(p + 3 * mq, l, make_double2(b1.x - u3.x, b1.y - u3.y), fa3, wr3, wl);
+                    continue;
+                }
                 emit(p, l, make_double2(b0.x + u2.x, b0.y + u2.y));
                 emit(p + 2 * mq, l, make_double2(b0.x - u2.x, b0.y - u2.y));
                 emit(p + mq, l, make_double2(b1.x + u3.x, b1.y + u3.y));
@@ -337,7 +434,12 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
     if (BIN) {
         __syncthreads();
         for (int i = tid; i < pb.nk; i += NT) {
-            if (BIN == 2) { if (hp[i] != 0.0) atomicAdd(pb.pk_sum + i, hp[i]); }
+            if (XPK) {
+                if (TAB ? (hp[i] != 0.0 || hbb[i] != 0.0 || hab[i] != 0.0) : (hc[i] != 0ull)) {
+                    atomicAdd(pb.pk_sum + i, hp[i]); atomicAdd(xa.pbb_sum + i, hbb[i]); atomicAdd(xa.pab_sum + i, hab[i]);
+                    if (!TAB) { atomicAdd(pb.k_sum + i, hk[i]); atomicAdd(pb.counts + i, hc[i]); }
+                }
+            } else if (BIN == 2) { if (hp[i] != 0.0) atomicAdd(pb.pk_sum + i, hp[i]); }
             else if (hc[i]) { atomicAdd(pb.pk_sum + i, hp[i]); atomicAdd(pb.k_sum + i, hk[i]); atomicAdd(pb.counts + i, hc[i]); }
         }
     }

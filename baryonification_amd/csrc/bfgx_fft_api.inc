@@ -1,5 +1,6 @@
 // bfgx_fft_api.inc -- host side of the 3-D FFT and C ABI of the power spectrum of gridded maps (include/bfgx.h, "power spectrum");
-// included by bfgx_api.hip after bfgx_deposit_api.inc.  bfgx_bispec_api.inc builds on FftSetup, fft_setup, fft_planes and fft_pitch.
+// included by bfgx_api.hip after bfgx_deposit_api.inc.  bfgx_bispec_api.inc and bfgx_xpk_api.inc build on FftSetup, fft_setup, fft_planes
+// and fft_pitch.
 // Kernels: bfgx_fft.hpp.
 
 namespace {
@@ -13,7 +14,7 @@ struct FftSetup {
     bool tab_ready = false;
     int lg = 0, nz = 0, tile = 1, lt = 2, threads = 256;
     unsigned ztiles = 1;
-    size_t lds = 0, lds_bin1 = 0, lds_bin2 = 0;
+    size_t lds = 0, lds_bin1 = 0, lds_bin2 = 0, lds_bin3 = 0, lds_bin4 = 0;
     // the instantiation of the strided kernel for this setup's (lines per tile, threads)
     template <int BIN> const void *strided_fn()
     {
@@ -33,6 +34,28 @@ struct FftSetup {
         PkBins pbv = pb;
         void *args[] = {&F, &N, &lg_, &nz_, &stride, &outer_stride, &twp, &nzt_, &nouter, &pbv};
         HIP_TRY(hipLaunchKernel(strided_fn<BIN>(), dim3(wgs), dim3((unsigned)threads), args, bytes, s));
+        return BFGX_OK;
+    }
+    // the cross modes (BIN 3, 4; bfgx_xpk_api.inc): instantiated for the thread counts init() selects
+    template <int BIN> const void *xpk_fn()
+    {
+        if (lt == 3) return threads == 512 ? (const void *)fft_c2c_strided_kernel<BIN, 3, 512, XpkArgs> : (const void *)fft_c2c_strided_kernel<BIN, 3, 256, XpkArgs>;
+        return threads == 512 ? (const void *)fft_c2c_strided_kernel<BIN, 2, 512, XpkArgs> : (const void *)fft_c2c_strided_kernel<BIN, 2, 256, XpkArgs>;
+    }
+    template <int BIN> int xpk_attr(size_t bytes)
+    {
+        HIP_TRY(hipFuncSetAttribute(xpk_fn<BIN>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        return BFGX_OK;
+    }
+    template <int BIN> int xpk_launch(hipStream_t s, unsigned wgs, size_t bytes, double2 *F, int N, int64_t stride, int64_t outer_stride, int nouter,
+                                      const PkBins &pb, const XpkArgs &xa)
+    {
+        const double2 *twp = dtw.as<double2>();
+        int lg_ = lg, nz_ = nz, nzt_ = (int)ztiles;
+        PkBins pbv = pb;
+        XpkArgs xav = xa;
+        void *args[] = {&F, &N, &lg_, &nz_, &stride, &outer_stride, &twp, &nzt_, &nouter, &pbv, &xav};
+        HIP_TRY(hipLaunchKernel(xpk_fn<BIN>(), dim3(wgs), dim3((unsigned)threads), args, bytes, s));
         return BFGX_OK;
     }
     int n_cu = 256;
@@ -70,6 +93,10 @@ struct FftSetup {
         if (int rc = strided_attr<0>(lds)) return rc;
         if (int rc = strided_attr<1>(lds_bin1)) return rc;
         if (int rc = strided_attr<2>(lds_bin2)) return rc;
+        lds_bin3 = fft_c2c_lds_bytes(N, lt, nk, 3);
+        lds_bin4 = fft_c2c_lds_bytes(N, lt, nk, 4);
+        if (int rc = xpk_attr<3>(lds_bin3)) return rc;
+        if (int rc = xpk_attr<4>(lds_bin4)) return rc;
         n_cu = device_cu_count(device);
         return BFGX_OK;
     }
@@ -129,6 +156,24 @@ int fft_planes(FftSetup &f, hipStream_t s, int N, int planes, const double *map_
     return BFGX_OK;
 }
 
+// bins, counts and |k| sums are functions of (N, L, nk) alone: tabulated by the first binned pass that wants them (one byte per mode),
+// looked up afterwards.  pb: the setup's k axis and bins.
+int fft_bin_table(FftSetup &f, hipStream_t s, int N, int nk, const PkBins &pb)
+{
+    if (f.tab_ready) return BFGX_OK;
+    if (f.dtab.up(nullptr, ((size_t)N * f.ztiles * N) << f.lt) || f.dksb.up(nullptr, sizeof(double) * (size_t)N * nk) ||
+        f.dcnb.up(nullptr, sizeof(unsigned long long) * (size_t)N * nk))
+        return alloc_fail("P(k) bin table");
+    PkBins all = pb;
+    all.b0 = 0;
+    hipLaunchKernelGGL(pk_table_build_kernel, dim3((unsigned)N), dim3(kFftBlock), 16 * (size_t)nk, s, all, N, f.nz, f.lt, (int)f.ztiles, f.dtab.as<uint8_t>(),
+                       f.dksb.as<double>(), f.dcnb.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));                    // (built once; later calls on any stream find it complete)
+    f.tab_ready = true;
+    return BFGX_OK;
+}
+
 // complex transforms along the FIRST axis of F [N][nb][pitch] (the columns b0 .. b0 + nb of the middle axis) fused with the P(k)
 // sums: the transformed tiles are binned from LDS and never written back (F is scratch afterwards)
 int fft_axis0_pk(FftSetup &f, hipStream_t s, int N, int nb, int b0, double2 *F, int pitch, int nk, double *pk_sum_dev, double *k_sum_dev,
@@ -142,21 +187,9 @@ int fft_axis0_pk(FftSetup &f, hipStream_t s, int N, int nb, int b0, double2 *F, 
     const int64_t ntiles = (int64_t)f.ztiles * nb;
     const unsigned wgs = (unsigned)std::min<int64_t>(ntiles, (int64_t)f.n_cu * std::max<size_t>(1, (size_t)(160 * 1024) / f.lds_bin2));
     PkBins pb{f.dkl.as<double>(), f.k_lo, f.dk, 1.0 / f.dk, nk, b0, pk_sum_dev, k_sum_dev, counts_dev, nullptr, pitch};
-    // bins, counts and |k| sums are functions of (N, L, nk) alone: tabulated by the first call (one byte per mode), looked up afterwards
     const bool use_tab = nk <= 254;
-    if (use_tab && !f.tab_ready) {
-        if (f.dtab.up(nullptr, ((size_t)N * f.ztiles * N) << f.lt) || f.dksb.up(nullptr, sizeof(double) * (size_t)N * nk) ||
-            f.dcnb.up(nullptr, sizeof(unsigned long long) * (size_t)N * nk))
-            return alloc_fail("P(k) bin table");
-        PkBins all = pb;
-        all.b0 = 0;
-        hipLaunchKernelGGL(pk_table_build_kernel, dim3((unsigned)N), dim3(kFftBlock), 16 * (size_t)nk, s, all, N, f.nz, f.lt, (int)f.ztiles, f.dtab.as<uint8_t>(),
-                           f.dksb.as<double>(), f.dcnb.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));                    // (built once; later calls on any stream find it complete)
-        f.tab_ready = true;
-    }
     if (use_tab) {
+        if (int rc = fft_bin_table(f, s, N, nk, pb)) return rc;
         pb.tab = f.dtab.as<uint8_t>();
         if (int rc = f.strided_launch<2>(s, wgs, f.lds_bin2, F, N, (int64_t)nb * pitch, (int64_t)pitch, nb, pb)) return rc;
         hipLaunchKernelGGL(pk_table_sums_kernel, dim3((unsigned)nk), dim3(256), 0, s, nk, b0, nb, f.dksb.as<double>(),

@@ -400,6 +400,110 @@ def power_spectrum(Map, Lbox, Nk=180, device=0):
     return kc, pk, cnt
 
 
+def _cuda_f8_cube(Map, what):
+    """a CUDA float64 tensor holding a cubic 3-D map, contiguous (ValueError otherwise)"""
+    import torch
+    if not isinstance(Map, torch.Tensor) or not Map.is_cuda or Map.dtype != torch.float64:
+        raise ValueError("%s needs a CUDA float64 tensor" % what)
+    if Map.dim() != 3 or len(set(Map.shape)) != 1:
+        raise ValueError("%s needs a cubic 3-D map" % what)
+    return Map.contiguous()
+
+
+def power_spectrum_tensor(Map, Lbox, Nk=180):
+    """power_spectrum for a CUDA float64 tensor, analysed where it lies on the current stream.  Returns (k_cen, Pk, k_count) as numpy
+    arrays, empty bins NaN."""
+    import torch
+    Map = _cuda_f8_cube(Map, "power_spectrum_tensor")
+    N, Nk = int(Map.shape[0]), int(Nk)
+    work = torch.empty(power_spectrum_work_doubles(N), dtype=torch.float64, device=Map.device)
+    sums = torch.empty((2, max(Nk, 1)), dtype=torch.float64, device=Map.device)
+    cnt = torch.empty(max(Nk, 1), dtype=torch.int64, device=Map.device)
+    power_spectrum_device(Map.data_ptr(), N, Lbox, Nk, work.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), cnt.data_ptr(),
+                          device=Map.device.index or 0, stream=torch.cuda.current_stream(Map.device).cuda_stream)
+    s, c = sums.cpu().numpy(), cnt.cpu().numpy()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return s[1] / c, s[0] / c, c
+
+
+def cross_power_spectrum_work_doubles(n_grid):
+    """doubles of scratch cross_power_spectrum_device needs (two half spectra)"""
+    return int(_lib.load().bfgx_cross_power_spectrum_work_doubles(int(n_grid)))
+
+
+def cross_power_spectrum_device(map_a_ptr, map_b_ptr, n_grid, L, nk, window_order, work_ptr, paa_sum_ptr, pbb_sum_ptr, pab_sum_ptr, k_sum_ptr,
+                                counts_ptr, device=0, stream=0):
+    """the sums of |F_A|^2, |F_B|^2, Re(F_A conj F_B), |k| and the counts per linear k-bin of two device-resident maps (which may be the
+    same); work = cross_power_spectrum_work_doubles(n_grid) doubles of scratch; window_order 0, 1, 2, 3 = none, NGP, CIC, TSC"""
+    _lib.check(_lib.load().bfgx_cross_power_spectrum_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), C.c_void_p(int(map_a_ptr)),
+                                                           C.c_void_p(int(map_b_ptr)), float(L), int(nk), int(window_order),
+                                                           C.c_void_p(int(work_ptr)), C.c_void_p(int(paa_sum_ptr)), C.c_void_p(int(pbb_sum_ptr)),
+                                                           C.c_void_p(int(pab_sum_ptr)), C.c_void_p(int(k_sum_ptr)), C.c_void_p(int(counts_ptr))))
+
+
+def fft_slab_axis0_xpk_device(spec_a_ptr, work_b_ptr, n_grid, ncols, col0, L, nk, window_order, paa_sum_ptr, pbb_sum_ptr, pab_sum_ptr, k_sum_ptr,
+                              counts_ptr, device=0, stream=0):
+    """the last pass of a cross spectrum alone: spec_a [n][ncols][fft_pitch(n)] = map A's finished spectrum of the columns col0 .. of the
+    middle axis, work_b = map B's before the transform along the first axis (neither is changed) -> partial bin sums"""
+    _lib.check(_lib.load().bfgx_fft_slab_axis0_xpk_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), int(ncols), int(col0),
+                                                         C.c_void_p(int(spec_a_ptr)), C.c_void_p(int(work_b_ptr)), float(L), int(nk),
+                                                         int(window_order), C.c_void_p(int(paa_sum_ptr)), C.c_void_p(int(pbb_sum_ptr)),
+                                                         C.c_void_p(int(pab_sum_ptr)), C.c_void_p(int(k_sum_ptr)), C.c_void_p(int(counts_ptr))))
+
+
+WINDOW_ORDERS = {'none': 0, 'ngp': 1, 'cic': 2, 'tsc': 3}
+
+
+def cross_power_spectrum(MapA, MapB, Lbox, Nk=180, window=0, device=0):
+    """Auto and cross power spectra of two cubic 3-D maps of one shape in the bins and units of power_spectrum (the unnormalised fftn).
+    MapA, MapB: two numpy arrays, or two CUDA float64 torch tensors, which are analysed where they lie on the current stream.  window:
+    0, 1, 2, 3 or 'none', 'ngp', 'cic', 'tsc' divides the mass-assignment window of that order out of every mode.  Returns a dict of numpy
+    arrays: k (mean |k| per bin), paa, pbb, pab = <Re(F_A conj F_B)>, r = pab / sqrt(paa pbb), counts (modes per bin); empty bins NaN."""
+    if isinstance(window, str):
+        if window.lower() not in WINDOW_ORDERS:
+            raise ValueError("cross_power_spectrum: window must be 0, 1, 2, 3 or 'none', 'ngp', 'cic', 'tsc'")
+        p = WINDOW_ORDERS[window.lower()]
+    else:
+        if isinstance(window, bool) or window not in (0, 1, 2, 3):
+            raise ValueError("cross_power_spectrum: window must be 0, 1, 2, 3 or 'none', 'ngp', 'cic', 'tsc'")
+        p = int(window)
+    Nk = int(Nk)
+    dev_a = hasattr(MapA, 'data_ptr') and not isinstance(MapA, np.ndarray)
+    dev_b = hasattr(MapB, 'data_ptr') and not isinstance(MapB, np.ndarray)
+    if dev_a != dev_b:
+        raise ValueError("cross_power_spectrum needs two numpy arrays or two CUDA float64 tensors, not one of each")
+    if not dev_a:
+        MapA, MapB = _lib.f8(MapA), _lib.f8(MapB)
+        if MapA.ndim != 3 or len(set(MapA.shape)) != 1:
+            raise ValueError("cross_power_spectrum needs cubic 3-D maps")
+        if MapA.shape != MapB.shape:
+            raise ValueError("cross_power_spectrum needs two maps of one shape")
+        out = np.empty((4, max(Nk, 1)))
+        cnt = np.empty(max(Nk, 1), dtype=np.int64)
+        _lib.check(_lib.load().bfgx_cross_power_spectrum(int(device), MapA.shape[0], MapA.ctypes.data, MapB.ctypes.data, float(Lbox), Nk, p,
+                                                        out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data,
+                                                        cnt.ctypes.data))
+        paa, pbb, pab, k = out
+    else:
+        import torch
+        MapA, MapB = _cuda_f8_cube(MapA, "cross_power_spectrum"), _cuda_f8_cube(MapB, "cross_power_spectrum")
+        if MapA.shape != MapB.shape or MapA.device != MapB.device:
+            raise ValueError("cross_power_spectrum needs two maps of one shape on one device")
+        N = int(MapA.shape[0])
+        work = torch.empty(cross_power_spectrum_work_doubles(N), dtype=torch.float64, device=MapA.device)
+        sums = torch.empty((4, max(Nk, 1)), dtype=torch.float64, device=MapA.device)
+        cntd = torch.empty(max(Nk, 1), dtype=torch.int64, device=MapA.device)
+        cross_power_spectrum_device(MapA.data_ptr(), MapB.data_ptr(), N, Lbox, Nk, p, work.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(),
+                                    sums[2].data_ptr(), sums[3].data_ptr(), cntd.data_ptr(), device=MapA.device.index or 0,
+                                    stream=torch.cuda.current_stream(MapA.device).cuda_stream)
+        s, cnt = sums.cpu().numpy(), cntd.cpu().numpy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            paa, pbb, pab, k = s[0] / cnt, s[1] / cnt, s[2] / cnt, s[3] / cnt
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = pab / np.sqrt(paa * pbb)
+    return {'k': k, 'paa': paa, 'pbb': pbb, 'pab': pab, 'r': r, 'counts': cnt}
+
+
 def fft_slab_axis0_device(work_ptr, n_grid, ncols, inverse=0, device=0, stream=0):
     """in-place complex transforms along the first axis of work [n][ncols][fft_pitch(n)]; inverse: exponent +i, unnormalised"""
     _lib.check(_lib.load().bfgx_fft_slab_axis0_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), int(ncols),

@@ -550,6 +550,36 @@ int  bfgx_bispectrum_device(int device, void *hip_stream, int32_t n_grid, const 
 int  bfgx_bispectrum(int device, int32_t n_grid, const double *map_host, double L, int32_t nbins, const double *k_edges, int32_t ntri,
                      const int32_t *tri, double *b_sum, double *n_tri, double *pk_sum, double *n_modes);
 
+/* ---- cross power spectrum of two gridded 3-D maps -----------------------------------------------------------
+ * Units and bins of bfgx_power_spectrum: F = the unnormalised np.fft.fftn(map), nk linear bins between 2 pi / L and the Nyquist
+ * frequency; counts and the sums of |k| are those of the auto spectrum.  Per bin, over the modes in it (the mirrored half of the spectrum
+ * through a weight of 2):  paa_sum = sum w |F_A|^2,  pbb_sum = sum w |F_B|^2,  pab_sum = sum w Re(F_A conj F_B).
+ * window_order p = 0, 1, 2, 3 (none, NGP, CIC, TSC) divides out the mass-assignment window: for a mode with integer wave numbers
+ * (n_a, n_b, n_c) (fftfreq(N) N per axis) and s(n) = sin(pi n / N) / (pi n / N), s(0) = 1, w = [s(n_a) s(n_b) s(n_c)]^(-2p); k_sum and
+ * counts are not weighted.  Map A is transformed along all three axes and kept; the last FFT pass of map B reads A's coefficient as B's
+ * leaves the butterflies, so B's spectrum is never stored.  The sums are added by floating-point atomics: correct to rounding, not bitwise
+ * reproducible from call to call (counts, and k_sum for nk <= 254, are).  Limits: n_grid a power of two in [8, 1024] (else
+ * BFGX_ERR_UNSUPPORTED), 1 <= nk <= 2048, L > 0; complex arrays 16-byte aligned, rows of bfgx_fft_pitch(n_grid) values whose pad columns
+ * may hold anything.  Tables are kept per (device, n_grid, L, nk) and (device, n_grid, p) until bfgx_cache_clear. */
+/* doubles of scratch bfgx_cross_power_spectrum_device needs: two half spectra (host arithmetic) */
+int64_t bfgx_cross_power_spectrum_work_doubles(int32_t n_grid);
+/* map_a_dev, map_b_dev [n][n][n] (they may be the same map) -> the five sums [nk], all pointers device.  Enqueue-only once the tables
+ * exist. */
+int  bfgx_cross_power_spectrum_device(int device, void *hip_stream, int32_t n_grid, const double *map_a_dev, const double *map_b_dev, double L,
+                                      int32_t nk, int32_t window_order, double *work_dev, double *paa_sum_dev, double *pbb_sum_dev,
+                                      double *pab_sum_dev, double *k_sum_dev, unsigned long long *counts_dev);
+/* the last pass alone on the columns [col0, col0 + ncols) of the middle axis, the counterpart of bfgx_fft_slab_axis0_pk_device: spec_a_dev
+ * [n][ncols][pitch] = map A's spectrum of these columns, transformed along all three axes (read-only); work_b_dev [n][ncols][pitch] = map
+ * B's before the axis-0 pass (read, not changed).  The two ranges must not overlap.  The sums are partial: a caller that splits the
+ * columns adds them up. */
+int  bfgx_fft_slab_axis0_xpk_device(int device, void *hip_stream, int32_t n_grid, int32_t ncols, int32_t col0, const double *spec_a_dev,
+                                    double *work_b_dev, double L, int32_t nk, int32_t window_order, double *paa_sum_dev, double *pbb_sum_dev,
+                                    double *pab_sum_dev, double *k_sum_dev, unsigned long long *counts_dev);
+/* the same on host arrays (synchronous): paa, pbb, pab = the sums divided by counts, kcen = mean |k| per bin, NaN for empty bins as in
+ * bfgx_power_spectrum */
+int  bfgx_cross_power_spectrum(int device, int32_t n_grid, const double *map_a_host, const double *map_b_host, double L, int32_t nk,
+                               int32_t window_order, double *paa, double *pbb, double *pab, double *kcen, int64_t *counts);
+
 /* ---- particle-snapshot path ----------------------------------------------------------
  * Replaces BaryonifySnapshot.process, BaryonForge/Runners/SnapshotRunner.py:173-262: every particle within
  * R_q = clip(epsilon_max R200c / a, 0, L/2) of a halo (periodic box) moves radially by displacement(d, M, a) * a;
