@@ -2,8 +2,6 @@
 (-> ctypes -> C ABI) against the reference's outputs (tests/golden/snap*.npz) and the brute-force CPU oracle.
 All fp64; differences are libm ulps and the order in which a particle's halos are summed  ->  |d| <= 1e-10 * max|offset|
 (and 1e-13 of the box size on the positions themselves)."""
-import os
-
 import numpy as np
 import pytest
 
@@ -34,14 +32,11 @@ def test_snapshot_runner_vs_reference_golden(gpu, name):
 
 
 @pytest.mark.parametrize('cells', ['7', '64', '301'])
-def test_snapshot_cell_grid_independence(gpu, cells):
+def test_snapshot_cell_grid_independence(gpu, monkeypatch, cells):
     """the halo-cell grid is only an acceleration structure: any resolution gives the same particles"""
     g = H.load_snapshot_golden('snap3d_baryonify')
-    os.environ['BFGX_SNAP_CELLS'] = cells
-    try:
-        out = _positions(H.snapshot_product_runner(g).process(), 3)
-    finally:
-        del os.environ['BFGX_SNAP_CELLS']
+    monkeypatch.setenv('BFGX_SNAP_CELLS', cells)
+    out = _positions(H.snapshot_product_runner(g).process(), 3)
     assert np.nanmax(np.abs(out - g['expected'])) <= 1e-13 * g['L']
 
 
