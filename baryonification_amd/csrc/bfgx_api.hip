@@ -864,7 +864,7 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
 {
     if (!model || !out) return fail(BFGX_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    // (NSIDE 16384 has 3.2e9 pixels: the tile kernels keep first-pixel-of-ring offsets and per-tile counters in 32 bits -- RowScan.start, the
+    // (the next power of two, NSIDE 2^14, has 3.2e9 pixels: the tile kernels keep first-pixel-of-ring offsets and per-tile counters in 32 bits -- RowScan.start, the
     // walking regrid; 8192, 8.05e8 pixels / 6.4 GB of fp64 map, is the largest shell that is tested)
     if (nside < 1 || nside > 8192) return fail(BFGX_ERR_INVALID, "nside must be 1 .. 8192 (the tile kernels index pixels with 32 bits inside a ring table)");
     if (max_halos < 0) return fail(BFGX_ERR_INVALID, "max_halos < 0");
@@ -969,24 +969,6 @@ int bfgx_plan_precision(bfgx_plan *p, int acc_requested, int32_t *acc_resolved, 
     return BFGX_OK;
 }
 
-int bfgx_plan_bands(bfgx_plan *p, int32_t *nbands, int64_t *band_first_pixel)
-{
-    if (!p || !nbands) return fail(BFGX_ERR_INVALID, "NULL argument");
-    *nbands = p->tiling.nbands;
-    if (band_first_pixel) {                       // band b = rings [1 + BR b, 1 + BR (b + 1)): a contiguous RING pixel range
-        const int64_t nl4 = 4 * p->hpx.nside;
-        for (int b = 0; b <= p->tiling.nbands; ++b) {
-            const int64_t ring = std::min<int64_t>(1 + (int64_t)p->tiling.BR * b, nl4);
-            if (ring >= nl4) { band_first_pixel[b] = p->hpx.npix; continue; }
-            const int64_t ns = p->hpx.nside, q = nl4 - ring;
-            band_first_pixel[b] = (ring < ns) ? 2 * ring * (ring - 1)
-                                : (ring < 3 * ns) ? p->hpx.ncap + (ring - ns) * 4 * ns
-                                : p->hpx.npix - 2 * q * (q + 1);
-        }
-    }
-    return BFGX_OK;
-}
-
 // arguments of the gathering regrid that do not depend on the data
 static ReachArgs reach_args(const bfgx_plan *p, double cap)
 {
@@ -1005,160 +987,19 @@ static int64_t ring_first_pixel(const Hpx &h, int64_t ring)
     return (ring < ns) ? 2 * ring * (ring - 1) : (ring < 3 * ns) ? h.ncap + (ring - ns) * 4 * ns : h.npix - 2 * q * (q + 1);
 }
 
-int bfgx_plan_band_apron(bfgx_plan *p, int32_t band0, int32_t band1, int64_t *olo, int64_t *ohi)
+// The bands [b0, b1) of the tiling as the launches take them: the RING pixels [p0, p1), the tiles [t0, t0 + nt).  Band b holds the rings
+// [1 + BR b, 1 + BR (b + 1)); 0 <= b0 <= b1 <= nbands (check_band_range).  Nothing else reads band_tile0_host or turns a band into a pixel
+struct BandRange { int64_t p0, p1; int t0, nt; };
+static BandRange band_range(const bfgx_plan *p, int b0, int b1)
 {
-    if (!p || !olo || !ohi) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (band0 < 0 || band1 > p->tiling.nbands || band0 > band1) return fail(BFGX_ERR_INVALID, "band range out of bounds");
-    const int64_t i0 = 1 + (int64_t)p->tiling.BR * band0, i1 = 1 + (int64_t)p->tiling.BR * band1;      // rings [i0, i1)
-    *olo = ring_first_pixel(p->hpx, i0 - p->band_reach);
-    *ohi = ring_first_pixel(p->hpx, i1 + p->band_reach);
-    return BFGX_OK;
+    const auto first_pixel = [p](int b) { return ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * b); };
+    return BandRange{first_pixel(b0), first_pixel(b1), p->band_tile0_host[b0], p->band_tile0_host[b1] - p->band_tile0_host[b0]};
 }
 
-int bfgx_plan_reach_rings(bfgx_plan *p, double max_offset, int32_t *rings)
+static int check_band_range(const bfgx_plan *p, int32_t b0, int32_t b1, bool tiles = false)      // tiles: for a pass over the range's tiles
 {
-    if (!p || !rings) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (!(max_offset >= 0.0)) return fail(BFGX_ERR_INVALID, "max_offset must be >= 0");
-    *rings = regrid_reach_rings(p->hpx.nside, std::min(max_offset * 1.001, regrid_cap(p->hpx.nside)));
-    return BFGX_OK;
-}
-
-int bfgx_plan_set_band_reach(bfgx_plan *p, int32_t rings)
-{
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    if (rings < 1 || rings > kReachMax) return fail(BFGX_ERR_INVALID, "band reach must be 1 .. %d rings", kReachMax);
-    p->band_reach = rings;
-    return BFGX_OK;
-}
-
-// reset_far = false: the far-deposit list keeps what earlier calls have listed (the one-shot host entry regrids the sphere in several
-// band ranges while the map is still arriving, and applies one list at the end)
-// m SPLIT (the fused band entry, the one-shot host entry): the low halves of the pixels [olo, ohi) follow their high halves
-static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const double *map_in_dev, const void *offsets_dev,
-                             int64_t olo, int64_t ohi, const DispMode &m, double *out_slice_dev, double *sums_dev, bool reset_far,
-                             bool sums_later = false)
-{
-    if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "banded regrid needs the tiled algorithm (algo 1)");
-    int64_t need_lo = 0, need_hi = 0;
-    if (int rc = bfgx_plan_band_apron(p, band0, band1, &need_lo, &need_hi)) return rc;
-    if (band0 == band1) {
-        // a rank that owns no band (more ranks than bands): empty buffers, whose data pointers are NULL, are fine
-        HIP_TRY(hipSetDevice(p->device));
-        if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, sizeof(unsigned long long), p->stream));
-        if (sums_dev) HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
-        return BFGX_OK;
-    }
-    if (!map_in_dev || !offsets_dev || !out_slice_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (olo > need_lo || ohi < need_hi || olo < 0 || ohi > p->hpx.npix)
-        return fail(BFGX_ERR_INVALID, "pix_offsets range [%lld, %lld) does not cover the bands and %d ring(s) either side [%lld, %lld)",
-                    (long long)olo, (long long)ohi, p->band_reach, (long long)need_lo, (long long)need_hi);
-    HIP_TRY(hipSetDevice(p->device));
-    if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, sizeof(unsigned long long), p->stream));
-    const int64_t p0 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0);
-    const int t0 = p->band_tile0_host[band0], t1 = p->band_tile0_host[band1];
-    {
-        KernelTimer kt(p, BFGX_K_REGRID);
-        const size_t lds = regrid3_lds_bytes(p->tiling.BR, p->tiling.W, m.fp64() ? sizeof(double) : sizeof(float), p->band_reach > 1,
-                                             m.split() ? sizeof(float) : 0);
-        // virtual bases: the kernel indexes every array by global pixel number
-        double *out_base = out_slice_dev - p0;
-        // every rank gathers with the same fixed reach (so that all of them classify a source pixel the same way)
-        const ReachArgs reach = reach_args(p, regrid_cap_for_rings(p->hpx.nside, p->band_reach));
-        hipLaunchKernelGGL(tile_apron_kernel, dim3((t1 - t0 + 255) / 256), dim3(256), 0, p->stream, p->hpx, p->tiling, (const float *)nullptr,
-                           p->band_reach, reach.cap, t0, t1 - t0, p->tile_apron, (int32_t *)nullptr);
-        double *ts = sums_dev ? p->tile_sums : nullptr;
-        const dim3 grid(t1 - t0), blk(256);
-        int *none = nullptr;
-#define BFGX_REGRID3(ACC, REAL, SPLIT, OL)                                                                                                     \
-        do {                                                                                                                                    \
-            const ACC *o = (const ACC *)offsets_dev - 3 * olo;                                                                                  \
-            if (p->band_reach == 1) hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 0, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
-                                                       out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);                      \
-            else hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 2, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
-                                    out_base, p->far, reach, ts, t0, t1 - t0, none, (double *)nullptr);                                         \
-        } while (0)
-        if (m.split()) BFGX_REGRID3(float, double, true, m.lo(offsets_dev, ohi - olo) - 3 * olo);
-        else if (m.fp64()) BFGX_REGRID3(double, double, false, (const double *)nullptr);
-        else BFGX_REGRID3(float, float, false, (const float *)nullptr);
-#undef BFGX_REGRID3
-        HIP_TRY(hipGetLastError());
-    }
-    if (sums_dev && !sums_later) {             // (sums_later: the caller's next kernel adds the per-tile sums up)
-        KernelTimer kt(p, BFGX_K_SUM);
-        if (t1 - t0 > 16384) {
-            HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
-            hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, t1 - t0, (const double *)(p->tile_sums + 2 * (size_t)t0), sums_dev);
-        } else
-            hipLaunchKernelGGL(sum_tiles_kernel, dim3(1), dim3(256), 0, p->stream, t1 - t0, (const double *)(p->tile_sums + 2 * (size_t)t0), sums_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_plan_set_route_margin(bfgx_plan *p, int32_t rings)
-{
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    if (rings < 0 || rings > 4 * p->hpx.nside) return fail(BFGX_ERR_INVALID, "route margin must be 0 .. 4 nside rings");
-    p->route_margin = rings;
-    return BFGX_OK;
-}
-
-int bfgx_regrid_bands_device(bfgx_plan *p, int32_t band0, int32_t band1, const double *map_in_dev, const void *offsets_dev,
-                             int64_t olo, int64_t ohi, int acc_f64, double *out_slice_dev, double *sums_dev)
-{
-    DispMode m;
-    if (int rc = disp_mode(p, acc_f64, true, m)) return rc;
-    return regrid_bands_impl(p, band0, band1, map_in_dev, offsets_dev, olo, ohi, m, out_slice_dev, sums_dev, true);
-}
-
-int bfgx_plan_far_apply_device(bfgx_plan *p, double *out_slice_dev, int64_t p0, int64_t p1, unsigned long long *foreign_dev)
-{
-    if (!p || !out_slice_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    hipLaunchKernelGGL(regrid_far_local_kernel, dim3(64), dim3(256), 0, p->stream, p->far, out_slice_dev, p0, p1, foreign_dev);
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-int bfgx_plan_far_fetch(bfgx_plan *p, int64_t cap, int64_t *pix_host, double *val_host, int64_t *n_host)
-{
-    if (!p || !n_host) return fail(BFGX_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    unsigned long long n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, p->far.count, sizeof(n), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if ((int64_t)n > p->far.cap) return fail(BFGX_ERR_INVALID, "the regrid's list of far deposits overflowed (%lld entries)", (long long)p->far.cap);
-    *n_host = (int64_t)n;
-    if (n == 0 || (!pix_host && !val_host)) return BFGX_OK;          // count only
-    if ((int64_t)n > cap || !pix_host || !val_host) return fail(BFGX_ERR_INVALID, "far-deposit buffers hold %lld entries, %lld are listed", (long long)cap, (long long)n);
-    HIP_TRY(hipMemcpyAsync(pix_host, p->far.pix, sizeof(int64_t) * n, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(val_host, p->far.val, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return BFGX_OK;
-}
-
-int bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_overflowed, int32_t *tiles_walked, int32_t *max_reach_rings)
-{
-    if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
-    if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "regrid statistics exist for the tiled algorithm (algo 1) only");
-    HIP_TRY(hipSetDevice(p->device));
-    RegridCtrl ctrl = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(&ctrl, p->arena.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, p->stream));
-    std::vector<int32_t> apron;
-    if (max_reach_rings) {
-        apron.resize(2 * (size_t)p->tiling.ntiles);
-        HIP_TRY(hipMemcpyAsync(apron.data(), p->tile_apron, sizeof(int32_t) * apron.size(), hipMemcpyDeviceToHost, p->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (far_listed) *far_listed = (int64_t)ctrl.far_count;
-    if (far_overflowed) *far_overflowed = ctrl.far_overflow_full;
-    if (tiles_walked) *tiles_walked = ctrl.todo_count;
-    if (max_reach_rings) {
-        int32_t m = 0;
-        for (int t = 0; t < p->tiling.ntiles; ++t) m = std::max(m, apron[2 * (size_t)t]);
-        *max_reach_rings = m;
-    }
-    return BFGX_OK;
+    if (tiles && p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "band-restricted passes need the tiled algorithm (algo 1)");
+    return (b0 < 0 || b1 > p->tiling.nbands || b0 > b1) ? fail(BFGX_ERR_INVALID, "band range out of bounds") : BFGX_OK;
 }
 
 // the checks of a K0 + K1 / K3 entry: the catalog, the kind of table (paint: a profile table), the output pointer.  bands: a pass over the tiles
@@ -1166,8 +1007,7 @@ int bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_overf
 static int check_scatter(const bfgx_plan *p, const bfgx_catalog *cat, const void *out, bool paint, bool bands = false, int32_t band0 = 0, int32_t band1 = 0)
 {
     if (int rc = check_catalog(p, cat)) return rc;
-    if (bands && p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "band-restricted passes need the tiled algorithm (algo 1)");
-    if (bands && (band0 < 0 || band1 > p->tiling.nbands || band0 > band1)) return fail(BFGX_ERR_INVALID, "band range out of bounds");
+    if (bands) if (int rc = check_band_range(p, band0, band1, true)) return rc;
     if ((p->model.tab.logv != 0) != paint) return fail(BFGX_ERR_INVALID, paint ? "profile painting needs a table with log_values = 1"
                                                                                : "displacement read-out needs a table with log_values = 0");
     if ((!bands || band0 < band1) && !out) return fail(BFGX_ERR_INVALID, paint ? "map pointer is NULL" : "offsets pointer is NULL");
@@ -1211,93 +1051,12 @@ int bfgx_offsets_device(bfgx_plan *p, const bfgx_catalog *cat, void *offsets_dev
     return offsets_impl(p, cat, offsets_dev, m, TileLaunch{});
 }
 
-// K0 + K1 for the bands [band0, band1) (band0 < band1) into pix_offsets from the first pixel of band0 (SPLIT: the low halves follow the high ones)
-static int offsets_bands(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *slice, const DispMode &m)
-{
-    TileLaunch k1;
-    k1.tile_lo = p->band_tile0_host[band0];
-    k1.tile_n = p->band_tile0_host[band1] - k1.tile_lo;
-    if (int rc = launch_k0(p, cat, 1, m.fp64())) return rc;
-    // K1's flush leaves the largest |offset|^2 of every tile it stores (bfgx_bands_max_offset2_device reduces them: the reach of the
-    // regrid then needs no second pass over the slice)
-    k1.omax = p->arena.omax;
-    return launch_offsets(p, m, slice, ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0),
-                          ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band1), k1);
-}
-
-int bfgx_offsets_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *offsets_slice_dev, int acc_f64)
-{
-    if (int rc = check_scatter(p, cat, offsets_slice_dev, false, true, band0, band1)) return rc;
-    if (band0 == band1) return BFGX_OK;
-    DispMode m;
-    if (int rc = disp_mode(p, acc_f64, true, m)) return rc;
-    return offsets_bands(p, cat, band0, band1, offsets_slice_dev, m);
-}
-
 // K3 into the map held at `slice` from pixel p0 on (virtual base: the kernels index the output by global pixel number)
 static int launch_paint(bfgx_plan *p, const PaintMode &m, void *slice, int64_t p0, TileLaunch k3)
 {
     k3.paint_pair_f32 = m.pair_f32();
     if (m.map_f64()) return launch_tile_scatter<MODE_PAINT, double>(p, (double *)slice - p0, k3);
     return launch_tile_scatter<MODE_PAINT, float>(p, (float *)slice - p0, k3);
-}
-
-int bfgx_paint_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0, int32_t band1, void *map_slice_dev, int acc_f64)
-{
-    if (int rc = check_scatter(p, cat, map_slice_dev, true, true, band0, band1)) return rc;
-    if (band0 == band1) return BFGX_OK;
-    PaintMode m;
-    if (int rc = paint_mode(p, acc_f64, m)) return rc;
-    TileLaunch k3;
-    k3.tile_lo = p->band_tile0_host[band0];
-    k3.tile_n = p->band_tile0_host[band1] - k3.tile_lo;
-    if (int rc = launch_k0(p, cat, 0, m.k0_f64())) return rc;
-    return launch_paint(p, m, map_slice_dev, ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * band0), k3);
-}
-
-// One rank's share of a resident multi-GPU BaryonifyShell step after the routing, as ONE enqueue-only call (Parallelize.py:250-318 has one call
-// drive all workers): K0 + binning + K1 for the bands [B0, B1) (the rank's own and, with a route margin, the band either side: the aprons of
-// its regrid) into offsets_dev (pixels from the first of band B0), the banded regrid of ITS bands [b0, b1) into out_slice_dev, the listed far
-// deposits that fall into its pixels added, the others counted into *foreign_dev, the two sums of the mass check.  One memset (the binning's)
-// zeroes every control word; eight launches.
-int bfgx_offsets_regrid_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t B0, int32_t B1, void *offsets_dev, int acc_f64,
-                                     int32_t b0, int32_t b1, const double *map_in_dev, double *out_slice_dev, double *sums_dev,
-                                     unsigned long long *foreign_dev)
-{
-    if (!p || !cat) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (B0 < 0 || B1 > p->tiling.nbands || B0 > b0 || b1 > B1 || b0 > b1) return fail(BFGX_ERR_INVALID, "band ranges must nest: [B0, B1) around [b0, b1)");
-    // the parity-grade mode: both halves of pix_offsets stay on this device (24 bytes per pixel, as fp64 would take)
-    DispMode m;
-    if (int rc = disp_mode(p, acc_f64, false, m)) return rc;
-    const int64_t wlo = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * B0), whi = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * B1);
-    if (int rc = check_scatter(p, cat, offsets_dev, false, true, B0, B1)) return rc;
-    if (B0 < B1) if (int rc = offsets_bands(p, cat, B0, B1, offsets_dev, m)) return rc;      // (its memset also zeroes the far list's counter)
-    if (b0 == b1) {
-        if (sums_dev) HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
-        return BFGX_OK;
-    }
-    if (int rc = regrid_bands_impl(p, b0, b1, map_in_dev, offsets_dev, wlo, whi, m, out_slice_dev, sums_dev, false, true)) return rc;
-    const int64_t p0 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * b0), p1 = ring_first_pixel(p->hpx, 1 + (int64_t)p->tiling.BR * b1);
-    const int t0 = p->band_tile0_host[b0], t1 = p->band_tile0_host[b1];
-    hipLaunchKernelGGL(regrid_far_local_kernel, dim3(64), dim3(256), 0, p->stream, p->far, out_slice_dev, p0, p1, foreign_dev, t1 - t0,
-                       sums_dev ? (const double *)(p->tile_sums + 2 * (size_t)t0) : (const double *)nullptr, sums_dev);
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-int bfgx_bands_max_offset2_device(bfgx_plan *p, int32_t band0, int32_t band1, float *out_dev)
-{
-    if (!p || !out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "band-restricted passes need the tiled algorithm (algo 1)");
-    if (band0 < 0 || band1 > p->tiling.nbands || band0 > band1) return fail(BFGX_ERR_INVALID, "band range out of bounds");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemsetAsync(out_dev, 0, sizeof(float), p->stream));
-    const int t0 = p->band_tile0_host[band0], nt = p->band_tile0_host[band1] - t0;
-    if (nt > 0) {
-        hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(1024), 0, p->stream, nt, (const unsigned *)p->arena.omax + t0, (unsigned *)out_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
 }
 
 int bfgx_max_offset2_device(bfgx_plan *p, const void *offsets_dev, int64_t npixels, int acc_f64, float *out_dev)
@@ -1317,120 +1076,6 @@ int bfgx_max_offset2_device(bfgx_plan *p, const void *offsets_dev, int64_t npixe
     return BFGX_OK;
 }
 
-// shared argument checks / set-up of the two routing passes
-static int route_args(bfgx_plan *p, const bfgx_catalog *cat, int32_t world, const int32_t *ring_bounds, int32_t ncols, const double *const *cols,
-                      RouteArgs &a)
-{
-    if (!p || !cat || !ring_bounds || !cols) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (world < 1 || world > kRouteMaxRanks) return fail(BFGX_ERR_INVALID, "routing supports 1 .. %d ranks", kRouteMaxRanks);
-    if (ncols < 1 || ncols > kRouteMaxCols) return fail(BFGX_ERR_INVALID, "routing packs 1 .. %d columns", kRouteMaxCols);
-    if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
-    std::memset(&a, 0, sizeof(a));
-    a.world = world; a.ncols = ncols;
-    for (int j = 0; j <= world; ++j) {
-        if (j > 0 && ring_bounds[j] < ring_bounds[j - 1]) return fail(BFGX_ERR_INVALID, "ring bounds must ascend");
-        a.bounds[j] = ring_bounds[j];
-    }
-    for (int c = 0; c < ncols; ++c) { if (cat->n > 0 && !cols[c]) return fail(BFGX_ERR_INVALID, "column pointer is NULL"); a.col[c] = cols[c]; }
-    return BFGX_OK;
-}
-
-int bfgx_route_count_device(bfgx_plan *p, int64_t n, const int32_t *rings_dev, int32_t world, const int32_t *ring_bounds, int32_t *counts_dev)
-{
-    bfgx_catalog c;
-    std::memset(&c, 0, sizeof(c));
-    c.n = n;
-    RouteArgs a;
-    const double *none[1] = {nullptr};
-    if (n < 0 || !counts_dev || (n > 0 && !rings_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
-    c.n = 0;                                                    // (no columns are read in the counting pass)
-    if (int rc = route_args(p, &c, world, ring_bounds, 1, none, a)) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int32_t) * world, p->stream));
-    if (n > 0) {
-        hipLaunchKernelGGL(route_halos_kernel<false>, dim3((unsigned)std::min<int64_t>((n + 255) / 256, kRouteGrid)), dim3(256), 0, p->stream, a, n, rings_dev, counts_dev,
-                           (int32_t *)nullptr, (double *)nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_route_fill_device(bfgx_plan *p, int64_t n, const int32_t *rings_dev, int32_t world, const int32_t *ring_bounds, const int64_t *start,
-                           int32_t ncols, const double *const *cols_dev, int32_t *cursor_dev, double *rows_dev)
-{
-    bfgx_catalog c;
-    std::memset(&c, 0, sizeof(c));
-    c.n = n;
-    RouteArgs a;
-    if (n < 0 || !start || !cursor_dev || (n > 0 && (!rings_dev || !rows_dev))) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (int rc = route_args(p, &c, world, ring_bounds, ncols, cols_dev, a)) return rc;
-    for (int j = 0; j < world; ++j) a.start[j] = start[j];
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(int32_t) * world, p->stream));
-    if (n > 0) {
-        hipLaunchKernelGGL(route_halos_kernel<true>, dim3((unsigned)std::min<int64_t>((n + 255) / 256, kRouteGrid)), dim3(256), 0, p->stream, a, n, rings_dev, (int32_t *)nullptr,
-                           cursor_dev, rows_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-int bfgx_route_pack_device(bfgx_plan *p, int64_t n, const int32_t *rings_dev, int32_t world, const int32_t *ring_bounds, int64_t blockcap,
-                           int32_t ncols, const double *const *cols_dev, int32_t *cursor_dev, double *blocks_dev, int32_t *overflow_dev)
-{
-    bfgx_catalog c;
-    std::memset(&c, 0, sizeof(c));
-    c.n = n;
-    RouteArgs a;
-    if (n < 0 || !cursor_dev || !blocks_dev || !overflow_dev || (n > 0 && !rings_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (blockcap < 1) return fail(BFGX_ERR_INVALID, "block capacity must be >= 1");
-    if (int rc = route_args(p, &c, world, ring_bounds, ncols, cols_dev, a)) return rc;
-    a.blockcap = blockcap; a.overflow = overflow_dev;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(int32_t) * world, p->stream));
-    hipLaunchKernelGGL(route_blank_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)world * blockcap + 255) / 256, 1024)), dim3(256), 0, p->stream,
-                       world, ncols, blockcap, blocks_dev);
-    HIP_TRY(hipGetLastError());
-    if (n > 0) {
-        hipLaunchKernelGGL(route_halos_kernel<true>, dim3((unsigned)std::min<int64_t>((n + 255) / 256, kRouteGrid)), dim3(256), 0, p->stream, a, n, rings_dev, (int32_t *)nullptr,
-                           cursor_dev, blocks_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BFGX_OK;
-}
-
-// The routing of one resident multi-GPU step as ONE call and two launches (bfgx_disc_rings_device + bfgx_route_pack_device were four, with a
-// fill): route_prepare_kernel (NaN into column 0 of every block, the cursors zeroed) and route_step_kernel (ring range per halo, rows
-// packed by destination).  send_blocks_dev holds (world - 1) blocks [ncols][blockcap] in rank order WITHOUT this rank, recv_blocks_dev
-// world blocks: the other ranks' in rank order (what all_to_all_single delivers when the split towards oneself is empty), this rank's
-// own rows LAST -- they never enter the collective.  K0 reads the received blocks as they are (bfgx_plan_set_catalog_blocks).
-int bfgx_route_step_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t world, int32_t rank, const int32_t *ring_bounds, int64_t blockcap,
-                           int32_t ncols, const double *const *cols_dev, int32_t *cursor_dev, double *send_blocks_dev, double *recv_blocks_dev,
-                           int32_t *overflow_dev)
-{
-    if (!p || !cat || !cursor_dev || !recv_blocks_dev || !overflow_dev || (world > 1 && !send_blocks_dev)) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (rank < 0 || rank >= world) return fail(BFGX_ERR_INVALID, "rank out of range");
-    if (blockcap < 1) return fail(BFGX_ERR_INVALID, "block capacity must be >= 1");
-    if (cat->n > 0 && (!cat->M || !cat->z || !cat->dec)) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    RouteStepArgs s;
-    std::memset(&s, 0, sizeof(s));
-    if (int rc = route_args(p, cat, world, ring_bounds, ncols, cols_dev, s.r)) return rc;
-    s.r.blockcap = blockcap; s.r.overflow = overflow_dev;
-    s.rank = rank; s.margin = p->route_margin;
-    s.M = cat->M; s.z = cat->z; s.dec = cat->dec;
-    s.send = send_blocks_dev; s.recv = recv_blocks_dev;
-    HIP_TRY(hipSetDevice(p->device));
-    const int64_t nblank = (int64_t)(2 * world - 1) * blockcap;
-    hipLaunchKernelGGL(route_prepare_kernel, dim3((unsigned)std::min<int64_t>((nblank + 255) / 256, 1024)), dim3(256), 0, p->stream, world, ncols, blockcap,
-                       send_blocks_dev, recv_blocks_dev, cursor_dev);
-    if (cat->n > 0)
-        // (2048 workgroups: eight waves per SIMD hide the latency of the strided column stores; each adds to the per-destination cursors once)
-        hipLaunchKernelGGL(route_step_kernel, dim3((unsigned)std::min<int64_t>((cat->n + 255) / 256, 4 * kRouteGrid)), dim3(256), 0, p->stream, s, p->model, p->hpx,
-                           cat->n, cursor_dev);
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
 // the catalogs of the following K0 launches are BLOCKED: rows halo j's columns at (j / rows) * stride + (j % rows) from the column pointers (what
 // an all_to_all of fixed-capacity blocks [block][column][rows] delivers: stride = ncols * rows); rows = 0: plain columns again
 int bfgx_plan_set_catalog_blocks(bfgx_plan *p, int64_t rows, int64_t stride)
@@ -1446,22 +1091,6 @@ int bfgx_plan_tile_shape(bfgx_plan *p, int32_t *rings_per_band, int32_t *max_col
     if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
     if (rings_per_band) *rings_per_band = p->tiling.BR;
     if (max_columns) *max_columns = p->tiling.W;
-    return BFGX_OK;
-}
-
-int bfgx_disc_rings_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t *rings_dev)
-{
-    // (uses none of the plan's per-halo workspace: the catalog may be larger than the plan's max_halos)
-    if (!p || !cat) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (cat->n < 0) return fail(BFGX_ERR_INVALID, "catalog size < 0");
-    if (cat->n > 0 && (!cat->M || !cat->z || !cat->dec)) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
-    if (cat->n > 0 && !rings_dev) return fail(BFGX_ERR_INVALID, "rings pointer is NULL");
-    HIP_TRY(hipSetDevice(p->device));
-    if (cat->n > 0) {
-        hipLaunchKernelGGL(disc_rings_kernel, dim3((unsigned)((cat->n + 255) / 256)), dim3(256), 0, p->stream, p->model, p->hpx, cat->n, cat->M, cat->z,
-                           cat->dec, rings_dev, p->route_margin);
-        HIP_TRY(hipGetLastError());
-    }
     return BFGX_OK;
 }
 
@@ -1484,6 +1113,20 @@ int bfgx_paint_device(bfgx_plan *p, const bfgx_catalog *cat, void *map_out_dev, 
 
 }  // extern "C"
 
+// The two sums of the mass check from the per-tile sums of the tiles [t0, t0 + nt): added up by one workgroup, or -- above kSumTilesOneWg
+// tiles, where that single workgroup's loop takes 0.2 - 0.6 ms -- by 64 workgroups into the zeroed sums.  The caller checks the launch
+constexpr int kSumTilesOneWg = 16384;
+static int launch_tile_sums(bfgx_plan *p, int t0, int nt, double *sums_dev)
+{
+    const double *ts = p->tile_sums + 2 * (size_t)t0;
+    if (nt <= kSumTilesOneWg) hipLaunchKernelGGL(sum_tiles_kernel, dim3(1), dim3(256), 0, p->stream, nt, ts, sums_dev);
+    else {
+        HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
+        hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, nt, ts, sums_dev);
+    }
+    return BFGX_OK;
+}
+
 // the gathering regrid (algo 1): [largest |offset|^2 per tile unless K1 left it], aprons, lean gather, gather with the ring
 // walk over the tiles that need it, far list / repair
 template <typename ACC, typename real, bool SPLIT = false>
@@ -1504,15 +1147,12 @@ static void launch_regrid_gather(bfgx_plan *p, const double *map_in_dev, const A
                        map_out_dev, far, reach, ts, -1, nt, p->regrid_lean, (double *)nullptr);
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 2, SPLIT>), dim3(nwalk), dim3(256), lds_walk, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
                        map_out_dev, far, reach, ts, -1, nt, p->arena.todo, (double *)nullptr);
-    // the two sums of the mass check: added up by the last launch, or -- above 16384 tiles, where that single workgroup's loop
-    // takes 0.2 - 0.6 ms -- by 64 workgroups afterwards
-    const bool many = nt > 16384 && sums_dev != nullptr && ts != nullptr;
+    // the two sums of the mass check (ts: the plan's per-tile sums): added up by the last launch, or -- too many tiles for its one
+    // workgroup -- by launch_tile_sums afterwards (regrid_impl checks the launches)
+    const bool many = nt > kSumTilesOneWg && sums_dev != nullptr && ts != nullptr;
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 1, SPLIT>), dim3(nfix), dim3(256), lds, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
                        map_out_dev, far, reach, ts, -1, nt, p->arena.todo, many ? (double *)nullptr : sums_dev, p->regrid_lean);
-    if (many) {
-        (void)hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream);
-        hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, nt, (const double *)ts, sums_dev);
-    }
+    if (many) (void)launch_tile_sums(p, 0, nt, sums_dev);
 }
 
 extern "C" {
@@ -1620,12 +1260,20 @@ int bfgx_count_pairs_device(bfgx_plan *p, const bfgx_catalog *cat, int fallback4
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------ the banded (multi-GPU) passes, the far-deposit list
+#include "bfgx_shell_bands.inc"
+
+// ------------------------------------------------------------------------------ halo routing between ranks
+#include "bfgx_route_api.inc"
+
 // ------------------------------------------------------------------------------ one-shot host API
 #include "bfgx_oneshot.hpp"
 
 namespace {
 
 constexpr int kCatCols = 4 + BFGX_MAX_EXTRA + 2;       // M, z, ra, dec, extra[2], ln1pz, lnM
+// column i of them travels for a table with nex extra parameter axes (the extra[] beyond nex stay NULL)
+constexpr bool catalog_col_used(int i, int nex) { return i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA; }
 
 // the host columns of a catalog in upload order (M, z, ra, dec, extra[], ln1pz, lnM).  The (z, M) table coordinates are the caller's numpy
 // values when given, else libm on the host here (never the device's log: README.md:78-80 puts table edges exactly on the catalog's min/max)
@@ -1647,7 +1295,7 @@ int catalog_columns(const bfgx_catalog *h, int nex, std::vector<double> &hostlog
     for (int k = 0; k < BFGX_MAX_EXTRA; ++k) src[4 + k] = k < nex ? h->extra[k] : nullptr;
     src[4 + BFGX_MAX_EXTRA] = lnz; src[5 + BFGX_MAX_EXTRA] = lnm;
     for (int i = 0; i < kCatCols; ++i)
-        if ((i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA) && h->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
+        if (catalog_col_used(i, nex) && h->n > 0 && !src[i]) return fail(BFGX_ERR_INVALID, "catalog column pointer is NULL");
     return BFGX_OK;
 }
 
@@ -1661,19 +1309,27 @@ void catalog_view(int64_t n, int nex, const double *const col[kCatCols], bfgx_ca
     d->ln1pz = col[4 + BFGX_MAX_EXTRA]; d->lnM = col[5 + BFGX_MAX_EXTRA];
 }
 
-int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], bfgx_catalog *d, std::vector<double> &hostlog)
+// the used columns of a host catalog -> cols[] on the plan's stream, *d their device view; size(buffer, bytes) != 0: no memory
+template <class Buf, class Size>
+int upload_catalog_columns(bfgx_plan *p, const bfgx_catalog *h, Buf cols[kCatCols], Size size, bfgx_catalog *d, std::vector<double> &hostlog)
 {
     const int nex = p->model.tab.ndim - 3;
     const double *src[kCatCols], *dp[kCatCols] = {};
     if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
     for (int i = 0; i < kCatCols; ++i) {
-        if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
-        if (cols[i].alloc(sizeof(double) * (size_t)h->n)) return alloc_fail("catalog");
+        if (!catalog_col_used(i, nex)) continue;
+        if (size(cols[i], sizeof(double) * (size_t)h->n)) return alloc_fail("catalog");
         if (h->n > 0) HIP_TRY(hipMemcpyAsync(cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
         dp[i] = (const double *)cols[i].p;
     }
     catalog_view(h->n, nex, dp, d);
     return BFGX_OK;
+}
+
+// into buffers of the exact size that the caller's handle owns
+int upload_catalog(bfgx_plan *p, const bfgx_catalog *h, DevBuf cols[kCatCols], bfgx_catalog *d, std::vector<double> &hostlog)
+{
+    return upload_catalog_columns(p, h, cols, [](DevBuf &b, size_t bytes) { return b.alloc(bytes) != hipSuccess; }, d, hostlog);
 }
 
 struct ShellEntry : CacheEntry<bfgx_plan> {
@@ -1689,23 +1345,14 @@ std::atomic<long long> g_catalog_uploads{0};
 
 int upload_catalog_pooled(ShellEntry *e, const bfgx_catalog *h, bfgx_catalog *d, std::vector<double> &hostlog, uint64_t token)
 {
-    bfgx_plan *p = e->plan;
     if (token != 0 && token == e->cat_token && h->n == e->cat_n) {      // the same catalog as last time: its columns are still there
         *d = e->cat_dev;
         return BFGX_OK;
     }
     e->cat_token = 0;
     g_catalog_uploads.fetch_add(1);
-    const int nex = p->model.tab.ndim - 3;
-    const double *src[kCatCols], *dp[kCatCols] = {};
-    if (int rc = catalog_columns(h, nex, hostlog, src)) return rc;
-    for (int i = 0; i < kCatCols; ++i) {
-        if (!(i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA)) continue;
-        if (e->cols[i].need(sizeof(double) * (size_t)std::max<int64_t>(h->n, 1))) return alloc_fail("catalog");
-        if (h->n > 0) HIP_TRY(hipMemcpyAsync(e->cols[i].p, src[i], sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, p->stream));
-        dp[i] = (const double *)e->cols[i].p;
-    }
-    catalog_view(h->n, nex, dp, d);
+    auto size = [](PoolBuf &b, size_t bytes) { return b.need(std::max(bytes, sizeof(double))); };      // (an empty catalog: one element per column)
+    if (int rc = upload_catalog_columns(e->plan, h, e->cols, size, d, hostlog)) return rc;
     // (the copies above are from pageable memory: they have left the host buffers when hipMemcpyAsync returns)
     e->cat_token = token; e->cat_n = h->n; e->cat_dev = *d;
     return BFGX_OK;
@@ -1871,15 +1518,14 @@ int paint_streamed(ShellEntry *e, const bfgx_catalog *dcat, const PaintMode &m, 
     k3.paint_pair_f32 = m.pair_f32();
     k3.spread_tiles = p->tiling.ntiles;                  // K0 has binned the WHOLE catalog; every range launch sees the same density (ADVICE, round 4)
     for (int c = 0; c < ch.n; ++c) {
-        k3.tile_lo = p->band_tile0_host[ch.cb[c]];
-        k3.tile_n = p->band_tile0_host[ch.cb[c + 1]] - k3.tile_lo;
+        const BandRange r = band_range(p, ch.cb[c], ch.cb[c + 1]);
+        k3.tile_lo = r.t0; k3.tile_n = r.nt;
         // (the persistent kernel draws its tiles from a counter that the binning step zeroes: once more for every further launch)
         if (c > 0) HIP_TRY(hipMemsetAsync(p->arena.tile_counter, 0, sizeof(unsigned int), p->stream));
         if (int rc = launch_tile_scatter<MODE_PAINT, double>(p, (double *)e->out.p, k3)) return rc;      // (indexed by global pixel number)
         HIP_TRY(hipEventRecord(e->ev_k[c], p->stream));
         HIP_TRY(hipStreamWaitEvent(e->down, e->ev_k[c], 0));
-        const int64_t lo = ch.bfp[ch.cb[c]], n = ch.bfp[ch.cb[c + 1]] - lo;
-        HIP_TRY(hipMemcpyAsync(map_out + lo, (double *)e->out.p + lo, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->down));
+        HIP_TRY(hipMemcpyAsync(map_out + r.p0, (double *)e->out.p + r.p0, (size_t)(r.p1 - r.p0) * sizeof(double), hipMemcpyDeviceToHost, e->down));
     }
     return BFGX_OK;
 }
@@ -2034,99 +1680,7 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 #include "bfgx_hostcall.hpp"
 
 // ------------------------------------------------------------------------------ table builders (a6-a8)
-extern "C" {
-
-int bfgx_project_profile(int device, int64_t nrows, int32_t nl, const double *l, const double *rho,
-                         int64_t nr, const double *r, double scale, double *sigma_out)
-{
-    if (!l || !rho || !r || !sigma_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes (1 <= nrows <= 65535, 2 <= nl <= 2048)");
-    HostCall c(device);
-    const double *dl = c.in(l, nl), *drho = c.in(rho, nrows * nl), *dr = c.in(r, nr);
-    double *dout = c.out(sigma_out, nrows * nr);
-    if (int rc = c.ready()) return rc;
-    hipLaunchKernelGGL(project_kernel, dim3((unsigned)((nr + 255) / 256), (unsigned)nrows), dim3(256), 3 * sizeof(double) * nl, 0,
-                       nl, dl, drho, nr, dr, scale, dout);
-    return c.finish();
-}
-
-static int enclosed_mass_rows(int dim, int device, int64_t nrows, int64_t n_int, const double *r_int, const double *Sigma,
-                              int32_t nr, const double *r, double *M_f)
-{
-    if (!r_int || !Sigma || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nrows < 1 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    HostCall c(device);
-    const double *dri = c.in(r_int, n_int), *dS = c.in(Sigma, nrows * n_int), *dr = c.in(r, nr);
-    double *dcx = c.scratch<double>(nrows * n_int), *dcy = c.scratch<double>(nrows * n_int), *dM = c.out(M_f, nrows * nr);
-    if (int rc = c.ready()) return rc;
-    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri, dS, nr, dr, dcx, dcy, dM, dim);
-    return c.finish();
-}
-
-int bfgx_enclosed_mass_from_sigma(int device, int64_t nrows, int64_t n_int, const double *r_int, const double *Sigma,
-                                  int32_t nr, const double *r, double *M_f)
-{
-    return enclosed_mass_rows(2, device, nrows, n_int, r_int, Sigma, nr, r, M_f);
-}
-
-int bfgx_enclosed_mass_3d(int device, int64_t nrows, int64_t n_int, const double *r_int, const double *rho,
-                          int32_t nr, const double *r, double *M_f)
-{
-    return enclosed_mass_rows(3, device, nrows, n_int, r_int, rho, nr, r, M_f);
-}
-
-int bfgx_enclosed_mass_2d(int device, int64_t nrows, int32_t nl, const double *l, const double *rho, double a,
-                          int64_t n_int, const double *r_int, int32_t nr, const double *r, double *M_f)
-{
-    if (!l || !rho || !r_int || !r || !M_f) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nrows < 1 || nrows > 65535 || nl < 2 || nl > 2048 || n_int < 3 || nr < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    HostCall c(device);
-    const double *dl = c.in(l, nl), *drho = c.in(rho, nrows * nl), *dri = c.in(r_int, n_int);
-    double *dS = c.scratch<double>(nrows * n_int);
-    const double *dr = c.in(r, nr);
-    double *dcx = c.scratch<double>(nrows * n_int), *dcy = c.scratch<double>(nrows * n_int), *dM = c.out(M_f, nrows * nr);
-    if (int rc = c.ready()) return rc;
-    // Sigma = model.projected(r_int) * a   (BaryonCorrection.py:646), then the prefix sum + log-log PCHIP
-    hipLaunchKernelGGL(project_kernel, dim3((unsigned)((n_int + 255) / 256), (unsigned)nrows), dim3(256), 3 * sizeof(double) * nl, 0,
-                       nl, dl, drho, n_int, dri, a, dS);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enclosed_mass_kernel, dim3((unsigned)nrows), dim3(kTabThreads), 0, 0, n_int, dri, dS, nr, dr, dcx, dcy, dM, 2);
-    return c.finish();
-}
-
-int bfgx_displacement_rows(int device, int64_t nrows, int32_t nr, const double *r, const double *M_dmo, const double *M_dmb,
-                           double *d_out, int32_t *status)
-{
-    if (!r || !M_dmo || !M_dmb || !d_out || !status) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nrows < 1 || nr < 3 || nr > kMaxNR) return fail(BFGX_ERR_INVALID, "N_samples_R must be in [3, %d]", kMaxNR);
-    HostCall c(device);
-    const double *dr = c.in(r, nr), *da = c.in(M_dmo, nrows * nr), *db = c.in(M_dmb, nrows * nr);
-    double *dd = c.out(d_out, nrows * nr);
-    int32_t *ds = c.out(status, nrows);
-    if (int rc = c.ready()) return rc;
-    const size_t lds = kDisplacementLdsPerNode * nr;
-    HIP_TRY(hipFuncSetAttribute((const void *)displacement_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(displacement_kernel, dim3((unsigned)nrows), dim3(256), lds, 0, nr, dr, da, db, dd, ds);
-    return c.finish();
-}
-
-int bfgx_pressure_profile(int device, int64_t nrows, const double *r500, const double *rho_tot, const double *rho_gas,
-                          int32_t nr_out, const double *r_out, double cutoff, double *P_out)
-{
-    if (!r500 || !rho_tot || !rho_gas || !r_out || !P_out) return fail(BFGX_ERR_INVALID, "NULL argument");
-    if (nrows < 1 || nr_out < 1) return fail(BFGX_ERR_INVALID, "bad sizes");
-    HostCall c(device);
-    const double *dg = c.in(r500, kPressureN), *dt = c.in(rho_tot, nrows * kPressureN), *dgas = c.in(rho_gas, nrows * kPressureN);
-    const double *dr = c.in(r_out, nr_out);
-    double *dP = c.out(P_out, nrows * nr_out);
-    if (int rc = c.ready()) return rc;
-    const double G = kGnewt / (kMpcToMeter * kMpcToMeter * kMpcToMeter) * kSolarMass;       // Thermodynamic.py:11
-    const double unit = (kSolarMass * 1e3) / (kMpcToMeter * 1e2);                           // :265
-    hipLaunchKernelGGL(pressure_kernel, dim3((unsigned)nrows), dim3(256), 0, 0, dg, dt, dgas, nr_out, dr, G, unit, cutoff, dP);
-    return c.finish();
-}
-
-}  // extern "C"
+#include "bfgx_tables_api.inc"
 
 // ------------------------------------------------------------------------------ all GPUs of a node from one call
 #include "bfgx_multi_api.inc"

@@ -115,7 +115,7 @@ int shell_multi(bool paint, const bfgx_catalog *cat, const bfgx_model *model, in
     if (int rc = catalog_columns(cat, nex, hostlog, src)) return rc;
     // the catalog columns that travel with a halo (M, z, ra, dec, property columns, the caller's table coordinates)
     int colidx[kCatCols], ncol = 0;
-    for (int i = 0; i < kCatCols; ++i) if (i < 4 + nex || i >= 4 + BFGX_MAX_EXTRA) colidx[ncol++] = i;
+    for (int i = 0; i < kCatCols; ++i) if (catalog_col_used(i, nex)) colidx[ncol++] = i;
     // ---- phase 1 (all devices concurrently): upload the shard, ring range of every disc, halos per destination
     for (int d = 0; d < N; ++d) {
         MultiRank &r = R[d];
