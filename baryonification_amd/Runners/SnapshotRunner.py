@@ -71,12 +71,18 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
         cat, cols = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if is2D else hcat['z'], lnM)
         return snap, is2D, model, keep, cat, cols
 
-    def process_make_map(self, N_grid):
+    def process_make_map(self, N_grid, assignment='ngp'):
         """`ParticleSnapshot(cat=self.process(), ...).make_map(N_grid)` (SnapshotRunner.py:173-262 followed by io.py:622-670) as ONE call for
         the common case that only the map of the baryonified particles is wanted (the reference's notebook 10): the records go to the device
         once, the displaced coordinates exist only as the deposit's sort keys, the map comes back.  Not in the reference's API; the result
         equals the two calls (cell for cell with unit masses, to the order of the sums inside a cell otherwise).  Snapshots whose `cat` is
-        not one C-contiguous structured array of float64 fields take the two calls."""
+        not one C-contiguous structured array of float64 fields take the two calls.  The fused displace + deposit is nearest grid point
+        only: assignment='cic' or 'tsc' (see ParticleSnapshot.make_map) takes the two calls, process() and then make_map(N_grid, assignment)."""
+        if not isinstance(assignment, str) or assignment.lower() != 'ngp':
+            from .. import engine
+            if not isinstance(assignment, str) or engine.WINDOW_ORDERS.get(assignment.lower(), 0) < 1:      # (before any work, as make_map says it)
+                raise ValueError("make_map: assignment must be 'ngp', 'cic' or 'tsc', not %r" % (assignment,))
+            return self._map_of(self.process(), N_grid, assignment)
         if wants_exact(self, 'displacement'):            # a plain-Python model with bfgx_exact = True: the two calls
             return self._map_of(self.process(), N_grid)
         snap, is2D, model, keep, cat, cols = self._setup()
@@ -104,13 +110,13 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
                 return out
         return self._map_of(self.process(), N_grid)
 
-    def _map_of(self, new_cat, N_grid):
-        """ParticleSnapshot(cat=new_cat, ...).make_map(N_grid) with the snapshot's other attributes"""
+    def _map_of(self, new_cat, N_grid, assignment='ngp'):
+        """ParticleSnapshot(cat=new_cat, ...).make_map(N_grid, assignment) with the snapshot's other attributes"""
         from ..utils.io import ParticleSnapshot
         new = ParticleSnapshot.__new__(ParticleSnapshot)
         new.__dict__.update(self.ParticleSnapshot.__dict__)
         new.cat = new_cat
-        return new.make_map(N_grid)
+        return new.make_map(N_grid, assignment)
 
     def process(self):
         if wants_exact(self, 'displacement'):            # a plain-Python model with bfgx_exact = True: called per halo (:228, :245)

@@ -37,6 +37,7 @@
 #include "bfgx_fft.hpp"
 #include "bfgx_bispec.hpp"
 #include "bfgx_deposit.hpp"
+#include "bfgx_deposit_cloud.hpp"
 #include "bfgx_snapshot.hpp"
 #include "bfgx_snapshot_pairs.hpp"
 #include "bfgx_grid_gather.hpp"
@@ -1693,6 +1694,9 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 
 // particle deposit (ParticleSnapshot.make_map) and particle routing; the fused deposit + regrid needs the grid plan
 #include "bfgx_deposit_api.inc"
+
+// CIC / TSC particle deposit (make_map(N, assignment=...)): shares the deposit's sort and workspace
+#include "bfgx_deposit_cloud_api.inc"
 
 // 3-D FFT and power spectrum of gridded maps
 #include "bfgx_fft_api.inc"

@@ -7,6 +7,7 @@ namespace {
 // grow-only workspace of the tiled deposit, one per device (released by bfgx_cache_clear); one deposit in flight per device
 struct DepWork {
     PoolBuf keys[2], mass[2], ctr, bsum, total;     // uint32_t keys, double masses, int32_t counters and block sums, one int64_t (slack: an eighth)
+    PoolBuf halo;                                   // per-tile halo slabs of the CIC / TSC deposit (bfgx_deposit_cloud_api.inc)
 };
 std::mutex g_dep_mu;
 std::map<int, DepWork> g_dep;

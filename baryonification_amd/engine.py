@@ -355,6 +355,17 @@ def deposit_particles_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, edges_ptr
                                                         int(n_grid), C.c_void_p(int(edges_ptr)), C.c_void_p(int(map_out_ptr))))
 
 
+def deposit_cloud_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, L, order, map_out_ptr, ndim=3, device=0, stream=0):
+    """CIC (order 2) / TSC (order 3) mass assignment of device-resident columns on the periodic box [0, L]^ndim, enqueue-only; order as in
+    WINDOW_ORDERS (a name is taken too).  map_out [n_grid^ndim] is stored whole."""
+    if isinstance(order, str):
+        order = WINDOW_ORDERS.get(order.lower(), 0)
+    _lib.check(_lib.load().bfgx_deposit_cloud_device(int(device), C.c_void_p(int(stream) or None), int(ndim), int(n),
+                                                    C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None),
+                                                    C.c_void_p(int(z_ptr) or None), C.c_void_p(int(mass_ptr) or None),
+                                                    int(n_grid), float(L), int(order), C.c_void_p(int(map_out_ptr))))
+
+
 def route_particles_count_device(x_ptr, n, n_grid, edges_ptr, world, owner_ptr, counts_ptr, device=0, stream=0):
     """pass 1 of the particle routing of a slab-decomposed grid (enqueue-only): owner[n] uint8, counts[world] int32"""
     _lib.check(_lib.load().bfgx_route_particles_count_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(x_ptr) or None), int(n_grid),

@@ -208,9 +208,15 @@ class ParticleSnapshot(object):
     def cosmology(self):
         return self.cosmo
 
-    def make_map(self, N_grid):
+    def make_map(self, N_grid, assignment='ngp'):
+        """The masses on a grid of N_grid cells per axis.  assignment: 'ngp' (the reference's np.histogramdd), 'cic' or 'tsc' (cloud in
+        cell / triangular shaped cloud on the periodic box, cell centres at (i + 1/2) L / N_grid; not in the reference), case-insensitive.
+        `engine.cross_power_spectrum(..., window=assignment)` divides the matching window out."""
         import ctypes as C
-        from .. import _lib
+        from .. import _lib, engine
+        order = engine.WINDOW_ORDERS.get(assignment.lower(), 0) if isinstance(assignment, str) else 0
+        if order < 1:
+            raise ValueError("make_map: assignment must be 'ngp', 'cic' or 'tsc', not %r" % (assignment,))
         edges = np.linspace(0, self.L, N_grid + 1)
         ndim = 2 if self.is2D else 3
         rec = self.cat
@@ -221,17 +227,26 @@ class ParticleSnapshot(object):
             # the records as they are: no strided gather of the columns on the host (the library also makes the reference's NaN check of the
             # masses, io.py:636, and raises the same AssertionError)
             out = _lib.pinned_empty(N_grid ** ndim).reshape((N_grid,) * ndim)
-            rc = _lib.load().bfgx_deposit_particles_records(int(self.device), ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
-                                                            fields['x'][1], fields['y'][1], 0 if self.is2D else fields['z'][1], fields['M'][1],
-                                                            int(N_grid), edges.ctypes.data, out.ctypes.data)
+            offs = (fields['x'][1], fields['y'][1], 0 if self.is2D else fields['z'][1], fields['M'][1])
+            if order == 1:
+                rc = _lib.load().bfgx_deposit_particles_records(int(self.device), ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
+                                                                *offs, int(N_grid), edges.ctypes.data, out.ctypes.data)
+            else:
+                rc = _lib.load().bfgx_deposit_cloud_records(int(self.device), ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
+                                                            *offs, int(N_grid), float(self.L), order, out.ctypes.data)
             _lib.check(rc)
             return out
         assert np.isnan(self.cat['M']).sum() == 0, "If you want to make a map, provide a value for the particle mass"      # io.py:636
         x, y, m = _lib.f8(self.cat['x']), _lib.f8(self.cat['y']), _lib.f8(self.cat['M'])
         z = None if self.is2D else _lib.f8(self.cat['z'])
         out = np.empty((N_grid,) * ndim)
-        rc = _lib.load().bfgx_deposit_particles(int(self.device), ndim, x.size, x.ctypes.data, y.ctypes.data,
-                                                None if z is None else z.ctypes.data, m.ctypes.data, int(N_grid),
-                                                edges.ctypes.data, out.ctypes.data)
+        if order == 1:
+            rc = _lib.load().bfgx_deposit_particles(int(self.device), ndim, x.size, x.ctypes.data, y.ctypes.data,
+                                                    None if z is None else z.ctypes.data, m.ctypes.data, int(N_grid),
+                                                    edges.ctypes.data, out.ctypes.data)
+        else:
+            rc = _lib.load().bfgx_deposit_cloud(int(self.device), ndim, x.size, x.ctypes.data, y.ctypes.data,
+                                                None if z is None else z.ctypes.data, m.ctypes.data, int(N_grid), float(self.L), order,
+                                                out.ctypes.data)
         _lib.check(rc)
         return out

@@ -437,6 +437,19 @@ int bfgx_deposit_particles(int device, int32_t ndim, int64_t n, const double *x,
  * multiples of 8.  Device buffers are kept between calls (bfgx_cache_clear). */
 int bfgx_deposit_particles_records(int device, int32_t ndim, int64_t n, const void *records, int32_t itemsize, int32_t off_x, int32_t off_y,
                                    int32_t off_z, int32_t off_mass, int32_t n_grid, const double *edges, double *map_out);
+/* ParticleSnapshot.make_map(N, assignment='cic' | 'tsc'): cloud-in-cell (order 2) or triangular-shaped-cloud (order 3) mass assignment
+ * of n particles on the periodic box [0, L]^ndim with n_grid cells per axis (cell centres at (i + 1/2) L / n_grid); `order` as
+ * window_order of bfgx_cross_power_spectrum, which divides the matching window out.  Per axis, with t = v n_grid / L: CIC u = t - 1/2,
+ * i = floor(u), f = u - i: cells i and i + 1 (mod n_grid) get 1 - f and f; TSC i = min(floor(t), n_grid - 1), d = t - i - 1/2: cells
+ * i - 1, i, i + 1 (mod n_grid) get (1/2 - d)^2 / 2, 3/4 - d^2, (1/2 + d)^2 / 2.  A particle with a coordinate outside [0, L] (or NaN) is
+ * dropped as np.histogramdd drops it.  mass NULL -> 1; z NULL for 2D.  order must be 2 or 3 (BFGX_ERR_INVALID otherwise: nearest grid
+ * point is bfgx_deposit_particles).  x, y, z, mass host arrays. */
+int bfgx_deposit_cloud(int device, int32_t ndim, int64_t n, const double *x, const double *y, const double *z, const double *mass,
+                       int32_t n_grid, double L, int32_t order, double *map_out_host);
+/* The same on the snapshot's records (see bfgx_deposit_particles_records: same layout rules, same device-side NaN test of the masses
+ * with the same BFGX_ERR_ASSERT, same buffers kept between calls). */
+int bfgx_deposit_cloud_records(int device, int32_t ndim, int64_t n, const void *records, int32_t itemsize, int32_t off_x, int32_t off_y,
+                               int32_t off_z, int32_t off_mass, int32_t n_grid, double L, int32_t order, double *map_out);
 /* |FFT(map)|^2 averaged in nk linear k-bins between 2 pi / L and the Nyquist frequency (3D, n_grid a power of two):
  * pk[nk], kcen[nk] (mean |k| per bin), counts[nk] (modes per bin).  Empty bins give NaN as in the notebook. */
 int bfgx_power_spectrum(int device, int32_t n_grid, const double *map_host, double L, int32_t nk,
@@ -488,6 +501,11 @@ int  bfgx_deposit_particles_device(int device, void *hip_stream, int32_t ndim, i
 int  bfgx_deposit_particles_slab_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y,
                                         const double *z, const double *mass, int32_t n_grid, const double *edges_dev,
                                         int32_t plane_lo, int32_t plane_n, double *map_out_dev);
+/* bfgx_deposit_cloud on device-resident columns, enqueue-only: map_out_dev [n_grid^ndim] is stored whole (no need to zero it).  The
+ * tile-owned form (n >= 2^20 on a grid the NGP tiles take; BFGX_DEPOSIT=atomic / tiled forces a form) keeps a grow-only workspace per
+ * device, the per-tile halo scratch included, that bfgx_cache_clear releases; one deposit in flight per device. */
+int  bfgx_deposit_cloud_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
+                               const double *mass, int32_t n_grid, double L, int32_t order, double *map_out_dev);
 /* work_dev: scratch of bfgx_power_spectrum_work_doubles(n_grid) doubles (the half spectrum, complex [n_grid][n_grid][pitch] with
  * rows padded to whole 128-byte lines; its content is undefined afterwards: the last FFT pass bins |F|^2 straight from LDS) */
 int64_t bfgx_power_spectrum_work_doubles(int32_t n_grid);
