@@ -1707,6 +1707,9 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 // cross power spectrum of two gridded 3-D maps: the cross modes of the last FFT pass, window weights
 #include "bfgx_xpk_api.inc"
 
+// interlaced power spectrum of two grids half a cell apart, P(k) straight from particle columns
+#include "bfgx_interlace_api.inc"
+
 // ------------------------------------------------------------------------------ particle snapshots (8f-2)
 #include "bfgx_snapshot_api.inc"
 
@@ -1750,6 +1753,7 @@ extern "C" void bfgx_cache_clear(void)
     fft_release_all();           // twiddle / wavenumber tables of the power spectrum
     bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
     xpk_release_all();           // window tables of the cross power spectrum (bfgx_xpk_api.inc)
+    interlace_release_all();     // half-cell phase tables of the interlaced power spectrum (bfgx_interlace_api.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries
     g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
     deprec_release_all();        // device buffers of the deposit's records entry

@@ -6,11 +6,15 @@
 //   dropped   !(0 <= v <= L): below, above, NaN, +-inf; the whole particle goes (np.histogramdd's rule; v == L and -0.0 are inside)
 //   CIC       u = t - 0.5, i = floor(u), f = u - i: cell i mod N gets 1 - f, cell (i + 1) mod N gets f (i = -1 for u < 0)
 //   TSC       i = min(floor(t), N - 1), d = t - i - 0.5: cells (i - 1) mod N, i, (i + 1) mod N get 0.5 (0.5 - d)^2, 0.75 - d^2, 0.5 (0.5 + d)^2
+// On the SHIFTED grid (template flag SHIFT: grid 2 of an interlaced pair, every particle moved by +L / (2N) along every axis, periodically;
+// which particles are kept does not change, v == L lands in cell 0):
+//   CIC       i = floor(t) (0 .. N), f = t - i: cells i mod N and (i + 1) mod N get 1 - f and f
+//   TSC       t2 = t + 0.5, i = floor(t2) (0 .. N), d = t2 - i - 0.5: cells (i - 1) mod N, i mod N, (i + 1) mod N get the same three weights
 // and the particle adds m x the product of its per-axis weights to 2^dim / 3^dim cells.  No product is contracted into an FMA: the functions
 // that evaluate weights carry `#pragma clang fp contract(off)` (the HIP headers' __dmul_rn is a plain product and contracts like one),
 // so every weight is the fp64 number that the same expression gives on the host.
 //
-// Tile-owned form.  The particles are sorted by the tile of their BASE cell (CIC: i mod N; TSC: i) with the NGP sort as it is: the key
+// Tile-owned form.  The particles are sorted by the tile of their BASE cell (CIC: i mod N; TSC: i; shifted: i mod N) with the NGP sort as it is: the key
 // is dep_key of the base cell, and the 8-byte payload column that carries the masses for NGP carries the particle's INDEX (as a double,
 // exact below 2^53).  A workgroup per tile gathers x, y, z, m by that index, evaluates the weights again and accumulates in an LDS box of
 // the tile plus its halo (CIC: one cell on the upper side of every axis, 17 x 17 x 33 doubles = 76 KB; TSC: one cell on both sides,
@@ -29,16 +33,27 @@
 
 namespace bfgx {
 
-// one axis of one particle.  c: the base cell the particle is sorted by (CIC: i mod N; TSC: i); the cloud's cells are
+// one axis of one particle.  c: the base cell the particle is sorted by (CIC: i mod N; TSC: i; SHIFT: i mod N); the cloud's cells are
 // c - LO + k (mod N), k = 0 .. ORDER - 1, with LO = 0 (CIC) or 1 (TSC), and w[k] their weights.  false: the particle is dropped.
-template <int ORDER>
+template <int ORDER, bool SHIFT = false>
 __device__ inline bool cloud_axis(double v, double L, double s, int N, int &c, double (&w)[ORDER])
 {
 #pragma clang fp contract(off)
     static_assert(ORDER == 2 || ORDER == 3, "CIC or TSC");
     if (!(v >= 0.0) || !(v <= L)) return false;
     const double t = v * s;
-    if constexpr (ORDER == 2) {
+    if constexpr (SHIFT && ORDER == 2) {
+        const double fl = floor(t), f = t - fl;
+        const int i = (int)fl;                               // 0 .. N
+        w[0] = 1.0 - f; w[1] = f;
+        c = (i >= N) ? 0 : i;
+    } else if constexpr (SHIFT) {
+        const double t2 = t + 0.5, fl = floor(t2);
+        const int i = (int)fl;                               // 0 .. N
+        const double d = t2 - fl - 0.5, a = 0.5 - d, b = 0.5 + d;
+        w[0] = 0.5 * (a * a); w[1] = 0.75 - d * d; w[2] = 0.5 * (b * b);
+        c = (i >= N) ? 0 : i;
+    } else if constexpr (ORDER == 2) {
         const double u = t - 0.5, fl = floor(u), f = u - fl;
         const int i = (int)fl;                               // -1 .. N - 1
         w[0] = 1.0 - f; w[1] = f;
@@ -100,7 +115,7 @@ template <int DIM, int ORDER> struct CloudHalo {
 // grid cell of (tile origin) - LO + b, wrapped: the argument lies in [-1, N]
 __device__ inline int cloud_wrap(int gx, int N) { return gx < 0 ? gx + N : (gx >= N ? gx - N : gx); }
 
-template <int DIM, int ORDER>
+template <int DIM, int ORDER, bool SHIFT = false>
 __global__ void __launch_bounds__(256)
 deposit_cloud_keys_kernel(DepGeom g, int64_t n, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                           double L, double s, uint32_t *__restrict__ keys, double *__restrict__ index, int32_t *__restrict__ wg_hist, int64_t stride)
@@ -117,8 +132,8 @@ deposit_cloud_keys_kernel(DepGeom g, int64_t n, const double *__restrict__ x, co
         const double vx = on ? x[p * stride] : 0.0, vy = on ? y[p * stride] : 0.0, vz = (DIM == 3 && on) ? z[p * stride] : 0.0;
         int cx = 0, cy = 0, cz = 0;
         double w[ORDER];
-        bool inside = on && cloud_axis<ORDER>(vx, L, s, g.nb, cx, w) && cloud_axis<ORDER>(vy, L, s, g.nb, cy, w);
-        if (DIM == 3) inside = inside && cloud_axis<ORDER>(vz, L, s, g.nb, cz, w);
+        bool inside = on && cloud_axis<ORDER, SHIFT>(vx, L, s, g.nb, cx, w) && cloud_axis<ORDER, SHIFT>(vy, L, s, g.nb, cy, w);
+        if (DIM == 3) inside = inside && cloud_axis<ORDER, SHIFT>(vz, L, s, g.nb, cz, w);
         const uint32_t key = inside ? dep_key(g, cx, cy, cz) : kDepNoKey;
         lds_hist_rank(hist, (int)((key >> kDepLocalBits) >> g.lB2), inside);            // (every lane calls)
         if (on) { keys[p] = key; index[p] = (double)p; }
@@ -130,7 +145,7 @@ deposit_cloud_keys_kernel(DepGeom g, int64_t n, const double *__restrict__ x, co
 constexpr int kCloudTileThreads = 1024;            // one workgroup per CU (67 - 88 KB of LDS): make it large
 constexpr int kCloudFoldThreads = 256;
 
-template <int DIM, int ORDER>
+template <int DIM, int ORDER, bool SHIFT = false>
 __global__ void __launch_bounds__(kCloudTileThreads)
 deposit_cloud_tiles_kernel(DepGeom g, double L, double s, const int32_t *__restrict__ start2, const double *__restrict__ index,
                            const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
@@ -151,8 +166,8 @@ deposit_cloud_tiles_kernel(DepGeom g, double L, double s, const int32_t *__restr
         const double m = mass ? mass[p * stride] : 1.0;
         int cx = 0, cy = 0, cz = 0;
         double wx[ORDER], wy[ORDER], wz[ORDER];
-        bool ok = cloud_axis<ORDER>(x[p * stride], L, s, g.nb, cx, wx) && cloud_axis<ORDER>(y[p * stride], L, s, g.nb, cy, wy);
-        if (DIM == 3) ok = ok && cloud_axis<ORDER>(z[p * stride], L, s, g.nb, cz, wz);
+        bool ok = cloud_axis<ORDER, SHIFT>(x[p * stride], L, s, g.nb, cx, wx) && cloud_axis<ORDER, SHIFT>(y[p * stride], L, s, g.nb, cy, wy);
+        if (DIM == 3) ok = ok && cloud_axis<ORDER, SHIFT>(z[p * stride], L, s, g.nb, cz, wz);
         const int bx = cx - x0, by = cy - y0, bz = (DIM == 3) ? cz - z0 : 0;
         // (the sort brought the particle here because its base cell is in this tile; a box index is never taken on trust)
         if (!ok || bx < 0 || bx >= g.sx || by < 0 || by >= g.sy || bz < 0 || bz >= g.sz) continue;
@@ -212,7 +227,7 @@ deposit_cloud_fold_kernel(DepGeom g, const int32_t *__restrict__ start2, const d
 }
 
 // one thread per particle, 2^dim / 3^dim global atomics into a zero-filled map
-template <int DIM, int ORDER>
+template <int DIM, int ORDER, bool SHIFT = false>
 __global__ void __launch_bounds__(256)
 deposit_cloud_atomic_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                             const double *__restrict__ mass, int nb, double L, double s, double *__restrict__ out, int64_t stride)
@@ -223,8 +238,8 @@ deposit_cloud_atomic_kernel(int64_t n, const double *__restrict__ x, const doubl
     if (p >= n) return;
     int cx = 0, cy = 0, cz = 0;
     double wx[ORDER], wy[ORDER], wz[ORDER];
-    bool ok = cloud_axis<ORDER>(x[p * stride], L, s, nb, cx, wx) && cloud_axis<ORDER>(y[p * stride], L, s, nb, cy, wy);
-    if (DIM == 3) ok = ok && cloud_axis<ORDER>(z[p * stride], L, s, nb, cz, wz);
+    bool ok = cloud_axis<ORDER, SHIFT>(x[p * stride], L, s, nb, cx, wx) && cloud_axis<ORDER, SHIFT>(y[p * stride], L, s, nb, cy, wy);
+    if (DIM == 3) ok = ok && cloud_axis<ORDER, SHIFT>(z[p * stride], L, s, nb, cz, wz);
     if (!ok) return;
     const double m = mass ? mass[p * stride] : 1.0;
 #pragma unroll

@@ -1,20 +1,25 @@
-// bfgx_deposit_cloud_api.inc -- C ABI of the CIC / TSC particle deposit (ParticleSnapshot.make_map(N, assignment='cic' | 'tsc')); included
+// bfgx_deposit_cloud_api.inc -- C ABI of the CIC / TSC particle deposit (ParticleSnapshot.make_map(N, assignment='cic' | 'tsc')) and of
+// the same on the grid displaced by half a cell (bfgx_deposit_cloud_shifted_device, grid 2 of bfgx_interlace_api.inc); included
 // by bfgx_api.hip after bfgx_deposit_api.inc, whose workspace (DepWork, with the halo scratch), dep_tileable and record buffers (DepRecBuf)
 // it shares.  Kernels: bfgx_deposit_cloud.hpp; declarations: include/bfgx.h.
 
 namespace {
 
-// f(dim, order) with both as integral constants
-template <typename F> void cloud_dispatch(int ndim, int order, F &&f)
+// f(dim, order, shift) with all three as integral constants; shift: the grid displaced by half a cell (the second grid of an interlaced pair)
+template <typename F> void cloud_dispatch(int ndim, int order, int shift, F &&f)
 {
     grid_dim(ndim, [&](auto dim) {
-        if (order == 2) f(dim, std::integral_constant<int, 2>{});
-        else f(dim, std::integral_constant<int, 3>{});
+        auto with_order = [&](auto sh) {
+            if (order == 2) f(dim, std::integral_constant<int, 2>{}, sh);
+            else f(dim, std::integral_constant<int, 3>{}, sh);
+        };
+        if (shift) with_order(std::true_type{});
+        else with_order(std::false_type{});
     });
 }
 
 // the tile-owned form: the NGP sort (deposit_tiled) with the particle's index as payload, then the tile and fold launches
-int deposit_cloud_tiled(DepWork &w, const DepGeom &g, int order, hipStream_t s, int64_t n, const double *x, const double *y, const double *z,
+int deposit_cloud_tiled(DepWork &w, const DepGeom &g, int order, int shift, hipStream_t s, int64_t n, const double *x, const double *y, const double *z,
                         const double *mass, double L, double *map_out_dev, int64_t stride)
 {
     // counters as in deposit_tiled: count2[T + 1] start2[T + 1] cursor2[T], kDepPad words apart | level-1 histograms [B1][chunks] + 1
@@ -31,9 +36,10 @@ int deposit_cloud_tiled(DepWork &w, const DepGeom &g, int order, hipStream_t s, 
     const size_t lds = sizeof(double) * (size_t)cloud_box_cells(g, order);
     const double scale = (double)g.nb / L;             // s = N / L, computed once, on the host: the kernels multiply by the same number
     int rc = BFGX_OK;
-    cloud_dispatch(g.dim, order, [&](auto dim, auto ord) {
+    cloud_dispatch(g.dim, order, shift, [&](auto dim, auto ord, auto sh) {
         constexpr int DIM = decltype(dim)::value, ORDER = decltype(ord)::value;
-        hipLaunchKernelGGL((deposit_cloud_keys_kernel<DIM, ORDER>), dim3(chunks), dim3(256), 0, s, g, n, x, y, z, L, scale, keys[0], index[1], wg, stride);
+        constexpr bool SHIFT = decltype(sh)::value;
+        hipLaunchKernelGGL((deposit_cloud_keys_kernel<DIM, ORDER, SHIFT>), dim3(chunks), dim3(256), 0, s, g, n, x, y, z, L, scale, keys[0], index[1], wg, stride);
         exclusive_scan(s, nwg, wg, wg, bsum, total);          // (in place)
         hipLaunchKernelGGL((deposit_split_kernel<1, true>), dim3(chunks), dim3(256), 0, s, g, n, (const int32_t *)nullptr, (const uint32_t *)keys[0],
                            (const double *)index[1], (const int32_t *)wg, (int32_t *)nullptr, keys[1], index[0], (int64_t)1);
@@ -42,11 +48,11 @@ int deposit_cloud_tiled(DepWork &w, const DepGeom &g, int order, hipStream_t s, 
         exclusive_scan(s, (int64_t)g.T + 1, c2, s2, bsum, total);
         hipLaunchKernelGGL((deposit_split_kernel<2, true>), dim3(chunks), dim3(256), 0, s, g, n, nvalid, (const uint32_t *)keys[1],
                            (const double *)index[0], (const int32_t *)s2, k2, keys[0], index[1], (int64_t)1);
-        if (hipFuncSetAttribute((const void *)deposit_cloud_tiles_kernel<DIM, ORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        if (hipFuncSetAttribute((const void *)deposit_cloud_tiles_kernel<DIM, ORDER, SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             rc = fail(BFGX_ERR_HIP, "the cloud deposit's tile kernel needs %zu bytes of LDS", lds);
             return;
         }
-        hipLaunchKernelGGL((deposit_cloud_tiles_kernel<DIM, ORDER>), dim3(g.T), dim3(kCloudTileThreads), lds, s, g, L, scale, (const int32_t *)s2,
+        hipLaunchKernelGGL((deposit_cloud_tiles_kernel<DIM, ORDER, SHIFT>), dim3(g.T), dim3(kCloudTileThreads), lds, s, g, L, scale, (const int32_t *)s2,
                            (const double *)index[1], x, y, z, mass, stride, map_out_dev, halo);
         hipLaunchKernelGGL((deposit_cloud_fold_kernel<DIM, ORDER>), dim3(g.T), dim3(kCloudFoldThreads), 0, s, g, (const int32_t *)s2, (const double *)halo,
                            map_out_dev);
@@ -58,9 +64,10 @@ int deposit_cloud_tiled(DepWork &w, const DepGeom &g, int order, hipStream_t s, 
 
 // device columns (or fields of a record buffer at `stride` doubles) -> map_out_dev, enqueue-only
 int deposit_cloud_impl(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z, const double *mass,
-                       int32_t n_grid, double L, int32_t order, double *map_out_dev, int64_t stride = 1)
+                       int32_t n_grid, double L, int32_t order, double *map_out_dev, int64_t stride = 1, int32_t shift = 0)
 {
     if ((n > 0 && (!x || !y || (ndim == 3 && !z))) || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (shift != 0 && shift != 1) return fail(BFGX_ERR_INVALID, "shift %d: 0 (the grid) or 1 (the grid displaced by half a cell)", shift);
     if (order != 2 && order != 3)
         return fail(BFGX_ERR_INVALID, "the cloud deposit takes order 2 (CIC) or 3 (TSC), not %d; nearest grid point is bfgx_deposit_particles", order);
     if ((ndim != 2 && ndim != 3) || n_grid < 1 || n < 0 || !(L > 0.0) || !std::isfinite(L)) return fail(BFGX_ERR_INVALID, "deposit needs ndim in {2, 3}, n_grid >= 1, 0 < L < inf");
@@ -84,14 +91,14 @@ int deposit_cloud_impl(int device, void *hip_stream, int32_t ndim, int64_t n, co
         if (w.ctr.need(sizeof(int32_t) * nctr, 8, 0) || w.bsum.need(sizeof(int32_t) * (size_t)scan_block_count((int64_t)nctr), 8, 0) || w.total.need(sizeof(int64_t), 8, 0))
             return alloc_fail("deposit counters");
         if (w.halo.need(sizeof(double) * (size_t)g.T * (size_t)cloud_halo_cells(g, order), 8, 0)) return alloc_fail("deposit halo scratch");
-        return deposit_cloud_tiled(w, g, order, s, n, x, y, z, mass, L, map_out_dev, stride);
+        return deposit_cloud_tiled(w, g, order, shift, s, n, x, y, z, mass, L, map_out_dev, stride);
     }
     HIP_TRY(hipMemsetAsync(map_out_dev, 0, sizeof(double) * ntot, s));
     if (n > 0) {
         const double scale = (double)n_grid / L;       // (as in deposit_cloud_tiled)
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        cloud_dispatch(ndim, order, [&](auto dim, auto ord) {
-            hipLaunchKernelGGL((deposit_cloud_atomic_kernel<decltype(dim)::value, decltype(ord)::value>), dim3(blocks), dim3(256), 0, s, n, x, y, z, mass,
+        cloud_dispatch(ndim, order, shift, [&](auto dim, auto ord, auto sh) {
+            hipLaunchKernelGGL((deposit_cloud_atomic_kernel<decltype(dim)::value, decltype(ord)::value, decltype(sh)::value>), dim3(blocks), dim3(256), 0, s, n, x, y, z, mass,
                                n_grid, L, scale, map_out_dev, stride);
         });
         HIP_TRY(hipGetLastError());
@@ -107,6 +114,12 @@ int bfgx_deposit_cloud_device(int device, void *hip_stream, int32_t ndim, int64_
                               const double *mass, int32_t n_grid, double L, int32_t order, double *map_out_dev)
 {
     return deposit_cloud_impl(device, hip_stream, ndim, n, x, y, z, mass, n_grid, L, order, map_out_dev);
+}
+
+int bfgx_deposit_cloud_shifted_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
+                                      const double *mass, int32_t n_grid, double L, int32_t order, int32_t shift, double *map_out_dev)
+{
+    return deposit_cloud_impl(device, hip_stream, ndim, n, x, y, z, mass, n_grid, L, order, map_out_dev, 1, shift);
 }
 
 int bfgx_deposit_cloud(int device, int32_t ndim, int64_t n, const double *x, const double *y, const double *z, const double *mass,

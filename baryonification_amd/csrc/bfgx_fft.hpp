@@ -255,18 +255,36 @@ __host__ __device__ inline size_t fft_c2c_lds_bytes(int N, int lt, int nk, int b
 // The cross modes take one more kernel argument, XA = XpkArgs; BIN 0, 1, 2 are instantiated with the pack empty, which is the kernel
 // as it was before the cross modes existed, argument for argument (one body inlined into two kernels instead changed the register
 // allocation of BIN 0: 62 -> 78 VGPRs at LT = 2).
+// BIN 5 is BIN 0 with a twist, the store pass of grid 1 of an interlaced pair (bfgx_interlace_api.inc): the coefficient of mode (a, b, c)
+// is stored as 2 f conj(Phi), Phi = phi[a] phi[b] phi[c], phi[i] = exp(+i pi n_i / N) the half-cell phase of one axis (phi[N/2] = 1, which
+// keeps the combined field real).  The product of the three is one entry of a table over the sum of the wave numbers, phase[j] =
+// exp(+i pi j / N), j = (n_a + n_b + n_c) mod 2N with the Nyquist index counted as 0: one rounding and one complex product per mode
+// instead of three and three.  The cross pass of grid 2 against this spectrum then sums 4 |F1|^2, |F2|^2 and 2 Re(F1 conj(Phi F2)): the
+// three parts of |F1 + Phi F2|^2, the factor 2 (exact) put where the sums need it.  It takes TwistArgs as its extra argument and is an
+// instantiation of its own: BIN 0 .. 4 are compiled as they were.
+struct TwistArgs {
+    const double2 *phase;         // [2N]
+};
+// the wave number of index i as the twist counts it: fftfreq's, 0 at the Nyquist index
+__device__ inline int twist_wave_number(int i, int N) { return 2 * i < N ? i : (2 * i == N ? 0 : i - N); }
 __host__ __device__ inline XpkArgs xpk_args() { return XpkArgs{nullptr, nullptr, nullptr, nullptr}; }
 __host__ __device__ inline XpkArgs xpk_args(const XpkArgs &a) { return a; }
+__host__ __device__ inline XpkArgs xpk_args(const TwistArgs &) { return xpk_args(); }
+__host__ __device__ inline const double2 *twist_phase() { return nullptr; }
+__host__ __device__ inline const double2 *twist_phase(const XpkArgs &) { return nullptr; }
+__host__ __device__ inline const double2 *twist_phase(const TwistArgs &t) { return t.phase; }
 
 template <int BIN, int LT, int NT, typename... XA>
 __global__ void __launch_bounds__(NT, NT == 1024 ? 8 : 4)       // (1024 threads: 64 VGPRs, so that the two workgroups LDS holds both run)
 fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int64_t stride, int64_t outer_stride,
                        const double2 *__restrict__ tw, int nzt, int nouter, PkBins pb, XA... xargs)
 {
-    static_assert(sizeof...(XA) == (BIN >= 3 ? 1 : 0) && BIN >= 0 && BIN <= 4, "BIN 3 and 4 take XpkArgs, the others nothing");
+    static_assert(sizeof...(XA) == (BIN >= 3 ? 1 : 0) && BIN >= 0 && BIN <= 5, "BIN 3 and 4 take XpkArgs, BIN 5 TwistArgs, the others nothing");
     const XpkArgs xa = xpk_args(xargs...);
+    const double2 *const phase = twist_phase(xargs...);               // (BIN 5)
 
-    constexpr bool XPK = BIN >= 3;                                    // cross modes
+    constexpr bool XPK = BIN == 3 || BIN == 4;                        // cross modes
+    constexpr bool BINNED = BIN >= 1 && BIN <= 4;                     // nothing is written back
     constexpr bool TAB = BIN == 2 || BIN == 3;                        // bins from the table
     // a tile = the (1 << LT) adjacent lines kz0 .. kz0 + (1 << LT) of one `o`; rows are padded (fft_pitch), so the last tile of
     // a row reads up to 7 pad columns: lines of their own, transformed like the others and never binned or looked at
@@ -280,7 +298,7 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
     double *hbb = hp + pb.nk, *hab = hbb + pb.nk;                     // (BIN 3, 4)
     const int tid = threadIdx.x;
     for (int i = tid; i < (N >> 1); i += NT) twl[i] = tw[i];
-    if (BIN) {
+    if (BINNED) {
         for (int i = tid; i < pb.nk; i += NT) {
             hp[i] = 0.0;
             if (!TAB) { hk[i] = 0.0; hc[i] = 0ull; }
@@ -343,7 +361,11 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
         // ---- out: the last pass; row `row` of line l of the transform leaves through `emit`
         auto emit = [&](int row, int l, double2 f) {
             if (BIN == 0) base[(int64_t)row * stride + l] = f;
-            else if (BIN == 2) {
+            else if (BIN == 5) {                                                   // 2 f conj(Phi(row, column, line)); a pad column gets some phase
+                const int nsum = twist_wave_number(row, N) + twist_wave_number(pb.b0 + o, N) + twist_wave_number(kz0 + l, N);
+                const double2 ph = phase[nsum & (2 * N - 1)];                      // (N is a power of two)
+                base[(int64_t)row * stride + l] = make_double2(2.0 * (f.x * ph.x + f.y * ph.y), 2.0 * (f.y * ph.x - f.x * ph.y));
+            } else if (BIN == 2) {
                 const int bin = tb8[(row << LT) + l];                              // (pad columns carry 255)
                 if (bin != 255) {
                     const int cc = kz0 + l;
@@ -379,7 +401,7 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
                 const int l = t & (NL - 1), i0 = t >> LT;
                 // binned: neighbouring lanes take rows 37 apart (an odd multiplier permutes the rows): rows next to each other have
                 // almost the same |k| and would serialise on one histogram cell
-                const int i = BIN ? ((i0 * 37) & (h - 1)) : i0;
+                const int i = BINNED ? ((i0 * 37) & (h - 1)) : i0;
                 double2 fa0 = {}, fa1 = {};
                 double wr0 = 1.0, wr1 = 1.0, wl = 1.0;
                 if (XPK) {                                                         // issued first: in flight under the butterfly
@@ -400,7 +422,7 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
             const int mq = N >> 2;
             for (int t = tid; t < (mq << LT); t += NT) {
                 const int l = t & (NL - 1), b0_ = t >> LT;
-                const int p = BIN ? ((b0_ * 37) & (mq - 1)) : b0_;
+                const int p = BINNED ? ((b0_ * 37) & (mq - 1)) : b0_;
                 double2 fa0 = {}, fa1 = {}, fa2 = {}, fa3 = {};
                 double wr0 = 1.0, wr1 = 1.0, wr2 = 1.0, wr3 = 1.0, wl = 1.0;
                 if (XPK) {                                                         // issued first: in flight under the butterfly
@@ -431,7 +453,7 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
             }
         }
     }
-    if (BIN) {
+    if (BINNED) {
         __syncthreads();
         for (int i = tid; i < pb.nk; i += NT) {
             if (XPK) {
@@ -443,6 +465,18 @@ fft_c2c_strided_kernel(double2 *__restrict__ data, int N, int log2n, int nz, int
             else if (hc[i]) { atomicAdd(pb.pk_sum + i, hp[i]); atomicAdd(pb.k_sum + i, hk[i]); atomicAdd(pb.counts + i, hc[i]); }
         }
     }
+}
+
+// the sums the cross pass leaves for an interlaced pair (p1_sum = sum w 4 |F1|^2, p_sum = sum w (|F2|^2 + 2 Re(F1 conj(Phi F2)))) ->
+// p1_sum = sum w |F1|^2, p_sum = sum w |F1 + Phi F2|^2 / 4
+__global__ void __launch_bounds__(256)
+interlace_combine_kernel(int nk, double *__restrict__ p_sum, double *__restrict__ p1_sum)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nk) return;
+    const double p1 = 0.25 * p1_sum[i];
+    p1_sum[i] = p1;
+    p_sum[i] = 0.25 * (p1 + p_sum[i]);
 }
 
 }  // namespace bfgx

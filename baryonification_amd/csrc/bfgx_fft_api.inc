@@ -1,5 +1,5 @@
 // bfgx_fft_api.inc -- host side of the 3-D FFT and C ABI of the power spectrum of gridded maps (include/bfgx.h, "power spectrum");
-// included by bfgx_api.hip after bfgx_deposit_api.inc.  bfgx_bispec_api.inc and bfgx_xpk_api.inc build on FftSetup, fft_setup, fft_planes
+// included by bfgx_api.hip after bfgx_deposit_api.inc.  bfgx_bispec_api.inc, bfgx_xpk_api.inc and bfgx_interlace_api.inc build on FftSetup, fft_setup, fft_planes
 // and fft_pitch.
 // Kernels: bfgx_fft.hpp.
 
@@ -58,6 +58,23 @@ struct FftSetup {
         HIP_TRY(hipLaunchKernel(xpk_fn<BIN>(), dim3(wgs), dim3((unsigned)threads), args, bytes, s));
         return BFGX_OK;
     }
+    // the twisted store pass of an interlaced pair (BIN 5; bfgx_interlace_api.inc): the LDS of BIN 0, the thread counts init() selects
+    const void *twist_fn()
+    {
+        if (lt == 3) return threads == 512 ? (const void *)fft_c2c_strided_kernel<5, 3, 512, TwistArgs> : (const void *)fft_c2c_strided_kernel<5, 3, 256, TwistArgs>;
+        return threads == 512 ? (const void *)fft_c2c_strided_kernel<5, 2, 512, TwistArgs> : (const void *)fft_c2c_strided_kernel<5, 2, 256, TwistArgs>;
+    }
+    int twist_launch(hipStream_t s, unsigned wgs, double2 *F, int N, int64_t stride, int64_t outer_stride, int nouter, int b0, const double2 *phase)
+    {
+        const double2 *twp = dtw.as<double2>();
+        int lg_ = lg, nz_ = nz, nzt_ = (int)ztiles;
+        PkBins pbv{};
+        pbv.b0 = b0;
+        TwistArgs tav{phase};
+        void *args[] = {&F, &N, &lg_, &nz_, &stride, &outer_stride, &twp, &nzt_, &nouter, &pbv, &tav};
+        HIP_TRY(hipLaunchKernel(twist_fn(), dim3(wgs), dim3((unsigned)threads), args, lds, s));
+        return BFGX_OK;
+    }
     int n_cu = 256;
     double k_lo = 0, dk = 0;
     int init(int device, int N, double L, int nk)            // (device: the current one)
@@ -97,6 +114,7 @@ struct FftSetup {
         lds_bin4 = fft_c2c_lds_bytes(N, lt, nk, 4);
         if (int rc = xpk_attr<3>(lds_bin3)) return rc;
         if (int rc = xpk_attr<4>(lds_bin4)) return rc;
+        HIP_TRY(hipFuncSetAttribute(twist_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         n_cu = device_cu_count(device);
         return BFGX_OK;
     }

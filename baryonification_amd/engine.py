@@ -355,15 +355,16 @@ def deposit_particles_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, edges_ptr
                                                         int(n_grid), C.c_void_p(int(edges_ptr)), C.c_void_p(int(map_out_ptr))))
 
 
-def deposit_cloud_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, L, order, map_out_ptr, ndim=3, device=0, stream=0):
+def deposit_cloud_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, L, order, map_out_ptr, ndim=3, device=0, stream=0, shift=0):
     """CIC (order 2) / TSC (order 3) mass assignment of device-resident columns on the periodic box [0, L]^ndim, enqueue-only; order as in
-    WINDOW_ORDERS (a name is taken too).  map_out [n_grid^ndim] is stored whole."""
+    WINDOW_ORDERS (a name is taken too).  map_out [n_grid^ndim] is stored whole.  shift=1: on the grid displaced by half a cell (every
+    particle moved by +L / (2 n_grid) along every axis), the second grid of interlaced_power_spectrum."""
     if isinstance(order, str):
         order = WINDOW_ORDERS.get(order.lower(), 0)
-    _lib.check(_lib.load().bfgx_deposit_cloud_device(int(device), C.c_void_p(int(stream) or None), int(ndim), int(n),
-                                                    C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None),
-                                                    C.c_void_p(int(z_ptr) or None), C.c_void_p(int(mass_ptr) or None),
-                                                    int(n_grid), float(L), int(order), C.c_void_p(int(map_out_ptr))))
+    _lib.check(_lib.load().bfgx_deposit_cloud_shifted_device(int(device), C.c_void_p(int(stream) or None), int(ndim), int(n),
+                                                            C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None),
+                                                            C.c_void_p(int(z_ptr) or None), C.c_void_p(int(mass_ptr) or None),
+                                                            int(n_grid), float(L), int(order), int(shift), C.c_void_p(int(map_out_ptr))))
 
 
 def route_particles_count_device(x_ptr, n, n_grid, edges_ptr, world, owner_ptr, counts_ptr, device=0, stream=0):
@@ -513,6 +514,150 @@ def cross_power_spectrum(MapA, MapB, Lbox, Nk=180, window=0, device=0):
     with np.errstate(divide='ignore', invalid='ignore'):
         r = pab / np.sqrt(paa * pbb)
     return {'k': k, 'paa': paa, 'pbb': pbb, 'pab': pab, 'r': r, 'counts': cnt}
+
+
+def _window_order(window, what):
+    """0 .. 3 of a window given as that number or as a name of WINDOW_ORDERS (ValueError otherwise)"""
+    if isinstance(window, str):
+        if window.lower() in WINDOW_ORDERS:
+            return WINDOW_ORDERS[window.lower()]
+    elif not isinstance(window, bool) and window in (0, 1, 2, 3):
+        return int(window)
+    raise ValueError("%s: window must be 0, 1, 2, 3 or 'none', 'ngp', 'cic', 'tsc'" % what)
+
+
+def interlaced_power_spectrum_device(map1_ptr, map2_ptr, n_grid, L, nk, window_order, work_ptr, p_sum_ptr, p1_sum_ptr, k_sum_ptr, counts_ptr,
+                                     device=0, stream=0):
+    """the sums of w |F1 + Phi F2|^2 / 4 (p_sum) and of w |F1|^2 (p1_sum), of |k| and the counts per linear k-bin of two device-resident
+    grids, the second deposited half a cell away; work = cross_power_spectrum_work_doubles(n_grid) doubles of scratch"""
+    _lib.check(_lib.load().bfgx_interlaced_power_spectrum_device(int(device), C.c_void_p(int(stream) or None), int(n_grid), C.c_void_p(int(map1_ptr)),
+                                                                C.c_void_p(int(map2_ptr)), float(L), int(nk), int(window_order),
+                                                                C.c_void_p(int(work_ptr)), C.c_void_p(int(p_sum_ptr)), C.c_void_p(int(p1_sum_ptr)),
+                                                                C.c_void_p(int(k_sum_ptr)), C.c_void_p(int(counts_ptr))))
+
+
+def interlaced_power_spectrum(Map1, Map2, Lbox, Nk=180, window='tsc'):
+    """P(k) of two grids of ONE particle set, Map2 deposited half a cell away from Map1 (deposit_cloud_device(..., shift=1)), combined in
+    Fourier space so that the odd aliased images cancel, in the bins and units of power_spectrum; `window` as in cross_power_spectrum.
+    Two numpy cubes (uploaded to device 0) or two CUDA float64 tensors, which are analysed where they lie on the current stream.  Returns
+    a dict of numpy arrays: k, pk (the interlaced estimate), pk_grid1 (Map1 alone: the aliased estimate), counts; empty bins NaN."""
+    import torch
+    p = _window_order(window, "interlaced_power_spectrum")
+    Nk = int(Nk)
+    dev1 = hasattr(Map1, 'data_ptr') and not isinstance(Map1, np.ndarray)
+    dev2 = hasattr(Map2, 'data_ptr') and not isinstance(Map2, np.ndarray)
+    if dev1 != dev2:
+        raise ValueError("interlaced_power_spectrum needs two numpy arrays or two CUDA float64 tensors, not one of each")
+    if not dev1:
+        Map1, Map2 = _lib.f8(Map1), _lib.f8(Map2)
+        if Map1.ndim != 3 or len(set(Map1.shape)) != 1:
+            raise ValueError("interlaced_power_spectrum needs cubic 3-D maps")
+        if Map1.shape != Map2.shape:
+            raise ValueError("interlaced_power_spectrum needs two maps of one shape")
+        # (torch takes no read-only array: such a map is copied first)
+        Map1, Map2 = (torch.from_numpy(m if m.flags.writeable else m.copy()).to('cuda:0') for m in (Map1, Map2))
+    Map1, Map2 = _cuda_f8_cube(Map1, "interlaced_power_spectrum"), _cuda_f8_cube(Map2, "interlaced_power_spectrum")
+    if Map1.shape != Map2.shape or Map1.device != Map2.device:
+        raise ValueError("interlaced_power_spectrum needs two maps of one shape on one device")
+    N = int(Map1.shape[0])
+    work = torch.empty(cross_power_spectrum_work_doubles(N), dtype=torch.float64, device=Map1.device)
+    sums = torch.empty((3, max(Nk, 1)), dtype=torch.float64, device=Map1.device)
+    cntd = torch.empty(max(Nk, 1), dtype=torch.int64, device=Map1.device)
+    interlaced_power_spectrum_device(Map1.data_ptr(), Map2.data_ptr(), N, Lbox, Nk, p, work.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(),
+                                     sums[2].data_ptr(), cntd.data_ptr(), device=Map1.device.index or 0,
+                                     stream=torch.cuda.current_stream(Map1.device).cuda_stream)
+    s, cnt = sums.cpu().numpy(), cntd.cpu().numpy()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return {'k': s[2] / cnt, 'pk': s[0] / cnt, 'pk_grid1': s[1] / cnt, 'counts': cnt}
+
+
+def particle_power_spectrum_work_doubles(n_grid):
+    """doubles of scratch particle_power_spectrum_device needs (two maps and two half spectra)"""
+    return int(_lib.load().bfgx_particle_power_spectrum_work_doubles(int(n_grid)))
+
+
+def particle_power_spectrum_device(x_ptr, y_ptr, z_ptr, mass_ptr, n, n_grid, L, order, interlace, nk, work_ptr, p_sum_ptr, p1_sum_ptr, k_sum_ptr,
+                                   counts_ptr, device=0, stream=0):
+    """device-resident particle columns -> the four sums of interlaced_power_spectrum_device: deposit, shifted deposit, spectrum, enqueue-only;
+    order 2 (CIC) or 3 (TSC), whose window is divided out; interlace=0: one deposit, the windowed auto spectrum in both p_sum and p1_sum"""
+    _lib.check(_lib.load().bfgx_particle_power_spectrum_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(x_ptr) or None),
+                                                              C.c_void_p(int(y_ptr) or None), C.c_void_p(int(z_ptr) or None),
+                                                              C.c_void_p(int(mass_ptr) or None), int(n_grid), float(L), int(order), int(interlace),
+                                                              int(nk), C.c_void_p(int(work_ptr)), C.c_void_p(int(p_sum_ptr)),
+                                                              C.c_void_p(int(p1_sum_ptr)), C.c_void_p(int(k_sum_ptr)), C.c_void_p(int(counts_ptr))))
+
+
+def particle_power_spectrum(coords, mass, N_grid, Lbox, Nk=180, assignment='tsc', interlace=True, normalize=False, subtract_shot_noise=False,
+                            device=0):
+    """P(k) of particles of the periodic box [0, Lbox]^3 up to the Nyquist frequency of a grid of N_grid cells per axis, without the maps
+    ever leaving the device: CIC or TSC deposit (`assignment`), with interlace=True a second deposit half a cell away and the two grids
+    combined in Fourier space (the odd aliased images cancel), the assignment's window divided out.  coords = (x, y, z) as numpy arrays
+    or as CUDA float64 tensors (analysed where they lie on the current stream; `device` is then theirs); mass: likewise, or None for unit
+    masses.  Particles with a coordinate outside [0, Lbox] are dropped, as make_map drops them.
+    Returns a dict of numpy arrays k, pk, pk_grid1 (the first grid alone: the aliased estimate; equal to pk without interlacing), counts,
+    and the floats shot_noise = sum m^2 and mass = sum m over the kept particles.  The defaults are in the units of power_spectrum (the
+    unnormalised fftn of the mass grid); normalize=True multiplies pk, pk_grid1 and shot_noise by Lbox^3 / mass^2 (the spectrum of the
+    density contrast); subtract_shot_noise=True subtracts shot_noise from pk and pk_grid1."""
+    order = WINDOW_ORDERS.get(assignment.lower(), -1) if isinstance(assignment, str) else -1
+    if order < 1:
+        raise ValueError("particle_power_spectrum: assignment must be 'cic' or 'tsc', not %r" % (assignment,))
+    if order == 1:
+        raise ValueError("particle_power_spectrum: assignment 'ngp' has no interlaced form%s; use 'cic' or 'tsc'" % (
+            "" if interlace else " and no entry here (make_map and power_spectrum give its spectrum)"))
+    if len(coords) != 3:
+        raise ValueError("particle_power_spectrum needs coords = (x, y, z): the spectra here are 3-D")
+    Nk, N_grid, Lbox = int(Nk), int(N_grid), float(Lbox)
+    on_dev = [hasattr(c, 'data_ptr') and not isinstance(c, np.ndarray) for c in coords]
+    m_dev = mass is not None and hasattr(mass, 'data_ptr') and not isinstance(mass, np.ndarray)
+    if any(on_dev) != all(on_dev) or (mass is not None and m_dev != on_dev[0]):
+        raise ValueError("particle_power_spectrum needs numpy arrays or CUDA float64 tensors, not some of each")
+    out = np.empty((3, max(Nk, 1)))
+    cnt = np.empty(max(Nk, 1), dtype=np.int64)
+    if not on_dev[0]:
+        x, y, z = (_lib.f8(c).ravel() for c in coords)
+        m = None if mass is None else _lib.f8(mass).ravel()
+        if not (x.size == y.size == z.size and (m is None or m.size == x.size)):
+            raise ValueError("particle_power_spectrum needs columns of one length")
+        _lib.check(_lib.load().bfgx_particle_power_spectrum(int(device), x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data,
+                                                           None if m is None else m.ctypes.data, N_grid, Lbox, order, int(bool(interlace)), Nk,
+                                                           out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, cnt.ctypes.data))
+        pk, pk1, k = out
+        with np.errstate(invalid='ignore'):
+            keep = (x >= 0) & (x <= Lbox) & (y >= 0) & (y <= Lbox) & (z >= 0) & (z <= Lbox)
+        mk = np.ones(int(keep.sum())) if m is None else m[keep]
+        m_tot, shot = float(mk.sum()), float((mk * mk).sum())
+    else:
+        import torch
+        cols = list(coords) + ([] if mass is None else [mass])
+        for c in cols:
+            if not isinstance(c, torch.Tensor) or not c.is_cuda or c.dtype != torch.float64 or c.dim() != 1:
+                raise ValueError("particle_power_spectrum needs 1-D CUDA float64 tensors")
+        if any(c.shape != cols[0].shape or c.device != cols[0].device for c in cols):
+            raise ValueError("particle_power_spectrum needs columns of one length on one device")
+        cols = [c.contiguous() for c in cols]
+        x, y, z = cols[:3]
+        m = None if mass is None else cols[3]
+        dev = x.device
+        n = int(x.shape[0])
+        work = torch.empty(particle_power_spectrum_work_doubles(N_grid), dtype=torch.float64, device=dev)
+        sums = torch.empty((3, max(Nk, 1)), dtype=torch.float64, device=dev)
+        cntd = torch.empty(max(Nk, 1), dtype=torch.int64, device=dev)
+        particle_power_spectrum_device(x.data_ptr() if n else 0, y.data_ptr() if n else 0, z.data_ptr() if n else 0,
+                                       m.data_ptr() if (m is not None and n) else 0, n, N_grid, Lbox, order, int(bool(interlace)), Nk,
+                                       work.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), sums[2].data_ptr(), cntd.data_ptr(),
+                                       device=dev.index or 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+        s, cnt = sums.cpu().numpy(), cntd.cpu().numpy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            pk, pk1, k = s[0] / cnt, s[1] / cnt, s[2] / cnt
+        keep = (x >= 0) & (x <= Lbox) & (y >= 0) & (y <= Lbox) & (z >= 0) & (z <= Lbox)
+        mk = keep.to(torch.float64) if m is None else torch.where(keep, m, torch.zeros_like(m))
+        m_tot, shot = float(mk.sum()), float((mk * mk).sum())
+    if subtract_shot_noise:
+        pk, pk1 = pk - shot, pk1 - shot
+    if normalize:
+        norm = Lbox ** 3 / m_tot ** 2 if m_tot != 0 else float('nan')
+        pk, pk1, shot = pk * norm, pk1 * norm, shot * norm
+    return {'k': k, 'pk': pk, 'pk_grid1': pk1, 'counts': cnt, 'shot_noise': shot, 'mass': m_tot}
 
 
 def fft_slab_axis0_device(work_ptr, n_grid, ncols, inverse=0, device=0, stream=0):

@@ -250,3 +250,15 @@ class ParticleSnapshot(object):
                                                 out.ctypes.data)
         _lib.check(rc)
         return out
+
+    def power_spectrum(self, N_grid, Nk=180, assignment='tsc', interlace=True, normalize=False, subtract_shot_noise=False):
+        """P(k) of the particles up to the Nyquist frequency of a grid of N_grid cells per axis: `engine.particle_power_spectrum` on the
+        snapshot's columns (CIC or TSC deposit, by default on two interlaced grids, the window divided out; the maps stay on the device).
+        The suppression of a baryonified snapshot is the ratio of two such calls.  3-D snapshots only."""
+        from .. import _lib, engine
+        if self.is2D:
+            raise ValueError("power_spectrum: the spectra here are 3-D, this snapshot is 2-D")
+        assert np.isnan(self.cat['M']).sum() == 0, "If you want to make a map, provide a value for the particle mass"      # (as make_map)
+        cols = tuple(_lib.f8(self.cat[k]) for k in ('x', 'y', 'z'))
+        return engine.particle_power_spectrum(cols, _lib.f8(self.cat['M']), N_grid, self.L, Nk=Nk, assignment=assignment, interlace=interlace,
+                                              normalize=normalize, subtract_shot_noise=subtract_shot_noise, device=self.device)

@@ -506,6 +506,13 @@ int  bfgx_deposit_particles_slab_device(int device, void *hip_stream, int32_t nd
  * device, the per-tile halo scratch included, that bfgx_cache_clear releases; one deposit in flight per device. */
 int  bfgx_deposit_cloud_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
                                const double *mass, int32_t n_grid, double L, int32_t order, double *map_out_dev);
+/* The same with shift = 1 on the grid displaced by half a cell, the second grid of an interlaced pair: every particle moved by
+ * +L / (2 n_grid) along every axis, periodically, defined in cell units.  Per axis, with t = v n_grid / L: CIC i = floor(t) (0 .. n_grid),
+ * f = t - i: cells i and i + 1 (mod n_grid) get 1 - f and f; TSC t2 = t + 1/2, i = floor(t2), d = t2 - i - 1/2: cells i - 1, i, i + 1 (mod
+ * n_grid) get (1/2 - d)^2 / 2, 3/4 - d^2, (1/2 + d)^2 / 2.  Which particles are kept does not change (v = L is inside and lands in cell 0).
+ * shift = 0 is bfgx_deposit_cloud_device; any other value is BFGX_ERR_INVALID. */
+int  bfgx_deposit_cloud_shifted_device(int device, void *hip_stream, int32_t ndim, int64_t n, const double *x, const double *y, const double *z,
+                                       const double *mass, int32_t n_grid, double L, int32_t order, int32_t shift, double *map_out_dev);
 /* work_dev: scratch of bfgx_power_spectrum_work_doubles(n_grid) doubles (the half spectrum, complex [n_grid][n_grid][pitch] with
  * rows padded to whole 128-byte lines; its content is undefined afterwards: the last FFT pass bins |F|^2 straight from LDS) */
 int64_t bfgx_power_spectrum_work_doubles(int32_t n_grid);
@@ -597,6 +604,33 @@ int  bfgx_fft_slab_axis0_xpk_device(int device, void *hip_stream, int32_t n_grid
  * bfgx_power_spectrum */
 int  bfgx_cross_power_spectrum(int device, int32_t n_grid, const double *map_a_host, const double *map_b_host, double L, int32_t nk,
                                int32_t window_order, double *paa, double *pbb, double *pab, double *kcen, int64_t *counts);
+
+/* ---- interlaced power spectrum ------------------------------------------------------------------------------
+ * Two grids of one particle set, the second deposited half a cell away (bfgx_deposit_cloud_shifted_device), combined in Fourier space so
+ * that the odd aliased images cancel: with F1, F2 the unnormalised fftn of the grids and phi[i] = exp(+i pi n_i / N) per axis (n =
+ * fftfreq(N) N; phi[N/2] = 1, a definition that keeps the combined field real), C = (F1 + phi[a] phi[b] phi[c] F2) / 2.  Per linear
+ * k-bin of bfgx_power_spectrum, p_sum = sum w |C|^2 and p1_sum = sum w |F1|^2 (grid 1 alone, the aliased estimate), w the window weights of
+ * bfgx_cross_power_spectrum; k_sum and counts as there.  Limits, alignment and messages are those of the cross power spectrum; the phase
+ * table is kept per (device, n_grid) until bfgx_cache_clear.  Sums by floating-point atomics, as there. */
+/* map1_dev, map2_dev [n][n][n] -> the four sums [nk], all pointers device; work_dev: bfgx_cross_power_spectrum_work_doubles(n_grid)
+ * doubles.  Enqueue-only once the tables exist. */
+int  bfgx_interlaced_power_spectrum_device(int device, void *hip_stream, int32_t n_grid, const double *map1_dev, const double *map2_dev, double L,
+                                           int32_t nk, int32_t window_order, double *work_dev, double *p_sum_dev, double *p1_sum_dev,
+                                           double *k_sum_dev, unsigned long long *counts_dev);
+/* doubles of scratch bfgx_particle_power_spectrum_device needs: the two maps and the two half spectra (host arithmetic) */
+int64_t bfgx_particle_power_spectrum_work_doubles(int32_t n_grid);
+/* Particle columns (device, 3-D; mass NULL -> 1) -> the same four sums: the deposit of `order` (2 = CIC, 3 = TSC; anything else, nearest
+ * grid point included, is BFGX_ERR_INVALID), the shifted deposit, the interlaced spectrum with that order's window divided out; nothing
+ * leaves the device.  interlace = 0: one deposit and the windowed auto spectrum, p_sum = p1_sum.  One call in flight per device (the
+ * deposit's workspace). */
+int  bfgx_particle_power_spectrum_device(int device, void *hip_stream, int64_t n, const double *x, const double *y, const double *z,
+                                         const double *mass, int32_t n_grid, double L, int32_t order, int32_t interlace, int32_t nk,
+                                         double *work_dev, double *p_sum_dev, double *p1_sum_dev, double *k_sum_dev,
+                                         unsigned long long *counts_dev);
+/* the same on host columns (synchronous): pk, pk_grid1 = the sums divided by counts, kcen = mean |k| per bin, NaN for empty bins */
+int  bfgx_particle_power_spectrum(int device, int64_t n, const double *x, const double *y, const double *z, const double *mass, int32_t n_grid,
+                                  double L, int32_t order, int32_t interlace, int32_t nk, double *pk, double *pk_grid1, double *kcen,
+                                  int64_t *counts);
 
 /* ---- particle-snapshot path ----------------------------------------------------------
  * Replaces BaryonifySnapshot.process, BaryonForge/Runners/SnapshotRunner.py:173-262: every particle within
