@@ -179,6 +179,7 @@ struct bfgx_plan {
     int32_t cnt_pad = 1;             // words between region A's counters of two tiles (a 128-byte line each up to 8192 tiles): see wave_run_issue
     TileRef *tref = nullptr;
     FarList far;                     // deposits of the gathering regrid that need the generic route (bfgx_regrid2.hpp); count and overflow lie in the arena
+    FarSrc far_src;                  // the source pixels of those deposits, listed by the gather kernels for regrid_far_eval_kernel; count in the arena, sums behind tile_sums
     int32_t *regrid_lean = nullptr;  // [0] = count (zeroed by the regrid's last launch), then the tiles of the lean kernel (reach <= 1 ring)
     // precision of the displacement path when the caller leaves it to the plan (BFGX_ACC_AUTO): chosen at plan creation from how far the
     // TABLE can move a pixel (plan_pick_precision): fp32 pair math holds SURVEY 8(d)'s 1e-6 mean(map) while one halo moves a pixel by less
@@ -198,7 +199,7 @@ struct bfgx_plan {
     const float *tab8f = nullptr;
     const double *tab8d = nullptr;
     unsigned long long *pair_total = nullptr;
-    double *tile_sums = nullptr;     // [ntiles][2] per-tile {sum of source values, sum of deposits} of the tiled regrid
+    double *tile_sums = nullptr;     // [ntiles + 1][2] per-tile {sum of source values, sum of deposits} of the tiled regrid, then [kFarEvalWgs] deposit totals of the far-pixel evaluator
     std::vector<int32_t> band_tile0_host;   // first tile of every band (+ total)
     int64_t capacity = 0;
     KernelEvents events;             // optional per-kernel HIP-event timing (bfgx_plan_timing_*)
@@ -783,13 +784,15 @@ static int plan_init_regrid(bfgx_plan *p)
     const int64_t want = p->table_disp_pixels < 0.25 ? npx / 16 : (p->table_disp_pixels < 2.0 ? npx / 2 : 4 * npx);
     p->far.cap = std::min<int64_t>(std::max<int64_t>((int64_t)1 << 20, want), (int64_t)1 << 28);
     if (const char *e = std::getenv("BFGX_FAR_CAP")) p->far.cap = std::max<int64_t>(1024, std::atoll(e));          // tests: force the overflow
+    p->far_src.cap = p->far.cap / 4;                  // four deposits per source pixel
     if (p->mem.alloc(p->far.pix, (size_t)p->far.cap) || p->mem.alloc(p->far.val, (size_t)p->far.cap) ||
-        p->mem.alloc(p->tile_apron, 2 * (size_t)(T.ntiles + 1)))
+        p->mem.alloc(p->far_src.ent, (size_t)p->far_src.cap) || p->mem.alloc(p->tile_apron, 2 * (size_t)(T.ntiles + 1)))
         return alloc_fail("far list");
     if (p->mem.alloc(p->regrid_lean, (size_t)(T.ntiles + 4))) return alloc_fail("lean tile list");
     if (hipMemsetAsync(p->regrid_lean, 0, sizeof(int32_t) * 4, p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "hipMemset failed");
     // the list's counter and its two overflow flags lie in the arena (the full-map regrid swaps far_overflow_full in: launch_regrid_gather)
     p->far.count = &p->arena.ctrl->far_count;
+    p->far_src.count = &p->arena.ctrl->far_src_count;
     p->far.overflow = p->arena.band_overflow;
     if (hipMemsetAsync(p->arena.ctrl, 0, p->arena.tail_bytes, p->stream) != hipSuccess) return fail(BFGX_ERR_HIP, "hipMemset failed");
     return BFGX_OK;
@@ -901,7 +904,9 @@ int bfgx_plan_create(int device, void *hip_stream, int64_t nside, int64_t max_ha
     int32_t *scan = nullptr;
     if (p->mem.alloc(scan, SL.total_words)) return bail(alloc_fail("tile scan scratch"));
     p->scan.bind(scan, SL);
-    if (p->mem.alloc(p->tile_sums, 2 * (size_t)(p->tiling.ntiles + 1))) return bail(alloc_fail("tile sums"));
+    if (p->mem.alloc(p->tile_sums, 2 * (size_t)(p->tiling.ntiles + 1) + kFarEvalWgs)) return bail(alloc_fail("tile sums"));
+    p->far_src.sums = p->tile_sums + 2 * (size_t)(p->tiling.ntiles + 1);
+    if (hipMemsetAsync(p->far_src.sums, 0, sizeof(double) * kFarEvalWgs, p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
     if (hipMemsetAsync(p->overflow, 0, sizeof(int32_t), p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "hipMemset failed"));
     if (hipStreamSynchronize(p->stream) != hipSuccess) return bail(fail(BFGX_ERR_HIP, "stream sync failed"));
     *out = p;
@@ -1115,21 +1120,23 @@ int bfgx_paint_device(bfgx_plan *p, const bfgx_catalog *cat, void *map_out_dev, 
 }  // extern "C"
 
 // The two sums of the mass check from the per-tile sums of the tiles [t0, t0 + nt): added up by one workgroup, or -- above kSumTilesOneWg
-// tiles, where that single workgroup's loop takes 0.2 - 0.6 ms -- by 64 workgroups into the zeroed sums.  The caller checks the launch
+// tiles, where that single workgroup's loop takes 0.2 - 0.6 ms -- by 64 workgroups into the zeroed sums; the deposit totals the far-pixel
+// evaluator left behind the per-tile sums go in with them.  The caller checks the launch
 constexpr int kSumTilesOneWg = 16384;
 static int launch_tile_sums(bfgx_plan *p, int t0, int nt, double *sums_dev)
 {
     const double *ts = p->tile_sums + 2 * (size_t)t0;
-    if (nt <= kSumTilesOneWg) hipLaunchKernelGGL(sum_tiles_kernel, dim3(1), dim3(256), 0, p->stream, nt, ts, sums_dev);
+    const double *fs = p->far_src.sums;
+    if (nt <= kSumTilesOneWg) hipLaunchKernelGGL(sum_tiles_kernel, dim3(1), dim3(256), 0, p->stream, nt, ts, sums_dev, fs, kFarEvalWgs);
     else {
         HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
-        hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, nt, ts, sums_dev);
+        hipLaunchKernelGGL(sum_tiles_multi_kernel, dim3(64), dim3(256), 0, p->stream, nt, ts, sums_dev, fs, kFarEvalWgs);
     }
     return BFGX_OK;
 }
 
 // the gathering regrid (algo 1): [largest |offset|^2 per tile unless K1 left it], aprons, lean gather, gather with the ring
-// walk over the tiles that need it, far list / repair
+// walk over the tiles that need it, the generic route of the pixels those two listed, far list / repair
 template <typename ACC, typename real, bool SPLIT = false>
 static void launch_regrid_gather(bfgx_plan *p, const double *map_in_dev, const ACC *o, const ACC *o_lo, double *map_out_dev, double *ts, bool from_k1, double *sums_dev)
 {
@@ -1145,14 +1152,15 @@ static void launch_regrid_gather(bfgx_plan *p, const double *map_in_dev, const A
                        reach.cap, 0, nt, p->tile_apron, p->arena.todo, p->regrid_lean);
     // (the lean kernel: a persistent grid over the tiles whose reach is one ring -- all of them on a table of sub-pixel moves, none on the S19 table)
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 0, SPLIT>), dim3(std::min(nt, 8 * p->num_cus)), dim3(256), lds, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
-                       map_out_dev, far, reach, ts, -1, nt, p->regrid_lean, (double *)nullptr);
+                       map_out_dev, far, p->far_src, reach, ts, -1, nt, p->regrid_lean, (double *)nullptr);
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 2, SPLIT>), dim3(nwalk), dim3(256), lds_walk, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
-                       map_out_dev, far, reach, ts, -1, nt, p->arena.todo, (double *)nullptr);
+                       map_out_dev, far, p->far_src, reach, ts, -1, nt, p->arena.todo, (double *)nullptr);
+    hipLaunchKernelGGL((regrid_far_eval_kernel<ACC, SPLIT>), dim3(kFarEvalWgs), dim3(256), 0, p->stream, p->hpx, p->tiling.rings, map_in_dev, o, o_lo, p->far_src, far);
     // the two sums of the mass check (ts: the plan's per-tile sums): added up by the last launch, or -- too many tiles for its one
     // workgroup -- by launch_tile_sums afterwards (regrid_impl checks the launches)
     const bool many = nt > kSumTilesOneWg && sums_dev != nullptr && ts != nullptr;
     hipLaunchKernelGGL((tile_regrid3_kernel<ACC, real, 1, SPLIT>), dim3(nfix), dim3(256), lds, p->stream, p->hpx, p->tiling, map_in_dev, o, o_lo,
-                       map_out_dev, far, reach, ts, -1, nt, p->arena.todo, many ? (double *)nullptr : sums_dev, p->regrid_lean);
+                       map_out_dev, far, p->far_src, reach, ts, -1, nt, p->arena.todo, many ? (double *)nullptr : sums_dev, p->regrid_lean);
     if (many) (void)launch_tile_sums(p, 0, nt, sums_dev);
 }
 

@@ -2067,13 +2067,14 @@ ring_functions_kernel(Hpx h, int first, int n, RingRec *__restrict__ out)
     out[i] = g;
 }
 
-// sums[0] = sum of tile_sums[2 t], sums[1] = sum of tile_sums[2 t + 1]   (one workgroup)
+// sums[0] = sum of tile_sums[2 t], sums[1] = sum of tile_sums[2 t + 1] + sum of the nextra doubles of extra   (one workgroup)
 __global__ void __launch_bounds__(256)
-sum_tiles_kernel(int ntiles, const double *__restrict__ tile_sums, double *__restrict__ sums)
+sum_tiles_kernel(int ntiles, const double *__restrict__ tile_sums, double *__restrict__ sums, const double *__restrict__ extra = nullptr, int nextra = 0)
 {
     __shared__ double sa[256 / kWave], sb[256 / kWave];
     double xa = 0.0, xb = 0.0;
     for (int t = threadIdx.x; t < ntiles; t += 256) { xa += tile_sums[2 * t]; xb += tile_sums[2 * t + 1]; }
+    for (int t = threadIdx.x; t < nextra; t += 256) xb += extra[t];
 #pragma unroll
     for (int s = kWave >> 1; s > 0; s >>= 1) { xa += __shfl_down(xa, s, kWave); xb += __shfl_down(xb, s, kWave); }
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
@@ -2089,12 +2090,13 @@ sum_tiles_kernel(int ntiles, const double *__restrict__ tile_sums, double *__res
 // the same over many tiles (NSIDE >= 4096: 1e5 .. 4e5 tiles, 0.6 ms for one workgroup): sums[0 .. 1] += the workgroup's part (sums zeroed
 // by the caller; one atomic pair per workgroup)
 __global__ void __launch_bounds__(256)
-sum_tiles_multi_kernel(int ntiles, const double *__restrict__ tile_sums, double *__restrict__ sums)
+sum_tiles_multi_kernel(int ntiles, const double *__restrict__ tile_sums, double *__restrict__ sums, const double *__restrict__ extra = nullptr, int nextra = 0)
 {
     __shared__ double sa[256 / kWave], sb[256 / kWave];
     double xa = 0.0, xb = 0.0;
     const double2 *ts = reinterpret_cast<const double2 *>(tile_sums);
     for (int t = blockIdx.x * 256 + threadIdx.x; t < ntiles; t += gridDim.x * 256) { const double2 v = ts[t]; xa += v.x; xb += v.y; }
+    if (blockIdx.x == 0) for (int t = threadIdx.x; t < nextra; t += 256) xb += extra[t];      // (the first workgroup takes the extra terms)
 #pragma unroll
     for (int s = kWave >> 1; s > 0; s >>= 1) { xa += __shfl_down(xa, s, kWave); xb += __shfl_down(xb, s, kWave); }
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;

@@ -47,14 +47,45 @@ __device__ inline float row_inv_dphi(const RegRow *, const RegRowC<float> *rowc,
 __device__ inline double row_inv_dphi(const RegRow *rows, const RegRowC<double> *, int t) { return rows[t].inv_dphi; }
 __host__ __device__ inline size_t regrowc_bytes(size_t real_size) { return real_size == 4 ? sizeof(RegRowC<float>) : sizeof(RegRowC<double>); }
 
-// the 4 targets of one displaced pixel by the generic route: get_interpol (healpix_cxx) on (theta, phi) of v + o, fp64
-__device__ inline void regrid_targets_generic(const Hpx &h, const RingRec *__restrict__ rings, const RegRow *rows, int LR, int rth0, int ti, int x,
-                                                    double o0, double o1, double o2, int tr[4], int tk[4], double w[4])
+// Where the generic route takes its ring data from.  Both forms answer in GLOBAL ring numbers with the bits of the plan's ring table (a tile's
+// rows are copies of its records): the repair pass has the tile's window in LDS and asks the table only beyond it, the far-pixel evaluator has
+// no tile and reads the table throughout.  lo() .. hi(): the rings whose colatitudes the displaced colatitude is compared with.
+struct GenRing { double theta, inv_dphi; int nr; bool shf; };
+struct GenSrc { double theta, z, sth, dphi; int ring, k; bool shf; };          // the source pixel: its ring's geometry, ring number, column in the ring
+struct GenRows {                     // a tile's ring tables: rows 0 .. LR + 1 are the rings rth0 .. rth0 + LR + 1
+    const RegRow *rows; const RingRec *__restrict__ rings; int rth0, LR;
+    __device__ inline int lo() const { return rth0; }
+    __device__ inline int hi() const { return rth0 + LR + 1; }
+    __device__ inline double theta(int ir) const { return rows[ir - rth0].theta; }
+    __device__ inline GenRing ring(int ir) const
+    {
+        const int t2 = ir - rth0;
+        if (t2 >= 0 && t2 < LR + 2) { const RegRow &r2 = rows[t2]; return GenRing{r2.theta, r2.inv_dphi, r2.nr, r2.shf != 0}; }
+        const RingRec &g2 = rings[ir];                                          // a ring beyond the window: from the plan's ring table
+        return GenRing{g2.theta, g2.inv_dphi, g2.nr, g2.shifted != 0};
+    }
+    __device__ inline GenSrc source(int ti, int x) const
+    {
+        const RegRow &rw = rows[ti];
+        return GenSrc{rw.theta, rw.z, rw.sth, rw.dphi, rth0 + ti, rw.ks + x, rw.shf != 0};
+    }
+};
+constexpr int kGenWalk = 17;         // the evaluator compares with the rings up to kReachMax + 1 either side of the source ring, the least a walking tile's window holds
+struct GenTable {                    // the plan's ring table alone (rings 0 and 4 nside: theta = -+1e300, which ends every walk)
+    const RingRec *__restrict__ rings; int lo_, hi_;
+    __device__ inline int lo() const { return lo_; }
+    __device__ inline int hi() const { return hi_; }
+    __device__ inline double theta(int ir) const { return rings[ir].theta; }
+    __device__ inline GenRing ring(int ir) const { const RingRec &g2 = rings[ir]; return GenRing{g2.theta, g2.inv_dphi, g2.nr, g2.shifted != 0}; }
+};
+
+// the 4 targets of one displaced pixel by the generic route: get_interpol (healpix_cxx) on (theta, phi) of v + o, fp64.  tr: GLOBAL ring numbers
+template <typename RS>
+__device__ inline void regrid_targets_generic(const Hpx &h, const RS &rs, const GenSrc &src, double o0, double o1, double o2, int tr[4], int tk[4], double w[4])
 {
     const int nl4 = (int)(4 * h.nside);
-    const RegRow &rw = rows[ti];
-    const double z = rw.z, sth = rw.sth;
-    const double phi = ((double)(rw.ks + x) + (rw.shf ? 0.5 : 0.0)) * rw.dphi;
+    const double z = src.z, sth = src.sth;
+    const double phi = ((double)src.k + (src.shf ? 0.5 : 0.0)) * src.dphi;
     double s, c;
     sincos_bounded(phi, s, c);
     const double nx = sth * c + o0, ny = sth * s + o1, nz = z + o2;                  // HealpixRunner.py:333
@@ -67,18 +98,24 @@ __device__ inline void regrid_targets_generic(const Hpx &h, const RingRec *__res
     double theta, ph;
     if (xr > 0.0 && fabs(tq) <= 0.1 && fabs(q) <= 0.05) {
         ph = phi + atan_small(tq);
-        theta = rw.theta + asin_small(q);
+        theta = src.theta + asin_small(q);
     } else {
         theta = atan2_generic(sn, zc);
         ph = atan2_generic(ny, nx);
     }
     if (ph < 0) ph += kTwoPi;
     if (ph >= kTwoPi) ph -= kTwoPi;
-    int t1 = ti;
-    while (t1 > 0 && theta < rows[t1].theta) --t1;
-    while (t1 < LR + 1 && theta >= rows[t1 + 1].theta) ++t1;
-    const bool in_window = (theta >= rows[t1].theta) && (t1 < LR + 1) && (theta < rows[t1 + 1].theta);
-    const int ir1 = in_window ? rth0 + t1 : (int)ring_above(h, zc);
+    // the ring above the displaced colatitude: by comparison with the ring colatitudes around the source ring; ring_above beyond them.
+    // The colatitudes rise with the ring number, so the pair of rings that brackets theta is the same wherever the comparisons start:
+    // they start at ring_above's answer (held inside the compared range), one or two steps from the bracket, not at the source ring --
+    // from the plan's ring table every step is a dependent read, and a listed pixel has moved 15 rings or more
+    const int rlo = rs.lo(), rhi = rs.hi();
+    const int rz = (int)ring_above(h, zc);
+    int r1 = rz < rlo ? rlo : (rz > rhi ? rhi : rz);
+    while (r1 > rlo && theta < rs.theta(r1)) --r1;
+    while (r1 < rhi && theta >= rs.theta(r1 + 1)) ++r1;
+    const bool in_window = (theta >= rs.theta(r1)) && (r1 < rhi) && (theta < rs.theta(r1 + 1));
+    const int ir1 = in_window ? r1 : rz;
     const int ir2 = ir1 + 1;
     double theta1 = 0.0, theta2 = 0.0;
     for (int q4 = 0; q4 < 4; ++q4) { tr[q4] = 0; tk[q4] = 0; w[q4] = 0.0; }
@@ -86,15 +123,9 @@ __device__ inline void regrid_targets_generic(const Hpx &h, const RingRec *__res
     for (int half = 0; half < 2; ++half) {
         const int ir = half ? ir2 : ir1;
         if (half ? (ir < nl4) : (ir > 0)) {
-            const int t2 = ir - rth0;
-            int n2; double shd, invd, th;
-            if (t2 >= 0 && t2 < LR + 2) {
-                const RegRow &r2 = rows[t2];
-                n2 = r2.nr; shd = r2.shf ? 0.5 : 0.0; invd = r2.inv_dphi; th = r2.theta;
-            } else {
-                const RingRec &g2 = rings[ir];                          // a ring beyond the window: from the plan's ring table
-                n2 = g2.nr; shd = g2.shifted ? 0.5 : 0.0; invd = g2.inv_dphi; th = g2.theta;
-            }
+            const GenRing g2 = rs.ring(ir);
+            const int n2 = g2.nr;
+            const double shd = g2.shf ? 0.5 : 0.0, invd = g2.inv_dphi, th = g2.theta;
             const double tmp = ph * invd - shd;
             int j1 = (int)floor(tmp);
             const double w1 = tmp - (double)j1;
@@ -178,9 +209,10 @@ struct RMathE {
 // Which pixels are gathered is a property of the SOURCE pixel alone, decided by arithmetic every tile repeats bit for bit:
 //     gathered  <=>  |o|^2 < lim(ring)^2,   lim = min(cap, 0.09 sin(theta_ring), 0.999 x the distance to the first / last ring)
 // (cap = regrid_cap(nside), at most kReachMax rings); the move is then small enough for the small-angle formulas (|t| < 0.1,
-// |q| < 0.021) and never crosses a pole.  Everything else (huge displacements, the pixels next to a pole) is appended by the
-// tile that OWNS the source pixel to a global list which a small fix-up kernel adds to the stored map afterwards; if that
-// list overflows, a second pass over the owners (regrid_far_pass_kernel) applies those deposits with atomics instead.
+// |q| < 0.021) and never crosses a pole.  Everything else (huge displacements, the pixels next to a pole) is LISTED by the
+// tile that OWNS the source pixel (FarSrc); regrid_far_eval_kernel evaluates that list by the generic route and appends four
+// deposits per pixel to a global list (FarList), which the regrid's last launch adds to the stored map; if either list
+// overflows, that launch walks the owners again (PASS 1) and applies those deposits with atomics instead.
 //
 // The apron of a tile follows the data: tile_reach_kernel leaves the largest |o| of every tile, a tile takes the maximum m
 // over the tiles around it and evaluates R = regrid_reach_rings(m) rings and K columns beyond its own pixels -- 1 ring and
@@ -222,6 +254,36 @@ struct FarList {
     int32_t *overflow;
 };
 
+// The source pixels that take the generic route, listed by the tile that owns them (each at most once per regrid) and evaluated by
+// regrid_far_eval_kernel: four deposits each, so cap = FarList.cap / 4 -- a longer list would overflow the deposit list anyway.  Entries beyond
+// cap are dropped and raise FarList.overflow like a deposit that does not fit.
+// workgroups of the evaluator: each leaves the total of its deposits in sums[blockIdx.x], zero included.  1024 of four waves fill the 256 CUs
+// at the four waves per SIMD its 110 VGPRs allow.  (An entry is a chain of dependent reads -- entry, ring record, offsets, the colatitudes round
+// the guessed ring, the two target rings' records, the returning atomic -- and that chain, not the grid, is what bounds a long list: 2.9e7
+// entries, config 4 at its real density, take 6.6 ms with 256 workgroups and with 1024)
+constexpr int kFarEvalWgs = 1024;
+struct FarSrc {
+    unsigned int *count;          // entries appended (may exceed cap: overflow)
+    int2 *ent;                    // {ring, column in the ring}
+    int64_t cap;
+    double *sums;                 // [kFarEvalWgs], behind the per-tile sums: the final summation of the mass check runs over them too
+};
+
+// One wave appends the positions of its active lanes to the source list: ONE returning atomic.  A lane whose entry does not fit returns false
+__device__ inline bool far_src_append(const FarSrc &fs, int ring, int k)
+{
+    const unsigned long long act = __ballot(1);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, 0u));
+    const int leader = __ffsll((long long)act) - 1;
+    unsigned base = 0;
+    if (rank == 0) base = atomicAdd(fs.count, (unsigned)__popcll(act));
+    base = (unsigned)__shfl((int)base, leader, kWave);
+    const unsigned i = base + (unsigned)rank;
+    if ((int64_t)i >= fs.cap) return false;
+    fs.ent[i] = make_int2(ring, k);
+    return true;
+}
+
 struct ReachArgs {
     const int32_t *apron;         // [ntiles][2]: rings / columns of apron of every tile (tile_apron_kernel)
     double cap;                   // no pixel with |o| >= cap is gathered
@@ -237,7 +299,8 @@ constexpr int kWalkFar = (256 / kWave) * kWalkQ;      // per wave a second queue
 __host__ __device__ inline size_t regrid3_lds_bytes(int BR, int W, size_t real_size, bool walk = false, size_t acc_size = 0)
 {
     if (acc_size == 0) acc_size = real_size;
-    const size_t base = (size_t)BR * W * sizeof(double) + (size_t)(BR + 2 * kReachMax + 2) * (sizeof(RegRow) + regrowc_bytes(real_size)) + 16;
+    // (the last 32 bytes: what the waves that build the ring tables publish of them -- widest span, shortest / longest ring)
+    const size_t base = (size_t)BR * W * sizeof(double) + (size_t)(BR + 2 * kReachMax + 2) * (sizeof(RegRow) + regrowc_bytes(real_size)) + 16 + 32;
     if (!walk) return base;
     return base + (size_t)(BR + 2 * kReachMax + 2) * sizeof(RowScan) + (size_t)(256 / kWave) * kWalkQ * (sizeof(double) + sizeof(int32_t) + 3 * acc_size)
            + (size_t)(kWalkFar + 4) * sizeof(int32_t);
@@ -485,15 +548,16 @@ __device__ inline bool regrid_gather_targets(const RegRow *rows, const RegRowC<r
     return true;
 }
 
-// one source pixel by the generic route, its four deposits appended to the far list; returns the sum of the deposits.  (Out of line it costs
-// the walking kernel 23 spilled registers around the call and 3 % of its time, the lean kernel 20 %: inlined.)
-__device__ inline double regrid_far_pixel(
-    const Hpx &h, const RingRec *__restrict__ rings, const RegRow *rows, int LR, int rth0, int ti, int x, double o0, double o1, double o2,
-                                                double val, FarList far)
+// one source pixel by the generic route, its four deposits appended to the far list; returns the sum of the deposits.  The gather kernels do
+// not call it: inlined into their loops it cost the walking kernel registers it does not have (7 of its 10 spilled VGPRs) and ran on the handful
+// of lanes a wave finds among its own pixels; they list such pixels (FarSrc) and regrid_far_eval_kernel evaluates the list on full waves.
+template <typename RS>
+__device__ inline double regrid_far_pixel(const Hpx &h, const RingRec *__restrict__ rings, const RS &rs, const GenSrc &src, double o0, double o1, double o2,
+                                          double val, FarList far)
 {
     int tr[4], tk[4];
     double w[4], tot = 0.0;
-    regrid_targets_generic(h, rings, rows, LR, rth0, ti, x, o0, o1, o2, tr, tk, w);
+    regrid_targets_generic(h, rs, src, o0, o1, o2, tr, tk, w);
     // ONE returning atomic per wave reserves the four entries of every active lane (one per deposit would be tens of millions of atomics on
     // a single address where the field moves far: they serialise at ~5 ns each)
     const unsigned long long act = __ballot(1);
@@ -522,7 +586,7 @@ constexpr int kK2Occ = 4;         // waves per SIMD the regrid kernels are compi
 template <typename ACC, typename real, int PASS, bool SPLIT = false>
 __global__ void __launch_bounds__(256, kK2Occ)
 tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const ACC *__restrict__ offsets, const ACC *__restrict__ offsets_lo,
-                    double *__restrict__ map_out, FarList far, ReachArgs reach, double *__restrict__ tile_sums, int tile_off, int ntiles,
+                    double *__restrict__ map_out, FarList far, FarSrc fsrc, ReachArgs reach, double *__restrict__ tile_sums, int tile_off, int ntiles,
                     int *__restrict__ todo, double *__restrict__ sums_out, int *__restrict__ lean_reset = nullptr)
 {
     // map_in, offsets and map_out are indexed by GLOBAL pixel number.  tile_off < 0: all tiles, heavy ones first; tile_off >= 0
@@ -544,6 +608,7 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
         // tiles are done); sums_out[0] = sum of the source values, [1] = sum of the deposits
         double sa = 0.0, sb = 0.0;
         for (int i = tid; i < ntiles; i += 256) { sa += tile_sums[2 * (int64_t)i]; sb += tile_sums[2 * (int64_t)i + 1]; }
+        for (int i = tid; i < kFarEvalWgs; i += 256) sb += fsrc.sums[i];                    // the deposits regrid_far_eval_kernel listed
 #pragma unroll
         for (int sft = kWave >> 1; sft > 0; sft >>= 1) { sa += __shfl_down(sa, sft, kWave); sb += __shfl_down(sb, sft, kWave); }
         double *red = reinterpret_cast<double *>(smem);
@@ -610,6 +675,8 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
     for (int i = tid; i < T.BR * T.W; i += 256) acc[i] = 0.0;
     const int NT = T.BR + 2 * R + 2;                           // rings rth0 .. rth0 + NT - 1 in the ring tables
     const int rth0 = i0 - R - 1;
+    const int NR = T.BR + 2 * R;                               // source rings: the tile's rings +- R (rows 1 .. NR of the tables)
+    int my_span = 0, my_nrmin = 0x7fffffff, my_nrmax = 1;      // of the row this thread builds
     if (tid < NT) {
         // one record of the plan's ring table (everything that depends on NSIDE alone, the spacings to the neighbouring rings included: no
         // second phase over the neighbours' theta); per tile only the column span, the azimuth of its first pixel and the thresholds
@@ -628,6 +695,10 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             rw.lim2 = (lim > 0.0 && ring > 1 && ring < nl4 - 1) ? (double)(float)(lim * lim) : 0.0;      // (a float: the walking kernel's scan compares in fp32)
         }
         rows[tid] = rw;
+        if (tid >= 1 && tid <= NR) {
+            my_span = rw.ke - rw.ks;
+            if (PASS == 2 && rw.nr > 0) { my_nrmin = rw.nr; my_nrmax = rw.nr; }
+        }
         RegRowC<real> rc;
         if constexpr (sizeof(real) == 4) {
             rc.z = (real)rw.z; rc.sth = (real)rw.sth; rc.dphi = (real)rw.dphi; rc.inv_dphi = (real)rw.inv_dphi;
@@ -660,26 +731,29 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
             scan[tid] = rs;
         }
     }
-    if (PASS == 2 && tid == 0) reinterpret_cast<int32_t *>(reinterpret_cast<RowScan *>(rowc + NTmax) + NTmax)[0] = 0;       // far pixels listed by this tile
-    __syncthreads();
-    auto far_add = [&](int64_t p, double v) {
-        if (PASS != 1) {
-            const unsigned long long i = atomicAdd(far.count, 1ull);
-            if ((int64_t)i < far.cap) { far.pix[i] = p; far.val[i] = v; } else atomicOr(far.overflow, 1);
-            sum_out += v;
-        } else {
-            atomicAdd(map_out + p, v);
+    // widest span and shortest / longest ring of the source rows: reduced in the (at most two) waves that built them, one triple per wave
+    int32_t *tred = reinterpret_cast<int32_t *>(smem + regrid3_lds_bytes(T.BR, T.W, sizeof(real), PASS == 2, SPLIT ? sizeof(ACC) : sizeof(real)) - 32);
+    if (tid < 2 * kWave) {
+#pragma unroll
+        for (int sft = kWave >> 1; sft > 0; sft >>= 1) {
+            my_span = max(my_span, __shfl_xor(my_span, sft, kWave));
+            my_nrmin = min(my_nrmin, __shfl_xor(my_nrmin, sft, kWave));
+            my_nrmax = max(my_nrmax, __shfl_xor(my_nrmax, sft, kWave));
         }
+        if ((tid & (kWave - 1)) == 0) { int32_t *t3 = tred + 3 * (tid / kWave); t3[0] = my_span; t3[1] = my_nrmin; t3[2] = my_nrmax; }
+    }
+    __syncthreads();
+    // an own pixel that takes the generic route (active lanes: those that hold one) goes onto the source list.  The deposits of an entry that
+    // does not fit are made by the repair pass; their total is the pixel's value (the four weights add up to one)
+    auto far_list = [&](int ring, int k, int64_t p) {
+        if (!far_src_append(fsrc, ring, k)) { atomicOr(far.overflow, 1); sum_out += map_in[p]; }
     };
 
     // source pixels: the tile's rings +- R, its columns +- K (a tile that spans whole rings has no column apron)
     // (in a short ring the apron is what is left of the ring, split between the two sides, so that no pixel is visited twice)
-    const int NR = T.BR + 2 * R;
-    int maxspan = 0, nrmin = 0x7fffffff, nrmax = 1;
-    for (int i = 1; i <= NR; ++i) {
-        maxspan = max(maxspan, rows[i].ke - rows[i].ks);
-        if (PASS == 2 && rows[i].nr > 0) { nrmin = min(nrmin, rows[i].nr); nrmax = max(nrmax, rows[i].nr); }
-    }
+    // (widest span, shortest / longest ring of the source rows: six LDS reads here; as a loop of every thread over the rows, ~190 reads per
+    // thread and tile, it was 14 us of the headline's walking launch)
+    const int maxspan = max(tred[0], tred[3]), nrmin = min(tred[1], tred[4]), nrmax = max(tred[2], tred[5]);
     const int LWs = maxspan + 2 * kap;
     const unsigned inv_lws = (unsigned)((0x100000000ull + (unsigned)LWs - 1u) / (unsigned)LWs);      // idx / LWs for idx < 2^16
     using OT = typename std::conditional<SPLIT, double, ACC>::type;      // a source pixel's offset as the lean / repair passes hold it
@@ -755,17 +829,14 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
                 }
             }
         };
-        // a listed position (ring of the tables << 16 | column + kap) of one of the tile's own pixels -> its deposits on the far list
+        // a queued position (ring of the tables << 16 | column + kap) of one of the tile's own pixels -> the source list
         auto far_from = [&](int pk) {
             const int ti = pk >> 16, x = (pk & 0xffff) - kap;
             const RegRow &rw = rows[ti];
             int k = rw.ks + x;
             if (k < 0) k += rw.nr;
             if (k >= rw.nr) k -= rw.nr;
-            const int64_t p = rw.start + k;
-            double f0 = (double)offsets[3 * p + 0], f1 = (double)offsets[3 * p + 1], f2 = (double)offsets[3 * p + 2];
-            if (SPLIT) { f0 += (double)offsets_lo[3 * p + 0]; f1 += (double)offsets_lo[3 * p + 1]; f2 += (double)offsets_lo[3 * p + 2]; }
-            sum_out += regrid_far_pixel(h, T.rings, rows, NT - 2, rth0, ti, x, f0, f1, f2, map_in[p], far);
+            far_list(rth0 + ti, k, rw.start + k);
         };
         int32_t *fq = farq + wid * kWalkQ;
         int fn = 0;                                                            // entries in this wave's queue of generic-route pixels
@@ -870,11 +941,17 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
                     }
                 }
             }
-        } else if (cur.own) {                                                // rare: the owner of the source pixel lists its deposits
-            int tr[4], tk[4];
-            double w[4];
-            regrid_targets_generic(h, T.rings, rows, NT - 2, rth0, cur.ti, cur.x, (double)cur.o0, (double)cur.o1, (double)cur.o2, tr, tk, w);
-            for (int q4 = 0; q4 < 4; ++q4) far_add(T.rings[tr[q4]].start + tk[q4], w[q4] * val);
+        } else if (cur.own) {                                                // rare: the owner of the source pixel lists it ...
+            if constexpr (PASS == 0) {
+                const RegRow &rw = rows[cur.ti];
+                far_list(rth0 + cur.ti, rw.ks + cur.x, rw.start + rw.ks + cur.x);
+            } else {                                                         // ... or, repairing an overflow, adds its deposits to the stored map
+                int tr[4], tk[4];
+                double w[4];
+                const GenRows rs{rows, T.rings, rth0, NT - 2};
+                regrid_targets_generic(h, rs, rs.source(cur.ti, cur.x), (double)cur.o0, (double)cur.o1, (double)cur.o2, tr, tk, w);
+                for (int q4 = 0; q4 < 4; ++q4) atomicAdd(map_out + (T.rings[tr[q4]].start + tk[q4]), w[q4] * val);
+            }
         }
     };
     // two window pixels per lane and trip: the four loads are in flight before either pixel is evaluated
@@ -915,16 +992,60 @@ tile_regrid3_kernel(Hpx h, Tiling T, const double *__restrict__ map_in, const AC
     }
 }
 
+// The pass of the generic route: the source pixels the gather kernels listed, one per lane on full waves, evaluated from the plan's ring table
+// (no tile tables) and their four deposits appended to the far list.  Grid-stride over the list's device-side count with kFarEvalWgs workgroups;
+// every workgroup leaves the total of its deposits in fsrc.sums (zero included: the final summation reads all of them on every call).
+// offsets / map_in are indexed by GLOBAL pixel number, as in the gather kernels.
+template <typename ACC, bool SPLIT>
+__global__ void __launch_bounds__(256)
+regrid_far_eval_kernel(Hpx h, const RingRec *__restrict__ rings, const double *__restrict__ map_in, const ACC *__restrict__ offsets,
+                       const ACC *__restrict__ offsets_lo, FarSrc fsrc, FarList far)
+{
+    __shared__ double red[256 / kWave];
+    const int tid = threadIdx.x;
+    const unsigned listed = *fsrc.count;
+    if (listed == 0u) {
+        if (tid == 0) fsrc.sums[blockIdx.x] = 0.0;
+        return;
+    }
+    const unsigned n = (int64_t)listed < fsrc.cap ? listed : (unsigned)fsrc.cap;
+    // the sources that did not fit would have made four deposits each: the deposit count says so, as it does for deposits that do not fit
+    if (listed > n && blockIdx.x == 0 && tid == 0) atomicAdd(far.count, 4ull * (unsigned long long)(listed - n));
+    const int nl4 = (int)(4 * h.nside);
+    double tot = 0.0;
+    for (unsigned i = blockIdx.x * 256u + (unsigned)tid; i < n; i += (unsigned)kFarEvalWgs * 256u) {
+        const int2 e = fsrc.ent[i];
+        const RingRec &g = rings[e.x];
+        const int64_t p = g.start + e.y;
+        double o0 = (double)offsets[3 * p + 0], o1 = (double)offsets[3 * p + 1], o2 = (double)offsets[3 * p + 2];
+        if (SPLIT) { o0 += (double)offsets_lo[3 * p + 0]; o1 += (double)offsets_lo[3 * p + 1]; o2 += (double)offsets_lo[3 * p + 2]; }
+        const GenTable rs{rings, max(e.x - kGenWalk, 0), min(e.x + kGenWalk, nl4)};
+        const GenSrc src{g.theta, g.z, g.sth, g.dphi, e.x, e.y, g.shifted != 0};
+        tot += regrid_far_pixel(h, rings, rs, src, o0, o1, o2, map_in[p], far);
+    }
+#pragma unroll
+    for (int sft = kWave >> 1; sft > 0; sft >>= 1) tot += __shfl_down(tot, sft, kWave);
+    if ((tid & (kWave - 1)) == 0) red[tid / kWave] = tot;
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int w = 0; w < 256 / kWave; ++w) t += red[w];
+        fsrc.sums[blockIdx.x] = t;
+    }
+}
+
 // banded regrid: adds the listed deposits whose pixel lies in [p0, p1) to the slice that starts at pixel p0, counts the others
-// (tile_sums != NULL: the last workgroup also adds up the per-tile sums of the banded regrid into sums[2] -- one launch less per step)
+// (tile_sums != NULL: the last workgroup also adds up the per-tile sums of the banded regrid, and far_sums, into sums[2] -- one launch less per step)
 __global__ void __launch_bounds__(256)
 regrid_far_local_kernel(FarList far, double *__restrict__ out_slice, int64_t p0, int64_t p1, unsigned long long *__restrict__ foreign,
-                        int ntiles = 0, const double *__restrict__ tile_sums = nullptr, double *__restrict__ sums = nullptr)
+                        int ntiles = 0, const double *__restrict__ tile_sums = nullptr, double *__restrict__ sums = nullptr,
+                        const double *__restrict__ far_sums = nullptr)
 {
     if (tile_sums != nullptr && blockIdx.x == gridDim.x - 1) {
         __shared__ double sa[256 / kWave], sb[256 / kWave];
         double xa = 0.0, xb = 0.0;
         for (int t = threadIdx.x; t < ntiles; t += 256) { xa += tile_sums[2 * t]; xb += tile_sums[2 * t + 1]; }
+        if (far_sums != nullptr) for (int t = threadIdx.x; t < kFarEvalWgs; t += 256) xb += far_sums[t];       // (regrid_far_eval_kernel's deposits)
 #pragma unroll
         for (int sft = kWave >> 1; sft > 0; sft >>= 1) { xa += __shfl_down(xa, sft, kWave); xb += __shfl_down(xb, sft, kWave); }
         const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;

@@ -39,11 +39,13 @@ int bfgx_plan_set_band_reach(bfgx_plan *p, int32_t rings)
 }
 
 // reset_far = false: the far-deposit list keeps what earlier calls have listed (the one-shot host entry regrids the sphere in several
-// band ranges while the map is still arriving, and applies one list at the end)
+// band ranges while the map is still arriving, and applies one list at the end).  The list of far SOURCE pixels is consumed by every call
+// (regrid_far_eval_kernel turns it into deposits before the call's last launch) and starts every call empty; src_zeroed: the caller's
+// memset has seen to that
 // m SPLIT (the fused band entry, the one-shot host entry): the low halves of the pixels [olo, ohi) follow their high halves
 static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const double *map_in_dev, const void *offsets_dev,
                              int64_t olo, int64_t ohi, const DispMode &m, double *out_slice_dev, double *sums_dev, bool reset_far,
-                             bool sums_later = false)
+                             bool sums_later = false, bool src_zeroed = false)
 {
     if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "banded regrid needs the tiled algorithm (algo 1)");
     int64_t need_lo = 0, need_hi = 0;
@@ -51,7 +53,7 @@ static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const d
     if (band0 == band1) {
         // a rank that owns no band (more ranks than bands): empty buffers, whose data pointers are NULL, are fine
         HIP_TRY(hipSetDevice(p->device));
-        if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, sizeof(unsigned long long), p->stream));
+        if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, kFarCountersBytes, p->stream));
         if (sums_dev) HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
         return BFGX_OK;
     }
@@ -60,7 +62,8 @@ static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const d
         return fail(BFGX_ERR_INVALID, "pix_offsets range [%lld, %lld) does not cover the bands and %d ring(s) either side [%lld, %lld)",
                     (long long)olo, (long long)ohi, p->band_reach, (long long)need_lo, (long long)need_hi);
     HIP_TRY(hipSetDevice(p->device));
-    if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, sizeof(unsigned long long), p->stream));
+    if (reset_far) HIP_TRY(hipMemsetAsync(p->far.count, 0, kFarCountersBytes, p->stream));           // both lists
+    else if (!src_zeroed) HIP_TRY(hipMemsetAsync(p->far_src.count, 0, sizeof(uint32_t), p->stream));
     const BandRange r = band_range(p, band0, band1);
     {
         KernelTimer kt(p, BFGX_K_REGRID);
@@ -79,9 +82,10 @@ static int regrid_bands_impl(bfgx_plan *p, int32_t band0, int32_t band1, const d
         do {                                                                                                                                    \
             const ACC *o = (const ACC *)offsets_dev - 3 * olo;                                                                                  \
             if (p->band_reach == 1) hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 0, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
-                                                       out_base, p->far, reach, ts, r.t0, r.nt, none, (double *)nullptr);                       \
+                                                       out_base, p->far, p->far_src, reach, ts, r.t0, r.nt, none, (double *)nullptr);           \
             else hipLaunchKernelGGL((tile_regrid3_kernel<ACC, REAL, 2, SPLIT>), grid, blk, lds, p->stream, p->hpx, p->tiling, map_in_dev, o, OL, \
-                                    out_base, p->far, reach, ts, r.t0, r.nt, none, (double *)nullptr);                                          \
+                                    out_base, p->far, p->far_src, reach, ts, r.t0, r.nt, none, (double *)nullptr);                              \
+            hipLaunchKernelGGL((regrid_far_eval_kernel<ACC, SPLIT>), dim3(kFarEvalWgs), blk, 0, p->stream, p->hpx, p->tiling.rings, map_in_dev, o, OL, p->far_src, p->far); \
         } while (0)
         if (m.split()) BFGX_REGRID3(float, double, true, m.lo(offsets_dev, ohi - olo) - 3 * olo);
         else if (m.fp64()) BFGX_REGRID3(double, double, false, (const double *)nullptr);
@@ -144,7 +148,7 @@ int bfgx_paint_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t band0
 // drive all workers): K0 + binning + K1 for the bands [B0, B1) (the rank's own and, with a route margin, the band either side: the aprons of
 // its regrid) into offsets_dev (pixels from the first of band B0), the banded regrid of ITS bands [b0, b1) into out_slice_dev, the listed far
 // deposits that fall into its pixels added, the others counted into *foreign_dev, the two sums of the mass check.  One memset (the binning's)
-// zeroes every control word; eight launches.
+// zeroes every control word; nine launches.
 int bfgx_offsets_regrid_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int32_t B0, int32_t B1, void *offsets_dev, int acc_f64,
                                      int32_t b0, int32_t b1, const double *map_in_dev, double *out_slice_dev, double *sums_dev,
                                      unsigned long long *foreign_dev)
@@ -161,9 +165,9 @@ int bfgx_offsets_regrid_bands_device(bfgx_plan *p, const bfgx_catalog *cat, int3
         if (sums_dev) HIP_TRY(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), p->stream));
         return BFGX_OK;
     }
-    if (int rc = regrid_bands_impl(p, b0, b1, map_in_dev, offsets_dev, w.p0, w.p1, m, out_slice_dev, sums_dev, false, true)) return rc;
+    if (int rc = regrid_bands_impl(p, b0, b1, map_in_dev, offsets_dev, w.p0, w.p1, m, out_slice_dev, sums_dev, false, true, B0 < B1)) return rc;
     hipLaunchKernelGGL(regrid_far_local_kernel, dim3(64), dim3(256), 0, p->stream, p->far, out_slice_dev, r.p0, r.p1, foreign_dev, r.nt,
-                       sums_dev ? (const double *)(p->tile_sums + 2 * (size_t)r.t0) : (const double *)nullptr, sums_dev);
+                       sums_dev ? (const double *)(p->tile_sums + 2 * (size_t)r.t0) : (const double *)nullptr, sums_dev, (const double *)p->far_src.sums);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
 }
@@ -213,7 +217,7 @@ int bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_overf
     if (!p) return fail(BFGX_ERR_INVALID, "NULL plan");
     if (p->algo != 1) return fail(BFGX_ERR_UNSUPPORTED, "regrid statistics exist for the tiled algorithm (algo 1) only");
     HIP_TRY(hipSetDevice(p->device));
-    RegridCtrl ctrl = {0, 0, 0};
+    RegridCtrl ctrl = {};
     HIP_TRY(hipMemcpyAsync(&ctrl, p->arena.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, p->stream));
     std::vector<int32_t> apron;
     if (max_reach_rings) {

@@ -9,7 +9,8 @@
 //   tile_counter  1              the counter the persistent K1 / K3 grids draw their tiles from
 //   omax          ntiles + 1     largest |offset|^2 of every tile (K1's flush or tile_reach_kernel): the reach of the gathering regrid
 //   (rounded up to 4 words)
-//   ctrl          4              RegridCtrl: entries of the far list, overflow of the full-map regrid, tiles left to the walking kernel
+//   ctrl          8              RegridCtrl: entries of the far list and of its source list, overflow of the full-map regrid, tiles left to
+//                                the walking kernel
 //   ---- the step's one memset zeroes [base, here): a single buffer and a multiple of 16 bytes (two buffers, or another length, cost a
 //        4.5 us fill kernel each) ----
 //   todo_list     ntiles         the tiles left to the walking kernel: RegridCtrl.todo_count is the word in front of them, so that
@@ -29,12 +30,16 @@ namespace bfgx {
 // the regrid's control words, reset together (regrid_impl) and read back together (bfgx_plan_regrid_stats)
 struct RegridCtrl {
     unsigned long long far_count;    // FarList.count: entries appended (may exceed the capacity)
-    int32_t far_overflow_full;       // full-map regrid: overflow of the list is repaired in-stream (pass 1), not an error
+    uint32_t far_src_count;          // FarSrc.count: source pixels listed for the generic route (may exceed the capacity); follows far_count: one memset resets both
+    int32_t spare[3];                // (the step's memset stays a multiple of 16 bytes)
+    int32_t far_overflow_full;       // full-map regrid: overflow of either list is repaired in-stream (pass 1), not an error
     int32_t todo_count;              // tiles the lean gather kernel leaves to the one with the ring walk (followed by their numbers)
 };
-static_assert(sizeof(RegridCtrl) == 16 && alignof(RegridCtrl) == 8, "RegridCtrl is four words, the first two a 64-bit counter");
+static_assert(sizeof(RegridCtrl) == 32 && alignof(RegridCtrl) == 8, "RegridCtrl is eight words, the first two a 64-bit counter");
+static_assert(offsetof(RegridCtrl, far_src_count) == 8 && offsetof(RegridCtrl, todo_count) == 28, "the two list counters are adjacent; the todo count is the last word");
 
-constexpr size_t kCtrlWords = sizeof(RegridCtrl) / sizeof(int32_t);
+constexpr size_t kFarCountersBytes = offsetof(RegridCtrl, far_src_count) + sizeof(uint32_t);      // what a banded regrid that starts both lists afresh zeroes
+constexpr size_t kCtrlWords =sizeof(RegridCtrl) / sizeof(int32_t);
 constexpr size_t round_up4(size_t words) { return (words + 3) & ~(size_t)3; }
 
 // word offsets of the regions from the base, and the lengths the host needs
@@ -125,18 +130,18 @@ struct TileArenaCheck {
                   "cnt_b and cur_b: ntiles + 1 words each, and nothing else lies in the cursors' span");
     static_assert(L.omax == L.tile_counter + 1, "the |offset|^2 block follows the tile counter");
     static_assert(L.ctrl >= L.omax + blk && L.ctrl - (L.omax + blk) < 4, "the control words follow the three blocks and the tile counter, rounded up to four words");
-    static_assert(L.far_overflow_full == L.ctrl + 2 && L.todo == L.ctrl + 3 && L.todo_list == L.todo + 1, "count (64 bits), overflow, todo count, todo tiles");
+    static_assert(L.far_overflow_full == L.ctrl + 6 && L.todo == L.ctrl + 7 && L.todo_list == L.todo + 1, "count (64 bits), source count, three spare, overflow, todo count, todo tiles");
     static_assert(L.band_overflow == L.todo_list + NT && L.total_words > L.band_overflow, "the banded overflow flag follows the todo tiles, inside the allocation");
     // the step's memset
     static_assert(L.zeroed_words == L.ctrl + kCtrlWords, "the zeroed span starts at the base and ends exactly after RegridCtrl");
     static_assert(L.zeroed_words % 4 == 0, "the zeroed span is a multiple of 16 bytes");
     static_assert(L.todo_list >= L.zeroed_words && L.band_overflow >= L.zeroed_words, "the step's memset touches neither the todo tiles nor the banded overflow flag");
     static_assert(L.ctrl % 2 == 0, "RegridCtrl's 64-bit counter is 8-byte aligned (the base is a device allocation)");
-    static_assert(L.tail_words == L.total_words - L.ctrl && L.tail_words == NT + 8, "plan creation zeroes the control words and all behind them");
+    static_assert(L.tail_words == L.total_words - L.ctrl && L.tail_words == NT + 12, "plan creation zeroes the control words and all behind them");
     // packed: the padded region holds exactly ntiles * cnt_pad words wherever that is a multiple of four, and the lengths follow from it
     static_assert(L.cnt_b == round_up4(NT * PAD) && (!unrounded || L.cnt_b == NT * PAD), "only a padded region that is no multiple of four words is rounded up");
     static_assert(L.tile_counter == L.cnt_b + 2 * blk && L.omax == L.cnt_b + 2 * blk + 1 && L.ctrl == L.cnt_b + n3p, "the three blocks, the tile counter between the second and the third");
-    static_assert(L.zeroed_words == L.cnt_b + n3p + 4 && L.total_words == L.cnt_b + n3p + NT + 8, "lengths of the memset and of the allocation");
+    static_assert(L.zeroed_words == L.cnt_b + n3p + 8 && L.total_words == L.cnt_b + n3p + NT + 12, "lengths of the memset and of the allocation");
     static constexpr bool ok = true;
 };
 // one scan block (NSIDE 1, 2, 8, 16), the benchmark's NSIDE 1024, NSIDE 4096 and 8192 with their narrower padding, and two tilings
