@@ -254,6 +254,21 @@ SYMBOLS = {
                                                       C.c_void_p]),
     'bfgx_particle_power_spectrum': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_fft2_work_doubles': (C.c_int64, [C.c_int32]),
+    'bfgx_rfft2_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_irfft2_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    'bfgx_power_spectrum_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_filter_map_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'bfgx_kappa_to_shear_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_shear_to_kappa_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_power_spectrum_2d': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_filter_map_2d': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p]),
+    'bfgx_kappa_to_shear_2d': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bfgx_shear_to_kappa_2d': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_grid_plan_timing_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'bfgx_grid_plan_timing_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_deposit_particles_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

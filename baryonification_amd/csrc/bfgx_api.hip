@@ -36,6 +36,7 @@
 #include "bfgx_grid_pairs.hpp"
 #include "bfgx_fft.hpp"
 #include "bfgx_bispec.hpp"
+#include "bfgx_fft2d.hpp"
 #include "bfgx_deposit.hpp"
 #include "bfgx_deposit_cloud.hpp"
 #include "bfgx_snapshot.hpp"
@@ -1718,6 +1719,9 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 // interlaced power spectrum of two grids half a cell apart, P(k) straight from particle columns
 #include "bfgx_interlace_api.inc"
 
+// 2-D FFTs of gridded flat-sky maps: transform pair, power spectra, filters, Kaiser-Squires
+#include "bfgx_fft2d_api.inc"
+
 // ------------------------------------------------------------------------------ particle snapshots (8f-2)
 #include "bfgx_snapshot_api.inc"
 
@@ -1762,6 +1766,7 @@ extern "C" void bfgx_cache_clear(void)
     bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
     xpk_release_all();           // window tables of the cross power spectrum (bfgx_xpk_api.inc)
     interlace_release_all();     // half-cell phase tables of the interlaced power spectrum (bfgx_interlace_api.inc)
+    fft2_release_all();          // twiddle tables of the 2-D transforms (bfgx_fft2d_api.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries
     g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
     deprec_release_all();        // device buffers of the deposit's records entry

@@ -516,6 +516,59 @@ def cross_power_spectrum(MapA, MapB, Lbox, Nk=180, window=0, device=0):
     return {'k': k, 'paa': paa, 'pbb': pbb, 'pab': pab, 'r': r, 'counts': cnt}
 
 
+def fft2_work_doubles(n):
+    """doubles of scratch the 2-D entries below need (three half spectra [n][fft_pitch(n)]); 0 for an unsupported n"""
+    return int(_lib.load().bfgx_fft2_work_doubles(int(n)))
+
+
+def rfft2_device(map_ptr, n, work_ptr, spec_out_ptr, device=0, stream=0):
+    """map [n][n] -> its half spectrum [n][fft_pitch(n)] complex, unnormalised (enqueue-only, like all 2-D entries here)"""
+    _lib.check(_lib.load().bfgx_rfft2_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(map_ptr)),
+                                            C.c_void_p(int(work_ptr)), C.c_void_p(int(spec_out_ptr))))
+
+
+def irfft2_device(spec_ptr, n, scale, work_ptr, map_out_ptr, device=0, stream=0):
+    """half spectrum [n][fft_pitch(n)] (kept) -> map [n][n], times `scale` (1 / n^2 inverts rfft2_device)"""
+    _lib.check(_lib.load().bfgx_irfft2_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(spec_ptr)), float(scale),
+                                             C.c_void_p(int(work_ptr)), C.c_void_p(int(map_out_ptr))))
+
+
+def power_spectrum_2d_device(map_a_ptr, map_b_ptr, n, L, nk, window_order, work_ptr, paa_sum_ptr, pbb_sum_ptr, pab_sum_ptr, k_sum_ptr,
+                             counts_ptr, device=0, stream=0):
+    """cross_power_spectrum_device for two square 2-D maps (which may be the same): the five sums per linear k-bin"""
+    _lib.check(_lib.load().bfgx_power_spectrum_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(map_a_ptr)),
+                                                        C.c_void_p(int(map_b_ptr)), float(L), int(nk), int(window_order),
+                                                        C.c_void_p(int(work_ptr)), C.c_void_p(int(paa_sum_ptr)), C.c_void_p(int(pbb_sum_ptr)),
+                                                        C.c_void_p(int(pab_sum_ptr)), C.c_void_p(int(k_sum_ptr)), C.c_void_p(int(counts_ptr))))
+
+
+FILTER_KINDS_2D = {'gauss': 0, 'tophat': 1, 'table': 2}
+
+
+def filter_map_2d_device(map_ptr, n, L, kind, param, table_k, table_b, work_ptr, map_out_ptr, device=0, stream=0):
+    """map_out = irfft2(rfft2(map) b(k)); kind as in FILTER_KINDS_2D, param = sigma or R, (table_k, table_b) host arrays for 'table'"""
+    kind = FILTER_KINDS_2D[kind] if isinstance(kind, str) else int(kind)
+    tk = None if table_k is None else np.ascontiguousarray(table_k, dtype=np.float64)
+    tb = None if table_b is None else np.ascontiguousarray(table_b, dtype=np.float64)
+    _lib.check(_lib.load().bfgx_filter_map_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(map_ptr)), float(L),
+                                                    kind, float(param), None if tk is None else tk.ctypes.data,
+                                                    None if tb is None else tb.ctypes.data, 0 if tk is None else int(tk.size),
+                                                    C.c_void_p(int(work_ptr)), C.c_void_p(int(map_out_ptr))))
+
+
+def kappa_to_shear_2d_device(kappa_ptr, n, work_ptr, g1_out_ptr, g2_out_ptr, device=0, stream=0):
+    """Kaiser-Squires, convergence [n][n] -> shear (g1, g2)"""
+    _lib.check(_lib.load().bfgx_kappa_to_shear_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(kappa_ptr)),
+                                                        C.c_void_p(int(work_ptr)), C.c_void_p(int(g1_out_ptr)), C.c_void_p(int(g2_out_ptr))))
+
+
+def shear_to_kappa_2d_device(g1_ptr, g2_ptr, n, work_ptr, kappa_e_out_ptr, kappa_b_out_ptr, device=0, stream=0):
+    """Kaiser-Squires, shear (g1, g2) -> convergence E and B modes"""
+    _lib.check(_lib.load().bfgx_shear_to_kappa_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(g1_ptr)),
+                                                        C.c_void_p(int(g2_ptr)), C.c_void_p(int(work_ptr)), C.c_void_p(int(kappa_e_out_ptr)),
+                                                        C.c_void_p(int(kappa_b_out_ptr))))
+
+
 def _window_order(window, what):
     """0 .. 3 of a window given as that number or as a name of WINDOW_ORDERS (ValueError otherwise)"""
     if isinstance(window, str):

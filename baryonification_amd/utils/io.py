@@ -178,6 +178,19 @@ class GriddedMap(object):
     def cosmology(self):
         return self.cosmo
 
+    def power_spectrum(self, Nk=180, window='none', normalize=False):
+        """P(k) of the map over its side L = Npix * res as a dict of numpy arrays k, pk, counts (empty bins NaN): a 2-D map through
+        utils.power_spectrum_2d (normalize=True: times L^2 / N^4), a 3-D map through engine.cross_power_spectrum(map, map, ...)
+        (normalize=True: times L^3 / N^6); `window` divides a mass-assignment window out."""
+        L = float(self.Npix * self.res)
+        if self.is2D:
+            from .flatsky import power_spectrum_2d
+            return power_spectrum_2d(self.map, L, Nk, window, normalize)
+        from .. import engine
+        x = engine.cross_power_spectrum(self.map, self.map, L, Nk, window)
+        pk = x['paa'] * (L ** 3 / float(self.Npix) ** 6) if normalize else x['paa']
+        return {'k': x['k'], 'pk': pk, 'counts': x['counts']}
+
     def __str__(self):
         return (f"GriddedMap of {'2D' if self.is2D else '3D'} shape {self.map.shape}, res = {self.res}, z = {self.redshift}.\n"
                 f"Cosmology set to {self.cosmo}.")

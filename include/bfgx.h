@@ -632,6 +632,47 @@ int  bfgx_particle_power_spectrum(int device, int64_t n, const double *x, const 
                                   double L, int32_t order, int32_t interlace, int32_t nk, double *pk, double *pk_grid1, double *kcen,
                                   int64_t *counts);
 
+/* ---- flat-sky maps: 2-D FFTs, power spectra, filters, Kaiser-Squires ------------------------------------------
+ * A real map [n][n] (C order, axis 0 = x, axis 1 = y) and its half spectrum [n][pitch] of complex values, pitch = bfgx_fft_pitch(n), the
+ * coefficients c <= n/2 of axis 1: one plane of the layout above.  Transforms are unnormalised with exponent -i forward; n a power of two
+ * in [8, 4096] (else BFGX_ERR_UNSUPPORTED).  Every _device entry takes work_dev, bfgx_fft2_work_doubles(n) doubles of scratch (three half
+ * spectra), 16-byte aligned like every complex array, and only enqueues once the twiddles of (device, n) exist; they are kept until
+ * bfgx_cache_clear.  Pad columns c > n/2 are never read; what the entries store there is undefined.  The transforms use no atomics and
+ * repeat bitwise. */
+/* doubles of scratch of the entries below (host arithmetic; 0 for an unsupported n) */
+int64_t bfgx_fft2_work_doubles(int32_t n);
+/* map_dev [n][n] -> spec_out_dev [n][pitch] */
+int  bfgx_rfft2_device(int device, void *hip_stream, int32_t n, const double *map_dev, double *work_dev, double *spec_out_dev);
+/* spec_dev [n][pitch] (kept) -> map_out_dev [n][n] = scale * sum_k spec e^{+ikx}; the spectrum of a real field: the imaginary parts that
+ * break Hermitian symmetry in the columns 0 and n/2 are ignored, as numpy.irfft ignores them */
+int  bfgx_irfft2_device(int device, void *hip_stream, int32_t n, const double *spec_dev, double scale, double *work_dev, double *map_out_dev);
+/* Auto and cross spectra of two maps (which may be the same) in the bins, units and window weights of bfgx_cross_power_spectrum with the
+ * third wave number at 0: k = sqrt(klin[a]^2 + klin[c]^2), nk linear bins from 2 pi / L to pi n / L, bin = floor((k - k0) / dk), w =
+ * win[a] win[c]; the five sums [nk] as there (floating-point atomics; counts exact).  1 <= nk <= 2048, L > 0, window_order 0 .. 3. */
+int  bfgx_power_spectrum_2d_device(int device, void *hip_stream, int32_t n, const double *map_a_dev, const double *map_b_dev, double L, int32_t nk,
+                                   int32_t window_order, double *work_dev, double *paa_sum_dev, double *pbb_sum_dev, double *pab_sum_dev,
+                                   double *k_sum_dev, unsigned long long *counts_dev);
+/* map_out = irfft2(rfft2(map) b(k)) / n^2, k = 2 pi / L sqrt(n0^2 + n1^2) (fftfreq's wave numbers).  kind 0: Gaussian, b = exp(-k^2
+ * param^2 / 2); 1: top hat of radius param, b = 2 J1(k param) / (k param), 1 at 0; 2: the table (table_k, table_b)[ntable] (HOST arrays;
+ * k finite and strictly ascending, at most min(65536, n pitch) nodes), interpolated linearly and held at its end values (np.interp).
+ * param >= 0.  map_out_dev may be map_dev. */
+int  bfgx_filter_map_2d_device(int device, void *hip_stream, int32_t n, const double *map_dev, double L, int32_t kind, double param,
+                               const double *table_k_host, const double *table_b_host, int32_t ntable, double *work_dev, double *map_out_dev);
+/* Kaiser-Squires.  With fftfreq's integer wave numbers n0 (axis 0) and n1 = c (axis 1): c2 = (n0^2 - n1^2) / (n0^2 + n1^2), s2 = 2 n0 n1 /
+ * (n0^2 + n1^2), both 0 at the zero mode, s2 = 0 where either index is the Nyquist index.  g1^ = c2 kappa^, g2^ = s2 kappa^; back:
+ * kappa_E^ = c2 g1^ + s2 g2^, kappa_B^ = -s2 g1^ + c2 g2^.  Outputs may be the inputs. */
+int  bfgx_kappa_to_shear_2d_device(int device, void *hip_stream, int32_t n, const double *kappa_dev, double *work_dev, double *g1_out_dev,
+                                   double *g2_out_dev);
+int  bfgx_shear_to_kappa_2d_device(int device, void *hip_stream, int32_t n, const double *g1_dev, const double *g2_dev, double *work_dev,
+                                   double *kappa_e_out_dev, double *kappa_b_out_dev);
+/* the same on host arrays (synchronous); the spectra divided by counts, kcen = mean |k| per bin, NaN for empty bins */
+int  bfgx_power_spectrum_2d(int device, int32_t n, const double *map_a_host, const double *map_b_host, double L, int32_t nk, int32_t window_order,
+                            double *paa, double *pbb, double *pab, double *kcen, int64_t *counts);
+int  bfgx_filter_map_2d(int device, int32_t n, const double *map_host, double L, int32_t kind, double param, const double *table_k,
+                        const double *table_b, int32_t ntable, double *map_out);
+int  bfgx_kappa_to_shear_2d(int device, int32_t n, const double *kappa_host, double *g1, double *g2);
+int  bfgx_shear_to_kappa_2d(int device, int32_t n, const double *g1_host, const double *g2_host, double *kappa_e, double *kappa_b);
+
 /* ---- particle-snapshot path ----------------------------------------------------------
  * Replaces BaryonifySnapshot.process, BaryonForge/Runners/SnapshotRunner.py:173-262: every particle within
  * R_q = clip(epsilon_max R200c / a, 0, L/2) of a halo (periodic box) moves radially by displacement(d, M, a) * a;
