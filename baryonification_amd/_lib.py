@@ -261,6 +261,9 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_filter_map_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'bfgx_derivatives_2d_work_doubles': (C.c_int64, [C.c_int32, C.c_int32]),
+    'bfgx_derivatives_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'bfgx_kappa_to_shear_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_shear_to_kappa_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'bfgx_power_spectrum_2d': (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -320,6 +323,8 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p]),
     'bfgx_mapstats_peaks_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    'bfgx_mapstats_peaks_2d_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     'bfgx_mapstats_minkowski_work_doubles': (C.c_int64, [C.c_int64, C.c_int32]),
     'bfgx_mapstats_minkowski_device': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),

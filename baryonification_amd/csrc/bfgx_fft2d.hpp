@@ -1,5 +1,5 @@
 // bfgx_fft2d.hpp -- 2-D FFTs of gridded flat-sky maps and what is computed per Fourier mode on top of them (power spectra in linear
-// k-bins, isotropic filters, the Kaiser-Squires pair) for gfx950.
+// k-bins, isotropic filters, the Kaiser-Squires pair, the derivatives of a filtered map) for gfx950.
 //
 // Layout: a real map [N][N] (C order, axis 0 = x, axis 1 = y) <-> its half spectrum [N][pitch] of double2, pitch = fft_pitch(N), the
 // coefficients c <= N/2 of axis 1 -- one plane of the 3-D code's layout (bfgx_fft.hpp).  Unnormalised, exponent -i forward.
@@ -135,9 +135,24 @@ __device__ inline double fft2_table_beam(double k, const double *__restrict__ tk
     return slope * (k - tk[lo]) + tb[lo];
 }
 
-// out = conj(F) * b(k) * scale, ready for the inverse passes; k = kval sqrt(n0^2 + n1^2).  kind: Gaussian b = exp(-k^2 param^2 / 2); top
-// hat b = 2 J1(k param) / (k param), 1 at k param = 0; table (tk, tb)[nt]; unit b = 1 (the conjugation alone: bfgx_irfft2_device).  out may
-// be `spec`.  Pad columns are stored as zeros and not read.
+// b(k) of mode (a, c), k = kval sqrt(n0^2 + n1^2) with fftfreq's n0 and n1 = c.  kind: Gaussian b = exp(-k^2 param^2 / 2); top hat
+// b = 2 J1(k param) / (k param), 1 at k param = 0; table (tk, tb)[nt]; unit b = 1.  One statement of the arithmetic for the per-mode kernels
+__device__ inline double fft2_beam(int a, int c, int N, int kind, double kval, double param, const double *__restrict__ tk,
+                                   const double *__restrict__ tb, int nt)
+{
+    double b = 1.0;
+    if (kind != kFft2Unit) {
+        const double n0 = (double)fft2_wave_number(a, N), n1 = (double)c;
+        const double k = kval * sqrt(n0 * n0 + n1 * n1);
+        if (kind == kFft2Gauss) b = exp(-0.5 * (k * param) * (k * param));
+        else if (kind == kFft2TopHat) { const double x = k * param; b = x > 0.0 ? 2.0 * j1(x) / x : 1.0; }
+        else b = fft2_table_beam(k, tk, tb, nt);
+    }
+    return b;
+}
+
+// out = conj(F) * b(k) * scale, ready for the inverse passes (unit: the conjugation alone, bfgx_irfft2_device).  out may be `spec`.
+// Pad columns are stored as zeros and not read.
 __global__ void __launch_bounds__(kFft2Threads)
 fft2_filter_kernel(const double2 *spec, double2 *out, int N, int pitch, int kind, double kval, double param, const double *__restrict__ tk,
                    const double *__restrict__ tb, int nt, double scale)
@@ -148,19 +163,54 @@ fft2_filter_kernel(const double2 *spec, double2 *out, int N, int pitch, int kind
         const int a = (int)(t / (unsigned)pitch), c = (int)(t - (unsigned)a * pitch);
         double2 v = make_double2(0.0, 0.0);
         if (c <= h) {
-            double b = 1.0;
-            if (kind != kFft2Unit) {
-                const double n0 = (double)fft2_wave_number(a, N), n1 = (double)c;
-                const double k = kval * sqrt(n0 * n0 + n1 * n1);
-                if (kind == kFft2Gauss) b = exp(-0.5 * (k * param) * (k * param));
-                else if (kind == kFft2TopHat) { const double x = k * param; b = x > 0.0 ? 2.0 * j1(x) / x : 1.0; }
-                else b = fft2_table_beam(k, tk, tb, nt);
-            }
+            const double b = fft2_beam(a, c, N, kind, kval, param, tk, tb, nt);
             const double2 f = spec[t];
             const double s = b * scale;
             v = make_double2(f.x * s, -f.y * s);
         }
         out[t] = v;
+    }
+}
+
+// The derivatives of a filtered map from its half spectrum, one pass over the modes: `spec` [N][pitch] (as bfgx_rfft2_device leaves it) is
+// read once and kept, b(k) is evaluated once per mode, and out[d][N][pitch], d < nder, receives conj(F m_d b) * scale, ready for the
+// inverse passes.  With n0 = fft2_wave_number(a, N) (axis 0, x), n1 = c (axis 1, y), g0 = kval n0, g1 = kval n1, h = N / 2:
+//   u 1;  u_x i g0 (0 where a == h);  u_y i g1 (0 where c == h);  u_xx -g0^2;  u_xy -g0 g1 (0 where a == h or c == h);  u_yy -g1^2
+// (a factor that is odd in an index is set to 0 at that index's Nyquist value, the rule of fft2_ks_angles' s2: it would break the Hermitian
+// symmetry of a real map's spectrum there).  spin_form == 0: [u, u_x, u_y, u_xx, u_xy, u_yy]; spin_form != 0: [u, u_x, u_y, lap, q_plus,
+// q_cross] with the multipliers -(g0^2 + g1^2), -(g0^2 - g1^2), -2 g0 g1 (q_cross with u_xy's zero rule).  nder = 1 writes u alone, with
+// the arithmetic of fft2_filter_kernel.  out must not overlap spec.  Pad columns are stored as zeros and not read.
+__global__ void __launch_bounds__(kFft2Threads)
+fft2_der_kernel(const double2 *__restrict__ spec, double2 *__restrict__ out, int N, int pitch, int kind, double kval, double param,
+                const double *__restrict__ tk, const double *__restrict__ tb, int nt, double scale, int nder, int spin_form)
+{
+    const int h = N >> 1;
+    const unsigned total = (unsigned)N * pitch;                      // (at most 4096 * 2056 < 2^24)
+    for (unsigned t = blockIdx.x * kFft2Threads + threadIdx.x; t < total; t += gridDim.x * kFft2Threads) {
+        const int a = (int)(t / (unsigned)pitch), c = (int)(t - (unsigned)a * pitch);
+        const double2 zero = make_double2(0.0, 0.0);
+        double2 v[6] = {zero, zero, zero, zero, zero, zero};
+        if (c <= h) {
+            const double b = fft2_beam(a, c, N, kind, kval, param, tk, tb, nt);
+            const double2 f = spec[t];
+            const double s = b * scale;
+            const double fx = f.x * s, fy = f.y * s;                 // F b scale
+            v[0] = make_double2(fx, -fy);
+            if (nder > 1) {
+                const double g0 = kval * (double)fft2_wave_number(a, N), g1 = kval * (double)c;
+                const double o0 = a != h ? g0 : 0.0, o1 = c != h ? g1 : 0.0;      // the odd factors
+                v[1] = make_double2(-(o0 * fy), -(o0 * fx));         // conj(i g (fx + i fy)) = -g fy - i g fx
+                v[2] = make_double2(-(o1 * fy), -(o1 * fx));
+                const double m00 = g0 * g0, m11 = g1 * g1, m01 = o0 * o1;
+                const double m3 = spin_form ? m00 + m11 : m00, m4 = spin_form ? m00 - m11 : m01, m5 = spin_form ? 2.0 * m01 : m11;
+                v[3] = make_double2(-(m3 * fx), m3 * fy);            // conj(-m (fx + i fy))
+                v[4] = make_double2(-(m4 * fx), m4 * fy);
+                v[5] = make_double2(-(m5 * fx), m5 * fy);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 6; ++d)
+            if (d < nder) out[(size_t)d * total + t] = v[d];
     }
 }
 

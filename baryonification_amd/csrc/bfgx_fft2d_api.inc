@@ -1,5 +1,5 @@
 // bfgx_fft2d_api.inc -- host side and C ABI of the 2-D FFTs of gridded maps (include/bfgx.h, "flat-sky maps"): the transform pair, power
-// spectra, filters and the Kaiser-Squires pair; included by bfgx_api.hip after bfgx_interlace_api.inc (fft_pitch, ilog2_exact, xpk_window).
+// spectra, filters, the Kaiser-Squires pair and the derivatives of a filtered map; included by bfgx_api.hip after bfgx_interlace_api.inc (fft_pitch, ilog2_exact, xpk_window).
 // Kernels: bfgx_fft2d.hpp, and the line and strided kernels of bfgx_fft.hpp / bfgx_bispec.hpp through a setup of their own.
 
 namespace {
@@ -216,6 +216,8 @@ int fft2_filter(Fft2Setup &f, hipStream_t s, int N, const double2 *spec, double2
     return BFGX_OK;
 }
 
+void fft2_free_beam(void *p) { delete static_cast<std::vector<double> *>(p); }
+
 int fft2_ks(Fft2Setup &f, hipStream_t s, int N, double2 *s1, double2 *s2, int eb)
 {
     const int pitch = fft_pitch(N);
@@ -330,6 +332,57 @@ int bfgx_filter_map_2d_device(int device, void *hip_stream, int32_t n, const dou
     if (int rc = fft2_forward(*f, s, N, map_dev, w.s1, w.u)) return rc;
     if (int rc = fft2_filter(*f, s, N, w.s1, w.s1, kind, L, param, tk, tb, ntable, 1.0 / ((double)N * (double)N))) return rc;
     return fft2_inverse_conj(*f, s, N, w.s1, w.u, map_out_dev);
+}
+
+// The work array of the derivatives: nder products [n][pitch], then u, the other side of the out-of-place column pass.  The beam table
+// rides in u: it is copied there before fft2_der_kernel, read by that kernel alone, and u is first written by the column passes after it.
+// Its host copy is a vector of the call's own (not Fft2Setup::beam, which calls on one setup share), deleted by a host function that the
+// stream runs after the copy: two threads on one setup cannot reach each other's table.
+int64_t bfgx_derivatives_2d_work_doubles(int32_t n, int32_t nder)
+{
+    if (n < kFft2MinN || n > kFft2MaxN || ilog2_exact(n) < 3 || (nder != 1 && nder != 6)) return 0;
+    return 2 * (int64_t)n * fft_pitch(n) * (nder + 1);
+}
+
+int bfgx_derivatives_2d_device(int device, void *hip_stream, int32_t n, const double *spec_dev, double L, int32_t kind, double param,
+                               const double *table_k_host, const double *table_b_host, int32_t ntable, int32_t nder, int32_t spin_form,
+                               double *work_dev, double *ders_out_dev)
+{
+    if (!spec_dev || !work_dev || !ders_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (int rc = fft2_check_n(n)) return rc;
+    if (kind < kFft2Gauss || kind > kFft2Unit) return fail(BFGX_ERR_INVALID, "2-D derivatives kind %d: 0 (Gaussian), 1 (top hat), 2 (table) or 3 (no filter)", kind);
+    if (kind == kFft2Unit) { if (!(L > 0)) return fail(BFGX_ERR_INVALID, "2-D filter needs L > 0"); }
+    else if (int rc = fft2_check_filter(n, L, kind, param, table_k_host, table_b_host, ntable)) return rc;
+    if (nder != 1 && nder != 6) return fail(BFGX_ERR_INVALID, "2-D derivatives: nder must be 1 or 6 (got %d)", nder);
+    if (int rc = fft2_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fft2_check_aligned(spec_dev, "spec_dev")) return rc;
+    if (int rc = select_device(device)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    Fft2Setup *f = nullptr;
+    if (int rc = fft2_setup(device, n, &f)) return rc;
+    const int N = n, pitch = fft_pitch(N);
+    const int64_t half = (int64_t)N * pitch;
+    double2 *prod = (double2 *)work_dev, *u = prod + (int64_t)nder * half;
+    const double *tk = nullptr, *tb = nullptr;
+    if (kind == kFft2Table) {
+        // the host side of the upload belongs to this call alone: it is freed by the stream itself, after the copy that reads it
+        std::vector<double> *beam = new std::vector<double>(table_k_host, table_k_host + ntable);
+        beam->insert(beam->end(), table_b_host, table_b_host + ntable);
+        hipError_t e = hipMemcpyAsync(u, beam->data(), sizeof(double) * beam->size(), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipLaunchHostFunc(s, fft2_free_beam, beam);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(s);                             // (the copy may be pending: nothing reads the vector after this)
+            delete beam;
+            HIP_TRY(e);
+        }
+        tk = (const double *)u; tb = tk + ntable;
+    }
+    hipLaunchKernelGGL(fft2_der_kernel, dim3(fft2_stream_grid(*f, half)), dim3(kFft2Threads), 0, s, (const double2 *)spec_dev, prod, N, pitch,
+                       (int)kind, 2 * 3.141592653589793 / L, param, tk, tb, (int)ntable, 1.0 / ((double)N * (double)N), (int)nder, (int)spin_form);
+    HIP_TRY(hipGetLastError());
+    for (int d = 0; d < nder; ++d)
+        if (int rc = fft2_inverse_conj(*f, s, N, prod + d * half, u, ders_out_dev + (int64_t)d * N * N)) return rc;
+    return BFGX_OK;
 }
 
 int bfgx_kappa_to_shear_2d_device(int device, void *hip_stream, int32_t n, const double *kappa_dev, double *work_dev, double *g1_out_dev,

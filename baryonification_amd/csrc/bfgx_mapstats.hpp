@@ -1,11 +1,13 @@
 // bfgx_mapstats.hpp -- reductions over whole HEALPix maps for gfx950: the higher-order statistics of shells (moments and
-// cross-moments of up to three maps, counts of local maxima and minima, Minkowski functionals of the excursion sets).
+// cross-moments of up to three maps, counts of local maxima and minima, Minkowski functionals of the excursion sets), and the
+// counts of maxima and minima of a square grid.  The moment and Minkowski kernels take npix values in any pixelisation.
 //
 //   mapstats_sum_kernel<K>      pass 1: per-block fp64 sums of the K maps over the good pixels, and their number
 //   mapstats_central_kernel<K>  pass 2: per-block fp64 sums of prod_a (x_a - mean_a)^{e_a} for every exponent tuple of degree 2..4
 //   mapstats_combine_kernel     one workgroup: the block partials of a pass added in a fixed order, divided by n
 //   mapstats_peaks_kernel       one lane per pixel: the 8 neighbours (hpx::pix_neighbours), strict maximum / minimum, a histogram of
 //                               the extrema's values per workgroup in LDS, integer atomics to the result
+//   mapstats_peaks_grid_kernel  the same outputs for a square grid [n][n]: tiles of 32 x 64 pixels staged in LDS with their halo
 //   mapstats_minkowski_kernel   one lane per pixel: the bin of u, sqrt(g2) and c / g2 from the six derivative maps, per-block fp64
 //                               sums per bin in a fixed order (below), integer counts per bin
 //   mapstats_minkowski_combine_kernel   one lane per (sum, bin): the block partials added in block order
@@ -25,7 +27,8 @@
 //
 // Per pixel: pass 1 and pass 2 each read K doubles (+ 1 mask byte) and write nothing; the peaks kernel reads 1 double (+ 1 byte),
 // gathers 8 neighbour values (+ 8 bytes) that mostly hit L2 (neighbours lie on the same and the two adjacent rings), and writes 1
-// flag byte when asked to; the Minkowski kernel reads 6 doubles (+ 1 byte) = 49 B and writes nothing.
+// flag byte when asked to; the grid peaks kernel reads 1.10 doubles (+ 1.10 bytes), its 8 neighbours from LDS, and writes the same
+// flag byte; the Minkowski kernel reads 6 doubles (+ 1 byte) = 49 B and writes nothing.
 #pragma once
 #include "bfgx_hpx.hpp"
 
@@ -215,6 +218,82 @@ mapstats_peaks_kernel(Peaks a, const double *__restrict__ map, const uint8_t *__
     }
     __syncthreads();
     for (int b = threadIdx.x; b < 2 * a.nb; b += kThreads)
+        if (s_hist[b]) atomicAdd(&counts[b], (unsigned long long)s_hist[b]);
+}
+
+// ---- extrema of a square grid [n][n] (C order), 3 <= n <= 16384: the 8 neighbours are (i + di, j + dj), wrapped on both axes when
+// `periodic`, else a pixel on the border is never an extremum
+constexpr int kGridTileW = 64;             // pixels of a tile row: four whole 128-byte lines, one pixel per lane of a wave
+constexpr int kGridTileH = 32;             // rows of a tile: each of the four waves takes every fourth
+constexpr int kGridLdsW = kGridTileW + 2, kGridLdsH = kGridTileH + 2;      // with the one-pixel halo: 34 x 66 doubles = 17 952 B
+constexpr int kGridMaxBlocks = 2048;       // 8 workgroups per CU (LDS: 8 x 17.5 KiB + the histograms), each taking tiles in turn
+constexpr int64_t kGridMinN = 3, kGridMaxN = 16384;
+
+// the value of pixel (i, j) if it is good, NaN if it is bad or outside the map.  periodic: i = -1 is row n - 1 and i = n is row 0 (the
+// only rows outside [0, n) a neighbour can lie in), the same for j.  A NaN makes every comparison false, so a pixel with a bad or
+// missing neighbour, or bad itself, is neither above nor below its neighbours: no separate flags
+__device__ inline double grid_good_value(const double *__restrict__ map, const uint8_t *__restrict__ mask, int n, int periodic, int i, int j)
+{
+    if (periodic) {
+        i = i == -1 ? n - 1 : i == n ? 0 : i;
+        j = j == -1 ? n - 1 : j == n ? 0 : j;
+    }
+    if (i < 0 || i >= n || j < 0 || j >= n) return __longlong_as_double(0x7ff8000000000000ll);
+    const int64_t p = (int64_t)i * n + j;
+    const double v = map[p];
+    return hpx::good_value(v) && (!mask || mask[p] != 0) ? v : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// The outputs of mapstats_peaks_kernel for a square grid.  A workgroup takes tiles of kGridTileH x kGridTileW pixels in turn: the tile
+// and its halo (wrapped at the seams, NaN outside a map that is not periodic, NaN where the pixel is bad) are staged in LDS once, so a
+// value is fetched once per tile that needs it (1.10 fetches per pixel) and not nine times; then lane = column, so a wave reads a row
+// of LDS at consecutive addresses.  Tiles beyond the map's edge are partial.  Dynamic LDS: 2 nb ints.
+__global__ void __launch_bounds__(kThreads)
+mapstats_peaks_grid_kernel(int n, int periodic, int nb, const double *__restrict__ map, const uint8_t *__restrict__ mask,
+                           const double *__restrict__ edges, unsigned long long *__restrict__ counts, int8_t *__restrict__ flags)
+{
+    extern __shared__ int s_hist[];
+    __shared__ double s_v[kGridLdsH * kGridLdsW];
+    for (int b = threadIdx.x; b < 2 * nb; b += kThreads) s_hist[b] = 0;
+    const int tcols = (n + kGridTileW - 1) / kGridTileW, trows = (n + kGridTileH - 1) / kGridTileH;
+    const int col = threadIdx.x & (kGridTileW - 1);
+    for (int tile = blockIdx.x; tile < tcols * trows; tile += gridDim.x) {
+        const int i0 = (tile / tcols) * kGridTileH, j0 = (tile % tcols) * kGridTileW;
+        __syncthreads();                                                   // (the histogram is zeroed; the last tile has been read)
+        for (int t = threadIdx.x; t < kGridLdsH * kGridLdsW; t += kThreads)
+            s_v[t] = grid_good_value(map, mask, n, periodic, i0 - 1 + t / kGridLdsW, j0 - 1 + t % kGridLdsW);
+        __syncthreads();
+        const int j = j0 + col;
+        for (int r = threadIdx.x / kGridTileW; r < kGridTileH; r += kThreads / kGridTileW) {
+            const int i = i0 + r;
+            if (i >= n || j >= n) continue;
+            const double *c = s_v + (r + 1) * kGridLdsW + col + 1;
+            const double v = c[0];
+            bool above = true, below = true;
+#pragma unroll
+            for (int di = -1; di <= 1; ++di) {
+#pragma unroll
+                for (int dj = -1; dj <= 1; ++dj) {
+                    if (di == 0 && dj == 0) continue;
+                    const double w = c[di * kGridLdsW + dj];
+                    above = above && v > w;
+                    below = below && v < w;
+                }
+            }
+            const int kind = above ? 1 : below ? -1 : 0;
+            if (flags) flags[(int64_t)i * n + j] = (int8_t)kind;
+            if (kind != 0 && v >= edges[0] && v < edges[nb]) {
+                int lo = 0, hi = nb;                                       // edges[lo] <= v < edges[hi]
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (v >= edges[mid]) lo = mid; else hi = mid;
+                }
+                atomicAdd(&s_hist[(kind > 0 ? 0 : nb) + lo], 1);
+            }
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < 2 * nb; b += kThreads)
         if (s_hist[b]) atomicAdd(&counts[b], (unsigned long long)s_hist[b]);
 }
 

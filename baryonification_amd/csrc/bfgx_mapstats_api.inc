@@ -61,6 +61,23 @@ int bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int3
     return BFGX_OK;
 }
 
+int bfgx_mapstats_peaks_2d_device(int device, void *hip_stream, int64_t n, int32_t periodic, const double *map_dev, const uint8_t *mask_dev,
+                                  int32_t nb, const double *edges_dev, int64_t *counts_dev, int8_t *flags_dev)
+{
+    if (!map_dev || !edges_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
+    if (n < mapstats::kGridMinN || n > mapstats::kGridMaxN) return fail(BFGX_ERR_INVALID, "n must be in [%lld, %lld] (got %lld)", (long long)mapstats::kGridMinN, (long long)mapstats::kGridMaxN, (long long)n);
+    if (nb < 1 || nb > mapstats::kMaxBins) return fail(BFGX_ERR_INVALID, "nb must be in [1, %d] (got %d)", mapstats::kMaxBins, nb);
+    if (int rc = select_device(device)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 2 * nb, s));
+    const int64_t tiles = ((n + mapstats::kGridTileW - 1) / mapstats::kGridTileW) * ((n + mapstats::kGridTileH - 1) / mapstats::kGridTileH);
+    hipLaunchKernelGGL(mapstats::mapstats_peaks_grid_kernel, dim3((unsigned)std::min<int64_t>(tiles, mapstats::kGridMaxBlocks)), dim3(mapstats::kThreads),
+                       sizeof(int) * 2 * nb, s, (int)n, periodic ? 1 : 0, (int)nb, map_dev, mask_dev, edges_dev,
+                       reinterpret_cast<unsigned long long *>(counts_dev), flags_dev);
+    HIP_TRY(hipGetLastError());
+    return BFGX_OK;
+}
+
 int64_t bfgx_mapstats_minkowski_work_doubles(int64_t npix, int32_t nb)
 {
     if (npix < 1 || npix > 12 * kHpxMaxNside * kHpxMaxNside || nb < 1 || nb > mapstats::kMaxMfBins) return -1;

@@ -556,6 +556,34 @@ def filter_map_2d_device(map_ptr, n, L, kind, param, table_k, table_b, work_ptr,
                                                     C.c_void_p(int(work_ptr)), C.c_void_p(int(map_out_ptr))))
 
 
+DERIVATIVE_KINDS_2D = dict(FILTER_KINDS_2D, unit=3)
+
+
+def derivatives_2d_work_doubles(n, nder=6):
+    """doubles of scratch of derivatives_2d_device: nder + 1 half spectra [n][fft_pitch(n)]; 0 for an unsupported n or nder"""
+    return int(_lib.load().bfgx_derivatives_2d_work_doubles(int(n), int(nder)))
+
+
+def derivatives_2d_device(spec_ptr, n, L, kind, param, table_k, table_b, nder, spin_form, work_ptr, ders_out_ptr, device=0, stream=0):
+    """half spectrum [n][fft_pitch(n)] (kept) -> ders_out [nder][n][n], nder = 6: [u, u_x, u_y, u_xx, u_xy, u_yy] of the filtered map (or
+    [u, u_x, u_y, lap, q_plus, q_cross] with spin_form), nder = 1: u alone; kind as in DERIVATIVE_KINDS_2D ('unit': no filter)"""
+    kind = DERIVATIVE_KINDS_2D[kind] if isinstance(kind, str) else int(kind)
+    tk = None if table_k is None else np.ascontiguousarray(table_k, dtype=np.float64)
+    tb = None if table_b is None else np.ascontiguousarray(table_b, dtype=np.float64)
+    _lib.check(_lib.load().bfgx_derivatives_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(spec_ptr)), float(L),
+                                                     kind, float(param), None if tk is None else tk.ctypes.data,
+                                                     None if tb is None else tb.ctypes.data, 0 if tk is None else int(tk.size), int(nder),
+                                                     int(bool(spin_form)), C.c_void_p(int(work_ptr)), C.c_void_p(int(ders_out_ptr))))
+
+
+def peaks_2d_device(map_ptr, n, periodic, mask_ptr, nb, edges_ptr, counts_ptr, flags_ptr=0, device=0, stream=0):
+    """maxima | minima of a square grid [n][n] per bin of their value: counts int64 [2][nb], optional int8 flags [n][n]"""
+    _lib.check(_lib.load().bfgx_mapstats_peaks_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), int(bool(periodic)),
+                                                        C.c_void_p(int(map_ptr)), C.c_void_p(int(mask_ptr) or None), int(nb),
+                                                        C.c_void_p(int(edges_ptr)), C.c_void_p(int(counts_ptr)),
+                                                        C.c_void_p(int(flags_ptr) or None)))
+
+
 def kappa_to_shear_2d_device(kappa_ptr, n, work_ptr, g1_out_ptr, g2_out_ptr, device=0, stream=0):
     """Kaiser-Squires, convergence [n][n] -> shear (g1, g2)"""
     _lib.check(_lib.load().bfgx_kappa_to_shear_2d_device(int(device), C.c_void_p(int(stream) or None), int(n), C.c_void_p(int(kappa_ptr)),

@@ -8,4 +8,5 @@ from .pixelfunc import ud_grade, get_interp_weights, get_interp_val, get_all_nei
 from .mapstats import (map_moments, peak_counts, shell_statistics, moment_exponents, minkowski_functionals,
                        minkowski_from_derivatives, minkowski_gaussian)
 from .flatsky import rfft2, irfft2, power_spectrum_2d, cross_power_spectrum_2d, smoothing_2d, kappa_to_shear_2d, shear_to_kappa_2d
+from .flatstats import derivatives_2d, peak_counts_2d, minkowski_functionals_2d, minkowski_gaussian_2d, patch_statistics
 from .pseudocl import mode_coupling_matrix, mask_spectrum, ClBins, pseudo_cl, PseudoClWorkspace, decoupled_cl

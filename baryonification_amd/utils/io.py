@@ -191,6 +191,15 @@ class GriddedMap(object):
         pk = x['paa'] * (L ** 3 / float(self.Npix) ** 6) if normalize else x['paa']
         return {'k': x['k'], 'pk': pk, 'counts': x['counts']}
 
+    def statistics(self, scales, window='gauss', order=4, peak_bins=None, mask=None, mf_bins=None, periodic=True):
+        """utils.patch_statistics of a 2-D map over its side L = Npix * res: moments, and with peak_bins / mf_bins peak counts and
+        Minkowski functionals, of the map smoothed at each of `scales` (in the units of `res`)."""
+        if not self.is2D:
+            raise ValueError("statistics: the patch statistics are 2-D, this map is 3-D")
+        from .flatstats import patch_statistics
+        return patch_statistics(self.map, float(self.Npix * self.res), scales, window=window, order=order, peak_bins=peak_bins, mask=mask,
+                                mf_bins=mf_bins, periodic=periodic)
+
     def __str__(self):
         return (f"GriddedMap of {'2D' if self.is2D else '3D'} shape {self.map.shape}, res = {self.res}, z = {self.redshift}.\n"
                 f"Cosmology set to {self.cosmo}.")

@@ -658,6 +658,20 @@ int  bfgx_power_spectrum_2d_device(int device, void *hip_stream, int32_t n, cons
  * param >= 0.  map_out_dev may be map_dev. */
 int  bfgx_filter_map_2d_device(int device, void *hip_stream, int32_t n, const double *map_dev, double L, int32_t kind, double param,
                                const double *table_k_host, const double *table_b_host, int32_t ntable, double *work_dev, double *map_out_dev);
+/* The derivatives of a filtered map from its half spectrum spec_dev [n][pitch] (what bfgx_rfft2_device leaves; kept, 16-byte aligned):
+ * ders_out_dev[nder][n][n], map d = irfft2(spec m_d b(k)) / n^2.  With fftfreq's n0 (axis 0, x), n1 = c (axis 1, y), g = 2 pi / L n and
+ * h = n / 2 the multipliers are  u: 1;  u_x: i g0 (0 where a == h);  u_y: i g1 (0 where c == h);  u_xx: -g0^2;  u_xy: -g0 g1 (0 where
+ * a == h or c == h);  u_yy: -g1^2 -- a factor odd in an index is 0 at that index's Nyquist value, as s2 below.  spin_form == 0:
+ * [u, u_x, u_y, u_xx, u_xy, u_yy]; spin_form != 0: [u, u_x, u_y, lap = u_xx + u_yy, q_plus = u_xx - u_yy, q_cross = 2 u_xy], the six maps
+ * bfgx_mapstats_minkowski_device takes.  nder = 6, or 1 for the filtered map alone.  kind, param and the table as in
+ * bfgx_filter_map_2d_device, and kind 3: no filter (b = 1; param and the table are ignored).  work_dev:
+ * bfgx_derivatives_2d_work_doubles(n, nder) = 2 n pitch (nder + 1) doubles (host arithmetic; 0 for an unsupported n or nder): the nder
+ * products, then the scratch of the out-of-place column pass, in which the beam table rides until the products are formed.  The
+ * spectrum is read once, b(k) is evaluated once per mode; no atomics: a repeated call gives the same bits. */
+int64_t bfgx_derivatives_2d_work_doubles(int32_t n, int32_t nder);
+int  bfgx_derivatives_2d_device(int device, void *hip_stream, int32_t n, const double *spec_dev, double L, int32_t kind, double param,
+                                const double *table_k_host, const double *table_b_host, int32_t ntable, int32_t nder, int32_t spin_form,
+                                double *work_dev, double *ders_out_dev);
 /* Kaiser-Squires.  With fftfreq's integer wave numbers n0 (axis 0) and n1 = c (axis 1): c2 = (n0^2 - n1^2) / (n0^2 + n1^2), s2 = 2 n0 n1 /
  * (n0^2 + n1^2), both 0 at the zero mode, s2 = 0 where either index is the Nyquist index.  g1^ = c2 kappa^, g2^ = s2 kappa^; back:
  * kappa_E^ = c2 g1^ + s2 g2^, kappa_B^ = -s2 g1^ + c2 g2^.  Outputs may be the inputs. */
@@ -888,6 +902,9 @@ int  bfgx_hpx_scatter_add(int device, int64_t npix, double *hmap_host, int64_t n
  *   counts_dev[2][nb] (zeroed by the entry) = maxima | minima with edges[b] <= value < edges[b + 1]; values outside the edges are not
  *   counted.  edges_dev: nb + 1 ascending finite doubles on the device (1 <= nb <= 4096; the order is the caller's to check).
  *   flags_dev (optional, one int8 per pixel): +1 maximum, -1 minimum, 0 neither.  Integer atomics: the counts are exact.
+ * peaks_2d: the same outputs for a square grid map_dev [n][n] (C order), 3 <= n <= 16384 (any n): the 8 neighbours of pixel (i, j) are
+ *   (i + di, j + dj); periodic != 0 wraps both axes, periodic == 0 makes a pixel on the border never an extremum.  A pixel counts only
+ *   if it and all 8 neighbours are good.  counts_dev, edges_dev, nb and flags_dev as for peaks.
  * minkowski: ders_dev = six maps of npix doubles, row after row, the derivatives of a map u in the orthonormal basis (e_theta, e_phi) in
  *   spin form: u, u_t, u_p, lap = u;tt + u;pp, q_plus = u;tt - u;pp, q_cross = 2 u;tp.  A pixel is good if all six are finite, u is not UNSEEN and the mask is nonzero.  With
  *   g2 = u_t^2 + u_p^2 and c = u_t u_p q_cross - lap g2 / 2 + q_plus (u_t^2 - u_p^2) / 2 (= 2 u_t u_p u;tp - u_t^2 u;pp - u_p^2 u;tt),
@@ -903,6 +920,8 @@ int  bfgx_mapstats_moments_device(int device, void *hip_stream, int64_t npix, in
                                   const uint8_t *mask_dev, int64_t *n_dev, double *out_dev, double *work_dev);
 int  bfgx_mapstats_peaks_device(int device, void *hip_stream, int64_t nside, int32_t nest, const double *map_dev, const uint8_t *mask_dev,
                                 int32_t nb, const double *edges_dev, int64_t *counts_dev, int8_t *flags_dev);
+int  bfgx_mapstats_peaks_2d_device(int device, void *hip_stream, int64_t n, int32_t periodic, const double *map_dev, const uint8_t *mask_dev,
+                                   int32_t nb, const double *edges_dev, int64_t *counts_dev, int8_t *flags_dev);
 int64_t bfgx_mapstats_minkowski_work_doubles(int64_t npix, int32_t nb);
 int  bfgx_mapstats_minkowski_device(int device, void *hip_stream, int64_t npix, const double *ders_dev, const uint8_t *mask_dev, int32_t nb,
                                     const double *edges_dev, int64_t *counts_dev, double *sums_dev, double *work_dev);
