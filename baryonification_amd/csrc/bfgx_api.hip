@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -1707,6 +1709,9 @@ int bfgx_paint_shell(const bfgx_catalog *cat, const bfgx_model *model, int64_t n
 // CIC / TSC particle deposit (make_map(N, assignment=...)): shares the deposit's sort and workspace
 #include "bfgx_deposit_cloud_api.inc"
 
+// what the five Fourier files below share: checks, table cache, kernel attributes, launchers, the 3-D setup and its transform passes
+#include "bfgx_fourier_host.inc"
+
 // 3-D FFT and power spectrum of gridded maps
 #include "bfgx_fft_api.inc"
 
@@ -1762,11 +1767,7 @@ extern "C" void bfgx_cache_clear(void)
 {
     g_shells.clear();            // plans + device buffers of the one-shot shell entries
     dep_release_all();           // workspace of the tiled particle deposit (bfgx_deposit_api.inc)
-    fft_release_all();           // twiddle / wavenumber tables of the power spectrum
-    bispec_release_all();        // n^2 -> bin tables of the bispectrum (bfgx_bispec_api.inc)
-    xpk_release_all();           // window tables of the cross power spectrum (bfgx_xpk_api.inc)
-    interlace_release_all();     // half-cell phase tables of the interlaced power spectrum (bfgx_interlace_api.inc)
-    fft2_release_all();          // twiddle tables of the 2-D transforms (bfgx_fft2d_api.inc)
+    fourier_release_all();       // setups and tables of the 3-D and 2-D transforms and spectra (bfgx_fourier_host.inc)
     g_grids.clear();             // plans + device maps of the one-shot grid entries
     g_snaps.clear();             // plans + device record buffers of the snapshot records entries (bfgx_snapshot_api.inc)
     deprec_release_all();        // device buffers of the deposit's records entry

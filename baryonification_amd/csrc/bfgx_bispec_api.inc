@@ -1,12 +1,12 @@
 // C ABI of the bispectrum of gridded 3-D maps and of the inverse slab transforms it is built on (include/bfgx.h, "bispectrum");
-// included by bfgx_api.hip after bfgx_fft_api.inc (FftSetup, fft_planes, fft_pitch).  Kernels: bfgx_bispec.hpp.
+// included by bfgx_api.hip after bfgx_fourier_host.inc, on which alone it builds (FftSetup, the transform passes, the table cache,
+// upload_owned).  Kernels: bfgx_bispec.hpp.
 
 namespace {
 
-// the n^2 -> bin table of one (device, n, L, edges), and what the triangle kernels need besides the FFT setup
+// the n^2 -> bin table of one (device, n, L, edges): what the triangle kernels need besides the FFT setup
 struct BispecSetup {
     DevBuf dtab;                         // uint8 [3 (n/2)^2 + 1], 255 = outside the bins
-    std::vector<uint32_t> ent;           // the packed terms of the last call (host side of the upload)
     int init(int N, double L, int nb, const double *edges)
     {
         const int h = N / 2;
@@ -21,42 +21,16 @@ struct BispecSetup {
     }
 };
 
-std::mutex g_bispec_mu;
-std::map<std::tuple<int, int, double, std::vector<double>>, BispecSetup *> g_bispec;
+FourierCache<BispecSetup, int, double, std::vector<double>> g_bispec;
 
 int bispec_setup(int device, int N, double L, int nb, const double *edges, BispecSetup **out)
 {
-    std::lock_guard<std::mutex> lk(g_bispec_mu);
-    const auto key = std::make_tuple(device, N, L, std::vector<double>(edges, edges + nb + 1));
-    auto it = g_bispec.find(key);
-    if (it == g_bispec.end()) {
-        BispecSetup *b = new BispecSetup();
-        if (int rc = b->init(N, L, nb, edges)) { delete b; return rc; }
-        it = g_bispec.emplace(key, b).first;
-    }
-    *out = it->second;
-    return BFGX_OK;
-}
-
-void bispec_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_bispec_mu);
-    for (auto &kv : g_bispec) { (void)hipSetDevice(std::get<0>(kv.first)); delete kv.second; }
-    g_bispec.clear();
+    return g_bispec.get(std::make_tuple(device, N, L, std::vector<double>(edges, edges + nb + 1)), out,
+                        [&](BispecSetup &b) { return b.init(N, L, nb, edges); });
 }
 
 // ---- argument checks, stated once (no device call)
-int bispec_check_grid(int n_grid)
-{
-    if (n_grid > 1024 || ilog2_exact(n_grid) < 3) return fail(BFGX_ERR_UNSUPPORTED, "n_grid must be a power of two with 8 <= n_grid <= 1024");
-    return BFGX_OK;
-}
-
-int bispec_check_aligned(const void *p, const char *what)
-{
-    if (reinterpret_cast<uintptr_t>(p) & 15) return fail(BFGX_ERR_INVALID, "%s must be 16-byte aligned (complex values)", what);
-    return BFGX_OK;
-}
+int bispec_check_grid(int n_grid) { return fourier_check_grid(n_grid, kFft3MaxN, "n_grid must be a power of two with 8 <= n_grid <= 1024"); }
 
 int bispec_check_bins(double L, int nbins, const double *edges)
 {
@@ -77,76 +51,13 @@ int bispec_check_triangles(int nbins, int ntri, const int32_t *tri)
     return BFGX_OK;
 }
 
-// ---- the transforms
-unsigned stream_grid(const FftSetup &f, int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)f.n_cu * 8)); }
-
-int fft_conj(const FftSetup &f, hipStream_t s, double2 *F, int64_t n)
-{
-    hipLaunchKernelGGL(fft_conj_kernel, dim3(stream_grid(f, n)), dim3(256), 0, s, F, n);
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-// forward complex transforms, in place, along the FIRST axis of F [N][ncols][pitch]: the strides of fft_axis0_pk, the result stored
-int fft_axis0_store(FftSetup &f, hipStream_t s, int N, int ncols, double2 *F, int pitch)
-{
-    const int64_t ntiles = (int64_t)f.ztiles * ncols;
-    const unsigned wgs = (unsigned)std::min<int64_t>(ntiles, (int64_t)f.n_cu * std::max<size_t>(1, (size_t)(160 * 1024) / f.lds));
-    if (int rc = f.strided_launch<0>(s, wgs, f.lds, F, N, (int64_t)ncols * pitch, (int64_t)pitch, ncols, PkBins{})) return rc;
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
-// the instantiations of bispec_triangle_kernel: terms per thread (the last one holds kBispecMaxTri + kBispecMaxBins terms)
-#define BFGX_BISPEC_TPT_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(28) X(33)
-static_assert(kBispecMaxPerThread == 33, "the list ends at kBispecMaxPerThread");
-
-// the dynamic-LDS attribute of the kernels of bfgx_bispec.hpp: the most any setup asks for, so the order in which setups of different
-// sizes are built and used does not matter
-std::vector<int> g_bispec_attr_devices;          // (under g_bispec_mu) the devices whose kernels have the attribute
-
-int bispec_kernel_attrs(int device)
-{
-    std::lock_guard<std::mutex> lk(g_bispec_mu);
-    if (std::find(g_bispec_attr_devices.begin(), g_bispec_attr_devices.end(), device) != g_bispec_attr_devices.end()) return BFGX_OK;
-    g_bispec_attr_devices.push_back(device);
-    HIP_TRY(hipFuncSetAttribute((const void *)fft_c2r_lines_kernel<2, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * sizeof(double2) * 512)));
-    HIP_TRY(hipFuncSetAttribute((const void *)fft_c2r_lines_kernel<1, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double2) * 1024)));
-    const int tri = (int)bispec_lds_bytes(kBispecMaxBins);
-#define BFGX_TRI_ATTR(T) HIP_TRY(hipFuncSetAttribute((const void *)bispec_triangle_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, tri));
-    BFGX_BISPEC_TPT_LIST(BFGX_TRI_ATTR)
-#undef BFGX_TRI_ATTR
-    return BFGX_OK;
-}
-
-// forward transforms along the middle axis of F [planes][N][pitch], then complex to real along the last one -> map [planes][N][N].
-// F holds the CONJUGATE of the spectrum to invert (conj(FFT(conj X)) = IFFT(X)): the last pass reads it back conjugated.
-int ifft_planes_conj(FftSetup &f, hipStream_t s, int N, int planes, double2 *F, double *map, int pitch)
-{
-    const unsigned wgs = f.ztiles * (unsigned)planes;
-    if (int rc = f.strided_launch<0>(s, wgs, f.lds, F, N, (int64_t)pitch, (int64_t)N * pitch, planes, PkBins{})) return rc;
-    HIP_TRY(hipGetLastError());
-    // the workgroup shapes of the forward r2c pass (fft_planes)
-    const size_t npairs = (size_t)planes * N / 2;
-    const bool two = N <= 512 && npairs % 2 == 0;
-    const unsigned wg = (unsigned)(two ? npairs / 2 : npairs);
-    const size_t ldsb = (two ? 2 : 1) * sizeof(double2) * N;
-    const double2 *Fc = F;
-#define BFGX_C2R(P, T) hipLaunchKernelGGL((fft_c2r_lines_kernel<P, T>), dim3(wg), dim3(P * T), ldsb, s, Fc, map, N, f.lg, f.dtw.as<double2>(), pitch)
-    if (two) BFGX_C2R(2, 128);
-    else BFGX_C2R(1, 256);
-#undef BFGX_C2R
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
-}
-
 // fields[i] = the inverse transform of spec [N][N][pitch] restricted to bin i (unit: of ones there), i < nb; scratch: one half spectrum
 int bispec_fields(FftSetup &f, BispecSetup &bs, hipStream_t s, int N, int nb, const double2 *spec, int unit, double2 *scratch, double *fields)
 {
     const int pitch = fft_pitch(N);
     const int64_t nspec = (int64_t)N * N * pitch, npts = (int64_t)N * N * N;
     for (int i = 0; i < nb; ++i) {
-        hipLaunchKernelGGL(bispec_select_kernel, dim3(stream_grid(f, nspec)), dim3(256), 0, s, spec, scratch, bs.dtab.as<uint8_t>(), N, pitch, i, unit);
+        hipLaunchKernelGGL(bispec_select_kernel, dim3(stream_grid(f.n_cu, nspec)), dim3(256), 0, s, spec, scratch, bs.dtab.as<uint8_t>(), N, pitch, i, unit);
         HIP_TRY(hipGetLastError());
         if (int rc = fft_axis0_store(f, s, N, N, scratch, pitch)) return rc;
         if (int rc = ifft_planes_conj(f, s, N, N, scratch, fields + (int64_t)i * npts, pitch)) return rc;
@@ -186,7 +97,7 @@ int bispec_sums(const FftSetup &f, hipStream_t s, int N, int nb, const double *f
     // CU measured 5 % slower, 37.8 against 35.9 ms for two sweeps of 580 terms at N = 512) -- and as the partials of the work array
     // have room for
     const int by_regs = tpt <= 2 ? 4 : tpt <= 10 ? 3 : tpt <= 20 ? 2 : 1;
-    const int per_cu = (int)std::min<size_t>((size_t)by_regs, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
+    const int per_cu = (int)std::min<size_t>((size_t)by_regs, std::max<size_t>(1, kCuLdsBytes / lds));
     const int64_t room = (int64_t)kBispecMaxWgs * kBispecMaxPerThread / tpt;
     const int nwg = (int)std::min<int64_t>(std::min<int64_t>(npts / kBispecChunk, room), (int64_t)f.n_cu * per_cu);
 #define BFGX_TRI(T) case T: hipLaunchKernelGGL((bispec_triangle_kernel<T>), dim3((unsigned)nwg), dim3(kBispecThreads), lds, s, fields, npts, nb, ent_dev, ntot, G, partials); break;
@@ -208,7 +119,7 @@ int bfgx_fft_slab_axis0_device(int device, void *hip_stream, int32_t n_grid, int
     if (!work_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (int rc = bispec_check_grid(n_grid)) return rc;
     if (ncols < 1 || ncols > n_grid) return fail(BFGX_ERR_INVALID, "slab of %d columns: 1 <= ncols <= n_grid", ncols);
-    if (int rc = bispec_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fourier_check_aligned(work_dev, "work_dev")) return rc;
     if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
@@ -226,12 +137,11 @@ int bfgx_ifft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, i
     if (!work_dev || !map_out_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (int rc = bispec_check_grid(n_grid)) return rc;
     if (planes < 1 || planes > n_grid || ((int64_t)planes * n_grid) % 2) return fail(BFGX_ERR_INVALID, "slab of %d planes: 1 <= planes <= n_grid", planes);
-    if (int rc = bispec_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fourier_check_aligned(work_dev, "work_dev")) return rc;
     if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     if (int rc = fft_setup(device, n_grid, 1.0, 1, &f)) return rc;
-    if (int rc = bispec_kernel_attrs(device)) return rc;
     const int pitch = fft_pitch(n_grid);
     if (int rc = fft_conj(*f, s, (double2 *)work_dev, (int64_t)planes * n_grid * pitch)) return rc;
     return ifft_planes_conj(*f, s, n_grid, planes, (double2 *)work_dev, map_out_dev, pitch);
@@ -239,7 +149,7 @@ int bfgx_ifft_slab_planes_device(int device, void *hip_stream, int32_t n_grid, i
 
 int64_t bfgx_bispectrum_work_doubles(int32_t n_grid, int32_t nbins)
 {
-    if (n_grid > 1024 || ilog2_exact(n_grid) < 3 || nbins < 1 || nbins > kBispecMaxBins) return 0;
+    if (!fourier_grid_ok(n_grid, kFft3MaxN) || nbins < 1 || nbins > kBispecMaxBins) return 0;
     return BispecWork(n_grid, nbins).total;
 }
 
@@ -249,14 +159,13 @@ int bfgx_bispectrum_shell_fields_device(int device, void *hip_stream, int32_t n_
     if (!k_edges_host || !spec_dev || !scratch_spec_dev || !fields_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (int rc = bispec_check_grid(n_grid)) return rc;
     if (int rc = bispec_check_bins(L, nbins, k_edges_host)) return rc;
-    if (int rc = bispec_check_aligned(spec_dev, "spec_dev")) return rc;
-    if (int rc = bispec_check_aligned(scratch_spec_dev, "scratch_spec_dev")) return rc;
+    if (int rc = fourier_check_aligned(spec_dev, "spec_dev")) return rc;
+    if (int rc = fourier_check_aligned(scratch_spec_dev, "scratch_spec_dev")) return rc;
     if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     BispecSetup *bs = nullptr;
     if (int rc = fft_setup(device, n_grid, 1.0, 1, &f)) return rc;
-    if (int rc = bispec_kernel_attrs(device)) return rc;
     if (int rc = bispec_setup(device, n_grid, L, nbins, k_edges_host, &bs)) return rc;
     return bispec_fields(*f, *bs, s, n_grid, nbins, (const double2 *)spec_dev, unit, (double2 *)scratch_spec_dev, fields_dev);
 }
@@ -270,33 +179,29 @@ int bfgx_bispectrum_device(int device, void *hip_stream, int32_t n_grid, const d
     if (int rc = bispec_check_grid(n_grid)) return rc;
     if (int rc = bispec_check_bins(L, nbins, k_edges_host)) return rc;
     if (int rc = bispec_check_triangles(nbins, ntri, tri_host)) return rc;
-    if (int rc = bispec_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fourier_check_aligned(work_dev, "work_dev")) return rc;
     if (int rc = select_device(device)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     FftSetup *f = nullptr;
     BispecSetup *bs = nullptr;
     if (int rc = fft_setup(device, n_grid, 1.0, 1, &f)) return rc;
-    if (int rc = bispec_kernel_attrs(device)) return rc;
     if (int rc = bispec_setup(device, n_grid, L, nbins, k_edges_host, &bs)) return rc;
     const int N = n_grid, pitch = fft_pitch(N);
     const BispecWork w(N, nbins);
     double2 *spec = (double2 *)(work_dev + w.spec), *scratch = (double2 *)(work_dev + w.scratch);
     double *fields = work_dev + w.fields, *partials = work_dev + w.partials;
     uint32_t *ent_dev = (uint32_t *)(work_dev + w.ent);
-    {
-        // the terms: the triangles, then (i, i, ones) for the diagonal sums; the copy is ordered on the stream before its readers
-        std::lock_guard<std::mutex> lk(g_bispec_mu);
-        bs->ent.resize((size_t)ntri + nbins);
-        for (int t = 0; t < ntri; ++t)
-            bs->ent[t] = (uint32_t)tri_host[3 * t] | (uint32_t)tri_host[3 * t + 1] << 8 | (uint32_t)tri_host[3 * t + 2] << 16;
-        for (int i = 0; i < nbins; ++i) bs->ent[ntri + i] = (uint32_t)i | (uint32_t)i << 8 | (uint32_t)nbins << 16;
-        HIP_TRY(hipMemcpyAsync(ent_dev, bs->ent.data(), sizeof(uint32_t) * bs->ent.size(), hipMemcpyHostToDevice, s));
-    }
     // the full half spectrum, kept
     if (int rc = fft_planes(*f, s, N, N, map_dev, spec, pitch)) return rc;
     if (int rc = fft_axis0_store(*f, s, N, N, spec, pitch)) return rc;
     // sweep 1: the data fields I_i; sweep 2: the unit fields U_i in the same buffers
     if (int rc = bispec_fields(*f, *bs, s, N, nbins, spec, 0, scratch, fields)) return rc;
+    // the terms: the triangles, then (i, i, ones) for the diagonal sums.  Uploaded here, behind work that keeps the device busy meanwhile
+    // and before its first reader
+    std::vector<uint32_t> ent((size_t)ntri + nbins);
+    for (int t = 0; t < ntri; ++t) ent[t] = (uint32_t)tri_host[3 * t] | (uint32_t)tri_host[3 * t + 1] << 8 | (uint32_t)tri_host[3 * t + 2] << 16;
+    for (int i = 0; i < nbins; ++i) ent[ntri + i] = (uint32_t)i | (uint32_t)i << 8 | (uint32_t)nbins << 16;
+    if (int rc = upload_owned(s, ent_dev, std::move(ent))) return rc;
     if (int rc = bispec_sums(*f, s, N, nbins, fields, ent_dev, ntri, partials, b_sum_dev, pk_sum_dev)) return rc;
     if (int rc = bispec_fields(*f, *bs, s, N, nbins, spec, 1, scratch, fields)) return rc;
     return bispec_sums(*f, s, N, nbins, fields, ent_dev, ntri, partials, n_tri_dev, n_modes_dev);

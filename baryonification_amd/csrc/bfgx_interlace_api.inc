@@ -1,6 +1,6 @@
 // C ABI of the interlaced power spectrum of two grids displaced by half a cell, and of P(k) straight from particle columns
-// (include/bfgx.h, "interlaced power spectrum"); included by bfgx_api.hip after bfgx_xpk_api.inc (xpk_check_shape, xpk_window,
-// fft_axis0_xpk) and bfgx_deposit_cloud_api.inc (deposit_cloud_impl).  Kernels: BIN 5 of fft_c2c_strided_kernel (the twisted store of grid
+// (include/bfgx.h, "interlaced power spectrum"); included by bfgx_api.hip after bfgx_fourier_host.inc (FftSetup, the transform passes,
+// the table cache), bfgx_xpk_api.inc (xpk_check_shape, xpk_window, fft_axis0_xpk) and bfgx_deposit_cloud_api.inc (deposit_cloud_impl).  Kernels: BIN 5 of fft_c2c_strided_kernel (the twisted store of grid
 // 1) and interlace_combine_kernel in bfgx_fft.hpp; the shifted deposit in bfgx_deposit_cloud.hpp.
 //
 // With F1, F2 the transforms of the two grids, the combined coefficient is C = (F1 + Phi F2) / 2, Phi = phi[a] phi[b] phi[c], and
@@ -14,47 +14,21 @@ namespace {
 // value keeps the combined field real, which the half spectrum's double count of the modes 0 < c < N/2 needs).  The kernel looks the
 // product phi[a] phi[b] phi[c] up by the sum of the three wave numbers, the Nyquist index counted as 0 (twist_wave_number): the table is
 // phase[j] = exp(+i pi j / N), j < 2N.  Per (device, n_grid), built in long double like the twiddles, kept until bfgx_cache_clear.
-std::mutex g_interlace_mu;
-std::map<std::tuple<int, int>, DevBuf *> g_interlace_phi;
+FourierCache<DevBuf, int> g_interlace_phi;
 
 int interlace_phi(int device, int N, const double2 **out)
 {
-    std::lock_guard<std::mutex> lk(g_interlace_mu);
-    const auto key = std::make_tuple(device, N);
-    auto it = g_interlace_phi.find(key);
-    if (it == g_interlace_phi.end()) {
-        std::vector<double> t(4 * (size_t)N);
-        const long double pi = 3.141592653589793238462643383279502884L;
-        for (int j = 0; j < 2 * N; ++j) {
-            const long double x = pi * (long double)(j < N ? j : j - 2 * N) / (long double)N;       // (|x| <= pi)
-            t[2 * j] = (double)cosl(x);
-            t[2 * j + 1] = (double)sinl(x);
-        }
+    DevBuf *b = nullptr;
+    const int rc = g_interlace_phi.get(std::make_tuple(device, N), &b, [&](DevBuf &buf) {
+        std::vector<double> t;
+        unit_circle(t, 2 * N, 0, N, +1);                                                          // (|angle| <= pi)
+        unit_circle(t, 2 * N, -N, N, +1);
         t[0] = 1.0; t[1] = 0.0; t[2 * N] = -1.0; t[2 * N + 1] = 0.0;                              // 1, -1, i and -i exactly
         t[N] = 0.0; t[N + 1] = 1.0; t[3 * N] = 0.0; t[3 * N + 1] = -1.0;
-        DevBuf *b = new DevBuf();
-        if (b->up(t.data(), sizeof(double) * t.size())) { delete b; return alloc_fail("interlacing phase table"); }
-        it = g_interlace_phi.emplace(key, b).first;
-    }
-    *out = it->second->as<double2>();
-    return BFGX_OK;
-}
-
-void interlace_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_interlace_mu);
-    for (auto &kv : g_interlace_phi) { (void)hipSetDevice(std::get<0>(kv.first)); delete kv.second; }
-    g_interlace_phi.clear();
-}
-
-// fft_axis0_store with the twist: F [N][N][pitch] after the plane passes -> 2 F1 conj(Phi)
-int fft_axis0_store_twisted(FftSetup &f, hipStream_t s, int N, double2 *F, int pitch, const double2 *phi)
-{
-    const int64_t ntiles = (int64_t)f.ztiles * N;
-    const unsigned wgs = (unsigned)std::min<int64_t>(ntiles, (int64_t)f.n_cu * std::max<size_t>(1, (size_t)(160 * 1024) / f.lds));
-    if (int rc = f.twist_launch(s, wgs, F, N, (int64_t)N * pitch, (int64_t)pitch, N, 0, phi)) return rc;
-    HIP_TRY(hipGetLastError());
-    return BFGX_OK;
+        return buf.up(t.data(), sizeof(double) * t.size()) ? alloc_fail("interlacing phase table") : BFGX_OK;
+    });
+    if (rc == BFGX_OK) *out = b->as<double2>();
+    return rc;
 }
 
 // the two grids -> p_sum, p1_sum, k_sum, counts (arguments checked by the callers; the device is selected)
@@ -70,9 +44,9 @@ int interlaced_enqueue(int device, hipStream_t s, int N, const double *map1, con
     const int pitch = fft_pitch(N);
     double2 *spec_a = (double2 *)work, *work_b = spec_a + (int64_t)N * N * pitch;
     if (int rc = fft_planes(*f, s, N, N, map1, spec_a, pitch)) return rc;
-    if (int rc = fft_axis0_store_twisted(*f, s, N, spec_a, pitch, phi)) return rc;
+    if (int rc = fft_axis0_store<5>(*f, s, N, N, spec_a, pitch, TwistArgs{phi})) return rc;
     if (int rc = fft_planes(*f, s, N, N, map2, work_b, pitch)) return rc;
-    if (int rc = fft_axis0_xpk(*f, s, N, N, 0, spec_a, work_b, pitch, nk, win, p1_sum, p_sum, p_sum, k_sum, counts)) return rc;
+    if (int rc = fft_axis0_xpk(*f, s, N, N, 0, spec_a, work_b, pitch, win, p1_sum, p_sum, p_sum, k_sum, counts)) return rc;
     hipLaunchKernelGGL(interlace_combine_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, nk, p_sum, p1_sum);
     HIP_TRY(hipGetLastError());
     return BFGX_OK;
@@ -108,7 +82,7 @@ int bfgx_interlaced_power_spectrum_device(int device, void *hip_stream, int32_t 
 {
     if (!map1_dev || !map2_dev || !work_dev || !p_sum_dev || !p1_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (int rc = xpk_check_shape(n_grid, L, nk, window_order)) return rc;
-    if (int rc = xpk_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fourier_check_aligned(work_dev, "work_dev")) return rc;
     if (int rc = select_device(device)) return rc;
     return interlaced_enqueue(device, (hipStream_t)hip_stream, n_grid, map1_dev, map2_dev, L, nk, window_order, work_dev, p_sum_dev, p1_sum_dev,
                               k_sum_dev, counts_dev);
@@ -126,7 +100,7 @@ int bfgx_particle_power_spectrum_device(int device, void *hip_stream, int64_t n,
     if ((n > 0 && (!x || !y || !z)) || !work_dev || !p_sum_dev || !p1_sum_dev || !k_sum_dev || !counts_dev) return fail(BFGX_ERR_INVALID, "NULL argument");
     if (n < 0) return fail(BFGX_ERR_INVALID, "n = %lld particles", (long long)n);
     if (int rc = particle_pk_check(n_grid, L, order, interlace, nk)) return rc;
-    if (int rc = xpk_check_aligned(work_dev, "work_dev")) return rc;
+    if (int rc = fourier_check_aligned(work_dev, "work_dev")) return rc;
     // work: map 1, map 2, the two half spectra (n_grid^3 is a multiple of 2 doubles, so the spectra stay 16-byte aligned)
     const int64_t npts = (int64_t)n_grid * n_grid * n_grid;
     double *map1 = work_dev, *map2 = map1 + npts, *spectra = map2 + npts;
@@ -144,7 +118,7 @@ int bfgx_particle_power_spectrum(int device, int64_t n, const double *x, const d
     if (n < 0) return fail(BFGX_ERR_INVALID, "n = %lld particles", (long long)n);
     if (int rc = particle_pk_check(n_grid, L, order, interlace, nk)) return rc;
     HostCall c(device);
-    std::vector<double> h(3 * (size_t)nk);                   // the bins' sums (combined, grid 1, |k|), divided by their counts below
+    std::vector<double> h(3 * (size_t)nk);                   // the bins' sums (combined, grid 1, |k|)
     std::vector<unsigned long long> hc(nk);
     const double *dx = c.in(x, n), *dy = c.in(y, n), *dz = c.in(z, n), *dm = mass ? c.in(mass, n) : nullptr;
     double *dw = c.scratch<double>((size_t)bfgx_particle_power_spectrum_work_doubles(n_grid));
@@ -154,13 +128,7 @@ int bfgx_particle_power_spectrum(int device, int64_t n, const double *x, const d
     if (int rc = bfgx_particle_power_spectrum_device(device, nullptr, n, dx, dy, dz, dm, n_grid, L, order, interlace, nk, dw, ds, ds + nk, ds + 2 * nk, dc))
         return rc;
     if (int rc = c.finish()) return rc;
-    for (int i = 0; i < nk; ++i) {
-        const double m = (double)hc[i];                      // 0 / 0 -> NaN for empty bins, as in bfgx_power_spectrum
-        counts[i] = (int64_t)hc[i];
-        pk[i] = h[i] / m;
-        pk_grid1[i] = h[nk + i] / m;
-        kcen[i] = h[2 * (size_t)nk + i] / m;
-    }
+    bin_means(nk, h, hc, counts, {pk, pk_grid1, kcen});
     return BFGX_OK;
 }
 

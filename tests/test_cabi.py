@@ -88,6 +88,25 @@ def test_null_arguments_are_refused_before_any_device_call():
     assert L.bfgx_power_spectrum_device(0, None, 64, None, 100.0, 10, None, None, None, None) == _lib.ERR_INVALID
 
 
+@pytest.mark.parametrize('n_grid', [7, 12, 2048])
+def test_power_spectrum_device_entries_check_n_grid_before_any_device_call(n_grid):
+    """the three 3-D P(k) _device entries refuse a bad n_grid as bfgx_power_spectrum does, code and message, before the device is
+    selected: host arrays stand in the device slots, and nothing may touch them with or without a device"""
+    import ctypes as C
+    L = _lib.load()
+    host = np.zeros(64)
+    p = host.ctypes.data_as(C.c_void_p)
+    assert L.bfgx_power_spectrum(0, n_grid, p, 100.0, 4, p, p, p) == _lib.ERR_UNSUPPORTED
+    msg = L.bfgx_last_error()
+    assert b'power spectrum needs n_grid = 2^m with 8 <= n_grid <= 1024' == msg
+    for rc in (L.bfgx_power_spectrum_device(0, None, n_grid, p, 100.0, 4, p, p, p, p),
+               L.bfgx_fft_slab_planes_device(0, None, n_grid, 2, p, p),
+               L.bfgx_fft_slab_axis0_pk_device(0, None, n_grid, 1, 0, p, 100.0, 4, p, p, p)):
+        assert rc == _lib.ERR_UNSUPPORTED
+        assert L.bfgx_last_error() == msg
+    assert not host.any()
+
+
 def test_round5_entries_refuse_bad_arguments_before_any_device_call():
     """the entries added in round 5 (one-call snapshot -> map, per-halo callable bridge, fused band entry) check their arguments first"""
     import ctypes as C

@@ -390,3 +390,34 @@ def test_normalize(gpu):
     assert np.array_equal(nrm['B'], raw['B'] * (L_BOX ** 6 / float(N) ** 9))
     assert np.array_equal(nrm['pk'], raw['pk'] * (L_BOX ** 3 / float(N) ** 6))
     assert np.array_equal(_bits(nrm['n_tri']), _bits(raw['n_tri']))
+
+
+def test_two_threads_with_their_own_triangle_lists(gpu):
+    """the packed terms of a call are uploaded from a copy of the call's own: two threads on one cached N = 16 setup, each four calls
+    with a list of its own (one triangle; all triangles of the first 3 bins), meet the brute-force sums of their list.  The sums are
+    atomic, so they are held to test_estimator_against_brute_force's tolerance, not to the bit."""
+    import threading
+    N = 16
+    edges, tris, est, bru = references(N)
+    tris = np.asarray(tris)
+    lists = [np.array([len(tris) // 2]), np.flatnonzero((tris < 3).all(axis=1))]
+    assert len(lists[0]) == 1 and len(lists[1]) > 1
+    Map = noise_map(N)
+    gate, got = threading.Barrier(2), [[], []]
+
+    def calls(t):
+        gate.wait()
+        for _ in range(4):
+            got[t].append(_raw(Map, edges, tris[lists[t]], N))
+
+    threads = [threading.Thread(target=calls, args=(t,)) for t in range(2)]
+    for th in threads: th.start()
+    for th in threads: th.join()
+    for t in range(2):
+        sel = lists[t]
+        assert len(got[t]) == 4
+        for b_sum, n_tri, pk_sum, n_modes in got[t]:
+            assert (np.abs(b_sum - bru['b_sum'][sel]) / est['abs_sum'][sel]).max() <= _bound_sum(N)
+            assert (np.abs(pk_sum - bru['pk_sum']) / bru['pk_sum']).max() <= _bound_sum(N)
+            assert np.array_equal(np.rint(n_tri).astype(np.int64), bru['n_tri'][sel])
+            assert np.array_equal(np.rint(n_modes).astype(np.int64), bru['n_modes'])

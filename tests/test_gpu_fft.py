@@ -7,6 +7,8 @@
   3. bin edges through engine.power_spectrum at shapes where the reciprocal floor and the division floor differ
      (test_fft_oracle_host.py shows that they do)
   4. cached setups called in the order large, small, large (the dynamic-LDS attribute is per instantiation, the setups per shape)
+  5. the shared Fourier host code: one owner of the attributes across the 2-D and 3-D families, the lazy bin table built once by two
+     threads, one release of all five caches
 
 Bound (fft_oracle.bound): max|got - ref| / max|ref| <= 16 x numpy's own error against the long-double DFT at the same N, i.e. about
 5e-15.  Both are O(eps log N) fp64 recursions with other radices and twiddle sources; 16 is the margin the mode-coupling tests give a
@@ -19,11 +21,10 @@ Measured on the MI355X, max|got - ref| / max|ref| of the plane passes, worst of 
   impulse    2.3e-16  2.7e-16  2.7e-16  3.6e-16  5.4e-16  6.9e-16  7.2e-16  8.7e-16
   wave       1.1e-16  1.1e-16  7.5e-17  7.9e-17  1.1e-16  1.1e-16  1.1e-16  5.8e-17
 binned axis-0 pass, |F|^2 sums per bin against long-double sums: at most 1.4e-15 (N = 1024, nk = 255), mostly 3e-16 to 1e-15.
-Large, small, large: the runtime does not refuse the launch of a cached large setup after a smaller one lowered the kernel's dynamic-LDS
-attribute; all calls return and repeat their results.  The file takes 21 s, 12 of them the first call's start-up of the runtime.
+Large, small, large: every instantiation has its dynamic-LDS attribute set once per device to the most any shape asks of it; all
+calls return and repeat their results.  The file takes 21 s, 12 of them the first call's start-up of the runtime.
 
-Not covered: the NT == 1024 instantiations of fft_c2c_strided_kernel.  FftSetup::init never selects them (threads is 256 or 512), so
-no entry reaches them.  A full 1024^3 power_spectrum is not run either (17 GB of scratch): the slab entries run the same kernels at
+Not covered: a full 1024^3 power_spectrum (17 GB of scratch): the slab entries run the same kernels at
 N = 1024 on a few planes or columns."""
 import numpy as np
 import pytest
@@ -299,3 +300,92 @@ def test_cached_binned_setups_large_small_large(gpu, big, small):
     assert np.array_equal(res[0][2], res[2][2])
     if big[1] <= 254:
         assert np.array_equal(res[0][1].view(np.uint64), res[2][1].view(np.uint64))
+
+
+# ------------------------------------------------------------------------------------------------- 5. one owner of the attributes, one cache
+def _run_rfft2(x):
+    """engine.rfft2_device on a real plane [N][N] -> complex [N][N/2 + 1]"""
+    import torch
+    from baryonification_amd import engine
+    N = x.shape[0]
+    work = torch.zeros((engine.fft2_work_doubles(N),), dtype=torch.float64, device='cuda:0')
+    out = torch.zeros((N, engine.fft_pitch(N), 2), dtype=torch.float64, device='cuda:0')
+    engine.rfft2_device(_dev(x).data_ptr(), N, work.data_ptr(), out.data_ptr())
+    torch.cuda.synchronize()
+    return out.cpu().numpy().view(np.complex128)[..., 0][:, :N // 2 + 1]
+
+
+def _clear_caches():
+    import torch
+    from baryonification_amd import _lib
+    torch.cuda.synchronize()
+    _lib.load().bfgx_cache_clear()
+    return _lib.load().bfgx_debug_live_allocs()
+
+
+def test_one_attribute_owner_across_families(gpu):
+    """The 2-D and the 3-D transforms launch the same instantiations of the strided kernel, and the binned passes ask the most LDS of
+    theirs at (1024, nk 2048): in an order that mixes the families and the sizes every call launches, meets its oracle, and repeats its
+    bits."""
+    from baryonification_amd import engine
+    _clear_caches()
+    L = 91.0
+    m512, m128, p256, p512 = _noise(512, 1)[0], _noise(128, 1)[0], _noise(256, 2), _noise(512, 2)
+
+    def first_three():
+        return [_run_rfft2(m512), _run_planes(p256, 0.0)[:, :, :129], _run_planes(p512, 0.0)[:, :, :257]]
+
+    first = first_three()
+    for (N, nk) in ((1024, 2048), (1024, 8)):
+        work = _synthetic_work(N, 1, N + nk)
+        got = _run_axis0(_padded(work, engine.fft_pitch(N)), N, 1, 1, L, nk)
+        _check_axis0(got, O.axis0_pk_ref(work, N, 1, L, nk), N)
+    small = _run_rfft2(m128)
+    again = first_three()
+    for a, b in zip(first, again):
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+    assert O.rel_err(first[0], O.planes_ref(m512[None])[0]) <= O.bound(512)
+    assert O.rel_err(first[1], O.planes_ref(p256)) <= O.bound(256)
+    assert O.rel_err(first[2], O.planes_ref(p512)) <= O.bound(512)
+    assert O.rel_err(small, O.planes_ref(m128[None])[0]) <= O.bound(128)
+
+
+def test_lazy_bin_table_is_built_once_by_two_threads(gpu):
+    """two threads make the first binned call of a fresh (64, L, 20) setup at the same time: both meet the oracle, and the library owns
+    exactly one setup afterwards -- its twiddles, its k axis and the three buffers of one bin table"""
+    import threading
+    from baryonification_amd import _lib, engine
+    N, L, nk = 64, 123.25, 20
+    before = _clear_caches()
+    works = [_synthetic_work(N, 2, 900 + t) for t in range(2)]
+    devs = [_padded(w, engine.fft_pitch(N)) for w in works]
+    gate, got = threading.Barrier(2), [None, None]
+
+    def call(t):
+        gate.wait()
+        got[t] = _run_axis0(devs[t], N, 2, 3, L, nk)
+
+    threads = [threading.Thread(target=call, args=(t,)) for t in range(2)]
+    for th in threads: th.start()
+    for th in threads: th.join()
+    for t in range(2):
+        _check_axis0(got[t], O.axis0_pk_ref(works[t], N, 3, L, nk), N)
+    assert _lib.load().bfgx_debug_live_allocs() == before + 5
+    assert _clear_caches() == before
+
+
+def test_one_release_for_all_fourier_caches(gpu):
+    """one small call of every family, then bfgx_cache_clear: no device allocation of theirs is left"""
+    from baryonification_amd import engine, utils as U
+    before = _clear_caches()
+    rng = np.random.default_rng(16)
+    A, B = rng.standard_normal((16, 16, 16)), rng.standard_normal((16, 16, 16))
+    engine.power_spectrum(A, 100.0, 6)
+    engine.cross_power_spectrum(A, B, 100.0, 6, window='cic')
+    engine.interlaced_power_spectrum(A, B, 100.0, 6)
+    engine.bispectrum(A, 100.0, 2 * np.pi / 100.0 * np.array([0.5, 2.5, 4.5, 6.5]))
+    U.rfft2(rng.standard_normal((8, 8)))
+    U.rfft2(rng.standard_normal((2048, 2048)))
+    from baryonification_amd import _lib
+    assert _lib.load().bfgx_debug_live_allocs() > before
+    assert _clear_caches() == before

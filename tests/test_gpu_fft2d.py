@@ -464,3 +464,33 @@ def test_residency(gpu):
     c3 = Map3.power_spectrum(Nk=6)
     kc, pk, cnt = engine.power_spectrum(cube, 32.0, 6)
     assert set(c3) == {'k', 'pk', 'counts'} and np.array_equal(c3['counts'], cnt) and np.allclose(c3['pk'], pk, rtol=1e-12, equal_nan=True)
+
+
+def test_two_threads_filter_one_resident_map_with_their_own_tables(gpu):
+    """the beam table of a call is uploaded from a copy of the call's own: two threads on one cached N = 64 setup, each four calls with
+    a table of its own (16 and 33 nodes), get bit for bit what the same call gives alone"""
+    import threading
+    from baryonification_amd import utils as U
+    N, L = 64, 45.0
+    x = _dev(F.noise(N, 9))
+    kmax = F.k_plane(N, L).max()
+    beams = []
+    for nodes, width in ((16, 1.1), (33, 3.7)):
+        tk = np.linspace(0.0, 0.8 * kmax, nodes)
+        beams.append((tk, 1.0 / (1.0 + (tk * width) ** 2)))
+    alone = [U.smoothing_2d(x, L, beam=b).cpu().numpy() for b in beams]
+    assert not np.array_equal(alone[0], alone[1])
+    gate, got = threading.Barrier(2), [[], []]
+
+    def calls(t):
+        gate.wait()
+        for _ in range(4):
+            got[t].append(U.smoothing_2d(x, L, beam=beams[t]).cpu().numpy())
+
+    threads = [threading.Thread(target=calls, args=(t,)) for t in range(2)]
+    for th in threads: th.start()
+    for th in threads: th.join()
+    for t in range(2):
+        assert len(got[t]) == 4
+        for g in got[t]:
+            assert np.array_equal(g.view(np.uint64), alone[t].view(np.uint64))
