@@ -7,11 +7,9 @@ same `process()` return value (float64 map of shape (Npix,)) and the same except
 `process()` does no per-halo work in Python: the catalog, the shell and the model's raw table go
 through the C ABI (include/bfgx.h) to the HIP kernels in csrc/.  There is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _tensors
 from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
 from ..utils.pixelfunc import scatter_add
@@ -174,8 +172,7 @@ class BaryonifyShell(DefaultRunner):
 
         def call(cat):
             opts.catalog_token = self._catalog_token
-            _lib.check(_lib.load().bfgx_baryonify_shell(C.byref(cat), C.byref(model), nside, orig_map.ctypes.data,
-                                                        new_map.ctypes.data, C.byref(opts), C.byref(stats)))
+            _lib.call('bfgx_baryonify_shell', cat, model, nside, orig_map.ctypes.data, new_map.ctypes.data, opts, stats)
         self._call_with_catalog(p_keys, call)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep
@@ -203,7 +200,7 @@ class PaintProfilesShell(DefaultRunner):
 
         def call(cat):
             opts.catalog_token = self._catalog_token
-            _lib.check(_lib.load().bfgx_paint_shell(C.byref(cat), C.byref(model), nside, new_map.ctypes.data, C.byref(opts), C.byref(stats)))
+            _lib.call('bfgx_paint_shell', cat, model, nside, new_map.ctypes.data, opts, stats)
         self._call_with_catalog(p_keys, call)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep
@@ -258,7 +255,6 @@ class MeasureProfilesShell(DefaultRunner):
         model, keep = _placeholder_model(self, cosmo_to_dict(self.cosmo))
         edges, nb = self.r_edges, self.r_edges.size - 1
         n = int(self.HaloLightConeCatalog.cat.size)
-        lib = _lib.load()
         if all(on_dev):
             import torch
             dev = maps[0].device
@@ -267,12 +263,11 @@ class MeasureProfilesShell(DefaultRunner):
                     raise ValueError("device maps must be 1-D float64 tensors of 12 NSIDE^2 pixels on one device")
             maps = [x.contiguous() for x in maps]
             outs, optr = alloc_profile_outs(n, nb, pair, dev)
-            ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
+            ptr = [x.data_ptr() for x in maps] + [None] * (3 - len(maps))
 
             def call(cat):
-                _lib.check(lib.bfgx_shell_profiles_device(dev.index or 0, stream, C.byref(cat), C.byref(model), nside, ptr[0], ptr[1], ptr[2], nb,
-                                                          edges.ctypes.data, int(self.scaled), *optr))
+                _lib.call('bfgx_shell_profiles_device', _tensors.device_index(dev), _tensors.stream(dev), cat, model, nside, ptr[0], ptr[1],
+                          ptr[2], nb, edges.ctypes.data, self.scaled, *optr)
         else:
             maps = [_lib.f8(x).reshape(-1) for x in maps]
             if maps[0].size != 12 * nside * nside:
@@ -281,8 +276,7 @@ class MeasureProfilesShell(DefaultRunner):
             ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
 
             def call(cat):
-                _lib.check(lib.bfgx_shell_profiles(C.byref(cat), C.byref(model), nside, ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,
-                                                   int(self.scaled), int(self.device), *optr))
+                _lib.call('bfgx_shell_profiles', cat, model, nside, ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data, self.scaled, self.device, *optr)
         self._call_with_catalog([], call)
         del keep
         return ShellProfiles(edges.copy(), *outs, scaled=self.scaled)

@@ -18,11 +18,9 @@ Not built: `PaintProfilesAnisGrid` (:820-942).
 around the halos, with the constructor keywords, the (n_halo, n_bins) results and the `stack()` of MeasureProfilesShell and
 MeasureProfilesSnapshot (csrc/bfgx_grid_stack.hpp).
 """
-import ctypes as C
-
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _tensors
 from ..utils.cosmology import MassDef
 from ..utils.Tabulate import ParamTabulatedProfile
 from ._model import _placeholder_model, build_model, process_grid_exact, wants_exact
@@ -42,9 +40,7 @@ def _regrid(grid, pix_positions, pix_values, ndim, device=0):
     val = _lib.f8(pix_values)
     if pos.shape != (val.size, ndim):
         raise ValueError("pix_positions must have shape (N, %d)" % ndim)
-    rc = _lib.load().bfgx_regrid_pixels(int(device), ndim, grid.shape[0], val.size, pos.ctypes.data, val.ctypes.data,
-                                        grid.ctypes.data)
-    _lib.check(rc)
+    _lib.call('bfgx_regrid_pixels', device, ndim, grid.shape[0], val.size, pos.ctypes.data, val.ctypes.data, grid.ctypes.data)
 
 
 def regrid_pixels_2D(grid, pix_positions, pix_values):
@@ -173,9 +169,7 @@ class BaryonifyGrid(DefaultRunnerGrid):
         new_map = _lib.pinned_empty(orig_map.size).reshape(orig_map.shape)     # page-locked and pooled: the copy back runs at the PCIe rate
         opts = _lib.bfgx_opts(int(self.device), 1, 1, 1, 1, 0)
         stats = _lib.bfgx_stats()
-        rc = _lib.load().bfgx_baryonify_grid(C.byref(cat), C.byref(model), C.byref(grid), orig_map.ctypes.data,
-                                             new_map.ctypes.data, C.byref(opts), C.byref(stats))
-        _lib.check(rc)
+        _lib.call('bfgx_baryonify_grid', cat, model, grid, orig_map.ctypes.data, new_map.ctypes.data, opts, stats)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep, cols, gkeep
         return new_map
@@ -203,9 +197,7 @@ class PaintProfilesGrid(DefaultRunnerGrid):
         new_map = _lib.pinned_empty(int(np.prod(self.GriddedMap.map.shape))).reshape(self.GriddedMap.map.shape)
         opts = _lib.bfgx_opts(int(self.device), 1, 1, 0, 1, 0)
         stats = _lib.bfgx_stats()
-        rc = _lib.load().bfgx_paint_grid(C.byref(cat), C.byref(model), C.byref(grid), new_map.ctypes.data, C.byref(opts),
-                                         C.byref(stats))
-        _lib.check(rc)
+        _lib.call('bfgx_paint_grid', cat, model, grid, new_map.ctypes.data, opts, stats)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep, cols, gkeep
         return new_map
@@ -317,7 +309,6 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
         c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if G.is2D else hcat['z'])
         grid, gkeep = self._grid()
         edges, nb, n = self.r_edges, self.r_edges.size - 1, int(hcat.size)
-        lib = _lib.load()
         if all(on_dev):
             import torch
             dev = maps[0].device
@@ -325,10 +316,9 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
                 if x.dtype != torch.float64 or tuple(x.shape) != self.shape or x.device != dev or not x.is_contiguous():
                     raise ValueError("device maps must be C-contiguous float64 tensors of shape %s on one device" % (self.shape,))
             outs, optr = alloc_profile_outs(n, nb, pair, dev)
-            ptr = [C.c_void_p(x.data_ptr()) for x in maps] + [None] * (3 - len(maps))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
-            _lib.check(lib.bfgx_grid_profiles_device(dev.index or 0, stream, C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2],
-                                                     nb, edges.ctypes.data, int(self.scaled), *optr))
+            ptr = [x.data_ptr() for x in maps] + [None] * (3 - len(maps))
+            _lib.call('bfgx_grid_profiles_device', _tensors.device_index(dev), _tensors.stream(dev), c, model, grid, ptr[0], ptr[1], ptr[2], nb,
+                      edges.ctypes.data, self.scaled, *optr)
         else:
             maps = [_lib.f8(x) for x in maps]
             for x in maps:
@@ -336,8 +326,7 @@ class MeasureProfilesGrid(DefaultRunnerGrid):
                     raise ValueError("the map must have the shape of the GriddedMap %s: got %s" % (self.shape, x.shape))
             outs, optr = alloc_profile_outs(n, nb, pair)
             ptr = [x.ctypes.data for x in maps] + [None] * (3 - len(maps))
-            _lib.check(lib.bfgx_grid_profiles(C.byref(c), C.byref(model), C.byref(grid), ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data,
-                                              int(self.scaled), int(self.device), *optr))
+            _lib.call('bfgx_grid_profiles', c, model, grid, ptr[0], ptr[1], ptr[2], nb, edges.ctypes.data, self.scaled, self.device, *optr)
         del keep, ckeep, gkeep
         R, R_q = self.radii()
         return GridProfiles(edges.copy(), *outs, *([None] * (5 - len(outs))), scaled=self.scaled, ndim=len(self.shape), res=float(G.bins[1] - G.bins[0]),

@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _tensors
 from ..utils.cosmology import MassDef, cosmo_to_dict
 from ._model import _placeholder_model, build_model, process_snapshot_exact, wants_exact
 from ._profiles import MAX_PROFILE_BINS, _is_cuda_tensor, check_r_edges, halo_radii, ratio      # noqa: F401 (MAX_PROFILE_BINS: importable from here)
@@ -132,11 +132,9 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
             # the records as they are: uploaded in chunks, displaced in place on the device, downloaded into the new catalog -- the host
             # neither gathers the strided columns nor scatters them back (`new_cat = cat.copy(); new_cat['x'] = ...`, SnapshotRunner.py:254-262)
             new_cat = _lib.pinned_empty(rec.size * rec.dtype.itemsize, np.uint8).view(rec.dtype) if rec.size else rec.copy()
-            rc = _lib.load().bfgx_baryonify_snapshot_records(
-                C.byref(cat), C.byref(model), 2 if is2D else 3, float(snap.L), float(self.HaloNDCatalog.redshift), rec.size,
-                rec.ctypes.data if rec.size else None, new_cat.ctypes.data if rec.size else None, rec.dtype.itemsize, fields['x'][1], fields['y'][1],
-                0 if is2D else fields['z'][1], C.byref(opts), C.byref(stats))
-            _lib.check(rc)
+            _lib.call('bfgx_baryonify_snapshot_records', cat, model, 2 if is2D else 3, snap.L, self.HaloNDCatalog.redshift, rec.size,
+                      rec.ctypes.data if rec.size else None, new_cat.ctypes.data if rec.size else None, rec.dtype.itemsize, fields['x'][1],
+                      fields['y'][1], 0 if is2D else fields['z'][1], opts, stats)
             self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
             del keep, cols
             return new_cat
@@ -146,9 +144,7 @@ class BaryonifySnapshot(DefaultRunnerSnapshot):
                                float(snap.L), float(self.HaloNDCatalog.redshift))
         ox, oy = np.empty_like(x), np.empty_like(y)
         oz = None if is2D else np.empty_like(z)
-        rc = _lib.load().bfgx_baryonify_snapshot(C.byref(cat), C.byref(model), C.byref(s), ox.ctypes.data, oy.ctypes.data,
-                                                 None if is2D else oz.ctypes.data, C.byref(opts), C.byref(stats))
-        _lib.check(rc)
+        _lib.call('bfgx_baryonify_snapshot', cat, model, s, ox.ctypes.data, oy.ctypes.data, None if is2D else oz.ctypes.data, opts, stats)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         new_cat = snap.cat.copy()
         new_cat['x'], new_cat['y'] = ox, oy
@@ -266,7 +262,6 @@ class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
         c, ckeep = _lib.make_grid_catalog_host(hcat['M'], hcat['x'], hcat['y'], None if is2D else hcat['z'])
         edges, nb, n = self.r_edges, self.r_edges.size - 1, int(hcat.size)
         L, zr = float(snap.L), float(self.HaloNDCatalog.redshift)
-        lib = _lib.load()
         if isinstance(cat, (tuple, list)):
             import torch
             cols = list(cat)
@@ -284,11 +279,9 @@ class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
             has_w = len(cols) > ndim
             out_n = torch.empty((n, nb), dtype=torch.int64, device=dev)
             out_s = torch.empty((n, nb), dtype=torch.float64, device=dev) if has_w else None
-            ptr = [C.c_void_p(t.data_ptr()) for t in cols[:ndim]] + [None] * (3 - ndim)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
-            _lib.check(lib.bfgx_snapshot_profiles_device(dev.index or 0, stream, C.byref(c), C.byref(model), ndim, L, zr, npart, ptr[0], ptr[1], ptr[2],
-                                                         C.c_void_p(cols[ndim].data_ptr()) if has_w else None, nb, edges.ctypes.data, int(self.scaled),
-                                                         C.c_void_p(out_n.data_ptr()), C.c_void_p(out_s.data_ptr()) if has_w else None))
+            ptr = [t.data_ptr() for t in cols[:ndim]] + [None] * (3 - ndim)
+            _lib.call('bfgx_snapshot_profiles_device', _tensors.device_index(dev), _tensors.stream(dev), c, model, ndim, L, zr, npart, ptr[0], ptr[1],
+                      ptr[2], cols[ndim].data_ptr() if has_w else None, nb, edges.ctypes.data, self.scaled, out_n.data_ptr(), _tensors.ptr(out_s))
         else:
             rec = snap.cat if cat is None else cat
             x, y = _lib.f8(rec['x']), _lib.f8(rec['y'])
@@ -302,8 +295,8 @@ class MeasureProfilesSnapshot(DefaultRunnerSnapshot):
             s = _lib.bfgx_snapshot(ndim, 0, x.size, x.ctypes.data, y.ctypes.data, None if is2D else z.ctypes.data, L, zr)
             out_n = np.empty((n, nb), dtype=np.int64)                 # (every cell is written by the library: no zero-fill)
             out_s = None if w is None else np.empty((n, nb), dtype=np.float64)
-            _lib.check(lib.bfgx_snapshot_profiles(C.byref(c), C.byref(model), C.byref(s), None if w is None else w.ctypes.data, nb, edges.ctypes.data,
-                                                  int(self.scaled), int(self.device), out_n.ctypes.data, None if w is None else out_s.ctypes.data))
+            _lib.call('bfgx_snapshot_profiles', c, model, s, _tensors.ptr(w), nb, edges.ctypes.data, self.scaled, self.device, out_n.ctypes.data,
+                      _tensors.ptr(out_s))
         del keep, ckeep
         R, R_q = self.radii()
         return SnapshotProfiles(edges.copy(), out_n, out_s, self.scaled, ndim, R, R_q)

@@ -2,17 +2,12 @@
 What MeasureProfilesShell, MeasureProfilesSnapshot and MeasureProfilesGrid share in Python: the check of `r_edges`, the quotient with NaN
 for an empty bin, the result class of the two map measurements, the halo radii of the two box measurements, the result arrays.
 """
-import ctypes as C
-
 import numpy as np
 
+from .._tensors import is_cuda_tensor as _is_cuda_tensor, ptr
 from ..utils.cosmology import Cosmology, MassDef, massdef_to_tuple
 
 MAX_PROFILE_BINS = 64          # csrc/bfgx_stack_core.hpp kStackMaxBins: the bins of a halo live on chip
-
-
-def _is_cuda_tensor(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
 
 
 def check_r_edges(r_edges):
@@ -95,9 +90,7 @@ def alloc_profile_outs(n, nb, shear, device=None):
     kinds = 'ififf' if shear else 'if'
     if device is None:
         outs = [np.zeros((n, nb), dtype=(np.int64 if k == 'i' else np.float64)) for k in kinds]
-        optr = [o.ctypes.data for o in outs]
     else:
         import torch
         outs = [torch.empty((n, nb), dtype=(torch.int64 if k == 'i' else torch.float64), device=device) for k in kinds]
-        optr = [C.c_void_p(o.data_ptr()) for o in outs]
-    return outs, optr + [None] * (5 - len(outs))
+    return outs, [ptr(o) for o in outs] + [None] * (5 - len(outs))

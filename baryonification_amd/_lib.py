@@ -356,6 +356,48 @@ MATH_FN_TWO_RESULTS = ('sincos_small', 'sincos_small_kreg', 'sincos_bounded', 's
 
 _lib = None
 
+# ---- call(): arguments converted once, from the declared signature -------------------------------------------------
+# c_int entries whose result is a number, not a bfgx_status (include/bfgx.h; int32_t is c_int here, hence the last two)
+NOT_STATUS = frozenset(('bfgx_abi_version', 'bfgx_device_count', 'bfgx_fft_pitch', 'bfgx_mapstats_moment_terms'))
+_calls = {}            # symbol -> (function, one converter per argument, result is a status); filled by load()
+
+
+def _pointer(x):
+    """an address as ctypes takes it: 0 and None are NULL; a ctypes array or handle passes as it is"""
+    return x if x is None or isinstance(x, (C.Array, C.c_void_p)) else int(x) or None
+
+
+def _by_ref(x):
+    return C.byref(x) if isinstance(x, C.Structure) else x
+
+
+def _as_is(x):
+    return x
+
+
+def _converter(t):
+    if t is C.c_void_p:
+        return _pointer
+    if t is C.c_double:
+        return float
+    if issubclass(t, C._Pointer):        # a struct goes by reference; out-arguments (byref(c_int64) ...) and arrays pass as they are
+        return _by_ref if issubclass(t._type_, C.Structure) else _as_is
+    return int
+
+
+def call(name, *args):
+    """the entry `name` of libbfgx called with plain arguments (tensor.data_ptr(), array.ctypes.data, numpy scalars, struct instances); a status is
+    mapped to its exception (check), any other result is returned"""
+    try:
+        fn, conv, status = _calls[name]
+    except KeyError:
+        load()
+        fn, conv, status = _calls[name]
+    if len(args) != len(conv):
+        raise TypeError("%s takes %d arguments (%d given)" % (name, len(conv), len(args)))
+    rc = fn(*[c(a) for c, a in zip(conv, args)])
+    return check(rc) if status else rc
+
 
 def _preload_hip_runtime():
     """One process must use ONE HIP runtime.  PyTorch-ROCm wheels bundle their own libamdhip64.so (same SONAME as
@@ -387,12 +429,15 @@ def load():
                 "Build it with `make -C %s` (hipcc --offload-arch=gfx950)." % (LIB_PATH, os.path.dirname(LIB_PATH)))
         _preload_hip_runtime()
         L = C.CDLL(LIB_PATH)
+        calls = {}
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(L, name)        # AttributeError here = ABI drift between header and library
             fn.restype = res
             fn.argtypes = args
+            calls[name] = (fn, tuple(_converter(t) for t in args), res is C.c_int and name not in NOT_STATUS)
         if L.bfgx_abi_version() != ABI_VERSION:
             raise ImportError("libbfgx.so ABI version %d != %d (a stale build? run `make -C baryonification_amd/csrc`)" % (L.bfgx_abi_version(), ABI_VERSION))
+        _calls.update(calls)
         _lib = L
     return _lib
 

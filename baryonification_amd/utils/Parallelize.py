@@ -648,7 +648,7 @@ class SplitJoinParallel(object):
         self.Runner, self.seed, self.backend = Runner, seed, backend
         if njobs == -1:
             from .. import _lib
-            njobs = max(1, _lib.load().bfgx_device_count()) if devices is None else len(devices)
+            njobs = max(1, _lib.call('bfgx_device_count')) if devices is None else len(devices)
         self.njobs = njobs
         self.devices = list(range(njobs)) if devices is None else [int(d) for d in devices]
         assert len(self.devices) == self.njobs, "len(devices) must equal njobs"
@@ -705,13 +705,10 @@ class SplitJoinParallel(object):
         if self.kind == 'baryonify':
             opts = _lib.bfgx_opts(0, _lib.acc_mode(acc64), 1, 1, 1, 0)
             orig_map = _lib.f8(runner.LightconeShell.map)
-            rc = _lib.load().bfgx_baryonify_shell_multi(C.byref(c), C.byref(model), nside, orig_map.ctypes.data, new_map.ctypes.data,
-                                                        self.njobs, devs, C.byref(opts), C.byref(stats))
+            _lib.call('bfgx_baryonify_shell_multi', c, model, nside, orig_map.ctypes.data, new_map.ctypes.data, self.njobs, devs, opts, stats)
         else:
             opts = _lib.bfgx_opts(0, 0, 1, 0, 1, 0)
-            rc = _lib.load().bfgx_paint_shell_multi(C.byref(c), C.byref(model), nside, new_map.ctypes.data, self.njobs, devs,
-                                                    C.byref(opts), C.byref(stats))
-        _lib.check(rc)
+            _lib.call('bfgx_paint_shell_multi', c, model, nside, new_map.ctypes.data, self.njobs, devs, opts, stats)
         self.last_stats = {k: getattr(stats, k) for k, _ in stats._fields_}
         del keep, keep_cols
         return new_map
@@ -724,7 +721,7 @@ class SimpleParallel(object):
     def __init__(self, Runner_list, njobs=-1):
         self.Runner_list = Runner_list
         from .. import _lib
-        ndev = max(1, _lib.load().bfgx_device_count())
+        ndev = max(1, _lib.call('bfgx_device_count'))
         self.njobs = ndev if njobs == -1 else min(njobs, max(ndev, 1))
 
     def process(self):

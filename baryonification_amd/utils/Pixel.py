@@ -30,8 +30,8 @@ def fftlog_transform(rs, frs, dim, mu, power_law_index, device=0):
         raise ValueError("rs should be a 1D array and frs should have len(rs) columns")
     k = np.empty_like(rs)
     out = np.empty_like(f)
-    _lib.check(_lib.load().bfgx_fftlog_transform(int(device), f.shape[0], rs.size, rs.ctypes.data, f.ctypes.data, int(dim), float(mu),
-                                                 float(power_law_index), k.ctypes.data, out.ctypes.data))
+    _lib.call('bfgx_fftlog_transform', device, f.shape[0], rs.size, rs.ctypes.data, f.ctypes.data, dim, mu, power_law_index, k.ctypes.data,
+              out.ctypes.data)
     return k, (out[0] if np.ndim(frs) == 1 else out)
 
 
@@ -41,8 +41,7 @@ def fftlog_u(rs, dim, mu, power_law_index):
     rs = _lib.f8(rs)
     u = np.empty(rs.size // 2 + 1, dtype=np.complex128)
     lnkr = C.c_double()
-    _lib.check(_lib.load().bfgx_fftlog_u(rs.size, rs.ctypes.data, int(dim), float(mu), float(power_law_index), u.ctypes.data,
-                                         C.addressof(lnkr)))
+    _lib.call('bfgx_fftlog_u', rs.size, rs.ctypes.data, dim, mu, power_law_index, u.ctypes.data, C.addressof(lnkr))
     return u, lnkr.value
 
 
@@ -52,24 +51,22 @@ def pchip_rows(x, y, q, device=0):
     if x.ndim != 1 or y2.shape[1] != x.size:
         raise ValueError("x should be a 1D array and y should have len(x) columns")
     out = np.empty((y2.shape[0], q.size))
-    _lib.check(_lib.load().bfgx_pchip_rows(int(device), y2.shape[0], x.size, x.ctypes.data, y2.ctypes.data, q.size, q.ctypes.data,
-                                           out.ctypes.data))
+    _lib.call('bfgx_pchip_rows', device, y2.shape[0], x.size, x.ctypes.data, y2.ctypes.data, q.size, q.ctypes.data, out.ctypes.data)
     return out[0] if np.ndim(y) == 1 else out
 
 
 def _kgrid(r, dim, mu, plaw):
     r = _lib.f8(r)
     k = np.empty_like(r)
-    _lib.check(_lib.load().bfgx_fftlog_kgrid(r.size, r.ctypes.data, int(dim), float(mu), float(plaw), k.ctypes.data))
+    _lib.call('bfgx_fftlog_kgrid', r.size, r.ctypes.data, dim, mu, plaw, k.ctypes.data)
     return k
 
 
 def _convolve(r_fft, prof, dim, plaw_fwd, plaw_back, window, r_eval, r_scale, device=0):
     r_fft, prof2, window, r_eval = _lib.f8(r_fft), _lib.f8(np.atleast_2d(prof)), _lib.f8(window), _lib.f8(r_eval)
     out = np.empty((prof2.shape[0], r_eval.size))
-    _lib.check(_lib.load().bfgx_fftlog_convolve(int(device), prof2.shape[0], r_fft.size, r_fft.ctypes.data, prof2.ctypes.data, int(dim), 0.0,
-                                                float(plaw_fwd), float(plaw_back), window.ctypes.data, r_eval.size, r_eval.ctypes.data,
-                                                float(r_scale), out.ctypes.data))
+    _lib.call('bfgx_fftlog_convolve', device, prof2.shape[0], r_fft.size, r_fft.ctypes.data, prof2.ctypes.data, dim, 0.0, plaw_fwd, plaw_back,
+              window.ctypes.data, r_eval.size, r_eval.ctypes.data, r_scale, out.ctypes.data)
     return out
 
 

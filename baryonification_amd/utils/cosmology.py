@@ -7,8 +7,6 @@ real pyccl objects are accepted everywhere too (duck-typed through `cosmo_to_dic
 
 Reference call sites mirrored: HealpixRunner.py:268-280, :296; BaryonCorrection.py:370.
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib
@@ -85,7 +83,7 @@ class Cosmology(object):
     def E2(self, a):
         a = _lib.f8(np.atleast_1d(a))
         out = np.empty_like(a)
-        _lib.check(_lib.load().bfgx_cosmo_E2(C.byref(self._c()), a.size, a.ctypes.data, out.ctypes.data))
+        _lib.call('bfgx_cosmo_E2', self._c(), a.size, a.ctypes.data, out.ctypes.data)
         return out
 
     def angular_diameter_distance(self, a):
@@ -93,15 +91,14 @@ class Cosmology(object):
         aa = _lib.f8(np.atleast_1d(a))
         z = 1.0 / aa - 1.0
         out = np.empty_like(z)
-        _lib.check(_lib.load().bfgx_cosmo_angular_diameter_distance(C.byref(self._c()), z.size, z.ctypes.data,
-                                                                    out.ctypes.data))
+        _lib.call('bfgx_cosmo_angular_diameter_distance', self._c(), z.size, z.ctypes.data, out.ctypes.data)
         return out if np.ndim(a) else out[0]
 
     def Da_of_z(self, z):
         """the runner's CubicSpline D_a(z) (HealpixRunner.py:279-280, :297)"""
         zz = _lib.f8(np.atleast_1d(z))
         out = np.empty_like(zz)
-        _lib.check(_lib.load().bfgx_cosmo_da_eval(C.byref(self._c()), zz.size, zz.ctypes.data, out.ctypes.data))
+        _lib.call('bfgx_cosmo_da_eval', self._c(), zz.size, zz.ctypes.data, out.ctypes.data)
         return out if np.ndim(z) else out[0]
 
 
@@ -119,8 +116,7 @@ class MassDef(object):
         out = np.empty_like(M)
         c = _lib.make_cosmo(cosmo_to_dict(cosmo))
         md = _lib.make_massdef(self.Delta, self.rho_type)
-        _lib.check(_lib.load().bfgx_cosmo_radius(C.byref(c), C.byref(md), M.size, M.ctypes.data, aa.ctypes.data,
-                                                 out.ctypes.data))
+        _lib.call('bfgx_cosmo_radius', c, md, M.size, M.ctypes.data, aa.ctypes.data, out.ctypes.data)
         return out
 
     def __eq__(self, other):

@@ -6,15 +6,12 @@ out (uploaded to device 0); a C-contiguous CUDA float64 tensor is analysed where
 as tensors on its device.  Per-bin spectra are numpy arrays either way.  Mixing the two kinds in one call is a ValueError."""
 import numpy as np
 
-from .. import _lib, engine
+from .. import _lib, _tensors, engine
+from .._tensors import is_tensor, launch_args, to_cuda
 
 __all__ = ['rfft2', 'irfft2', 'power_spectrum_2d', 'cross_power_spectrum_2d', 'smoothing_2d', 'kappa_to_shear_2d', 'shear_to_kappa_2d']
 
 MIN_SIDE, MAX_SIDE = 8, 4096
-
-
-def _is_tensor(m):
-    return hasattr(m, 'data_ptr') and not isinstance(m, np.ndarray)
 
 
 def _check_side(N, what):
@@ -25,7 +22,7 @@ def _check_side(N, what):
 def _square_maps(what, *maps):
     """(on_device, maps made contiguous float64): all numpy or all CUDA float64 tensors on one device, square 2-D, one shape, a supported
     side; ValueError otherwise, before the library is touched"""
-    kinds = [_is_tensor(m) for m in maps]
+    kinds = [is_tensor(m) for m in maps]
     if any(kinds) and not all(kinds):
         raise ValueError("%s needs numpy arrays or CUDA float64 tensors, not one of each" % what)
     out = []
@@ -49,17 +46,6 @@ def _square_maps(what, *maps):
     return kinds[0], out
 
 
-def _to_device(m):
-    """a numpy map as a tensor on device 0 (torch takes no read-only array: such a map is copied first)"""
-    import torch
-    return torch.from_numpy(m if m.flags.writeable else m.copy()).to('cuda:0')
-
-
-def _launch_args(t):
-    import torch
-    return dict(device=t.device.index or 0, stream=torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _work(N, like):
     import torch
     return torch.empty(engine.fft2_work_doubles(N), dtype=torch.float64, device=like.device)
@@ -70,11 +56,11 @@ def rfft2(Map):
     a float64 tensor [N][fft_pitch(N)][2] (real, imaginary) whose columns c > N/2 are padding."""
     import torch
     on_dev, (m,) = _square_maps("rfft2", Map)
-    d = m if on_dev else _to_device(m)
+    d = m if on_dev else to_cuda(m)
     N = int(d.shape[0])
     spec = torch.empty((N, engine.fft_pitch(N), 2), dtype=torch.float64, device=d.device)
     work = _work(N, d)
-    engine.rfft2_device(d.data_ptr(), N, work.data_ptr(), spec.data_ptr(), **_launch_args(d))
+    engine.rfft2_device(d.data_ptr(), N, work.data_ptr(), spec.data_ptr(), **launch_args(d))
     if on_dev:
         return spec
     return np.ascontiguousarray(spec.cpu().numpy().view(np.complex128)[:, :N // 2 + 1, 0])
@@ -86,7 +72,7 @@ def irfft2(spec, N):
     N = int(N)
     _check_side(N, "irfft2")
     pitch, nz = N // 2 + 1 + 7 & ~7, N // 2 + 1
-    on_dev = _is_tensor(spec)
+    on_dev = is_tensor(spec)
     if on_dev:
         if not spec.is_cuda or spec.dtype != torch.float64 or tuple(spec.shape) != (N, pitch, 2):
             raise ValueError("irfft2 needs a CUDA float64 tensor of shape [N][fft_pitch(N)][2]")
@@ -100,12 +86,12 @@ def irfft2(spec, N):
         d = torch.from_numpy(padded.view(np.float64).reshape(N, pitch, 2)).to('cuda:0')
     out = torch.empty((N, N), dtype=torch.float64, device=d.device)
     work = _work(N, d)
-    engine.irfft2_device(d.data_ptr(), N, 1.0 / (float(N) * float(N)), work.data_ptr(), out.data_ptr(), **_launch_args(d))
+    engine.irfft2_device(d.data_ptr(), N, 1.0 / (float(N) * float(N)), work.data_ptr(), out.data_ptr(), **launch_args(d))
     return out if on_dev else out.cpu().numpy()
 
 
 def _check_bins(what, L, Nk, window):
-    p = engine._window_order(window, what)
+    p = engine.window_order(window, what)
     if isinstance(Nk, bool) or int(Nk) != Nk or not 1 <= int(Nk) <= 2048:
         raise ValueError("%s needs 1 <= Nk <= 2048" % what)
     if not float(L) > 0:
@@ -125,19 +111,13 @@ def cross_power_spectrum_2d(MapA, MapB, L, Nk=180, window='none', normalize=Fals
     if not on_dev:
         out = np.empty((4, Nk))
         cnt = np.empty(Nk, dtype=np.int64)
-        _lib.check(_lib.load().bfgx_power_spectrum_2d(0, N, A.ctypes.data, B.ctypes.data, L, Nk, p, out[0].ctypes.data, out[1].ctypes.data,
-                                                     out[2].ctypes.data, out[3].ctypes.data, cnt.ctypes.data))
+        _lib.call('bfgx_power_spectrum_2d', 0, N, A.ctypes.data, B.ctypes.data, L, Nk, p, out[0].ctypes.data, out[1].ctypes.data,
+                  out[2].ctypes.data, out[3].ctypes.data, cnt.ctypes.data)
         paa, pbb, pab, k = out
     else:
-        import torch
         work = _work(N, A)
-        sums = torch.empty((4, Nk), dtype=torch.float64, device=A.device)
-        cntd = torch.empty(Nk, dtype=torch.int64, device=A.device)
-        engine.power_spectrum_2d_device(A.data_ptr(), B.data_ptr(), N, L, Nk, p, work.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(),
-                                        sums[2].data_ptr(), sums[3].data_ptr(), cntd.data_ptr(), **_launch_args(A))
-        s, cnt = sums.cpu().numpy(), cntd.cpu().numpy()
-        with np.errstate(divide='ignore', invalid='ignore'):
-            paa, pbb, pab, k = s[0] / cnt, s[1] / cnt, s[2] / cnt, s[3] / cnt
+        (paa, pbb, pab, k), cnt = _tensors.bin_means(A.device, 4, Nk, lambda *out: engine.power_spectrum_2d_device(
+            A.data_ptr(), B.data_ptr(), N, L, Nk, p, work.data_ptr(), *out, **launch_args(A)))
     with np.errstate(divide='ignore', invalid='ignore'):
         r = pab / np.sqrt(paa * pbb)
     if normalize:
@@ -179,14 +159,13 @@ def smoothing_2d(Map, L, fwhm=None, sigma=None, tophat=None, beam=None):
     N = int(m.shape[0])
     if not on_dev:
         out = np.empty((N, N))
-        _lib.check(_lib.load().bfgx_filter_map_2d(0, N, m.ctypes.data, float(L), engine.FILTER_KINDS_2D[kind], param,
-                                                 None if tk is None else tk.ctypes.data, None if tb is None else tb.ctypes.data,
-                                                 0 if tk is None else int(tk.size), out.ctypes.data))
+        _lib.call('bfgx_filter_map_2d', 0, N, m.ctypes.data, L, engine.FILTER_KINDS_2D[kind], param, _tensors.ptr(tk), _tensors.ptr(tb),
+                  0 if tk is None else tk.size, out.ctypes.data)
         return out
     import torch
     out = torch.empty_like(m)
     work = _work(N, m)
-    engine.filter_map_2d_device(m.data_ptr(), N, L, kind, param, tk, tb, work.data_ptr(), out.data_ptr(), **_launch_args(m))
+    engine.filter_map_2d_device(m.data_ptr(), N, L, kind, param, tk, tb, work.data_ptr(), out.data_ptr(), **launch_args(m))
     return out
 
 
@@ -199,12 +178,12 @@ def kappa_to_shear_2d(kappa):
     N = int(m.shape[0])
     if not on_dev:
         g1, g2 = np.empty((N, N)), np.empty((N, N))
-        _lib.check(_lib.load().bfgx_kappa_to_shear_2d(0, N, m.ctypes.data, g1.ctypes.data, g2.ctypes.data))
+        _lib.call('bfgx_kappa_to_shear_2d', 0, N, m.ctypes.data, g1.ctypes.data, g2.ctypes.data)
         return g1, g2
     import torch
     g1, g2 = torch.empty_like(m), torch.empty_like(m)
     work = _work(N, m)
-    engine.kappa_to_shear_2d_device(m.data_ptr(), N, work.data_ptr(), g1.data_ptr(), g2.data_ptr(), **_launch_args(m))
+    engine.kappa_to_shear_2d_device(m.data_ptr(), N, work.data_ptr(), g1.data_ptr(), g2.data_ptr(), **launch_args(m))
     return g1, g2
 
 
@@ -215,10 +194,10 @@ def shear_to_kappa_2d(g1, g2):
     N = int(a.shape[0])
     if not on_dev:
         ke, kb = np.empty((N, N)), np.empty((N, N))
-        _lib.check(_lib.load().bfgx_shear_to_kappa_2d(0, N, a.ctypes.data, b.ctypes.data, ke.ctypes.data, kb.ctypes.data))
+        _lib.call('bfgx_shear_to_kappa_2d', 0, N, a.ctypes.data, b.ctypes.data, ke.ctypes.data, kb.ctypes.data)
         return ke, kb
     import torch
     ke, kb = torch.empty_like(a), torch.empty_like(a)
     work = _work(N, a)
-    engine.shear_to_kappa_2d_device(a.data_ptr(), b.data_ptr(), N, work.data_ptr(), ke.data_ptr(), kb.data_ptr(), **_launch_args(a))
+    engine.shear_to_kappa_2d_device(a.data_ptr(), b.data_ptr(), N, work.data_ptr(), ke.data_ptr(), kb.data_ptr(), **launch_args(a))
     return ke, kb

@@ -32,8 +32,9 @@ Before / after baryonification:
 import numpy as np
 
 from .. import _lib, engine
+from .._tensors import is_tensor, launch_args, to_cuda, mask_u8, ptr
 from . import mapstats as _ms
-from .flatsky import _is_tensor, _square_maps, _to_device, _launch_args
+from .flatsky import _square_maps
 from .sphtfunc import UNSEEN, unseen_mask
 
 __all__ = ['derivatives_2d', 'peak_counts_2d', 'minkowski_functionals_2d', 'minkowski_gaussian_2d', 'patch_statistics']
@@ -70,7 +71,7 @@ def _check_mask_2d(what, mask, shape, on_dev):
     """mask of the map's shape and kind (None stays None); ValueError otherwise"""
     if mask is None:
         return None
-    if _is_tensor(mask) != on_dev:
+    if is_tensor(mask) != on_dev:
         raise ValueError("%s needs numpy arrays or CUDA tensors, not one of each" % what)
     if on_dev and not mask.is_cuda:
         raise ValueError("%s needs a CUDA mask" % what)
@@ -80,9 +81,9 @@ def _check_mask_2d(what, mask, shape, on_dev):
     return mk
 
 
-def _mask_u8(mask, dev):
+def _flat_mask(mask, dev):
     """uint8 [n * n] on dev, 1 where the mask is nonzero (None stays None)"""
-    return None if mask is None else _ms._mask_u8(mask.reshape(-1), int(mask.shape[0]) * int(mask.shape[1]), dev)
+    return None if mask is None else mask_u8(mask.reshape(-1), dev)
 
 
 class _PatchBuffers(object):
@@ -97,12 +98,12 @@ class _PatchBuffers(object):
         self.ders = torch.empty((nder, N, N), dtype=torch.float64, device=dev)
 
     def forward(self, m, k=0):
-        engine.rfft2_device(m.data_ptr(), self.N, self.work.data_ptr(), self.spec[k].data_ptr(), **_launch_args(m))
+        engine.rfft2_device(m.data_ptr(), self.N, self.work.data_ptr(), self.spec[k].data_ptr(), **launch_args(m))
 
     def derivatives(self, L, flt, spin_form, k=0):
         kind, param, tk, tb = flt
         engine.derivatives_2d_device(self.spec[k].data_ptr(), self.N, L, kind, param, tk, tb, self.nder, spin_form, self.work.data_ptr(),
-                                     self.ders.data_ptr(), **_launch_args(self.ders))
+                                     self.ders.data_ptr(), **launch_args(self.ders))
         return self.ders
 
 
@@ -113,7 +114,7 @@ def derivatives_2d(Map, L, fwhm=None, sigma=None, tophat=None, beam=None, spin_f
     what = "derivatives_2d"
     on_dev, (m,) = _square_maps(what, Map)
     flt = _filter(what, L, fwhm, sigma, tophat, beam)
-    d = m if on_dev else _to_device(m)
+    d = m if on_dev else to_cuda(m)
     buf = _PatchBuffers(int(d.shape[0]), 1, 6, d.device)
     buf.forward(d)
     ders = buf.derivatives(float(L), flt, spin_form)
@@ -122,7 +123,7 @@ def derivatives_2d(Map, L, fwhm=None, sigma=None, tophat=None, beam=None, spin_f
 
 def _grid_map(what, Map):
     """(on_device, the map made contiguous float64): a square 2-D grid of a side in [3, 16384]; ValueError otherwise"""
-    on_dev = _is_tensor(Map)
+    on_dev = is_tensor(Map)
     if on_dev:
         if not Map.is_cuda or str(Map.dtype) != 'torch.float64':
             raise ValueError("%s needs a CUDA float64 tensor" % what)
@@ -137,9 +138,9 @@ def _grid_map(what, Map):
     return on_dev, m
 
 
-def _peaks_device(m, mask_u8, periodic, edges_dev, counts, flags):
-    engine.peaks_2d_device(m.data_ptr(), int(m.shape[0]), periodic, 0 if mask_u8 is None else mask_u8.data_ptr(), edges_dev.numel() - 1,
-                           edges_dev.data_ptr(), counts.data_ptr(), 0 if flags is None else flags.data_ptr(), **_launch_args(m))
+def _peaks_device(m, mask, periodic, edges_dev, counts, flags):
+    engine.peaks_2d_device(m.data_ptr(), int(m.shape[0]), periodic, ptr(mask), edges_dev.numel() - 1, edges_dev.data_ptr(), counts.data_ptr(),
+                           ptr(flags), **launch_args(m))
 
 
 def peak_counts_2d(Map, bins, mask=None, periodic=True, return_flags=False):
@@ -152,11 +153,11 @@ def peak_counts_2d(Map, bins, mask=None, periodic=True, return_flags=False):
     on_dev, m = _grid_map(what, Map)
     e = _ms._edges(bins)
     mask = _check_mask_2d(what, mask, m.shape, on_dev)
-    d = m if on_dev else _to_device(m)
+    d = m if on_dev else to_cuda(m)
     dev = d.device
     counts = torch.empty((2, e.size - 1), dtype=torch.int64, device=dev)
     flags = torch.empty(tuple(d.shape), dtype=torch.int8, device=dev) if return_flags else None
-    _peaks_device(d, _mask_u8(mask, dev), periodic, torch.from_numpy(e).to(dev), counts, flags)
+    _peaks_device(d, _flat_mask(mask, dev), periodic, torch.from_numpy(e).to(dev), counts, flags)
     if not on_dev:
         counts = counts.cpu().numpy()
         flags = flags.cpu().numpy() if return_flags else None
@@ -184,9 +185,9 @@ def minkowski_functionals_2d(Map, L, bins, mask=None, fwhm=None, sigma=None, top
     flt = _filter(what, L, fwhm, sigma, tophat, beam)
     e = _ms._edges(bins, _ms.MAX_MF_BINS)
     mask = _check_mask_2d(what, mask, m.shape, on_dev)
-    d = m if on_dev else _to_device(m)
+    d = m if on_dev else to_cuda(m)
     N, dev = int(d.shape[0]), d.device
-    mk = _mask_u8(mask, dev)
+    mk = _flat_mask(mask, dev)
     d, unseen = _zeroed(d, mk)
     buf = _PatchBuffers(N, 1, 6, dev)
     buf.forward(d)
@@ -214,7 +215,7 @@ def minkowski_gaussian_2d(sigma0, sigma1, thresholds):
 
 def _patch_maps(what, maps):
     """the K <= 3 maps of patch_statistics as a list: one map [N, N], a stack [K, N, N] or a sequence of maps"""
-    if _is_tensor(maps) or isinstance(maps, np.ndarray):
+    if is_tensor(maps) or isinstance(maps, np.ndarray):
         ms = [maps] if maps.ndim == 2 else list(maps) if maps.ndim == 3 else None
         if ms is None:
             raise ValueError("%s: maps must be one map (N, N) or several (K, N, N) (got shape %s)" % (what, tuple(maps.shape)))
@@ -257,11 +258,11 @@ def patch_statistics(maps, L, scales, window='gauss', order=4, peak_bins=None, m
     me = None if mf_bins is None else _ms._edges(mf_bins, _ms.MAX_MF_BINS)
     mask = _check_mask_2d(what, mask, ms[0].shape, on_dev)
     L = float(L)
-    ds = ms if on_dev else [_to_device(m) for m in ms]
+    ds = ms if on_dev else [to_cuda(m) for m in ms]
     N, dev = int(ds[0].shape[0]), ds[0].device
     npix = N * N
     S, exps = len(flts), _ms.moment_exponents(K, order)
-    mk = _mask_u8(mask, dev)
+    mk = _flat_mask(mask, dev)
     buf = _PatchBuffers(N, K, 1 if me is None else 6, dev)
     unseen = torch.empty((K, N, N), dtype=torch.bool, device=dev)
     for k in range(K):

@@ -251,26 +251,23 @@ class ParticleSnapshot(object):
             out = _lib.pinned_empty(N_grid ** ndim).reshape((N_grid,) * ndim)
             offs = (fields['x'][1], fields['y'][1], 0 if self.is2D else fields['z'][1], fields['M'][1])
             if order == 1:
-                rc = _lib.load().bfgx_deposit_particles_records(int(self.device), ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
-                                                                *offs, int(N_grid), edges.ctypes.data, out.ctypes.data)
+                _lib.call('bfgx_deposit_particles_records', self.device, ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
+                          *offs, N_grid, edges.ctypes.data, out.ctypes.data)
             else:
-                rc = _lib.load().bfgx_deposit_cloud_records(int(self.device), ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
-                                                            *offs, int(N_grid), float(self.L), order, out.ctypes.data)
-            _lib.check(rc)
+                _lib.call('bfgx_deposit_cloud_records', self.device, ndim, rec.size, rec.ctypes.data if rec.size else None, rec.dtype.itemsize,
+                          *offs, N_grid, self.L, order, out.ctypes.data)
             return out
         assert np.isnan(self.cat['M']).sum() == 0, "If you want to make a map, provide a value for the particle mass"      # io.py:636
         x, y, m = _lib.f8(self.cat['x']), _lib.f8(self.cat['y']), _lib.f8(self.cat['M'])
         z = None if self.is2D else _lib.f8(self.cat['z'])
         out = np.empty((N_grid,) * ndim)
+        z_ptr = None if z is None else z.ctypes.data
         if order == 1:
-            rc = _lib.load().bfgx_deposit_particles(int(self.device), ndim, x.size, x.ctypes.data, y.ctypes.data,
-                                                    None if z is None else z.ctypes.data, m.ctypes.data, int(N_grid),
-                                                    edges.ctypes.data, out.ctypes.data)
+            _lib.call('bfgx_deposit_particles', self.device, ndim, x.size, x.ctypes.data, y.ctypes.data, z_ptr, m.ctypes.data, N_grid,
+                      edges.ctypes.data, out.ctypes.data)
         else:
-            rc = _lib.load().bfgx_deposit_cloud(int(self.device), ndim, x.size, x.ctypes.data, y.ctypes.data,
-                                                None if z is None else z.ctypes.data, m.ctypes.data, int(N_grid), float(self.L), order,
-                                                out.ctypes.data)
-        _lib.check(rc)
+            _lib.call('bfgx_deposit_cloud', self.device, ndim, x.size, x.ctypes.data, y.ctypes.data, z_ptr, m.ctypes.data, N_grid, self.L, order,
+                      out.ctypes.data)
         return out
 
     def power_spectrum(self, N_grid, Nk=180, assignment='tsc', interlace=True, normalize=False, subtract_shot_noise=False):

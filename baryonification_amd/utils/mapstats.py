@@ -28,11 +28,10 @@ Before / after baryonification:
     s1 = shell_statistics(baryonified_shell, scales)
     ratio = s1['central'][:, s1['exponents'].index((3,))] / s0['central'][:, s0['exponents'].index((3,))]
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib, engine
+from .._tensors import is_cuda_tensor, device_index, stream, ptr, mask_u8, need_gpu
 from .io import npix2nside
 from .pixelfunc import check_nside
 from . import sphtfunc
@@ -41,10 +40,6 @@ __all__ = ['map_moments', 'peak_counts', 'shell_statistics', 'moment_exponents',
            'minkowski_from_derivatives', 'minkowski_gaussian']
 
 MAX_MAPS, MAX_ORDER, MAX_BINS, MAX_MF_BINS = 3, 4, 4096, 512
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
 
 
 def moment_exponents(nmaps, order=4):
@@ -72,14 +67,14 @@ def _check_k_order(nmaps, order):
 
 def _map_list(maps):
     """the maps as a list of 1-D arrays / tensors of one size; ValueError otherwise (before any device call)"""
-    if _is_torch(maps) or isinstance(maps, np.ndarray):
+    if is_cuda_tensor(maps) or isinstance(maps, np.ndarray):
         ms = [maps] if maps.ndim == 1 else list(maps) if maps.ndim == 2 else None
         if ms is None:
             raise ValueError("maps must be one map (npix,) or several (nmaps, npix) (got shape %s)" % (tuple(maps.shape),))
     elif isinstance(maps, (list, tuple)) and len(maps) and all(np.ndim(m) == 0 for m in maps):
         ms = [np.asarray(maps)]
     elif isinstance(maps, (list, tuple)):
-        ms = [m if _is_torch(m) else np.asarray(m) for m in maps]
+        ms = [m if is_cuda_tensor(m) else np.asarray(m) for m in maps]
     else:
         return _map_list(np.asarray(maps))
     if not 1 <= len(ms) <= MAX_MAPS:
@@ -89,7 +84,7 @@ def _map_list(maps):
             raise ValueError("every map must be 1-D and not empty (got shape %s)" % (tuple(m.shape),))
         if m.shape[0] != ms[0].shape[0]:
             raise ValueError("the maps have different sizes (%d, %d)" % (ms[0].shape[0], m.shape[0]))
-        kind = 'c' if (m.dtype.is_complex if _is_torch(m) else m.dtype.kind == 'c') else 'f'
+        kind = 'c' if (m.dtype.is_complex if is_cuda_tensor(m) else m.dtype.kind == 'c') else 'f'
         if kind == 'c':
             raise ValueError("maps must be real")
     return ms
@@ -98,22 +93,17 @@ def _map_list(maps):
 def _device_of(*xs):
     import torch
     for x in xs:
-        if _is_torch(x):
+        if is_cuda_tensor(x):
             return x.device, True
     return torch.device('cuda', 0), False
-
-
-def _need_gpu():
-    if _lib.load().bfgx_device_count() <= 0:
-        raise _lib.BfgxError("bfgx: no HIP device visible: libbfgx has no CPU fallback")
 
 
 def _stack(ms, dev, maps=None):
     """float64 [K, npix] on dev; `maps` (what the caller passed) is used as it is when it already is such a tensor"""
     import torch
-    if _is_torch(maps) and maps.dtype == torch.float64 and maps.device == dev and maps.is_contiguous():
+    if is_cuda_tensor(maps) and maps.dtype == torch.float64 and maps.device == dev and maps.is_contiguous():
         return maps if maps.dim() == 2 else maps.unsqueeze(0)
-    ts = [m.to(device=dev, dtype=torch.float64) if _is_torch(m) else torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64)).to(dev)
+    ts = [m.to(device=dev, dtype=torch.float64) if is_cuda_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64)).to(dev)
           for m in ms]
     return ts[0].contiguous().unsqueeze(0) if len(ts) == 1 else torch.stack(ts)
 
@@ -122,36 +112,17 @@ def _check_mask(mask, npix):
     """mask as an array / tensor of the maps' shape (None stays None); ValueError otherwise (before any device call)"""
     if mask is None:
         return None
-    mk = mask if _is_torch(mask) else np.asarray(mask)
+    mk = mask if is_cuda_tensor(mask) else np.asarray(mask)
     if tuple(mk.shape) != (npix,):
         raise ValueError("mask must have the maps' shape (%d,) (got %s)" % (npix, tuple(mk.shape)))
     return mk
 
 
-def _mask_u8(mask, npix, dev):
-    """uint8 [npix] on dev: 1 where mask is nonzero (None stays None)"""
-    import torch
-    if mask is None:
-        return None
-    if _is_torch(mask):
-        return (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
-    return torch.from_numpy((mask != 0).astype(np.uint8)).to(dev)
-
-
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _moments_device(stack, mask, order, n_out, out, work):
     """bfgx_mapstats_moments_device on a float64 [K, npix] tensor: n_out int64 [1], out float64 [K + nterms], work scratch"""
     dev = stack.device
-    _lib.check(_lib.load().bfgx_mapstats_moments_device(dev.index or 0, _stream(dev), stack.shape[1], stack.shape[0], order, _p(stack),
-                                                       _p(mask), _p(n_out), _p(out), _p(work)))
+    _lib.call('bfgx_mapstats_moments_device', device_index(dev), stream(dev), stack.shape[1], stack.shape[0], order, ptr(stack), ptr(mask),
+              ptr(n_out), ptr(out), ptr(work))
 
 
 def map_moments(maps, order=4, mask=None):
@@ -165,18 +136,18 @@ def map_moments(maps, order=4, mask=None):
     npix = int(ms[0].shape[0])
     dev, _ = _device_of(*(ms + [mask]))
     mask = _check_mask(mask, npix)
-    _need_gpu()
+    need_gpu()
     exps = moment_exponents(K, order)
     n_out = torch.empty(1, dtype=torch.int64, device=dev)
     out = torch.empty(K + len(exps), dtype=torch.float64, device=dev)
     work = torch.empty(_lib.MAPSTATS_WORK_DOUBLES, dtype=torch.float64, device=dev)
-    _moments_device(_stack(ms, dev, maps), _mask_u8(mask, npix, dev), order, n_out, out, work)
+    _moments_device(_stack(ms, dev, maps), mask_u8(mask, dev), order, n_out, out, work)
     vals = out.cpu().numpy()
     return {'n': int(n_out.item()), 'mean': vals[:K].copy(), 'central': {e: float(v) for e, v in zip(exps, vals[K:])}}
 
 
 def _edges(bins, max_bins=MAX_BINS):
-    e = np.asarray(bins.cpu() if _is_torch(bins) else bins, dtype=np.float64)
+    e = np.asarray(bins.cpu() if is_cuda_tensor(bins) else bins, dtype=np.float64)
     if e.ndim != 1 or not 2 <= e.size <= max_bins + 1:
         raise ValueError("bins must be 1-D with 2 to %d edges (1 to %d bins) (got shape %s)" % (max_bins + 1, max_bins, e.shape))
     if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
@@ -186,8 +157,8 @@ def _edges(bins, max_bins=MAX_BINS):
 
 def _peaks_device(m, mask, nside, nest, edges_dev, counts, flags):
     dev = m.device
-    _lib.check(_lib.load().bfgx_mapstats_peaks_device(dev.index or 0, _stream(dev), nside, int(bool(nest)), _p(m), _p(mask),
-                                                     edges_dev.numel() - 1, _p(edges_dev), _p(counts), _p(flags)))
+    _lib.call('bfgx_mapstats_peaks_device', device_index(dev), stream(dev), nside, bool(nest), ptr(m), ptr(mask), edges_dev.numel() - 1,
+              ptr(edges_dev), ptr(counts), ptr(flags))
 
 
 def peak_counts(map, bins, mask=None, nest=False, return_flags=False):
@@ -205,11 +176,11 @@ def peak_counts(map, bins, mask=None, nest=False, return_flags=False):
     e = _edges(bins)
     mask = _check_mask(mask, npix)
     dev, on_dev = _device_of(ms[0], mask)
-    _need_gpu()
+    need_gpu()
     m = _stack(ms, dev, map)[0]
     counts = torch.empty((2, e.size - 1), dtype=torch.int64, device=dev)
     flags = torch.empty(npix, dtype=torch.int8, device=dev) if return_flags else None
-    _peaks_device(m, _mask_u8(mask, npix, dev), nside, nest, torch.from_numpy(e).to(dev), counts, flags)
+    _peaks_device(m, mask_u8(mask, dev), nside, nest, torch.from_numpy(e).to(dev), counts, flags)
     if not on_dev:
         counts = counts.cpu().numpy()
         flags = flags.cpu().numpy() if return_flags else None
@@ -249,10 +220,10 @@ def shell_statistics(maps, scales, window='gauss', lmax=None, iter=3, order=4, p
     me = None if mf_bins is None else _edges(mf_bins, MAX_MF_BINS)
     mask = _check_mask(mask, npix)
     dev, on_dev = _device_of(*(ms + [mask]))
-    _need_gpu()
-    plan = engine.sht_plan(nside, lmax, mmax, device=dev.index or 0)
+    need_gpu()
+    plan = engine.sht_plan(nside, lmax, mmax, device=device_index(dev))
     S, exps = len(wins), moment_exponents(K, order)
-    mk = _mask_u8(mask, npix, dev)
+    mk = mask_u8(mask, dev)
     stack = _stack(ms, dev, maps)
     if mk is not None:
         stack = torch.where(mk.bool().unsqueeze(0), stack, torch.zeros((), dtype=torch.float64, device=dev))
@@ -306,7 +277,7 @@ class _MinkowskiBuffers(object):
     def __init__(self, npix, edges, batch, dev):
         import torch
         self.npix, self.nb, self.dev = int(npix), edges.size - 1, dev
-        nw = int(_lib.load().bfgx_mapstats_minkowski_work_doubles(self.npix, self.nb))
+        nw = int(_lib.call('bfgx_mapstats_minkowski_work_doubles', self.npix, self.nb))
         if nw < 0:
             raise ValueError("minkowski: npix %d or %d bins out of range" % (self.npix, self.nb))
         self.edges = torch.from_numpy(edges).to(dev)
@@ -316,8 +287,8 @@ class _MinkowskiBuffers(object):
 
     def run(self, ders, mask, at=()):
         """enqueue the kernel on float64 [6, npix] (spin form) into the slot `at` of the batch"""
-        _lib.check(_lib.load().bfgx_mapstats_minkowski_device(self.dev.index or 0, _stream(self.dev), self.npix, _p(ders), _p(mask), self.nb,
-                                                             _p(self.edges), _p(self.counts[at]), _p(self.sums[at]), _p(self.work)))
+        _lib.call('bfgx_mapstats_minkowski_device', device_index(self.dev), stream(self.dev), self.npix, ptr(ders), ptr(mask), self.nb,
+                  ptr(self.edges), ptr(self.counts[at]), ptr(self.sums[at]), ptr(self.work))
 
     def functionals(self):
         """{'n' [*batch], 'count' [*batch, nb], 'v0' [*batch, nb + 1], 'v1', 'v2' [*batch, nb]} as device tensors"""
@@ -347,21 +318,21 @@ def minkowski_from_derivatives(ders, bins, mask=None, spin_form=False):
     Returns {'n': good pixels (int), 'count': int64 [nb] pixels per bin, 'v0': [nb + 1], 'v1': [nb], 'v2': [nb]} (the module
     docstring has the definitions); no good pixel gives n = 0 and NaN.  A CUDA tensor gives CUDA results."""
     import torch
-    d = ders if _is_torch(ders) else np.asarray(ders)
+    d = ders if is_cuda_tensor(ders) else np.asarray(ders)
     if d.ndim != 2 or d.shape[0] != 6 or d.shape[1] == 0:
         raise ValueError("ders must hold six maps (6, npix) (got shape %s)" % (tuple(d.shape),))
-    if d.dtype.is_complex if _is_torch(d) else d.dtype.kind == 'c':
+    if d.dtype.is_complex if is_cuda_tensor(d) else d.dtype.kind == 'c':
         raise ValueError("ders must be real")
     npix = int(d.shape[1])
     e = _edges(bins, MAX_MF_BINS)
     mask = _check_mask(mask, npix)
     dev, on_dev = _device_of(d, mask)
-    _need_gpu()
-    t = d.to(device=dev, dtype=torch.float64) if _is_torch(d) else torch.from_numpy(np.ascontiguousarray(d, dtype=np.float64)).to(dev)
+    need_gpu()
+    t = d.to(device=dev, dtype=torch.float64) if is_cuda_tensor(d) else torch.from_numpy(np.ascontiguousarray(d, dtype=np.float64)).to(dev)
     if not spin_form:
         t = torch.cat([t[:3], (t[3] + t[5]).unsqueeze(0), (t[3] - t[5]).unsqueeze(0), (2.0 * t[4]).unsqueeze(0)])
     mf = _MinkowskiBuffers(npix, e, (), dev)
-    mf.run(t.contiguous(), _mask_u8(mask, npix, dev))
+    mf.run(t.contiguous(), mask_u8(mask, dev))
     return _minkowski_result(mf.functionals(), on_dev)
 
 
@@ -385,9 +356,9 @@ def minkowski_functionals(map, bins, mask=None, lmax=None, iter=3, fwhm=0.0, sig
     fl = sphtfunc._window(lmax, fwhm, sigma, beam_window) if filtered else None
     mask = _check_mask(mask, npix)
     dev, on_dev = _device_of(ms[0], mask)
-    _need_gpu()
-    plan = engine.sht_plan(nside, lmax, mmax, device=dev.index or 0)
-    mk = _mask_u8(mask, npix, dev)
+    need_gpu()
+    plan = engine.sht_plan(nside, lmax, mmax, device=device_index(dev))
+    mk = mask_u8(mask, dev)
     m = _stack(ms, dev, map)[0]
     if mk is not None:
         m = torch.where(mk.bool(), m, torch.zeros((), dtype=torch.float64, device=dev))

@@ -19,21 +19,16 @@ Definitions that differ from, or go beyond, healpy's:
   * With phi=None the points are pixel centres and the pixel's own ring is taken as the ring above, which is what the rule gives in
     exact arithmetic (healpy recomputes cos(theta), which can round across the ring).
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib
+from .._tensors import is_cuda_tensor, device_index, stream, ptr
 from .io import npix2nside
 from .sphtfunc import UNSEEN
 
 __all__ = ['ud_grade', 'get_interp_weights', 'get_interp_val', 'get_all_neighbours', 'UNSEEN']
 
 MAX_NSIDE = 8192
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
 
 
 def _is_pow2(n):
@@ -60,29 +55,15 @@ def _order(o, name):
     raise ValueError("%s must be 'RING', 'NESTED' or 'NEST' (got %r)" % (name, o))
 
 
-def _stream(t):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream or None)
-
-
-def _dev(t):
-    import torch
-    return t.device.index if t.device.index is not None else torch.cuda.current_device()
-
-
-def _ptr(x):
-    return C.c_void_p(x.data_ptr() if hasattr(x, 'data_ptr') else x.ctypes.data)
-
-
 def _like(x, device):
     """x as a torch tensor on `device` (no copy when it already is one)"""
     import torch
-    return x if _is_torch(x) else torch.as_tensor(np.asarray(x), device=device)
+    return x if is_cuda_tensor(x) else torch.as_tensor(np.asarray(x), device=device)
 
 
 def _find_device(*xs):
     for x in xs:
-        if _is_torch(x):
+        if is_cuda_tensor(x):
             return x.device
     return None
 
@@ -104,7 +85,7 @@ def ud_grade(map_in, nside_out, pess=False, order_in='RING', order_out=None, pow
     nest_in = _order(order_in, 'order_in')
     nest_out = nest_in if order_out is None else _order(order_out, 'order_out')
     nside_out = check_nside(nside_out, True, 'nside_out')
-    on_dev = _is_torch(map_in)
+    on_dev = is_cuda_tensor(map_in)
     if on_dev:
         import torch
         m = map_in
@@ -136,17 +117,16 @@ def ud_grade(map_in, nside_out, pess=False, order_in='RING', order_out=None, pow
     npix_out = 12 * nside_out * nside_out
     oshape = (npix_out,) if m.ndim == 1 else (nmaps, npix_out)
     dt_in, dt_out = int(np.dtype(tdt) == np.float64), int(out_dt == np.float64)
-    L = _lib.load()
     if on_dev:
         import torch
         m = m.contiguous()
         out = torch.empty(oshape, dtype=torch.float64 if dt_out else torch.float32, device=m.device)
-        _lib.check(L.bfgx_hpx_ud_grade_device(_dev(m), _stream(m), nside_in, nside_out, nmaps, nest_in, nest_out, int(bool(pess)), ratio,
-                                              dt_in, dt_out, _ptr(m), _ptr(out)))
+        _lib.call('bfgx_hpx_ud_grade_device', device_index(m), stream(m), nside_in, nside_out, nmaps, nest_in, nest_out, bool(pess), ratio, dt_in,
+                  dt_out, ptr(m), ptr(out))
         return out
     m = np.ascontiguousarray(m)
     out = np.empty(oshape, dtype=out_dt)
-    _lib.check(L.bfgx_hpx_ud_grade(0, nside_in, nside_out, nmaps, nest_in, nest_out, int(bool(pess)), ratio, dt_in, dt_out, _ptr(m), _ptr(out)))
+    _lib.call('bfgx_hpx_ud_grade', 0, nside_in, nside_out, nmaps, nest_in, nest_out, bool(pess), ratio, dt_in, dt_out, ptr(m), ptr(out))
     return out
 
 
@@ -184,7 +164,6 @@ def get_interp_weights(nside, theta, phi=None, nest=False, lonlat=False):
     nside = check_nside(nside, bool(nest))
     npix = 12 * nside * nside
     device = _find_device(theta, phi)
-    L = _lib.load()
     if phi is None:
         if device is not None:
             import torch
@@ -212,15 +191,13 @@ def get_interp_weights(nside, theta, phi=None, nest=False, lonlat=False):
         w = torch.empty((4,) + shape, dtype=torch.float64, device=device)
         ref = ip if ip is not None else t
         if n:
-            _lib.check(L.bfgx_hpx_interp_weights_device(_dev(ref), _stream(ref), nside, int(bool(nest)), n,
-                                                        None if t is None else _ptr(t), None if p is None else _ptr(p),
-                                                        None if ip is None else _ptr(ip), _ptr(pix), _ptr(w)))
+            _lib.call('bfgx_hpx_interp_weights_device', device_index(ref), stream(ref), nside, bool(nest), n, ptr(t), ptr(p), ptr(ip), ptr(pix),
+                      ptr(w))
         return pix, w
     pix = np.empty((4,) + shape, dtype=np.int64)
     w = np.empty((4,) + shape, dtype=np.float64)
     if n:
-        _lib.check(L.bfgx_hpx_interp_weights(0, nside, int(bool(nest)), n, None if t is None else _ptr(t), None if p is None else _ptr(p),
-                                             None if ip is None else _ptr(ip), _ptr(pix), _ptr(w)))
+        _lib.call('bfgx_hpx_interp_weights', 0, nside, bool(nest), n, ptr(t), ptr(p), ptr(ip), ptr(pix), ptr(w))
     return pix, w
 
 
@@ -250,17 +227,15 @@ def get_interp_val(m, theta, phi, nest=False, lonlat=False):
     shape = tuple(t.shape)
     n = int(np.prod(shape, dtype=np.int64))
     oshape = shape if mm.ndim == 1 else (nmaps,) + shape
-    L = _lib.load()
     if device is not None:
         import torch
         out = torch.empty(oshape, dtype=torch.float64, device=device)
         if n:
-            _lib.check(L.bfgx_hpx_interp_val_device(_dev(mm), _stream(mm), nside, int(bool(nest)), nmaps, dt, _ptr(mm), n, _ptr(t), _ptr(p),
-                                                    _ptr(out)))
+            _lib.call('bfgx_hpx_interp_val_device', device_index(mm), stream(mm), nside, bool(nest), nmaps, dt, ptr(mm), n, ptr(t), ptr(p), ptr(out))
         return out
     out = np.empty(oshape, dtype=np.float64)
     if n:
-        _lib.check(L.bfgx_hpx_interp_val(0, nside, int(bool(nest)), nmaps, dt, _ptr(mm), n, _ptr(t), _ptr(p), _ptr(out)))
+        _lib.call('bfgx_hpx_interp_val', 0, nside, bool(nest), nmaps, dt, ptr(mm), n, ptr(t), ptr(p), ptr(out))
     return out[()] if out.ndim == 0 else out
 
 
@@ -274,8 +249,7 @@ def get_all_neighbours(nside, theta, phi=None, nest=False, lonlat=False):
         raise NotImplementedError("get_all_neighbours takes pixel indices only (phi must be None: there is no ang2pix here)")
     nside = check_nside(nside, bool(nest))
     npix = 12 * nside * nside
-    L = _lib.load()
-    if _is_torch(theta):
+    if is_cuda_tensor(theta):
         import torch
         ip = theta
         if ip.dtype.is_floating_point or ip.dtype.is_complex or ip.dtype == torch.bool:
@@ -287,7 +261,7 @@ def get_all_neighbours(nside, theta, phi=None, nest=False, lonlat=False):
             raise ValueError("pixel indices must be in [0, %d)" % npix)
         out = torch.empty((8,) + tuple(ip.shape), dtype=torch.int64, device=ip.device)
         if ip.numel():
-            _lib.check(L.bfgx_hpx_neighbours_device(_dev(ip), _stream(ip), nside, int(bool(nest)), ip.numel(), _ptr(ip), _ptr(out)))
+            _lib.call('bfgx_hpx_neighbours_device', device_index(ip), stream(ip), nside, bool(nest), ip.numel(), ptr(ip), ptr(out))
         return out
     ip = np.asarray(theta)
     if ip.dtype.kind not in 'iu':
@@ -299,14 +273,14 @@ def get_all_neighbours(nside, theta, phi=None, nest=False, lonlat=False):
         raise ValueError("pixel indices must be in [0, %d)" % npix)
     out = np.empty((8,) + ip.shape, dtype=np.int64)
     if ip.size:
-        _lib.check(L.bfgx_hpx_neighbours(0, nside, int(bool(nest)), ip.size, _ptr(ip), _ptr(out)))
+        _lib.call('bfgx_hpx_neighbours', 0, nside, bool(nest), ip.size, ptr(ip), ptr(out))
     return out
 
 
 # ---------------------------------------------------------------------------------------------- regrid_pixels_hpix
 def scatter_add(hmap, parent_pix_vals, child_pix, child_weights):
     """hmap[child_pix[i, j]] += child_weights[i, j] * parent_pix_vals[i] in place (Runners.regrid_pixels_hpix)"""
-    on_dev = _is_torch(hmap)
+    on_dev = is_cuda_tensor(hmap)
     if on_dev:
         import torch
         if hmap.dtype != torch.float64 or hmap.dim() != 1 or not hmap.is_contiguous():
@@ -336,16 +310,15 @@ def scatter_add(hmap, parent_pix_vals, child_pix, child_weights):
         lo, hi = int(cp.min()), int(cp.max())
         if lo < -npix or hi >= npix:
             raise IndexError("child_pix holds index %d, outside [-%d, %d)" % (lo if lo < -npix else hi, npix, npix))
-    L = _lib.load()
     if on_dev:
         import torch
         vals, cp, cw = vals.to(torch.float64).contiguous(), cp.to(torch.int64).contiguous(), cw.to(torch.float64).contiguous()
         if N:
-            _lib.check(L.bfgx_hpx_scatter_add_device(_dev(hmap), _stream(hmap), npix, _ptr(hmap), N, _ptr(vals), _ptr(cp), _ptr(cw)))
+            _lib.call('bfgx_hpx_scatter_add_device', device_index(hmap), stream(hmap), npix, ptr(hmap), N, ptr(vals), ptr(cp), ptr(cw))
         return hmap
     vals = np.ascontiguousarray(vals, dtype=np.float64)
     cp = np.ascontiguousarray(cp, dtype=np.int64)
     cw = np.ascontiguousarray(cw, dtype=np.float64)
     if N:
-        _lib.check(L.bfgx_hpx_scatter_add(0, npix, _ptr(hmap), N, _ptr(vals), _ptr(cp), _ptr(cw)))
+        _lib.call('bfgx_hpx_scatter_add', 0, npix, ptr(hmap), N, ptr(vals), ptr(cp), ptr(cw))
     return hmap

@@ -21,8 +21,9 @@ A spin-2 field is a pair (q, u) as map2alm_spin takes it.  No purification, no n
 import numpy as np
 
 from .. import engine
+from .._tensors import is_cuda_tensor, device_index
 from . import sphtfunc
-from .sphtfunc import _is_torch, _map_input
+from .sphtfunc import _map_input
 
 __all__ = ['mode_coupling_matrix', 'mask_spectrum', 'ClBins', 'pseudo_cl', 'PseudoClWorkspace', 'decoupled_cl']
 
@@ -57,12 +58,12 @@ def mode_coupling_matrix(wl, lmax, spin1=0, spin2=0):
     |l - l'| > lw are exactly 0.  A CUDA float64 tensor gives CUDA results."""
     kind = _spins(spin1, spin2)
     lmax = _check_lmax(lmax)
-    on_dev = _is_torch(wl)
+    on_dev = is_cuda_tensor(wl)
     if on_dev:
         import torch
         if wl.dim() != 1 or wl.numel() < 1 or wl.dtype != torch.float64:
             raise ValueError("wl must be a non-empty 1-D float64 array (got dtype %s, shape %s)" % (wl.dtype, tuple(wl.shape)))
-        return engine.pcl_coupling_device(wl[:2 * lmax + 1].contiguous(), lmax, kind, device=wl.device.index or 0)
+        return engine.pcl_coupling_device(wl[:2 * lmax + 1].contiguous(), lmax, kind, device=device_index(wl))
     w = np.asarray(wl)
     if w.ndim != 1 or w.size < 1 or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
         raise ValueError("wl must be a non-empty 1-D real array (got dtype %s, shape %s)" % (w.dtype, w.shape))
@@ -261,7 +262,7 @@ class PseudoClWorkspace(object):
         self._wl = wl if on_dev else torch.from_numpy(wl).to(torch.device('cuda', 0))
         dev = self._wl.device
         self.fsky = float((k1 * (k1 if k2 is None else k2)).mean())
-        mats = engine.pcl_coupling_device(self._wl.contiguous(), self.lmax, self.kind, device=dev.index or 0)
+        mats = engine.pcl_coupling_device(self._wl.contiguous(), self.lmax, self.kind, device=device_index(dev))
         self._mats = mats if self.kind == 2 else (mats,)
         self._B = torch.from_numpy(bins.matrix(self.lmax)).to(dev)                               # [nb, n]
         U = (self._B > 0).to(torch.float64).T.contiguous()                                        # [n, nb]
@@ -287,7 +288,7 @@ class PseudoClWorkspace(object):
     def _in(self, x, name):
         """(float64 [ns, lmax + 1] on the workspace's device, as given: on_device, 1-D)"""
         import torch
-        on_dev = _is_torch(x)
+        on_dev = is_cuda_tensor(x)
         t = x if on_dev else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
         flat = t.dim() == 1
         if flat:

@@ -36,6 +36,7 @@ They are syntheses of scaled alm in the spin convention above: spin 1 of [sqrt(l
 import numpy as np
 
 from .. import engine
+from .._tensors import is_cuda_tensor, device_index
 from .io import npix2nside
 
 __all__ = ['map2alm', 'alm2map', 'alm2cl', 'anafast', 'map2alm_spin', 'alm2map_spin', 'getlmax', 'getidx', 'getsize', 'UNSEEN',
@@ -66,10 +67,6 @@ def getlmax(s, mmax=None):
     return int(x)
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith('torch') and getattr(x, 'is_cuda', False)
-
-
 def _unsupported(**kw):
     for name, (value, default) in kw.items():
         if value is not default and value != default:
@@ -78,7 +75,7 @@ def _unsupported(**kw):
 
 def _map_input(maps, name='maps'):
     """(1-D float64 map, nside, on_device)"""
-    if _is_torch(maps):
+    if is_cuda_tensor(maps):
         import torch
         m = maps
         if m.dim() == 2 and m.shape[0] == 1:
@@ -131,7 +128,7 @@ def map2alm(maps, lmax=None, mmax=None, iter=3, pol=True, use_weights=False, dat
 
 
 def _alm_input(alms, lmax, mmax, name='alms'):
-    if _is_torch(alms):
+    if is_cuda_tensor(alms):
         import torch
         a = alms
         if a.dim() == 2 and a.shape[0] == 1:
@@ -188,7 +185,7 @@ def alm2cl(alms1, alms2=None, lmax=None, mmax=None, lmax_out=None):
     if lmax_out < 0:
         raise ValueError("lmax_out must be >= 0")
     if on_dev:
-        return engine.alm2cl_device(a, b, lmax, mmax, lmax_out, device=a.device.index or 0)
+        return engine.alm2cl_device(a, b, lmax, mmax, lmax_out, device=device_index(a))
     return engine.sht_alm2cl_host(a, b, lmax, mmax, lmax_out)
 
 
@@ -230,7 +227,7 @@ def _spin_check(spin, lmax):
 
 def _pair(x, name):
     """the two members of a map or alm pair: a (2, n) array or tensor, or a sequence of two 1-D ones"""
-    if _is_torch(x) or isinstance(x, np.ndarray):
+    if is_cuda_tensor(x) or isinstance(x, np.ndarray):
         if x.ndim != 2 or x.shape[0] != 2:
             raise ValueError("%s must hold 2 %s (got shape %s)" % (name, 'maps' if name == 'maps' else 'sets of alm', tuple(x.shape)))
         return x[0], x[1]
@@ -242,7 +239,7 @@ def _pair(x, name):
 
 
 def _size(x):
-    return x.numel() if _is_torch(x) else np.asarray(x).size
+    return x.numel() if is_cuda_tensor(x) else np.asarray(x).size
 
 
 def map2alm_spin(maps, spin, lmax=None, mmax=None):
@@ -295,7 +292,7 @@ def _alm2map_der(alm, nside, lmax, mmax, nmaps):
     if nside < 1:
         raise ValueError("nside must be >= 1")
     _shape(nside, lmax, mmax)
-    plan = engine.sht_plan(nside, lmax, mmax, device=(a.device.index or 0) if on_dev else 0)
+    plan = engine.sht_plan(nside, lmax, mmax, device=device_index(a) if on_dev else 0)
     import torch
     out = torch.empty((nmaps, plan.npix), dtype=torch.float64, device=plan.dev)
     return plan.alm2map_der_device(a if on_dev else _to_device(a, plan), out), on_dev
@@ -370,7 +367,7 @@ def _window(lmax, fwhm, sigma, beam_window):
 
 
 def _fl_input(fl):
-    if _is_torch(fl):
+    if is_cuda_tensor(fl):
         if fl.dim() != 1 or fl.dtype.is_complex:
             raise ValueError("fl must be a 1-D real array")
         return fl
@@ -383,7 +380,7 @@ def _fl_input(fl):
 def _fl_device(fl, dev):
     """fl as a float64 tensor on dev with at least one element (an empty fl filters everything to 0)"""
     import torch
-    f = fl if _is_torch(fl) else torch.from_numpy(fl)
+    f = fl if is_cuda_tensor(fl) else torch.from_numpy(fl)
     f = f.to(device=dev, dtype=torch.float64).contiguous()
     return f if f.numel() else torch.zeros(1, dtype=torch.float64, device=dev)
 
@@ -397,11 +394,11 @@ def almxfl(alm, fl, mmax=None, inplace=False):
     if on_dev:
         if inplace and (a is not alm and a.data_ptr() != alm.data_ptr()):
             raise ValueError("inplace=True needs a contiguous 1-D complex128 tensor")
-        out = engine.almxfl_device(a, _fl_device(f, a.device), lmax, mmax, out=a if inplace else None, device=a.device.index or 0)
+        out = engine.almxfl_device(a, _fl_device(f, a.device), lmax, mmax, out=a if inplace else None, device=device_index(a))
         return alm if inplace else out
     if inplace and not (isinstance(alm, np.ndarray) and np.shares_memory(a, alm)):
         raise ValueError("inplace=True needs a C-contiguous 1-D complex128 numpy array")
-    if _is_torch(f):
+    if is_cuda_tensor(f):
         f = f.cpu().numpy().astype(np.float64)
     if f.size == 0:
         f = np.zeros(1)

@@ -62,6 +62,6 @@ for nside in nsides:
     r['legendre_fp64_steps_per_s_map2alm_spin'] = steps / (r['map2alm_spin_dev_ms'] * 1e-3)
     out['nside%d' % nside] = {k: (round(v, 3) if isinstance(v, float) and v < 1e6 else v) for k, v in r.items()}
     del plan, dm, alms, omaps, alm0
-    engine._SHT_PLANS.clear()
+    engine.sphere._SHT_PLANS.clear()
     torch.cuda.empty_cache()
 print(json.dumps(out))

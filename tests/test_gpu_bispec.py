@@ -1,5 +1,5 @@
 """The bispectrum kernels of csrc/bfgx_bispec.hpp and the inverse slab transforms under them, against tests/bispec_oracle.py and numpy.
-Everything goes through the Python entries of engine.py.
+Everything goes through the Python entries of engine/fourier.py.
 
   1. slab inverses (fft_conj_kernel, fft_c2c_strided_kernel<0>, fft_c2r_lines_kernel): noise, one-hot spectra, NaN pad columns, round trips;
      N = 8 .. 1024 on 1 to 3 planes or columns

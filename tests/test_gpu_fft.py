@@ -1,5 +1,5 @@
 """The LDS FFT and P(k) kernels of csrc/bfgx_fft.hpp, one Fourier coefficient at a time, N = 8 .. 1024, against tests/fft_oracle.py
-(plain numpy, long double where it is affordable).  Everything goes through the Python entries of engine.py.
+(plain numpy, long double where it is affordable).  Everything goes through the Python entries of engine/fourier.py.
 
   1. plane passes (fft_r2c_lines_kernel + fft_c2c_strided_kernel<0>): noise, impulses, plane waves, NaN-filled pad columns
   2. axis-0 pass with binning (fft_c2c_strided_kernel<1 | 2>, pk_table_build_kernel, pk_table_sums_kernel) on synthetic spectra,
