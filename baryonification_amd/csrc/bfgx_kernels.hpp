@@ -29,6 +29,15 @@ constexpr double kTwoThird = 2.0 / 3.0;
 constexpr double kDeg2Rad  = kPi / 180.0;
 constexpr double kRad2Deg  = 180.0 / kPi;
 
+// Colatitude of a halo at declination `dec` [deg].  The product is fused into the subtraction, and 90 * kDeg2Rad, unrounded, exceeds the
+// rounded pi / 2 by 3.5e-17: without the clamp a halo at dec = 90 exactly (theta = 0 in the reference's numpy, pi / 2 - radians(90)) would
+// sit outside the sphere and be dropped as invalid.  (dec = -90 rounds to kPi; every other declination is left as it was, dec > 90 stays < 0.)
+__device__ inline double dec_to_theta(double dec)
+{
+    const double t = kHalfPi - dec * kDeg2Rad;
+    return (t < 0.0 && dec <= 90.0) ? 0.0 : t;
+}
+
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kNC = 4;                 // (z, M) corner rows per halo for a 3-axis table
@@ -700,7 +709,7 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     // hp.ang2vec(ra, dec, lonlat=True) (:303) followed by query_disc's pointing(vec) (:306): the pointing of the unit
     // vector (sin t cos p, sin t sin p, cos t) is (t, p mod 2 pi) again, so the two atan2 of the round trip are skipped
     // (they return theta and phi to within an ulp)
-    const double theta = kHalfPi - dec[jin] * kDeg2Rad;
+    const double theta = dec_to_theta(dec[jin]);
     const double phi = ra[jin] * kDeg2Rad;
     double st, ct, sp, cp;
     sincos_bounded(theta, st, ct);                                        // libm-free (bfgx_math.hpp): K0 is latency-bound
@@ -913,8 +922,10 @@ __device__ __forceinline__ void halo_prep_one(const DevModel &m, const Hpx &h, i
     }
 }
 
-// Ring range [first, last] (1-based, inclusive; first > last: nothing) that a halo's disc -- or its 4 fallback pixels -- can touch,
-// widened by 2 rings: what a rank that owns a range of bands needs to know to take the halos that matter to it (spatially
+// Ring range [first, last] (1-based, inclusive; first > last: nothing) that a halo's disc -- or its 4 fallback pixels -- can touch: the rings
+// whose colatitude lies in [theta - radius, theta + radius] (halo_prep_kernel's irmin .. irmax), widened by 2 rings either side (+ margin)
+// and clipped -- first = ring_above(cos lo) - 1 = irmin - 2, last = ring_above(cos hi) + 2 = irmax + 2.  Every touched pixel lies within
+// [irmin - 1, irmax + 1] (the disc's within the band, the fallback's in the two rings around theta), so one ring is spare: what a rank that owns a range of bands needs to know to take the halos that matter to it (spatially
 // sharded multi-GPU runs).  Same arithmetic as halo_prep_kernel for a, R, D_A and the colatitude band of the disc.
 __global__ void __launch_bounds__(256)
 disc_rings_kernel(DevModel m, Hpx h, int64_t nhalo, const double *__restrict__ M, const double *__restrict__ z,
@@ -934,7 +945,7 @@ disc_rings_kernel(DevModel m, Hpx h, int64_t nhalo, const double *__restrict__ M
         D = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
     }
     const double radius = R * m.eps_runner / D;
-    const double theta = kHalfPi - dec[j] * kDeg2Rad;
+    const double theta = dec_to_theta(dec[j]);
     const int nl4 = (int)(4 * h.nside);
     int first = 1, last = 0;
     const bool bad = !(radius > 0.0) || !isfinite(radius) || !(theta >= 0.0) || !(theta <= kPi) || !(M_j > 0.0) || !isfinite(M_j) || !(z_j > -1.0);
@@ -942,9 +953,8 @@ disc_rings_kernel(DevModel m, Hpx h, int64_t nhalo, const double *__restrict__ M
         if (radius >= kPi) { first = 1; last = nl4 - 1; }
         else {
             const double lo = fmax(theta - radius, 0.0), hi = fmin(theta + radius, kPi);
-            first = (int)ring_above(h, cos(lo)) - 1;              // ring_above: last ring with colatitude <= the argument's
-            last = (int)ring_above(h, cos(hi)) + 2;
-            first = max(1, first - 1); last = min(nl4 - 1, last + 1);
+            first = max(1, (int)ring_above(h, cos(lo)) - 1);      // ring_above: last ring with colatitude <= the argument's, i.e. irmin - 1
+            last = min(nl4 - 1, (int)ring_above(h, cos(hi)) + 2);
         }
         // (a rank that also computes the bands next to its own -- the aprons of its regrid -- takes the halos of those too)
         first = max(1, first - margin); last = min(nl4 - 1, last + margin);
@@ -1075,16 +1085,15 @@ route_step_kernel(RouteStepArgs s, DevModel m, Hpx h, int64_t n, int32_t *__rest
             D = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
         }
         const double radius = R * m.eps_runner / D;
-        const double theta = kHalfPi - s.dec[j] * kDeg2Rad;
+        const double theta = dec_to_theta(s.dec[j]);
         first = 1; last = 0;
         const bool bad = !(radius > 0.0) || !isfinite(radius) || !(theta >= 0.0) || !(theta <= kPi) || !(M_j > 0.0) || !isfinite(M_j) || !(z_j > -1.0);
         if (bad) return;
         if (radius >= kPi) { first = 1; last = nl4 - 1; }
         else {
             const double lo = fmax(theta - radius, 0.0), hi = fmin(theta + radius, kPi);
-            first = (int)ring_above(h, cos(lo)) - 1;
-            last = (int)ring_above(h, cos(hi)) + 2;
-            first = max(1, first - 1); last = min(nl4 - 1, last + 1);
+            first = max(1, (int)ring_above(h, cos(lo)) - 1);
+            last = min(nl4 - 1, (int)ring_above(h, cos(hi)) + 2);
         }
         first = max(1, first - s.margin); last = min(nl4 - 1, last + s.margin);
     };

@@ -90,7 +90,7 @@ class ShellPlan(TimedPlan):
         return int(br.value), int(w.value)
 
     def disc_rings(self, cat_dev, rings_ptr):
-        """per halo the ring range [first, last] (1-based, inclusive, 2 rings of margin) its disc can touch -> int32 [n][2]"""
+        """per halo the ring range [first, last] (1-based, inclusive: the disc's colatitude band + 2 rings + the route margin) its disc can touch -> int32 [n][2]"""
         _lib.call('bfgx_disc_rings_device', self._h, cat_dev, rings_ptr)
 
     def set_route_margin(self, rings):

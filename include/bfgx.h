@@ -295,8 +295,12 @@ int  bfgx_plan_regrid_stats(bfgx_plan *p, int64_t *far_listed, int32_t *far_over
  * p0) and adds the number of the others to *foreign_dev (optional device counter the caller inspects later) */
 int  bfgx_plan_far_apply_device(bfgx_plan *p, double *out_slice_dev, int64_t p0, int64_t p1, unsigned long long *foreign_dev);
 /* Spatially sharded multi-GPU runs: a rank that owns the bands [band0, band1) (bfgx_plan_bands) takes every halo whose disc can
- * touch them -- bfgx_disc_rings_device gives, per halo, the ring range [first, last] (1-based, inclusive, widened by 2 rings;
- * first > last: nothing) -- and runs K0 + K1 (or K3) for ITS tiles only: offsets_slice_dev / map_slice_dev point at the first
+ * touch them -- bfgx_disc_rings_device gives, per halo, the ring range [first, last] (1-based, inclusive; first > last: nothing,
+ * always as (1, 0)): the rings whose colatitude lies within the disc's colatitude band theta -+ radius (query_disc's irmin .. irmax),
+ * widened by 2 rings either side and by the route margin, clipped to [1, 4 nside - 1]; a band that holds no ring (a disc between two
+ * rings: the 4-pixel fallback) gives the 2 rings either side of the gap.  Every touched pixel lies within 1 ring of the band; the first
+ * or last ring of the band may hold no pixel centre inside the disc, so the range exceeds the rings of the touched PIXELS by at most 3
+ * (tests/test_gpu_route_step.py) -- and runs K0 + K1 (or K3) for ITS tiles only: offsets_slice_dev / map_slice_dev point at the first
  * pixel of band0 ([p1 - p0][3] resp. [p1 - p0] elements, every one stored exactly once); halos that reach into other bands are
  * clipped.  No accumulator travels between the ranks; the regrid then needs the neighbours' apron rings as above. */
 int  bfgx_plan_tile_shape(bfgx_plan *p, int32_t *rings_per_band, int32_t *max_columns);     /* band b = rings [1 + b R, 1 + (b + 1) R) */
